@@ -7,7 +7,9 @@ A "step" is one whole frame: zero the accumulator, integrate every sample of eve
 owned pixel (one HIP launch per rank), assemble the frame over ranks (N>1), resolve on
 rank 0.  Metric: Mrays/s = (closest-hit + shadow rays actually cast) / wall time, whole job.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+--dump-outputs DIR writes the last timed step's frame as DIR/image.npy (resolved RGB) and
+DIR/accum.npy (the accumulator), float32; see dump_outputs() for frames above 64 MB.
 With N>1 and no WORLD_SIZE in the environment the script starts its own
 `torch.distributed.run` (one rank per GPU, RCCL) as a child process, before anything
 touches the GPU.  The frame is tile-sharded over ranks, i.e. total work is fixed:
@@ -39,9 +41,9 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, "ray-tracing-engine_amd"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-HBM_PEAK_GBS = 8000.0     # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+HBM_PEAK_GBS = 8000.0     # MI355X: HBM3E 8.0 TB/s spec
 SIMDS = 256 * 4           # 256 CUs x 4 SIMD-32
-CLOCK_GHZ = 2.4           # max shader clock (same guide)
+CLOCK_GHZ = 2.4           # max shader clock (same spec)
 VALU_PEAK_GINSTR = SIMDS * CLOCK_GHZ / 2.0  # one wave64 VALU op per 2 cycles per SIMD -> 1228.8 G wave-instr/s
 
 WORKLOADS = {
@@ -297,6 +299,29 @@ def build_params(ctx, pyrt, args, w, h, spp, mode, nph, k, rank, world):
                             wavefront=args.integrator == "wavefront")
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6
+DUMP_SAMPLE_SEED = 1
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each (h, w, c) array as <path>/<name>.npy, float32.  When they come to more than 64 MB in all
+    (C4's 2048x2048 frame), every array keeps the same fixed, seeded sample of pixels, (n, c) in ascending pixel order,
+    and pixel_index.npy (float64) holds their flat indices y * w + x."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    h, w = next(iter(arrays.values())).shape[:2]
+    npix = h * w
+    headers = 256 * (len(arrays) + 1)
+    if sum(a.nbytes for a in arrays.values()) + headers > DUMP_LIMIT_BYTES:
+        per_pixel = sum(a.nbytes for a in arrays.values()) // npix + 8  # (+ the float64 index)
+        n = (DUMP_LIMIT_BYTES - headers) // per_pixel
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(npix, n, replace=False))
+        arrays = {k: a.reshape(npix, -1)[idx] for k, a in arrays.items()}
+        arrays["pixel_index"] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
 def second_build_ms(pyrt, scene, local, args):
     """rt_create's build time once the process is warm (rank 0, after the timed region)."""
     c2 = pyrt.Context(scene, device=local, bvh_leaf_max=args.leaf)
@@ -330,7 +355,11 @@ def main():
                          "at 128x128x1 (deterministic: a probe count, not a time limit); 0 = off (the default)")
     ap.add_argument("--integrator", default="fused", choices=["fused", "wavefront"],
                     help="wavefront = the opt-in queue-based integrator (same image; DESIGN.md section 8)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's frame (image.npy, accum.npy; float32, at most 64 MB) to DIR")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.pmc_child:
         return pmc_child(args)
@@ -438,6 +467,9 @@ def main():
     elapsed = time.perf_counter() - t0
     elapsed = rdist.max_over_ranks(elapsed, dev)
     kernel_ms, launches = ctx.profile_collect()
+    if args.dump_outputs and rank == 0:
+        # (after the timed region: what the last timed step left in the assembled accumulator and the resolved image)
+        dump_outputs(args.dump_outputs, {"image": out.cpu().numpy(), "accum": accum.cpu().numpy()})
     avg_ms = kernel_ms / max(launches, 1)
     secs = avg_ms * 1e-3
     # per-rank kernel time (slowest / fastest rank: the load balance of the tile sharding) and the

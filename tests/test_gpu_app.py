@@ -86,13 +86,18 @@ def test_bench_two_ranks_rehearsal_on_one_gpu(tmp_path):
     env = dict(os.environ, RT_DIST_BACKEND="gloo", RT_SHARE_GPU="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29711", os.path.join(pyrt.ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
-           "--workload", "C1"]
+           "--workload", "C1", "--dump-outputs", str(tmp_path / "two")]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900, cwd=tmp_path)
     assert r.returncode == 0, r.stderr[-3000:]
     two = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     r1 = subprocess.run([sys.executable, os.path.join(pyrt.ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--workload", "C1",
-                         "--no-cpu-baseline"], capture_output=True, text=True, timeout=300, cwd=tmp_path)
+                         "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "one")], capture_output=True, text=True, timeout=300,
+                        cwd=tmp_path)
     one = json.loads([l for l in r1.stdout.splitlines() if l.startswith("{")][-1])
+    # the frame rank 0 assembled from both ranks' tiles is the one-rank frame, bit for bit
+    for name in ("image", "accum"):
+        a, b = np.load(tmp_path / "two" / (name + ".npy")), np.load(tmp_path / "one" / (name + ".npy"))
+        assert a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32)), name
     assert two["n_gpus"] == 2 and two["scaling"] == "strong"
     assert two["cpu_baseline"]["value"] > 0  # (rank 0 times the CPU beside it at every N)
     assert two["config"]["rays_per_frame"] == one["config"]["rays_per_frame"] == 5526901
@@ -101,6 +106,29 @@ def test_bench_two_ranks_rehearsal_on_one_gpu(tmp_path):
     assert one["roofline"]["bound"] == "valu_issue" and one["roofline"]["hbm"]["bound"] == "hbm"
     if one["roofline"]["frac"] is not None:  # (None only when rocprofv3 is unavailable)
         assert 0 < one["roofline"]["frac"] <= 1 and 0 < one["roofline"]["hbm"]["frac"] <= 1
+
+
+def test_bench_dump_outputs_is_the_timed_frame(tmp_path):
+    """--dump-outputs writes the frame of the last timed step, resolved image and accumulator, and it is the CPU
+    oracle's frame for the same scene, size, samples and seed, bit for bit; --steps sets the timed steps."""
+    import json
+    import sys
+    d = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(pyrt.ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--workload", "C1",
+                        "--spp", "2", "--no-pmc", "--no-cpu-baseline", "--dump-outputs", str(d)],
+                       capture_output=True, text=True, timeout=300, cwd=tmp_path)
+    assert r.returncode == 0, r.stderr[-3000:]
+    res = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert res["steps"] == 3 and res["ms_per_step"] > 0
+    assert res["roofline"]["launches"] == 3  # (one integrate launch per timed step, one rank)
+    assert sorted(os.listdir(d)) == ["accum.npy", "image.npy"]
+    img, acc = np.load(d / "image.npy"), np.load(d / "accum.npy")
+    assert img.dtype == acc.dtype == np.float32 and img.shape == (256, 256, 3) and acc.shape == (256, 256, 4)
+    s = pyrt.Scene("cubes", 256, 256)
+    p = pyrt.make_params(256, 256, 2, mode=pyrt.MODE_PATH, seed=1)
+    ref_out, ref_acc, _ = orc.render(s, p, math_mode=orc.MATH_DET, bg=pyrt.background(256, 256))
+    assert np.array_equal(acc.view(np.uint32), ref_acc.view(np.uint32))
+    assert np.array_equal(img.view(np.uint32), ref_out.view(np.uint32))
 
 
 def test_bench_spawns_its_own_launcher(tmp_path):
