@@ -274,6 +274,12 @@ int rt_trace(rt_ctx* ctx, const rt_ray* rays, uint32_t n, uint32_t accel,
  * (camera, surface points); the host cannot check device-resident rays. */
 int rt_trace_stream_device(rt_ctx* ctx, const void* d_ray_o, const void* d_ray_d, uint32_t n,
                            void* d_res, void* stream);
+/* kdtree::knearest for n queries over the context's photon map (rt_set_photons order):
+ * slots of the map in the reference's result order, their float distances, nodes visited.
+ * This is the walk photon frames run, on their layout: the same entry width (16-bit stack
+ * entries below 65,535 photons) and the same stack rows as a frame whose BVH is shallower
+ * than the kd tree (the tightest layout), with the k-slot heap directly above the stack.
+ * k in 1..16 (else RT_ERR_UNSUPPORTED); an empty map or k > photons: RT_ERR_STATE. */
 int rt_knn(rt_ctx* ctx, const float* query3, uint32_t n, uint32_t k,
            uint32_t* idx_out /*[n][k]*/, float* dist_out /*[n][k]*/,
            uint32_t* visited_out /*[n] or NULL*/);

@@ -15,6 +15,7 @@
 // Sub-commands
 //   render  <meshdir> <scene> <w> <h> <mode> <N> <p> <k> <out.ppm>
 //   vectors <meshdir> <out.json>
+//   knn     <out.json>                                        (tie-heavy k-NN maps)
 //   time    <meshdir> <scene> <w> <h> <mode> <N> <p> <k>     (prints seconds)
 #define _USE_MATH_DEFINES
 #include <assert.h>
@@ -522,10 +523,196 @@ int cmdRender(int argc, char** argv, bool timeOnly) {
   return 0;
 }
 
+// ---------------------------------------------------------------- k-NN tie maps
+// Photon maps on a grid of spacing 1/8 (exact in float), built so that equal
+// coordinates and equal distances are the rule: a lattice, repeated positions,
+// axis-aligned walls, a line, one point, tiny maps, and the lattice scaled by powers
+// of two whose squares underflow, go subnormal, approach FLT_MAX or overflow.
+// Photon i of a map has direction (i / 2, 1, n - i): unique, so a result identifies
+// its photon even where positions repeat.
+struct KnnMap {
+  std::string name;
+  int scaleExp;
+  std::vector<Vec3f> pos;
+};
+
+std::vector<KnnMap> knnMaps(Lcg& g) {
+  const float s = 0.125f;
+  auto shuffle = [&](std::vector<Vec3f>& v) {
+    for (size_t i = v.size(); i > 1; i--) std::swap(v[i - 1], v[g.next() % i]);
+  };
+  auto lattice = [&](int a) {
+    std::vector<Vec3f> v;
+    for (int x = 0; x < a; x++)
+      for (int y = 0; y < a; y++)
+        for (int z = 0; z < a; z++) v.push_back(Vec3f(x * s, y * s, z * s));
+    shuffle(v);
+    return v;
+  };
+  auto grid = [&](int lo, int hi) { return (float)((int)(g.next() % (uint32_t)(hi - lo + 1)) + lo) * s; };
+  // (one draw per statement: the order of a constructor's arguments is unspecified)
+  auto grid3 = [&](int lo0, int hi0, int lo1, int hi1, int lo2, int hi2) {
+    Vec3f p;
+    p[0] = grid(lo0, hi0);
+    p[1] = grid(lo1, hi1);
+    p[2] = grid(lo2, hi2);
+    return p;
+  };
+  std::vector<KnnMap> m;
+  m.push_back({"lattice", 0, lattice(10)});
+  {
+    std::vector<Vec3f> v;
+    for (const Vec3f& p : lattice(7))
+      for (int r = 0, reps = 2 + (int)(g.next() % 2); r < reps; r++) v.push_back(p);
+    shuffle(v);
+    m.push_back({"duplicates", 0, v});
+  }
+  {
+    std::vector<Vec3f> v;
+    for (int i = 0; i < 600; i++) {
+      Vec3f p = grid3(-12, 12, -8, 12, -12, 12);
+      switch (g.next() % 5) {
+        case 0: p[1] = -1.f; break;
+        case 1: p[0] = -1.5f; break;
+        case 2: p[0] = 1.5f; break;
+        case 3: p[2] = -1.5f; break;
+        default: break;
+      }
+      v.push_back(p);
+    }
+    m.push_back({"walls", 0, v});
+  }
+  {
+    std::vector<Vec3f> v;
+    for (int i = 0; i < 300; i++) v.push_back(Vec3f(0.25f, grid(-20, 19), -0.5f));
+    m.push_back({"line", 0, v});
+  }
+  m.push_back({"point", 0, std::vector<Vec3f>(100, Vec3f(0.375f, -0.25f, 0.5f))});
+  for (int n = 1; n <= 5; n++) {
+    std::vector<Vec3f> v;
+    for (int i = 0; i < n; i++) v.push_back(grid3(-2, 2, -2, 2, -2, 2));
+    m.push_back({"tiny" + std::to_string(n), 0, v});
+  }
+  for (int e : {-80, -70, 62, 64}) m.push_back({"lattice_2^" + std::to_string(e), e, lattice(6)});
+  return m;
+}
+
+// Queries on the map's own grid (before scaling): photon positions, cell centres, face
+// centres and edge midpoints (exact equal-distance ties), points on a photon's split
+// coordinate, random points, and points 10^3 x the map's extent away.
+std::vector<Vec3f> knnQueries(Lcg& g, const std::vector<Vec3f>& pos) {
+  const float h = 0.0625f;
+  Vec3f lo = pos[0], hi = pos[0];
+  for (const Vec3f& p : pos)
+    for (int a = 0; a < 3; a++) lo[a] = std::min(lo[a], p[a]), hi[a] = std::max(hi[a], p[a]);
+  float ext = std::max(std::max(hi[0] - lo[0], hi[1] - lo[1]), std::max(hi[2] - lo[2], 0.125f));
+  auto any = [&]() { return pos[g.next() % pos.size()]; };
+  auto sgn = [&]() { return g.next() % 2 ? h : -h; };
+  auto sgn3 = [&]() {
+    Vec3f d;
+    for (int a = 0; a < 3; a++) d[a] = sgn();
+    return d;
+  };
+  auto inBox = [&]() {
+    Vec3f p;
+    for (int a = 0; a < 3; a++) p[a] = g.uni(lo[a] - 0.125f, hi[a] + 0.125f);
+    return p;
+  };
+  std::vector<Vec3f> q;
+  for (int i = 0; i < 8; i++) q.push_back(any());
+  for (int i = 0; i < 8; i++) {
+    const Vec3f p = any();
+    q.push_back(p + sgn3());
+  }
+  for (int i = 0; i < 8; i++) {
+    Vec3f p = any();
+    const int a = (int)(g.next() % 3);
+    p[a] += sgn();
+    if (i % 2) p[(a + 1) % 3] += sgn();
+    q.push_back(p);
+  }
+  for (int i = 0; i < 6; i++) {
+    Vec3f p = inBox();
+    const uint32_t a = g.next() % 3;
+    p[a] = any()[a];
+    q.push_back(p);
+  }
+  for (int i = 0; i < 6; i++) q.push_back(inBox());
+  const Vec3f c = (lo + hi) * 0.5f;
+  for (const Vec3f& d : {Vec3f(-1.f, -1.f, -1.f), Vec3f(1.f, 1.f, 1.f), Vec3f(-1.f, 1.f, -1.f), Vec3f(1.f, -1.f, 0.5f)})
+    q.push_back(c + d * (1000.f * ext));
+  return q;
+}
+
+// knn <out.json>: the maps, the reference's kdtree order of each, and kdtree::knearest
+// for every query and every k in 1..min(16, n): m_visited and the results as slots of
+// the tree order (found by exact position + direction).
+int cmdKnn(const std::string& out) {
+  Lcg g(8128);
+  std::ostringstream o;
+  o << "{\"maps\":[\n";
+  bool firstMap = true;
+  for (KnnMap& m : knnMaps(g)) {
+    const size_t n = m.pos.size();
+    std::vector<Vec3f> qs = knnQueries(g, m.pos);
+    for (std::vector<Vec3f>* v : {&m.pos, &qs})
+      for (Vec3f& p : *v)
+        for (int a = 0; a < 3; a++) p[a] = std::ldexp(p[a], m.scaleExp);  // exact: a power of two
+    std::vector<Particle> list;
+    for (size_t i = 0; i < n; i++) list.push_back(Particle(m.pos[i], Vec3f(0.5f * i, 1.f, float(n - i)), 1.f));
+    kdtree tree(list.begin(), list.end());
+    std::unordered_map<uint32_t, uint32_t> slotOf;  // direction x bits -> tree slot
+    std::vector<uint32_t> given, order, qv, res;
+    for (const Particle& p : list) push3(given, p.position()), push3(given, p.incomeDirection());
+    for (size_t i = 0; i < n; i++) {
+      const Particle& p = tree.m_nodes[i].m_point;
+      push3(order, p.position());
+      push3(order, p.incomeDirection());
+      slotOf[fbits(p.incomeDirection()[0])] = (uint32_t)i;
+    }
+    for (size_t qi = 0; qi < qs.size(); qi++) {
+      push3(qv, qs[qi]);
+      Particle t;
+      t.position() = qs[qi];
+      for (int k = 1; k <= (int)std::min<size_t>(16, n); k++) {
+        std::vector<Particle> r;
+        tree.knearest(t, k, r);
+        res.push_back((uint32_t)qi);
+        res.push_back((uint32_t)k);
+        res.push_back((uint32_t)tree.m_visited);
+        for (const Particle& p : r) {
+          const uint32_t slot = slotOf.at(fbits(p.incomeDirection()[0]));
+          const Particle& s = tree.m_nodes[slot].m_point;
+          if (fbits(s.position()[0]) != fbits(p.position()[0]) || fbits(s.position()[1]) != fbits(p.position()[1]) ||
+              fbits(s.position()[2]) != fbits(p.position()[2]))
+            throw std::runtime_error("knn result not found in the tree order");
+          res.push_back(slot);
+        }
+      }
+    }
+    J j;
+    j.o << (firstMap ? "{" : ",\n{");
+    firstMap = false;
+    j.key("name");
+    j.o << "\"" << m.name << "\"";
+    j.i64("scale_exp", {m.scaleExp});
+    j.u32("given", given);
+    j.u32("tree", order);
+    j.u32("queries", qv);
+    j.u32("knn", res);
+    o << j.o.str() << "}";
+  }
+  o << "\n]}\n";
+  std::ofstream f(out);
+  f << o.str();
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
   if (argc >= 4 && !strcmp(argv[1], "vectors")) return cmdVectors(argv[2], argv[3]);
+  if (argc >= 3 && !strcmp(argv[1], "knn")) return cmdKnn(argv[2]);
   if (argc >= 11 && !strcmp(argv[1], "render")) return cmdRender(argc, argv, false);
   if (argc >= 10 && !strcmp(argv[1], "time")) return cmdRender(argc, argv, true);
   fprintf(stderr, "usage: see header of oracle/ref_harness.cpp\n");

@@ -865,7 +865,10 @@ int orc_knn(const float* photons7_kd, uint32_t n, const float* query3, uint32_t 
   t.nodes.resize(n);
   memcpy(t.nodes.data(), photons7_kd, sizeof(Photon) * (size_t)n);
   int bad = 0;
-#pragma omp parallel for schedule(static)
+  // a team sized by the work (one thread per 64 queries): the test sweeps make thousands of small calls, and a
+  // full team per call costs more than the queries wherever the visible cores outnumber the CPU time granted
+  const int64_t team = std::max<int64_t>(1, std::min<int64_t>(omp_get_max_threads(), ((int64_t)nq + 63) / 64));
+#pragma omp parallel for schedule(static) num_threads(team)
   for (int64_t i = 0; i < (int64_t)nq; i++) {
     std::vector<KdTree::HE> res;
     size_t vis = 0;

@@ -294,6 +294,26 @@ int read_counters(rt_ctx* c, rt_stats* st) {
   return RT_OK;
 }
 
+// The photon k-NN walk's LDS stack (rt_kernels.hip knn_query) over a map of n photons: its entry width and the
+// rows it needs.  The walk's stack holds a sentinel + at most one pending far child per tree level + the entry written
+// ahead of the top; 16-bit entries (two per row) when every photon index fits below the 16-bit sentinel 0xffff.
+// Photon frames and rt_knn both size the walk by this rule.
+struct KdStack {
+  bool kd16;
+  uint32_t rows;
+};
+KdStack kd_stack(uint32_t n_photons) {
+  uint32_t kd = 1;  // levels of the median tree over n_photons
+  while ((1ull << kd) <= n_photons) ++kd;
+  const bool kd16 = n_photons < 65535u;
+  return {kd16, kd16 ? (kd + 2u + 1u) / 2u : kd + 1u};
+}
+// A lane's stack rows for a walk that needs `levels` of them (+1: row 0 of a lane's stack is the TERM sentinel,
+// rt_kernels.hip Trav)
+uint32_t stack_levels(uint32_t levels) {
+  return (levels > (uint32_t)rtbvh::kMaxDepth ? (uint32_t)rtbvh::kMaxDepth : levels) + 1u;
+}
+
 // Launch the integrate kernel for p on `stream`, bracketed by an event pair.
 int launch_frame(rt_ctx* c, const rt_params* p, float4* dAccum, hipStream_t stream, int* evIndex) {
   const uint32_t sppCount = p->spp_count ? p->spp_count : p->spp;
@@ -318,16 +338,11 @@ int launch_frame(rt_ctx* c, const rt_params* p, float4* dAccum, hipStream_t stre
   uint32_t levels = c->bvh.maxDepth > 1 ? c->bvh.maxDepth : 1;
   A.kd16 = 0;
   if (p->use_photons) {
-    uint32_t kd = 1;
-    while ((1ull << kd) <= c->S.n_photons) ++kd;
-    // the walk's stack: a sentinel + at most one pending far child per tree level + the row written ahead of the top;
-    // 16-bit entries (two per word) when every photon index fits
-    A.kd16 = c->S.n_photons < 65535u ? 1u : 0u;
-    const uint32_t kdRows = A.kd16 ? (kd + 2u + 1u) / 2u : kd + 1u;
-    levels = levels > kdRows ? levels : kdRows;
+    const KdStack ks = kd_stack(c->S.n_photons);
+    A.kd16 = ks.kd16 ? 1u : 0u;
+    levels = levels > ks.rows ? levels : ks.rows;
   }
-  // (+1: row 0 of a lane's stack is the TERM sentinel, rt_kernels.hip Trav)
-  A.stackLevels = (levels > (uint32_t)rtbvh::kMaxDepth ? (uint32_t)rtbvh::kMaxDepth : levels) + 1u;
+  A.stackLevels = stack_levels(levels);
   A.tileCounter = c->dTileCounter, A.numCUs = c->numCUs, A.waveWords = 0, A.tilesPerBlock = 1;
   const int e = c->evUsed % kEventPairs;
   // rt_params.reserved[2] bit 0: the queue-based (wavefront) integrator — BVH direct lighting with
@@ -971,7 +986,9 @@ int rt_knn(rt_ctx* c, const float* q3, uint32_t n, uint32_t k, uint32_t* idx, fl
   hipError_t he = hipMalloc(reinterpret_cast<void**>(&dI), (size_t)n * k * sizeof(uint32_t));
   if (he == hipSuccess) he = hipMalloc(reinterpret_cast<void**>(&dD), (size_t)n * k * sizeof(float));
   if (he == hipSuccess) he = hipMalloc(reinterpret_cast<void**>(&dV), (size_t)n * sizeof(uint32_t));
-  if (he == hipSuccess) he = rtk::launch_knn(c->S, dQ, n, k, dI, dD, dV, nullptr);
+  // the walk a photon frame runs, on the frame's layout when the BVH is shallower than the kd tree (the tightest one)
+  const KdStack ks = kd_stack(c->S.n_photons);
+  if (he == hipSuccess) he = rtk::launch_knn(c->S, dQ, n, k, ks.kd16, stack_levels(ks.rows), dI, dD, dV, nullptr);
   if (he == hipSuccess) he = hipMemcpy(idx, dI, (size_t)n * k * sizeof(uint32_t), hipMemcpyDeviceToHost);
   if (he == hipSuccess) he = hipMemcpy(dist, dD, (size_t)n * k * sizeof(float), hipMemcpyDeviceToHost);
   if (he == hipSuccess && visited) he = hipMemcpy(visited, dV, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost);

@@ -108,8 +108,9 @@ hipError_t launch_pack(bool unpack, const float4* src, float4* dst, const uint32
                        uint32_t height, hipStream_t stream);
 hipError_t launch_trace(bool brute_force, bool any, const DevScene& S, const rt_ray* rays, uint32_t n,
                         rt_hit* hits, unsigned long long* counters, hipStream_t stream);
-hipError_t launch_knn(const DevScene& S, const float* q, uint32_t n, uint32_t k, uint32_t* idx, float* dist,
-                      uint32_t* visited, hipStream_t stream);
+// the photon frames' k-NN walk (knn_query<kd16>) on their layout: stackLevels rows of LDS stack, the k-slot heap above
+hipError_t launch_knn(const DevScene& S, const float* q, uint32_t n, uint32_t k, bool kd16, uint32_t stackLevels,
+                      uint32_t* idx, float* dist, uint32_t* visited, hipStream_t stream);
 hipError_t launch_emit(const DevScene& S, uint32_t perLight, uint32_t seed, float4* outPos, float4* outDir,
                        unsigned long long* counters, hipStream_t stream);
 // scene BVH on the device (bvh_gpu.hip): arrays are hipMalloc'ed by the builder, owned by the caller

@@ -1476,15 +1476,17 @@ __global__ __launch_bounds__(BLOCK) void k_trace(DevScene S, const rt_ray* __res
   flush_stats(st, counters, true);
 }
 
+// The photon frames' walk on their tightest layout (k_render with a BVH shallower than the kd tree): S16 and
+// stackLevels as launch_frame gives them (rt_api.cpp kd_stack), the k-slot heap directly above the stack rows.
+template <bool S16>
 __global__ __launch_bounds__(BLOCK) void k_knn(DevScene S, const float* __restrict__ q, uint32_t n, uint32_t k,
-                                               uint32_t* __restrict__ idx, float* __restrict__ dst,
+                                               uint32_t stackLevels, uint32_t* __restrict__ idx, float* __restrict__ dst,
                                                uint32_t* __restrict__ visited) {
-  __shared__ uint32_t lds[(STACK + 2 * KMAX) * BLOCK];
-  const Lds L = carve_lds<true>(lds);
+  const Lds L = carve_lds<true>(g_lds, stackLevels, k);
   const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
   if (i >= n) return;
   const Heap H{L.heap};
-  const uint32_t vis = knn_query<false>(S, ld(q + 3 * (size_t)i), (int)k, H, L.stack);
+  const uint32_t vis = knn_query<S16>(S, ld(q + 3 * (size_t)i), (int)k, H, L.stack);
   for (uint32_t j = 0; j < k; j++) {
     idx[(size_t)i * k + j] = H.I((int)j);
     dst[(size_t)i * k + j] = H.D((int)j);
@@ -1886,10 +1888,17 @@ hipError_t launch_trace(bool brute_force, bool any, const DevScene& S, const rt_
   return hipGetLastError();
 }
 
-hipError_t launch_knn(const DevScene& S, const float* q, uint32_t n, uint32_t k, uint32_t* idx, float* dist,
-                      uint32_t* visited, hipStream_t stream) {
+hipError_t launch_knn(const DevScene& S, const float* q, uint32_t n, uint32_t k, bool kd16, uint32_t stackLevels,
+                      uint32_t* idx, float* dist, uint32_t* visited, hipStream_t stream) {
   if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_knn, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, stream, S, q, n, k, idx, dist, visited);
+  if (k < 1 || k > (uint32_t)KMAX || stackLevels < 2 || stackLevels > (uint32_t)STACK + 1) return hipErrorInvalidValue;
+  const size_t ldsBytes = 4u * (size_t)(stackLevels + 2 * k) * BLOCK;
+  if (kd16)
+    hipLaunchKernelGGL(k_knn<true>, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), ldsBytes, stream, S, q, n, k, stackLevels,
+                       idx, dist, visited);
+  else
+    hipLaunchKernelGGL(k_knn<false>, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), ldsBytes, stream, S, q, n, k, stackLevels,
+                       idx, dist, visited);
   return hipGetLastError();
 }
 

@@ -8,6 +8,7 @@ oracle/ref_harness.cpp) and stores their OUTPUTS as data:
   tests/golden/ppm/*.ppm       small whole-image P3 outputs (legacy RNG, seed 1)
   tests/golden/manifest.json   command line -> md5 for every image (incl. big ones)
   tests/golden/ref_vectors.json  per-function input/output bit patterns
+  tests/golden/ref_knn_ties.npz   kdtree order + knearest on tie-heavy and scaled photon maps
 
 Nothing from /root/reference is copied except the .off meshes, which are data
 (tests/golden/meshes).  Usage:  python tests/golden/make_golden.py [--slow]
@@ -42,6 +43,28 @@ CASES = [
 
 def md5(path):
     return hashlib.md5(open(path, "rb").read()).hexdigest()
+
+
+def knn_ties_npz(src, out):
+    """The harness' `knn` JSON as a compact binary fixture (tests/knn_ties.py reads it): per map i,
+    m<i>_given [n][6] position + direction bits as given, m<i>_perm [n] the reference's tree order as
+    indices into given (found by the unique direction), m<i>_queries [nq][3] bits, m<i>_knn the
+    records {query, k, m_visited, k tree slots} back to back."""
+    import numpy as np
+    maps = json.load(open(src))["maps"]
+    arrs = dict(names=np.array([m["name"] for m in maps]), scale_exp=np.array([m["scale_exp"][0] for m in maps], np.int32))
+    for i, m in enumerate(maps):
+        given = np.array(m["given"], np.uint32).reshape(-1, 6)
+        tree = np.array(m["tree"], np.uint32).reshape(-1, 6)
+        slot_of = {d: j for j, d in enumerate(given[:, 3])}
+        perm = np.array([slot_of[d] for d in tree[:, 3]], np.uint32)
+        assert len(given) < 65536 and np.array_equal(given[perm], tree)
+        rec = np.array(m["knn"], np.uint32)
+        assert rec.max() < 65536
+        arrs["m%d_given" % i], arrs["m%d_perm" % i] = given, perm.astype(np.uint16)
+        arrs["m%d_queries" % i] = np.array(m["queries"], np.uint32).reshape(-1, 3)
+        arrs["m%d_knn" % i] = rec.astype(np.uint16)
+    np.savez_compressed(out, **arrs)
 
 
 def main():
@@ -83,6 +106,11 @@ def main():
         subprocess.run([os.path.join(REF, "ref_harness"), "vectors", MESHES, vec], cwd=cwd, check=True,
                        capture_output=True)
         print("vectors", os.path.getsize(vec), "bytes")
+        ties = os.path.join(tmp, "knn.json")
+        subprocess.run([os.path.join(REF, "ref_harness"), "knn", ties], cwd=cwd, check=True, capture_output=True)
+        out = os.path.join(HERE, "ref_knn_ties.npz")
+        knn_ties_npz(ties, out)
+        print("knn ties", os.path.getsize(out), "bytes")
     json.dump(manifest, open(man_path, "w"), indent=1, sort_keys=True)
 
 

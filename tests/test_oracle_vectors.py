@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import knn_ties
 import orc
 import pyrt
 
@@ -164,3 +165,26 @@ def test_photon_emission_and_kdtree(golden):
         idx, dist, vis = orc.knn(kd, pos[None, :], k)
         assert vis[0] == visited
         assert np.array_equal(kd[idx[0], :6].view(np.uint32), res)
+
+
+def test_kdtree_and_knearest_on_ties():
+    """The reference's kdtree on maps where ties are the rule (lattice, repeated positions,
+    walls, a line, one point, tiny maps, the lattice at 2^-80 .. 2^64): the oracle and the
+    product's host builder reproduce its tree order, and the oracle every knearest result
+    and m_visited — every k in 1..min(16, n), queries on photons, cell / face centres,
+    edge midpoints, split planes, random and far away."""
+    maps = knn_ties.load()
+    assert len(maps) == 14
+    for m in maps:
+        given, tree = m["given"], m["tree"]
+        n = len(given)
+        kd = orc.kd_build(np.concatenate([given, np.ones((n, 1), np.float32)], 1))
+        assert np.array_equal(u32(kd[:, :6]), u32(tree)), m["name"]
+        hp, hd, _ = pyrt.kd_order(given[:, 0:3], given[:, 3:6])
+        assert np.array_equal(u32(hp), u32(tree[:, 0:3])) and np.array_equal(u32(hd), u32(tree[:, 3:6])), m["name"]
+        assert sorted(m["by_k"]) == list(range(1, min(16, n) + 1))
+        for k, (qi, visited, slots) in m["by_k"].items():
+            assert np.array_equal(qi, np.arange(len(m["queries"])))
+            idx, _, vis = orc.knn(kd, m["queries"], k)
+            assert np.array_equal(idx, slots), (m["name"], k, int((idx != slots).any(1).sum()))
+            assert np.array_equal(vis, visited), (m["name"], k)
