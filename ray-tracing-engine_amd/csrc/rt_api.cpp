@@ -19,6 +19,7 @@
 #include <cstring>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "bvh_build.h"
@@ -61,12 +62,49 @@ int select_device(int device) {
   return RT_OK;
 }
 
+// Owners of device memory, events and streams.  Where a failed hipFree must be reported, the caller
+// releases the owner and checks: HIP_TRY(hipFree(p.release())).
+struct HipFree {
+  void operator()(void* p) const { (void)hipFree(p); }
+};
 template <class T>
-int upload(T** dptr, const void* src, size_t count) {
-  *dptr = nullptr;
+using DevBuf = std::unique_ptr<T, HipFree>;
+struct EventDestroy {
+  void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); }
+};
+using Event = std::unique_ptr<std::remove_pointer_t<hipEvent_t>, EventDestroy>;
+struct StreamDestroy {
+  void operator()(hipStream_t s) const { (void)hipStreamDestroy(s); }
+};
+using Stream = std::unique_ptr<std::remove_pointer_t<hipStream_t>, StreamDestroy>;
+
+template <class T>
+hipError_t dev_alloc(DevBuf<T>* out, size_t count) {
+  void* p = nullptr;
+  const hipError_t e = hipMalloc(&p, count * sizeof(T));
+  out->reset(e == hipSuccess ? static_cast<T*>(p) : nullptr);
+  return e;
+}
+hipError_t make_event(Event* out, unsigned flags = hipEventDefault) {
+  hipEvent_t e = nullptr;
+  const hipError_t r = hipEventCreateWithFlags(&e, flags);
+  out->reset(r == hipSuccess ? e : nullptr);
+  return r;
+}
+hipError_t make_stream(Stream* out) {
+  hipStream_t s = nullptr;
+  const hipError_t r = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+  out->reset(r == hipSuccess ? s : nullptr);
+  return r;
+}
+
+// A device copy of count elements of src (none when count is 0)
+template <class T>
+int upload(DevBuf<T>* out, const void* src, size_t count) {
+  out->reset();
   if (count == 0) return RT_OK;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(dptr), count * sizeof(T)));
-  HIP_TRY(hipMemcpy(*dptr, src, count * sizeof(T), hipMemcpyHostToDevice));
+  HIP_TRY(dev_alloc(out, count));
+  HIP_TRY(hipMemcpy(out->get(), src, count * sizeof(T), hipMemcpyHostToDevice));
   return RT_OK;
 }
 
@@ -88,53 +126,69 @@ constexpr int kEventPairs = 256;
 
 }  // namespace
 
+// Releasing a context frees everything it owns on the current device: rt_destroy selects the context's first.
 struct rt_ctx {
   int device = 0;
-  rtk::DevScene S{};
+  rtk::DevScene S{};  // the kernels' argument: views of the buffers below
   rtbvh::Built bvh;  // host copy kept for rt_bvh_export
-  std::vector<void*> allocs;
-  float4* phPos = nullptr;
-  float4* phDir = nullptr;
-  uint4* phTopo = nullptr;  // explicit kd topology over phPos (rtk::launch_kd_topology)
-  uint32_t* dTiles = nullptr;
+  // the scene's arrays (S's fields of the same names)
+  DevBuf<uint4> triShade, nodes, q8;
+  DevBuf<float> vpos, vnrm;
+  DevBuf<float4> tris, trisRef;
+  DevBuf<rt_material> mats;
+  DevBuf<rtd::DevMat> matsDev;
+  DevBuf<rt_light> lights;
+  DevBuf<uint32_t> meshTriBegin, meshVtxBegin;
+  // device-built BVH (rt_options.bvh_builder / RT_BVH_GPU): the float form of the nodes stays
+  // on the device for rt_bvh_export
+  DevBuf<float4> nodesF;
+  // the photon map (install_photons / drop_photons)
+  DevBuf<float4> phPos, phDir;
+  DevBuf<uint4> phTopo;  // explicit kd topology over phPos (rtk::launch_kd_topology)
+  DevBuf<uint32_t> dTiles;
   uint32_t nTiles = 0;
   TileKey tileKey;
-  unsigned long long* dCounters = nullptr;
-  uint32_t* dTileCounter = nullptr;  // work queue head of the persistent render kernel
+  DevBuf<unsigned long long> dCounters;
+  DevBuf<uint32_t> dTileCounter;  // work queue head of the persistent render kernel
   // owned-granule lists of the ranks of a tile-sharded frame (multi-GPU assembly), by key
   struct GranList {
-    uint32_t* d = nullptr;
+    DevBuf<uint32_t> d;
     uint32_t n = 0;
   };
   std::map<std::string, GranList> granules;
-  // device-built BVH (rt_options.bvh_builder / RT_BVH_GPU): the float form of the nodes stays
-  // on the device for rt_bvh_export
-  float4* dNodesF = nullptr;
   // path state + ray queues of the wavefront integrator (allocated on first use)
   rtk::WfArgs wf{};
   size_t wfCap = 0;
-  void* wfBlock = nullptr;
+  DevBuf<char> wfBlock;
   uint32_t builder = RT_BVH_HOST;
   bool broken = false;  // the device tree is in an unknown state (rt_bvh_tune could not restore it): launches are refused
   uint32_t recipCheck = 0;  // 0: short reciprocal forms not wanted (operand bounds), 1: verified on this device, 2: self-check FAILED (dividing)
   uint32_t nodeFormat = RT_NODES_F16;  // what the pooled render kernel and rt_trace traverse
   float buildMs = 0.f;
   uint32_t numCUs = 0;
-  hipEvent_t ev[kEventPairs][2];
+  Event ev[kEventPairs][2];
   int evUsed = 0;
-  bool evReady = false;
 };
 
 namespace {
 
-template <class T>
-int upload_owned(rt_ctx* c, const T** field, const void* src, size_t count) {
-  T* d = nullptr;
-  int rc = upload(&d, src, count);
-  if (rc != RT_OK) return rc;
-  if (d) c->allocs.push_back(d);
-  *field = d;
+// The device scene forgets the photon map BEFORE it is freed: a failure anywhere after leaves "no photons"
+// behind (check_params then refuses use_photons), never dangling pointers.
+int drop_photons(rt_ctx* c) {
+  c->S.phPos = c->S.phDir = nullptr, c->S.phTopo = nullptr, c->S.n_photons = 0;
+  if (c->phPos) HIP_TRY(hipFree(c->phPos.release()));
+  if (c->phDir) HIP_TRY(hipFree(c->phDir.release()));
+  if (c->phTopo) HIP_TRY(hipFree(c->phTopo.release()));
   return RT_OK;
+}
+void install_photons(rt_ctx* c, DevBuf<float4> pos, DevBuf<float4> dir, DevBuf<uint4> topo, uint32_t n) {
+  c->phPos = std::move(pos), c->phDir = std::move(dir), c->phTopo = std::move(topo);
+  c->S.phPos = c->phPos.get(), c->S.phDir = c->phDir.get(), c->S.phTopo = c->phTopo.get(), c->S.n_photons = n;
+}
+// PhotonMap.h:19-20: lightPdf = 1.f / #lights; photonsPerLS = (int)(n * lightPdf)
+uint32_t photons_per_light(uint32_t n_requested, uint32_t n_lights) {
+  const float lightPdf = 1.f / static_cast<float>(n_lights);
+  return static_cast<uint32_t>(static_cast<int>(static_cast<float>(static_cast<int>(n_requested)) * lightPdf));
 }
 
 // How many samples of a pixel one wave integrates side by side.  A pixel's float
@@ -181,6 +235,18 @@ uint32_t choose_sshift(const rt_ctx* c, const rt_params* p, uint32_t spp_count) 
   return s;
 }
 
+// f(x8, y8) for each 8x8-pixel granule rank `rank` of `world` owns, row-major — the order ensure_tiles
+// renders them in and the order of the packed exchange buffer.
+template <class F>
+void owned_granules(uint32_t w, uint32_t h, uint32_t rank, uint32_t world, uint32_t tile, F f) {
+  if (tile == 0) tile = 8;
+  if (world == 0) world = 1;
+  const uint32_t gx = (w + 7) / 8, gy = (h + 7) / 8;
+  for (uint32_t y8 = 0; y8 < gy; ++y8)
+    for (uint32_t x8 = 0; x8 < gx; ++x8)
+      if (world <= 1 || (x8 * 8 / tile + y8 * 8 / tile) % world == rank) f(x8, y8);
+}
+
 int ensure_tiles(rt_ctx* c, const rt_params* p, uint32_t sshift) {
   TileKey k;
   k.w = p->width, k.h = p->height, k.rank = p->rank, k.world = p->world ? p->world : 1;
@@ -190,20 +256,12 @@ int ensure_tiles(rt_ctx* c, const rt_params* p, uint32_t sshift) {
   std::vector<uint32_t> tiles;
   uint32_t tw, th;
   wave_tile_shape(sshift, tw, th);
-  // enumerate 8x8 granules row-major and the wave tiles inside each granule, so that
-  // consecutive waves touch neighbouring pixels
-  const uint32_t gx = (k.w + 7) / 8, gy = (k.h + 7) / 8;
-  for (uint32_t y8 = 0; y8 < gy; ++y8)
-    for (uint32_t x8 = 0; x8 < gx; ++x8) {
-      const uint32_t ox = x8 * 8 / k.tile, oy = y8 * 8 / k.tile;
-      if (k.world > 1 && (ox + oy) % k.world != k.rank) continue;
-      for (uint32_t y = y8 * 8; y < y8 * 8 + 8 && y < k.h; y += th)
-        for (uint32_t x = x8 * 8; x < x8 * 8 + 8 && x < k.w; x += tw) tiles.push_back(x | (y << 16));
-    }
-  if (c->dTiles) {
-    HIP_TRY(hipFree(c->dTiles));
-    c->dTiles = nullptr;
-  }
+  // the wave tiles inside each owned granule, row-major, so that consecutive waves touch neighbouring pixels
+  owned_granules(k.w, k.h, k.rank, k.world, k.tile, [&](uint32_t x8, uint32_t y8) {
+    for (uint32_t y = y8 * 8; y < y8 * 8 + 8 && y < k.h; y += th)
+      for (uint32_t x = x8 * 8; x < x8 * 8 + 8 && x < k.w; x += tw) tiles.push_back(x | (y << 16));
+  });
+  if (c->dTiles) HIP_TRY(hipFree(c->dTiles.release()));
   int rc = upload(&c->dTiles, tiles.data(), tiles.size());
   if (rc != RT_OK) return rc;
   c->nTiles = static_cast<uint32_t>(tiles.size());
@@ -211,37 +269,20 @@ int ensure_tiles(rt_ctx* c, const rt_params* p, uint32_t sshift) {
   return RT_OK;
 }
 
-// The 8x8-pixel granules rank `rank` of `world` owns, row-major — the order ensure_tiles
-// renders them in and the order of the packed exchange buffer.
-void owned_granules(uint32_t w, uint32_t h, uint32_t rank, uint32_t world, uint32_t tile, std::vector<uint32_t>* out,
-                    uint32_t* count) {
-  if (tile == 0) tile = 8;
-  if (world == 0) world = 1;
-  uint32_t n = 0;
-  const uint32_t gx = (w + 7) / 8, gy = (h + 7) / 8;
-  for (uint32_t y8 = 0; y8 < gy; ++y8)
-    for (uint32_t x8 = 0; x8 < gx; ++x8) {
-      if (world > 1 && (x8 * 8 / tile + y8 * 8 / tile) % world != rank) continue;
-      if (out) out->push_back(x8 | (y8 << 16));
-      ++n;
-    }
-  if (count) *count = n;
-}
-
-int ensure_granules(rt_ctx* c, const rt_params* p, uint32_t rank, rt_ctx::GranList* out) {
+int ensure_granules(rt_ctx* c, const rt_params* p, uint32_t rank, const rt_ctx::GranList** out) {
   char key[96];
   snprintf(key, sizeof key, "%u.%u.%u.%u.%u", p->width, p->height, rank, p->world ? p->world : 1, p->tile ? p->tile : 8);
   auto it = c->granules.find(key);
   if (it == c->granules.end()) {
     std::vector<uint32_t> g;
-    owned_granules(p->width, p->height, rank, p->world, p->tile, &g, nullptr);
+    owned_granules(p->width, p->height, rank, p->world, p->tile, [&](uint32_t x8, uint32_t y8) { g.push_back(x8 | (y8 << 16)); });
     rt_ctx::GranList L;
     int rc = upload(&L.d, g.data(), g.size());
     if (rc != RT_OK) return rc;
     L.n = static_cast<uint32_t>(g.size());
-    it = c->granules.emplace(key, L).first;
+    it = c->granules.emplace(key, std::move(L)).first;
   }
-  *out = it->second;
+  *out = &it->second;
   return RT_OK;
 }
 
@@ -273,7 +314,7 @@ int check_params(const rt_ctx* c, const rt_params* p) {
 
 int read_counters(rt_ctx* c, rt_stats* st) {
   unsigned long long h[RTK_CNT_COUNT];
-  HIP_TRY(hipMemcpy(h, c->dCounters, sizeof h, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h, c->dCounters.get(), sizeof h, hipMemcpyDeviceToHost));
   st->rays_closest = h[RTK_CNT_CLOSEST];
   st->rays_shadow = h[RTK_CNT_SHADOW];
   st->knn_queries = h[RTK_CNT_KNN];
@@ -314,6 +355,48 @@ uint32_t stack_levels(uint32_t levels) {
   return (levels > (uint32_t)rtbvh::kMaxDepth ? (uint32_t)rtbvh::kMaxDepth : levels) + 1u;
 }
 
+// The wavefront integrator's arguments for p: rank p->rank's granules and its path state + ray queues, carved from
+// one block that grows with the batch.  *out keeps nGran 0 when the rank owns no pixel: there is nothing to launch.
+int wavefront_args(rt_ctx* c, const rt_params* p, const rtk::RenderArgs& A, uint32_t sppCount, hipStream_t stream,
+                   rtk::WfArgs* out) {
+  const rt_ctx::GranList* G = nullptr;
+  int rc = ensure_granules(c, p, p->rank, &G);
+  if (rc != RT_OK) return rc;
+  const size_t perSample = (size_t)G->n * 64u;
+  if (perSample == 0) return RT_OK;
+  size_t batch = (4u << 20) / perSample;  // ~4 M paths per batch (1.1 GB of state + queues)
+  batch = batch < 1 ? 1 : batch > sppCount ? sppCount : batch;
+  const size_t P = batch * perSample;
+  if (P > c->wfCap) {
+    c->wfCap = 0;
+    if (c->wfBlock) HIP_TRY(hipFree(c->wfBlock.release()));
+    // rng 4, org 16, dir 16, key 8, nrm 16, pnt 16, col 48, rayO 64, rayD 64, res 32 = 284 B per path
+    const size_t bytes = P * 284 + 4096 + 2048 * sizeof(unsigned long long);
+    HIP_TRY(dev_alloc(&c->wfBlock, bytes));
+    char* q = c->wfBlock.get();
+    auto take = [&](size_t n) {
+      char* r = q;
+      q += (n + 255) / 256 * 256;
+      return r;
+    };
+    rtk::WfArgs& W = c->wf;
+    W.rayO = reinterpret_cast<float4*>(take(P * 64)), W.rayD = reinterpret_cast<float4*>(take(P * 64));
+    W.col = reinterpret_cast<float4*>(take(P * 48));
+    W.org = reinterpret_cast<float4*>(take(P * 16)), W.dir = reinterpret_cast<float4*>(take(P * 16));
+    W.nrm = reinterpret_cast<float4*>(take(P * 16)), W.pnt = reinterpret_cast<float4*>(take(P * 16));
+    W.res = reinterpret_cast<uint2*>(take(P * 32)), W.key = reinterpret_cast<uint2*>(take(P * 8));
+    W.rng = reinterpret_cast<uint32_t*>(take(P * 4));
+    W.stripes = reinterpret_cast<unsigned long long*>(take(2048 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(W.stripes, 0, 2048 * sizeof(unsigned long long), stream));
+    c->wfCap = P;
+  }
+  rtk::WfArgs W = c->wf;
+  W.gran = G->d.get(), W.nGran = G->n, W.width = p->width, W.height = p->height, W.spp = p->spp, W.seed = p->seed;
+  W.s0 = A.s0, W.s1 = A.s1, W.batch = (uint32_t)batch, W.nPaths = 0;
+  *out = W;
+  return RT_OK;
+}
+
 // Launch the integrate kernel for p on `stream`, bracketed by an event pair.
 int launch_frame(rt_ctx* c, const rt_params* p, float4* dAccum, hipStream_t stream, int* evIndex) {
   const uint32_t sppCount = p->spp_count ? p->spp_count : p->spp;
@@ -323,7 +406,7 @@ int launch_frame(rt_ctx* c, const rt_params* p, float4* dAccum, hipStream_t stre
   rtk::RenderArgs A;
   A.sshift = sshift;
   wave_tile_shape(sshift, A.tileW, A.tileH);
-  A.tiles = c->dTiles, A.n_tiles = c->nTiles;
+  A.tiles = c->dTiles.get(), A.n_tiles = c->nTiles;
   A.width = p->width, A.height = p->height, A.spp = p->spp;
   A.s0 = p->spp_count ? p->spp_begin : 0;
   A.s1 = p->spp_count ? p->spp_begin + p->spp_count : p->spp;
@@ -343,64 +426,24 @@ int launch_frame(rt_ctx* c, const rt_params* p, float4* dAccum, hipStream_t stre
     levels = levels > ks.rows ? levels : ks.rows;
   }
   A.stackLevels = stack_levels(levels);
-  A.tileCounter = c->dTileCounter, A.numCUs = c->numCUs, A.waveWords = 0, A.tilesPerBlock = 1;
-  const int e = c->evUsed % kEventPairs;
+  A.tileCounter = c->dTileCounter.get(), A.numCUs = c->numCUs, A.waveWords = 0, A.tilesPerBlock = 1;
   // rt_params.reserved[2] bit 0: the queue-based (wavefront) integrator — BVH direct lighting with
   // at most 3 lights, like the pooled kernel; same frame bit for bit
-  if ((p->reserved[2] & 1u) && !p->use_photons && p->accel != RT_ACCEL_BRUTE && c->S.n_lights <= 3u) {
-    rt_ctx::GranList G;
-    rc = ensure_granules(c, p, p->rank, &G);
-    if (rc != RT_OK) return rc;
-    const size_t perSample = (size_t)G.n * 64u;
-    if (perSample == 0) {
-      HIP_TRY(hipEventRecord(c->ev[e][0], stream));
-      HIP_TRY(hipEventRecord(c->ev[e][1], stream));
-      c->evUsed++;
-      if (evIndex) *evIndex = e;
-      return RT_OK;
-    }
-    size_t batch = (4u << 20) / perSample;  // ~4 M paths per batch (1.1 GB of state + queues)
-    batch = batch < 1 ? 1 : batch > sppCount ? sppCount : batch;
-    const size_t P = batch * perSample;
-    if (P > c->wfCap) {
-      if (c->wfBlock) HIP_TRY(hipFree(c->wfBlock));
-      c->wfBlock = nullptr, c->wfCap = 0;
-      // rng 4, org 16, dir 16, key 8, nrm 16, pnt 16, col 48, rayO 64, rayD 64, res 32 = 284 B per path
-      const size_t bytes = P * 284 + 4096 + 2048 * sizeof(unsigned long long);
-      HIP_TRY(hipMalloc(&c->wfBlock, bytes));
-      char* q = static_cast<char*>(c->wfBlock);
-      auto take = [&](size_t n) {
-        char* r = q;
-        q += (n + 255) / 256 * 256;
-        return r;
-      };
-      rtk::WfArgs& W = c->wf;
-      W.rayO = reinterpret_cast<float4*>(take(P * 64)), W.rayD = reinterpret_cast<float4*>(take(P * 64));
-      W.col = reinterpret_cast<float4*>(take(P * 48));
-      W.org = reinterpret_cast<float4*>(take(P * 16)), W.dir = reinterpret_cast<float4*>(take(P * 16));
-      W.nrm = reinterpret_cast<float4*>(take(P * 16)), W.pnt = reinterpret_cast<float4*>(take(P * 16));
-      W.res = reinterpret_cast<uint2*>(take(P * 32)), W.key = reinterpret_cast<uint2*>(take(P * 8));
-      W.rng = reinterpret_cast<uint32_t*>(take(P * 4));
-      W.stripes = reinterpret_cast<unsigned long long*>(take(2048 * sizeof(unsigned long long)));
-      HIP_TRY(hipMemsetAsync(W.stripes, 0, 2048 * sizeof(unsigned long long), stream));
-      c->wfCap = P;
-    }
-    rtk::WfArgs W = c->wf;
-    W.gran = G.d, W.nGran = G.n, W.width = p->width, W.height = p->height, W.spp = p->spp, W.seed = p->seed;
-    W.s0 = A.s0, W.s1 = A.s1, W.batch = (uint32_t)batch, W.nPaths = 0;
-    HIP_TRY(hipEventRecord(c->ev[e][0], stream));
-    hipError_t hw = rtk::launch_wavefront(c->S, W, p->mode, p->max_depth, dAccum, c->dCounters, c->dTileCounter, A.stackLevels, c->numCUs, stream);
+  const bool wavefront = (p->reserved[2] & 1u) && !p->use_photons && p->accel != RT_ACCEL_BRUTE && c->S.n_lights <= 3u;
+  rtk::WfArgs W{};
+  if (wavefront && (rc = wavefront_args(c, p, A, sppCount, stream, &W)) != RT_OK) return rc;
+  const int e = c->evUsed % kEventPairs;
+  HIP_TRY(hipEventRecord(c->ev[e][0].get(), stream));
+  if (!wavefront) {
+    hipError_t he = rtk::launch_render(p->accel == RT_ACCEL_BRUTE, p->use_photons != 0, p->collect_stats != 0, c->S, A,
+                                       dAccum, c->dCounters.get(), stream);
+    if (he != hipSuccess) return fail(RT_ERR_HIP, "render launch failed: %s", hipGetErrorString(he));
+  } else if (W.nGran) {
+    hipError_t hw = rtk::launch_wavefront(c->S, W, p->mode, p->max_depth, dAccum, c->dCounters.get(), c->dTileCounter.get(),
+                                          A.stackLevels, c->numCUs, stream);
     if (hw != hipSuccess) return fail(RT_ERR_HIP, "wavefront launch failed: %s", hipGetErrorString(hw));
-    HIP_TRY(hipEventRecord(c->ev[e][1], stream));
-    c->evUsed++;
-    if (evIndex) *evIndex = e;
-    return RT_OK;
   }
-  HIP_TRY(hipEventRecord(c->ev[e][0], stream));
-  hipError_t he = rtk::launch_render(p->accel == RT_ACCEL_BRUTE, p->use_photons != 0, p->collect_stats != 0, c->S, A,
-                                     dAccum, c->dCounters, stream);
-  if (he != hipSuccess) return fail(RT_ERR_HIP, "render launch failed: %s", hipGetErrorString(he));
-  HIP_TRY(hipEventRecord(c->ev[e][1], stream));
+  HIP_TRY(hipEventRecord(c->ev[e][1].get(), stream));
   c->evUsed++;
   if (evIndex) *evIndex = e;
   return RT_OK;
@@ -445,6 +488,92 @@ void par_chunks(size_t b, size_t e, F f) {
   for (std::thread& x : th) x.join();
 }
 
+// The tree the device builder left on the device, read back into c->bvh: its float nodes, and with nTris > 0 its
+// triangle records in both orders (throws: the callers report it as their step's failure)
+void read_back_tree(rt_ctx* c, uint32_t nTris) {
+  const size_t nn = c->S.n_nodes;
+  c->bvh.nodes.resize(nn), c->bvh.tris.resize(nTris), c->bvh.trisRef.resize(nTris);
+  if (hipMemcpy(c->bvh.nodes.data(), c->nodesF.get(), nn * sizeof(rtbvh::Node), hipMemcpyDeviceToHost) != hipSuccess ||
+      (nTris && (hipMemcpy(c->bvh.tris.data(), c->tris.get(), (size_t)nTris * sizeof(rtbvh::TriRec), hipMemcpyDeviceToHost) != hipSuccess ||
+                 hipMemcpy(c->bvh.trisRef.data(), c->trisRef.get(), (size_t)nTris * sizeof(rtbvh::TriRec), hipMemcpyDeviceToHost) != hipSuccess)))
+    throw std::runtime_error("reading the device-built tree back failed");
+}
+
+// The short reciprocal (rt_device.h recip_fast: v_rcp_f32 + one Newton step, the division's bits for 2^-100 <= |x| < 2^101
+// — exhaustive check, tools/microbench/recip_exact.hip) replaces the division in the default render instances
+// (rt_kernels.hip LT_FASTDET) in two places, and the host vouches for the range here:
+//  * 1 / det of the triangle test: |det| = |e1 . (d x e2)| <= |e1| |e2| |d|; edges are at most 2 sqrt(3) maxAbs long, and
+//    the rays the RENDER kernels make are unit vectors (camera, bounce) or run from a surface point to a light sample;
+//  * length and 1 / length in normalisations (sqrt_fast: the same check, 2^-100 <= x < 2^101): every vector the kernels
+//    normalise is a small sum of scene inputs, so |input| <= 1e14 keeps the squared length below 2^100 (the lower end
+//    is tested per lane: rt_device.h unit3).
+// Outside these bounds — or with any non-finite input — the kernels divide.  (User rays, rt_trace /
+// rt_trace_stream_device, always divide.)  Sets c->S.slowRecip and c->recipCheck.
+void vouch_short_forms(rt_ctx* c, const rt_scene_desc* sc) {
+  rtk::DevScene& S = c->S;
+  double maxAbs = 0, maxLight = 0, maxAny = 0;
+  bool finite = true;
+  // (a non-finite value has all exponent bits set: its magnitude bits compare above every finite float's)
+  auto eat = [&](const float* p, size_t n) {
+    uint32_t top[64] = {0};
+    par_chunks(0, n, [&](uint32_t th, size_t b, size_t e) {
+      uint32_t m = 0;
+      for (size_t i = b; i < e; ++i) {
+        uint32_t u;
+        memcpy(&u, p + i, 4);
+        u &= 0x7fffffffu;
+        m = u > m ? u : m;
+      }
+      top[th] = m;
+    });
+    uint32_t m = 0;
+    for (uint32_t t : top) m = t > m ? t : m;
+    float f;
+    memcpy(&f, &m, 4);
+    if (m >= 0x7f800000u) finite = false;
+    else maxAny = std::max(maxAny, (double)f);
+    return m >= 0x7f800000u ? 0.0 : (double)f;
+  };
+  maxAbs = eat(sc->vertex_pos, 3 * (size_t)sc->n_vertices);
+  eat(sc->vertex_nrm, 3 * (size_t)sc->n_vertices);
+  eat(sc->camera.position, 12);
+  for (uint32_t l = 0; l < sc->n_lights; ++l) {
+    const rt_light& L = sc->lights[l];
+    eat(L.position, 15);
+    eat(&L.intensity, 6);
+    double pos = 0, ver = 0, hor = 0;
+    for (int a = 0; a < 3; ++a) pos += (double)L.position[a] * L.position[a], ver += (double)L.vertical[a] * L.vertical[a], hor += (double)L.horizontal[a] * L.horizontal[a];
+    maxLight = std::max(maxLight, std::sqrt(pos) + std::fabs((double)L.side) * (std::sqrt(ver) + std::sqrt(hor)));
+  }
+  const double edge = 2.0 * 1.7320508 * maxAbs, dir = 1.7320508 * maxAbs + maxLight + 2.0;
+  const double detBound = 1.01 * edge * edge * dir;
+  S.slowRecip = (finite && maxAny <= 1e14 && maxLight <= 1e14 && std::isfinite(detBound) && detBound < 1.2676506e30) ? 0u : 1u;
+  if (getenv("RT_SLOW_RECIP")) S.slowRecip = 1u;  // (A/B and the parity tests of the division path)
+  // ... and the device vouches for the short forms itself, once per process and device (2^25 inputs, well under a
+  // millisecond): the exhaustive check ran on one MI355X; a part whose v_rcp_f32 / v_rsq_f32 rounded differently would
+  // show here, and its contexts divide.
+  if (S.slowRecip) return;
+  static std::mutex mu;
+  static std::map<int, bool> verified;
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = verified.find(c->device);
+  if (it == verified.end()) {
+    bool ok = false;
+    {
+      DevBuf<uint32_t> dBad;
+      uint32_t bad = 1u;
+      if (dev_alloc(&dBad, 1) == hipSuccess && hipMemset(dBad.get(), 0, sizeof(uint32_t)) == hipSuccess &&
+          rtk::launch_selfcheck_recip(dBad.get(), nullptr) == hipSuccess &&
+          hipMemcpy(&bad, dBad.get(), sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess)
+        ok = bad == 0u;
+    }
+    it = verified.emplace(c->device, ok).first;
+    if (getenv("RT_BVH_VERBOSE")) fprintf(stderr, "short reciprocal / square root self-check on device %d: %s\n", c->device, ok ? "bit-identical" : "MISMATCH, dividing");
+  }
+  if (!it->second) S.slowRecip = 1u;
+  c->recipCheck = it->second ? 1u : 2u;
+}
+
 int create_ctx(const rt_scene_desc* sc, const rt_options* opt, const rtbvh::Built* prebuilt, rt_ctx** out) {
   if (!sc || !out) return fail(RT_ERR_INVALID, "scene/out is null");
   *out = nullptr;
@@ -458,17 +587,15 @@ int create_ctx(const rt_scene_desc* sc, const rt_options* opt, const rtbvh::Buil
   int rc = select_device(opt ? opt->device : 0);
   if (rc != RT_OK) return rc;
 
-  rt_ctx* c = new rt_ctx();
+  // (every exit before the release at the end frees what the context holds so far, on this device)
+  std::unique_ptr<rt_ctx> c(new rt_ctx());
   c->device = opt ? opt->device : 0;
   // the tree: host SAH builder, or the device builder (tiny scenes always take the host's
   // special cases)
   // (RT_BVH_GPU=1 / 2 / 3: the device / hybrid / host builder whatever the options say — the test suites run whole on each)
   const char* gpuEnv = getenv("RT_BVH_GPU");
   uint32_t wantBuilder = gpuEnv ? (uint32_t)atoi(gpuEnv) : (opt ? opt->bvh_builder : (uint32_t)RT_BVH_AUTO);
-  if (wantBuilder > RT_BVH_HOST) {
-    delete c;
-    return fail(RT_ERR_INVALID, "unknown bvh_builder %u", wantBuilder);
-  }
+  if (wantBuilder > RT_BVH_HOST) return fail(RT_ERR_INVALID, "unknown bvh_builder %u", wantBuilder);
   // AUTO: the device builder gives the host builder's tree (tests/treedigest.py; profiles/r04_builders.txt) 2 ... 14 x sooner,
   // so every scene it is faster on takes it (from 8,192 triangles: below that a build is 1-3 ms either way and the host needs no
   // device round trip); a group of contexts given a host-built tree shares it
@@ -503,7 +630,6 @@ int create_ctx(const rt_scene_desc* sc, const rt_options* opt, const rtbvh::Buil
       rtbvh::build(*sc, opt ? opt->bvh_leaf_max : 0, c->bvh);
     }
   } catch (const std::exception& e) {
-    delete c;
     return fail(RT_ERR_INVALID, "scene rejected: %s", e.what());
   }
   static_assert(sizeof(rtbvh::Node16) == 2 * sizeof(uint4), "node layout");
@@ -517,32 +643,23 @@ int create_ctx(const rt_scene_desc* sc, const rt_options* opt, const rtbvh::Buil
     });
 
   rtk::DevScene& S = c->S;
-#define UP(field, src, n)                                  \
-  if ((rc = upload_owned(c, &S.field, src, n)) != RT_OK) { \
-    rt_destroy(c);                                         \
-    return rc;                                             \
-  }
-  UP(triShade, shade.get(), (size_t)sc->n_triangles);
+  if ((rc = upload(&c->triShade, shade.get(), (size_t)sc->n_triangles)) != RT_OK) return rc;
   shade.reset();
-  UP(vpos, sc->vertex_pos, (size_t)sc->n_vertices * 3);
-  UP(vnrm, sc->vertex_nrm, (size_t)sc->n_vertices * 3);
+  if ((rc = upload(&c->vpos, sc->vertex_pos, (size_t)sc->n_vertices * 3)) != RT_OK ||
+      (rc = upload(&c->vnrm, sc->vertex_nrm, (size_t)sc->n_vertices * 3)) != RT_OK)
+    return rc;
   if (gpuBuild) {
     if (getenv("RT_BVH_VERBOSE"))
       fprintf(stderr, "scene arrays on the device %.2f ms after the start\n", std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - tBuild0).count());
     rtk::GpuBvh G;
     hipError_t he = hipSuccess;
     if (hybrid) {
-      he = rtk::gpu_bvh_build_over_top(S.vpos, S.triShade, sizeKey.data(), sc->n_triangles, topBuilt, &G, nullptr);
+      he = rtk::gpu_bvh_build_over_top(c->vpos.get(), c->triShade.get(), sizeKey.data(), sc->n_triangles, topBuilt, &G, nullptr);
     } else {
-      he = rtk::gpu_bvh_build_exact(S.vpos, S.triShade, sizeKey.data(), sc->n_triangles, plan, &G, nullptr);
+      he = rtk::gpu_bvh_build_exact(c->vpos.get(), c->triShade.get(), sizeKey.data(), sc->n_triangles, plan, &G, nullptr);
     }
-    if (he != hipSuccess) {
-      rt_destroy(c);
-      return fail(RT_ERR_HIP, "device BVH build failed: %s", hipGetErrorString(he));
-    }
-    S.nodes = G.nodes16, S.tris = G.tris, S.trisRef = G.trisRef;
-    c->allocs.push_back(G.nodes16), c->allocs.push_back(G.tris), c->allocs.push_back(G.trisRef);
-    c->dNodesF = G.nodesF;
+    if (he != hipSuccess) return fail(RT_ERR_HIP, "device BVH build failed: %s", hipGetErrorString(he));
+    c->nodes.reset(G.nodes16), c->tris.reset(G.tris), c->trisRef.reset(G.trisRef), c->nodesF.reset(G.nodesF);
     c->bvh.maxDepth = G.maxDepth;
     S.n_nodes = G.n_nodes;
     c->builder = hybrid ? RT_BVH_HYBRID : RT_BVH_DEVICE;
@@ -551,159 +668,69 @@ int create_ctx(const rt_scene_desc* sc, const rt_options* opt, const rtbvh::Buil
     // relayoutTop) — instead of the device's pre-order: C4 loses 2 % on a pre-order tree.  64 KB ... 4 MB back and forth.
     if (S.n_nodes >= 2u && S.n_nodes <= 65536u) {
       try {
-        c->bvh.nodes.resize(S.n_nodes);
-        if (hipMemcpy(c->bvh.nodes.data(), c->dNodesF, (size_t)S.n_nodes * sizeof(rtbvh::Node), hipMemcpyDeviceToHost) != hipSuccess)
-          throw std::runtime_error("reading the device-built tree back failed");
+        read_back_tree(c.get(), 0);
         rtbvh::relayoutAndPack(c->bvh);
-        if (hipMemcpy(c->dNodesF, c->bvh.nodes.data(), (size_t)S.n_nodes * sizeof(rtbvh::Node), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(const_cast<uint4*>(S.nodes), c->bvh.nodes16.data(), (size_t)S.n_nodes * sizeof(rtbvh::Node16), hipMemcpyHostToDevice) != hipSuccess)
+        if (hipMemcpy(c->nodesF.get(), c->bvh.nodes.data(), (size_t)S.n_nodes * sizeof(rtbvh::Node), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(c->nodes.get(), c->bvh.nodes16.data(), (size_t)S.n_nodes * sizeof(rtbvh::Node16), hipMemcpyHostToDevice) != hipSuccess)
           throw std::runtime_error("writing the renumbered tree failed");
         c->bvh.nodes.clear(), c->bvh.nodes16.clear();  // (rt_bvh_export reads the device copies)
       } catch (const std::exception& e) {
-        rt_destroy(c);
         return fail(RT_ERR_HIP, "device BVH build: %s", e.what());
       }
     }
   } else {
-    UP(nodes, c->bvh.nodes16.data(), c->bvh.nodes16.size() * 2);
-    UP(tris, c->bvh.tris.data(), c->bvh.tris.size() * 3);
-    UP(trisRef, c->bvh.trisRef.data(), c->bvh.trisRef.size() * 3);
+    if ((rc = upload(&c->nodes, c->bvh.nodes16.data(), c->bvh.nodes16.size() * 2)) != RT_OK ||
+        (rc = upload(&c->tris, c->bvh.tris.data(), c->bvh.tris.size() * 3)) != RT_OK ||
+        (rc = upload(&c->trisRef, c->bvh.trisRef.data(), c->bvh.trisRef.size() * 3)) != RT_OK)
+      return rc;
     S.n_nodes = static_cast<uint32_t>(c->bvh.nodes.size());
   }
   // The node records the pooled render kernel and rt_trace traverse (rt_options.node_format; RT_NODES=f16|q8 overrides).
   // RT_NODES_Q8 — 16-byte records, ONE vector-memory request per visit (bvh_build.h Slot16) — is for trees the caches do
   // not hold, where the traversal sits on the vector L1's request rate.  The other kernels (photon emission, ray streams,
   // the wavefront integrator, the one-wave-per-workgroup render instances) keep the 32-byte records, so both forms are resident.
-  {
-    uint32_t want = opt ? opt->node_format : (uint32_t)RT_NODES_AUTO;
-    if (const char* e = getenv("RT_NODES")) want = !strcmp(e, "q8") ? (uint32_t)RT_NODES_Q8 : !strcmp(e, "f16") ? (uint32_t)RT_NODES_F16 : want;
-    if (want > RT_NODES_Q8) {
-      rt_destroy(c);
-      return fail(RT_ERR_INVALID, "unknown node_format %u", want);
+  uint32_t wantNodes = opt ? opt->node_format : (uint32_t)RT_NODES_AUTO;
+  if (const char* e = getenv("RT_NODES")) wantNodes = !strcmp(e, "q8") ? (uint32_t)RT_NODES_Q8 : !strcmp(e, "f16") ? (uint32_t)RT_NODES_F16 : wantNodes;
+  if (wantNodes > RT_NODES_Q8) return fail(RT_ERR_INVALID, "unknown node_format %u", wantNodes);
+  if (wantNodes == RT_NODES_Q8) {
+    try {
+      if (gpuBuild) read_back_tree(c.get(), sc->n_triangles);  // the packer works from the float records
+      if (c->bvh.q8.empty()) rtbvh::packQ8(c->bvh);
+      if (gpuBuild) c->bvh.nodes.clear(), c->bvh.tris.clear(), c->bvh.trisRef.clear();  // (rt_bvh_export reads the device copies)
+    } catch (const std::exception& e) {
+      return fail(RT_ERR_UNSUPPORTED, "node_format RT_NODES_Q8: %s", e.what());
     }
-    if (want == RT_NODES_AUTO) want = RT_NODES_F16;
-    if (want == RT_NODES_Q8) {
-      try {
-        if (gpuBuild) {  // the packer works from the float records: fetch what the device builder left on the device
-          c->bvh.nodes.resize(S.n_nodes), c->bvh.tris.resize(sc->n_triangles), c->bvh.trisRef.resize(sc->n_triangles);
-          if (hipMemcpy(c->bvh.nodes.data(), c->dNodesF, (size_t)S.n_nodes * sizeof(rtbvh::Node), hipMemcpyDeviceToHost) != hipSuccess ||
-              hipMemcpy(c->bvh.tris.data(), S.tris, (size_t)sc->n_triangles * sizeof(rtbvh::TriRec), hipMemcpyDeviceToHost) != hipSuccess ||
-              hipMemcpy(c->bvh.trisRef.data(), S.trisRef, (size_t)sc->n_triangles * sizeof(rtbvh::TriRec), hipMemcpyDeviceToHost) != hipSuccess)
-            throw std::runtime_error("reading the device-built tree back failed");
-        }
-        if (c->bvh.q8.empty()) rtbvh::packQ8(c->bvh);
-        if (gpuBuild) c->bvh.nodes.clear(), c->bvh.tris.clear(), c->bvh.trisRef.clear();  // (rt_bvh_export reads the device copies)
-      } catch (const std::exception& e) {
-        rt_destroy(c);
-        return fail(RT_ERR_UNSUPPORTED, "node_format RT_NODES_Q8: %s", e.what());
-      }
-      static_assert(sizeof(rtbvh::Slot16) == sizeof(uint4), "slot layout");
-      if ((rc = upload_owned(c, &S.q8, c->bvh.q8.data(), c->bvh.q8.size())) != RT_OK) {
-        rt_destroy(c);
-        return rc;
-      }
-      S.q8ShiftBytes = c->bvh.q8Shift + 4u;
-      c->nodeFormat = RT_NODES_Q8;
-      std::vector<rtbvh::Slot16>().swap(c->bvh.q8);  // (the host copy is not needed again)
-    }
+    static_assert(sizeof(rtbvh::Slot16) == sizeof(uint4), "slot layout");
+    if ((rc = upload(&c->q8, c->bvh.q8.data(), c->bvh.q8.size())) != RT_OK) return rc;
+    S.q8ShiftBytes = c->bvh.q8Shift + 4u;
+    c->nodeFormat = RT_NODES_Q8;
+    std::vector<rtbvh::Slot16>().swap(c->bvh.q8);  // (the host copy is not needed again)
   }
   c->buildMs = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - tBuild0).count();
   if (getenv("RT_BVH_VERBOSE")) fprintf(stderr, "tree resident %.2f ms after the start\n", c->buildMs);
-  UP(mats, sc->materials, sc->n_meshes);
-  {
-    std::vector<rtd::DevMat> dm(sc->n_meshes);
-    for (uint32_t m = 0; m < sc->n_meshes; ++m) dm[m] = rtd::make_dev_mat(sc->materials[m]);
-    UP(matsDev, dm.data(), dm.size());
-  }
-  UP(lights, sc->lights, sc->n_lights);
-  UP(meshTriBegin, sc->mesh_tri_begin, sc->n_meshes + 1);
-  UP(meshVtxBegin, sc->mesh_vtx_begin, sc->n_meshes + 1);
-#undef UP
+  std::vector<rtd::DevMat> dm(sc->n_meshes);
+  for (uint32_t m = 0; m < sc->n_meshes; ++m) dm[m] = rtd::make_dev_mat(sc->materials[m]);
+  if ((rc = upload(&c->mats, sc->materials, sc->n_meshes)) != RT_OK || (rc = upload(&c->matsDev, dm.data(), dm.size())) != RT_OK ||
+      (rc = upload(&c->lights, sc->lights, sc->n_lights)) != RT_OK ||
+      (rc = upload(&c->meshTriBegin, sc->mesh_tri_begin, sc->n_meshes + 1)) != RT_OK ||
+      (rc = upload(&c->meshVtxBegin, sc->mesh_vtx_begin, sc->n_meshes + 1)) != RT_OK)
+    return rc;
+  S.triShade = c->triShade.get(), S.vpos = c->vpos.get(), S.vnrm = c->vnrm.get();
+  S.nodes = c->nodes.get(), S.q8 = c->q8.get(), S.tris = c->tris.get(), S.trisRef = c->trisRef.get();
+  S.mats = c->mats.get(), S.matsDev = c->matsDev.get(), S.lights = c->lights.get();
+  S.meshTriBegin = c->meshTriBegin.get(), S.meshVtxBegin = c->meshVtxBegin.get();
   S.n_tris = sc->n_triangles;
   S.n_lights = sc->n_lights;
   S.n_photons = 0;
   S.invBoxScale = 1.f / c->bvh.boxScale;
   S.originBound = c->bvh.originBound;
+  vouch_short_forms(c.get(), sc);
   // Pool thresholds (Trav::round's descent early exit, the steal and refill levels).  Two scene
   // classes, as for the samples-of-a-pixel-per-wave rule: trees the caches hold (<= 65,536 nodes)
   // are issue-bound and want long descents (12 / 8 / 24: C2 50.5 ms; 16 or 24 lanes cost 0.2-1 %);
   // beyond that every step waits on the vector L1, and leaving the descent with up to 24 lanes still
   // in it plus refilling at 32 hands out work sooner (C5 328.5 -> 317.4 ms, C5x8 55.0 -> 52.4 ms;
   // profiles/r03_pool_thresholds.txt).
-  // The short reciprocal (rt_device.h recip_fast: v_rcp_f32 + one Newton step, the division's bits for 2^-100 <= |x| < 2^101
-  // — exhaustive check, tools/microbench/recip_exact.hip) replaces the division in the default render instances
-  // (rt_kernels.hip LT_FASTDET) in two places, and the host vouches for the range here:
-  //  * 1 / det of the triangle test: |det| = |e1 . (d x e2)| <= |e1| |e2| |d|; edges are at most 2 sqrt(3) maxAbs long, and
-  //    the rays the RENDER kernels make are unit vectors (camera, bounce) or run from a surface point to a light sample;
-  //  * length and 1 / length in normalisations (sqrt_fast: the same check, 2^-100 <= x < 2^101): every vector the kernels
-  //    normalise is a small sum of scene inputs, so |input| <= 1e14 keeps the squared length below 2^100 (the lower end
-  //    is tested per lane: rt_device.h unit3).
-  // Outside these bounds — or with any non-finite input — the kernels divide.  (User rays, rt_trace /
-  // rt_trace_stream_device, always divide.)
-  {
-    double maxAbs = 0, maxLight = 0, maxAny = 0;
-    bool finite = true;
-    // (a non-finite value has all exponent bits set: its magnitude bits compare above every finite float's)
-    auto eat = [&](const float* p, size_t n) {
-      uint32_t top[64] = {0};
-      par_chunks(0, n, [&](uint32_t th, size_t b, size_t e) {
-        uint32_t m = 0;
-        for (size_t i = b; i < e; ++i) {
-          uint32_t u;
-          memcpy(&u, p + i, 4);
-          u &= 0x7fffffffu;
-          m = u > m ? u : m;
-        }
-        top[th] = m;
-      });
-      uint32_t m = 0;
-      for (uint32_t t : top) m = t > m ? t : m;
-      float f;
-      memcpy(&f, &m, 4);
-      if (m >= 0x7f800000u) finite = false;
-      else maxAny = std::max(maxAny, (double)f);
-      return m >= 0x7f800000u ? 0.0 : (double)f;
-    };
-    maxAbs = eat(sc->vertex_pos, 3 * (size_t)sc->n_vertices);
-    eat(sc->vertex_nrm, 3 * (size_t)sc->n_vertices);
-    eat(sc->camera.position, 12);
-    for (uint32_t l = 0; l < sc->n_lights; ++l) {
-      const rt_light& L = sc->lights[l];
-      eat(L.position, 15);
-      eat(&L.intensity, 6);
-      double pos = 0, ver = 0, hor = 0;
-      for (int a = 0; a < 3; ++a) pos += (double)L.position[a] * L.position[a], ver += (double)L.vertical[a] * L.vertical[a], hor += (double)L.horizontal[a] * L.horizontal[a];
-      maxLight = std::max(maxLight, std::sqrt(pos) + std::fabs((double)L.side) * (std::sqrt(ver) + std::sqrt(hor)));
-    }
-    const double edge = 2.0 * 1.7320508 * maxAbs, dir = 1.7320508 * maxAbs + maxLight + 2.0;
-    const double detBound = 1.01 * edge * edge * dir;
-    S.slowRecip = (finite && maxAny <= 1e14 && maxLight <= 1e14 && std::isfinite(detBound) && detBound < 1.2676506e30) ? 0u : 1u;
-    if (getenv("RT_SLOW_RECIP")) S.slowRecip = 1u;  // (A/B and the parity tests of the division path)
-    // ... and the device vouches for the short forms itself, once per process and device (2^25 inputs, well under a
-    // millisecond): the exhaustive check ran on one MI355X; a part whose v_rcp_f32 / v_rsq_f32 rounded differently would
-    // show here, and its contexts divide.
-    if (!S.slowRecip) {
-      static std::mutex mu;
-      static std::map<int, bool> verified;
-      std::lock_guard<std::mutex> lock(mu);
-      auto it = verified.find(c->device);
-      if (it == verified.end()) {
-        bool ok = false;
-        uint32_t* dBad = nullptr;
-        uint32_t bad = 1u;
-        if (hipMalloc(reinterpret_cast<void**>(&dBad), sizeof(uint32_t)) == hipSuccess) {
-          if (hipMemset(dBad, 0, sizeof(uint32_t)) == hipSuccess && rtk::launch_selfcheck_recip(dBad, nullptr) == hipSuccess &&
-              hipMemcpy(&bad, dBad, sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess)
-            ok = bad == 0u;
-          (void)hipFree(dBad);
-        }
-        it = verified.emplace(c->device, ok).first;
-        if (getenv("RT_BVH_VERBOSE")) fprintf(stderr, "short reciprocal / square root self-check on device %d: %s\n", c->device, ok ? "bit-identical" : "MISMATCH, dividing");
-      }
-      if (!it->second) S.slowRecip = 1u;
-      c->recipCheck = it->second ? 1u : 2u;
-    }
-  }
   const bool bigTree = S.n_nodes > 65536;
   S.leafT = getenv("RT_LEAFT") ? atoi(getenv("RT_LEAFT")) : bigTree ? 32 : 12;
   S.leafMul = getenv("RT_LEAFMUL") ? atoi(getenv("RT_LEAFMUL")) : bigTree ? 32 : 22;
@@ -712,31 +739,17 @@ int create_ctx(const rt_scene_desc* sc, const rt_options* opt, const rtbvh::Buil
   S.phPos = S.phDir = nullptr, S.phTopo = nullptr;
   S.topK = 0;
   S.cam = sc->camera;
-  {
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) == hipSuccess && cus > 0) c->numCUs = (uint32_t)cus;
-    if (hipMalloc(reinterpret_cast<void**>(&c->dTileCounter), sizeof(uint32_t)) != hipSuccess) {
-      rt_destroy(c);
-      return fail(RT_ERR_HIP, "tile counter allocation failed");
-    }
-    if (c->numCUs == 0) {
-      rt_destroy(c);
-      return fail(RT_ERR_HIP, "device %d reports no compute units", c->device);
-    }
-  }
+  int cus = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) == hipSuccess && cus > 0) c->numCUs = (uint32_t)cus;
+  if (dev_alloc(&c->dTileCounter, 1) != hipSuccess) return fail(RT_ERR_HIP, "tile counter allocation failed");
+  if (c->numCUs == 0) return fail(RT_ERR_HIP, "device %d reports no compute units", c->device);
   // (the counter block + 1,024 striped slots x 4 for the one-wave-per-workgroup kernels: rt_kernels.hip flush_stats_striped)
-  if (hipMalloc(reinterpret_cast<void**>(&c->dCounters), (RTK_CNT_COUNT + 4096) * sizeof(unsigned long long)) != hipSuccess ||
-      hipMemset(c->dCounters, 0, (RTK_CNT_COUNT + 4096) * sizeof(unsigned long long)) != hipSuccess) {
-    rt_destroy(c);
+  if (dev_alloc(&c->dCounters, RTK_CNT_COUNT + 4096) != hipSuccess ||
+      hipMemset(c->dCounters.get(), 0, (RTK_CNT_COUNT + 4096) * sizeof(unsigned long long)) != hipSuccess)
     return fail(RT_ERR_HIP, "counter allocation failed");
-  }
   for (auto& pr : c->ev)
-    if (hipEventCreate(&pr[0]) != hipSuccess || hipEventCreate(&pr[1]) != hipSuccess) {
-      rt_destroy(c);
-      return fail(RT_ERR_HIP, "event creation failed");
-    }
-  c->evReady = true;
-  *out = c;
+    if (make_event(&pr[0]) != hipSuccess || make_event(&pr[1]) != hipSuccess) return fail(RT_ERR_HIP, "event creation failed");
+  *out = c.release();
   return RT_OK;
 }
 }  // namespace
@@ -746,19 +759,6 @@ extern "C" {
 void rt_destroy(rt_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  for (void* p : c->allocs) (void)hipFree(p);
-  if (c->phPos) (void)hipFree(c->phPos);
-  if (c->phDir) (void)hipFree(c->phDir);
-  if (c->phTopo) (void)hipFree(c->phTopo);
-  if (c->dTiles) (void)hipFree(c->dTiles);
-  if (c->dCounters) (void)hipFree(c->dCounters);
-  if (c->dTileCounter) (void)hipFree(c->dTileCounter);
-  if (c->dNodesF) (void)hipFree(c->dNodesF);
-  if (c->wfBlock) (void)hipFree(c->wfBlock);
-  for (auto& kv : c->granules)
-    if (kv.second.d) (void)hipFree(kv.second.d);
-  if (c->evReady)
-    for (auto& pr : c->ev) (void)hipEventDestroy(pr[0]), (void)hipEventDestroy(pr[1]);
   delete c;
 }
 
@@ -767,36 +767,23 @@ int rt_set_photons(rt_ctx* c, const float* pos3, const float* dir3, uint32_t n) 
   if (n && (!pos3 || !dir3)) return fail(RT_ERR_INVALID, "photon arrays are null");
   if (n >= (1u << 30)) return fail(RT_ERR_UNSUPPORTED, "too many photons");
   HIP_TRY(hipSetDevice(c->device));
-  // the device scene forgets the old map BEFORE it is freed: a failed upload must leave
-  // "no photons" behind (check_params then refuses use_photons), never dangling pointers
-  c->S.phPos = c->S.phDir = nullptr, c->S.phTopo = nullptr, c->S.n_photons = 0;
-  float4 *oldP = c->phPos, *oldD = c->phDir;
-  uint4* oldT = c->phTopo;
-  c->phPos = c->phDir = nullptr, c->phTopo = nullptr;
-  if (oldP) HIP_TRY(hipFree(oldP));
-  if (oldD) HIP_TRY(hipFree(oldD));
-  if (oldT) HIP_TRY(hipFree(oldT));
+  int rc = drop_photons(c);
+  if (rc != RT_OK) return rc;
   std::vector<float4> p(n), d(n);
   for (uint32_t i = 0; i < n; ++i) {
     p[i] = make_float4(pos3[3 * (size_t)i], pos3[3 * (size_t)i + 1], pos3[3 * (size_t)i + 2], 0.f);
     d[i] = make_float4(dir3[3 * (size_t)i], dir3[3 * (size_t)i + 1], dir3[3 * (size_t)i + 2], 0.f);
   }
-  int rc = upload(&c->phPos, p.data(), n);
-  if (rc == RT_OK) rc = upload(&c->phDir, d.data(), n);
-  if (rc == RT_OK && n) {  // the arrays come in tree order (kdtree.h:60-69): the explicit topology follows from it
-    hipError_t he = hipMalloc(reinterpret_cast<void**>(&c->phTopo), 2 * (size_t)n * sizeof(uint4));
-    if (he == hipSuccess) he = rtk::launch_kd_topology(c->phPos, n, c->phTopo, nullptr);
+  DevBuf<float4> pos, dir;
+  DevBuf<uint4> topo;
+  if ((rc = upload(&pos, p.data(), n)) != RT_OK || (rc = upload(&dir, d.data(), n)) != RT_OK) return rc;
+  if (n) {  // the arrays come in tree order (kdtree.h:60-69): the explicit topology follows from it
+    hipError_t he = dev_alloc(&topo, 2 * (size_t)n);
+    if (he == hipSuccess) he = rtk::launch_kd_topology(pos.get(), n, topo.get(), nullptr);
     if (he == hipSuccess) he = hipDeviceSynchronize();
-    if (he != hipSuccess) rc = fail(RT_ERR_HIP, "photon topology failed: %s", hipGetErrorString(he));
+    if (he != hipSuccess) return fail(RT_ERR_HIP, "photon topology failed: %s", hipGetErrorString(he));
   }
-  if (rc != RT_OK) {  // drop whatever part of the map made it
-    if (c->phPos) (void)hipFree(c->phPos);
-    if (c->phDir) (void)hipFree(c->phDir);
-    if (c->phTopo) (void)hipFree(c->phTopo);
-    c->phPos = c->phDir = nullptr, c->phTopo = nullptr;
-    return rc;
-  }
-  c->S.phPos = c->phPos, c->S.phDir = c->phDir, c->S.phTopo = c->phTopo, c->S.n_photons = n;
+  install_photons(c, std::move(pos), std::move(dir), std::move(topo), n);
   return RT_OK;
 }
 
@@ -807,22 +794,16 @@ int rt_emit_photons(rt_ctx* c, uint32_t n_requested, uint32_t seed, float* pos3,
   if (n_requested == 0 || c->S.n_lights == 0) return RT_OK;
   if (!pos3 || !dir3) return fail(RT_ERR_INVALID, "output arrays are null");
   HIP_TRY(hipSetDevice(c->device));
-  // PhotonMap.h:19-20: lightPdf = 1.f / #lights; photonsPerLS = (int)(n * lightPdf)
-  const float lightPdf = 1.f / static_cast<float>(c->S.n_lights);
-  const uint32_t perLight = static_cast<uint32_t>(static_cast<int>(static_cast<float>(static_cast<int>(n_requested)) * lightPdf));
+  const uint32_t perLight = photons_per_light(n_requested, c->S.n_lights);
   const uint32_t n = perLight * c->S.n_lights;
   if (n == 0) return RT_OK;
-  float4 *dPos = nullptr, *dDir = nullptr;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&dPos), n * sizeof(float4)));
-  if (hipMalloc(reinterpret_cast<void**>(&dDir), n * sizeof(float4)) != hipSuccess) {
-    (void)hipFree(dPos);
-    return fail(RT_ERR_HIP, "photon buffer allocation failed");
-  }
-  hipError_t he = rtk::launch_emit(c->S, perLight, seed, dPos, dDir, c->dCounters, nullptr);
+  DevBuf<float4> dPos, dDir;
+  HIP_TRY(dev_alloc(&dPos, n));
+  if (dev_alloc(&dDir, n) != hipSuccess) return fail(RT_ERR_HIP, "photon buffer allocation failed");
+  hipError_t he = rtk::launch_emit(c->S, perLight, seed, dPos.get(), dDir.get(), c->dCounters.get(), nullptr);
   std::vector<float4> hp(n), hd(n);
-  if (he == hipSuccess) he = hipMemcpy(hp.data(), dPos, n * sizeof(float4), hipMemcpyDeviceToHost);
-  if (he == hipSuccess) he = hipMemcpy(hd.data(), dDir, n * sizeof(float4), hipMemcpyDeviceToHost);
-  (void)hipFree(dPos), (void)hipFree(dDir);
+  if (he == hipSuccess) he = hipMemcpy(hp.data(), dPos.get(), n * sizeof(float4), hipMemcpyDeviceToHost);
+  if (he == hipSuccess) he = hipMemcpy(hd.data(), dDir.get(), n * sizeof(float4), hipMemcpyDeviceToHost);
   if (he != hipSuccess) return fail(RT_ERR_HIP, "photon emission failed: %s", hipGetErrorString(he));
   uint32_t m = 0;
   for (uint32_t j = 0; j < n; ++j) {
@@ -842,7 +823,7 @@ int rt_render_device(rt_ctx* c, const rt_params* p, void* d_accum, void* stream,
   if (rc != RT_OK) return rc;
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (stats) HIP_TRY(hipMemsetAsync(c->dCounters, 0, RTK_CNT_COUNT * sizeof(unsigned long long), s));
+  if (stats) HIP_TRY(hipMemsetAsync(c->dCounters.get(), 0, RTK_CNT_COUNT * sizeof(unsigned long long), s));
   int e = 0;
   rc = launch_frame(c, p, static_cast<float4*>(d_accum), s, &e);
   if (rc != RT_OK) return rc;
@@ -852,19 +833,14 @@ int rt_render_device(rt_ctx* c, const rt_params* p, void* d_accum, void* stream,
     rc = read_counters(c, stats);
     if (rc != RT_OK) return rc;
     float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev[e][0], c->ev[e][1]));
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev[e][0].get(), c->ev[e][1].get()));
     stats->kernel_ms = ms;
-    const uint32_t n = p->spp_count ? p->spp_count : p->spp;
-    // samples of the tiles this rank owns
-    stats->samples = 0;
-    if (c->nTiles) {
-      uint64_t px = 0;
-      const uint32_t tile = c->tileKey.tile, world = c->tileKey.world;
-      for (uint32_t y = 0; y < p->height; ++y)
-        for (uint32_t x = 0; x < p->width; ++x)
-          if (world <= 1 || ((x / tile) + (y / tile)) % world == p->rank) ++px;
-      stats->samples = px * n;
-    }
+    // samples of the pixels this rank owns: its granules, clipped to the image
+    uint64_t px = 0;
+    owned_granules(p->width, p->height, p->rank, p->world, p->tile, [&](uint32_t x8, uint32_t y8) {
+      px += (uint64_t)std::min(8u, p->width - x8 * 8) * std::min(8u, p->height - y8 * 8);
+    });
+    stats->samples = px * (p->spp_count ? p->spp_count : p->spp);
   }
   return RT_OK;
 }
@@ -888,39 +864,26 @@ int rt_render(rt_ctx* c, const rt_params* p, const float* bg, float* out_rgb, fl
   if (out_rgb && !bg) return fail(RT_ERR_INVALID, "out_rgb requested without a background image");
   HIP_TRY(hipSetDevice(c->device));
   const size_t npx = (size_t)p->width * p->height;
-  float4* dAccum = nullptr;
-  float *dBg = nullptr, *dOut = nullptr;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&dAccum), npx * sizeof(float4)));
-  auto cleanup = [&]() {
-    (void)hipFree(dAccum);
-    if (dBg) (void)hipFree(dBg);
-    if (dOut) (void)hipFree(dOut);
-  };
-  hipError_t he = hipMemset(dAccum, 0, npx * sizeof(float4));
-  if (he != hipSuccess) {
-    cleanup();
-    return fail(RT_ERR_HIP, "memset failed: %s", hipGetErrorString(he));
-  }
+  DevBuf<float4> dAccum;
+  DevBuf<float> dBg, dOut;
+  HIP_TRY(dev_alloc(&dAccum, npx));
+  hipError_t he = hipMemset(dAccum.get(), 0, npx * sizeof(float4));
+  if (he != hipSuccess) return fail(RT_ERR_HIP, "memset failed: %s", hipGetErrorString(he));
   rt_stats local;
-  rc = rt_render_device(c, p, dAccum, nullptr, stats ? stats : &local);
-  if (rc != RT_OK) {
-    cleanup();
-    return rc;
-  }
+  rc = rt_render_device(c, p, dAccum.get(), nullptr, stats ? stats : &local);
+  if (rc != RT_OK) return rc;
   if (out_rgb) {
-    if ((he = hipMalloc(reinterpret_cast<void**>(&dBg), npx * 3 * sizeof(float))) == hipSuccess &&
-        (he = hipMalloc(reinterpret_cast<void**>(&dOut), npx * 3 * sizeof(float))) == hipSuccess &&
-        (he = hipMemcpy(dBg, bg, npx * 3 * sizeof(float), hipMemcpyHostToDevice)) == hipSuccess) {
-      rc = rt_resolve_device(c, p->width, p->height, p->spp, dAccum, dBg, dOut, nullptr);
-      if (rc == RT_OK) he = hipMemcpy(out_rgb, dOut, npx * 3 * sizeof(float), hipMemcpyDeviceToHost);
+    if ((he = dev_alloc(&dBg, npx * 3)) == hipSuccess && (he = dev_alloc(&dOut, npx * 3)) == hipSuccess &&
+        (he = hipMemcpy(dBg.get(), bg, npx * 3 * sizeof(float), hipMemcpyHostToDevice)) == hipSuccess) {
+      rc = rt_resolve_device(c, p->width, p->height, p->spp, dAccum.get(), dBg.get(), dOut.get(), nullptr);
+      if (rc == RT_OK) he = hipMemcpy(out_rgb, dOut.get(), npx * 3 * sizeof(float), hipMemcpyDeviceToHost);
     }
     if (rc == RT_OK && he != hipSuccess) rc = fail(RT_ERR_HIP, "resolve failed: %s", hipGetErrorString(he));
   }
   if (rc == RT_OK && accum_out) {
-    he = hipMemcpy(accum_out, dAccum, npx * sizeof(float4), hipMemcpyDeviceToHost);
+    he = hipMemcpy(accum_out, dAccum.get(), npx * sizeof(float4), hipMemcpyDeviceToHost);
     if (he != hipSuccess) rc = fail(RT_ERR_HIP, "accumulator read-back failed: %s", hipGetErrorString(he));
   }
-  cleanup();
   return rc;
 }
 
@@ -931,21 +894,18 @@ int rt_render_passes(rt_ctx* c, const rt_params* p, const float* bg, float* accu
   HIP_TRY(hipSetDevice(c->device));
   const size_t npx = (size_t)p->width * p->height;
   const uint32_t soFar = p->spp_count ? p->spp_begin + p->spp_count : p->spp;
-  float4* dAccum = nullptr;
-  float *dBg = nullptr, *dOut = nullptr;
-  hipError_t he = hipMalloc(reinterpret_cast<void**>(&dAccum), npx * sizeof(float4));
-  if (he == hipSuccess) he = hipMalloc(reinterpret_cast<void**>(&dBg), npx * 3 * sizeof(float));
-  if (he == hipSuccess) he = hipMalloc(reinterpret_cast<void**>(&dOut), npx * 3 * sizeof(float));
-  if (he == hipSuccess) he = hipMemcpy(dAccum, accum_io, npx * sizeof(float4), hipMemcpyHostToDevice);
-  if (he == hipSuccess) he = hipMemcpy(dBg, bg, npx * 3 * sizeof(float), hipMemcpyHostToDevice);
+  DevBuf<float4> dAccum;
+  DevBuf<float> dBg, dOut;
+  hipError_t he = dev_alloc(&dAccum, npx);
+  if (he == hipSuccess) he = dev_alloc(&dBg, npx * 3);
+  if (he == hipSuccess) he = dev_alloc(&dOut, npx * 3);
+  if (he == hipSuccess) he = hipMemcpy(dAccum.get(), accum_io, npx * sizeof(float4), hipMemcpyHostToDevice);
+  if (he == hipSuccess) he = hipMemcpy(dBg.get(), bg, npx * 3 * sizeof(float), hipMemcpyHostToDevice);
   rt_stats local;
-  if (he == hipSuccess) rc = rt_render_device(c, p, dAccum, nullptr, stats ? stats : &local);
-  if (he == hipSuccess && rc == RT_OK) rc = rt_resolve_device(c, p->width, p->height, soFar, dAccum, dBg, dOut, nullptr);
-  if (he == hipSuccess && rc == RT_OK) he = hipMemcpy(accum_io, dAccum, npx * sizeof(float4), hipMemcpyDeviceToHost);
-  if (he == hipSuccess && rc == RT_OK) he = hipMemcpy(out_rgb, dOut, npx * 3 * sizeof(float), hipMemcpyDeviceToHost);
-  if (dAccum) (void)hipFree(dAccum);
-  if (dBg) (void)hipFree(dBg);
-  if (dOut) (void)hipFree(dOut);
+  if (he == hipSuccess) rc = rt_render_device(c, p, dAccum.get(), nullptr, stats ? stats : &local);
+  if (he == hipSuccess && rc == RT_OK) rc = rt_resolve_device(c, p->width, p->height, soFar, dAccum.get(), dBg.get(), dOut.get(), nullptr);
+  if (he == hipSuccess && rc == RT_OK) he = hipMemcpy(accum_io, dAccum.get(), npx * sizeof(float4), hipMemcpyDeviceToHost);
+  if (he == hipSuccess && rc == RT_OK) he = hipMemcpy(out_rgb, dOut.get(), npx * 3 * sizeof(float), hipMemcpyDeviceToHost);
   if (he != hipSuccess) return fail(RT_ERR_HIP, "progressive render failed: %s", hipGetErrorString(he));
   return rc;
 }
@@ -954,19 +914,15 @@ int rt_trace(rt_ctx* c, const rt_ray* rays, uint32_t n, uint32_t accel, uint32_t
   if (!c || (n && (!rays || !hits))) return fail(RT_ERR_INVALID, "null argument");
   if (n == 0) return RT_OK;
   HIP_TRY(hipSetDevice(c->device));
-  rt_ray* dR = nullptr;
-  rt_hit* dH = nullptr;
+  DevBuf<rt_ray> dR;
+  DevBuf<rt_hit> dH;
   int rc = upload(&dR, rays, n);
   if (rc != RT_OK) return rc;
-  if (hipMalloc(reinterpret_cast<void**>(&dH), n * sizeof(rt_hit)) != hipSuccess) {
-    (void)hipFree(dR);
-    return fail(RT_ERR_HIP, "hit buffer allocation failed");
-  }
+  if (dev_alloc(&dH, n) != hipSuccess) return fail(RT_ERR_HIP, "hit buffer allocation failed");
   rtk::DevScene Su = c->S;
   Su.slowRecip = 1u;  // the caller's rays: any length
-  hipError_t he = rtk::launch_trace(accel == RT_ACCEL_BRUTE, kind == RT_TRACE_ANY, Su, dR, n, dH, c->dCounters, nullptr);
-  if (he == hipSuccess) he = hipMemcpy(hits, dH, n * sizeof(rt_hit), hipMemcpyDeviceToHost);
-  (void)hipFree(dR), (void)hipFree(dH);
+  hipError_t he = rtk::launch_trace(accel == RT_ACCEL_BRUTE, kind == RT_TRACE_ANY, Su, dR.get(), n, dH.get(), c->dCounters.get(), nullptr);
+  if (he == hipSuccess) he = hipMemcpy(hits, dH.get(), n * sizeof(rt_hit), hipMemcpyDeviceToHost);
   if (he != hipSuccess) return fail(RT_ERR_HIP, "trace failed: %s", hipGetErrorString(he));
   return RT_OK;
 }
@@ -978,24 +934,19 @@ int rt_knn(rt_ctx* c, const float* q3, uint32_t n, uint32_t k, uint32_t* idx, fl
   if (k > c->S.n_photons) return fail(RT_ERR_STATE, "k is greater than the number of nodes");  // kdtree.h:182-183
   if (n == 0) return RT_OK;
   HIP_TRY(hipSetDevice(c->device));
-  float* dQ = nullptr;
-  uint32_t *dI = nullptr, *dV = nullptr;
-  float* dD = nullptr;
+  DevBuf<float> dQ, dD;
+  DevBuf<uint32_t> dI, dV;
   int rc = upload(&dQ, q3, (size_t)n * 3);
   if (rc != RT_OK) return rc;
-  hipError_t he = hipMalloc(reinterpret_cast<void**>(&dI), (size_t)n * k * sizeof(uint32_t));
-  if (he == hipSuccess) he = hipMalloc(reinterpret_cast<void**>(&dD), (size_t)n * k * sizeof(float));
-  if (he == hipSuccess) he = hipMalloc(reinterpret_cast<void**>(&dV), (size_t)n * sizeof(uint32_t));
+  hipError_t he = dev_alloc(&dI, (size_t)n * k);
+  if (he == hipSuccess) he = dev_alloc(&dD, (size_t)n * k);
+  if (he == hipSuccess) he = dev_alloc(&dV, n);
   // the walk a photon frame runs, on the frame's layout when the BVH is shallower than the kd tree (the tightest one)
   const KdStack ks = kd_stack(c->S.n_photons);
-  if (he == hipSuccess) he = rtk::launch_knn(c->S, dQ, n, k, ks.kd16, stack_levels(ks.rows), dI, dD, dV, nullptr);
-  if (he == hipSuccess) he = hipMemcpy(idx, dI, (size_t)n * k * sizeof(uint32_t), hipMemcpyDeviceToHost);
-  if (he == hipSuccess) he = hipMemcpy(dist, dD, (size_t)n * k * sizeof(float), hipMemcpyDeviceToHost);
-  if (he == hipSuccess && visited) he = hipMemcpy(visited, dV, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost);
-  (void)hipFree(dQ);
-  if (dI) (void)hipFree(dI);
-  if (dD) (void)hipFree(dD);
-  if (dV) (void)hipFree(dV);
+  if (he == hipSuccess) he = rtk::launch_knn(c->S, dQ.get(), n, k, ks.kd16, stack_levels(ks.rows), dI.get(), dD.get(), dV.get(), nullptr);
+  if (he == hipSuccess) he = hipMemcpy(idx, dI.get(), (size_t)n * k * sizeof(uint32_t), hipMemcpyDeviceToHost);
+  if (he == hipSuccess) he = hipMemcpy(dist, dD.get(), (size_t)n * k * sizeof(float), hipMemcpyDeviceToHost);
+  if (he == hipSuccess && visited) he = hipMemcpy(visited, dV.get(), (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost);
   if (he != hipSuccess) return fail(RT_ERR_HIP, "knn failed: %s", hipGetErrorString(he));
   return RT_OK;
 }
@@ -1019,7 +970,7 @@ int rt_bvh_export(rt_ctx* c, void* nodes64, void* tris48) {
   if (!c) return fail(RT_ERR_INVALID, "ctx is null");
   if (c->builder != RT_BVH_HOST) {  // the arrays only exist on the device
     HIP_TRY(hipSetDevice(c->device));
-    if (nodes64) HIP_TRY(hipMemcpy(nodes64, c->dNodesF, (size_t)c->S.n_nodes * sizeof(rtbvh::Node), hipMemcpyDeviceToHost));
+    if (nodes64) HIP_TRY(hipMemcpy(nodes64, c->nodesF.get(), (size_t)c->S.n_nodes * sizeof(rtbvh::Node), hipMemcpyDeviceToHost));
     if (tris48) HIP_TRY(hipMemcpy(tris48, c->S.tris, (size_t)c->S.n_tris * sizeof(rtbvh::TriRec), hipMemcpyDeviceToHost));
     return RT_OK;
   }
@@ -1248,14 +1199,14 @@ int rt_bvh_tune(rt_ctx* c, const rt_params* probe, double budget_seconds, uint32
   if (rc != RT_OK) return rc;
   if (!(budget_seconds > 0)) return RT_OK;
   HIP_TRY(hipSetDevice(c->device));
-  float4* dAcc = nullptr;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&dAcc), (size_t)probe->width * probe->height * sizeof(float4)));
+  DevBuf<float4> dAcc;
+  HIP_TRY(dev_alloc(&dAcc, (size_t)probe->width * probe->height));
   rt_params p = *probe;
   p.collect_stats = 1;
   const size_t nodeBytes = c->bvh.nodes.size() * sizeof(rtbvh::Node16);
   std::string err;
   auto upload = [&]() -> bool {
-    if (hipMemcpy(const_cast<uint4*>(c->S.nodes), c->bvh.nodes16.data(), nodeBytes, hipMemcpyHostToDevice) != hipSuccess) {
+    if (hipMemcpy(c->nodes.get(), c->bvh.nodes16.data(), nodeBytes, hipMemcpyHostToDevice) != hipSuccess) {
       err = "node upload failed";
       return false;
     }
@@ -1265,12 +1216,12 @@ int rt_bvh_tune(rt_ctx* c, const rt_params* probe, double budget_seconds, uint32
     if (!err.empty()) return 1e300;
     rtbvh::packNodes(c->bvh);
     if (!upload()) return 1e300;
-    if (hipMemset(dAcc, 0, (size_t)p.width * p.height * sizeof(float4)) != hipSuccess) {
+    if (hipMemset(dAcc.get(), 0, (size_t)p.width * p.height * sizeof(float4)) != hipSuccess) {
       err = "probe accumulator reset failed";
       return 1e300;
     }
     rt_stats st;
-    if (rt_render_device(c, &p, dAcc, nullptr, &st) != RT_OK) {
+    if (rt_render_device(c, &p, dAcc.get(), nullptr, &st) != RT_OK) {
       err = std::string("probe render failed: ") + rt_last_error();
       return 1e300;
     }
@@ -1315,7 +1266,6 @@ int rt_bvh_tune(rt_ctx* c, const rt_params* probe, double budget_seconds, uint32
       err = e.what();
     }
     if (err.empty()) upload();
-    (void)hipFree(dAcc);
     if (!err.empty()) {  // not even that: the device tree is unknown, the context must not render again
       c->broken = true;
       return fail(RT_ERR_STATE, "rt_bvh_tune: %s; restoring the original tree failed too (%s): the context is unusable", why.c_str(), err.c_str());
@@ -1323,7 +1273,6 @@ int rt_bvh_tune(rt_ctx* c, const rt_params* probe, double budget_seconds, uint32
     return fail(RT_ERR_HIP, "rt_bvh_tune: %s (the original tree is back in place)", why.c_str());
   }
   upload();
-  (void)hipFree(dAcc);
   if (!err.empty()) {
     c->broken = true;
     return fail(RT_ERR_STATE, "rt_bvh_tune: %s: the context is unusable", err.c_str());
@@ -1346,7 +1295,7 @@ int rt_profile_collect(rt_ctx* c, double* total_ms, uint32_t* launches) {
   double sum = 0;
   for (int i = 0; i < n; ++i) {
     float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev[i][0], c->ev[i][1]));
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev[i][0].get(), c->ev[i][1].get()));
     sum += ms;
   }
   *total_ms = sum, *launches = static_cast<uint32_t>(n);
@@ -1361,15 +1310,13 @@ int rt_test_unit(int32_t device, uint32_t which, const void* in, void* out, uint
   if (n == 0) return RT_OK;
   int rc = select_device(device);
   if (rc != RT_OK) return rc;
-  void *dIn = nullptr, *dOut = nullptr;
-  HIP_TRY(hipMalloc(&dIn, (size_t)n * inBytes[which]));
-  hipError_t he = hipMalloc(&dOut, (size_t)n * outBytes[which]);
-  if (he == hipSuccess) he = hipMemcpy(dIn, in, (size_t)n * inBytes[which], hipMemcpyHostToDevice);
-  if (he == hipSuccess) he = hipMemcpy(dOut, out, (size_t)n * outBytes[which], hipMemcpyHostToDevice);
-  if (he == hipSuccess) he = rtk::launch_unit(which, dIn, dOut, n, nullptr);
-  if (he == hipSuccess) he = hipMemcpy(out, dOut, (size_t)n * outBytes[which], hipMemcpyDeviceToHost);
-  (void)hipFree(dIn);
-  if (dOut) (void)hipFree(dOut);
+  DevBuf<char> dIn, dOut;
+  HIP_TRY(dev_alloc(&dIn, (size_t)n * inBytes[which]));
+  hipError_t he = dev_alloc(&dOut, (size_t)n * outBytes[which]);
+  if (he == hipSuccess) he = hipMemcpy(dIn.get(), in, (size_t)n * inBytes[which], hipMemcpyHostToDevice);
+  if (he == hipSuccess) he = hipMemcpy(dOut.get(), out, (size_t)n * outBytes[which], hipMemcpyHostToDevice);
+  if (he == hipSuccess) he = rtk::launch_unit(which, dIn.get(), dOut.get(), n, nullptr);
+  if (he == hipSuccess) he = hipMemcpy(out, dOut.get(), (size_t)n * outBytes[which], hipMemcpyDeviceToHost);
   if (he != hipSuccess) return fail(RT_ERR_HIP, "unit kernel failed: %s", hipGetErrorString(he));
   return RT_OK;
 }
@@ -1382,7 +1329,7 @@ int rt_trace_stream_device(rt_ctx* c, const void* d_ray_o, const void* d_ray_d, 
   rtk::DevScene Su = c->S;
   Su.slowRecip = 1u;  // the caller's rays: any length
   hipError_t he = rtk::launch_trace_stream(Su, static_cast<const float4*>(d_ray_o), static_cast<const float4*>(d_ray_d), n,
-                                           static_cast<uint2*>(d_res), c->dTileCounter, levels, c->numCUs,
+                                           static_cast<uint2*>(d_res), c->dTileCounter.get(), levels, c->numCUs,
                                            static_cast<hipStream_t>(stream));
   if (he != hipSuccess) return fail(RT_ERR_HIP, "stream trace launch failed: %s", hipGetErrorString(he));
   return RT_OK;
@@ -1393,64 +1340,45 @@ int rt_build_photon_map(rt_ctx* c, uint32_t n_requested, uint32_t seed, uint32_t
   if (!c || !n_stored) return fail(RT_ERR_INVALID, "ctx/n_stored is null");
   *n_stored = 0;
   HIP_TRY(hipSetDevice(c->device));
-  // forget the old map first (see rt_set_photons)
-  c->S.phPos = c->S.phDir = nullptr, c->S.phTopo = nullptr, c->S.n_photons = 0;
-  if (c->phPos) (void)hipFree(c->phPos);
-  if (c->phDir) (void)hipFree(c->phDir);
-  if (c->phTopo) (void)hipFree(c->phTopo);
-  c->phPos = c->phDir = nullptr, c->phTopo = nullptr;
+  (void)drop_photons(c);  // forget the old map first (a failed free does not stop the new one)
   if (n_requested == 0 || c->S.n_lights == 0) return RT_OK;
-  const float lightPdf = 1.f / static_cast<float>(c->S.n_lights);  // PhotonMap.h:19-20
-  const uint32_t perLight = static_cast<uint32_t>(static_cast<int>(static_cast<float>(static_cast<int>(n_requested)) * lightPdf));
+  const uint32_t perLight = photons_per_light(n_requested, c->S.n_lights);
   const uint32_t n = perLight * c->S.n_lights;
   if (n == 0) return RT_OK;
-  float4 *slotPos = nullptr, *slotDir = nullptr, *items = nullptr, *phPos = nullptr, *phDir = nullptr;
-  uint4* phTopo = nullptr;
-  uint32_t* dCount = nullptr;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  auto cleanup = [&]() {
-    for (void* p : {(void*)slotPos, (void*)slotDir, (void*)items, (void*)dCount})
-      if (p) (void)hipFree(p);
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  };
-  hipError_t he = hipMalloc(reinterpret_cast<void**>(&slotPos), n * sizeof(float4));
-  if (he == hipSuccess) he = hipMalloc(reinterpret_cast<void**>(&slotDir), n * sizeof(float4));
-  if (he == hipSuccess) he = hipMalloc(reinterpret_cast<void**>(&items), n * sizeof(float4));
-  if (he == hipSuccess) he = hipMalloc(reinterpret_cast<void**>(&dCount), sizeof(uint32_t));
-  for (auto& e : ev)
-    if (he == hipSuccess) he = hipEventCreate(&e);
-  if (he == hipSuccess) he = hipEventRecord(ev[0], nullptr);
-  if (he == hipSuccess) he = rtk::launch_emit(c->S, perLight, seed, slotPos, slotDir, c->dCounters, nullptr);
-  if (he == hipSuccess) he = rtk::launch_photon_compact(slotPos, n, items, dCount, nullptr);
-  if (he == hipSuccess) he = hipEventRecord(ev[1], nullptr);
+  DevBuf<float4> slotPos, slotDir, items, phPos, phDir;
+  DevBuf<uint4> phTopo;
+  DevBuf<uint32_t> dCount;
+  Event ev[3];
+  hipError_t he = dev_alloc(&slotPos, n);
+  if (he == hipSuccess) he = dev_alloc(&slotDir, n);
+  if (he == hipSuccess) he = dev_alloc(&items, n);
+  if (he == hipSuccess) he = dev_alloc(&dCount, 1);
+  for (Event& e : ev)
+    if (he == hipSuccess) he = make_event(&e);
+  if (he == hipSuccess) he = hipEventRecord(ev[0].get(), nullptr);
+  if (he == hipSuccess) he = rtk::launch_emit(c->S, perLight, seed, slotPos.get(), slotDir.get(), c->dCounters.get(), nullptr);
+  if (he == hipSuccess) he = rtk::launch_photon_compact(slotPos.get(), n, items.get(), dCount.get(), nullptr);
+  if (he == hipSuccess) he = hipEventRecord(ev[1].get(), nullptr);
   uint32_t m = 0;
-  if (he == hipSuccess) he = hipMemcpy(&m, dCount, sizeof m, hipMemcpyDeviceToHost);  // (the count only)
+  if (he == hipSuccess) he = hipMemcpy(&m, dCount.get(), sizeof m, hipMemcpyDeviceToHost);  // (the count only)
   if (he == hipSuccess && m) {
-    he = rtk::launch_kd_build(items, m, -1, nullptr);
-    if (he == hipSuccess) he = hipMalloc(reinterpret_cast<void**>(&phPos), m * sizeof(float4));
-    if (he == hipSuccess) he = hipMalloc(reinterpret_cast<void**>(&phDir), m * sizeof(float4));
-    if (he == hipSuccess) he = hipMalloc(reinterpret_cast<void**>(&phTopo), 2 * (size_t)m * sizeof(uint4));
-    if (he == hipSuccess) he = rtk::launch_photon_gather(items, slotDir, m, phPos, phDir, nullptr, nullptr);
-    if (he == hipSuccess) he = rtk::launch_kd_topology(phPos, m, phTopo, nullptr);
+    he = rtk::launch_kd_build(items.get(), m, -1, nullptr);
+    if (he == hipSuccess) he = dev_alloc(&phPos, m);
+    if (he == hipSuccess) he = dev_alloc(&phDir, m);
+    if (he == hipSuccess) he = dev_alloc(&phTopo, 2 * (size_t)m);
+    if (he == hipSuccess) he = rtk::launch_photon_gather(items.get(), slotDir.get(), m, phPos.get(), phDir.get(), nullptr, nullptr);
+    if (he == hipSuccess) he = rtk::launch_kd_topology(phPos.get(), m, phTopo.get(), nullptr);
   }
-  if (he == hipSuccess) he = hipEventRecord(ev[2], nullptr);
+  if (he == hipSuccess) he = hipEventRecord(ev[2].get(), nullptr);
   if (he == hipSuccess) he = hipDeviceSynchronize();
-  if (he == hipSuccess && ms_out) {
+  if (he != hipSuccess) return fail(RT_ERR_HIP, "photon map build failed: %s", hipGetErrorString(he));
+  if (ms_out) {
     float a = 0.f, b = 0.f;
-    (void)hipEventElapsedTime(&a, ev[0], ev[1]);
-    (void)hipEventElapsedTime(&b, ev[1], ev[2]);
+    (void)hipEventElapsedTime(&a, ev[0].get(), ev[1].get());
+    (void)hipEventElapsedTime(&b, ev[1].get(), ev[2].get());
     ms_out[0] = a, ms_out[1] = b;  // emission + compaction, kd order + gather
   }
-  cleanup();
-  if (he != hipSuccess) {
-    if (phPos) (void)hipFree(phPos);
-    if (phDir) (void)hipFree(phDir);
-    if (phTopo) (void)hipFree(phTopo);
-    return fail(RT_ERR_HIP, "photon map build failed: %s", hipGetErrorString(he));
-  }
-  c->phPos = phPos, c->phDir = phDir, c->phTopo = phTopo;
-  c->S.phPos = phPos, c->S.phDir = phDir, c->S.phTopo = phTopo, c->S.n_photons = m;
+  install_photons(c, std::move(phPos), std::move(phDir), std::move(phTopo), m);
   *n_stored = m;
   return RT_OK;
 }
@@ -1463,8 +1391,8 @@ int rt_get_photons(rt_ctx* c, float* pos3, float* dir3, float* weight, uint32_t 
   if (cap < n) return fail(RT_ERR_INVALID, "capacity %u < %u photons", cap, n);
   HIP_TRY(hipSetDevice(c->device));
   std::vector<float4> p(n), d(n);
-  HIP_TRY(hipMemcpy(p.data(), c->phPos, n * sizeof(float4), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(d.data(), c->phDir, n * sizeof(float4), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(p.data(), c->phPos.get(), n * sizeof(float4), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(d.data(), c->phDir.get(), n * sizeof(float4), hipMemcpyDeviceToHost));
   for (uint32_t i = 0; i < n; ++i) {
     if (pos3) pos3[3 * (size_t)i] = p[i].x, pos3[3 * (size_t)i + 1] = p[i].y, pos3[3 * (size_t)i + 2] = p[i].z;
     if (dir3) dir3[3 * (size_t)i] = d[i].x, dir3[3 * (size_t)i + 1] = d[i].y, dir3[3 * (size_t)i + 2] = d[i].z;
@@ -1485,30 +1413,25 @@ int rt_test_kd_order(int32_t device, const float* pos3, uint32_t n, int32_t dept
     memcpy(&f, &bits, 4);
     h[i] = make_float4(pos3[3 * (size_t)i], pos3[3 * (size_t)i + 1], pos3[3 * (size_t)i + 2], f);
   }
-  float4 *items = nullptr, *scratch = nullptr;
-  uint32_t* dPerm = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
+  DevBuf<float4> items, scratch;
+  DevBuf<uint32_t> dPerm;
+  Event e0, e1;
   rc = upload(&items, h.data(), n);
   if (rc != RT_OK) return rc;
-  hipError_t he = hipMalloc(reinterpret_cast<void**>(&scratch), n * sizeof(float4));
-  if (he == hipSuccess) he = hipMalloc(reinterpret_cast<void**>(&dPerm), n * sizeof(uint32_t));
-  if (he == hipSuccess) he = hipEventCreate(&e0);
-  if (he == hipSuccess) he = hipEventCreate(&e1);
-  if (he == hipSuccess) he = hipEventRecord(e0, nullptr);
-  if (he == hipSuccess) he = rtk::launch_kd_build(items, n, depth_limit, nullptr);
-  if (he == hipSuccess) he = hipEventRecord(e1, nullptr);
-  if (he == hipSuccess) he = rtk::launch_photon_gather(items, nullptr, n, scratch, nullptr, dPerm, nullptr);
-  if (he == hipSuccess) he = hipMemcpy(perm_out, dPerm, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
+  hipError_t he = dev_alloc(&scratch, n);
+  if (he == hipSuccess) he = dev_alloc(&dPerm, n);
+  if (he == hipSuccess) he = make_event(&e0);
+  if (he == hipSuccess) he = make_event(&e1);
+  if (he == hipSuccess) he = hipEventRecord(e0.get(), nullptr);
+  if (he == hipSuccess) he = rtk::launch_kd_build(items.get(), n, depth_limit, nullptr);
+  if (he == hipSuccess) he = hipEventRecord(e1.get(), nullptr);
+  if (he == hipSuccess) he = rtk::launch_photon_gather(items.get(), nullptr, n, scratch.get(), nullptr, dPerm.get(), nullptr);
+  if (he == hipSuccess) he = hipMemcpy(perm_out, dPerm.get(), n * sizeof(uint32_t), hipMemcpyDeviceToHost);
   if (he == hipSuccess && ms_out) {
     float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventElapsedTime(&ms, e0.get(), e1.get());
     *ms_out = ms;
   }
-  (void)hipFree(items);
-  if (scratch) (void)hipFree(scratch);
-  if (dPerm) (void)hipFree(dPerm);
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
   if (he != hipSuccess) return fail(RT_ERR_HIP, "kd order failed: %s", hipGetErrorString(he));
   return RT_OK;
 }
@@ -1517,7 +1440,8 @@ int rt_test_kd_order(int32_t device, const float* pos3, uint32_t n, int32_t dept
 int rt_owned_granules(const rt_params* p, uint32_t rank, uint32_t* n_out) {
   if (!p || !n_out) return fail(RT_ERR_INVALID, "null argument");
   if (p->tile % 8 != 0) return fail(RT_ERR_INVALID, "tile must be a multiple of 8");
-  owned_granules(p->width, p->height, rank, p->world, p->tile, nullptr, n_out);
+  *n_out = 0;
+  owned_granules(p->width, p->height, rank, p->world, p->tile, [&](uint32_t, uint32_t) { ++*n_out; });
   return RT_OK;
 }
 
@@ -1525,10 +1449,10 @@ int rt_pack_owned_device(rt_ctx* c, const rt_params* p, const void* d_accum, voi
   if (!c || !p || !d_accum || !d_packed) return fail(RT_ERR_INVALID, "null argument");
   if (p->tile % 8 != 0 || (p->world > 1 && p->rank >= p->world)) return fail(RT_ERR_INVALID, "bad rank/world/tile");
   HIP_TRY(hipSetDevice(c->device));
-  rt_ctx::GranList L;
+  const rt_ctx::GranList* L = nullptr;
   int rc = ensure_granules(c, p, p->rank, &L);
   if (rc != RT_OK) return rc;
-  hipError_t he = rtk::launch_pack(false, static_cast<const float4*>(d_accum), static_cast<float4*>(d_packed), L.d, L.n, p->width,
+  hipError_t he = rtk::launch_pack(false, static_cast<const float4*>(d_accum), static_cast<float4*>(d_packed), L->d.get(), L->n, p->width,
                                    p->height, static_cast<hipStream_t>(stream));
   if (he != hipSuccess) return fail(RT_ERR_HIP, "pack launch failed: %s", hipGetErrorString(he));
   return RT_OK;
@@ -1538,10 +1462,10 @@ int rt_unpack_owned_device(rt_ctx* c, const rt_params* p, uint32_t from_rank, co
   if (!c || !p || !d_accum || !d_packed) return fail(RT_ERR_INVALID, "null argument");
   if (p->tile % 8 != 0 || from_rank >= (p->world ? p->world : 1)) return fail(RT_ERR_INVALID, "bad rank/world/tile");
   HIP_TRY(hipSetDevice(c->device));
-  rt_ctx::GranList L;
+  const rt_ctx::GranList* L = nullptr;
   int rc = ensure_granules(c, p, from_rank, &L);
   if (rc != RT_OK) return rc;
-  hipError_t he = rtk::launch_pack(true, static_cast<const float4*>(d_packed), static_cast<float4*>(d_accum), L.d, L.n, p->width,
+  hipError_t he = rtk::launch_pack(true, static_cast<const float4*>(d_packed), static_cast<float4*>(d_accum), L->d.get(), L->n, p->width,
                                    p->height, static_cast<hipStream_t>(stream));
   if (he != hipSuccess) return fail(RT_ERR_HIP, "unpack launch failed: %s", hipGetErrorString(he));
   return RT_OK;
@@ -1586,15 +1510,15 @@ Rccl g_rccl;
 struct rt_group {
   std::vector<rt_ctx*> ctx;
   std::vector<int> dev;
-  std::vector<hipStream_t> stream;
-  hipStream_t xstream = nullptr;  // device 0: receives and scatters the other ranks' granules beside rank 0's own render
-  hipEvent_t assembled = nullptr; // ... and tells stream[0] when the frame is whole
-  std::vector<hipEvent_t> packed_ready;
-  std::vector<float4*> accum;   // [rank] full frame on that rank's device
-  std::vector<float4*> packed;  // [rank] owned granules, on that rank's device (rank > 0)
-  std::vector<float4*> recv;    // [rank] the same bytes on device 0 (rank > 0)
+  std::vector<Stream> stream;
+  Stream xstream;   // device 0: receives and scatters the other ranks' granules beside rank 0's own render
+  Event assembled;  // ... and tells stream[0] when the frame is whole
+  std::vector<Event> packed_ready;
+  std::vector<DevBuf<float4>> accum;   // [rank] full frame on that rank's device
+  std::vector<DevBuf<float4>> packed;  // [rank] owned granules, on that rank's device (rank > 0)
+  std::vector<DevBuf<float4>> recv;    // [rank] the same bytes on device 0 (rank > 0)
   std::vector<ncclComm_t> comm; // RCCL communicators (all devices distinct), else empty: peer copies
-  float *dBg = nullptr, *dOut = nullptr;
+  DevBuf<float> dBg, dOut;
   size_t npx = 0;
   uint32_t fw = 0, fh = 0, ftile = 0;  // what the frame buffers are sized for
   uint32_t tile = 32;
@@ -1602,21 +1526,15 @@ struct rt_group {
 };
 
 namespace {
+// (each rank's resources are released with that rank's device current)
 void group_free_frame(rt_group* g) {
   for (size_t r = 0; r < g->ctx.size(); ++r) {
     (void)hipSetDevice(g->dev[r]);
-    if (g->accum[r]) (void)hipFree(g->accum[r]);
-    if (g->packed[r]) (void)hipFree(g->packed[r]);
-    g->accum[r] = g->packed[r] = nullptr;
+    g->accum[r].reset(), g->packed[r].reset();
   }
   (void)hipSetDevice(g->dev[0]);
-  for (auto& p : g->recv) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-  }
-  if (g->dBg) (void)hipFree(g->dBg);
-  if (g->dOut) (void)hipFree(g->dOut);
-  g->dBg = g->dOut = nullptr;
+  for (auto& p : g->recv) p.reset();
+  g->dBg.reset(), g->dOut.reset();
   g->npx = 0, g->fw = g->fh = g->ftile = 0;
 }
 }  // namespace
@@ -1627,61 +1545,47 @@ int rt_group_create(const rt_scene_desc* scene, const int32_t* devices, uint32_t
   if (!scene || !devices || !out || n == 0) return fail(RT_ERR_INVALID, "scene/devices/out is null or n == 0");
   if (n > 64) return fail(RT_ERR_INVALID, "at most 64 devices");
   *out = nullptr;
-  rt_group* g = new rt_group();
+  // (a failure below releases the group by rt_group_destroy, and the failing rank's own stream, event and context by
+  // scope: none of them touches the g_err message the caller reads)
+  std::unique_ptr<rt_group, void (*)(rt_group*)> g(new rt_group(), rt_group_destroy);
   bool distinct = true;
   for (uint32_t r = 0; r < n; ++r)
     for (uint32_t q = 0; q < r; ++q) distinct = distinct && devices[r] != devices[q];
-  // (sized before the first context exists: the failure path below runs rt_group_destroy ->
-  // group_free_frame, which walks these for every context created so far)
-  g->accum.assign(n, nullptr), g->packed.assign(n, nullptr), g->recv.assign(n, nullptr);
+  // (sized before the first context exists: rt_group_destroy -> group_free_frame walks these for every context so far)
+  g->accum.resize(n), g->packed.resize(n), g->recv.resize(n);
   for (uint32_t r = 0; r < n; ++r) {
     rt_options o{};
     if (opt) o = *opt;
     o.device = devices[r];
-    rt_ctx* c = nullptr;
+    rt_ctx* created = nullptr;
     // the host tree is built by the first context and copied by the others
     const rtbvh::Built* shared = (r > 0 && g->ctx[0]->builder == RT_BVH_HOST) ? &g->ctx[0]->bvh : nullptr;
-    int rc = create_ctx(scene, &o, shared, &c);
-    hipStream_t s = nullptr;
-    hipEvent_t e = nullptr;
-    if (rc == RT_OK && (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess ||
-                        hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess))
-      rc = fail(RT_ERR_HIP, "stream/event creation failed on device %d", devices[r]);
-    if (rc != RT_OK) {
-      const std::string keep = g_err;
-      // (the failing rank's own stream / event / context are not in the group yet)
-      if (s) (void)hipStreamDestroy(s);
-      if (e) (void)hipEventDestroy(e);
-      if (c) rt_destroy(c);
-      rt_group_destroy(g);
-      g_err = keep;
-      return rc;
-    }
-    g->ctx.push_back(c), g->dev.push_back(devices[r]), g->stream.push_back(s), g->packed_ready.push_back(e);
+    int rc = create_ctx(scene, &o, shared, &created);
+    if (rc != RT_OK) return rc;
+    std::unique_ptr<rt_ctx> c(created);  // (create_ctx left its device current)
+    Stream s;
+    Event e;
+    if (make_stream(&s) != hipSuccess || make_event(&e, hipEventDisableTiming) != hipSuccess)
+      return fail(RT_ERR_HIP, "stream/event creation failed on device %d", devices[r]);
+    g->ctx.push_back(c.release()), g->dev.push_back(devices[r]), g->stream.push_back(std::move(s)), g->packed_ready.push_back(std::move(e));
   }
   (void)hipSetDevice(g->dev[0]);
-  if (hipStreamCreateWithFlags(&g->xstream, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&g->assembled, hipEventDisableTiming) != hipSuccess) {
-    rt_group_destroy(g);
+  if (make_stream(&g->xstream) != hipSuccess || make_event(&g->assembled, hipEventDisableTiming) != hipSuccess)
     return fail(RT_ERR_HIP, "exchange stream creation failed on device %d", devices[0]);
-  }
   // exchange path: RCCL send/recv when every rank has its own device (ncclCommInitAll refuses
   // duplicates); ranks sharing a device (rehearsal on one GPU) use peer copies
   if (((n > 1 && distinct) || (n == 1 && getenv("RT_GROUP_FORCE_RCCL"))) && !getenv("RT_GROUP_NO_RCCL")) {
-    if (!g_rccl.load()) {
-      rt_group_destroy(g);
+    if (!g_rccl.load())
       return fail(RT_ERR_UNSUPPORTED, "librccl.so could not be loaded (%s); set RT_GROUP_NO_RCCL=1 for peer copies", dlerror());
-    }
     g->comm.assign(n, nullptr);
     ncclResult_t nr = g_rccl.CommInitAll(g->comm.data(), static_cast<int>(n), g->dev.data());
     if (nr != ncclSuccess) {
       g->comm.clear();
-      rt_group_destroy(g);
       return fail(RT_ERR_HIP, "ncclCommInitAll failed: %s", g_rccl.GetErrorString(nr));
     }
     g->rccl = true;
   }
-  *out = g;
+  *out = g.release();
   return RT_OK;
 }
 
@@ -1691,12 +1595,10 @@ void rt_group_destroy(rt_group* g) {
   for (ncclComm_t c : g->comm)
     if (c) (void)g_rccl.CommDestroy(c);
   if (!g->dev.empty()) (void)hipSetDevice(g->dev[0]);
-  if (g->xstream) (void)hipStreamDestroy(g->xstream);
-  if (g->assembled) (void)hipEventDestroy(g->assembled);
+  g->xstream.reset(), g->assembled.reset();
   for (size_t r = 0; r < g->ctx.size(); ++r) {
     (void)hipSetDevice(g->dev[r]);
-    if (g->stream[r]) (void)hipStreamDestroy(g->stream[r]);
-    if (g->packed_ready[r]) (void)hipEventDestroy(g->packed_ready[r]);
+    g->stream[r].reset(), g->packed_ready[r].reset();
     rt_destroy(g->ctx[r]);
   }
   delete g;
@@ -1725,19 +1627,19 @@ int rt_group_render(rt_group* g, const rt_params* p, const float* bg, float* out
   rt_params base = *p;
   base.world = n, base.tile = p->tile ? p->tile : g->tile;
   std::vector<uint32_t> cnt(n, 0);
-  for (uint32_t r = 0; r < n; ++r) owned_granules(p->width, p->height, r, n, base.tile, nullptr, &cnt[r]);
+  for (uint32_t r = 0; r < n; ++r) owned_granules(p->width, p->height, r, n, base.tile, [&](uint32_t, uint32_t) { ++cnt[r]; });
   if (p->width != g->fw || p->height != g->fh || base.tile != g->ftile) {  // frame buffers for this image size and sharding
     group_free_frame(g);
     for (uint32_t r = 0; r < n; ++r) {
       HIP_TRY(hipSetDevice(g->dev[r]));
-      HIP_TRY(hipMalloc(reinterpret_cast<void**>(&g->accum[r]), npx * sizeof(float4)));
-      if (r > 0 && cnt[r]) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&g->packed[r]), (size_t)cnt[r] * 64 * sizeof(float4)));
+      HIP_TRY(dev_alloc(&g->accum[r], npx));
+      if (r > 0 && cnt[r]) HIP_TRY(dev_alloc(&g->packed[r], (size_t)cnt[r] * 64));
     }
     HIP_TRY(hipSetDevice(g->dev[0]));
     for (uint32_t r = 1; r < n; ++r)
-      if (cnt[r]) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&g->recv[r]), (size_t)cnt[r] * 64 * sizeof(float4)));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&g->dBg), npx * 3 * sizeof(float)));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&g->dOut), npx * 3 * sizeof(float)));
+      if (cnt[r]) HIP_TRY(dev_alloc(&g->recv[r], (size_t)cnt[r] * 64));
+    HIP_TRY(dev_alloc(&g->dBg, npx * 3));
+    HIP_TRY(dev_alloc(&g->dOut, npx * 3));
     g->npx = npx, g->fw = p->width, g->fh = p->height, g->ftile = base.tile;
   }
   // 1. every rank integrates its tiles (asynchronously, each on its own device and stream)
@@ -1746,18 +1648,19 @@ int rt_group_render(rt_group* g, const rt_params* p, const float* bg, float* out
     rt_params pr = base;
     pr.rank = r;
     HIP_TRY(hipSetDevice(g->dev[r]));
-    HIP_TRY(hipMemsetAsync(g->accum[r], 0, npx * sizeof(float4), g->stream[r]));
+    hipStream_t s = g->stream[r].get();
+    HIP_TRY(hipMemsetAsync(g->accum[r].get(), 0, npx * sizeof(float4), s));
     if (r == 0) {  // the exchange stream scatters into this buffer: only after it has been zeroed
-      HIP_TRY(hipEventRecord(g->assembled, g->stream[0]));
-      HIP_TRY(hipStreamWaitEvent(g->xstream, g->assembled, 0));
+      HIP_TRY(hipEventRecord(g->assembled.get(), s));
+      HIP_TRY(hipStreamWaitEvent(g->xstream.get(), g->assembled.get(), 0));
     }
-    HIP_TRY(hipMemsetAsync(g->ctx[r]->dCounters, 0, RTK_CNT_COUNT * sizeof(unsigned long long), g->stream[r]));
-    rc = launch_frame(g->ctx[r], &pr, g->accum[r], g->stream[r], &ev[r]);
+    HIP_TRY(hipMemsetAsync(g->ctx[r]->dCounters.get(), 0, RTK_CNT_COUNT * sizeof(unsigned long long), s));
+    rc = launch_frame(g->ctx[r], &pr, g->accum[r].get(), s, &ev[r]);
     if (rc != RT_OK) return rc;
     if (r > 0 && cnt[r]) {
-      rc = rt_pack_owned_device(g->ctx[r], &pr, g->accum[r], g->packed[r], g->stream[r]);
+      rc = rt_pack_owned_device(g->ctx[r], &pr, g->accum[r].get(), g->packed[r].get(), s);
       if (rc != RT_OK) return rc;
-      HIP_TRY(hipEventRecord(g->packed_ready[r], g->stream[r]));
+      HIP_TRY(hipEventRecord(g->packed_ready[r].get(), s));
     }
   }
   // 2. owned granules travel to rank 0's device: 1/N of the frame per rank, nothing else.  Device 0
@@ -1768,8 +1671,8 @@ int rt_group_render(rt_group* g, const rt_params* p, const float* bg, float* out
     for (uint32_t r = 1; r < n && nr == ncclSuccess; ++r) {
       if (!cnt[r]) continue;
       const size_t floats = (size_t)cnt[r] * 64 * 4;
-      nr = g_rccl.Send(g->packed[r], floats, ncclFloat, 0, g->comm[r], g->stream[r]);
-      if (nr == ncclSuccess) nr = g_rccl.Recv(g->recv[r], floats, ncclFloat, static_cast<int>(r), g->comm[0], g->xstream);
+      nr = g_rccl.Send(g->packed[r].get(), floats, ncclFloat, 0, g->comm[r], g->stream[r].get());
+      if (nr == ncclSuccess) nr = g_rccl.Recv(g->recv[r].get(), floats, ncclFloat, static_cast<int>(r), g->comm[0], g->xstream.get());
     }
     const ncclResult_t ne = g_rccl.GroupEnd();
     if (nr == ncclSuccess) nr = ne;
@@ -1778,34 +1681,36 @@ int rt_group_render(rt_group* g, const rt_params* p, const float* bg, float* out
     HIP_TRY(hipSetDevice(g->dev[0]));
     for (uint32_t r = 1; r < n; ++r) {
       if (!cnt[r]) continue;
-      HIP_TRY(hipStreamWaitEvent(g->xstream, g->packed_ready[r], 0));
-      HIP_TRY(hipMemcpyPeerAsync(g->recv[r], g->dev[0], g->packed[r], g->dev[r], (size_t)cnt[r] * 64 * sizeof(float4), g->xstream));
+      HIP_TRY(hipStreamWaitEvent(g->xstream.get(), g->packed_ready[r].get(), 0));
+      HIP_TRY(hipMemcpyPeerAsync(g->recv[r].get(), g->dev[0], g->packed[r].get(), g->dev[r], (size_t)cnt[r] * 64 * sizeof(float4),
+                                 g->xstream.get()));
     }
   }
   // 3. rank 0 scatters them into its frame, resolves (Renderer.cpp:262-265) and hands the image back
   HIP_TRY(hipSetDevice(g->dev[0]));
   for (uint32_t r = 1; r < n; ++r) {
     if (!cnt[r]) continue;
-    rc = rt_unpack_owned_device(g->ctx[0], &base, r, g->recv[r], g->accum[0], g->xstream);
+    rc = rt_unpack_owned_device(g->ctx[0], &base, r, g->recv[r].get(), g->accum[0].get(), g->xstream.get());
     if (rc != RT_OK) return rc;
   }
-  HIP_TRY(hipEventRecord(g->assembled, g->xstream));
-  HIP_TRY(hipStreamWaitEvent(g->stream[0], g->assembled, 0));
+  hipStream_t s0 = g->stream[0].get();
+  HIP_TRY(hipEventRecord(g->assembled.get(), g->xstream.get()));
+  HIP_TRY(hipStreamWaitEvent(s0, g->assembled.get(), 0));
   hipError_t he = hipSuccess;
   if (out_rgb) {
-    he = hipMemcpyAsync(g->dBg, bg, npx * 3 * sizeof(float), hipMemcpyHostToDevice, g->stream[0]);
-    if (he == hipSuccess) rc = rt_resolve_device(g->ctx[0], p->width, p->height, p->spp, g->accum[0], g->dBg, g->dOut, g->stream[0]);
+    he = hipMemcpyAsync(g->dBg.get(), bg, npx * 3 * sizeof(float), hipMemcpyHostToDevice, s0);
+    if (he == hipSuccess) rc = rt_resolve_device(g->ctx[0], p->width, p->height, p->spp, g->accum[0].get(), g->dBg.get(), g->dOut.get(), s0);
     if (rc != RT_OK) return rc;
-    if (he == hipSuccess) he = hipMemcpyAsync(out_rgb, g->dOut, npx * 3 * sizeof(float), hipMemcpyDeviceToHost, g->stream[0]);
+    if (he == hipSuccess) he = hipMemcpyAsync(out_rgb, g->dOut.get(), npx * 3 * sizeof(float), hipMemcpyDeviceToHost, s0);
   }
-  if (he == hipSuccess && accum_out) he = hipMemcpyAsync(accum_out, g->accum[0], npx * sizeof(float4), hipMemcpyDeviceToHost, g->stream[0]);
+  if (he == hipSuccess && accum_out) he = hipMemcpyAsync(accum_out, g->accum[0].get(), npx * sizeof(float4), hipMemcpyDeviceToHost, s0);
   if (he != hipSuccess) return fail(RT_ERR_HIP, "frame read-back failed: %s", hipGetErrorString(he));
   for (uint32_t r = 0; r < n; ++r) {
     HIP_TRY(hipSetDevice(g->dev[r]));
-    HIP_TRY(hipStreamSynchronize(g->stream[r]));
+    HIP_TRY(hipStreamSynchronize(g->stream[r].get()));
   }
   HIP_TRY(hipSetDevice(g->dev[0]));
-  HIP_TRY(hipStreamSynchronize(g->xstream));
+  HIP_TRY(hipStreamSynchronize(g->xstream.get()));
   if (stats) {
     memset(stats, 0, sizeof *stats);
     for (uint32_t r = 0; r < n; ++r) {
@@ -1814,7 +1719,7 @@ int rt_group_render(rt_group* g, const rt_params* p, const float* bg, float* out
       rc = read_counters(g->ctx[r], &s);
       if (rc != RT_OK) return rc;
       float ms = 0.f;
-      HIP_TRY(hipEventElapsedTime(&ms, g->ctx[r]->ev[ev[r]][0], g->ctx[r]->ev[ev[r]][1]));
+      HIP_TRY(hipEventElapsedTime(&ms, g->ctx[r]->ev[ev[r]][0].get(), g->ctx[r]->ev[ev[r]][1].get()));
       stats->rays_closest += s.rays_closest, stats->rays_shadow += s.rays_shadow, stats->knn_queries += s.knn_queries;
       stats->nodes_visited += s.nodes_visited, stats->tris_tested += s.tris_tested, stats->kd_visited += s.kd_visited;
       stats->kernel_ms = ms > stats->kernel_ms ? ms : stats->kernel_ms;  // the slowest rank

@@ -10,6 +10,7 @@ import pytest
 
 import orc
 import pyrt
+from pyrt import dist as rdist
 
 pytestmark = pytest.mark.gpu
 
@@ -325,7 +326,10 @@ def test_frame_is_deterministic_and_split_invariant():
         ctx.render_device(q, acc.data_ptr(), torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
     assert np.array_equal(bits(acc.cpu().numpy()), bits(full))
-    for world, tile in ((2, 8), (3, 16), (5, 32)):
+    # (61 x 37: granules at the right and bottom edges are clipped to the image)
+    for w, h, world, tile in ((w, h, 2, 8), (w, h, 3, 16), (w, h, 5, 32), (61, 37, 3, 16)):
+        if full.shape[:2] != (h, w):
+            _, full, _ = ctx.render(pyrt.make_params(w, h, spp, seed=5))
         total = np.zeros((h, w, 4), np.float32)
         owned = np.zeros((h, w), np.int32)
         for r in range(world):
@@ -333,7 +337,8 @@ def test_frame_is_deterministic_and_split_invariant():
             _, part, st = ctx.render(q)
             owned += (part[..., :3].sum(-1) + part[..., 3] > 0)
             total += part  # adding zeros is exact
-        assert np.array_equal(bits(total), bits(full)), (world, tile)
+            assert st.samples == (rdist.owned_granule_index(w, h, r, world, tile) >= 0).sum() * spp, (w, h, world, tile, r)
+        assert np.array_equal(bits(total), bits(full)), (w, h, world, tile)
         assert owned.max() <= 1
     ctx.close()
 
