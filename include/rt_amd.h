@@ -15,7 +15,7 @@
  *   rt_render_device/_resolve_device : same, on caller-owned DEVICE buffers and a
  *                                  caller stream (multi-GPU tile sharding, bench)
  *   rt_trace                    <- RayTracer::rayTrace (RayTracer.h:27-53) test hook
- *   rt_knn                      <- kdtree::knearest (kdtree.h:180-195) test hook
+ *   rt_knn / rt_knn_wide        <- kdtree::knearest (kdtree.h:180-195) test hooks
  *
  * Conventions: plain C, int status (0 = RT_OK), caller-owned buffers, no C++
  * types or exceptions across the boundary, one host thread per context and ONE LAUNCH IN
@@ -35,6 +35,8 @@ extern "C" {
 #endif
 
 #define RT_ABI_VERSION 2
+/* largest photon-map k (rt_params.k, rt_knn_wide): the k-slot heap of a wave lives in LDS */
+#define RT_KNN_KMAX 256
 
 enum {
   RT_OK = 0,
@@ -116,7 +118,7 @@ typedef struct rt_params {
   uint32_t rng_mode;   /* RT_RNG_PIXEL                                         */
   uint32_t accel;      /* RT_ACCEL_*                                           */
   uint32_t use_photons;       /* 1: photon-map shading (Renderer.cpp:63-104)   */
-  uint32_t k;                 /* -k                                            */
+  uint32_t k;                 /* -k: 1..RT_KNN_KMAX (<= photons)               */
   uint32_t photons_requested; /* -p: density denominator (Renderer.cpp:99)     */
   uint32_t spp_begin, spp_count; /* sample sub-range of this call; 0,0 = all   */
   uint32_t rank, world;       /* tile ownership: this call renders the 8x8-pixel
@@ -279,10 +281,18 @@ int rt_trace_stream_device(rt_ctx* ctx, const void* d_ray_o, const void* d_ray_d
  * This is the walk photon frames run, on their layout: the same entry width (16-bit stack
  * entries below 65,535 photons) and the same stack rows as a frame whose BVH is shallower
  * than the kd tree (the tightest layout), with the k-slot heap directly above the stack.
- * k in 1..16 (else RT_ERR_UNSUPPORTED); an empty map or k > photons: RT_ERR_STATE. */
+ * k in 1..16 (else RT_ERR_UNSUPPORTED); an empty map or k > photons: RT_ERR_STATE.
+ * Photon frames with k above 16 run the wide walk: see rt_knn_wide. */
 int rt_knn(rt_ctx* ctx, const float* query3, uint32_t n, uint32_t k,
            uint32_t* idx_out /*[n][k]*/, float* dist_out /*[n][k]*/,
            uint32_t* visited_out /*[n] or NULL*/);
+/* rt_knn for k in 1..RT_KNN_KMAX (else RT_ERR_UNSUPPORTED; the same RT_ERR_STATE cases).
+ * k <= 16 runs rt_knn's instance and returns exactly what it returns; larger k run the
+ * walk photon frames with that k run, on their tightest layout (the wide k-heap's LDS
+ * layout, DESIGN.md "Photon k up to 256"). */
+int rt_knn_wide(rt_ctx* ctx, const float* query3, uint32_t n, uint32_t k,
+                uint32_t* idx_out /*[n][k]*/, float* dist_out /*[n][k]*/,
+                uint32_t* visited_out /*[n] or NULL*/);
 
 /* Inspection hooks for tests (host copies of the flattened acceleration data). */
 int rt_bvh_info_get(rt_ctx* ctx, rt_bvh_info* out);

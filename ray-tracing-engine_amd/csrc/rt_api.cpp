@@ -304,7 +304,7 @@ int check_params(const rt_ctx* c, const rt_params* p) {
     return fail(RT_ERR_INVALID, "sample range [%u,+%u) exceeds spp %u", p->spp_begin, p->spp_count, p->spp);
   if (p->use_photons) {
     if (c->S.n_photons == 0) return fail(RT_ERR_STATE, "use_photons set but no photons were uploaded (rt_set_photons)");
-    if (p->k < 1 || p->k > RTK_KMAX) return fail(RT_ERR_UNSUPPORTED, "k must be in 1..%d", RTK_KMAX);
+    if (p->k < 1 || p->k > RT_KNN_KMAX) return fail(RT_ERR_UNSUPPORTED, "k must be in 1..%d", RT_KNN_KMAX);
     // kdtree.h:182-183 throws std::logic_error here
     if (p->k > c->S.n_photons) return fail(RT_ERR_STATE, "k is greater than the number of nodes");
     if (p->photons_requested == 0) return fail(RT_ERR_INVALID, "photons_requested must be > 0 with use_photons");
@@ -927,10 +927,13 @@ int rt_trace(rt_ctx* c, const rt_ray* rays, uint32_t n, uint32_t accel, uint32_t
   return RT_OK;
 }
 
-int rt_knn(rt_ctx* c, const float* q3, uint32_t n, uint32_t k, uint32_t* idx, float* dist, uint32_t* visited) {
+// rt_knn (k in 1..RTK_KMAX) and rt_knn_wide (1..RT_KNN_KMAX) differ in the cap only: launch_knn_wide runs rt_knn's
+// instance for k <= RTK_KMAX
+static int knn_common(rt_ctx* c, const float* q3, uint32_t n, uint32_t k, uint32_t kmax, uint32_t* idx, float* dist,
+                      uint32_t* visited) {
   if (!c || (n && (!q3 || !idx || !dist))) return fail(RT_ERR_INVALID, "null argument");
   if (c->S.n_photons == 0) return fail(RT_ERR_STATE, "tree is empty");              // kdtree.h:181
-  if (k < 1 || k > RTK_KMAX) return fail(RT_ERR_UNSUPPORTED, "k must be in 1..%d", RTK_KMAX);
+  if (k < 1 || k > kmax) return fail(RT_ERR_UNSUPPORTED, "k must be in 1..%u", kmax);
   if (k > c->S.n_photons) return fail(RT_ERR_STATE, "k is greater than the number of nodes");  // kdtree.h:182-183
   if (n == 0) return RT_OK;
   HIP_TRY(hipSetDevice(c->device));
@@ -943,12 +946,20 @@ int rt_knn(rt_ctx* c, const float* q3, uint32_t n, uint32_t k, uint32_t* idx, fl
   if (he == hipSuccess) he = dev_alloc(&dV, n);
   // the walk a photon frame runs, on the frame's layout when the BVH is shallower than the kd tree (the tightest one)
   const KdStack ks = kd_stack(c->S.n_photons);
-  if (he == hipSuccess) he = rtk::launch_knn(c->S, dQ.get(), n, k, ks.kd16, stack_levels(ks.rows), dI.get(), dD.get(), dV.get(), nullptr);
+  if (he == hipSuccess) he = rtk::launch_knn_wide(c->S, dQ.get(), n, k, ks.kd16, stack_levels(ks.rows), dI.get(), dD.get(), dV.get(), nullptr);
   if (he == hipSuccess) he = hipMemcpy(idx, dI.get(), (size_t)n * k * sizeof(uint32_t), hipMemcpyDeviceToHost);
   if (he == hipSuccess) he = hipMemcpy(dist, dD.get(), (size_t)n * k * sizeof(float), hipMemcpyDeviceToHost);
   if (he == hipSuccess && visited) he = hipMemcpy(visited, dV.get(), (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost);
   if (he != hipSuccess) return fail(RT_ERR_HIP, "knn failed: %s", hipGetErrorString(he));
   return RT_OK;
+}
+
+int rt_knn(rt_ctx* c, const float* q3, uint32_t n, uint32_t k, uint32_t* idx, float* dist, uint32_t* visited) {
+  return knn_common(c, q3, n, k, RTK_KMAX, idx, dist, visited);
+}
+
+int rt_knn_wide(rt_ctx* c, const float* q3, uint32_t n, uint32_t k, uint32_t* idx, float* dist, uint32_t* visited) {
+  return knn_common(c, q3, n, k, RT_KNN_KMAX, idx, dist, visited);
 }
 
 int rt_bvh_info_get(rt_ctx* c, rt_bvh_info* out) {

@@ -9,7 +9,8 @@
 #include "rt_amd.h"
 #include "rt_device.h"
 
-#define RTK_KMAX 16  // photon k-heap slots per lane (LDS budget, rt_kernels.hip)
+#define RTK_KMAX 16  // photon k-heap slots per lane of k_render / k_knn (LDS budget, rt_kernels.hip); up to RT_KNN_KMAX
+                     // (rt_amd.h) the wide instances k_render_wide / k_knn_wide serve
 
 enum {
   RTK_CNT_CLOSEST = 0,
@@ -111,6 +112,9 @@ hipError_t launch_trace(bool brute_force, bool any, const DevScene& S, const rt_
 // the photon frames' k-NN walk (knn_query<kd16>) on their layout: stackLevels rows of LDS stack, the k-slot heap above
 hipError_t launch_knn(const DevScene& S, const float* q, uint32_t n, uint32_t k, bool kd16, uint32_t stackLevels,
                       uint32_t* idx, float* dist, uint32_t* visited, hipStream_t stream);
+// the same for k in 1..RT_KNN_KMAX: k <= RTK_KMAX runs launch_knn's instance, larger k the wide frames' walk on their layout
+hipError_t launch_knn_wide(const DevScene& S, const float* q, uint32_t n, uint32_t k, bool kd16, uint32_t stackLevels,
+                           uint32_t* idx, float* dist, uint32_t* visited, hipStream_t stream);
 hipError_t launch_emit(const DevScene& S, uint32_t perLight, uint32_t seed, float4* outPos, float4* outDir,
                        unsigned long long* counters, hipStream_t stream);
 // scene BVH on the device (bvh_gpu.hip): arrays are hipMalloc'ed by the builder, owned by the caller

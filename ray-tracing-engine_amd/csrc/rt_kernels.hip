@@ -25,6 +25,7 @@
 // Built with -ffp-contract=off (bit parity with the x86-64 oracle, no FMA).
 #include <hip/hip_runtime.h>
 
+#include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 
@@ -549,13 +550,48 @@ RT_DEV f3 interp3(const float* arr, uint4 tv, float w, float u, float v) {
 // std::make_heap/pop_heap/push_heap/sort_heap are restated from libstdc++
 // (bits/stl_heap.h: __push_heap / __adjust_heap) because result ORDER feeds a
 // float sum (Renderer.cpp:93-96).
-struct Heap {
+// The entry accessors of a layout; HeapOps is the heap on top of them.
+struct HeapInterleaved {
   uint2* e;  // [slot * BLOCK]: {distance bits, photon index} in one 8-byte word (one LDS op per move)
   RT_DEV float D(int s) const { return __uint_as_float(e[s * BLOCK].x); }
   RT_DEV uint32_t I(int s) const { return e[s * BLOCK].y; }
   RT_DEV void set(int s, float dv, uint32_t iv) const { e[s * BLOCK] = make_uint2(__float_as_uint(dv), iv); }
   RT_DEV void move(int dst, int src) const { e[dst * BLOCK] = e[src * BLOCK]; }
+  // the heap of a lane whose Lds was carved for k slots (carve_lds puts it there)
+  RT_DEV static HeapInterleaved at(const Lds& L, int) { return HeapInterleaved{L.heap}; }
+};
 
+// The wide k-NN (17 <= k <= RT_KNN_KMAX: k_render_wide, k_knn_wide) runs the same heap on one of two layouts
+// (launcher: wide_layout):
+//   HEAP_WIDE8:   the interleaved 8-byte entries above (one LDS op per move);
+//   HEAP_SPLIT16: a plane of float distances [k][64], then a plane of 16-bit indices [k][64] (maps of fewer than
+//                 65,535 photons, the rule kd_stack applies to the walk's stack): 6 bytes per slot, two ops per move.
+enum { HEAP_WIDE8 = 0, HEAP_SPLIT16 = 1 };
+template <int HL>
+struct HeapPlanes {
+  static_assert(HL == HEAP_SPLIT16, "the planes hold 16-bit indices");
+  using Idx = uint16_t;
+  float* d;  // [slot * BLOCK]
+  Idx* i;    // [slot * BLOCK]
+  RT_DEV float D(int s) const { return d[s * BLOCK]; }
+  RT_DEV uint32_t I(int s) const { return i[s * BLOCK]; }
+  RT_DEV void set(int s, float dv, uint32_t iv) const { d[s * BLOCK] = dv, i[s * BLOCK] = (Idx)iv; }
+  RT_DEV void move(int dst, int src) const { d[dst * BLOCK] = d[src * BLOCK], i[dst * BLOCK] = i[src * BLOCK]; }
+  // (carve_lds points a lane at its column of the heap region: the region starts 2 words per lane below)
+  RT_DEV static HeapPlanes at(const Lds& L, int k) {
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t* region = reinterpret_cast<uint32_t*>(L.heap - lane);
+    return HeapPlanes{reinterpret_cast<float*>(region) + lane, reinterpret_cast<Idx*>(region + (size_t)k * BLOCK) + lane};
+  }
+};
+
+template <class E>
+struct HeapOps : E {
+  using E::D;
+  using E::I;
+  using E::set;
+  using E::move;
+  RT_DEV static HeapOps at(const Lds& L, int k) { return HeapOps{E::at(L, k)}; }
   RT_DEV void push_up(int hole, int top, float vd, uint32_t vi) const {
     int parent = (hole - 1) / 2;
     while (hole > top && D(parent) < vd) {
@@ -604,6 +640,11 @@ struct Heap {
     }
   }
 };
+using Heap = HeapOps<HeapInterleaved>;  // k <= 16 (k_render, k_knn)
+template <int HL>
+using WideHeap = HeapOps<typename std::conditional<HL == HEAP_WIDE8, HeapInterleaved, HeapPlanes<HL>>::type>;
+// LDS rows (64 words) of a k-slot heap on layout HL
+constexpr uint32_t heap_rows(int hl, uint32_t k) { return hl == HEAP_SPLIT16 ? k + (k + 1u) / 2u : 2u * k; }
 
 RT_DEV float photon_dist(const DevScene& S, uint32_t n, f3 p, float4& pos) {
   pos = S.phPos[n];
@@ -632,8 +673,8 @@ RT_DEV float photon_dist(const DevScene& S, uint32_t n, f3 p, float4& pos) {
 // S16: the pending far children as 16-bit indices (maps of fewer than 65,535 photons: config 3's 35,744): half the stack's LDS,
 // which with the k-heap is what caps the photon kernel's waves per CU.
 constexpr uint32_t KD_NONE = 0x3fffffffu;
-template <bool S16>
-RT_DEV uint32_t knn_query(const DevScene& S, f3 p, int k, const Heap& H, uint32_t* stack) {
+template <bool S16, class HP>
+RT_DEV uint32_t knn_query(const DevScene& S, f3 p, int k, const HP& H, uint32_t* stack) {
   using Entry = typename std::conditional<S16, uint16_t, uint32_t>::type;
   constexpr uint32_t NONE_E = S16 ? 0xffffu : KD_NONE;
   float4 pos;
@@ -740,12 +781,12 @@ RT_DEV void vertex_setup_ray(const DevScene& S, uint32_t id, f3 o, f3 d, f3& hit
   mesh = tv.w;
 }
 
-// Renderer.cpp:63-104: photon-map radiance estimate at the vertex
-template <bool STATS>
+// Renderer.cpp:63-104: photon-map radiance estimate at the vertex (HP: the heap's layout, WideHeap for k > 16)
+template <bool STATS, class HP = Heap>
 RT_DEV f3 shade_photon(const DevScene& S, const RenderArgs& A, f3 rayDir, const HitRec& h, const Lds& L, f3 hitNormal,
                        f3 point, LaneStats& st) {
   const rt_material mat = S.mats[h.mesh];
-  const Heap H{L.heap};
+  const HP H = HP::at(L, (int)A.k);
   const int k = (int)A.k;
   st.knn++;
   const uint32_t vis = A.kd16 ? knn_query<true>(S, point, k, H, L.stack) : knn_query<false>(S, point, k, H, L.stack);
@@ -1132,7 +1173,7 @@ RT_DEV Lds carve_lds(uint32_t* base, uint32_t levels = STACK, uint32_t kslots = 
 // One wave tile: lane = (pixel pl of the tile, sample slot sj).  The wave integrates
 // S = 1 << sshift consecutive samples of P = 64 >> sshift pixels side by side.
 
-template <bool BRUTE, bool PHOTON, bool POOLED, bool STATS, int LT>
+template <bool BRUTE, bool PHOTON, bool POOLED, bool STATS, int LT, class HP = Heap>
 RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restrict__ accum, const Lds& L, uint32_t* pool,
                         float* ex, uint32_t wave, LaneStats& st) {
   constexpr bool FR = (LT & LT_FASTDET) != 0;  // 1 / length by rtd::recip_fast (see rtd::unit3)
@@ -1202,7 +1243,7 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
       f3 nrm = mk(0.f, 0.f, 0.f), pt = nrm, c = nrm;
       if (alive) vertex_setup<FR>(S, h, nrm, pt);
       if (PHOTON) {
-        if (alive) c = shade_photon<STATS>(S, A, d, h, L, nrm, pt, st);
+        if (alive) c = shade_photon<STATS, HP>(S, A, d, h, L, nrm, pt, st);
       } else {
         if (alive) c = shade_direct_seq<BRUTE, STATS>(S, g, d, h, L.stack, nrm, pt, st);
       }
@@ -1267,6 +1308,23 @@ __global__ __launch_bounds__(BLOCK, MINW) void k_render(DevScene S, RenderArgs A
   for (uint32_t t = t0; t < t1; ++t) render_tile<BRUTE, PHOTON, POOLED, STATS, LT_NONE>(S, A, accum, L, pool, ex, t, st);
   if (STATS) flush_stats(st, counters, true);
   else flush_stats_striped(st, counters);  // (launch_render2 folds the stripes)
+}
+
+// Photon frames with 17 <= k <= RT_KNN_KMAX: k_render's photon path with the k-heap on layout HL (heap_rows(HL, k) rows
+// above the stack rows).  LDS, not registers, sets these kernels' waves (a k-slot heap is 6 or 8 x 64 x k bytes per
+// wave): MINW is the occupancy the smallest of them reaches, so the walk has every register it can use.
+template <bool BRUTE, bool STATS, int MINW, int HL>
+__global__ __launch_bounds__(BLOCK, MINW) void k_render_wide(DevScene S, RenderArgs A, float4* __restrict__ accum,
+                                                          unsigned long long* __restrict__ counters) {
+  uint32_t* lds = g_lds;
+  const Lds L = carve_lds<true>(lds, A.stackLevels, A.k);
+  float* ex = reinterpret_cast<float*>(lds);  // (the first four stack rows, idle when a sample is handed over)
+  LaneStats st;
+  const uint32_t t0 = blockIdx.x * A.tilesPerBlock, t1 = min(A.n_tiles, t0 + A.tilesPerBlock);
+  for (uint32_t t = t0; t < t1; ++t)
+    render_tile<BRUTE, true, false, STATS, LT_NONE, WideHeap<HL>>(S, A, accum, L, nullptr, ex, t, st);
+  if (STATS) flush_stats(st, counters, true);
+  else flush_stats_striped(st, counters);
 }
 
 // The pooled integrator as PERSISTENT workgroups: one workgroup of up to 16 waves per CU
@@ -1486,6 +1544,23 @@ __global__ __launch_bounds__(BLOCK) void k_knn(DevScene S, const float* __restri
   const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
   if (i >= n) return;
   const Heap H{L.heap};
+  const uint32_t vis = knn_query<S16>(S, ld(q + 3 * (size_t)i), (int)k, H, L.stack);
+  for (uint32_t j = 0; j < k; j++) {
+    idx[(size_t)i * k + j] = H.I((int)j);
+    dst[(size_t)i * k + j] = H.D((int)j);
+  }
+  if (visited) visited[i] = vis;
+}
+
+// The wide frames' walk (k_render_wide) on their layout: the k-slot heap on layout HL above the stack rows.
+template <bool S16, int MINW, int HL>
+__global__ __launch_bounds__(BLOCK, MINW) void k_knn_wide(DevScene S, const float* __restrict__ q, uint32_t n, uint32_t k,
+                                                       uint32_t stackLevels, uint32_t* __restrict__ idx,
+                                                       float* __restrict__ dst, uint32_t* __restrict__ visited) {
+  const Lds L = carve_lds<true>(g_lds, stackLevels, k);
+  const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= n) return;
+  const WideHeap<HL> H = WideHeap<HL>::at(L, (int)k);
   const uint32_t vis = knn_query<S16>(S, ld(q + 3 * (size_t)i), (int)k, H, L.stack);
   for (uint32_t j = 0; j < k; j++) {
     idx[(size_t)i * k + j] = H.I((int)j);
@@ -1736,6 +1811,66 @@ static PersistPlan plan_persist(const DevScene& S, const RenderArgs& A) {
   return PersistPlan{w, k, waveWords, 4u * (8u * k + w * waveWords)};
 }
 
+// The wide k-heap's layout (DESIGN.md "Photon k up to 256"; measured on config 3's frame at k = 17 .. 256): the 6-byte
+// split planes where the indices fit in 16 bits (kd16: fewer than 65,535 photons) AND they give the CU more waves than
+// the 8-byte entries — 11.65 / 28.2 / 99.8 / 307 ms against 12.4 / 33.2 / 116.9 / 425 ms at k = 17 / 32 / 64 / 128;
+// at equal waves the interleaved entries' one LDS op per move wins (k = 256, one wave per CU either way: 1593 against
+// 1686 ms).  RT_KNN_WIDE_LAYOUT=8 / 16 forces a layout (16: where the indices fit; tools/knn_wide_bench.py's A/B).
+static int wide_layout(bool kd16, uint32_t stackLevels, uint32_t k) {
+  static const int forced = getenv("RT_KNN_WIDE_LAYOUT") ? atoi(getenv("RT_KNN_WIDE_LAYOUT")) : 0;
+  if (!kd16 || forced == 8) return HEAP_WIDE8;
+  if (forced == 16) return HEAP_SPLIT16;
+  const uint32_t cu = rtbvh::kLdsWordsPerCU / BLOCK;  // LDS rows per CU
+  return cu / (stackLevels + heap_rows(HEAP_SPLIT16, k)) > cu / (stackLevels + heap_rows(HEAP_WIDE8, k)) ? HEAP_SPLIT16
+                                                                                                        : HEAP_WIDE8;
+}
+// Occupancy target (waves per SIMD) of the timed wide instances: what k = 17 reaches on config 3's layout (split planes,
+// 10 stack rows + 26 heap rows: 16 waves per CU); larger k hold fewer waves, bound by LDS
+constexpr int MINW_WIDE = 4;
+
+// RT_KNN_VERBOSE: one line on stderr per photon-frame or wide k-NN launch — the instance, its heap layout (-1: k_render's),
+// its LDS per wave and the waves per CU the runtime reports for it (tools/knn_wide_bench.py)
+template <class K>
+static void knn_report(K kernel, const char* name, int hl, uint32_t k, size_t ldsBytes) {
+  static const bool verbose = getenv("RT_KNN_VERBOSE") != nullptr;
+  if (!verbose) return;
+  int blocks = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, kernel, BLOCK, ldsBytes) != hipSuccess) blocks = -1;
+  fprintf(stderr, "{\"knn_kernel\": \"%s\", \"layout\": %d, \"k\": %u, \"lds_bytes\": %zu, \"waves_per_cu\": %d}\n", name, hl, k,
+          ldsBytes, blocks);
+}
+
+template <bool BRUTE>
+static hipError_t launch_render_wide(bool stats, const DevScene& S, const RenderArgs& A, float4* accum,
+                                     unsigned long long* counters, hipStream_t stream) {
+  const int hl = wide_layout(A.kd16 != 0, A.stackLevels, A.k);
+  const size_t ldsBytes = 4u * (size_t)(A.stackLevels + heap_rows(hl, A.k)) * BLOCK;
+  if (A.k > (uint32_t)RT_KNN_KMAX || ldsBytes > 4u * (size_t)rtbvh::kLdsWordsPerCU) return hipErrorInvalidValue;
+  RenderArgs A1 = A;
+  A1.tilesPerBlock = 1u;
+#define RT_LAUNCH_WIDE(ST, MW, HLV)                                                                               \
+  do {                                                                                                            \
+    static unsigned long long done = 0;                                                                           \
+    if (!allow_big_lds(&k_render_wide<BRUTE, ST, MW, HLV>, done)) return hipErrorInvalidConfiguration;            \
+    knn_report(k_render_wide<BRUTE, ST, MW, HLV>, "k_render_wide", HLV, A.k, ldsBytes);                          \
+    hipLaunchKernelGGL((k_render_wide<BRUTE, ST, MW, HLV>), dim3(A.n_tiles), dim3(BLOCK), ldsBytes, stream, S, A1, \
+                       accum, counters);                                                                          \
+  } while (0)
+#define RT_LAUNCH_WIDE_HL(ST, MW)                                   \
+  do {                                                              \
+    if (hl == HEAP_SPLIT16) RT_LAUNCH_WIDE(ST, MW, HEAP_SPLIT16);   \
+    else RT_LAUNCH_WIDE(ST, MW, HEAP_WIDE8);                        \
+  } while (0)
+  if (stats) RT_LAUNCH_WIDE_HL(true, 1);
+  else {
+    RT_LAUNCH_WIDE_HL(false, MINW_WIDE);
+    hipLaunchKernelGGL(k_fold_stripes, dim3(1), dim3(1024), 0, stream, counters);
+  }
+#undef RT_LAUNCH_WIDE_HL
+#undef RT_LAUNCH_WIDE
+  return hipGetLastError();
+}
+
 template <bool BRUTE, bool PHOTON, bool POOLED>
 static hipError_t launch_render2(bool stats, const DevScene& S, const RenderArgs& A, float4* accum,
                                  unsigned long long* counters, hipStream_t stream) {
@@ -1793,6 +1928,7 @@ static hipError_t launch_render2(bool stats, const DevScene& S, const RenderArgs
       return hipGetLastError();
     }
   }
+  if (PHOTON && A.k > (uint32_t)KMAX) return launch_render_wide<BRUTE>(stats, S, A, accum, counters, stream);
   const uint32_t rows = A.stackLevels + (PHOTON ? 2 * A.k : 0);
   const size_t ldsBytes = 4u * ((rows < 4u ? 4u : rows) * BLOCK + (POOLED ? VP_WORDS : 0));
   RenderArgs A1 = A;
@@ -1802,6 +1938,8 @@ static hipError_t launch_render2(bool stats, const DevScene& S, const RenderArgs
   // (the photon kernel at 5 waves per SIMD: its walk waits on L1-hit loads half of its life; 96 VGPRs cost 12 spilled registers
   // outside the walk, and the 16-bit stack makes the LDS room — measured: C3 7.3 -> see DESIGN.md 4.6)
   constexpr int MINW = PHOTON ? 5 : 4;
+  if (PHOTON) knn_report(stats ? k_render<BRUTE, PHOTON, POOLED, true, 1> : k_render<BRUTE, PHOTON, POOLED, false, MINW>,
+                         "k_render", -1, A.k, ldsBytes);
   if (stats) hipLaunchKernelGGL((k_render<BRUTE, PHOTON, POOLED, true, 1>), dim3(nBlocks), dim3(BLOCK), ldsBytes, stream, S, A1, accum, counters);
   else {
     hipLaunchKernelGGL((k_render<BRUTE, PHOTON, POOLED, false, MINW>), dim3(nBlocks), dim3(BLOCK), ldsBytes, stream, S, A1, accum, counters);
@@ -1899,6 +2037,29 @@ hipError_t launch_knn(const DevScene& S, const float* q, uint32_t n, uint32_t k,
   else
     hipLaunchKernelGGL(k_knn<false>, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), ldsBytes, stream, S, q, n, k, stackLevels,
                        idx, dist, visited);
+  return hipGetLastError();
+}
+
+hipError_t launch_knn_wide(const DevScene& S, const float* q, uint32_t n, uint32_t k, bool kd16, uint32_t stackLevels,
+                           uint32_t* idx, float* dist, uint32_t* visited, hipStream_t stream) {
+  if (k <= (uint32_t)KMAX) return launch_knn(S, q, n, k, kd16, stackLevels, idx, dist, visited, stream);  // (the same instance)
+  if (n == 0) return hipSuccess;
+  if (k > (uint32_t)RT_KNN_KMAX || stackLevels < 2 || stackLevels > (uint32_t)STACK + 1) return hipErrorInvalidValue;
+  const int hl = wide_layout(kd16, stackLevels, k);
+  const size_t ldsBytes = 4u * (size_t)(stackLevels + heap_rows(hl, k)) * BLOCK;
+  const dim3 grid((n + BLOCK - 1) / BLOCK);
+#define RT_LAUNCH_KNN_WIDE(S16, HLV)                                                                                  \
+  do {                                                                                                                \
+    static unsigned long long done = 0;                                                                               \
+    if (!allow_big_lds(&k_knn_wide<S16, MINW_WIDE, HLV>, done)) return hipErrorInvalidConfiguration;                  \
+    knn_report(k_knn_wide<S16, MINW_WIDE, HLV>, "k_knn_wide", HLV, k, ldsBytes);                                     \
+    hipLaunchKernelGGL((k_knn_wide<S16, MINW_WIDE, HLV>), grid, dim3(BLOCK), ldsBytes, stream, S, q, n, k, stackLevels, \
+                       idx, dist, visited);                                                                           \
+  } while (0)
+  if (!kd16) RT_LAUNCH_KNN_WIDE(false, HEAP_WIDE8);
+  else if (hl == HEAP_SPLIT16) RT_LAUNCH_KNN_WIDE(true, HEAP_SPLIT16);
+  else RT_LAUNCH_KNN_WIDE(true, HEAP_WIDE8);
+#undef RT_LAUNCH_KNN_WIDE
   return hipGetLastError();
 }
 

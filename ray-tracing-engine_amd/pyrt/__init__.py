@@ -23,7 +23,8 @@ BVH_AUTO, BVH_DEVICE, BVH_HYBRID, BVH_HOST = 0, 1, 2, 3
 TRACE_CLOSEST, TRACE_ANY = 0, 1
 (UNIT_ASIN, UNIT_SINF, UNIT_COSF, UNIT_STREAM_SEED, UNIT_TRIANGLE, UNIT_BSDF, UNIT_RAY_AT, UNIT_LIGHT_EVAL,
  UNIT_SAMPLERS, UNIT_LIGHT_SAMPLE, UNIT_POW, UNIT_RECIP) = range(12)
-KMAX = 16
+KMAX = 16  # rt_knn
+KMAX_WIDE = 256  # rt_knn_wide and photon frames (RT_KNN_KMAX)
 
 
 class RtError(RuntimeError):
@@ -92,7 +93,7 @@ HIT_DTYPE = np.dtype([("hit", "<i4"), ("mesh", "<u4"), ("tri", "<u4"), ("vtx", "
 
 # every symbol include/rt_amd.h / include/rt_host.h declares
 AMD_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_create", "rt_destroy", "rt_set_photons", "rt_emit_photons",
-               "rt_render", "rt_render_passes", "rt_render_device", "rt_resolve_device", "rt_trace", "rt_knn", "rt_bvh_info_get",
+               "rt_render", "rt_render_passes", "rt_render_device", "rt_resolve_device", "rt_trace", "rt_knn", "rt_knn_wide", "rt_bvh_info_get",
                "rt_bvh_export", "rt_bvh_build_host", "rt_bvh_check_host", "rt_bvh_top_check_host", "rt_bvh_tune", "rt_profile_reset", "rt_profile_collect", "rt_test_unit",
                "rt_trace_stream_device", "rt_build_photon_map", "rt_get_photons", "rt_test_kd_order", "rt_owned_granules", "rt_pack_owned_device", "rt_unpack_owned_device", "rt_group_create", "rt_group_destroy",
                "rt_group_size", "rt_group_uses_rccl", "rt_group_ctx", "rt_group_set_photons", "rt_group_render"]
@@ -139,6 +140,7 @@ def amd():
                                         C.c_void_p, C.c_void_p]
         L.rt_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
         L.rt_knn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rt_knn_wide.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rt_bvh_info_get.argtypes = [C.c_void_p, C.POINTER(BvhInfo)]
         L.rt_bvh_export.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.rt_bvh_tune.argtypes = [C.c_void_p, C.POINTER(Params), C.c_double, C.c_uint32, C.POINTER(TuneReport)]
@@ -416,6 +418,15 @@ class Context:
         dist = np.zeros((len(q), k), np.float32)
         vis = np.zeros(len(q), np.uint32)
         _check(amd().rt_knn(self._h, _ptr(q), len(q), k, _ptr(idx), _ptr(dist), _ptr(vis)))
+        return idx, dist, vis
+
+    def knn_wide(self, queries, k):
+        """rt_knn_wide: knn for k in 1..KMAX_WIDE (k <= KMAX: exactly knn; above: the wide frames' walk)."""
+        q = np.ascontiguousarray(queries, np.float32)
+        idx = np.zeros((len(q), k), np.uint32)
+        dist = np.zeros((len(q), k), np.float32)
+        vis = np.zeros(len(q), np.uint32)
+        _check(amd().rt_knn_wide(self._h, _ptr(q), len(q), k, _ptr(idx), _ptr(dist), _ptr(vis)))
         return idx, dist, vis
 
 
