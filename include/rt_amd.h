@@ -11,6 +11,8 @@
  *   rt_set_photons              <- PhotonMap + kdtree built in render()
  *                                  (Renderer.cpp:209-213; kdtree.h:60-69 order)
  *   rt_emit_photons             <- PhotonMap::PhotonMap (PhotonMap.h:14-50,92-155)
+ *   rt_update                   <- a scene changed between frames (Main.cpp:88-99 rotationY, a moving
+ *                                  camera or light): the resident context follows it, tree refit
  *   rt_render                   <- the spp/y/x loop + resolve (Renderer.cpp:219-271)
  *   rt_render_device/_resolve_device : same, on caller-owned DEVICE buffers and a
  *                                  caller stream (multi-GPU tile sharding, bench)
@@ -185,6 +187,45 @@ const char* rt_last_error(void);
 int rt_create(const rt_scene_desc* scene, const rt_options* opt, rt_ctx** out);
 void rt_destroy(rt_ctx* ctx);
 
+/* ---- updating a resident scene (animation) --------------------------------------------------------------------------
+ * After a successful update the context is what rt_create would make of the updated description, except for the tree's
+ * TOPOLOGY, which stays: the same leaves, child refs and numbering, with every box recomputed from the new positions
+ * (a refit).  The hits are exact on any tree whose boxes hold their padded triangles, so every frame is the frame of the
+ * updated scene, bit for bit; only its speed depends on how far the geometry moved from the tree's (rt_create again when
+ * that matters).  The box padding, the origin bound of rt_trace, the binary16 plane scale and the choice of the short
+ * reciprocal forms (rt_bvh_info.pad / .flags) follow the updated description by rt_create's own rules.
+ * Boxes are refit when positions are given or when the padding or the plane scale changed (a camera or a light moving
+ * outwards can change the padding); a camera-only update that changes neither only moves the camera.
+ * Any update that gives positions, normals, lights or materials releases the photon map: photon frames return
+ * RT_ERR_STATE until rt_set_photons / rt_build_photon_map runs again.  A camera-only update keeps it.
+ * Validation comes first and a rejected update leaves the context as it was: RT_ERR_INVALID for a null context or
+ * update, lights NULL with n_lights > 0, or a non-finite position a triangle references ("non-finite", as rt_create);
+ * RT_ERR_UNSUPPORTED for RT_NODES_Q8 contexts.  A HIP failure once the context has started to change leaves it refusing
+ * launches (RT_ERR_STATE): destroy it.  An update is a launch: it must not overlap another launch on the context. */
+typedef struct rt_scene_update {
+  const float* vertex_pos;        /* [n_vertices][3] or NULL = unchanged (same count, same tri_vtx as rt_create's)   */
+  const float* vertex_nrm;        /* [n_vertices][3] or NULL = unchanged                                           */
+  const rt_camera* camera;        /* or NULL = unchanged                                                           */
+  const rt_light* lights;         /* [n_lights] or NULL = unchanged; n_lights may differ from rt_create's          */
+  uint32_t n_lights;
+  const rt_material* materials;   /* [n_meshes] or NULL = unchanged                                                */
+  uint32_t reserved[6];           /* zero                                                                          */
+} rt_scene_update;
+
+typedef struct rt_update_report {
+  uint32_t refitted;        /* 1: boxes (and, with positions, triangle records) were recomputed           */
+  uint32_t photons_dropped; /* 1: the context's photon map was released                                   */
+  double refit_ms;          /* device time of the refit kernels (HIP events), 0 if none ran              */
+  double total_ms;          /* wall time of the call                                                      */
+  uint64_t reserved[4];
+} rt_update_report;
+
+int rt_update(rt_ctx* ctx, const rt_scene_update* u, rt_update_report* rep /* may be NULL */);
+/* rt_update with positions / normals already in DEVICE memory (e.g. a torch tensor) on the context's device, ordered on
+ * `stream` (a hipStream_t, may be NULL); either pointer may be NULL.  Synchronises once to read the magnitude summary
+ * back (the finiteness check and the rules above need it) and once at the end. */
+int rt_update_vertices_device(rt_ctx* ctx, const void* d_pos, const void* d_nrm, void* stream, rt_update_report* rep);
+
 /* Photon arrays already in the host-built kd-tree (median-implicit) order. */
 int rt_set_photons(rt_ctx* ctx, const float* pos3, const float* dir3, uint32_t n);
 /* Emit photons on the GPU (pixel RNG mode, one stream per emitted photon), in
@@ -260,6 +301,9 @@ rt_ctx* rt_group_ctx(rt_group* g, uint32_t rank); /* borrowed: e.g. rt_emit_phot
 int rt_group_set_photons(rt_group* g, const float* pos3, const float* dir3, uint32_t n);
 int rt_group_render(rt_group* g, const rt_params* p, const float* background_rgb,
                     float* out_rgb, float* accum_out, rt_stats* stats);
+/* rt_update on every rank, rank 0 first (a rejected update leaves every rank as it was); rep: rank 0's report, total_ms
+ * the whole call.  A HIP failure on a later rank leaves the ranks before it updated: destroy the group. */
+int rt_group_update(rt_group* g, const rt_scene_update* u, rt_update_report* rep);
 
 /* Ray origins: the BVH's exactness argument (box padding vs the float triangle test's
  * error) covers origins up to 16 x max(|scene coordinate|, |camera|, |light position|);

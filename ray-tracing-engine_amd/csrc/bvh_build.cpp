@@ -848,16 +848,23 @@ ScenePlan planSceneExact(const rt_scene_desc& sc, uint32_t leafMax, std::vector<
   for (uint32_t n = sc.n_triangles; n > leafMax; n = (n + 1) / 2) ++levels;
   const char* slack = getenv("RT_BVH_SLACK");
   P.depthCap = std::min(kMaxDepth - 1, levels + (slack ? atoi(slack) : defaultDepthSlack(levels)));  // (as build() / buildTop())
-  float padRef = std::max(1.f, P.maxAbs);
+  const Padding pd = paddingRule(P.maxAbs, sc.camera, sc.lights, sc.n_lights);
+  P.pad = pd.pad, P.originBound = pd.originBound, P.boxScale = pd.boxScale;
+  return P;
+}
+
+Padding paddingRule(float maxAbs, const rt_camera& camera, const rt_light* lights, uint32_t nLights) {
+  float padRef = std::max(1.f, maxAbs);
   for (int a = 0; a < 3; ++a)
-    if (std::isfinite(sc.camera.position[a])) padRef = std::max(padRef, std::fabs(sc.camera.position[a]));
-  for (uint32_t l = 0; l < sc.n_lights; ++l)
+    if (std::isfinite(camera.position[a])) padRef = std::max(padRef, std::fabs(camera.position[a]));
+  for (uint32_t l = 0; l < nLights; ++l)
     for (int a = 0; a < 3; ++a)
-      if (std::isfinite(sc.lights[l].position[a])) padRef = std::max(padRef, std::fabs(sc.lights[l].position[a]));
+      if (std::isfinite(lights[l].position[a])) padRef = std::max(padRef, std::fabs(lights[l].position[a]));
+  Padding P;
   P.pad = 6e-5f * padRef;
   P.originBound = 16.f * padRef;
   int e = 0;
-  std::frexp(32768.f / std::max(P.maxAbs + P.pad, 1e-30f), &e);
+  std::frexp(32768.f / std::max(maxAbs + P.pad, 1e-30f), &e);  // value = m * 2^e, m in [0.5,1)
   P.boxScale = std::ldexp(1.f, std::min(std::max(e - 1, -100), 100));
   return P;
 }
@@ -1347,13 +1354,8 @@ void buildTop(const rt_scene_desc& sc, uint32_t leafMax, uint32_t cutoff, TopBui
   B.parThreads = std::min(nthreads, 64u);
   const float maxAbs = B.loadPrims(nullptr);
   if (B.parThreads > 1u && sc.n_triangles >= Builder::kParSplit) B.scratch.resize(sc.n_triangles);
-  float padRef = std::max(1.f, maxAbs);
-  for (int a = 0; a < 3; ++a)
-    if (std::isfinite(sc.camera.position[a])) padRef = std::max(padRef, std::fabs(sc.camera.position[a]));
-  for (uint32_t l = 0; l < sc.n_lights; ++l)
-    for (int a = 0; a < 3; ++a)
-      if (std::isfinite(sc.lights[l].position[a])) padRef = std::max(padRef, std::fabs(sc.lights[l].position[a]));
-  scratch.pad = 6e-5f * padRef;  // (recurse pads the boxes with it)
+  const Padding pd = paddingRule(maxAbs, sc.camera, sc.lights, sc.n_lights);
+  scratch.pad = pd.pad;  // (recurse pads the boxes with it)
   B.grain = nthreads > 1 ? std::max<uint32_t>(8192u, sc.n_triangles / (4u * nthreads)) : ~0u;
   if (sc.n_triangles <= cutoff) throw std::runtime_error("buildTop: the scene is a single part");
   const double tPrims = msSince();
@@ -1384,10 +1386,8 @@ void buildTop(const rt_scene_desc& sc, uint32_t leafMax, uint32_t cutoff, TopBui
     }
   out.order.resize(sc.n_triangles);
   for (uint32_t i = 0; i < sc.n_triangles; ++i) out.order[i] = B.prims[i].id;
-  out.leafMax = leafMax, out.depthCap = B.depthCap, out.pad = scratch.pad, out.originBound = 16.f * padRef;
-  int e = 0;
-  std::frexp(32768.f / std::max(maxAbs + out.pad, 1e-30f), &e);
-  out.boxScale = std::ldexp(1.f, std::min(std::max(e - 1, -100), 100));
+  out.leafMax = leafMax, out.depthCap = B.depthCap, out.maxAbs = maxAbs, out.pad = pd.pad, out.originBound = pd.originBound;
+  out.boxScale = pd.boxScale;
   if (getenv("RT_BVH_VERBOSE"))
     fprintf(stderr, "buildTop: primitives %.1f ms, splits %.1f ms, numbering %.1f ms (%u threads)\n", tPrims, tSplit - tPrims, msSince() - tSplit, nthreads);
 }
@@ -1416,19 +1416,9 @@ void build(const rt_scene_desc& sc, uint32_t leafMax, Built& out, uint32_t threa
   out.trisRef.resize(sc.n_triangles);
   const float maxAbs = B.loadPrims(out.trisRef.data());
   if (B.parThreads > 1u && sc.n_triangles >= Builder::kParSplit) B.scratch.resize(sc.n_triangles);
-  // The padding must dominate the float triangle test's own error, which grows with the
-  // distance of the ray ORIGIN from the geometry (tvec = o - p0 rounds to ulp(|o|)): the
-  // origins the integrator uses are the camera, the lights (photon emission) and surface
-  // points, so they all enter the reference magnitude.  rt_trace rays from farther away
-  // than originBound run the exhaustive loop instead (k_trace).
-  float padRef = std::max(1.f, maxAbs);
-  for (int a = 0; a < 3; ++a)
-    if (std::isfinite(sc.camera.position[a])) padRef = std::max(padRef, std::fabs(sc.camera.position[a]));
-  for (uint32_t l = 0; l < sc.n_lights; ++l)
-    for (int a = 0; a < 3; ++a)
-      if (std::isfinite(sc.lights[l].position[a])) padRef = std::max(padRef, std::fabs(sc.lights[l].position[a]));
-  out.pad = 6e-5f * padRef;
-  out.originBound = 16.f * padRef;
+  // (bvh_build.h paddingRule: the padding, the origin bound and the plane scale)
+  const Padding pd = paddingRule(maxAbs, sc.camera, sc.lights, sc.n_lights);
+  out.maxAbs = maxAbs, out.pad = pd.pad, out.originBound = pd.originBound;
 
   B.grain = nthreads > 1 ? std::max<uint32_t>(8192u, sc.n_triangles / (4u * nthreads)) : ~0u;
 
@@ -1488,9 +1478,7 @@ void build(const rt_scene_desc& sc, uint32_t leafMax, Built& out, uint32_t threa
   for (uint32_t i = 0; i < sc.n_triangles; ++i) out.tris[i] = out.trisRef[B.prims[i].id];
 
   // packed device nodes
-  int e = 0;
-  std::frexp(32768.f / std::max(maxAbs + out.pad, 1e-30f), &e);  // value = m * 2^e, m in [0.5,1)
-  out.boxScale = std::ldexp(1.f, std::min(std::max(e - 1, -100), 100));
+  out.boxScale = pd.boxScale;
   out.depthCap = B.depthCap;
   packNodes(out);
   if (getenv("RT_BVH_VERBOSE")) {

@@ -136,10 +136,22 @@ struct Built {
   int depthCap = kMaxDepth - 1;  // the cap the tree was built under
   float pad = 0.f;
   float originBound = 0.f;      // ray origins with a larger |coordinate| are outside the padding analysis
+  float maxAbs = 0.f;           // largest |coordinate| of a vertex a triangle references (what paddingRule took)
   // the one-request form (packQ8): empty unless requested
   std::vector<Slot16> q8;
   uint32_t q8Shift = 0, q8Blocks = 0;
 };
+
+// The box padding, the origin bound and the f16 plane scale of a scene whose triangles reference vertex coordinates of at
+// most maxAbs in magnitude.  The padding must dominate the float triangle test's own error, which grows with the distance
+// of the ray ORIGIN from the geometry (tvec = o - p0 rounds to ulp(|o|)): the origins the integrator uses are the camera,
+// the lights (photon emission) and surface points, so they all enter the reference magnitude.  rt_trace rays from farther
+// away than originBound run the exhaustive loop instead (k_trace).  build(), buildTop(), planSceneExact() and rt_update all
+// take it from here.
+struct Padding {
+  float pad, originBound, boxScale;
+};
+Padding paddingRule(float maxAbs, const rt_camera& camera, const rt_light* lights, uint32_t nLights);
 
 // What the device builder (csrc/bvh_gpu.hip) takes from the host before it touches a triangle: validation (throws
 // std::runtime_error on an inconsistent description), the leaf size, the HOST builder's depth cap, the box padding, the f16
@@ -173,7 +185,7 @@ struct TopBuilt {
   std::vector<Part> parts;      // ascending by b
   uint32_t leafMax = 2, maxDepth = 0;  // maxDepth: deepest leaf / part root of the top
   int depthCap = kMaxDepth - 1;
-  float pad = 0.f, originBound = 0.f, boxScale = 1.f;
+  float maxAbs = 0.f, pad = 0.f, originBound = 0.f, boxScale = 1.f;
 };
 constexpr uint32_t kPartFlag = 0x40000000u;
 void buildTop(const rt_scene_desc& scene, uint32_t leafMax, uint32_t cutoff, TopBuilt& out, uint32_t threads = 0);

@@ -26,6 +26,7 @@
 // four scenes, 1 M triangles in 21 ms (host: 170-180 ms).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 
@@ -112,20 +113,23 @@ __device__ __forceinline__ uint32_t half_directed(float x, bool up) {
 
 // 48-B triangle records (rtbvh::TriRec): p0, e1 = p1 - p0, e2 = p2 - p0 (the float subtraction
 // Ray.cpp:11 performs per test), global id, mesh; in `order` (leaf order) or reference order
-__global__ void k_tri_records(const float* __restrict__ vpos, const uint4* __restrict__ triShade, const uint32_t* __restrict__ order,
-                              uint32_t n, float4* __restrict__ recs) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t t = order ? order[i] : i;
+__device__ __forceinline__ void write_tri_record(const float* __restrict__ vpos, const uint4* __restrict__ triShade, uint32_t t,
+                                                 float4* __restrict__ rec) {
   const uint4 tv = triShade[t];
   const float* p0 = vpos + 3 * (size_t)tv.x;
   const float* p1 = vpos + 3 * (size_t)tv.y;
   const float* p2 = vpos + 3 * (size_t)tv.z;
   const float e1x = p1[0] - p0[0], e1y = p1[1] - p0[1], e1z = p1[2] - p0[2];
   const float e2x = p2[0] - p0[0], e2y = p2[1] - p0[1], e2z = p2[2] - p0[2];
-  recs[3 * (size_t)i + 0] = make_float4(p0[0], p0[1], p0[2], e1x);
-  recs[3 * (size_t)i + 1] = make_float4(e1y, e1z, e2x, e2y);
-  recs[3 * (size_t)i + 2] = make_float4(e2z, __uint_as_float(t), __uint_as_float(tv.w), 0.f);
+  rec[0] = make_float4(p0[0], p0[1], p0[2], e1x);
+  rec[1] = make_float4(e1y, e1z, e2x, e2y);
+  rec[2] = make_float4(e2z, __uint_as_float(t), __uint_as_float(tv.w), 0.f);
+}
+__global__ void k_tri_records(const float* __restrict__ vpos, const uint4* __restrict__ triShade, const uint32_t* __restrict__ order,
+                              uint32_t n, float4* __restrict__ recs) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  write_tri_record(vpos, triShade, order ? order[i] : i, recs + 3 * (size_t)i);
 }
 
 // ---------------------------------------------------------------- exact subtrees (step 6)
@@ -565,27 +569,110 @@ __global__ void k_rot_level(RNode* __restrict__ nodes, uint32_t n, const uint8_t
   nodes[idx] = N;
   height[idx] = (uint8_t)(1 + max(rot_height(height, N.child[0]), rot_height(height, N.child[1])));
 }
+// one float record -> its packed record (rtbvh::packNodes' bits)
+__device__ __forceinline__ void pack_record(const RNode& N, float s, uint4* __restrict__ out) {
+  const Box3 B0 = rot_child(N, 0), B1 = rot_child(N, 1);
+  const uint32_t h[12] = {half_directed(B0.lx * s, false), half_directed(B0.hx * s, true), half_directed(B0.ly * s, false),
+                          half_directed(B0.hy * s, true),  half_directed(B0.lz * s, false), half_directed(B0.hz * s, true),
+                          half_directed(B1.lx * s, false), half_directed(B1.hx * s, true), half_directed(B1.ly * s, false),
+                          half_directed(B1.hy * s, true),  half_directed(B1.lz * s, false), half_directed(B1.hz * s, true)};
+  out[0] = make_uint4(h[0] | h[1] << 16, h[2] | h[3] << 16, h[4] | h[5] << 16, h[6] | h[7] << 16);
+  out[1] = make_uint4(h[8] | h[9] << 16, h[10] | h[11] << 16, packed_ref(N.child[0]), packed_ref(N.child[1]));
+}
 // float records -> packed records (child 0 = the smaller box: any-hit rays of the big-scene kernels enter it first)
 __global__ void k_rot_pack(RNode* __restrict__ nodes, uint32_t n, float boxScale, uint4* __restrict__ nodes16) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   RNode N = nodes[i];
-  Box3 B0 = rot_child(N, 0), B1 = rot_child(N, 1);
+  const Box3 B0 = rot_child(N, 0), B1 = rot_child(N, 1);
   if (half_area(B1) < half_area(B0)) {
-    const Box3 t = B0;
-    B0 = B1, B1 = t;
     const int32_t c0 = N.child[0];
     N.child[0] = N.child[1], N.child[1] = c0;
-    rot_set(N, 0, N.child[0], B0), rot_set(N, 1, N.child[1], B1);
+    rot_set(N, 0, N.child[0], B1), rot_set(N, 1, N.child[1], B0);
     nodes[i] = N;
   }
-  const float s = boxScale;
-  const uint32_t h[12] = {half_directed(B0.lx * s, false), half_directed(B0.hx * s, true), half_directed(B0.ly * s, false),
-                          half_directed(B0.hy * s, true),  half_directed(B0.lz * s, false), half_directed(B0.hz * s, true),
-                          half_directed(B1.lx * s, false), half_directed(B1.hx * s, true), half_directed(B1.ly * s, false),
-                          half_directed(B1.hy * s, true),  half_directed(B1.lz * s, false), half_directed(B1.hz * s, true)};
-  nodes16[2 * (size_t)i + 0] = make_uint4(h[0] | h[1] << 16, h[2] | h[3] << 16, h[4] | h[5] << 16, h[6] | h[7] << 16);
-  nodes16[2 * (size_t)i + 1] = make_uint4(h[8] | h[9] << 16, h[10] | h[11] << 16, packed_ref(N.child[0]), packed_ref(N.child[1]));
+  pack_record(N, boxScale, nodes16 + 2 * (size_t)i);
+}
+
+// ---------------------------------------------------------------- refit (rt_update)
+// New vertex positions under the SAME tree: every box is recomputed, nothing else moves (child refs, slot order, numbering,
+// depth).  A leaf slot's box is the min / max of its triangles' vertex positions, then lo - pad, hi + pad in float — what
+// the builders' boundsOf + padding compute —; an inner slot's box is the union of its child's two slot boxes, which equals
+// the builders' padded bounds of the whole range bit for bit because fl(x - pad) and fl(x + pad) are monotone (and a
+// signed zero cannot survive the padding, pad > 0).  One launch per depth, deepest first: a level reads only boxes the
+// previous launch wrote, so no flag crosses workgroups, and min / max are exact, so no schedule changes a bit.
+
+// max |x| bits (uint compare = magnitude compare; a non-finite value has all exponent bits set and compares above every
+// finite one) over: [0] the positions the triangles reference, [1] all positions, [2] all normals.  pos / nrm may be null.
+__global__ __launch_bounds__(256) void k_magnitudes(const float* __restrict__ pos, const float* __restrict__ nrm,
+                                                    const uint4* __restrict__ triShade, uint32_t nTris, uint32_t nVerts,
+                                                    uint32_t* __restrict__ out) {
+  const uint32_t stride = gridDim.x * blockDim.x, i0 = blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t mRef = 0, mPos = 0, mNrm = 0;
+  const uint32_t* P = reinterpret_cast<const uint32_t*>(pos);
+  const uint32_t* Q = reinterpret_cast<const uint32_t*>(nrm);
+  if (P) {
+    for (uint32_t t = i0; t < nTris; t += stride) {
+      const uint4 tv = triShade[t];
+      for (int a = 0; a < 3; ++a)
+        mRef = max(mRef, max(P[3 * (size_t)tv.x + a] & 0x7fffffffu, max(P[3 * (size_t)tv.y + a] & 0x7fffffffu, P[3 * (size_t)tv.z + a] & 0x7fffffffu)));
+    }
+    for (size_t k = i0; k < 3 * (size_t)nVerts; k += stride) mPos = max(mPos, P[k] & 0x7fffffffu);
+  }
+  if (Q)
+    for (size_t k = i0; k < 3 * (size_t)nVerts; k += stride) mNrm = max(mNrm, Q[k] & 0x7fffffffu);
+  for (int off = 32; off > 0; off >>= 1) {
+    mRef = max(mRef, (uint32_t)__shfl_xor((int)mRef, off));
+    mPos = max(mPos, (uint32_t)__shfl_xor((int)mPos, off));
+    mNrm = max(mNrm, (uint32_t)__shfl_xor((int)mNrm, off));
+  }
+  if ((threadIdx.x & 63u) == 0u) {
+    if (mRef) atomicMax(out + 0, mRef);
+    if (mPos) atomicMax(out + 1, mPos);
+    if (mNrm) atomicMax(out + 2, mNrm);
+  }
+}
+
+// the leaf-order records again: each record keeps its triangle (the id it holds), its vertices are read anew
+__global__ void k_refit_tris(const float* __restrict__ vpos, const uint4* __restrict__ triShade, uint32_t n, float4* __restrict__ recs) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  write_tri_record(vpos, triShade, __float_as_uint(recs[3 * (size_t)i + 2].y), recs + 3 * (size_t)i);
+}
+
+__device__ __forceinline__ Box3 refit_slot(const RNode* __restrict__ nodes, int32_t ref, const float4* __restrict__ tris,
+                                           const float* __restrict__ vpos, const uint4* __restrict__ triShade, float pad) {
+  if (ref >= 0) {
+    const RNode C = nodes[ref];
+    return rot_union(rot_child(C, 0), rot_child(C, 1));
+  }
+  const uint32_t code = ~(uint32_t)ref, first = code >> 3, count = (code & 7u) + 1u;
+  Box3 b{INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+  for (uint32_t r = first; r < first + count; ++r) {
+    const uint4 tv = triShade[__float_as_uint(tris[3 * (size_t)r + 2].y)];
+    const uint32_t vs[3] = {tv.x, tv.y, tv.z};
+    for (int k = 0; k < 3; ++k) {
+      const float* q = vpos + 3 * (size_t)vs[k];
+      b.lx = fminf(b.lx, q[0]), b.ly = fminf(b.ly, q[1]), b.lz = fminf(b.lz, q[2]);
+      b.hx = fmaxf(b.hx, q[0]), b.hy = fmaxf(b.hy, q[1]), b.hz = fmaxf(b.hz, q[2]);
+    }
+  }
+  return Box3{b.lx - pad, b.ly - pad, b.lz - pad, b.hx + pad, b.hy + pad, b.hz + pad};
+}
+__global__ void k_refit_level(RNode* __restrict__ nodes, uint32_t n, const uint8_t* __restrict__ depth, uint32_t d,
+                              const float4* __restrict__ tris, const float* __restrict__ vpos, const uint4* __restrict__ triShade,
+                              float pad) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n || depth[i] != d) return;
+  RNode N = nodes[i];
+  for (int c = 0; c < 2; ++c) rot_set(N, c, N.child[c], refit_slot(nodes, N.child[c], tris, vpos, triShade, pad));
+  nodes[i] = N;
+}
+// the packed records of the refit boxes, slot order unchanged
+__global__ void k_refit_pack(const RNode* __restrict__ nodes, uint32_t n, float boxScale, uint4* __restrict__ nodes16) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  pack_record(nodes[i], boxScale, nodes16 + 2 * (size_t)i);
 }
 
 // Pre-order renumbering after the rotations (what the host builder's relayout leaves below its top, and what the
@@ -1665,6 +1752,53 @@ hipError_t gpu_bvh_build_exact(const float* dVpos, const uint4* dTriShade, const
     fprintf(stderr, "device build: top of %u nodes over %u parts in %u levels %.2f ms (allocations included), subtrees + rotations + records %.2f ms, release %.2f ms\n",
             nTop, nSub, depth, tTop, tDone - tTop, msSince() - tDone);
   return hipSuccess;
+}
+
+hipError_t launch_magnitudes(const float* dPos, const float* dNrm, const uint4* dTriShade, uint32_t nTris, uint32_t nVerts,
+                             uint32_t* dOut3, hipStream_t stream) {
+  hipError_t e = hipMemsetAsync(dOut3, 0, 3 * sizeof(uint32_t), stream);
+  if (e != hipSuccess) return e;
+  const uint32_t work = std::max(nTris, 3u * nVerts);
+  const uint32_t blocks = std::max(1u, std::min(4096u, (work + 255u) / 256u));
+  hipLaunchKernelGGL(k_magnitudes, dim3(blocks), dim3(256), 0, stream, dPos, dNrm, dTriShade, nTris, nVerts, dOut3);
+  return hipGetLastError();
+}
+
+hipError_t gpu_bvh_depths(const float4* nodesF, uint32_t n, uint8_t* dDepth, uint32_t* maxDepthOut, hipStream_t stream) {
+  const RNode* nodes = reinterpret_cast<const RNode*>(nodesF);
+  uint32_t *parent = nullptr, *scal = nullptr;
+  hipError_t e = hipMalloc((void**)&parent, (size_t)n * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMalloc((void**)&scal, sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMemsetAsync(scal, 0, sizeof(uint32_t), stream);
+  uint32_t maxD = 0;
+  if (e == hipSuccess) {
+    const dim3 blk(256), grd((n + 255) / 256);
+    hipLaunchKernelGGL(k_rot_parents, grd, blk, 0, stream, nodes, n, parent);
+    hipLaunchKernelGGL(k_rot_depths, grd, blk, 0, stream, parent, n, dDepth, scal);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(&maxD, scal, sizeof maxD, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  }
+  for (void* q : {(void*)parent, (void*)scal})
+    if (q) (void)hipFree(q);
+  if (e == hipSuccess) *maxDepthOut = maxD;
+  return e;
+}
+
+hipError_t gpu_bvh_refit(const float* dVpos, const uint4* dTriShade, uint32_t nTris, bool records, float4* tris, float4* trisRef,
+                         float4* nodesF, uint4* nodes16, uint32_t nNodes, const uint8_t* dDepth, uint32_t maxDepth, float pad,
+                         float boxScale, hipStream_t stream) {
+  const dim3 blk(256);
+  if (records) {
+    hipLaunchKernelGGL(k_refit_tris, dim3((nTris + 255) / 256), blk, 0, stream, dVpos, dTriShade, nTris, tris);
+    hipLaunchKernelGGL(k_tri_records, dim3((nTris + 255) / 256), blk, 0, stream, dVpos, dTriShade, (const uint32_t*)nullptr, nTris, trisRef);
+  }
+  RNode* nodes = reinterpret_cast<RNode*>(nodesF);
+  const dim3 grd((nNodes + 255) / 256);
+  for (int d = (int)maxDepth; d >= 0; --d)
+    hipLaunchKernelGGL(k_refit_level, grd, blk, 0, stream, nodes, nNodes, dDepth, (uint32_t)d, tris, dVpos, dTriShade, pad);
+  hipLaunchKernelGGL(k_refit_pack, grd, blk, 0, stream, nodes, nNodes, boxScale, nodes16);
+  return hipGetLastError();
 }
 
 }  // namespace rtk

@@ -161,13 +161,25 @@ struct rt_ctx {
   size_t wfCap = 0;
   DevBuf<char> wfBlock;
   uint32_t builder = RT_BVH_HOST;
-  bool broken = false;  // the device tree is in an unknown state (rt_bvh_tune could not restore it): launches are refused
+  bool broken = false;  // the device tree is in an unknown state (rt_bvh_tune could not restore it, rt_update failed partway): launches are refused
   uint32_t recipCheck = 0;  // 0: short reciprocal forms not wanted (operand bounds), 1: verified on this device, 2: self-check FAILED (dividing)
   uint32_t nodeFormat = RT_NODES_F16;  // what the pooled render kernel and rt_trace traverse
   float buildMs = 0.f;
   uint32_t numCUs = 0;
   Event ev[kEventPairs][2];
   int evUsed = 0;
+  // what the rules of rt_update read besides the scene's arrays (the camera is S.cam): the lights, and the magnitude
+  // summaries — max |x| bits of the positions the triangles reference (the padding rule), of all positions and of all
+  // normals (vouch_short_forms)
+  std::vector<rt_light> hostLights;
+  uint32_t nMeshes = 0, nVertices = 0;
+  uint32_t magRef = 0, magPos = 0, magNrm = 0;
+  // refit state (rt_update, allocated on first use): the depth of every node of nodesF (a host-built tree's nodes are
+  // uploaded to nodesF then and kept), and scratch for host-given arrays and the magnitude read-back
+  DevBuf<uint8_t> refitDepth;
+  uint32_t refitMaxDepth = 0;
+  DevBuf<float> updPos, updNrm;
+  DevBuf<uint32_t> dMag;
 };
 
 namespace {
@@ -288,7 +300,7 @@ int ensure_granules(rt_ctx* c, const rt_params* p, uint32_t rank, const rt_ctx::
 
 int check_params(const rt_ctx* c, const rt_params* p) {
   if (!p) return fail(RT_ERR_INVALID, "params is null");
-  if (c->broken) return fail(RT_ERR_STATE, "the context's device tree is in an unknown state (a failed rt_bvh_tune): destroy it");
+  if (c->broken) return fail(RT_ERR_STATE, "the context's device tree is in an unknown state (a failed rt_bvh_tune or rt_update): destroy it");
   if (p->width == 0 || p->height == 0 || p->width > 65535u || p->height > 65535u)
     return fail(RT_ERR_INVALID, "image size %ux%u out of range", p->width, p->height);
   if (p->spp == 0) return fail(RT_ERR_INVALID, "spp must be >= 1");
@@ -508,39 +520,47 @@ void read_back_tree(rt_ctx* c, uint32_t nTris) {
 //    normalise is a small sum of scene inputs, so |input| <= 1e14 keeps the squared length below 2^100 (the lower end
 //    is tested per lane: rt_device.h unit3).
 // Outside these bounds — or with any non-finite input — the kernels divide.  (User rays, rt_trace /
-// rt_trace_stream_device, always divide.)  Sets c->S.slowRecip and c->recipCheck.
-void vouch_short_forms(rt_ctx* c, const rt_scene_desc* sc) {
+// rt_trace_stream_device, always divide.)  Sets c->S.slowRecip and c->recipCheck.  rt_create and rt_update run it.
+// max |x| over n floats as bits (a non-finite value has all exponent bits set: its magnitude bits compare above every
+// finite float's)
+uint32_t max_abs_bits(const float* p, size_t n) {
+  uint32_t top[64] = {0};
+  par_chunks(0, n, [&](uint32_t th, size_t b, size_t e) {
+    uint32_t m = 0;
+    for (size_t i = b; i < e; ++i) {
+      uint32_t u;
+      memcpy(&u, p + i, 4);
+      u &= 0x7fffffffu;
+      m = u > m ? u : m;
+    }
+    top[th] = m;
+  });
+  uint32_t m = 0;
+  for (uint32_t t : top) m = t > m ? t : m;
+  return m;
+}
+float bits_float(uint32_t u) {
+  float f;
+  memcpy(&f, &u, 4);
+  return f;
+}
+
+// (reads the magnitude summaries c->magPos / c->magNrm, the camera S.cam and the lights c->hostLights)
+void vouch_short_forms(rt_ctx* c) {
   rtk::DevScene& S = c->S;
   double maxAbs = 0, maxLight = 0, maxAny = 0;
   bool finite = true;
-  // (a non-finite value has all exponent bits set: its magnitude bits compare above every finite float's)
-  auto eat = [&](const float* p, size_t n) {
-    uint32_t top[64] = {0};
-    par_chunks(0, n, [&](uint32_t th, size_t b, size_t e) {
-      uint32_t m = 0;
-      for (size_t i = b; i < e; ++i) {
-        uint32_t u;
-        memcpy(&u, p + i, 4);
-        u &= 0x7fffffffu;
-        m = u > m ? u : m;
-      }
-      top[th] = m;
-    });
-    uint32_t m = 0;
-    for (uint32_t t : top) m = t > m ? t : m;
-    float f;
-    memcpy(&f, &m, 4);
+  auto eat = [&](uint32_t m) {
     if (m >= 0x7f800000u) finite = false;
-    else maxAny = std::max(maxAny, (double)f);
-    return m >= 0x7f800000u ? 0.0 : (double)f;
+    else maxAny = std::max(maxAny, (double)bits_float(m));
+    return m >= 0x7f800000u ? 0.0 : (double)bits_float(m);
   };
-  maxAbs = eat(sc->vertex_pos, 3 * (size_t)sc->n_vertices);
-  eat(sc->vertex_nrm, 3 * (size_t)sc->n_vertices);
-  eat(sc->camera.position, 12);
-  for (uint32_t l = 0; l < sc->n_lights; ++l) {
-    const rt_light& L = sc->lights[l];
-    eat(L.position, 15);
-    eat(&L.intensity, 6);
+  maxAbs = eat(c->magPos);
+  eat(c->magNrm);
+  eat(max_abs_bits(S.cam.position, 12));
+  for (const rt_light& L : c->hostLights) {
+    eat(max_abs_bits(L.position, 15));
+    eat(max_abs_bits(&L.intensity, 6));
     double pos = 0, ver = 0, hor = 0;
     for (int a = 0; a < 3; ++a) pos += (double)L.position[a] * L.position[a], ver += (double)L.vertical[a] * L.vertical[a], hor += (double)L.horizontal[a] * L.horizontal[a];
     maxLight = std::max(maxLight, std::sqrt(pos) + std::fabs((double)L.side) * (std::sqrt(ver) + std::sqrt(hor)));
@@ -615,6 +635,7 @@ int create_ctx(const rt_scene_desc* sc, const rt_options* opt, const rtbvh::Buil
         fprintf(stderr, "hybrid builder: host top of %zu nodes over %zu parts in %.1f ms\n", topBuilt.nodes.size(), topBuilt.parts.size(),
                 std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - tBuild0).count());
       c->bvh.leafMax = topBuilt.leafMax, c->bvh.pad = topBuilt.pad, c->bvh.originBound = topBuilt.originBound, c->bvh.boxScale = topBuilt.boxScale;
+      c->bvh.maxAbs = topBuilt.maxAbs;
       c->bvh.depthCap = topBuilt.depthCap;
       (void)rtbvh::planSceneExact(*sc, opt ? opt->bvh_leaf_max : 0, sizeKey);  // (the size keys of the subtrees' sweeps)
     } else if (gpuBuild) {
@@ -623,6 +644,7 @@ int create_ctx(const rt_scene_desc* sc, const rt_options* opt, const rtbvh::Buil
       if (getenv("RT_BVH_VERBOSE"))
         fprintf(stderr, "device builder: validation + size keys in %.2f ms\n", std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - tBuild0).count());
       c->bvh.leafMax = plan.leafMax, c->bvh.pad = plan.pad, c->bvh.originBound = plan.originBound, c->bvh.boxScale = plan.boxScale;
+      c->bvh.maxAbs = plan.maxAbs;
       c->bvh.depthCap = plan.depthCap;
     } else if (prebuilt) {
       c->bvh = *prebuilt;
@@ -724,7 +746,13 @@ int create_ctx(const rt_scene_desc* sc, const rt_options* opt, const rtbvh::Buil
   S.n_photons = 0;
   S.invBoxScale = 1.f / c->bvh.boxScale;
   S.originBound = c->bvh.originBound;
-  vouch_short_forms(c.get(), sc);
+  S.cam = sc->camera;
+  c->hostLights.assign(sc->lights, sc->lights + sc->n_lights);
+  c->nMeshes = sc->n_meshes, c->nVertices = sc->n_vertices;
+  memcpy(&c->magRef, &c->bvh.maxAbs, 4);
+  c->magPos = max_abs_bits(sc->vertex_pos, 3 * (size_t)sc->n_vertices);
+  c->magNrm = max_abs_bits(sc->vertex_nrm, 3 * (size_t)sc->n_vertices);
+  vouch_short_forms(c.get());
   // Pool thresholds (Trav::round's descent early exit, the steal and refill levels).  Two scene
   // classes, as for the samples-of-a-pixel-per-wave rule: trees the caches hold (<= 65,536 nodes)
   // are issue-bound and want long descents (12 / 8 / 24: C2 50.5 ms; 16 or 24 lanes cost 0.2-1 %);
@@ -738,7 +766,6 @@ int create_ctx(const rt_scene_desc* sc, const rt_options* opt, const rtbvh::Buil
   S.refillT = getenv("RT_REFILLT") ? atoi(getenv("RT_REFILLT")) : bigTree ? 32 : 24;
   S.phPos = S.phDir = nullptr, S.phTopo = nullptr;
   S.topK = 0;
-  S.cam = sc->camera;
   int cus = 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) == hipSuccess && cus > 0) c->numCUs = (uint32_t)cus;
   if (dev_alloc(&c->dTileCounter, 1) != hipSuccess) return fail(RT_ERR_HIP, "tile counter allocation failed");
@@ -1210,6 +1237,8 @@ int rt_bvh_tune(rt_ctx* c, const rt_params* probe, double budget_seconds, uint32
   if (rc != RT_OK) return rc;
   if (!(budget_seconds > 0)) return RT_OK;
   HIP_TRY(hipSetDevice(c->device));
+  // (the tree may change: rt_update uploads it again)
+  c->nodesF.reset(), c->refitDepth.reset();
   DevBuf<float4> dAcc;
   HIP_TRY(dev_alloc(&dAcc, (size_t)probe->width * probe->height));
   rt_params p = *probe;
@@ -1737,6 +1766,186 @@ int rt_group_render(rt_group* g, const rt_params* p, const float* bg, float* out
     }
     stats->samples = (uint64_t)npx * (p->spp_count ? p->spp_count : p->spp);
   }
+  return RT_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- rt_update: a resident scene follows its description
+namespace {
+
+// what an update changes; positions / normals already on the device (the caller's arrays or the context's scratch)
+struct Update {
+  const float* dPos = nullptr;
+  const float* dNrm = nullptr;
+  const rt_camera* camera = nullptr;
+  const rt_light* lights = nullptr;
+  uint32_t nLights = 0;
+  const rt_material* materials = nullptr;
+};
+
+int update_checks(rt_ctx* c, const rt_light* lights, uint32_t nLights) {
+  if (!lights && nLights) return fail(RT_ERR_INVALID, "update: lights is null but n_lights is %u", nLights);
+  if (c->nodeFormat == RT_NODES_Q8) return fail(RT_ERR_UNSUPPORTED, "update: RT_NODES_Q8 contexts cannot be refit (create the context again)");
+  if (c->broken) return fail(RT_ERR_STATE, "the context is in an unknown state (a failed rt_bvh_tune or rt_update): destroy it");
+  return RT_OK;
+}
+
+// The rules rt_create applies, on the updated description: validation and every derived value first (nothing visible
+// changes), then the arrays, the refit and the derived state.  `stream` orders the work on the caller's arrays.
+int update_ctx(rt_ctx* c, const Update& u, hipStream_t stream, std::chrono::steady_clock::time_point t0, rt_update_report* rep) {
+  rtk::DevScene& S = c->S;
+  rt_update_report r{};
+  // 1. the magnitude summaries of the new arrays (the finiteness check, the padding rule, vouch_short_forms)
+  uint32_t magRef = c->magRef, magPos = c->magPos, magNrm = c->magNrm;
+  if (u.dPos || u.dNrm) {
+    if (!c->dMag) HIP_TRY(dev_alloc(&c->dMag, 3));
+    uint32_t h[3] = {0, 0, 0};
+    hipError_t he = rtk::launch_magnitudes(u.dPos, u.dNrm, c->triShade.get(), S.n_tris, c->nVertices, c->dMag.get(), stream);
+    if (he == hipSuccess) he = hipMemcpyAsync(h, c->dMag.get(), sizeof h, hipMemcpyDeviceToHost, stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(stream);
+    if (he != hipSuccess) return fail(RT_ERR_HIP, "update: magnitude pass failed: %s", hipGetErrorString(he));
+    if (u.dPos) magRef = h[0], magPos = h[1];
+    if (u.dNrm) magNrm = h[2];
+    if (magRef >= 0x7f800000u) return fail(RT_ERR_INVALID, "update rejected: non-finite vertex position");
+  }
+  const rt_camera cam = u.camera ? *u.camera : S.cam;
+  const std::vector<rt_light> lights = u.lights ? std::vector<rt_light>(u.lights, u.lights + u.nLights) : c->hostLights;
+  const rtbvh::Padding P = rtbvh::paddingRule(bits_float(magRef), cam, lights.data(), (uint32_t)lights.size());
+  const bool refit = u.dPos || P.pad != c->bvh.pad || P.boxScale != c->bvh.boxScale;
+  // 2. staging: new light and material arrays, the refit's float nodes and depth table (the context still renders as before)
+  int rc = RT_OK;
+  DevBuf<rt_light> dLights;
+  DevBuf<rt_material> dMats;
+  DevBuf<rtd::DevMat> dMatsDev;
+  if (u.lights && (rc = upload(&dLights, lights.data(), lights.size())) != RT_OK) return rc;
+  if (u.materials) {
+    std::vector<rtd::DevMat> dm(c->nMeshes);
+    for (uint32_t m = 0; m < c->nMeshes; ++m) dm[m] = rtd::make_dev_mat(u.materials[m]);
+    if ((rc = upload(&dMats, u.materials, c->nMeshes)) != RT_OK || (rc = upload(&dMatsDev, dm.data(), dm.size())) != RT_OK) return rc;
+  }
+  Event e0, e1;
+  if (refit) {
+    // (a host-built tree's float nodes go to the device on the first refit and stay; rt_bvh_tune drops them)
+    if (!c->nodesF && (rc = upload(&c->nodesF, c->bvh.nodes.data(), c->bvh.nodes.size() * 4)) != RT_OK) return rc;
+    if (!c->refitDepth) {
+      HIP_TRY(dev_alloc(&c->refitDepth, S.n_nodes));
+      const hipError_t he = rtk::gpu_bvh_depths(c->nodesF.get(), S.n_nodes, c->refitDepth.get(), &c->refitMaxDepth, stream);
+      if (he != hipSuccess) {
+        c->refitDepth.reset();
+        return fail(RT_ERR_HIP, "update: node depths failed: %s", hipGetErrorString(he));
+      }
+    }
+    HIP_TRY(make_event(&e0));
+    HIP_TRY(make_event(&e1));
+  }
+  // 3. the context changes: a failure from here on leaves it refusing launches
+  c->broken = true;
+  const size_t nv = 3 * (size_t)c->nVertices;
+  hipError_t he = hipSuccess;
+  if (u.dPos && u.dPos != c->vpos.get()) he = hipMemcpyAsync(c->vpos.get(), u.dPos, nv * sizeof(float), hipMemcpyDeviceToDevice, stream);
+  if (he == hipSuccess && u.dNrm && u.dNrm != c->vnrm.get())
+    he = hipMemcpyAsync(c->vnrm.get(), u.dNrm, nv * sizeof(float), hipMemcpyDeviceToDevice, stream);
+  if (refit) {
+    if (he == hipSuccess) he = hipEventRecord(e0.get(), stream);
+    if (he == hipSuccess)
+      he = rtk::gpu_bvh_refit(c->vpos.get(), c->triShade.get(), S.n_tris, u.dPos != nullptr, c->tris.get(), c->trisRef.get(), c->nodesF.get(),
+                              c->nodes.get(), S.n_nodes, c->refitDepth.get(), c->refitMaxDepth, P.pad, P.boxScale, stream);
+    if (he == hipSuccess) he = hipEventRecord(e1.get(), stream);
+  }
+  if (he == hipSuccess) he = hipStreamSynchronize(stream);
+  if (he == hipSuccess && refit) {
+    float ms = 0.f;
+    he = hipEventElapsedTime(&ms, e0.get(), e1.get());
+    r.refit_ms = ms;
+  }
+  // a host-built tree's host copy (rt_bvh_export, rt_bvh_tune) follows
+  if (he == hipSuccess && refit && c->builder == RT_BVH_HOST) {
+    rtbvh::Built& b = c->bvh;
+    he = hipMemcpy(b.nodes.data(), c->nodesF.get(), b.nodes.size() * sizeof(rtbvh::Node), hipMemcpyDeviceToHost);
+    if (he == hipSuccess) he = hipMemcpy(b.nodes16.data(), c->nodes.get(), b.nodes16.size() * sizeof(rtbvh::Node16), hipMemcpyDeviceToHost);
+    if (he == hipSuccess && u.dPos) he = hipMemcpy(b.tris.data(), c->tris.get(), b.tris.size() * sizeof(rtbvh::TriRec), hipMemcpyDeviceToHost);
+    if (he == hipSuccess && u.dPos) he = hipMemcpy(b.trisRef.data(), c->trisRef.get(), b.trisRef.size() * sizeof(rtbvh::TriRec), hipMemcpyDeviceToHost);
+  }
+  if (he != hipSuccess) return fail(RT_ERR_HIP, "update failed after the context had started to change (%s): it refuses launches", hipGetErrorString(he));
+  c->bvh.maxAbs = bits_float(magRef), c->bvh.pad = P.pad, c->bvh.originBound = P.originBound, c->bvh.boxScale = P.boxScale;
+  S.invBoxScale = 1.f / P.boxScale, S.originBound = P.originBound;
+  c->magRef = magRef, c->magPos = magPos, c->magNrm = magNrm;
+  S.cam = cam;
+  if (u.lights) {
+    c->lights = std::move(dLights), c->hostLights = lights;
+    S.lights = c->lights.get(), S.n_lights = (uint32_t)lights.size();
+  }
+  if (u.materials) {
+    c->mats = std::move(dMats), c->matsDev = std::move(dMatsDev);
+    S.mats = c->mats.get(), S.matsDev = c->matsDev.get();
+  }
+  vouch_short_forms(c);
+  // the photon map was emitted from the old geometry, normals, lights and materials
+  if (u.dPos || u.dNrm || u.lights || u.materials) {
+    r.photons_dropped = S.n_photons > 0 ? 1u : 0u;
+    if ((rc = drop_photons(c)) != RT_OK) return rc;
+  }
+  c->broken = false;
+  r.refitted = refit ? 1u : 0u;
+  r.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (rep) *rep = r;
+  return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_update(rt_ctx* c, const rt_scene_update* u, rt_update_report* rep) {
+  const auto t0 = std::chrono::steady_clock::now();
+  if (rep) memset(rep, 0, sizeof *rep);
+  if (!c || !u) return fail(RT_ERR_INVALID, "ctx/update is null");
+  int rc = update_checks(c, u->lights, u->n_lights);
+  if (rc != RT_OK) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  // the host form: the arrays go to the context's scratch, then the device form runs on them
+  const size_t nv = 3 * (size_t)c->nVertices;
+  Update x;
+  if (u->vertex_pos) {
+    if (!c->updPos) HIP_TRY(dev_alloc(&c->updPos, nv));
+    HIP_TRY(hipMemcpy(c->updPos.get(), u->vertex_pos, nv * sizeof(float), hipMemcpyHostToDevice));
+    x.dPos = c->updPos.get();
+  }
+  if (u->vertex_nrm) {
+    if (!c->updNrm) HIP_TRY(dev_alloc(&c->updNrm, nv));
+    HIP_TRY(hipMemcpy(c->updNrm.get(), u->vertex_nrm, nv * sizeof(float), hipMemcpyHostToDevice));
+    x.dNrm = c->updNrm.get();
+  }
+  x.camera = u->camera, x.lights = u->lights, x.nLights = u->n_lights, x.materials = u->materials;
+  return update_ctx(c, x, nullptr, t0, rep);
+}
+
+int rt_update_vertices_device(rt_ctx* c, const void* d_pos, const void* d_nrm, void* stream, rt_update_report* rep) {
+  const auto t0 = std::chrono::steady_clock::now();
+  if (rep) memset(rep, 0, sizeof *rep);
+  if (!c) return fail(RT_ERR_INVALID, "ctx is null");
+  int rc = update_checks(c, nullptr, 0);
+  if (rc != RT_OK) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  Update x;
+  x.dPos = static_cast<const float*>(d_pos), x.dNrm = static_cast<const float*>(d_nrm);
+  return update_ctx(c, x, static_cast<hipStream_t>(stream), t0, rep);
+}
+
+int rt_group_update(rt_group* g, const rt_scene_update* u, rt_update_report* rep) {
+  const auto t0 = std::chrono::steady_clock::now();
+  if (rep) memset(rep, 0, sizeof *rep);
+  if (!g || !u) return fail(RT_ERR_INVALID, "group/update is null");
+  rt_update_report first{};
+  for (size_t r = 0; r < g->ctx.size(); ++r) {
+    rt_update_report mine{};
+    const int rc = rt_update(g->ctx[r], u, r == 0 ? &first : &mine);
+    if (rc != RT_OK) return rc;
+  }
+  (void)hipSetDevice(g->dev[0]);
+  first.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (rep) *rep = first;
   return RT_OK;
 }
 

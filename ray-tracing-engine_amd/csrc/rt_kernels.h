@@ -131,6 +131,17 @@ hipError_t gpu_bvh_build_exact(const float* dVpos, const uint4* dTriShade, const
 // the hybrid build: the host builder's top (rtbvh::buildTop), exact subtrees of its parts on the device
 hipError_t gpu_bvh_build_over_top(const float* dVpos, const uint4* dTriShade, const float* hSizeKey, uint32_t n_tris, const rtbvh::TopBuilt& top,
                                   GpuBvh* out, hipStream_t stream);
+// refit of a built tree to new vertex positions (bvh_gpu.hip, rt_update): dOut3 = max |x| bits of the positions the
+// triangles reference, of all positions, of all normals (0 where pos / nrm is null; NaN and infinities compare above every
+// finite value); the depth of every node (*maxDepthOut = the deepest; synchronises); and the refit itself — records: the
+// triangle records in both orders anew from dVpos — then every box bottom-up, one launch per depth, and the packed records
+// with boxScale (slot order, refs and numbering untouched)
+hipError_t launch_magnitudes(const float* dPos, const float* dNrm, const uint4* dTriShade, uint32_t nTris, uint32_t nVerts,
+                             uint32_t* dOut3, hipStream_t stream);
+hipError_t gpu_bvh_depths(const float4* nodesF, uint32_t n, uint8_t* dDepth, uint32_t* maxDepthOut, hipStream_t stream);
+hipError_t gpu_bvh_refit(const float* dVpos, const uint4* dTriShade, uint32_t nTris, bool records, float4* tris, float4* trisRef,
+                         float4* nodesF, uint4* nodes16, uint32_t nNodes, const uint8_t* dDepth, uint32_t maxDepth, float pad,
+                         float boxScale, hipStream_t stream);
 // photon map on the device (kd_build.hip)
 hipError_t launch_photon_compact(const float4* slots, uint32_t n, float4* items, uint32_t* count, hipStream_t stream);
 hipError_t launch_kd_build(float4* items, uint32_t n, int depthOverride, hipStream_t stream);

@@ -87,6 +87,20 @@ class BvhInfo(C.Structure):
                 ("node_format", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class SceneUpdate(C.Structure):
+    _fields_ = [("vertex_pos", C.c_void_p), ("vertex_nrm", C.c_void_p), ("camera", C.POINTER(Camera)),
+                ("lights", C.POINTER(Light)), ("n_lights", C.c_uint32), ("materials", C.POINTER(Material)),
+                ("reserved", C.c_uint32 * 6)]
+
+
+class UpdateReport(C.Structure):
+    _fields_ = [("refitted", C.c_uint32), ("photons_dropped", C.c_uint32), ("refit_ms", C.c_double),
+                ("total_ms", C.c_double), ("reserved", C.c_uint64 * 4)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
+
+
 RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("direction", "<f4", 3)])
 HIT_DTYPE = np.dtype([("hit", "<i4"), ("mesh", "<u4"), ("tri", "<u4"), ("vtx", "<u4", 3), ("u", "<f4"),
                       ("v", "<f4"), ("d", "<f4")])
@@ -96,7 +110,8 @@ AMD_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_create", "rt_destroy", "rt
                "rt_render", "rt_render_passes", "rt_render_device", "rt_resolve_device", "rt_trace", "rt_knn", "rt_knn_wide", "rt_bvh_info_get",
                "rt_bvh_export", "rt_bvh_build_host", "rt_bvh_check_host", "rt_bvh_top_check_host", "rt_bvh_tune", "rt_profile_reset", "rt_profile_collect", "rt_test_unit",
                "rt_trace_stream_device", "rt_build_photon_map", "rt_get_photons", "rt_test_kd_order", "rt_owned_granules", "rt_pack_owned_device", "rt_unpack_owned_device", "rt_group_create", "rt_group_destroy",
-               "rt_group_size", "rt_group_uses_rccl", "rt_group_ctx", "rt_group_set_photons", "rt_group_render"]
+               "rt_group_size", "rt_group_uses_rccl", "rt_group_ctx", "rt_group_set_photons", "rt_group_render",
+               "rt_update", "rt_update_vertices_device", "rt_group_update"]
 HOST_SYMBOLS = ["rt_host_scene_build", "rt_host_scene_desc", "rt_host_scene_free", "rt_host_last_error",
                 "rt_host_fill_background", "rt_host_save_ppm", "rt_host_kd_order"]
 
@@ -169,6 +184,9 @@ def amd():
         L.rt_group_ctx.restype = C.c_void_p
         L.rt_group_set_photons.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
         L.rt_group_render.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        L.rt_update.argtypes = [C.c_void_p, C.POINTER(SceneUpdate), C.POINTER(UpdateReport)]
+        L.rt_update_vertices_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(UpdateReport)]
+        L.rt_group_update.argtypes = [C.c_void_p, C.POINTER(SceneUpdate), C.POINTER(UpdateReport)]
         _amd = L
     return _amd
 
@@ -288,6 +306,35 @@ def kd_order(pos, dir_, weight=None):
     return pos, dir_, w
 
 
+def _scene_update(pos, nrm, camera, lights, materials):
+    """An rt_scene_update over numpy arrays (None = unchanged); returns it and the arrays it points into.
+    camera: [4][3] floats (position, lower_left, horizontal, vertical), lights: [n][21], materials: [n_meshes][8]."""
+    u = SceneUpdate()
+    keep = []
+
+    def arr(a, cols):
+        a = np.ascontiguousarray(a, np.float32).reshape(-1, cols)
+        keep.append(a)
+        return a
+    if pos is not None:
+        u.vertex_pos = arr(pos, 3).ctypes.data
+    if nrm is not None:
+        u.vertex_nrm = arr(nrm, 3).ctypes.data
+    if camera is not None:
+        u.camera = C.cast(arr(camera, 3).ctypes.data, C.POINTER(Camera))
+    if lights is not None:
+        a = arr(lights, 21)
+        # (a non-null pointer even for zero lights: NULL means "unchanged")
+        u.lights = C.cast(a.ctypes.data if len(a) else C.addressof(_NO_LIGHT), C.POINTER(Light))
+        u.n_lights = len(a)
+    if materials is not None:
+        u.materials = C.cast(arr(materials, 8).ctypes.data, C.POINTER(Material))
+    return u, keep
+
+
+_NO_LIGHT = Light()
+
+
 class Context:
     """rt_ctx: the scene resident in HBM on one gfx950 device."""
 
@@ -320,6 +367,22 @@ class Context:
         rep = TuneReport()
         _check(amd().rt_bvh_tune(self._h, C.byref(probe_params), float(budget_seconds), int(max_probes), C.byref(rep)))
         return rep
+
+    def update(self, pos=None, nrm=None, camera=None, lights=None, materials=None):
+        """rt_update: the resident scene follows the given arrays (None = unchanged; pos / nrm [n_vertices][3],
+        camera [4][3], lights [n][21], materials [n_meshes][8]).  Returns the report as a dict."""
+        u, _keep = _scene_update(pos, nrm, camera, lights, materials)
+        rep = UpdateReport()
+        _check(amd().rt_update(self._h, C.byref(u), C.byref(rep)))
+        return rep.as_dict()
+
+    def update_vertices_device(self, d_pos, d_nrm, stream=0):
+        """rt_update_vertices_device: positions / normals already in device memory (pointers, 0 = unchanged), ordered
+        on `stream`.  Returns the report as a dict."""
+        rep = UpdateReport()
+        _check(amd().rt_update_vertices_device(self._h, C.c_void_p(d_pos or None), C.c_void_p(d_nrm or None),
+                                               C.c_void_p(stream or None), C.byref(rep)))
+        return rep.as_dict()
 
     def bvh_export(self):
         bi = self.bvh_info()
@@ -481,6 +544,13 @@ class Group:
         pos = np.ascontiguousarray(pos, np.float32)
         dir_ = np.ascontiguousarray(dir_, np.float32)
         _check(amd().rt_group_set_photons(self._h, _ptr(pos), _ptr(dir_), len(pos)))
+
+    def update(self, pos=None, nrm=None, camera=None, lights=None, materials=None):
+        """rt_group_update: Context.update on every rank; rank 0's report."""
+        u, _keep = _scene_update(pos, nrm, camera, lights, materials)
+        rep = UpdateReport()
+        _check(amd().rt_group_update(self._h, C.byref(u), C.byref(rep)))
+        return rep.as_dict()
 
     def render(self, params, bg=None, want_accum=True):
         w, h = params.width, params.height
