@@ -7,7 +7,9 @@ A "step" is one whole frame: zero the accumulator, integrate every sample of eve
 owned pixel (one HIP launch per rank), assemble the frame over ranks (N>1), resolve on
 rank 0.  Metric: Mrays/s = (closest-hit + shadow rays actually cast) / wall time, whole job.
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run does only what the headline figure needs: it sets up the scene, counts the rays of one
+frame (one untimed counted pass), warms up, times the K steps and prints the JSON line.
 --dump-outputs DIR writes the last timed step's frame as DIR/image.npy (resolved RGB) and
 DIR/accum.npy (the accumulator), float32; see dump_outputs() for frames above 64 MB.
 With N>1 and no WORLD_SIZE in the environment the script starts its own
@@ -19,11 +21,13 @@ The JSON line carries
   roofline      the roof that BINDS the dominant kernel: VALU issue rate for the cache-
                 resident scenes (C1-C4; SQ_INSTS_VALU of the timed kernel / its time against
                 1024 SIMDs x 2.4 GHz / 2 cycles per wave64 op), HBM bytes for the 1M-triangle
-                scene (C5).  Counters are measured IN THIS RUN by rocprofv3 child passes
-                (N=1 only; --no-pmc skips them and falls back to profiles/, marked as such).
-  cpu_baseline  the reference's own code timed on the host beside it, plus the CPU
-                restatement with and without a BVH and the GPU exhaustive kernel, so that
+                scene (C5).  With --full the counters are measured IN THIS RUN by rocprofv3
+                child passes (at N > 1 over rank 0's shard); at N = 1 a plain run or --no-pmc
+                takes them from profiles/ when the kernel source matches, marked as such.
+  cpu_baseline  (--full only) the reference's own code timed on the host beside it, plus the
+                CPU restatement with and without a BVH and the GPU exhaustive kernel, so that
                 the hardware gain and the algorithmic gain can be read separately.
+--full also times a second rt_create once the process is warm (config.bvh.build_ms).
 """
 import argparse
 import csv
@@ -337,13 +341,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="C2", choices=sorted(WORKLOADS))
     ap.add_argument("--spp", type=int, default=0, help="override samples per pixel (debug only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure, measure what takes runs of its own: the rocprofv3 counter passes, the "
+                         "CPU baseline and a warm rt_create (about two minutes more on C2)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-baseline-full", action="store_true", default=True,
-                    help="also time the reference's code on BASELINE config 1 at its stated size (256x256, -m 1 -N 8: ~65 s of "
-                         "one host core; the default since round 3: VERDICT r02 item 8)")
+                    help="with --full: also time the reference's code on BASELINE config 1 at its stated size (256x256, -m 1 "
+                         "-N 8: ~65 s of one host core; the default since round 3: VERDICT r02 item 8)")
     ap.add_argument("--no-cpu-baseline-full", dest="cpu_baseline_full", action="store_false",
-                    help="only the bounded 96x96 sample (~10 s)")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 counter passes")
+                    help="with --full: only the bounded 96x96 sample (~10 s)")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: skip the rocprofv3 counter passes")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--pmc-rank", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--pmc-world", type=int, default=1, help=argparse.SUPPRESS)
@@ -381,7 +388,9 @@ def main():
     # kernels would land in rank 0's device-wide counters, and under RCCL they would sit in their first collective for as
     # long as the passes take.  The ranks of one launcher share its pid as parent: a marker file keyed by it is the gate.)
     gate = os.path.join(tempfile.gettempdir(), "rt_bench_pmc_%d_%s.done" % (os.getppid(), os.environ.get("MASTER_PORT", "0")))
-    if args.integrator != "fused":
+    if not args.full:
+        pmc_source = "not measured: a plain run (--full measures them)"
+    elif args.integrator != "fused":
         pmc_source = "skipped: the counters are defined for the fused kernel (the wavefront integrator is several kernels)"
     elif rank_env == 0 and not args.no_pmc:
         if os.path.exists(gate):
@@ -579,15 +588,17 @@ def main():
                        "rays_per_frame": rays_per_frame, "samples_per_frame": tot[4],
                        "knn_queries_per_frame": tot[5],
                        # (outside the timed region: the scene's tree, who built it and how long rt_create's build took —
-                       # the process's first rt_create, which also loads the code objects, and a second one)
+                       # the process's first rt_create, which also loads the code objects, and with --full a second one)
                        "bvh": {"builder": {1: "device", 2: "hybrid", 3: "host"}.get(ctx.bvh_info().builder, "host"),
-                               "build_ms_first_create": ctx.bvh_info().build_ms, "build_ms": second_build_ms(pyrt, scene, local, args),
+                               "build_ms_first_create": ctx.bvh_info().build_ms,
                                "nodes": ctx.bvh_info().n_nodes, "max_depth": ctx.bvh_info().max_depth}},
             "roofline": roof,
         }
+        if args.full:
+            res["config"]["bvh"]["build_ms"] = second_build_ms(pyrt, scene, local, args)
         if tuned:
             res["config"]["bvh_tune"] = tuned
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # (rank 0 only, after the timed region; at N > 1 the other ranks have left the job by now)
             rdist.shutdown()
             cb = cpu_baseline(ctx, kind, mode, dev, full=args.cpu_baseline_full)

@@ -86,12 +86,12 @@ def test_bench_two_ranks_rehearsal_on_one_gpu(tmp_path):
     env = dict(os.environ, RT_DIST_BACKEND="gloo", RT_SHARE_GPU="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29711", os.path.join(pyrt.ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
-           "--workload", "C1", "--dump-outputs", str(tmp_path / "two")]
+           "--workload", "C1", "--full", "--dump-outputs", str(tmp_path / "two")]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900, cwd=tmp_path)
     assert r.returncode == 0, r.stderr[-3000:]
     two = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     r1 = subprocess.run([sys.executable, os.path.join(pyrt.ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--workload", "C1",
-                         "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "one")], capture_output=True, text=True, timeout=300,
+                         "--full", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "one")], capture_output=True, text=True, timeout=300,
                         cwd=tmp_path)
     one = json.loads([l for l in r1.stdout.splitlines() if l.startswith("{")][-1])
     # the frame rank 0 assembled from both ranks' tiles is the one-rank frame, bit for bit
@@ -131,6 +131,31 @@ def test_bench_dump_outputs_is_the_timed_frame(tmp_path):
     assert np.array_equal(img.view(np.uint32), ref_out.view(np.uint32))
 
 
+def test_bench_plain_run_is_only_the_headline(tmp_path):
+    """A plain run (no --full) measures nothing beside its headline figure: no counter passes, no CPU baseline, no
+    second rt_create; its line still says what the figure is and carries the counted pass's ray count.  The same at
+    N = 2 (two gloo ranks sharing this GPU), where no rank waits for counter passes."""
+    import json
+    import sys
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    env.update(RT_DIST_BACKEND="gloo", RT_SHARE_GPU="1", MASTER_PORT="29747")
+    for gpus in (1, 2):
+        r = subprocess.run([sys.executable, os.path.join(pyrt.ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "2", "--warmup", "1",
+                            "--workload", "C1"], capture_output=True, text=True, env=env, timeout=300, cwd=tmp_path)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d
+        assert d["unit"] == "Mrays/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert d["n_gpus"] == gpus and d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+        assert d["config"]["rays_per_frame"] == 5526901 and d["roofline"]["launches"] == 2
+        assert "cpu_baseline" not in d and "build_ms" not in d["config"]["bvh"]
+        assert "counters_per_launch" not in d["roofline"] or d["roofline"]["traffic_source"].startswith("profiles/")
+        assert "--full" in d["roofline"]["traffic_source"]
+
+
 def test_bench_spawns_its_own_launcher(tmp_path):
     """`python bench.py --gpus N` with no launcher in the environment starts
     torch.distributed.run itself (as a child, before touching the GPU) and rank 0 still prints the
@@ -140,7 +165,7 @@ def test_bench_spawns_its_own_launcher(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(RT_DIST_BACKEND="gloo", RT_SHARE_GPU="1", MASTER_PORT="29733")
     r = subprocess.run([sys.executable, os.path.join(pyrt.ROOT, "bench.py"), "--gpus", "3", "--steps", "2", "--warmup", "1",
-                        "--workload", "C1"], capture_output=True, text=True, env=env, timeout=900, cwd=tmp_path)
+                        "--workload", "C1", "--full"], capture_output=True, text=True, env=env, timeout=900, cwd=tmp_path)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
