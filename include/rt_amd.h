@@ -16,6 +16,8 @@
  *   rt_render                   <- the spp/y/x loop + resolve (Renderer.cpp:219-271)
  *   rt_render_device/_resolve_device : same, on caller-owned DEVICE buffers and a
  *                                  caller stream (multi-GPU tile sharding, bench)
+ *   rt_render_aov / rt_denoise  <- (no counterpart) first-hit AOVs of a frame's primary rays, and the a-trous
+ *                                  filter of a low-spp frame guided by them (+ _device forms)
  *   rt_trace                    <- RayTracer::rayTrace (RayTracer.h:27-53) test hook
  *   rt_knn / rt_knn_wide        <- kdtree::knearest (kdtree.h:180-195) test hooks
  *
@@ -270,6 +272,52 @@ int rt_render_device(rt_ctx* ctx, const rt_params* p, void* d_accum, void* strea
 int rt_resolve_device(rt_ctx* ctx, uint32_t width, uint32_t height, uint32_t spp,
                       const void* d_accum, const void* d_background_rgb,
                       void* d_out_rgb, void* stream);
+
+/* ---- first-hit AOVs and the a-trous denoiser (DESIGN.md "AOVs and the a-trous denoiser") ---------------------------
+ * rt_render_aov casts exactly the primary rays of the frame p describes — sample i of pixel (x, y) for i in the sample
+ * range (spp_begin / spp_count, or 0..spp), from the same stream seed, jitter_sample(i, spp) and camera_ray — through the
+ * context's tree (or the exhaustive loop for RT_ACCEL_BRUTE), so its hit is the frame's primary hit, and sums per pixel,
+ * in float32 in sample order (as rt_render forms accum), what the frame's first vertex sees.  A miss adds nothing.  Sums,
+ * not means: ranges chain, and the caller divides by hits.  Every pointer may be NULL (channel not wanted); the others
+ * are overwritten.  mode, max_depth, use_photons, k and photons_requested do not affect the pass; world > 1 returns
+ * RT_ERR_UNSUPPORTED (tile-sharded AOVs are out of scope); sizes and ranges are checked as rt_render checks them.
+ * RT_NODES_Q8 contexts run the pass on their 32-byte records (resident for the other kernels): the same hits.          */
+typedef struct rt_aov {
+  float* albedo;     /* [h][w][3] sum over hit samples of the hit mesh's material albedo                          */
+  float* normal;     /* [h][w][3] sum of the shading normal (Renderer.cpp:42)                                     */
+  float* position;   /* [h][w][3] sum of the hit point (Renderer.cpp:43)                                          */
+  float* depth;      /* [h][w]    sum of the hit distance t (rt_hit.d)                                            */
+  uint32_t* hits;    /* [h][w]    samples whose primary ray hit (== the w channel of rt_render's accum)           */
+  uint32_t* mesh;    /* [h][w]    mesh of sample spp_begin's primary hit, 0xffffffff = miss                       */
+  uint32_t* tri;     /* [h][w]    triangle within that mesh,              0xffffffff = miss                       */
+  uint32_t reserved[4];
+} rt_aov;
+int rt_render_aov(rt_ctx* ctx, const rt_params* p, const rt_aov* host_out);
+/* The same into DEVICE buffers (e.g. torch tensors) on `stream` (a hipStream_t, may be NULL); no synchronisation. */
+int rt_render_aov_device(rt_ctx* ctx, const rt_params* p, const rt_aov* device_out, void* stream);
+
+/* The edge-avoiding a-trous wavelet filter (Dammertz et al., HPG 2010) guided by the AOVs, with albedo demodulation.
+ * Guides a = albedo/hits, n = normal/hits, x = position/hits where hits > 0; a pixel with hits == 0 passes through
+ * unchanged and weighs 0 as a tap.  Filtered: c = rgb / max(a, 1e-3); iteration i (from 0) has step s = 2^i, taps
+ * q = p + s(dx, dy), dx, dy in -2..2 inside the image, weights h[dx] h[dy] exp(-|c_p-c_q|^2/sc_i^2)
+ * exp(-|n_p-n_q|^2/sn^2) exp(-|x_p-x_q|^2/sx^2) with h = {1/16, 1/4, 3/8, 1/4, 1/16} and sc_i = sc 2^-i, output
+ * sum(w c_q) / sum(w), the next iteration's input; the result times max(a, 1e-3).
+ * Defaults (0): iterations 5, sigma_color 2, sigma_normal 0.5, sigma_position 2 % of the diagonal of the bounding box
+ * of the vertices the context's triangles reference.  RT_ERR_INVALID: null arguments or guides, a size outside
+ * 1..65535, iterations above 8, a negative or non-finite sigma.                                                       */
+typedef struct rt_denoise_params {
+  uint32_t width, height;
+  uint32_t iterations;                             /* 0 = 5; at most 8                 */
+  float sigma_color, sigma_normal, sigma_position; /* 0 = the defaults above           */
+  uint32_t reserved[6];
+} rt_denoise_params;
+/* rgb: a resolved frame [h][w][3] (rt_render's out_rgb); aov: the SUMS of rt_render_aov for the same params (albedo,
+ * normal, position, hits required); out: [h][w][3].  rgb may equal out. */
+int rt_denoise(rt_ctx* ctx, const rt_denoise_params* d, const float* rgb, const rt_aov* aov, float* out);
+/* The same on DEVICE buffers, ordered on `stream` (may be NULL); no synchronisation.  A launch like any other: the
+ * context's scratch serves one call at a time. */
+int rt_denoise_device(rt_ctx* ctx, const rt_denoise_params* d, const void* d_rgb, const rt_aov* d_aov, void* d_out,
+                      void* stream);
 
 /* ---- multi-GPU (Renderer.cpp:219-265 sharded by pixel tiles) -------------
  * A tile-sharded frame: rank r of `world` integrates the pixels whose `tile`-pixel granule

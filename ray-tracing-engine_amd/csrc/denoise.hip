@@ -1,0 +1,155 @@
+// denoise.hip — the edge-avoiding a-trous wavelet filter (Dammertz et al., HPG 2010) guided by the first-hit AOVs of
+// rt_render_aov, with albedo demodulation: rt_denoise.  DESIGN.md "AOVs and the a-trous denoiser" defines it; every
+// kernel here is one lane per pixel.
+//
+//   k_dn_extent  bounding box of the vertices the triangles reference (only when the caller leaves sigma_position 0)
+//   k_dn_sigma   1 / sigma_position^2 into device memory (default: 2 % of that box's diagonal), read by every iteration
+//   k_dn_pack    per pixel the guides as two float4 (normal + validity flag, position), the albedo factor
+//                max(albedo / hits, 1e-3) and the demodulated colour rgb / factor (pixels without a hit: rgb itself)
+//   k_dn_iter    one iteration (step 2^i): 5x5 taps straight from global memory through L1 / L2; the last one
+//                multiplies the factor back and writes the [h][w][3] output
+#include <hip/hip_runtime.h>
+
+#include <math.h>
+
+#include "rt_kernels.h"
+
+namespace rtk {
+namespace {
+
+// order-preserving float <-> uint32 (atomicMin / atomicMax on the bits)
+__device__ __forceinline__ uint32_t f2o(float f) {
+  const uint32_t u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float o2f(uint32_t u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u); }
+
+// ext[0..2] = min x, y, z (initialised to 0xffffffff), ext[3..5] = max (initialised to 0)
+__global__ __launch_bounds__(256) void k_dn_extent(const float* __restrict__ vpos, const uint4* __restrict__ triShade,
+                                                   uint32_t nTris, uint32_t* __restrict__ ext) {
+  float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < nTris; t += gridDim.x * blockDim.x) {
+    const uint4 tv = triShade[t];
+    const uint32_t v[3] = {tv.x, tv.y, tv.z};
+    for (int k = 0; k < 3; k++)
+      for (int a = 0; a < 3; a++) {
+        const float c = vpos[3 * (size_t)v[k] + a];
+        lo[a] = fminf(lo[a], c), hi[a] = fmaxf(hi[a], c);
+      }
+  }
+  for (int off = 32; off > 0; off >>= 1)
+    for (int a = 0; a < 3; a++) lo[a] = fminf(lo[a], __shfl_xor(lo[a], off, 64)), hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], off, 64));
+  if ((threadIdx.x & 63u) == 0)
+    for (int a = 0; a < 3; a++) atomicMin(&ext[a], f2o(lo[a])), atomicMax(&ext[3 + a], f2o(hi[a]));
+}
+
+__global__ void k_dn_sigma(const uint32_t* __restrict__ ext, float sigma, float* __restrict__ isx) {
+  if (sigma <= 0.f) {
+    const float dx = o2f(ext[3]) - o2f(ext[0]), dy = o2f(ext[4]) - o2f(ext[1]), dz = o2f(ext[5]) - o2f(ext[2]);
+    sigma = 0.02f * sqrtf((dx * dx + dy * dy) + dz * dz);
+    if (!(sigma > 0.f) || !(sigma < INFINITY)) sigma = 1.f;  // (a flat or empty scene: any scale does)
+  }
+  *isx = 1.f / (sigma * sigma);
+}
+
+__global__ __launch_bounds__(256) void k_dn_pack(uint32_t n, const float* __restrict__ rgb, const float* __restrict__ alb,
+                                                 const float* __restrict__ nrm, const float* __restrict__ pos,
+                                                 const uint32_t* __restrict__ hits, float4* __restrict__ g0,
+                                                 float4* __restrict__ g1, float4* __restrict__ fac, float4* __restrict__ col) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const size_t i3 = 3 * (size_t)i;
+  const float r = rgb[i3], g = rgb[i3 + 1], b = rgb[i3 + 2];
+  const uint32_t h = hits[i];
+  if (h == 0) {  // passes through, weight 0 as a tap
+    g0[i] = make_float4(0.f, 0.f, 0.f, 0.f), g1[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    fac[i] = make_float4(1.f, 1.f, 1.f, 0.f), col[i] = make_float4(r, g, b, 0.f);
+    return;
+  }
+  const float fh = (float)h;
+  const float ax = fmaxf(alb[i3] / fh, 1e-3f), ay = fmaxf(alb[i3 + 1] / fh, 1e-3f), az = fmaxf(alb[i3 + 2] / fh, 1e-3f);
+  g0[i] = make_float4(nrm[i3] / fh, nrm[i3 + 1] / fh, nrm[i3 + 2] / fh, 1.f);
+  g1[i] = make_float4(pos[i3] / fh, pos[i3 + 1] / fh, pos[i3 + 2] / fh, 0.f);
+  fac[i] = make_float4(ax, ay, az, 0.f);
+  col[i] = make_float4(r / ax, g / ay, b / az, 0.f);
+}
+
+__device__ __forceinline__ float sq3(float4 a, float4 b) {
+  const float x = a.x - b.x, y = a.y - b.y, z = a.z - b.z;
+  return (x * x + y * y) + z * z;
+}
+
+// 16x16 pixels per workgroup (four waves of 16x4)
+__global__ __launch_bounds__(256) void k_dn_iter(uint32_t W, uint32_t H, int step, float isc, float isn,
+                                                 const float* __restrict__ isxp, const float4* __restrict__ g0,
+                                                 const float4* __restrict__ g1, const float4* __restrict__ fac,
+                                                 const float4* __restrict__ cin, float4* __restrict__ cout,
+                                                 float* __restrict__ out) {
+  const int x = (int)(blockIdx.x * 16u + (threadIdx.x & 15u)), y = (int)(blockIdx.y * 16u + (threadIdx.x >> 4));
+  if (x >= (int)W || y >= (int)H) return;
+  const size_t p = (size_t)y * W + x;
+  const float4 np = g0[p], cp = cin[p];
+  float4 res = cp;
+  if (np.w != 0.f) {
+    const float4 xp = g1[p];
+    const float isx = *isxp;
+    const float kh[5] = {1.f / 16.f, 1.f / 4.f, 3.f / 8.f, 1.f / 4.f, 1.f / 16.f};
+    float sr = 0.f, sg = 0.f, sb = 0.f, sw = 0.f;
+    for (int j = 0; j < 5; j++) {
+      const int yy = y + (j - 2) * step;
+      if (yy < 0 || yy >= (int)H) continue;
+      for (int i = 0; i < 5; i++) {
+        const int xx = x + (i - 2) * step;
+        if (xx < 0 || xx >= (int)W) continue;
+        const size_t q = (size_t)yy * W + xx;
+        const float4 nq = g0[q];
+        if (nq.w == 0.f) continue;
+        const float4 cq = cin[q], xq = g1[q];
+        const float w = kh[i] * kh[j] * expf(-(sq3(cp, cq) * isc + sq3(np, nq) * isn + sq3(xp, xq) * isx));
+        sr += w * cq.x, sg += w * cq.y, sb += w * cq.z, sw += w;
+      }
+    }
+    res = make_float4(sr / sw, sg / sw, sb / sw, 0.f);  // (sw >= (3/8)^2: the centre tap)
+  }
+  if (!out) {
+    cout[p] = res;
+    return;
+  }
+  const float4 f = fac[p];  // (1, 1, 1 for pixels without a hit: res is their rgb)
+  out[3 * p] = np.w != 0.f ? res.x * f.x : res.x;
+  out[3 * p + 1] = np.w != 0.f ? res.y * f.y : res.y;
+  out[3 * p + 2] = np.w != 0.f ? res.z * f.z : res.z;
+}
+
+}  // namespace
+
+hipError_t launch_denoise(const DevScene& S, const DenoiseArgs& D, hipStream_t stream) {
+  const size_t n = (size_t)D.width * D.height;
+  if (n == 0) return hipSuccess;
+  float4 *g0 = D.scratch, *g1 = g0 + n, *fac = g1 + n, *ca = fac + n, *cb = ca + n;
+  uint32_t* ext = reinterpret_cast<uint32_t*>(cb + n);  // 6 words, then 1 / sigma_position^2
+  float* isx = reinterpret_cast<float*>(ext + 8);
+  hipError_t e;
+  if (D.sigma_position <= 0.f) {
+    if ((e = hipMemsetAsync(ext, 0xff, 3 * sizeof(uint32_t), stream)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(ext + 3, 0, 3 * sizeof(uint32_t), stream)) != hipSuccess) return e;
+    const uint32_t blocks = S.n_tris ? (S.n_tris + 255u) / 256u < 1024u ? (S.n_tris + 255u) / 256u : 1024u : 1u;
+    hipLaunchKernelGGL(k_dn_extent, dim3(blocks), dim3(256), 0, stream, S.vpos, S.triShade, S.n_tris, ext);
+  }
+  hipLaunchKernelGGL(k_dn_sigma, dim3(1), dim3(1), 0, stream, ext, D.sigma_position, isx);
+  hipLaunchKernelGGL(k_dn_pack, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, (uint32_t)n, D.rgb, D.albedo, D.normal,
+                     D.position, D.hits, g0, g1, fac, ca);
+  const dim3 grid((D.width + 15u) / 16u, (D.height + 15u) / 16u);
+  const float isn = 1.f / (D.sigma_normal * D.sigma_normal);
+  for (uint32_t it = 0; it < D.iterations; it++) {
+    const float sc = D.sigma_color * ldexpf(1.f, -(int)it);  // the colour sigma halves every iteration
+    const bool last = it + 1 == D.iterations;
+    hipLaunchKernelGGL(k_dn_iter, grid, dim3(256), 0, stream, D.width, D.height, 1 << it, 1.f / (sc * sc), isn, isx, g0, g1, fac,
+                       ca, cb, last ? D.out : nullptr);
+    float4* t = ca;
+    ca = cb, cb = t;
+  }
+  return hipGetLastError();
+}
+
+}  // namespace rtk

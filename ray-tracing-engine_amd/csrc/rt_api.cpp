@@ -180,6 +180,9 @@ struct rt_ctx {
   uint32_t refitMaxDepth = 0;
   DevBuf<float> updPos, updNrm;
   DevBuf<uint32_t> dMag;
+  // scratch of rt_denoise_device (guides, albedo factors, two colour buffers; grows on demand)
+  DevBuf<float4> dnScratch;
+  size_t dnCap = 0;
 };
 
 namespace {
@@ -1946,6 +1949,136 @@ int rt_group_update(rt_group* g, const rt_scene_update* u, rt_update_report* rep
   (void)hipSetDevice(g->dev[0]);
   first.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (rep) *rep = first;
+  return RT_OK;
+}
+
+}  // extern "C"
+
+// ---- first-hit AOVs and the a-trous denoiser -------------------------------------------------------------------------
+namespace {
+
+// the defaults of rt_denoise_params (rt_amd.h, DESIGN.md "AOVs and the a-trous denoiser": chosen on C1 / C2 frames)
+constexpr uint32_t kDenoiseIterations = 5;
+constexpr float kDenoiseSigmaColor = 2.f, kDenoiseSigmaNormal = 0.5f;
+
+// rt_render_aov's own view of p: the fields that do not affect the pass are neutralised before rt_render's checks
+int aov_checks(const rt_ctx* c, const rt_params* p, rt_params* q) {
+  if (!c) return fail(RT_ERR_INVALID, "ctx is null");
+  if (!p) return fail(RT_ERR_INVALID, "params is null");
+  *q = *p;
+  q->mode = RT_MODE_RAY, q->max_depth = 1, q->use_photons = 0, q->k = 0, q->photons_requested = 0;
+  int rc = check_params(c, q);
+  if (rc != RT_OK) return rc;
+  if (q->world > 1) return fail(RT_ERR_UNSUPPORTED, "tile-sharded AOVs (world %u) are not supported", q->world);
+  return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_render_aov_device(rt_ctx* c, const rt_params* p, const rt_aov* out, void* stream) {
+  rt_params q;
+  int rc = aov_checks(c, p, &q);
+  if (rc != RT_OK) return rc;
+  if (!out) return fail(RT_ERR_INVALID, "aov is null");
+  HIP_TRY(hipSetDevice(c->device));
+  rtk::AovArgs A;
+  A.albedo = out->albedo, A.normal = out->normal, A.position = out->position, A.depth = out->depth;
+  A.hits = out->hits, A.mesh = out->mesh, A.tri = out->tri;
+  A.width = q.width, A.height = q.height, A.spp = q.spp, A.seed = q.seed;
+  A.s0 = q.spp_count ? q.spp_begin : 0;
+  A.s1 = q.spp_count ? q.spp_begin + q.spp_count : q.spp;
+  const hipError_t he = rtk::launch_aov(q.accel == RT_ACCEL_BRUTE, c->S, A, static_cast<hipStream_t>(stream));
+  if (he != hipSuccess) return fail(RT_ERR_HIP, "AOV launch failed: %s", hipGetErrorString(he));
+  return RT_OK;
+}
+
+int rt_render_aov(rt_ctx* c, const rt_params* p, const rt_aov* out) {
+  rt_params q;
+  int rc = aov_checks(c, p, &q);
+  if (rc != RT_OK) return rc;
+  if (!out) return fail(RT_ERR_INVALID, "aov is null");
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t npx = (size_t)q.width * q.height;
+  DevBuf<float> dF[4];
+  DevBuf<uint32_t> dU[3];
+  float* const hF[4] = {out->albedo, out->normal, out->position, out->depth};
+  uint32_t* const hU[3] = {out->hits, out->mesh, out->tri};
+  const size_t wF[4] = {3, 3, 3, 1};
+  for (int i = 0; i < 4; ++i)
+    if (hF[i]) HIP_TRY(dev_alloc(&dF[i], npx * wF[i]));
+  for (int i = 0; i < 3; ++i)
+    if (hU[i]) HIP_TRY(dev_alloc(&dU[i], npx));
+  rt_aov d = {};
+  d.albedo = dF[0].get(), d.normal = dF[1].get(), d.position = dF[2].get(), d.depth = dF[3].get();
+  d.hits = dU[0].get(), d.mesh = dU[1].get(), d.tri = dU[2].get();
+  if ((rc = rt_render_aov_device(c, &q, &d, nullptr)) != RT_OK) return rc;
+  for (int i = 0; i < 4; ++i)
+    if (hF[i]) HIP_TRY(hipMemcpy(hF[i], dF[i].get(), npx * wF[i] * sizeof(float), hipMemcpyDeviceToHost));
+  for (int i = 0; i < 3; ++i)
+    if (hU[i]) HIP_TRY(hipMemcpy(hU[i], dU[i].get(), npx * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return RT_OK;
+}
+
+int rt_denoise_device(rt_ctx* c, const rt_denoise_params* d, const void* d_rgb, const rt_aov* aov, void* d_out, void* stream) {
+  if (!c || !d || !d_rgb || !aov || !d_out) return fail(RT_ERR_INVALID, "null argument");
+  if (!aov->albedo || !aov->normal || !aov->position || !aov->hits)
+    return fail(RT_ERR_INVALID, "the denoiser needs the albedo, normal, position and hits channels");
+  if (c->broken) return fail(RT_ERR_STATE, "the context's device tree is in an unknown state: destroy it");
+  if (d->width == 0 || d->height == 0 || d->width > 65535u || d->height > 65535u)
+    return fail(RT_ERR_INVALID, "image size %ux%u out of range", d->width, d->height);
+  if (d->iterations > 8) return fail(RT_ERR_INVALID, "iterations %u > 8", d->iterations);
+  const float sg[3] = {d->sigma_color, d->sigma_normal, d->sigma_position};
+  for (float s : sg)
+    if (!(s >= 0.f) || !std::isfinite(s)) return fail(RT_ERR_INVALID, "sigmas must be finite and >= 0");
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t need = rtk::denoise_scratch(d->width, d->height);
+  if (need > c->dnCap) {
+    c->dnCap = 0;
+    if (c->dnScratch) HIP_TRY(hipFree(c->dnScratch.release()));
+    HIP_TRY(dev_alloc(&c->dnScratch, need));
+    c->dnCap = need;
+  }
+  rtk::DenoiseArgs D;
+  D.width = d->width, D.height = d->height;
+  D.iterations = d->iterations ? d->iterations : kDenoiseIterations;
+  D.sigma_color = d->sigma_color > 0.f ? d->sigma_color : kDenoiseSigmaColor;
+  D.sigma_normal = d->sigma_normal > 0.f ? d->sigma_normal : kDenoiseSigmaNormal;
+  D.sigma_position = d->sigma_position;  // 0: the device derives it from the scene's extent
+  D.rgb = static_cast<const float*>(d_rgb), D.albedo = aov->albedo, D.normal = aov->normal, D.position = aov->position;
+  D.hits = aov->hits, D.out = static_cast<float*>(d_out), D.scratch = c->dnScratch.get();
+  const hipError_t he = rtk::launch_denoise(c->S, D, static_cast<hipStream_t>(stream));
+  if (he != hipSuccess) return fail(RT_ERR_HIP, "denoise launch failed: %s", hipGetErrorString(he));
+  return RT_OK;
+}
+
+int rt_denoise(rt_ctx* c, const rt_denoise_params* d, const float* rgb, const rt_aov* aov, float* out) {
+  if (!c || !d || !rgb || !aov || !out) return fail(RT_ERR_INVALID, "null argument");
+  if (!aov->albedo || !aov->normal || !aov->position || !aov->hits)
+    return fail(RT_ERR_INVALID, "the denoiser needs the albedo, normal, position and hits channels");
+  if (d->width == 0 || d->height == 0 || d->width > 65535u || d->height > 65535u)
+    return fail(RT_ERR_INVALID, "image size %ux%u out of range", d->width, d->height);
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t npx = (size_t)d->width * d->height;
+  DevBuf<float> dRgb, dAlb, dNrm, dPos, dOut;
+  DevBuf<uint32_t> dHits;
+  HIP_TRY(dev_alloc(&dRgb, 3 * npx));
+  HIP_TRY(dev_alloc(&dAlb, 3 * npx));
+  HIP_TRY(dev_alloc(&dNrm, 3 * npx));
+  HIP_TRY(dev_alloc(&dPos, 3 * npx));
+  HIP_TRY(dev_alloc(&dOut, 3 * npx));
+  HIP_TRY(dev_alloc(&dHits, npx));
+  HIP_TRY(hipMemcpy(dRgb.get(), rgb, 3 * npx * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dAlb.get(), aov->albedo, 3 * npx * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dNrm.get(), aov->normal, 3 * npx * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dPos.get(), aov->position, 3 * npx * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dHits.get(), aov->hits, npx * sizeof(uint32_t), hipMemcpyHostToDevice));
+  rt_aov da = {};
+  da.albedo = dAlb.get(), da.normal = dNrm.get(), da.position = dPos.get(), da.hits = dHits.get();
+  int rc = rt_denoise_device(c, d, dRgb.get(), &da, dOut.get(), nullptr);
+  if (rc != RT_OK) return rc;
+  HIP_TRY(hipMemcpy(out, dOut.get(), 3 * npx * sizeof(float), hipMemcpyDeviceToHost));
   return RT_OK;
 }
 

@@ -100,6 +100,26 @@ struct WfArgs {
 hipError_t launch_wavefront(const DevScene& S, const WfArgs& W, uint32_t mode, uint32_t maxDepth, float4* accum,
                             unsigned long long* counters, uint32_t* queueCounter, uint32_t stackLevels, uint32_t numCUs,
                             hipStream_t stream);
+// first-hit AOVs of a frame's primary rays (aov_kernels.h, rt_render_aov): sums over the samples [s0, s1) of every pixel;
+// null channels are not written
+struct AovArgs {
+  float *albedo, *normal, *position, *depth;  // [h][w][3], [h][w][3], [h][w][3], [h][w]
+  uint32_t *hits, *mesh, *tri;                // [h][w] each
+  uint32_t width, height, spp, seed, s0, s1;
+};
+hipError_t launch_aov(bool brute_force, const DevScene& S, const AovArgs& A, hipStream_t stream);
+// the edge-avoiding a-trous filter (denoise.hip, rt_denoise): inputs and output [h][w][3] / [h][w], device memory;
+// scratch = 5 * w * h + 4 float4 (rtk::denoise_scratch)
+struct DenoiseArgs {
+  uint32_t width, height, iterations;
+  float sigma_color, sigma_normal, sigma_position;  // sigma_position 0: 2 % of the referenced vertices' box diagonal
+  const float *rgb, *albedo, *normal, *position;
+  const uint32_t* hits;
+  float* out;
+  float4* scratch;
+};
+inline size_t denoise_scratch(uint32_t w, uint32_t h) { return 5 * (size_t)w * h + 4; }
+hipError_t launch_denoise(const DevScene& S, const DenoiseArgs& D, hipStream_t stream);
 // ray queue in HBM -> results (wavefront stage T)
 hipError_t launch_trace_stream(const DevScene& S, const float4* rayO, const float4* rayD, uint32_t n, uint2* res,
                                uint32_t* counter, uint32_t stackLevels, uint32_t numCUs, hipStream_t stream);

@@ -27,6 +27,8 @@ int main(int argc, char** argv) {
   GpuSettings::get().accel = args.accel() ? RT_ACCEL_BRUTE : RT_ACCEL_BVH;
   GpuSettings::get().progress = static_cast<unsigned>(args.progress());
   GpuSettings::get().tune = args.tune();
+  GpuSettings::get().denoise = args.denoise() != 0;
+  GpuSettings::get().aov = args.aov() != 0;
   // -gpus N: devices gpu..gpu+N-1; -devices a,b,c: an explicit list (may repeat a device:
   // rehearsal of the N-rank flow on one GPU)
   if (!args.devices().empty()) {
@@ -42,6 +44,10 @@ int main(int argc, char** argv) {
     for (size_t i = 0; i < args.gpus(); ++i) GpuSettings::get().devices.push_back(static_cast<int>(args.gpu() + i));
   }
 
+  if ((args.denoise() || args.aov()) && GpuSettings::get().devices.size() > 1) {
+    std::cerr << "error: -denoise / -aov run on one GPU only (not with -gpus > 1)" << std::endl;
+    return 1;
+  }
   try {
     Image image(args.width(), args.height());
     Scene scene = rtpreset::buildCornellScene(args.scene(), args.meshDir(), args.width(), args.height());
@@ -57,6 +63,11 @@ int main(int argc, char** argv) {
     image.fillBackground();
     renderer.render(image);
     image.savePPM(args.outputFilename());
+    // -denoise / -aov: <stem>_denoised.ppm, <stem>_albedo.ppm, <stem>_normal.ppm next to the output
+    const std::string& of = args.outputFilename();
+    const std::string stem = of.size() > 4 && of.compare(of.size() - 4, 4, ".ppm") == 0 ? of.substr(0, of.size() - 4) : of;
+    if (args.denoise()) renderer.denoised().savePPM(stem + "_denoised.ppm");
+    if (args.aov()) renderer.albedo().savePPM(stem + "_albedo.ppm"), renderer.normal().savePPM(stem + "_normal.ppm");
 
     const rt_stats& st = renderer.lastStats();
     const double rays = static_cast<double>(st.rays_closest + st.rays_shadow);

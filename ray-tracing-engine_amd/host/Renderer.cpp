@@ -110,4 +110,33 @@ inline void Renderer::render(Image& image) {
     std::cout << "Raytracing... [" << std::string(50, '#') << "] 100%" << std::endl;
     image = result;
   }
+
+  // -aov / -denoise (extensions): the first-hit AOVs of this frame's primary rays (rt_render_aov) and the a-trous filter
+  // of the frame guided by them (rt_denoise).  The frame itself stays as it is.
+  const bool wantAov = GpuSettings::get().aov, wantDenoise = GpuSettings::get().denoise;
+  if ((wantAov || wantDenoise) && multi) throw std::runtime_error("-aov / -denoise run on one GPU only (not with -gpus > 1)");
+  if ((wantAov || wantDenoise) && p.spp > 0) {
+    p.spp_begin = 0, p.spp_count = 0;
+    const size_t npx = static_cast<size_t>(w) * h;
+    std::vector<float> alb(3 * npx), nrm(3 * npx), pos(3 * npx);
+    std::vector<uint32_t> hits(npx);
+    rt_aov aov = {};
+    aov.albedo = alb.data(), aov.normal = nrm.data(), aov.position = pos.data(), aov.hits = hits.data();
+    GpuSession::check(rt_render_aov(ctx0, &p, &aov), "rt_render_aov");
+    if (wantAov) {  // the means (sum / hits; 0 where no sample hit)
+      m_albedo = Image(w, h), m_normal = Image(w, h);
+      for (size_t i = 0; i < npx; ++i)
+        for (int k = 0; k < 3; ++k) {
+          const float n = static_cast<float>(hits[i]);
+          m_albedo.data()[3 * i + k] = hits[i] ? alb[3 * i + k] / n : 0.f;
+          m_normal.data()[3 * i + k] = hits[i] ? 0.5f * (nrm[3 * i + k] / n) + 0.5f : 0.f;
+        }
+    }
+    if (wantDenoise) {
+      rt_denoise_params dp = {};
+      dp.width = w, dp.height = h;
+      m_denoised = Image(w, h);
+      GpuSession::check(rt_denoise(ctx0, &dp, image.data(), &aov, m_denoised.data()), "rt_denoise");
+    }
+  }
 }

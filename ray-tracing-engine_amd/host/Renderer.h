@@ -19,6 +19,7 @@
 #include <string>
 
 #include "GpuSession.h"
+#include "Image.h"
 #include "PhotonMap.h"
 #include "RayTracer.h"
 #include "kdtree.h"
@@ -40,6 +41,10 @@ class Renderer {
 
   // device-side counters of the last render() (rays cast, kernel time, ...)
   const rt_stats& lastStats() const { return m_stats; }
+  // GpuSettings::denoise / aov: the filtered frame, the albedo and the normal (0.5 n + 0.5) means of the last render()
+  const Image& denoised() const { return m_denoised; }
+  const Image& albedo() const { return m_albedo; }
+  const Image& normal() const { return m_normal; }
 
  private:
   int m_numRays, m_mode, m_numPhotons, m_k;
@@ -48,4 +53,5 @@ class Renderer {
   Scene m_scene;
   float m_factor = 100.f;
   rt_stats m_stats = {};
+  Image m_denoised, m_albedo, m_normal;
 };

@@ -101,6 +101,34 @@ class UpdateReport(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
 
 
+class Aov(C.Structure):
+    """rt_aov: channel pointers (host or device), None = channel not wanted."""
+    _fields_ = [("albedo", C.c_void_p), ("normal", C.c_void_p), ("position", C.c_void_p), ("depth", C.c_void_p),
+                ("hits", C.c_void_p), ("mesh", C.c_void_p), ("tri", C.c_void_p), ("reserved", C.c_uint32 * 4)]
+
+
+class DenoiseParams(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("iterations", C.c_uint32), ("sigma_color", C.c_float),
+                ("sigma_normal", C.c_float), ("sigma_position", C.c_float), ("reserved", C.c_uint32 * 6)]
+
+
+AOV_FLOAT3 = ("albedo", "normal", "position")
+AOV_CHANNELS = ("albedo", "normal", "position", "depth", "hits", "mesh", "tri")
+
+
+def aov_means(sums):
+    """The means of rt_render_aov's sums: sum / hits, and 0 where hits == 0 (hits, mesh and tri as they are)."""
+    hits = sums["hits"]
+    out = {}
+    for k, v in sums.items():
+        if k in ("albedo", "normal", "position", "depth"):
+            den = hits.astype(np.float32).reshape(hits.shape + (1,) * (v.ndim - 2))
+            out[k] = np.where(den > 0, v / np.maximum(den, np.float32(1)), np.float32(0)).astype(np.float32)
+        else:
+            out[k] = v
+    return out
+
+
 RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("direction", "<f4", 3)])
 HIT_DTYPE = np.dtype([("hit", "<i4"), ("mesh", "<u4"), ("tri", "<u4"), ("vtx", "<u4", 3), ("u", "<f4"),
                       ("v", "<f4"), ("d", "<f4")])
@@ -111,7 +139,8 @@ AMD_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_create", "rt_destroy", "rt
                "rt_bvh_export", "rt_bvh_build_host", "rt_bvh_check_host", "rt_bvh_top_check_host", "rt_bvh_tune", "rt_profile_reset", "rt_profile_collect", "rt_test_unit",
                "rt_trace_stream_device", "rt_build_photon_map", "rt_get_photons", "rt_test_kd_order", "rt_owned_granules", "rt_pack_owned_device", "rt_unpack_owned_device", "rt_group_create", "rt_group_destroy",
                "rt_group_size", "rt_group_uses_rccl", "rt_group_ctx", "rt_group_set_photons", "rt_group_render",
-               "rt_update", "rt_update_vertices_device", "rt_group_update"]
+               "rt_update", "rt_update_vertices_device", "rt_group_update", "rt_render_aov", "rt_render_aov_device",
+               "rt_denoise", "rt_denoise_device"]
 HOST_SYMBOLS = ["rt_host_scene_build", "rt_host_scene_desc", "rt_host_scene_free", "rt_host_last_error",
                 "rt_host_fill_background", "rt_host_save_ppm", "rt_host_kd_order"]
 
@@ -187,6 +216,11 @@ def amd():
         L.rt_update.argtypes = [C.c_void_p, C.POINTER(SceneUpdate), C.POINTER(UpdateReport)]
         L.rt_update_vertices_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(UpdateReport)]
         L.rt_group_update.argtypes = [C.c_void_p, C.POINTER(SceneUpdate), C.POINTER(UpdateReport)]
+        L.rt_render_aov.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Aov)]
+        L.rt_render_aov_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Aov), C.c_void_p]
+        L.rt_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.POINTER(Aov), C.c_void_p]
+        L.rt_denoise_device.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.POINTER(Aov), C.c_void_p,
+                                        C.c_void_p]
         _amd = L
     return _amd
 
@@ -474,6 +508,62 @@ class Context:
         hits = np.zeros(len(rays), HIT_DTYPE)
         _check(amd().rt_trace(self._h, _ptr(rays), len(rays), accel, kind, _ptr(hits)))
         return hits
+
+    def render_aov(self, params, raw=False, channels=AOV_CHANNELS):
+        """rt_render_aov: first-hit AOVs of the frame `params` describes, as a dict of numpy arrays ([h][w][3] albedo,
+        normal, position; [h][w] depth, hits, mesh, tri).  The means (sum / hits, 0 where hits == 0); raw=True: the
+        sums rt_render_aov returns.  `channels`: the ones wanted (the others are not computed)."""
+        w, h = params.width, params.height
+        if not raw and "hits" not in channels:
+            channels = tuple(channels) + ("hits",)  # (the means divide by it)
+        sums = {}
+        a = Aov()
+        for k in channels:
+            arr = np.zeros((h, w, 3) if k in AOV_FLOAT3 else (h, w), np.float32 if k in AOV_FLOAT3 or k == "depth" else np.uint32)
+            sums[k] = arr
+            setattr(a, k, arr.ctypes.data)
+        _check(amd().rt_render_aov(self._h, C.byref(params), C.byref(a)))
+        return sums if raw else aov_means(sums)
+
+    def render_aov_device(self, params, ptrs, stream=0):
+        """rt_render_aov_device: the sums into device buffers; ptrs = {channel: device pointer} (missing = not wanted)."""
+        a = Aov()
+        for k, v in ptrs.items():
+            setattr(a, k, v or None)
+        _check(amd().rt_render_aov_device(self._h, C.byref(params), C.byref(a), C.c_void_p(stream or None)))
+
+    @staticmethod
+    def _denoise_params(width, height, iterations, sigma_color, sigma_normal, sigma_position):
+        d = DenoiseParams()
+        d.width, d.height, d.iterations = width, height, iterations
+        d.sigma_color, d.sigma_normal, d.sigma_position = sigma_color, sigma_normal, sigma_position
+        return d
+
+    def denoise(self, rgb, aov_sums, iterations=0, sigma_color=0., sigma_normal=0., sigma_position=0., out=None):
+        """rt_denoise: the a-trous filter of the resolved frame rgb [h][w][3] guided by the SUMS of render_aov
+        (raw=True) for the same params.  0 = the defaults.  `out` may be rgb itself (in place)."""
+        rgb = np.ascontiguousarray(rgb, np.float32)
+        h, w = rgb.shape[:2]
+        out = np.empty_like(rgb) if out is None else out
+        assert out.dtype == np.float32 and out.flags["C_CONTIGUOUS"] and out.shape == rgb.shape
+        keep = {k: np.ascontiguousarray(aov_sums[k], np.uint32 if k == "hits" else np.float32)
+                for k in ("albedo", "normal", "position", "hits")}
+        a = Aov()
+        for k, v in keep.items():
+            setattr(a, k, v.ctypes.data)
+        d = self._denoise_params(w, h, iterations, sigma_color, sigma_normal, sigma_position)
+        _check(amd().rt_denoise(self._h, C.byref(d), _ptr(rgb), C.byref(a), _ptr(out)))
+        return out
+
+    def denoise_device(self, width, height, d_rgb, ptrs, d_out, stream=0, iterations=0, sigma_color=0., sigma_normal=0.,
+                       sigma_position=0.):
+        """rt_denoise_device: device pointers (ptrs = {"albedo", "normal", "position", "hits": sums}), on `stream`."""
+        a = Aov()
+        for k, v in ptrs.items():
+            setattr(a, k, v or None)
+        d = self._denoise_params(width, height, iterations, sigma_color, sigma_normal, sigma_position)
+        _check(amd().rt_denoise_device(self._h, C.byref(d), C.c_void_p(d_rgb), C.byref(a), C.c_void_p(d_out),
+                                       C.c_void_p(stream or None)))
 
     def knn(self, queries, k):
         q = np.ascontiguousarray(queries, np.float32)
