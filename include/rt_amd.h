@@ -18,6 +18,8 @@
  *                                  caller stream (multi-GPU tile sharding, bench)
  *   rt_render_aov / rt_denoise  <- (no counterpart) first-hit AOVs of a frame's primary rays, and the a-trous
  *                                  filter of a low-spp frame guided by them (+ _device forms)
+ *   rt_render_adaptive          <- (no counterpart) passes of spp samples over the pixel granules whose estimate has
+ *                                  not yet converged (+ _device form)
  *   rt_trace                    <- RayTracer::rayTrace (RayTracer.h:27-53) test hook
  *   rt_knn / rt_knn_wide        <- kdtree::knearest (kdtree.h:180-195) test hooks
  *
@@ -318,6 +320,49 @@ int rt_denoise(rt_ctx* ctx, const rt_denoise_params* d, const float* rgb, const 
  * context's scratch serves one call at a time. */
 int rt_denoise_device(rt_ctx* ctx, const rt_denoise_params* d, const void* d_rgb, const rt_aov* d_aov, void* d_out,
                       void* stream);
+
+/* ---- adaptive sampling (DESIGN.md "Adaptive sampling") -----------------------------------------------------------
+ * A frame of passes of P = p->spp samples per pixel.  Pass k renders the frame rt_render renders for p with seed
+ * p->seed + k (uint32 wrap-around), over the 8x8-pixel granules still active only; each pass is a full stratified set
+ * (jitter_sample(i, P), i in 0..P-1).  A granule that ran K passes holds in accum exactly what K calls of
+ * rt_render_passes leave on a zero accumulator (call j: seed p->seed + j, spp P, spp_begin = spp_count = 0), bit for
+ * bit; spp[pixel] = K * P, and out_rgb is rt_resolve_device of that accumulator with spp = K * P, pixel by pixel.
+ * After every pass, per in-image pixel of a granule it rendered (float64, in this order, no contraction):
+ *   d = accum - prev (float32);  prev = accum;  miss = P - d.w
+ *   y = (0.2126 (d.x + bg_r miss) + 0.7152 (d.y + bg_g miss) + 0.0722 (d.z + bg_b miss)) / P;  S1 += y;  S2 += y y
+ *   converged: K >= max(min_passes, 2) and v / K <= (threshold (m + floor))^2, m = S1 / K,
+ *              v = max(0, (S2 - S1 m) / (K - 1))
+ * A granule retires when every in-image pixel of it has converged, and stays retired.  The run ends after max_passes
+ * passes or when no granule is active.  threshold 0: nothing retires (every granule runs max_passes).
+ * Validation comes first and a rejected call changes nothing: RT_ERR_INVALID for null arguments, spp_begin / spp_count
+ * not 0, a bad rt_adaptive_params or max_passes * spp above 2^31 - 1, and rt_render's checks; RT_ERR_UNSUPPORTED for
+ * world > 1 (tile-sharded adaptive frames) and the wavefront integrator (reserved[2] bit 0).                          */
+typedef struct rt_adaptive_params {
+  uint32_t max_passes;   /* >= 1                                                                                 */
+  uint32_t min_passes;   /* 0 = min(4, max_passes); otherwise 2..max_passes                                       */
+  float threshold;       /* relative standard error of a pixel's mean luminance; 0 = never retire; finite, >= 0 */
+  float floor;           /* 0 = 0.01; finite, > 0: keeps dark pixels from demanding unlimited samples             */
+  uint32_t reserved[6];  /* zero                                                                                 */
+} rt_adaptive_params;
+typedef struct rt_adaptive_report {
+  uint32_t passes;             /* passes run                                                                    */
+  uint32_t granules;           /* 8x8 granules of the frame                                                     */
+  uint64_t pixel_samples;      /* sum over pixels of spp                                                        */
+  uint32_t active[64];         /* granules rendered by pass k (k < 64)                                          */
+  double render_ms, adapt_ms;  /* device time: the render passes / the statistics and compaction kernels        */
+  double total_ms;             /* wall time of the call                                                         */
+  uint64_t reserved[4];
+} rt_adaptive_report;
+/* Host buffers: background_rgb / out_rgb [h][w][3]; accum_out [h][w][4] or NULL; spp_out [h][w] or NULL; rep, stats
+ * may be NULL (stats: summed over the passes, samples = rep->pixel_samples). */
+int rt_render_adaptive(rt_ctx* ctx, const rt_params* p, const rt_adaptive_params* a, const float* background_rgb,
+                       float* out_rgb, float* accum_out, uint32_t* spp_out, rt_adaptive_report* rep, rt_stats* stats);
+/* The same on DEVICE buffers, ordered on `stream` (may be NULL).  d_accum ([h][w][4]) is overwritten; d_spp may be
+ * NULL.  The pass loop reads the active-granule counts back to the host: one synchronisation of `stream` per pass
+ * (and one more at the end when rep or stats is given).  The context's adaptive scratch serves one call at a time. */
+int rt_render_adaptive_device(rt_ctx* ctx, const rt_params* p, const rt_adaptive_params* a, const void* d_bg,
+                              void* d_accum, void* d_out, void* d_spp, void* stream, rt_adaptive_report* rep,
+                              rt_stats* stats);
 
 /* ---- multi-GPU (Renderer.cpp:219-265 sharded by pixel tiles) -------------
  * A tile-sharded frame: rank r of `world` integrates the pixels whose `tile`-pixel granule

@@ -183,6 +183,9 @@ struct rt_ctx {
   // scratch of rt_denoise_device (guides, albedo factors, two colour buffers; grows on demand)
   DevBuf<float4> dnScratch;
   size_t dnCap = 0;
+  // scratch of rt_render_adaptive_device (moments, granule state and lists, tile list, counts; grows on demand)
+  DevBuf<char> adScratch;
+  size_t adCap = 0;
 };
 
 namespace {
@@ -213,14 +216,14 @@ uint32_t photons_per_light(uint32_t n_requested, uint32_t n_lights) {
 // them in order.  More samples per wave = more, shorter work items: the grid no longer
 // quantises into ~3 rounds of 16k tile-sized items, and a rank that owns 1/8 of the
 // pixels still fills the GPU.
-uint32_t choose_sshift(const rt_ctx* c, const rt_params* p, uint32_t spp_count) {
+// `pixels`: the pixels the launch renders (choose_sshift: the rank's share of the frame; an adaptive pass: its active
+// granules' in-image pixels).
+uint32_t choose_sshift_px(const rt_ctx* c, const rt_params* p, uint64_t pixels, uint32_t spp_count) {
   if (p->reserved[0]) {  // explicit lanes-per-pixel (tests, experiments)
     uint32_t s = 0;
     while ((1u << (s + 1)) <= p->reserved[0] && s < 6) ++s;
     return s;
   }
-  const uint64_t world = p->world ? p->world : 1;
-  const uint64_t pixels = (uint64_t)p->width * p->height / world;
   // measured on C2 (1024^2 x 128 spp), samples per wave 1/2/4/8/16/64:
   // 12.3 / 12.8 / 13.4 / 13.6 / 13.7 / 13.6 Grays/s -> aim for >= 32 rounds of a
   // 256-CU x 16-wave chip
@@ -248,6 +251,10 @@ uint32_t choose_sshift(const rt_ctx* c, const rt_params* p, uint32_t spp_count) 
   if (p->use_photons && p->accel != RT_ACCEL_BRUTE)
     while (s < 6u && (2u << s) <= spp_count) ++s;
   return s;
+}
+uint32_t choose_sshift(const rt_ctx* c, const rt_params* p, uint32_t spp_count) {
+  const uint64_t world = p->world ? p->world : 1;
+  return choose_sshift_px(c, p, (uint64_t)p->width * p->height / world, spp_count);
 }
 
 // f(x8, y8) for each 8x8-pixel granule rank `rank` of `world` owns, row-major — the order ensure_tiles
@@ -412,16 +419,23 @@ int wavefront_args(rt_ctx* c, const rt_params* p, const rtk::RenderArgs& A, uint
   return RT_OK;
 }
 
-// Launch the integrate kernel for p on `stream`, bracketed by an event pair.
-int launch_frame(rt_ctx* c, const rt_params* p, float4* dAccum, hipStream_t stream, int* evIndex) {
+// A wave-tile list of the caller's (an adaptive pass) instead of the frame's cached one: device memory, for `sshift`.
+struct TileList {
+  const uint32_t* tiles;
+  uint32_t n, sshift;
+};
+
+// Launch the integrate kernel for p on `stream`, bracketed by an event pair.  own: render those wave tiles only.
+int launch_frame(rt_ctx* c, const rt_params* p, float4* dAccum, hipStream_t stream, int* evIndex,
+                 const TileList* own = nullptr) {
   const uint32_t sppCount = p->spp_count ? p->spp_count : p->spp;
-  const uint32_t sshift = choose_sshift(c, p, sppCount);
-  int rc = ensure_tiles(c, p, sshift);
+  const uint32_t sshift = own ? own->sshift : choose_sshift(c, p, sppCount);
+  int rc = own ? RT_OK : ensure_tiles(c, p, sshift);
   if (rc != RT_OK) return rc;
   rtk::RenderArgs A;
   A.sshift = sshift;
   wave_tile_shape(sshift, A.tileW, A.tileH);
-  A.tiles = c->dTiles.get(), A.n_tiles = c->nTiles;
+  A.tiles = own ? own->tiles : c->dTiles.get(), A.n_tiles = own ? own->n : c->nTiles;
   A.width = p->width, A.height = p->height, A.spp = p->spp;
   A.s0 = p->spp_count ? p->spp_begin : 0;
   A.s1 = p->spp_count ? p->spp_begin + p->spp_count : p->spp;
@@ -2079,6 +2093,184 @@ int rt_denoise(rt_ctx* c, const rt_denoise_params* d, const float* rgb, const rt
   int rc = rt_denoise_device(c, d, dRgb.get(), &da, dOut.get(), nullptr);
   if (rc != RT_OK) return rc;
   HIP_TRY(hipMemcpy(out, dOut.get(), 3 * npx * sizeof(float), hipMemcpyDeviceToHost));
+  return RT_OK;
+}
+
+}  // extern "C"
+
+// ---- adaptive sampling ----------------------------------------------------------------------------------------------
+namespace {
+
+// the defaults of rt_adaptive_params (rt_amd.h, DESIGN.md "Adaptive sampling")
+constexpr uint32_t kAdaptiveMinPasses = 4;
+constexpr float kAdaptiveFloor = 0.01f;
+
+struct AdaptiveRule {
+  uint32_t maxPasses, minPasses;
+  float threshold, floor;
+};
+
+// Everything an adaptive frame checks before it touches the device; *r gets the rule with its defaults applied.
+int adaptive_checks(const rt_ctx* c, const rt_params* p, const rt_adaptive_params* a, AdaptiveRule* r) {
+  if (!c) return fail(RT_ERR_INVALID, "ctx is null");
+  if (!p) return fail(RT_ERR_INVALID, "params is null");
+  if (!a) return fail(RT_ERR_INVALID, "adaptive params are null");
+  int rc = check_params(c, p);
+  if (rc != RT_OK) return rc;
+  if (p->spp_begin || p->spp_count)
+    return fail(RT_ERR_INVALID, "an adaptive frame runs whole passes of spp samples: spp_begin and spp_count must be 0");
+  if (a->max_passes == 0) return fail(RT_ERR_INVALID, "max_passes must be >= 1");
+  if ((uint64_t)a->max_passes * p->spp > 0x7fffffffull)
+    return fail(RT_ERR_INVALID, "max_passes %u x spp %u exceeds 2^31 - 1 samples per pixel", a->max_passes, p->spp);
+  if (a->min_passes && (a->min_passes < 2 || a->min_passes > a->max_passes))
+    return fail(RT_ERR_INVALID, "min_passes %u outside 2..max_passes (%u)", a->min_passes, a->max_passes);
+  if (!std::isfinite(a->threshold) || !(a->threshold >= 0.f)) return fail(RT_ERR_INVALID, "threshold must be finite and >= 0");
+  const float fl = a->floor == 0.f ? kAdaptiveFloor : a->floor;
+  if (!std::isfinite(fl) || !(fl > 0.f)) return fail(RT_ERR_INVALID, "floor must be finite and > 0");
+  for (uint32_t v : a->reserved)
+    if (v) return fail(RT_ERR_INVALID, "rt_adaptive_params.reserved must be zero");
+  if (p->world > 1) return fail(RT_ERR_UNSUPPORTED, "tile-sharded adaptive frames (world %u) are not supported", p->world);
+  if (p->reserved[2] & 1u) return fail(RT_ERR_UNSUPPORTED, "adaptive frames do not run the wavefront integrator");
+  r->maxPasses = a->max_passes;
+  r->minPasses = a->min_passes ? a->min_passes : std::min(kAdaptiveMinPasses, a->max_passes);
+  r->threshold = a->threshold, r->floor = fl;
+  return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_render_adaptive_device(rt_ctx* c, const rt_params* p, const rt_adaptive_params* a, const void* d_bg, void* d_accum,
+                              void* d_out, void* d_spp, void* stream, rt_adaptive_report* rep, rt_stats* stats) {
+  const auto t0 = std::chrono::steady_clock::now();
+  AdaptiveRule R;
+  int rc = adaptive_checks(c, p, a, &R);
+  if (rc != RT_OK) return rc;
+  if (!d_bg || !d_accum || !d_out) return fail(RT_ERR_INVALID, "null argument");
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const uint32_t W = p->width, H = p->height, gx = (W + 7) / 8, gy = (H + 7) / 8, nG = gx * gy;
+  const size_t npx = (size_t)W * H;
+  // scratch: prev [npx] float4, moments [npx] double2, passes / retired / list [nG], tiles [64 nG], counts
+  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+  const size_t oMom = up(npx * sizeof(float4)), oPass = oMom + up(npx * sizeof(double2)), oRet = oPass + up(nG * 4ull);
+  const size_t oList = oRet + up(nG * 4ull), oTiles = oList + up(nG * 4ull), oCnt = oTiles + up(nG * 64ull * 4);
+  const size_t need = oCnt + rtk::ADAPT_CNT_WORDS * 4;
+  if (need > c->adCap) {
+    c->adCap = 0;
+    if (c->adScratch) HIP_TRY(hipFree(c->adScratch.release()));
+    HIP_TRY(dev_alloc(&c->adScratch, need));
+    c->adCap = need;
+  }
+  char* b = c->adScratch.get();
+  rtk::AdaptArgs A;
+  A.width = W, A.height = H, A.gx = gx, A.gy = gy, A.P = p->spp, A.minPasses = R.minPasses;
+  A.threshold = R.threshold, A.floor = R.floor;
+  A.accum = static_cast<const float4*>(d_accum), A.bg = static_cast<const float*>(d_bg);
+  A.prev = reinterpret_cast<float4*>(b), A.mom = reinterpret_cast<double2*>(b + oMom);
+  A.passes = reinterpret_cast<uint32_t*>(b + oPass), A.retired = reinterpret_cast<uint32_t*>(b + oRet);
+  A.list = reinterpret_cast<uint32_t*>(b + oList), A.tiles = reinterpret_cast<uint32_t*>(b + oTiles);
+  A.counts = reinterpret_cast<uint32_t*>(b + oCnt);
+  Event ev[6];
+  for (Event& e : ev) HIP_TRY(make_event(&e));
+  HIP_TRY(hipMemsetAsync(b, 0, oList, s));  // prev, moments, passes, retired
+  HIP_TRY(hipMemsetAsync(d_accum, 0, npx * sizeof(float4), s));
+  if (stats) HIP_TRY(hipMemsetAsync(c->dCounters.get(), 0, RTK_CNT_COUNT * sizeof(unsigned long long), s));
+  rt_adaptive_report out = {};
+  out.granules = nG;
+  double renderMs = 0., adaptMs = 0.;
+  auto elapsed = [&](int i, int j, double* acc) {
+    float ms = 0.f;
+    const hipError_t e = hipEventElapsedTime(&ms, ev[i].get(), ev[j].get());
+    *acc += ms;
+    return e;
+  };
+  bool pending = false;  // a pass whose events are not read yet
+  rt_params q = *p;
+  hipError_t he;
+  // pass k: compaction of the active granules -> counts read back -> wave tiles for the pass's sshift -> the render
+  // pass over them -> the rule over the granules it rendered
+  for (uint32_t k = 0; k < R.maxPasses; ++k) {
+    HIP_TRY(hipEventRecord(ev[0].get(), s));
+    if ((he = rtk::launch_adapt_compact(A, s)) != hipSuccess) return fail(RT_ERR_HIP, "adaptive compaction failed: %s", hipGetErrorString(he));
+    HIP_TRY(hipEventRecord(ev[1].get(), s));
+    uint32_t cnt[rtk::ADAPT_CNT_WORDS];
+    HIP_TRY(hipMemcpyAsync(cnt, A.counts, sizeof cnt, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(elapsed(0, 1, &adaptMs));
+    if (pending) {
+      HIP_TRY(elapsed(2, 3, &adaptMs));
+      HIP_TRY(elapsed(3, 4, &renderMs));
+      HIP_TRY(elapsed(4, 5, &adaptMs));
+      pending = false;
+    }
+    const uint32_t nAct = cnt[rtk::ADAPT_CNT_GRANULES];
+    if (nAct == 0) break;
+    if (k < 64) out.active[k] = nAct;
+    q.seed = p->seed + k;
+    const uint32_t sshift = choose_sshift_px(c, &q, cnt[rtk::ADAPT_CNT_PIXELS], p->spp);
+    uint32_t tw, th;
+    wave_tile_shape(sshift, tw, th);
+    HIP_TRY(hipEventRecord(ev[2].get(), s));
+    if ((he = rtk::launch_adapt_expand(A, nAct, tw, th, s)) != hipSuccess) return fail(RT_ERR_HIP, "adaptive tile list failed: %s", hipGetErrorString(he));
+    HIP_TRY(hipEventRecord(ev[3].get(), s));
+    const TileList own = {A.tiles, cnt[rtk::ADAPT_CNT_TILES + sshift], sshift};
+    if ((rc = launch_frame(c, &q, static_cast<float4*>(d_accum), s, nullptr, &own)) != RT_OK) return rc;
+    HIP_TRY(hipEventRecord(ev[4].get(), s));
+    if ((he = rtk::launch_adapt_update(A, nAct, s)) != hipSuccess) return fail(RT_ERR_HIP, "adaptive update failed: %s", hipGetErrorString(he));
+    HIP_TRY(hipEventRecord(ev[5].get(), s));
+    pending = true;
+    out.passes++;
+    out.pixel_samples += (uint64_t)cnt[rtk::ADAPT_CNT_PIXELS] * p->spp;
+  }
+  he = rtk::launch_resolve_adaptive(A, static_cast<float*>(d_out), static_cast<uint32_t*>(d_spp), s);
+  if (he != hipSuccess) return fail(RT_ERR_HIP, "adaptive resolve failed: %s", hipGetErrorString(he));
+  if (rep || stats) {
+    HIP_TRY(hipStreamSynchronize(s));
+    if (pending) {
+      HIP_TRY(elapsed(2, 3, &adaptMs));
+      HIP_TRY(elapsed(3, 4, &renderMs));
+      HIP_TRY(elapsed(4, 5, &adaptMs));
+    }
+  }
+  if (stats) {
+    memset(stats, 0, sizeof *stats);
+    if ((rc = read_counters(c, stats)) != RT_OK) return rc;
+    stats->kernel_ms = renderMs;
+    stats->samples = out.pixel_samples;
+  }
+  if (rep) {
+    out.render_ms = renderMs, out.adapt_ms = adaptMs;
+    out.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    *rep = out;
+  }
+  return RT_OK;
+}
+
+int rt_render_adaptive(rt_ctx* c, const rt_params* p, const rt_adaptive_params* a, const float* bg, float* out_rgb,
+                       float* accum_out, uint32_t* spp_out, rt_adaptive_report* rep, rt_stats* stats) {
+  const auto t0 = std::chrono::steady_clock::now();
+  AdaptiveRule R;
+  int rc = adaptive_checks(c, p, a, &R);
+  if (rc != RT_OK) return rc;
+  if (!bg || !out_rgb) return fail(RT_ERR_INVALID, "null argument");
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t npx = (size_t)p->width * p->height;
+  DevBuf<float4> dAccum;
+  DevBuf<float> dBg, dOut;
+  DevBuf<uint32_t> dSpp;
+  HIP_TRY(dev_alloc(&dAccum, npx));
+  HIP_TRY(dev_alloc(&dBg, npx * 3));
+  HIP_TRY(dev_alloc(&dOut, npx * 3));
+  if (spp_out) HIP_TRY(dev_alloc(&dSpp, npx));
+  HIP_TRY(hipMemcpy(dBg.get(), bg, npx * 3 * sizeof(float), hipMemcpyHostToDevice));
+  rc = rt_render_adaptive_device(c, p, a, dBg.get(), dAccum.get(), dOut.get(), dSpp.get(), nullptr, rep, stats);
+  if (rc != RT_OK) return rc;
+  HIP_TRY(hipMemcpy(out_rgb, dOut.get(), npx * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  if (accum_out) HIP_TRY(hipMemcpy(accum_out, dAccum.get(), npx * sizeof(float4), hipMemcpyDeviceToHost));
+  if (spp_out) HIP_TRY(hipMemcpy(spp_out, dSpp.get(), npx * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (rep) rep->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return RT_OK;
 }
 

@@ -120,6 +120,32 @@ struct DenoiseArgs {
 };
 inline size_t denoise_scratch(uint32_t w, uint32_t h) { return 5 * (size_t)w * h + 4; }
 hipError_t launch_denoise(const DevScene& S, const DenoiseArgs& D, hipStream_t stream);
+// adaptive sampling (adaptive.hip, rt_render_adaptive): per-pixel running moments and per-granule pass counts, the
+// compaction of the active granules into the next pass's wave tiles, and the resolve with per-pixel sample counts
+enum { ADAPT_CNT_GRANULES = 0, ADAPT_CNT_PIXELS = 1, ADAPT_CNT_TILES = 2, ADAPT_CNT_WORDS = 16 };  // counts[2 + sshift]
+struct AdaptArgs {
+  uint32_t width, height, gx, gy;  // image; granules per row / column
+  uint32_t P;                      // samples per pass
+  uint32_t minPasses;              // passes before a pixel may converge (>= 2 applied on the device)
+  float threshold, floor;          // the retirement rule (threshold 0: never)
+  const float4* accum;             // [h][w] the frame's accumulator
+  const float* bg;                 // [h][w][3]
+  float4* prev;                    // [h][w] accum after the previous pass
+  double2* mom;                    // [h][w] {S1, S2}
+  uint32_t* passes;                // [granules] passes run
+  uint32_t* retired;               // [granules] 1 = retired
+  uint32_t* list;                  // [granules] the active granules (x8 + y8 * gx), row-major
+  uint32_t* tiles;                 // [granules * 64] their wave tiles (x0 | y0 << 16)
+  uint32_t* counts;                // [ADAPT_CNT_WORDS]
+};
+// list + counts from retired (one workgroup)
+hipError_t launch_adapt_compact(const AdaptArgs& A, hipStream_t stream);
+// tiles from the first nAct entries of list for a wave footprint tw x th (one workgroup)
+hipError_t launch_adapt_expand(const AdaptArgs& A, uint32_t nAct, uint32_t tw, uint32_t th, hipStream_t stream);
+// the rule over the first nAct entries of list after a pass: moments, passes, retired
+hipError_t launch_adapt_update(const AdaptArgs& A, uint32_t nAct, hipStream_t stream);
+// out = k_resolve's expression with spp = passes[granule] * P per pixel; spp (may be null) = that count
+hipError_t launch_resolve_adaptive(const AdaptArgs& A, float* out, uint32_t* spp, hipStream_t stream);
 // ray queue in HBM -> results (wavefront stage T)
 hipError_t launch_trace_stream(const DevScene& S, const float4* rayO, const float4* rayD, uint32_t n, uint2* res,
                                uint32_t* counter, uint32_t stackLevels, uint32_t numCUs, hipStream_t stream);

@@ -79,6 +79,8 @@ struct GpuSettings {
   double tune = 0.;       // seconds of measured-cost BVH tuning before the frame (rt_bvh_tune; 0 = none)
   bool denoise = false;   // also the a-trous-filtered frame (Renderer::denoised(); single device only)
   bool aov = false;       // also the first-hit AOV means (Renderer::albedo() / normal(); single device only)
+  double adaptive = -1.;  // >= 0: adaptive sampling with this threshold (rt_render_adaptive; single device only)
+  unsigned pass = 16;     // samples per adaptive pass (the frame's spp is the per-pixel maximum, a multiple of it)
   std::vector<int> devices;  // more than one entry: Renderer::render tile-shards the frame over them (rt_group)
   static GpuSettings& get() {
     static GpuSettings s;

@@ -29,6 +29,8 @@ int main(int argc, char** argv) {
   GpuSettings::get().tune = args.tune();
   GpuSettings::get().denoise = args.denoise() != 0;
   GpuSettings::get().aov = args.aov() != 0;
+  GpuSettings::get().adaptive = args.adaptive();
+  GpuSettings::get().pass = static_cast<unsigned>(args.pass());
   // -gpus N: devices gpu..gpu+N-1; -devices a,b,c: an explicit list (may repeat a device:
   // rehearsal of the N-rank flow on one GPU)
   if (!args.devices().empty()) {
@@ -47,6 +49,16 @@ int main(int argc, char** argv) {
   if ((args.denoise() || args.aov()) && GpuSettings::get().devices.size() > 1) {
     std::cerr << "error: -denoise / -aov run on one GPU only (not with -gpus > 1)" << std::endl;
     return 1;
+  }
+  if (args.adaptive() >= 0.) {
+    if (GpuSettings::get().devices.size() > 1) {
+      std::cerr << "error: -adaptive runs on one GPU only (not with -gpus > 1)" << std::endl;
+      return 1;
+    }
+    if (args.pass() == 0 || args.numRays() % args.pass() != 0) {
+      std::cerr << "error: -N (" << args.numRays() << ") must be a multiple of -pass (" << args.pass() << ")" << std::endl;
+      return 1;
+    }
   }
   try {
     Image image(args.width(), args.height());
@@ -68,6 +80,7 @@ int main(int argc, char** argv) {
     const std::string stem = of.size() > 4 && of.compare(of.size() - 4, 4, ".ppm") == 0 ? of.substr(0, of.size() - 4) : of;
     if (args.denoise()) renderer.denoised().savePPM(stem + "_denoised.ppm");
     if (args.aov()) renderer.albedo().savePPM(stem + "_albedo.ppm"), renderer.normal().savePPM(stem + "_normal.ppm");
+    if (args.adaptive() >= 0.) renderer.sppMap().savePPM(stem + "_spp.ppm");
 
     const rt_stats& st = renderer.lastStats();
     const double rays = static_cast<double>(st.rays_closest + st.rays_shadow);

@@ -88,6 +88,30 @@ inline void Renderer::render(Image& image) {
     std::cout << "Raytracing on " << devs.size() << " GPUs" << (rt_group_uses_rccl(many->group()) ? " (RCCL)" : " (peer copies)")
               << "... [" << std::string(50, '#') << "] 100%" << std::endl;
     image = result;
+  } else if (p.spp > 0 && GpuSettings::get().adaptive >= 0.) {
+    // -adaptive T (extension): passes of -pass samples with seeds seed, seed + 1, ... over the 8x8-pixel granules whose
+    // estimate has not converged (rt_render_adaptive); -N is the per-pixel maximum.  update.ppm is written once.  The
+    // -aov / -denoise block below sees pass 0's parameters.
+    const uint32_t maxSpp = p.spp;
+    rt_adaptive_params a = {};
+    p.spp = GpuSettings::get().pass;
+    a.max_passes = maxSpp / p.spp;
+    a.threshold = static_cast<float>(GpuSettings::get().adaptive);
+    std::vector<uint32_t> spp(static_cast<size_t>(w) * h);
+    rt_adaptive_report rep = {};
+    rt_stats st = {};
+    GpuSession::check(rt_render_adaptive(ctx0, &p, &a, image.data(), result.data(), nullptr, spp.data(), &rep, &st),
+                      "rt_render_adaptive");
+    m_stats = st;
+    m_spp = Image(w, h);
+    for (size_t i = 0; i < spp.size(); ++i)
+      for (int k = 0; k < 3; ++k) m_spp.data()[3 * i + k] = static_cast<float>(spp[i]) / static_cast<float>(maxSpp);
+    result.savePPM("update.ppm");
+    std::cout << "Adaptive sampling: " << rep.passes << " passes of " << p.spp << " samples, "
+              << static_cast<double>(rep.pixel_samples) / (static_cast<double>(w) * h) << " samples per pixel on average (at most "
+              << maxSpp << ")" << std::endl;
+    std::cout << "Raytracing... [" << std::string(50, '#') << "] 100%" << std::endl;
+    image = result;
   } else if (p.spp > 0) {
     // The reference re-saves update.ppm after EVERY pass (Renderer.cpp:261-269).  Here a
     // "pass" is a sample range of one launch; GpuSettings::progress = P > 0 renders P

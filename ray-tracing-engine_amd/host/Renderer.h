@@ -45,6 +45,8 @@ class Renderer {
   const Image& denoised() const { return m_denoised; }
   const Image& albedo() const { return m_albedo; }
   const Image& normal() const { return m_normal; }
+  // GpuSettings::adaptive: samples per pixel of the last render() over the maximum (grey, spp / N)
+  const Image& sppMap() const { return m_spp; }
 
  private:
   int m_numRays, m_mode, m_numPhotons, m_k;
@@ -53,5 +55,5 @@ class Renderer {
   Scene m_scene;
   float m_factor = 100.f;
   rt_stats m_stats = {};
-  Image m_denoised, m_albedo, m_normal;
+  Image m_denoised, m_albedo, m_normal, m_spp;
 };

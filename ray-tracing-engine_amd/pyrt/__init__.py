@@ -112,6 +112,28 @@ class DenoiseParams(C.Structure):
                 ("sigma_normal", C.c_float), ("sigma_position", C.c_float), ("reserved", C.c_uint32 * 6)]
 
 
+class AdaptiveParams(C.Structure):
+    _fields_ = [("max_passes", C.c_uint32), ("min_passes", C.c_uint32), ("threshold", C.c_float), ("floor", C.c_float),
+                ("reserved", C.c_uint32 * 6)]
+
+
+class AdaptiveReport(C.Structure):
+    _fields_ = [("passes", C.c_uint32), ("granules", C.c_uint32), ("pixel_samples", C.c_uint64),
+                ("active", C.c_uint32 * 64), ("render_ms", C.c_double), ("adapt_ms", C.c_double),
+                ("total_ms", C.c_double), ("reserved", C.c_uint64 * 4)]
+
+    def as_dict(self):
+        d = {n: getattr(self, n) for n, _ in self._fields_ if n not in ("reserved", "active")}
+        d["active"] = list(self.active)[:min(self.passes, 64)]
+        return d
+
+
+def make_adaptive(threshold, max_passes, min_passes=0, floor=0.):
+    a = AdaptiveParams()
+    a.max_passes, a.min_passes, a.threshold, a.floor = max_passes, min_passes, threshold, floor
+    return a
+
+
 AOV_FLOAT3 = ("albedo", "normal", "position")
 AOV_CHANNELS = ("albedo", "normal", "position", "depth", "hits", "mesh", "tri")
 
@@ -140,7 +162,7 @@ AMD_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_create", "rt_destroy", "rt
                "rt_trace_stream_device", "rt_build_photon_map", "rt_get_photons", "rt_test_kd_order", "rt_owned_granules", "rt_pack_owned_device", "rt_unpack_owned_device", "rt_group_create", "rt_group_destroy",
                "rt_group_size", "rt_group_uses_rccl", "rt_group_ctx", "rt_group_set_photons", "rt_group_render",
                "rt_update", "rt_update_vertices_device", "rt_group_update", "rt_render_aov", "rt_render_aov_device",
-               "rt_denoise", "rt_denoise_device"]
+               "rt_denoise", "rt_denoise_device", "rt_render_adaptive", "rt_render_adaptive_device"]
 HOST_SYMBOLS = ["rt_host_scene_build", "rt_host_scene_desc", "rt_host_scene_free", "rt_host_last_error",
                 "rt_host_fill_background", "rt_host_save_ppm", "rt_host_kd_order"]
 
@@ -219,6 +241,11 @@ def amd():
         L.rt_render_aov.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Aov)]
         L.rt_render_aov_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Aov), C.c_void_p]
         L.rt_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.POINTER(Aov), C.c_void_p]
+        L.rt_render_adaptive.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(AdaptiveParams), C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.POINTER(AdaptiveReport), C.POINTER(Stats)]
+        L.rt_render_adaptive_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(AdaptiveParams), C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AdaptiveReport),
+                                                C.POINTER(Stats)]
         L.rt_denoise_device.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.POINTER(Aov), C.c_void_p,
                                         C.c_void_p]
         _amd = L
@@ -531,6 +558,32 @@ class Context:
         for k, v in ptrs.items():
             setattr(a, k, v or None)
         _check(amd().rt_render_aov_device(self._h, C.byref(params), C.byref(a), C.c_void_p(stream or None)))
+
+    def render_adaptive(self, params, bg, threshold, max_passes, min_passes=0, floor=0.):
+        """rt_render_adaptive: passes of params.spp samples over the granules not yet converged (DESIGN.md "Adaptive
+        sampling").  Returns (out [h][w][3], accum [h][w][4], spp [h][w] uint32, AdaptiveReport, Stats)."""
+        w, h = params.width, params.height
+        out = np.empty((h, w, 3), np.float32)
+        acc = np.empty((h, w, 4), np.float32)
+        spp = np.empty((h, w), np.uint32)
+        rep, st = AdaptiveReport(), Stats()
+        bgc = np.ascontiguousarray(bg, np.float32)
+        a = make_adaptive(threshold, max_passes, min_passes, floor)
+        _check(amd().rt_render_adaptive(self._h, C.byref(params), C.byref(a), _ptr(bgc), _ptr(out), _ptr(acc), _ptr(spp),
+                                        C.byref(rep), C.byref(st)))
+        return out, acc, spp, rep, st
+
+    def render_adaptive_device(self, params, d_bg, d_accum, d_out, threshold, max_passes, min_passes=0, floor=0.,
+                               d_spp=None, stream=0, stats=False):
+        """rt_render_adaptive_device on device pointers (d_accum is overwritten; d_spp may be None), on `stream`.
+        Returns (AdaptiveReport, Stats or None)."""
+        rep = AdaptiveReport()
+        st = Stats() if stats else None
+        a = make_adaptive(threshold, max_passes, min_passes, floor)
+        _check(amd().rt_render_adaptive_device(self._h, C.byref(params), C.byref(a), C.c_void_p(d_bg), C.c_void_p(d_accum),
+                                               C.c_void_p(d_out), C.c_void_p(d_spp or None), C.c_void_p(stream or None),
+                                               C.byref(rep), C.byref(st) if stats else None))
+        return rep, st
 
     @staticmethod
     def _denoise_params(width, height, iterations, sigma_color, sigma_normal, sigma_position):
