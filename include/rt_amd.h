@@ -20,6 +20,8 @@
  *                                  filter of a low-spp frame guided by them (+ _device forms)
  *   rt_render_adaptive          <- (no counterpart) passes of spp samples over the pixel granules whose estimate has
  *                                  not yet converged (+ _device form)
+ *   rt_render_views             <- (no counterpart) the frames of many cameras of one resident scene in one launch
+ *                                  (+ _device form)
  *   rt_trace                    <- RayTracer::rayTrace (RayTracer.h:27-53) test hook
  *   rt_knn / rt_knn_wide        <- kdtree::knearest (kdtree.h:180-195) test hooks
  *
@@ -363,6 +365,39 @@ int rt_render_adaptive(rt_ctx* ctx, const rt_params* p, const rt_adaptive_params
 int rt_render_adaptive_device(rt_ctx* ctx, const rt_params* p, const rt_adaptive_params* a, const void* d_bg,
                               void* d_accum, void* d_out, void* d_spp, void* stream, rt_adaptive_report* rep,
                               rt_stats* stats);
+
+/* ---- many views of one scene (DESIGN.md "Multi-view frames") -------------------------------------------------------
+ * One launch renders n_views frames of the same p, view j with camera cameras[j] and stream key seeds[j] (p->seed for
+ * every view when seeds is NULL).  Slice j of the accumulator is, bit for bit, what rt_render_device leaves for the same
+ * p on this context after a camera-only rt_update to cameras[j] (with p->seed replaced by seeds[j]); the resolved image
+ * is rt_resolve_device of that slice.  stats: rays_closest, rays_shadow and knn_queries are the sums of the per-view
+ * frames' counts, samples covers every view, kernel_ms is the one launch.  The context's own camera does not change.
+ * Cameras the tree must cover (rt_update's rules, per view camera): a non-finite view camera, or one beyond the operand
+ * bounds of a context that takes the short reciprocal forms (rt_bvh_info.flags), is RT_ERR_INVALID, naming the view in
+ * rt_last_error; a view camera that needs a wider box padding than the context has makes the call refit the boxes first
+ * to the widest padding any view needs, which the context keeps (rt_bvh_info.pad; the photon map stays, as after a
+ * camera-only update) — RT_ERR_UNSUPPORTED on RT_NODES_Q8 contexts.  The frames do not depend on the padding.
+ * Validation comes first and a rejected call writes nothing: RT_ERR_INVALID for a null ctx, p, v or cameras, n_views
+ * of 0 or above 65535, n_views * width * height of 2^31 or more, non-zero reserved fields, the camera rule and
+ * rt_render's checks; RT_ERR_UNSUPPORTED for world > 1 and the wavefront integrator (reserved[2] bit 0); RT_ERR_STATE
+ * for the photon cases, as rt_render.  The context's view scratch serves one call at a time.                        */
+typedef struct rt_views {
+  uint32_t n_views;            /* 1..65535; n_views * width * height < 2^31                       */
+  uint32_t reserved0;          /* zero                                                            */
+  const rt_camera* cameras;    /* [n_views], HOST memory                                          */
+  const uint32_t* seeds;       /* [n_views] HOST memory, or NULL = p->seed for every view         */
+  uint32_t reserved[6];        /* zero                                                            */
+} rt_views;
+/* background_rgb [h][w][3] shared by every view (required when out_rgb is given, as rt_render);
+ * out_rgb [n][h][w][3] or NULL; accum_out [n][h][w][4] or NULL; stats summed over the views. */
+int rt_render_views(rt_ctx* ctx, const rt_params* p, const rt_views* v, const float* background_rgb,
+                    float* out_rgb, float* accum_out, rt_stats* stats);
+/* Accumulate into caller-zeroed DEVICE d_accum [n][h][w][4] on `stream` (a hipStream_t, may be NULL), as
+ * rt_render_device does (sample ranges chain). To resolve view j, call rt_resolve_device on
+ * d_accum + j*h*w*4 floats.  The host waits only to refit (a wider padding), to read stats back, and for the previous
+ * call's upload of the view records. */
+int rt_render_views_device(rt_ctx* ctx, const rt_params* p, const rt_views* v, void* d_accum, void* stream,
+                           rt_stats* stats);
 
 /* ---- multi-GPU (Renderer.cpp:219-265 sharded by pixel tiles) -------------
  * A tile-sharded frame: rank r of `world` integrates the pixels whose `tile`-pixel granule

@@ -69,6 +69,11 @@ struct HipFree {
 };
 template <class T>
 using DevBuf = std::unique_ptr<T, HipFree>;
+struct HipHostFree {
+  void operator()(void* p) const { (void)hipHostFree(p); }
+};
+template <class T>
+using PinnedBuf = std::unique_ptr<T, HipHostFree>;
 struct EventDestroy {
   void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); }
 };
@@ -186,6 +191,16 @@ struct rt_ctx {
   // scratch of rt_render_adaptive_device (moments, granule state and lists, tile list, counts; grows on demand)
   DevBuf<char> adScratch;
   size_t adCap = 0;
+  // scratch of rt_render_views_device: the view-major wave tiles and their views (for vwKey and vwViews views), the view
+  // records and their pinned staging copy (vwStaged: recorded after the upload that last read it)
+  DevBuf<uint32_t> vwTiles, vwTileView;
+  uint32_t vwNTiles = 0, vwViews = 0;
+  TileKey vwKey;
+  DevBuf<rtk::ViewRec> vwRecs;
+  PinnedBuf<rtk::ViewRec> vwHost;
+  uint32_t vwCap = 0;
+  Event vwStaged;
+  bool vwStagedSet = false;
 };
 
 namespace {
@@ -269,20 +284,29 @@ void owned_granules(uint32_t w, uint32_t h, uint32_t rank, uint32_t world, uint3
       if (world <= 1 || (x8 * 8 / tile + y8 * 8 / tile) % world == rank) f(x8, y8);
 }
 
-int ensure_tiles(rt_ctx* c, const rt_params* p, uint32_t sshift) {
+TileKey tile_key(const rt_params* p, uint32_t sshift) {
   TileKey k;
   k.w = p->width, k.h = p->height, k.rank = p->rank, k.world = p->world ? p->world : 1;
   k.tile = p->tile ? p->tile : 8;
   k.sshift = sshift;
-  if (c->dTiles && k == c->tileKey) return RT_OK;
+  return k;
+}
+// the wave tiles inside each owned granule, row-major, so that consecutive waves touch neighbouring pixels
+std::vector<uint32_t> wave_tiles(const TileKey& k) {
   std::vector<uint32_t> tiles;
   uint32_t tw, th;
-  wave_tile_shape(sshift, tw, th);
-  // the wave tiles inside each owned granule, row-major, so that consecutive waves touch neighbouring pixels
+  wave_tile_shape(k.sshift, tw, th);
   owned_granules(k.w, k.h, k.rank, k.world, k.tile, [&](uint32_t x8, uint32_t y8) {
     for (uint32_t y = y8 * 8; y < y8 * 8 + 8 && y < k.h; y += th)
       for (uint32_t x = x8 * 8; x < x8 * 8 + 8 && x < k.w; x += tw) tiles.push_back(x | (y << 16));
   });
+  return tiles;
+}
+
+int ensure_tiles(rt_ctx* c, const rt_params* p, uint32_t sshift) {
+  const TileKey k = tile_key(p, sshift);
+  if (c->dTiles && k == c->tileKey) return RT_OK;
+  const std::vector<uint32_t> tiles = wave_tiles(k);
   if (c->dTiles) HIP_TRY(hipFree(c->dTiles.release()));
   int rc = upload(&c->dTiles, tiles.data(), tiles.size());
   if (rc != RT_OK) return rc;
@@ -419,10 +443,13 @@ int wavefront_args(rt_ctx* c, const rt_params* p, const rtk::RenderArgs& A, uint
   return RT_OK;
 }
 
-// A wave-tile list of the caller's (an adaptive pass) instead of the frame's cached one: device memory, for `sshift`.
+// A wave-tile list of the caller's (an adaptive pass, a multi-view frame) instead of the frame's cached one: device
+// memory, for `sshift`; a multi-view frame also gives each tile's view and the view records (rtk::RenderArgs).
 struct TileList {
   const uint32_t* tiles;
   uint32_t n, sshift;
+  const uint32_t* tileView = nullptr;
+  const rtk::ViewRec* views = nullptr;
 };
 
 // Launch the integrate kernel for p on `stream`, bracketed by an event pair.  own: render those wave tiles only.
@@ -436,6 +463,7 @@ int launch_frame(rt_ctx* c, const rt_params* p, float4* dAccum, hipStream_t stre
   A.sshift = sshift;
   wave_tile_shape(sshift, A.tileW, A.tileH);
   A.tiles = own ? own->tiles : c->dTiles.get(), A.n_tiles = own ? own->n : c->nTiles;
+  A.tileView = own ? own->tileView : nullptr, A.views = own ? own->views : nullptr;
   A.width = p->width, A.height = p->height, A.spp = p->spp;
   A.s0 = p->spp_count ? p->spp_begin : 0;
   A.s1 = p->spp_count ? p->spp_begin + p->spp_count : p->spp;
@@ -562,9 +590,9 @@ float bits_float(uint32_t u) {
   return f;
 }
 
-// (reads the magnitude summaries c->magPos / c->magNrm, the camera S.cam and the lights c->hostLights)
-void vouch_short_forms(rt_ctx* c) {
-  rtk::DevScene& S = c->S;
+// The operand bounds of the short forms for the context's positions, normals and lights with camera `cam` (reads the
+// magnitude summaries c->magPos / c->magNrm and the lights c->hostLights)
+bool short_forms_bound(const rt_ctx* c, const rt_camera& cam) {
   double maxAbs = 0, maxLight = 0, maxAny = 0;
   bool finite = true;
   auto eat = [&](uint32_t m) {
@@ -574,7 +602,7 @@ void vouch_short_forms(rt_ctx* c) {
   };
   maxAbs = eat(c->magPos);
   eat(c->magNrm);
-  eat(max_abs_bits(S.cam.position, 12));
+  eat(max_abs_bits(cam.position, 12));
   for (const rt_light& L : c->hostLights) {
     eat(max_abs_bits(L.position, 15));
     eat(max_abs_bits(&L.intensity, 6));
@@ -584,7 +612,13 @@ void vouch_short_forms(rt_ctx* c) {
   }
   const double edge = 2.0 * 1.7320508 * maxAbs, dir = 1.7320508 * maxAbs + maxLight + 2.0;
   const double detBound = 1.01 * edge * edge * dir;
-  S.slowRecip = (finite && maxAny <= 1e14 && maxLight <= 1e14 && std::isfinite(detBound) && detBound < 1.2676506e30) ? 0u : 1u;
+  return finite && maxAny <= 1e14 && maxLight <= 1e14 && std::isfinite(detBound) && detBound < 1.2676506e30;
+}
+
+// (reads the magnitude summaries c->magPos / c->magNrm, the camera S.cam and the lights c->hostLights)
+void vouch_short_forms(rt_ctx* c) {
+  rtk::DevScene& S = c->S;
+  S.slowRecip = short_forms_bound(c, S.cam) ? 0u : 1u;
   if (getenv("RT_SLOW_RECIP")) S.slowRecip = 1u;  // (A/B and the parity tests of the division path)
   // ... and the device vouches for the short forms itself, once per process and device (2^25 inputs, well under a
   // millisecond): the exhaustive check ran on one MI355X; a part whose v_rcp_f32 / v_rsq_f32 rounded differently would
@@ -1799,6 +1833,7 @@ struct Update {
   const rt_light* lights = nullptr;
   uint32_t nLights = 0;
   const rt_material* materials = nullptr;
+  const rtbvh::Padding* padding = nullptr;  // rt_render_views: its farthest view's padding in place of the camera's rule
 };
 
 int update_checks(rt_ctx* c, const rt_light* lights, uint32_t nLights) {
@@ -1828,7 +1863,7 @@ int update_ctx(rt_ctx* c, const Update& u, hipStream_t stream, std::chrono::stea
   }
   const rt_camera cam = u.camera ? *u.camera : S.cam;
   const std::vector<rt_light> lights = u.lights ? std::vector<rt_light>(u.lights, u.lights + u.nLights) : c->hostLights;
-  const rtbvh::Padding P = rtbvh::paddingRule(bits_float(magRef), cam, lights.data(), (uint32_t)lights.size());
+  const rtbvh::Padding P = u.padding ? *u.padding : rtbvh::paddingRule(bits_float(magRef), cam, lights.data(), (uint32_t)lights.size());
   const bool refit = u.dPos || P.pad != c->bvh.pad || P.boxScale != c->bvh.boxScale;
   // 2. staging: new light and material arrays, the refit's float nodes and depth table (the context still renders as before)
   int rc = RT_OK;
@@ -2271,6 +2306,163 @@ int rt_render_adaptive(rt_ctx* c, const rt_params* p, const rt_adaptive_params* 
   if (accum_out) HIP_TRY(hipMemcpy(accum_out, dAccum.get(), npx * sizeof(float4), hipMemcpyDeviceToHost));
   if (spp_out) HIP_TRY(hipMemcpy(spp_out, dSpp.get(), npx * sizeof(uint32_t), hipMemcpyDeviceToHost));
   if (rep) rep->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return RT_OK;
+}
+
+}  // extern "C"
+
+// ---- many views of one scene (DESIGN.md "Multi-view frames") --------------------------------------------------------
+namespace {
+
+// Everything a multi-view frame checks before it touches the device, and the padding its farthest view needs:
+// *refit = true when that is wider than the context's (rt_amd.h: the camera rule).
+int views_checks(rt_ctx* c, const rt_params* p, const rt_views* v, rtbvh::Padding* pad, bool* refit) {
+  if (!c || !p || !v || !v->cameras) return fail(RT_ERR_INVALID, "ctx/params/views/cameras is null");
+  int rc = check_params(c, p);
+  if (rc != RT_OK) return rc;
+  if (v->reserved0) return fail(RT_ERR_INVALID, "rt_views.reserved0 must be zero");
+  for (uint32_t r : v->reserved)
+    if (r) return fail(RT_ERR_INVALID, "rt_views.reserved must be zero");
+  if (v->n_views == 0 || v->n_views > 65535u) return fail(RT_ERR_INVALID, "n_views %u out of range 1..65535", v->n_views);
+  if ((uint64_t)v->n_views * p->width * p->height >= (1ull << 31))
+    return fail(RT_ERR_INVALID, "%u views of %ux%u pixels: 2^31 pixels or more", v->n_views, p->width, p->height);
+  if (p->world > 1) return fail(RT_ERR_UNSUPPORTED, "tile-sharded multi-view frames (world %u) are not supported", p->world);
+  if (p->reserved[2] & 1u) return fail(RT_ERR_UNSUPPORTED, "multi-view frames do not run the wavefront integrator");
+  // rt_update's rules, per view camera in place of the context's
+  const float magRef = bits_float(c->magRef);
+  *pad = rtbvh::Padding{c->bvh.pad, c->bvh.originBound, c->bvh.boxScale};
+  *refit = false;
+  for (uint32_t j = 0; j < v->n_views; ++j) {
+    const rt_camera& cam = v->cameras[j];
+    if (max_abs_bits(cam.position, 12) >= 0x7f800000u) return fail(RT_ERR_INVALID, "view %u: non-finite camera", j);
+    if (c->S.slowRecip == 0u && !short_forms_bound(c, cam))
+      return fail(RT_ERR_INVALID, "view %u: camera beyond the short forms' operand bounds (rt_update to it instead)", j);
+    const rtbvh::Padding P = rtbvh::paddingRule(magRef, cam, c->hostLights.data(), (uint32_t)c->hostLights.size());
+    if (P.pad > pad->pad) *pad = P, *refit = true;
+  }
+  if (*refit && c->nodeFormat == RT_NODES_Q8)
+    return fail(RT_ERR_UNSUPPORTED, "views need a wider box padding (%g) and RT_NODES_Q8 contexts cannot be refit", pad->pad);
+  return RT_OK;
+}
+
+// The view-major wave tiles of n views (each view's as a single-view frame has them) and each tile's view, cached on the
+// context by (frame, sshift, n)
+int ensure_view_tiles(rt_ctx* c, const rt_params* p, uint32_t sshift, uint32_t n) {
+  const TileKey k = tile_key(p, sshift);
+  if (c->vwTiles && k == c->vwKey && n == c->vwViews) return RT_OK;
+  c->vwTiles.reset(), c->vwTileView.reset(), c->vwNTiles = 0, c->vwViews = 0;
+  const std::vector<uint32_t> one = wave_tiles(k);
+  std::vector<uint32_t> tiles, view;
+  tiles.reserve(one.size() * n), view.reserve(one.size() * n);
+  for (uint32_t j = 0; j < n; ++j) {
+    tiles.insert(tiles.end(), one.begin(), one.end());
+    view.insert(view.end(), one.size(), j);
+  }
+  int rc = upload(&c->vwTiles, tiles.data(), tiles.size());
+  if (rc == RT_OK) rc = upload(&c->vwTileView, view.data(), view.size());
+  if (rc != RT_OK) return rc;
+  c->vwNTiles = static_cast<uint32_t>(tiles.size()), c->vwViews = n, c->vwKey = k;
+  return RT_OK;
+}
+
+// The view records to the device on `stream`, through a pinned copy that the previous call's upload has finished reading
+int upload_views(rt_ctx* c, const rt_params* p, const rt_views* v, hipStream_t stream) {
+  const uint32_t n = v->n_views;
+  if (n > c->vwCap) {
+    if (c->vwStagedSet) HIP_TRY(hipEventSynchronize(c->vwStaged.get()));
+    c->vwCap = 0, c->vwStagedSet = false;
+    c->vwRecs.reset(), c->vwHost.reset();
+    HIP_TRY(dev_alloc(&c->vwRecs, n));
+    void* h = nullptr;
+    HIP_TRY(hipHostMalloc(&h, n * sizeof(rtk::ViewRec)));
+    c->vwHost.reset(static_cast<rtk::ViewRec*>(h));
+    c->vwCap = n;
+  }
+  if (!c->vwStaged) HIP_TRY(make_event(&c->vwStaged, hipEventDisableTiming));
+  if (c->vwStagedSet) HIP_TRY(hipEventSynchronize(c->vwStaged.get()));
+  rtk::ViewRec* h = c->vwHost.get();
+  const uint32_t px = p->width * p->height;
+  for (uint32_t j = 0; j < n; ++j) {
+    h[j] = rtk::ViewRec{};
+    h[j].cam = v->cameras[j];
+    h[j].seed = v->seeds ? v->seeds[j] : p->seed;
+    h[j].accumOff = j * px;
+  }
+  HIP_TRY(hipMemcpyAsync(c->vwRecs.get(), h, n * sizeof(rtk::ViewRec), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipEventRecord(c->vwStaged.get(), stream));
+  c->vwStagedSet = true;
+  return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_render_views_device(rt_ctx* c, const rt_params* p, const rt_views* v, void* d_accum, void* stream, rt_stats* stats) {
+  rtbvh::Padding pad;
+  bool refit = false;
+  int rc = views_checks(c, p, v, &pad, &refit);
+  if (rc != RT_OK) return rc;
+  if (!d_accum) return fail(RT_ERR_INVALID, "d_accum is null");
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (refit) {  // a camera-only rt_update to the farthest view, whose camera the context does not take
+    if ((rc = update_checks(c, nullptr, 0)) != RT_OK) return rc;
+    Update x;
+    x.padding = &pad;
+    if ((rc = update_ctx(c, x, s, std::chrono::steady_clock::now(), nullptr)) != RT_OK) return rc;
+  }
+  const uint32_t n = v->n_views;
+  const uint32_t sppCount = p->spp_count ? p->spp_count : p->spp;
+  const uint32_t sshift = choose_sshift_px(c, p, (uint64_t)n * p->width * p->height, sppCount);
+  if ((rc = ensure_view_tiles(c, p, sshift, n)) != RT_OK) return rc;
+  if ((rc = upload_views(c, p, v, s)) != RT_OK) return rc;
+  if (stats) HIP_TRY(hipMemsetAsync(c->dCounters.get(), 0, RTK_CNT_COUNT * sizeof(unsigned long long), s));
+  TileList own = {c->vwTiles.get(), c->vwNTiles, sshift};
+  own.tileView = c->vwTileView.get(), own.views = c->vwRecs.get();
+  int e = 0;
+  if ((rc = launch_frame(c, p, static_cast<float4*>(d_accum), s, &e, &own)) != RT_OK) return rc;
+  if (stats) {
+    memset(stats, 0, sizeof *stats);
+    HIP_TRY(hipStreamSynchronize(s));
+    if ((rc = read_counters(c, stats)) != RT_OK) return rc;
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev[e][0].get(), c->ev[e][1].get()));
+    stats->kernel_ms = ms;
+    stats->samples = (uint64_t)n * p->width * p->height * sppCount;
+  }
+  return RT_OK;
+}
+
+int rt_render_views(rt_ctx* c, const rt_params* p, const rt_views* v, const float* bg, float* out_rgb, float* accum_out,
+                    rt_stats* stats) {
+  rtbvh::Padding pad;
+  bool refit = false;
+  int rc = views_checks(c, p, v, &pad, &refit);
+  if (rc != RT_OK) return rc;
+  if (out_rgb && !bg) return fail(RT_ERR_INVALID, "out_rgb requested without a background image");
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t npx = (size_t)p->width * p->height, all = npx * v->n_views;
+  DevBuf<float4> dAccum;
+  DevBuf<float> dBg, dOut;
+  HIP_TRY(dev_alloc(&dAccum, all));
+  HIP_TRY(hipMemset(dAccum.get(), 0, all * sizeof(float4)));
+  if (out_rgb) {
+    HIP_TRY(dev_alloc(&dBg, npx * 3));
+    HIP_TRY(dev_alloc(&dOut, all * 3));
+    HIP_TRY(hipMemcpy(dBg.get(), bg, npx * 3 * sizeof(float), hipMemcpyHostToDevice));
+  }
+  rt_stats local;
+  if ((rc = rt_render_views_device(c, p, v, dAccum.get(), nullptr, stats ? stats : &local)) != RT_OK) return rc;
+  if (out_rgb) {
+    // each view resolved over its slice, with the shared background
+    for (uint32_t j = 0; j < v->n_views; ++j) {
+      const hipError_t he = rtk::launch_resolve((uint32_t)npx, p->spp, dAccum.get() + j * npx, dBg.get(), dOut.get() + 3 * j * npx, nullptr);
+      if (he != hipSuccess) return fail(RT_ERR_HIP, "resolve launch failed: %s", hipGetErrorString(he));
+    }
+    HIP_TRY(hipMemcpy(out_rgb, dOut.get(), all * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  }
+  if (accum_out) HIP_TRY(hipMemcpy(accum_out, dAccum.get(), all * sizeof(float4), hipMemcpyDeviceToHost));
   return RT_OK;
 }
 

@@ -60,6 +60,16 @@ struct DevScene {
   rt_camera cam;
 };
 
+// One view of a multi-view frame (rt_render_views): what the wave tiles of that view render with in place of DevScene::cam,
+// RenderArgs::seed and the accumulator's base.  64 bytes, read by scalar loads.
+struct ViewRec {
+  rt_camera cam;
+  uint32_t seed;      // stream key of the view's pixels
+  uint32_t accumOff;  // first float4 of the view's accumulator slice (view * width * height)
+  uint32_t pad[2];
+};
+static_assert(sizeof(ViewRec) == 64, "ViewRec is four 16-byte scalar loads");
+
 struct RenderArgs {
   const uint32_t* tiles;  // owned wave tiles: x0 | y0 << 16 (pixels, top-left corner)
   uint32_t n_tiles;
@@ -75,6 +85,10 @@ struct RenderArgs {
   uint32_t* tileCounter;  // next wave tile to hand out (zeroed before the launch)
   uint32_t waveWords;     // LDS words per wave (stack levels x 64 + pool), set by the launcher
   uint32_t numCUs;        // workgroups to launch (one per CU)
+  // multi-view frames (rt_render_views): the view of each wave tile (an index into views, parallel to tiles) and the
+  // views' records; null: one view, S.cam, seed and accum as given
+  const uint32_t* tileView;
+  const ViewRec* views;
 };
 
 hipError_t launch_render(bool brute_force, bool photon, bool stats, const DevScene& S, const RenderArgs& A,

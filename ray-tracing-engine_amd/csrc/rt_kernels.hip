@@ -205,6 +205,10 @@ constexpr int LT_COMPACT3 = 64;
 // 1 / det of the triangle test by rtd::recip_fast (3 instructions, the division's bits for |det| < 2^100) instead of the
 // division: only the instances the launcher picks when the host has bounded |det| for the launch's rays (DevScene::slowRecip == 0).
 constexpr int LT_FASTDET = 256;
+// A multi-view frame (rt_render_views): RenderArgs::tileView / views give every wave tile its view's camera, stream key
+// and accumulator slice.  Only render_tile reads it (it strips the bit before it passes LT on).  Its own instances: read
+// at run time, the choice costs every single-view instance SGPR spills and one of them a wave.
+constexpr int LT_VIEWS = 512;
 constexpr uint32_t kPrioMaxNodes = 65536;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(3))) u32x4* lds_u4_ptr;
@@ -1173,14 +1177,32 @@ RT_DEV Lds carve_lds(uint32_t* base, uint32_t levels = STACK, uint32_t kslots = 
 // One wave tile: lane = (pixel pl of the tile, sample slot sj).  The wave integrates
 // S = 1 << sshift consecutive samples of P = 64 >> sshift pixels side by side.
 
-template <bool BRUTE, bool PHOTON, bool POOLED, bool STATS, int LT, class HP = Heap>
+template <bool BRUTE, bool PHOTON, bool POOLED, bool STATS, int LTV, class HP = Heap>
 RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restrict__ accum, const Lds& L, uint32_t* pool,
                         float* ex, uint32_t wave, LaneStats& st) {
+  constexpr int LT = LTV & ~LT_VIEWS;
+  constexpr bool VIEWS = (LTV & LT_VIEWS) != 0;
   constexpr bool FR = (LT & LT_FASTDET) != 0;  // 1 / length by rtd::recip_fast (see rtd::unit3)
   const uint32_t lane = threadIdx.x & 63u;
   // lane = (pixel pl of the wave tile, sample slot sj): the wave integrates
   // S = 1 << sshift consecutive samples of P = 64 >> sshift pixels side by side
   const uint32_t tile = A.tiles[wave];
+  // A multi-view frame: the tile's view picks the camera, the stream key and the accumulator slice.  `wave` is wave-
+  // uniform (a block index, or readfirstlane of the tile counter), so the view index and its record are read with scalar
+  // loads through the constant address space and stay in SGPRs.
+  // (single-view instances read S.cam and A.seed as they always did)
+  rt_camera cam;
+  uint32_t seed = A.seed;
+  if constexpr (VIEWS) {
+    typedef const __attribute__((address_space(4))) uint32_t* const_u32_ptr;
+    typedef const __attribute__((address_space(4))) ViewRec* const_view_ptr;
+    const const_view_ptr R = (const_view_ptr)A.views + ((const_u32_ptr)A.tileView)[wave];
+    for (int j = 0; j < 3; ++j)
+      cam.position[j] = R->cam.position[j], cam.lower_left[j] = R->cam.lower_left[j],
+      cam.horizontal[j] = R->cam.horizontal[j], cam.vertical[j] = R->cam.vertical[j];
+    seed = R->seed;
+    accum += R->accumOff;
+  }
   const uint32_t S_ = 1u << A.sshift, P_ = 64u >> A.sshift;
   const uint32_t pl = lane & (P_ - 1u), sj = lane >> (6u - A.sshift);
   const uint32_t wsh = (uint32_t)__builtin_ctz(A.tileW);
@@ -1194,11 +1216,13 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
   for (uint32_t base = A.s0; base < A.s1; base += S_) {
     const uint32_t i = base + sj;
     const bool active = inImage && i < A.s1;
-    Rng g{rt_stream_seed(A.seed, RT_STREAM_PIXEL, pix, i)};
+    Rng g{rt_stream_seed(VIEWS ? seed : A.seed, RT_STREAM_PIXEL, pix, i)};
     float sx, sy;
     jitter_sample(g, (int)i, (int)A.spp, sx, sy);
     f3 o, d;
-    camera_ray<FR>(S.cam, ((float)px + sx) / (float)A.width, 1.f - ((float)py + sy) / (float)A.height, o, d);
+    const float cu = ((float)px + sx) / (float)A.width, cv = 1.f - ((float)py + sy) / (float)A.height;
+    if constexpr (VIEWS) camera_ray<FR>(cam, cu, cv, o, d);
+    else camera_ray<FR>(S.cam, cu, cv, o, d);
     f3 c0 = mk(0.f, 0.f, 0.f), c1 = c0, c2 = c0;
     bool primary = true, alive = active;
     if constexpr (pooled) {
@@ -1287,7 +1311,7 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
   if (owner) accum[pix] = sum;
 }
 
-template <bool BRUTE, bool PHOTON, bool POOLED, bool STATS, int MINW>
+template <bool BRUTE, bool PHOTON, bool POOLED, bool STATS, int MINW, int LTV = LT_NONE>
 __global__ __launch_bounds__(BLOCK, MINW) void k_render(DevScene S, RenderArgs A, float4* __restrict__ accum,
                                                   unsigned long long* __restrict__ counters) {
   static_assert(BLOCK == 64, "one wave per workgroup");
@@ -1305,7 +1329,7 @@ __global__ __launch_bounds__(BLOCK, MINW) void k_render(DevScene S, RenderArgs A
   // A.tilesPerBlock consecutive wave tiles per workgroup (1 unless RT_TILES_PER_BLOCK says otherwise: more of them
   // unbalance the grid — C3 13.7 / 14.8 / 17.8 ms at 4 / 8 / 16)
   const uint32_t t0 = blockIdx.x * A.tilesPerBlock, t1 = min(A.n_tiles, t0 + A.tilesPerBlock);
-  for (uint32_t t = t0; t < t1; ++t) render_tile<BRUTE, PHOTON, POOLED, STATS, LT_NONE>(S, A, accum, L, pool, ex, t, st);
+  for (uint32_t t = t0; t < t1; ++t) render_tile<BRUTE, PHOTON, POOLED, STATS, LTV>(S, A, accum, L, pool, ex, t, st);
   if (STATS) flush_stats(st, counters, true);
   else flush_stats_striped(st, counters);  // (launch_render2 folds the stripes)
 }
@@ -1313,7 +1337,7 @@ __global__ __launch_bounds__(BLOCK, MINW) void k_render(DevScene S, RenderArgs A
 // Photon frames with 17 <= k <= RT_KNN_KMAX: k_render's photon path with the k-heap on layout HL (heap_rows(HL, k) rows
 // above the stack rows).  LDS, not registers, sets these kernels' waves (a k-slot heap is 6 or 8 x 64 x k bytes per
 // wave): MINW is the occupancy the smallest of them reaches, so the walk has every register it can use.
-template <bool BRUTE, bool STATS, int MINW, int HL>
+template <bool BRUTE, bool STATS, int MINW, int HL, int LTV = LT_NONE>
 __global__ __launch_bounds__(BLOCK, MINW) void k_render_wide(DevScene S, RenderArgs A, float4* __restrict__ accum,
                                                           unsigned long long* __restrict__ counters) {
   uint32_t* lds = g_lds;
@@ -1322,7 +1346,7 @@ __global__ __launch_bounds__(BLOCK, MINW) void k_render_wide(DevScene S, RenderA
   LaneStats st;
   const uint32_t t0 = blockIdx.x * A.tilesPerBlock, t1 = min(A.n_tiles, t0 + A.tilesPerBlock);
   for (uint32_t t = t0; t < t1; ++t)
-    render_tile<BRUTE, true, false, STATS, LT_NONE, WideHeap<HL>>(S, A, accum, L, nullptr, ex, t, st);
+    render_tile<BRUTE, true, false, STATS, LTV, WideHeap<HL>>(S, A, accum, L, nullptr, ex, t, st);
   if (STATS) flush_stats(st, counters, true);
   else flush_stats_striped(st, counters);
 }
@@ -1851,13 +1875,18 @@ static hipError_t launch_render_wide(bool stats, const DevScene& S, const Render
   if (A.k > (uint32_t)RT_KNN_KMAX || ldsBytes > 4u * (size_t)rtbvh::kLdsWordsPerCU) return hipErrorInvalidValue;
   RenderArgs A1 = A;
   A1.tilesPerBlock = 1u;
-#define RT_LAUNCH_WIDE(ST, MW, HLV)                                                                               \
-  do {                                                                                                            \
-    static unsigned long long done = 0;                                                                           \
-    if (!allow_big_lds(&k_render_wide<BRUTE, ST, MW, HLV>, done)) return hipErrorInvalidConfiguration;            \
-    knn_report(k_render_wide<BRUTE, ST, MW, HLV>, "k_render_wide", HLV, A.k, ldsBytes);                          \
-    hipLaunchKernelGGL((k_render_wide<BRUTE, ST, MW, HLV>), dim3(A.n_tiles), dim3(BLOCK), ldsBytes, stream, S, A1, \
-                       accum, counters);                                                                          \
+#define RT_LAUNCH_WIDE1(ST, MW, HLV, LTV)                                                                             \
+  do {                                                                                                                \
+    static unsigned long long done = 0;                                                                               \
+    if (!allow_big_lds(&k_render_wide<BRUTE, ST, MW, HLV, LTV>, done)) return hipErrorInvalidConfiguration;            \
+    knn_report(k_render_wide<BRUTE, ST, MW, HLV, LTV>, "k_render_wide", HLV, A.k, ldsBytes);                          \
+    hipLaunchKernelGGL((k_render_wide<BRUTE, ST, MW, HLV, LTV>), dim3(A.n_tiles), dim3(BLOCK), ldsBytes, stream, S, A1, \
+                       accum, counters);                                                                              \
+  } while (0)
+#define RT_LAUNCH_WIDE(ST, MW, HLV)                        \
+  do {                                                     \
+    if (A.tileView) RT_LAUNCH_WIDE1(ST, MW, HLV, LT_VIEWS); \
+    else RT_LAUNCH_WIDE1(ST, MW, HLV, LT_NONE);            \
   } while (0)
 #define RT_LAUNCH_WIDE_HL(ST, MW)                                   \
   do {                                                              \
@@ -1871,6 +1900,7 @@ static hipError_t launch_render_wide(bool stats, const DevScene& S, const Render
   }
 #undef RT_LAUNCH_WIDE_HL
 #undef RT_LAUNCH_WIDE
+#undef RT_LAUNCH_WIDE1
   return hipGetLastError();
 }
 
@@ -1891,12 +1921,17 @@ static hipError_t launch_render2(bool stats, const DevScene& S, const RenderArgs
       const uint32_t perCU = P.waves;                                    // waves one workgroup brings
       const uint32_t slots = P.compact == 3 ? 5u * A.numCUs : A.numCUs;  // workgroups the device holds at once
       const uint32_t wgs = (blocks + perCU - 1) / perCU < slots ? (blocks + perCU - 1) / perCU : slots;
-#define RT_LAUNCH_PERSIST(ST, LTV)                                                                          \
+#define RT_LAUNCH_PERSIST1(ST, LTV)                                                                         \
   do {                                                                                                      \
     static unsigned long long done = 0;                                                                     \
     if (!allow_big_lds(&k_render_persist<ST, LTV>, done)) return hipErrorInvalidConfiguration;              \
     hipLaunchKernelGGL((k_render_persist<ST, LTV>), dim3(wgs), dim3(64u * P.waves), P.ldsBytes, stream, S2, \
                        A2, accum, counters);                                                                \
+  } while (0)
+#define RT_LAUNCH_PERSIST(ST, LTV)                                \
+  do {                                                            \
+    if (A.tileView) RT_LAUNCH_PERSIST1(ST, (LTV) | LT_VIEWS);     \
+    else RT_LAUNCH_PERSIST1(ST, LTV);                             \
   } while (0)
       // Two instances per layout: the timed one, with the three-instruction 1 / det and 1 / length (the host has bounded
       // their operands: DevScene::slowRecip == 0), and the COUNTED one, which divides — and which also serves the rare
@@ -1908,15 +1943,21 @@ static hipError_t launch_render2(bool stats, const DevScene& S, const RenderArgs
   } while (0)
       const int lt = P.topK == 0 ? LT_NONE : P.topK >= S.n_nodes ? LT_ALL : LT_TOP;
       if (P.compact == 3) {
-        static unsigned long long done5s = 0, done5t = 0;
+#define RT_LAUNCH_PERSIST5(ST, LTV)                                                                                       \
+  do {                                                                                                                    \
+    static unsigned long long done = 0;                                                                                   \
+    if (!allow_big_lds(&k_render_persist5<ST, LTV>, done)) return hipErrorInvalidConfiguration;                           \
+    hipLaunchKernelGGL((k_render_persist5<ST, LTV>), dim3(wgs), dim3(256), P.ldsBytes, stream, S2, A2, accum, counters); \
+  } while (0)
+        constexpr int C3 = LT_NONE | LT_NOPRIO | LT_COMPACT3;
         if (stats || S.slowRecip) {
-          if (!allow_big_lds(&k_render_persist5<true, LT_NONE | LT_NOPRIO | LT_COMPACT3>, done5s)) return hipErrorInvalidConfiguration;
-          hipLaunchKernelGGL((k_render_persist5<true, LT_NONE | LT_NOPRIO | LT_COMPACT3>), dim3(wgs), dim3(256), P.ldsBytes, stream, S2, A2, accum, counters);
+          if (A.tileView) RT_LAUNCH_PERSIST5(true, C3 | LT_VIEWS);
+          else RT_LAUNCH_PERSIST5(true, C3);
         } else {
-          if (!allow_big_lds(&k_render_persist5<false, LT_NONE | LT_NOPRIO | LT_COMPACT3 | LT_FASTDET>, done5t)) return hipErrorInvalidConfiguration;
-          hipLaunchKernelGGL((k_render_persist5<false, LT_NONE | LT_NOPRIO | LT_COMPACT3 | LT_FASTDET>), dim3(wgs), dim3(256), P.ldsBytes, stream, S2, A2,
-                             accum, counters);
+          if (A.tileView) RT_LAUNCH_PERSIST5(false, C3 | LT_FASTDET | LT_VIEWS);
+          else RT_LAUNCH_PERSIST5(false, C3 | LT_FASTDET);
         }
+#undef RT_LAUNCH_PERSIST5
       } else if (S.q8) {  // the one-request records (the context chose them: rt_api.cpp create_ctx)
         if (P.compact == 2) RT_LAUNCH_EITHER(LT_Q8 | LT_NOPRIO | LT_COMPACT2);
         else if (P.compact) RT_LAUNCH_EITHER(LT_Q8 | LT_NOPRIO | LT_COMPACT);
@@ -1928,6 +1969,7 @@ static hipError_t launch_render2(bool stats, const DevScene& S, const RenderArgs
       else RT_LAUNCH_EITHER(LT_NONE | LT_NOPRIO);  // (a small tree beside stacks that leave no room for 256 of its nodes: rare)
 #undef RT_LAUNCH_EITHER
 #undef RT_LAUNCH_PERSIST
+#undef RT_LAUNCH_PERSIST1
       return hipGetLastError();
     }
   }
@@ -1943,9 +1985,12 @@ static hipError_t launch_render2(bool stats, const DevScene& S, const RenderArgs
   constexpr int MINW = PHOTON ? 5 : 4;
   if (PHOTON) knn_report(stats ? k_render<BRUTE, PHOTON, POOLED, true, 1> : k_render<BRUTE, PHOTON, POOLED, false, MINW>,
                          "k_render", -1, A.k, ldsBytes);
-  if (stats) hipLaunchKernelGGL((k_render<BRUTE, PHOTON, POOLED, true, 1>), dim3(nBlocks), dim3(BLOCK), ldsBytes, stream, S, A1, accum, counters);
-  else {
-    hipLaunchKernelGGL((k_render<BRUTE, PHOTON, POOLED, false, MINW>), dim3(nBlocks), dim3(BLOCK), ldsBytes, stream, S, A1, accum, counters);
+  if (stats) {
+    if (A.tileView) hipLaunchKernelGGL((k_render<BRUTE, PHOTON, POOLED, true, 1, LT_VIEWS>), dim3(nBlocks), dim3(BLOCK), ldsBytes, stream, S, A1, accum, counters);
+    else hipLaunchKernelGGL((k_render<BRUTE, PHOTON, POOLED, true, 1>), dim3(nBlocks), dim3(BLOCK), ldsBytes, stream, S, A1, accum, counters);
+  } else {
+    if (A.tileView) hipLaunchKernelGGL((k_render<BRUTE, PHOTON, POOLED, false, MINW, LT_VIEWS>), dim3(nBlocks), dim3(BLOCK), ldsBytes, stream, S, A1, accum, counters);
+    else hipLaunchKernelGGL((k_render<BRUTE, PHOTON, POOLED, false, MINW>), dim3(nBlocks), dim3(BLOCK), ldsBytes, stream, S, A1, accum, counters);
     hipLaunchKernelGGL(k_fold_stripes, dim3(1), dim3(1024), 0, stream, counters);
   }
   return hipGetLastError();

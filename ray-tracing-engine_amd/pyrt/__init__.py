@@ -128,6 +128,28 @@ class AdaptiveReport(C.Structure):
         return d
 
 
+class Views(C.Structure):
+    """rt_views: the cameras (and optional per-view seeds) of a multi-view frame, host memory."""
+    _fields_ = [("n_views", C.c_uint32), ("reserved0", C.c_uint32), ("cameras", C.POINTER(Camera)),
+                ("seeds", C.POINTER(C.c_uint32)), ("reserved", C.c_uint32 * 6)]
+
+
+def make_views(cameras, seeds=None):
+    """rt_views over cameras [n][4][3] (float32) and seeds [n] (uint32) or None; returns (views, arrays to keep alive)."""
+    cams = np.ascontiguousarray(cameras, np.float32).reshape(-1, 12)
+    v = Views()
+    v.n_views = len(cams)
+    v.cameras = C.cast(cams.ctypes.data, C.POINTER(Camera))
+    keep = [cams]
+    if seeds is not None:
+        sd = np.ascontiguousarray(seeds, np.uint32).reshape(-1)
+        if len(sd) != len(cams):
+            raise ValueError("%d seeds for %d cameras" % (len(sd), len(cams)))
+        v.seeds = C.cast(sd.ctypes.data, C.POINTER(C.c_uint32))
+        keep.append(sd)
+    return v, keep
+
+
 def make_adaptive(threshold, max_passes, min_passes=0, floor=0.):
     a = AdaptiveParams()
     a.max_passes, a.min_passes, a.threshold, a.floor = max_passes, min_passes, threshold, floor
@@ -162,7 +184,8 @@ AMD_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_create", "rt_destroy", "rt
                "rt_trace_stream_device", "rt_build_photon_map", "rt_get_photons", "rt_test_kd_order", "rt_owned_granules", "rt_pack_owned_device", "rt_unpack_owned_device", "rt_group_create", "rt_group_destroy",
                "rt_group_size", "rt_group_uses_rccl", "rt_group_ctx", "rt_group_set_photons", "rt_group_render",
                "rt_update", "rt_update_vertices_device", "rt_group_update", "rt_render_aov", "rt_render_aov_device",
-               "rt_denoise", "rt_denoise_device", "rt_render_adaptive", "rt_render_adaptive_device"]
+               "rt_denoise", "rt_denoise_device", "rt_render_adaptive", "rt_render_adaptive_device", "rt_render_views",
+               "rt_render_views_device"]
 HOST_SYMBOLS = ["rt_host_scene_build", "rt_host_scene_desc", "rt_host_scene_free", "rt_host_last_error",
                 "rt_host_fill_background", "rt_host_save_ppm", "rt_host_kd_order"]
 
@@ -246,6 +269,10 @@ def amd():
         L.rt_render_adaptive_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(AdaptiveParams), C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AdaptiveReport),
                                                 C.POINTER(Stats)]
+        L.rt_render_views.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Views), C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.POINTER(Stats)]
+        L.rt_render_views_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Views), C.c_void_p, C.c_void_p,
+                                             C.POINTER(Stats)]
         L.rt_denoise_device.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.POINTER(Aov), C.c_void_p,
                                         C.c_void_p]
         _amd = L
@@ -504,6 +531,26 @@ class Context:
         st = Stats() if stats else None
         _check(amd().rt_render_device(self._h, C.byref(params), C.c_void_p(d_accum_ptr), C.c_void_p(stream),
                                       C.byref(st) if stats else None))
+        return st
+
+    def render_views(self, params, cameras, bg=None, seeds=None, want_accum=True):
+        """rt_render_views: the frames of cameras [n][4][3] (seeds [n] or None = params.seed) in one launch; returns
+        (out [n][h][w][3] or None without bg, accum [n][h][w][4] or None, stats)."""
+        v, _keep = make_views(cameras, seeds)
+        w, h, n = params.width, params.height, v.n_views
+        out = np.empty((n, h, w, 3), np.float32) if bg is not None else None
+        acc = np.empty((n, h, w, 4), np.float32) if want_accum else None
+        st = Stats()
+        bgc = None if bg is None else np.ascontiguousarray(bg, np.float32)
+        _check(amd().rt_render_views(self._h, C.byref(params), C.byref(v), _ptr(bgc), _ptr(out), _ptr(acc), C.byref(st)))
+        return out, acc, st
+
+    def render_views_device(self, params, cameras, d_accum_ptr, stream=0, seeds=None, stats=False):
+        """rt_render_views_device: accumulate into the caller-zeroed device d_accum [n][h][w][4] on `stream`."""
+        v, _keep = make_views(cameras, seeds)
+        st = Stats() if stats else None
+        _check(amd().rt_render_views_device(self._h, C.byref(params), C.byref(v), C.c_void_p(d_accum_ptr),
+                                            C.c_void_p(stream), C.byref(st) if stats else None))
         return st
 
     def resolve_device(self, width, height, spp, d_accum_ptr, d_bg_ptr, d_out_ptr, stream=0):
