@@ -537,6 +537,12 @@ int rt_profile_collect(rt_ctx* ctx, double* total_kernel_ms, uint32_t* launches)
  *   RT_UNIT_RECIP        in: float x                      out: the three-instruction reciprocal, 1.0f / x, the five-
  *                        instruction square root, sqrtf(x) (Ray.cpp:14's inv_det, Vec3.h:170-178's length: each pair
  *                        must agree bit for bit for 2^-100 <= |x| <= 2^100)
+ *   RT_UNIT_BSDF_HOISTED in: as RT_UNIT_BSDF (17 f)       out: three rgb (9 f): the form the render kernels run — the
+ *                        per-material record rt_create / rt_update make on the host, then the per-vertex and per-light
+ *                        halves on the device — with the division and sqrtf, the same with the short reciprocal and
+ *                        square root (the render instances' FAST flavour), and RT_UNIT_BSDF's one-piece form FAST.
+ *                        FAST is only promised for vectors whose squared length is below 2^100 (rt_create vouches for
+ *                        that bound before it picks a FAST instance); all three then equal RT_UNIT_BSDF bit for bit.
  */
 enum {
   RT_UNIT_ASIN = 0,
@@ -550,7 +556,8 @@ enum {
   RT_UNIT_SAMPLERS = 8,
   RT_UNIT_LIGHT_SAMPLE = 9,
   RT_UNIT_POW = 10,
-  RT_UNIT_RECIP = 11
+  RT_UNIT_RECIP = 11,
+  RT_UNIT_BSDF_HOISTED = 12
 };
 int rt_test_unit(int32_t device, uint32_t which, const void* in, void* out, uint32_t n);
 

@@ -28,6 +28,10 @@ const char* rt_host_last_error(void);
 void rt_host_fill_background(float* rgb, uint32_t width, uint32_t height);
 int rt_host_save_ppm(const char* path, const float* rgb, uint32_t width, uint32_t height);
 
+/* LightSource(position, color, direction, intensity, sideLength): the basis its constructor derives
+ * (source/LightSource.h:28-32), out9 = vertical, horizontal, normal as rt_light carries them. */
+int rt_host_light_basis(const float* position3, const float* direction3, float* out9);
+
 /* kdtree::make_tree: permute n photons (pos[n][3], dir[n][3], weight[n]) in
  * place into the median-implicit order the k-NN kernel walks. */
 int rt_host_kd_order(float* pos3, float* dir3, float* weight, uint32_t n);

@@ -17,6 +17,7 @@
 //   vectors <meshdir> <out.json>
 //   knn     <out.json>                                        (tie-heavy k-NN maps)
 //   time    <meshdir> <scene> <w> <h> <mode> <N> <p> <k>     (prints seconds)
+//   shading <meshdir> <in.bin> <out.json> <ppm_prefix>        (swept materials, lights, frames: tests/shading_sweep.py)
 #define _USE_MATH_DEFINES
 #include <assert.h>
 // NB: <math.h> must NOT be pre-included: libstdc++'s wrapper would pull the float
@@ -708,9 +709,98 @@ int cmdKnn(const std::string& out) {
   return 0;
 }
 
+// ---------------------------------------------------------------- shading sweep
+// shading <meshdir> <in.bin> <out.json> <ppm_prefix>: the inputs tests/golden/make_shading_golden.py wrote from
+// tests/shading_sweep.py, through the reference's own Material, LightSource and Renderer.  in.bin (little endian):
+//   uint32 header[8] = 'SHAD', n_bsdf, n_eval, n_basis, n_frames, 0, 0, 0
+//   float  bsdf[n_bsdf][17]   kd alpha albedo3 f03 n3 wi3 wo3
+//   float  eval[n_eval][19]   light spec (position3 color3 direction3 intensity side factor ac al aq 0), point3
+//   float  basis[n_basis][6]  position3 direction3
+//   per frame: uint32 {w, h, mode, N, n_lights, 0}, float materials[5][8], float lights[n_lights][16] (specs)
+// out.json: "bsdf" [n][3], "evaluateLight" [n][3], "basis" [n][9] = m_vertical m_horizontal m_normal, as bit patterns;
+// frame i (cubes geometry, legacy serial RNG from a seed-1 engine) goes to <ppm_prefix><i>.ppm.
+LightSource lightOf(const float* s) {
+  LightSource l(Vec3f(s[0], s[1], s[2]), Vec3f(s[3], s[4], s[5]), Vec3f(s[6], s[7], s[8]), s[9], s[10]);
+  l.m_factor = s[11], l.ac = s[12], l.al = s[13], l.aq = s[14];
+  return l;
+}
+
+int cmdShading(const std::string& meshdir, const std::string& in, const std::string& out, const std::string& prefix) {
+  std::ifstream f(in, std::ios::binary);
+  if (!f) throw std::runtime_error("cannot open " + in);
+  uint32_t hdr[8];
+  f.read((char*)hdr, sizeof(hdr));
+  if (!f || hdr[0] != 0x44414853u) throw std::runtime_error("not a shading sweep file: " + in);
+  auto floats = [&](size_t n) {
+    std::vector<float> v(n);
+    f.read((char*)v.data(), (std::streamsize)(n * sizeof(float)));
+    if (!f) throw std::runtime_error("short shading sweep file");
+    return v;
+  };
+  const uint32_t nBsdf = hdr[1], nEval = hdr[2], nBasis = hdr[3], nFrames = hdr[4];
+  std::vector<float> bsdf = floats((size_t)nBsdf * 17), eval = floats((size_t)nEval * 19), basis = floats((size_t)nBasis * 6);
+  J j;
+  j.o << "{\n";
+  {
+    std::vector<uint32_t> v;
+    for (uint32_t i = 0; i < nBsdf; i++) {
+      const float* a = &bsdf[(size_t)i * 17];
+      Material M(a[0], a[1], Vec3f(a[2], a[3], a[4]), Vec3f(a[5], a[6], a[7]));
+      push3(v, M.evaluateColorResponse(Vec3f(a[8], a[9], a[10]), Vec3f(a[11], a[12], a[13]), Vec3f(a[14], a[15], a[16])));
+    }
+    j.u32("bsdf", v);
+  }
+  {
+    std::vector<uint32_t> v;
+    for (uint32_t i = 0; i < nEval; i++) {
+      const float* a = &eval[(size_t)i * 19];
+      LightSource l = lightOf(a);
+      push3(v, l.evaluateLight(Vec3f(a[16], a[17], a[18])));
+    }
+    j.u32("evaluateLight", v);
+  }
+  {
+    std::vector<uint32_t> v;
+    for (uint32_t i = 0; i < nBasis; i++) {
+      const float* a = &basis[(size_t)i * 6];
+      LightSource l(Vec3f(a[0], a[1], a[2]), Vec3f(1.f, 1.f, 1.f), Vec3f(a[3], a[4], a[5]), 1.f, 0.f);
+      push3(v, l.m_vertical);
+      push3(v, l.m_horizontal);
+      push3(v, l.m_normal);
+    }
+    j.u32("basis", v);
+  }
+  j.o << "\n}\n";
+  std::ofstream(out) << j.o.str();
+  std::cout.setstate(std::ios::failbit);  // silence the progress bar
+  for (uint32_t i = 0; i < nFrames; i++) {
+    uint32_t fh[6];
+    f.read((char*)fh, sizeof(fh));
+    if (!f) throw std::runtime_error("short shading sweep file (frame)");
+    std::vector<float> mats = floats(40), lights = floats((size_t)fh[4] * 16);
+    Scene scene = buildScene(meshdir, "cubes", fh[0], fh[1]);
+    for (int m = 0; m < 5; m++) {
+      const float* a = &mats[(size_t)m * 8];
+      scene.meshes()[m].material() = Material(a[0], a[1], Vec3f(a[2], a[3], a[4]), Vec3f(a[5], a[6], a[7]));
+    }
+    scene.lightsources().clear();
+    for (uint32_t l = 0; l < fh[4]; l++) scene.lightsources().push_back(lightOf(&lights[(size_t)l * 16]));
+    gen.seed(1);  // every frame from the engine state a fresh process has
+    Image image(fh[0], fh[1]);
+    RayTracer rt;
+    Renderer renderer(scene, (int)fh[3], (int)fh[2], rt);
+    image.fillBackground();
+    renderer.render(image);
+    image.savePPM(prefix + std::to_string(i) + ".ppm");
+  }
+  std::cout.clear();
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
+  if (argc >= 6 && !strcmp(argv[1], "shading")) return cmdShading(argv[2], argv[3], argv[4], argv[5]);
   if (argc >= 4 && !strcmp(argv[1], "vectors")) return cmdVectors(argv[2], argv[3]);
   if (argc >= 3 && !strcmp(argv[1], "knn")) return cmdKnn(argv[2]);
   if (argc >= 11 && !strcmp(argv[1], "render")) return cmdRender(argc, argv, false);

@@ -930,6 +930,23 @@ void orc_eval_light(const rt_light* l, const float* p, float* out3) {
   V3 r = evaluateLight(*l, ld3(p));
   out3[0] = r.x, out3[1] = r.y, out3[2] = r.z;
 }
+// the same two over packed rows (tests/shading_sweep.py): rows17 = kd alpha albedo3 f03 n3 wi3 wo3, rows24 = rt_light point3
+void orc_bsdf_rows(const float* rows17, uint32_t n, int32_t math_mode, float* out3) {
+  for (uint32_t i = 0; i < n; i++) {
+    const float* a = rows17 + 17 * (size_t)i;
+    rt_material m;
+    memcpy(&m, a, sizeof(m));
+    orc_bsdf(&m, math_mode, a + 8, a + 11, a + 14, out3 + 3 * (size_t)i);
+  }
+}
+void orc_eval_light_rows(const float* rows24, uint32_t n, float* out3) {
+  for (uint32_t i = 0; i < n; i++) {
+    const float* a = rows24 + 24 * (size_t)i;
+    rt_light l;
+    memcpy(&l, a, sizeof(l));
+    orc_eval_light(&l, a + 21, out3 + 3 * (size_t)i);
+  }
+}
 uint32_t orc_engine_next(uint32_t* state) {
   Engine e{*state};
   uint32_t v = e.next();

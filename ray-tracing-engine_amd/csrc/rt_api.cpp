@@ -1394,17 +1394,34 @@ int rt_profile_collect(rt_ctx* c, double* total_ms, uint32_t* launches) {
 }
 
 int rt_test_unit(int32_t device, uint32_t which, const void* in, void* out, uint32_t n) {
-  static const uint32_t inBytes[] = {8, 4, 4, 16, 60, 68, 56, 96, 112, 88, 8, 4};
-  static const uint32_t outBytes[] = {8, 4, 4, 4, 16, 12, 24, 12, 48, 16, 16, 16};
-  if (which > RT_UNIT_RECIP) return fail(RT_ERR_INVALID, "unknown unit %u", which);
+  static const uint32_t inBytes[] = {8, 4, 4, 16, 60, 68, 56, 96, 112, 88, 8, 4, 68};
+  static const uint32_t outBytes[] = {8, 4, 4, 4, 16, 12, 24, 12, 48, 16, 16, 16, 36};
+  if (which > RT_UNIT_BSDF_HOISTED) return fail(RT_ERR_INVALID, "unknown unit %u", which);
   if (n && (!in || !out)) return fail(RT_ERR_INVALID, "null argument");
   if (n == 0) return RT_OK;
   int rc = select_device(device);
   if (rc != RT_OK) return rc;
+  // RT_UNIT_BSDF_HOISTED: the device reads each row followed by the record rt_create would make of its material
+  std::vector<float> hoisted;
+  size_t devInBytes = inBytes[which];
+  if (which == RT_UNIT_BSDF_HOISTED) {
+    static_assert(sizeof(rtd::DevMat) == 16 * sizeof(float) && sizeof(rt_material) == 8 * sizeof(float), "unit row layout");
+    devInBytes = (17 + 16) * sizeof(float);
+    hoisted.resize((size_t)n * 33);
+    for (uint32_t i = 0; i < n; ++i) {
+      const float* row = static_cast<const float*>(in) + 17 * (size_t)i;
+      rt_material m;
+      memcpy(&m, row, sizeof(m));  // kd alpha albedo3 f03
+      const rtd::DevMat dm = rtd::make_dev_mat(m);
+      memcpy(&hoisted[33 * (size_t)i], row, 17 * sizeof(float));
+      memcpy(&hoisted[33 * (size_t)i + 17], &dm, sizeof(dm));
+    }
+    in = hoisted.data();
+  }
   DevBuf<char> dIn, dOut;
-  HIP_TRY(dev_alloc(&dIn, (size_t)n * inBytes[which]));
+  HIP_TRY(dev_alloc(&dIn, (size_t)n * devInBytes));
   hipError_t he = dev_alloc(&dOut, (size_t)n * outBytes[which]);
-  if (he == hipSuccess) he = hipMemcpy(dIn.get(), in, (size_t)n * inBytes[which], hipMemcpyHostToDevice);
+  if (he == hipSuccess) he = hipMemcpy(dIn.get(), in, (size_t)n * devInBytes, hipMemcpyHostToDevice);
   if (he == hipSuccess) he = hipMemcpy(dOut.get(), out, (size_t)n * outBytes[which], hipMemcpyHostToDevice);
   if (he == hipSuccess) he = rtk::launch_unit(which, dIn.get(), dOut.get(), n, nullptr);
   if (he == hipSuccess) he = hipMemcpy(out, dOut.get(), (size_t)n * outBytes[which], hipMemcpyDeviceToHost);

@@ -1752,6 +1752,23 @@ __global__ void k_unit(uint32_t which, const void* __restrict__ in, void* __rest
       o[0] = rtd::recip_fast(x), o[1] = 1.0f / x, o[2] = rtd::sqrt_fast(x), o[3] = __builtin_sqrtf(x);
       break;
     }
+    case RT_UNIT_BSDF_HOISTED: {
+      // in (33 floats): the 17 of RT_UNIT_BSDF, then the rtd::DevMat the host made of the material (rt_api.cpp);
+      // out: the hoisted form, the hoisted form FAST, the rt_material form FAST (9 floats)
+      const float* a = (const float*)in + 33 * (size_t)i;
+      rt_material m;
+      m.kd = a[0], m.alpha = a[1];
+      for (int c = 0; c < 3; c++) m.albedo[c] = a[2 + c], m.f0[c] = a[5 + c];
+      DevMat dm;
+      memcpy(&dm, a + 17, sizeof(DevMat));
+      const f3 n = ld(a + 8), wi = ld(a + 11), wo = ld(a + 14);
+      const f3 r0 = bsdf_apply<false>(bsdf_base<false>(dm, n, wo), wi);
+      const f3 r1 = bsdf_apply<true>(bsdf_base<true>(dm, n, wo), wi);
+      const f3 r2 = bsdf_apply<true>(bsdf_base<true>(m, n, wo), wi);
+      float* o = (float*)out + 9 * (size_t)i;
+      o[0] = r0.x, o[1] = r0.y, o[2] = r0.z, o[3] = r1.x, o[4] = r1.y, o[5] = r1.z, o[6] = r2.x, o[7] = r2.y, o[8] = r2.z;
+      break;
+    }
     default:
       break;
   }

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "Image.h"
+#include "LightSource.h"
 #include "Ray.h"
 #include "SceneFlatten.h"
 #include "ScenePresets.h"
@@ -94,6 +95,18 @@ int rt_host_save_ppm(const char* path, const float* rgb, uint32_t width, uint32_
   }
   probe.close();
   img.savePPM(path);
+  return RT_OK;
+}
+
+// The basis LightSource's five-argument constructor derives (LightSource.h:28-32), as the flattener stores it.
+int rt_host_light_basis(const float* position3, const float* direction3, float* out9) {
+  if (!position3 || !direction3 || !out9) {
+    g_hostErr = "null light arguments";
+    return RT_ERR_INVALID;
+  }
+  const LightSource l(Vec3f(position3[0], position3[1], position3[2]), Vec3f(1.f, 1.f, 1.f),
+                      Vec3f(direction3[0], direction3[1], direction3[2]), 1.f, 0.f);
+  for (int c = 0; c < 3; ++c) out9[c] = l.vertical()[c], out9[3 + c] = l.horizontal()[c], out9[6 + c] = l.normal()[c];
   return RT_OK;
 }
 

@@ -22,7 +22,7 @@ ACCEL_BVH, ACCEL_BRUTE = 0, 1
 BVH_AUTO, BVH_DEVICE, BVH_HYBRID, BVH_HOST = 0, 1, 2, 3
 TRACE_CLOSEST, TRACE_ANY = 0, 1
 (UNIT_ASIN, UNIT_SINF, UNIT_COSF, UNIT_STREAM_SEED, UNIT_TRIANGLE, UNIT_BSDF, UNIT_RAY_AT, UNIT_LIGHT_EVAL,
- UNIT_SAMPLERS, UNIT_LIGHT_SAMPLE, UNIT_POW, UNIT_RECIP) = range(12)
+ UNIT_SAMPLERS, UNIT_LIGHT_SAMPLE, UNIT_POW, UNIT_RECIP, UNIT_BSDF_HOISTED) = range(13)
 KMAX = 16  # rt_knn
 KMAX_WIDE = 256  # rt_knn_wide and photon frames (RT_KNN_KMAX)
 
@@ -187,7 +187,7 @@ AMD_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_create", "rt_destroy", "rt
                "rt_denoise", "rt_denoise_device", "rt_render_adaptive", "rt_render_adaptive_device", "rt_render_views",
                "rt_render_views_device"]
 HOST_SYMBOLS = ["rt_host_scene_build", "rt_host_scene_desc", "rt_host_scene_free", "rt_host_last_error",
-                "rt_host_fill_background", "rt_host_save_ppm", "rt_host_kd_order"]
+                "rt_host_fill_background", "rt_host_save_ppm", "rt_host_kd_order", "rt_host_light_basis"]
 
 _amd = None
 _host = None
@@ -298,6 +298,7 @@ def host():
         L.rt_host_fill_background.restype = None
         L.rt_host_save_ppm.argtypes = [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32]
         L.rt_host_kd_order.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+        L.rt_host_light_basis.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         _host = L
     return _host
 
@@ -392,6 +393,19 @@ def kd_order(pos, dir_, weight=None):
     if rc != RT_OK:
         raise RtError(rc, host().rt_host_last_error().decode())
     return pos, dir_, w
+
+
+def light_basis(position, direction):
+    """The basis the host's LightSource constructor derives for lights at position [n][3] aimed at direction [n][3]:
+    [n][9] = vertical, horizontal, normal (the order of rt_light)."""
+    pos = np.ascontiguousarray(position, np.float32).reshape(-1, 3)
+    dir_ = np.ascontiguousarray(direction, np.float32).reshape(-1, 3)
+    out = np.zeros((len(pos), 9), np.float32)
+    for i in range(len(pos)):
+        rc = host().rt_host_light_basis(_ptr(pos[i]), _ptr(dir_[i]), _ptr(out[i]))
+        if rc != RT_OK:
+            raise RtError(rc, host().rt_host_last_error().decode())
+    return out
 
 
 def _scene_update(pos, nrm, camera, lights, materials):
@@ -757,7 +771,8 @@ _UNIT_IO = {UNIT_ASIN: (np.float64, 1, np.float64, 1), UNIT_SINF: (np.float32, 1
             UNIT_TRIANGLE: (np.float32, 15, np.float32, 4), UNIT_BSDF: (np.float32, 17, np.float32, 3),
             UNIT_RAY_AT: (np.float32, 14, np.float32, 6), UNIT_LIGHT_EVAL: (np.float32, 24, np.float32, 3),
             UNIT_SAMPLERS: (np.uint32, 28, np.uint32, 12), UNIT_LIGHT_SAMPLE: (np.uint32, 22, np.uint32, 4),
-            UNIT_POW: (np.float64, 1, np.float64, 2), UNIT_RECIP: (np.float32, 1, np.float32, 4)}
+            UNIT_POW: (np.float64, 1, np.float64, 2), UNIT_RECIP: (np.float32, 1, np.float32, 4),
+            UNIT_BSDF_HOISTED: (np.float32, 17, np.float32, 9)}
 
 
 def unit(which, inp, out_init=None, device=0):

@@ -49,6 +49,10 @@ def lib():
         L.orc_bsdf.restype = None
         L.orc_eval_light.argtypes = [C.POINTER(pyrt.Light), C.c_void_p, C.c_void_p]
         L.orc_eval_light.restype = None
+        L.orc_bsdf_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p]
+        L.orc_bsdf_rows.restype = None
+        L.orc_eval_light_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        L.orc_eval_light_rows.restype = None
         L.orc_engine_next.argtypes = [C.POINTER(C.c_uint32)]
         L.orc_engine_next.restype = C.c_uint32
         L.orc_jitter.argtypes = [C.POINTER(C.c_uint32), C.c_int32, C.c_int32, C.c_void_p]
@@ -136,6 +140,22 @@ def emit_photons(scene, n_requested, rng_mode, seed=1, math_mode=MATH_LIBM, engi
                                 C.byref(n), C.byref(rays))
     assert rc == 0
     return out[:n.value].copy(), st.value, rays.value
+
+
+def bsdf_rows(rows17, math_mode=MATH_LIBM):
+    """evaluateColorResponse over rows [n][17] = kd alpha albedo3 f03 n3 wi3 wo3; returns rgb [n][3]."""
+    rows = np.ascontiguousarray(rows17, np.float32).reshape(-1, 17)
+    out = np.zeros((len(rows), 3), np.float32)
+    lib().orc_bsdf_rows(_p(rows), len(rows), math_mode, _p(out))
+    return out
+
+
+def eval_light_rows(rows24):
+    """evaluateLight over rows [n][24] = rt_light (21 floats), point3; returns rgb [n][3]."""
+    rows = np.ascontiguousarray(rows24, np.float32).reshape(-1, 24)
+    out = np.zeros((len(rows), 3), np.float32)
+    lib().orc_eval_light_rows(_p(rows), len(rows), _p(out))
+    return out
 
 
 def kd_build(photons7):

@@ -309,6 +309,33 @@ def test_frame_bit_exact_vs_oracle(kind, w, h, spp, mode):
     ctx.close()
 
 
+# the same on paths cut short: rt_params.max_depth 1 and 2 (the cases above run the default, 3)
+DEPTH_CASES = [("cubes", 64, 64, 4, pyrt.MODE_PATH, 1), ("cubes", 48, 48, 4, pyrt.MODE_PATH, 2),
+               ("lowres", 40, 40, 4, pyrt.MODE_PATH, 1), ("lowres", 32, 32, 3, pyrt.MODE_PATH, 2)]
+
+
+@pytest.mark.parametrize("kind,w,h,spp,mode,depth", DEPTH_CASES)
+def test_frame_bit_exact_vs_oracle_at_lower_depths(kind, w, h, spp, mode, depth):
+    s = pyrt.Scene(kind, w, h)
+    ctx = pyrt.Context(s)
+    bg = pyrt.background(w, h)
+    frames = {}
+    for d in (depth, depth + 1):
+        p = pyrt.make_params(w, h, spp, mode=mode, seed=17, max_depth=d)
+        ref_out, ref_acc, ref_st = orc.render(s, p, math_mode=orc.MATH_DET, bg=bg)
+        frames[d] = ref_acc
+        if d != depth:
+            continue
+        for kw in ({}, dict(accel=pyrt.ACCEL_BRUTE), dict(no_pool=True), dict(wavefront=True), dict(lanes_per_pixel=1)):
+            out, acc, st = ctx.render(pyrt.make_params(w, h, spp, mode=mode, seed=17, max_depth=d, **kw), bg)
+            assert np.array_equal(bits(acc), bits(ref_acc)), (kind, d, kw)
+            assert np.array_equal(bits(out), bits(ref_out)), (kind, d, kw)
+            assert (st.rays_closest, st.rays_shadow, st.samples) == (ref_st.rays_closest, ref_st.rays_shadow, w * h * spp)
+        assert ref_st.rays_closest <= w * h * spp * d
+    assert not np.array_equal(bits(frames[depth]), bits(frames[depth + 1]))  # (the depth matters to the frame)
+    ctx.close()
+
+
 def test_frame_is_deterministic_and_split_invariant():
     """Same frame rendered (a) twice, (b) as 3 sample ranges, (c) as 2 x 3 tile shards
     summed afterwards: all bit-identical (the per-pixel float sum order never changes)."""
