@@ -18,6 +18,8 @@
  *                                  caller stream (multi-GPU tile sharding, bench)
  *   rt_render_aov / rt_denoise  <- (no counterpart) first-hit AOVs of a frame's primary rays, and the a-trous
  *                                  filter of a low-spp frame guided by them (+ _device forms)
+ *   rt_render_motion / rt_temporal_accumulate <- (no counterpart) where each pixel's surface point was last frame, and
+ *                                  the previous frame's history reprojected there and blended (+ _device forms)
  *   rt_render_adaptive          <- (no counterpart) passes of spp samples over the pixel granules whose estimate has
  *                                  not yet converged (+ _device form)
  *   rt_render_views             <- (no counterpart) the frames of many cameras of one resident scene in one launch
@@ -322,6 +324,90 @@ int rt_denoise(rt_ctx* ctx, const rt_denoise_params* d, const float* rgb, const 
  * context's scratch serves one call at a time. */
 int rt_denoise_device(rt_ctx* ctx, const rt_denoise_params* d, const void* d_rgb, const rt_aov* d_aov, void* d_out,
                       void* stream);
+
+/* ---- motion vectors and temporal accumulation (DESIGN.md "Motion vectors and temporal accumulation") ----------------
+ * Two stateless calls for animated frames.  The library keeps nothing between frames: the caller hands in last frame's
+ * vertex positions and camera (what it gave rt_update then) and last frame's history buffers.
+ *
+ * rt_render_motion casts ONE ray per pixel, whatever spp is: the primary ray of sample spp_begin of the frame p describes
+ * (the sample rt_aov.mesh / .tri describe: same stream seed, jitter_sample, camera_ray, same tree walk, or the exhaustive
+ * loop for RT_ACCEL_BRUTE; RT_NODES_Q8 contexts walk their resident 32-byte records as rt_render_aov does).
+ *   Miss: motion = (0, 0), position = prev_position = 0, mesh = 0xffffffff.
+ *   Hit on global triangle g with the barycentrics (u, v) the frame shades with: position is the frame's hit point
+ *   (Renderer.cpp:43), float32: w = (1 - u) - v; X = (w P0 + u P1) + v P2 over the context's positions — rt_aov.position
+ *   of a one-sample range, in value.  prev_position X' is the SAME float32 expression over prev->vertex_pos at g's three
+ *   vertex ids.
+ *   Screen position of a point Y under a camera c, in float64 from the float32 inputs, in this order, no contraction
+ *   (cross(a, b) = (a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x), dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z):
+ *     q = Y - c.position;  a = c.lower_left - c.position;  H = c.horizontal;  V = c.vertical
+ *     qn = dot(q, cross(H, V));  den = dot(a, cross(H, V))
+ *     s = dot(a, cross(q, V)) / qn;  t = dot(a, cross(H, q)) / qn;  sx = s width;  sy = (1 - t) height
+ *   (camera_ray inverted: Y - position = lambda (a + s H + t V) by Cramer's rule); Y is in front of c iff qn / den > 0.
+ *   motion = ((float)(sx(X', prev camera) - sx(X, the context's camera)), (float)(sy(..) - sy(..))): previous minus
+ *   current screen position, in pixels.  If either point is not in front of its camera, or one of the four coordinates
+ *   is not finite: motion = (+inf, +inf).
+ *   With NULL prev members (or the context's own arrays and camera) every hit pixel has motion == (0, 0) exactly and
+ *   prev_position == position bit for bit.
+ * Validation comes first and a rejected call writes nothing: RT_ERR_INVALID for a null ctx, p, prev or out, non-zero
+ * reserved words, a non-finite prev->camera, and rt_render_aov's size and range checks; RT_ERR_UNSUPPORTED for world > 1.
+ * mode, max_depth and the photon fields do not affect the pass.                                                        */
+typedef struct rt_motion_prev {
+  const float* vertex_pos;   /* [n_vertices][3] LAST frame's positions (host form: host memory; device form: device
+                                memory on the context's device), or NULL = the context's own (geometry did not move) */
+  const rt_camera* camera;   /* HOST memory; last frame's camera, or NULL = the context's own                        */
+  uint32_t reserved[6];      /* zero */
+} rt_motion_prev;
+typedef struct rt_motion {   /* every pointer may be NULL (channel not wanted); the others are overwritten            */
+  float* motion;             /* [h][w][2] previous minus current screen position of the surface point, in pixels     */
+  float* position;           /* [h][w][3] the hit point X in THIS frame (float32)                                    */
+  float* prev_position;      /* [h][w][3] the same surface point X' in LAST frame's positions (float32)              */
+  uint32_t* mesh;            /* [h][w]    mesh of the hit, 0xffffffff = miss (== rt_aov.mesh for the same params)    */
+  uint32_t reserved[4];      /* zero */
+} rt_motion;
+/* The host form uploads prev->vertex_pos into scratch the context owns. */
+int rt_render_motion(rt_ctx* ctx, const rt_params* p, const rt_motion_prev* prev, const rt_motion* host_out);
+/* The same into DEVICE buffers on `stream` (a hipStream_t, may be NULL): prev->vertex_pos is read on `stream`; no
+ * synchronisation. */
+int rt_render_motion_device(rt_ctx* ctx, const rt_params* p, const rt_motion_prev* prev, const rt_motion* device_out,
+                            void* stream);
+
+/* rt_temporal_accumulate reprojects last frame's history along the motion vectors and blends the current frame in.
+ * Per pixel (px, py), float64, in this order, no contraction; c = cur_rgb at the pixel, (mx, my) = cur->motion there:
+ *   1. No history if cur->mesh == 0xffffffff or a motion component is not finite: out = c, out_length = 1.
+ *   2. rx = px + mx; ry = py + my (the pixel centres cancel).  rx < -1, rx >= width, ry < -1 or ry >= height: no
+ *      history.  x0 = floor(rx), ax = rx - x0; likewise y0, ay.
+ *   3. Taps (x0 + i, y0 + j) in the order (0,0), (1,0), (0,1), (1,1), weight wx_i wy_j with wx = (1 - ax, ax).  A tap
+ *      counts iff its weight is > 0, it is inside the image, prev->length > 0 there, prev->mesh there == cur->mesh and
+ *      (dx dx + dy dy) + dz dz <= sigma_position^2 for d = prev->position[tap] - cur->prev_position[pixel].
+ *   4. W = the sum of the counted weights.  W <= 0: no history.  Otherwise h = sum(w rgb_tap) / W per channel,
+ *      L = sum(w length_tap) / W, Ln = min(L + 1, max_history), alpha = max(1 / Ln, alpha_min),
+ *      out = (float)(h + alpha (c - h)), out_length = (float)Ln.
+ * (sigma_position is a float; its square is formed in float64.)  The next frame's history is {out_rgb, cur->position,
+ * cur->mesh, out_length}: the caller ping-pongs two sets.  The first frame of a sequence passes a history whose length
+ * is all 0.  Defaults (0), chosen on two turntable sequences: max_history 16; sigma_position 2 % of the
+ * diagonal of the bounding box of the vertices the context's triangles reference, in float32 (rt_denoise's default and
+ * reduction).  RT_ERR_INVALID: null arguments or required channels, a size outside 1..65535, a negative or non-finite
+ * sigma or alpha, alpha_min > 1, non-zero reserved words, out_rgb or out_length overlapping a history buffer (taps read
+ * neighbouring pixels).  out_rgb may equal cur_rgb.                                                                    */
+typedef struct rt_temporal_params {
+  uint32_t width, height;
+  uint32_t max_history;     /* 0 = default; the history length saturates here                          */
+  float alpha_min;          /* 0 = none: pure 1 / length; otherwise finite, in (0, 1]                  */
+  float sigma_position;     /* 0 = default: rt_denoise's default sigma_position (same reduction)       */
+  uint32_t reserved[6];     /* zero */
+} rt_temporal_params;
+typedef struct rt_history {  /* one frame's history; all four required                                 */
+  float* rgb;        /* [h][w][3] accumulated colour                                                   */
+  float* position;   /* [h][w][3] rt_motion.position of the frame that wrote it                       */
+  uint32_t* mesh;    /* [h][w]    rt_motion.mesh of that frame                                         */
+  float* length;     /* [h][w]    frames accumulated in rgb; 0 = no history                            */
+} rt_history;
+/* cur: motion, prev_position and mesh required.  Host buffers. */
+int rt_temporal_accumulate(rt_ctx* ctx, const rt_temporal_params* t, const float* cur_rgb, const rt_motion* cur,
+                           const rt_history* prev, float* out_rgb, float* out_length);
+/* The same on DEVICE buffers, ordered on `stream` (may be NULL); no synchronisation. */
+int rt_temporal_accumulate_device(rt_ctx* ctx, const rt_temporal_params* t, const void* d_cur_rgb, const rt_motion* d_cur,
+                                  const rt_history* d_prev, void* d_out_rgb, void* d_out_length, void* stream);
 
 /* ---- adaptive sampling (DESIGN.md "Adaptive sampling") -----------------------------------------------------------
  * A frame of passes of P = p->spp samples per pixel.  Pass k renders the frame rt_render renders for p with seed

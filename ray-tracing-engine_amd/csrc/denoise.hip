@@ -17,13 +17,6 @@
 namespace rtk {
 namespace {
 
-// order-preserving float <-> uint32 (atomicMin / atomicMax on the bits)
-__device__ __forceinline__ uint32_t f2o(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float o2f(uint32_t u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u); }
-
 // ext[0..2] = min x, y, z (initialised to 0xffffffff), ext[3..5] = max (initialised to 0)
 __global__ __launch_bounds__(256) void k_dn_extent(const float* __restrict__ vpos, const uint4* __restrict__ triShade,
                                                    uint32_t nTris, uint32_t* __restrict__ ext) {
@@ -123,6 +116,15 @@ __global__ __launch_bounds__(256) void k_dn_iter(uint32_t W, uint32_t H, int ste
 
 }  // namespace
 
+hipError_t launch_ref_extent(const DevScene& S, uint32_t* ext, hipStream_t stream) {
+  hipError_t e;
+  if ((e = hipMemsetAsync(ext, 0xff, 3 * sizeof(uint32_t), stream)) != hipSuccess) return e;
+  if ((e = hipMemsetAsync(ext + 3, 0, 3 * sizeof(uint32_t), stream)) != hipSuccess) return e;
+  const uint32_t blocks = S.n_tris ? (S.n_tris + 255u) / 256u < 1024u ? (S.n_tris + 255u) / 256u : 1024u : 1u;
+  hipLaunchKernelGGL(k_dn_extent, dim3(blocks), dim3(256), 0, stream, S.vpos, S.triShade, S.n_tris, ext);
+  return hipGetLastError();
+}
+
 hipError_t launch_denoise(const DevScene& S, const DenoiseArgs& D, hipStream_t stream) {
   const size_t n = (size_t)D.width * D.height;
   if (n == 0) return hipSuccess;
@@ -131,10 +133,7 @@ hipError_t launch_denoise(const DevScene& S, const DenoiseArgs& D, hipStream_t s
   float* isx = reinterpret_cast<float*>(ext + 8);
   hipError_t e;
   if (D.sigma_position <= 0.f) {
-    if ((e = hipMemsetAsync(ext, 0xff, 3 * sizeof(uint32_t), stream)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(ext + 3, 0, 3 * sizeof(uint32_t), stream)) != hipSuccess) return e;
-    const uint32_t blocks = S.n_tris ? (S.n_tris + 255u) / 256u < 1024u ? (S.n_tris + 255u) / 256u : 1024u : 1u;
-    hipLaunchKernelGGL(k_dn_extent, dim3(blocks), dim3(256), 0, stream, S.vpos, S.triShade, S.n_tris, ext);
+    if ((e = launch_ref_extent(S, ext, stream)) != hipSuccess) return e;
   }
   hipLaunchKernelGGL(k_dn_sigma, dim3(1), dim3(1), 0, stream, ext, D.sigma_position, isx);
   hipLaunchKernelGGL(k_dn_pack, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, (uint32_t)n, D.rgb, D.albedo, D.normal,

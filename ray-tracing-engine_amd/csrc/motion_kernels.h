@@ -1,0 +1,89 @@
+// motion_kernels.h — where was this pixel's surface point last frame: rt_render_motion.
+//
+// One ray per pixel: the primary ray of sample s0 of the frame (the sample rt_aov.mesh / .tri describe: same stream seed,
+// jitter_sample, camera_ray), cast as k_aov casts it.  At the hit, (u, v) as the frame shades with them, the hit point X
+// over the context's positions and the same float32 expression X' over LAST frame's positions; both projected to the
+// screen in float64 (the inverse of camera_ray by Cramer's rule, rt_amd.h states the order) under their own cameras;
+// motion = previous minus current screen position, in pixels.  A wave owns an 8x8-pixel tile, one lane one pixel.
+// Channels whose pointer is null are not written.
+// (included by rt_kernels.hip inside namespace rtk: shares its device functions)
+
+// vertex_setup_ray's sibling for the motion pass: the same (u, v) — tri_test on the same operands — and the same hit
+// point, and the triangle's vertex ids and (u, v) for the caller; no normal.
+RT_DEV void vertex_setup_ray_uv(const DevScene& S, uint32_t id, f3 o, f3 d, uint4& tv, float& u, float& v, f3& point) {
+  tv = S.triShade[id];
+  const f3 p0 = ld(S.vpos + 3 * (size_t)tv.x), p1 = ld(S.vpos + 3 * (size_t)tv.y), p2 = ld(S.vpos + 3 * (size_t)tv.z);
+  float t;
+  tri_test(o, d, p0, p1 - p0, p2 - p0, u, v, t, true);
+  const float w = 1.f - u - v;
+  point = w * p0 + u * p1 + v * p2;
+}
+
+struct d3 {
+  double x, y, z;
+};
+RT_DEV d3 dsub(const float* a, const float* b) { return d3{(double)a[0] - (double)b[0], (double)a[1] - (double)b[1], (double)a[2] - (double)b[2]}; }
+RT_DEV d3 dld(const float* a) { return d3{(double)a[0], (double)a[1], (double)a[2]}; }
+RT_DEV double ddot(d3 a, d3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+RT_DEV d3 dcross(d3 a, d3 b) { return d3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+
+// Screen position (pixels) of the point Y under camera c; false: Y is not in front of the camera.
+RT_DEV bool screen_pos(const rt_camera& c, f3 Y, double width, double height, double& sx, double& sy) {
+  const float y[3] = {Y.x, Y.y, Y.z};
+  const d3 q = dsub(y, c.position), a = dsub(c.lower_left, c.position), H = dld(c.horizontal), V = dld(c.vertical);
+  const d3 hv = dcross(H, V);
+  const double qn = ddot(q, hv), den = ddot(a, hv);
+  const double s = ddot(a, dcross(q, V)) / qn, t = ddot(a, dcross(H, q)) / qn;
+  sx = s * width, sy = (1.0 - t) * height;
+  return qn / den > 0.0;
+}
+
+template <bool BRUTE>
+__global__ __launch_bounds__(64) void k_motion(DevScene S, MotionArgs A) {
+  __shared__ uint32_t lds[(rtbvh::kMaxDepth + 1) * 64];
+  const uint32_t tilesX = (A.width + 7u) / 8u;
+  const uint32_t px = (blockIdx.x % tilesX) * 8u + (threadIdx.x & 7u), py = (blockIdx.x / tilesX) * 8u + (threadIdx.x >> 3);
+  const bool in = px < A.width && py < A.height;
+  const uint32_t pix = py * A.width + px;
+  Rng g{rt_stream_seed(A.seed, RT_STREAM_PIXEL, pix, A.s0)};
+  float jx, jy;
+  jitter_sample(g, (int)A.s0, (int)A.spp, jx, jy);
+  f3 o, d;
+  camera_ray(S.cam, ((float)px + jx) / (float)A.width, 1.f - ((float)py + jy) / (float)A.height, o, d);
+  HitRec h;
+  LaneStats st;
+  const bool hit = cast<BRUTE, false, false, LT_NONE>(S, in, o, d, lds + threadIdx.x, h, st);
+  if (!in) return;
+  f3 X = mk(0.f, 0.f, 0.f), Xp = mk(0.f, 0.f, 0.f);
+  float mx = 0.f, my = 0.f;
+  uint32_t mesh = 0xffffffffu;
+  if (hit) {
+    uint4 tv;
+    float u, v;
+    vertex_setup_ray_uv(S, h.id, o, d, tv, u, v, X);
+    mesh = tv.w;
+    const float w = 1.f - u - v;
+    Xp = w * ld(A.prevVpos + 3 * (size_t)tv.x) + u * ld(A.prevVpos + 3 * (size_t)tv.y) + v * ld(A.prevVpos + 3 * (size_t)tv.z);
+    if (A.motion) {
+      const double W = (double)A.width, H = (double)A.height;
+      double cx, cy, qx, qy;
+      const bool fc = screen_pos(S.cam, X, W, H, cx, cy), fp = screen_pos(A.prevCam, Xp, W, H, qx, qy);
+      const bool ok = fc && fp && isfinite(cx) && isfinite(cy) && isfinite(qx) && isfinite(qy);
+      mx = ok ? (float)(qx - cx) : INFINITY;
+      my = ok ? (float)(qy - cy) : INFINITY;
+    }
+  }
+  const size_t p3 = 3 * (size_t)pix;
+  if (A.motion) A.motion[2 * (size_t)pix] = mx, A.motion[2 * (size_t)pix + 1] = my;
+  if (A.position) A.position[p3] = X.x, A.position[p3 + 1] = X.y, A.position[p3 + 2] = X.z;
+  if (A.prevPosition) A.prevPosition[p3] = Xp.x, A.prevPosition[p3 + 1] = Xp.y, A.prevPosition[p3 + 2] = Xp.z;
+  if (A.mesh) A.mesh[pix] = mesh;
+}
+
+hipError_t launch_motion(bool brute_force, const DevScene& S, const MotionArgs& A, hipStream_t stream) {
+  const uint32_t tiles = ((A.width + 7u) / 8u) * ((A.height + 7u) / 8u);
+  if (tiles == 0) return hipSuccess;
+  if (brute_force) hipLaunchKernelGGL(k_motion<true>, dim3(tiles), dim3(64), 0, stream, S, A);
+  else hipLaunchKernelGGL(k_motion<false>, dim3(tiles), dim3(64), 0, stream, S, A);
+  return hipGetLastError();
+}

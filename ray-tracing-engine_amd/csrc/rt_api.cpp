@@ -188,6 +188,10 @@ struct rt_ctx {
   // scratch of rt_denoise_device (guides, albedo factors, two colour buffers; grows on demand)
   DevBuf<float4> dnScratch;
   size_t dnCap = 0;
+  // scratch of the motion pass and the temporal accumulation (allocated on first use): last frame's positions as the
+  // host form of rt_render_motion uploads them, and rtk::temporal_scratch_words words for the default sigma_position
+  DevBuf<float> mvPrev;
+  DevBuf<uint32_t> tpScratch;
   // scratch of rt_render_adaptive_device (moments, granule state and lists, tile list, counts; grows on demand)
   DevBuf<char> adScratch;
   size_t adCap = 0;
@@ -2145,6 +2149,168 @@ int rt_denoise(rt_ctx* c, const rt_denoise_params* d, const float* rgb, const rt
   int rc = rt_denoise_device(c, d, dRgb.get(), &da, dOut.get(), nullptr);
   if (rc != RT_OK) return rc;
   HIP_TRY(hipMemcpy(out, dOut.get(), 3 * npx * sizeof(float), hipMemcpyDeviceToHost));
+  return RT_OK;
+}
+
+}  // extern "C"
+
+// ---- motion vectors and temporal accumulation -------------------------------------------------------------------------
+namespace {
+
+// the defaults of rt_temporal_params (rt_amd.h, DESIGN.md "Motion vectors and temporal accumulation": chosen on two
+// turntable sequences)
+constexpr uint32_t kTemporalMaxHistory = 16;
+constexpr float kTemporalSigmaScale = 0.02f;  // of the diagonal of the referenced vertices' box
+
+bool any_set(const uint32_t* w, size_t n) {
+  for (size_t i = 0; i < n; ++i)
+    if (w[i]) return true;
+  return false;
+}
+
+// Everything rt_render_motion checks before it touches the device; *q gets rt_render_aov's view of p.
+int motion_checks(const rt_ctx* c, const rt_params* p, const rt_motion_prev* prev, const rt_motion* out, rt_params* q) {
+  if (!c || !p || !prev || !out) return fail(RT_ERR_INVALID, "null argument");
+  if (any_set(prev->reserved, 6) || any_set(out->reserved, 4)) return fail(RT_ERR_INVALID, "reserved words must be zero");
+  if (prev->camera) {
+    const float* f = prev->camera->position;  // (the four vectors are contiguous: 12 floats)
+    for (int i = 0; i < 12; ++i)
+      if (!std::isfinite(f[i])) return fail(RT_ERR_INVALID, "the previous camera is not finite");
+  }
+  return aov_checks(c, p, q);
+}
+
+rtk::MotionArgs motion_args(const rt_ctx* c, const rt_params& q, const rt_motion_prev* prev, const float* dPrevPos, const rt_motion& out) {
+  rtk::MotionArgs A;
+  A.motion = out.motion, A.position = out.position, A.prevPosition = out.prev_position, A.mesh = out.mesh;
+  A.prevVpos = dPrevPos ? dPrevPos : c->S.vpos;
+  A.prevCam = prev->camera ? *prev->camera : c->S.cam;
+  A.width = q.width, A.height = q.height, A.spp = q.spp, A.seed = q.seed;
+  A.s0 = q.spp_count ? q.spp_begin : 0;
+  return A;
+}
+
+bool overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const char *x = static_cast<const char*>(a), *y = static_cast<const char*>(b);
+  return x < y + nb && y < x + na;
+}
+
+// Everything rt_temporal_accumulate checks before it touches the device (and before it looks at the context).
+int temporal_checks(const rt_ctx* c, const rt_temporal_params* t, const float* cur_rgb, const rt_motion* cur, const rt_history* prev,
+                    const float* out_rgb, const float* out_length) {
+  if (!c || !t || !cur_rgb || !cur || !prev || !out_rgb || !out_length) return fail(RT_ERR_INVALID, "null argument");
+  if (!cur->motion || !cur->prev_position || !cur->mesh)
+    return fail(RT_ERR_INVALID, "the current frame needs the motion, prev_position and mesh channels");
+  if (!prev->rgb || !prev->position || !prev->mesh || !prev->length)
+    return fail(RT_ERR_INVALID, "the history needs rgb, position, mesh and length");
+  if (t->width == 0 || t->height == 0 || t->width > 65535u || t->height > 65535u)
+    return fail(RT_ERR_INVALID, "image size %ux%u out of range", t->width, t->height);
+  if (!(t->sigma_position >= 0.f) || !std::isfinite(t->sigma_position))
+    return fail(RT_ERR_INVALID, "sigma_position must be finite and >= 0");
+  if (!(t->alpha_min >= 0.f) || !(t->alpha_min <= 1.f)) return fail(RT_ERR_INVALID, "alpha_min must be 0 or in (0, 1]");
+  if (any_set(t->reserved, 6) || any_set(cur->reserved, 4)) return fail(RT_ERR_INVALID, "reserved words must be zero");
+  const size_t px = (size_t)t->width * t->height * sizeof(float);
+  const void* const hist[4] = {prev->rgb, prev->position, prev->mesh, prev->length};
+  const size_t histBytes[4] = {3 * px, 3 * px, px, px};
+  for (int i = 0; i < 4; ++i)
+    if (overlap(out_rgb, 3 * px, hist[i], histBytes[i]) || overlap(out_length, px, hist[i], histBytes[i]))
+      return fail(RT_ERR_INVALID, "the outputs must not alias the history (taps read neighbouring pixels)");
+  return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_render_motion_device(rt_ctx* c, const rt_params* p, const rt_motion_prev* prev, const rt_motion* out, void* stream) {
+  rt_params q;
+  int rc = motion_checks(c, p, prev, out, &q);
+  if (rc != RT_OK) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  const rtk::MotionArgs A = motion_args(c, q, prev, prev->vertex_pos, *out);
+  const hipError_t he = rtk::launch_motion(q.accel == RT_ACCEL_BRUTE, c->S, A, static_cast<hipStream_t>(stream));
+  if (he != hipSuccess) return fail(RT_ERR_HIP, "motion launch failed: %s", hipGetErrorString(he));
+  return RT_OK;
+}
+
+int rt_render_motion(rt_ctx* c, const rt_params* p, const rt_motion_prev* prev, const rt_motion* out) {
+  rt_params q;
+  int rc = motion_checks(c, p, prev, out, &q);
+  if (rc != RT_OK) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t npx = (size_t)q.width * q.height, nv = 3 * (size_t)c->nVertices;
+  if (prev->vertex_pos) {
+    if (!c->mvPrev) HIP_TRY(dev_alloc(&c->mvPrev, nv));
+    HIP_TRY(hipMemcpy(c->mvPrev.get(), prev->vertex_pos, nv * sizeof(float), hipMemcpyHostToDevice));
+  }
+  DevBuf<float> dF[3];
+  DevBuf<uint32_t> dMesh;
+  float* const hF[3] = {out->motion, out->position, out->prev_position};
+  const size_t wF[3] = {2, 3, 3};
+  for (int i = 0; i < 3; ++i)
+    if (hF[i]) HIP_TRY(dev_alloc(&dF[i], npx * wF[i]));
+  if (out->mesh) HIP_TRY(dev_alloc(&dMesh, npx));
+  rt_motion d = {};
+  d.motion = dF[0].get(), d.position = dF[1].get(), d.prev_position = dF[2].get(), d.mesh = dMesh.get();
+  const rtk::MotionArgs A = motion_args(c, q, prev, prev->vertex_pos ? c->mvPrev.get() : nullptr, d);
+  const hipError_t he = rtk::launch_motion(q.accel == RT_ACCEL_BRUTE, c->S, A, nullptr);
+  if (he != hipSuccess) return fail(RT_ERR_HIP, "motion launch failed: %s", hipGetErrorString(he));
+  for (int i = 0; i < 3; ++i)
+    if (hF[i]) HIP_TRY(hipMemcpy(hF[i], dF[i].get(), npx * wF[i] * sizeof(float), hipMemcpyDeviceToHost));
+  if (out->mesh) HIP_TRY(hipMemcpy(out->mesh, dMesh.get(), npx * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return RT_OK;
+}
+
+int rt_temporal_accumulate_device(rt_ctx* c, const rt_temporal_params* t, const void* d_cur_rgb, const rt_motion* cur,
+                                  const rt_history* prev, void* d_out_rgb, void* d_out_length, void* stream) {
+  int rc = temporal_checks(c, t, static_cast<const float*>(d_cur_rgb), cur, prev, static_cast<const float*>(d_out_rgb),
+                           static_cast<const float*>(d_out_length));
+  if (rc != RT_OK) return rc;
+  if (c->broken) return fail(RT_ERR_STATE, "the context's device tree is in an unknown state: destroy it");
+  HIP_TRY(hipSetDevice(c->device));
+  if (!c->tpScratch) HIP_TRY(dev_alloc(&c->tpScratch, rtk::temporal_scratch_words));
+  rtk::TemporalArgs T;
+  T.width = t->width, T.height = t->height;
+  T.maxHistory = t->max_history ? t->max_history : kTemporalMaxHistory;
+  T.alphaMin = t->alpha_min, T.sigmaPosition = t->sigma_position, T.sigmaScale = kTemporalSigmaScale;
+  T.curRgb = static_cast<const float*>(d_cur_rgb), T.motion = cur->motion, T.prevPosition = cur->prev_position, T.mesh = cur->mesh;
+  T.hRgb = prev->rgb, T.hPosition = prev->position, T.hLength = prev->length, T.hMesh = prev->mesh;
+  T.outRgb = static_cast<float*>(d_out_rgb), T.outLength = static_cast<float*>(d_out_length), T.scratch = c->tpScratch.get();
+  const hipError_t he = rtk::launch_temporal(c->S, T, static_cast<hipStream_t>(stream));
+  if (he != hipSuccess) return fail(RT_ERR_HIP, "temporal launch failed: %s", hipGetErrorString(he));
+  return RT_OK;
+}
+
+int rt_temporal_accumulate(rt_ctx* c, const rt_temporal_params* t, const float* cur_rgb, const rt_motion* cur,
+                           const rt_history* prev, float* out_rgb, float* out_length) {
+  int rc = temporal_checks(c, t, cur_rgb, cur, prev, out_rgb, out_length);
+  if (rc != RT_OK) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t npx = (size_t)t->width * t->height;
+  // inputs: cur_rgb, motion, prev_position, history rgb, history position, history length; mesh, history mesh
+  const float* const hF[6] = {cur_rgb, cur->motion, cur->prev_position, prev->rgb, prev->position, prev->length};
+  const size_t wF[6] = {3, 2, 3, 3, 3, 1};
+  const uint32_t* const hU[2] = {cur->mesh, prev->mesh};
+  DevBuf<float> dF[6], dOut, dLen;
+  DevBuf<uint32_t> dU[2];
+  for (int i = 0; i < 6; ++i) {
+    HIP_TRY(dev_alloc(&dF[i], npx * wF[i]));
+    HIP_TRY(hipMemcpy(dF[i].get(), hF[i], npx * wF[i] * sizeof(float), hipMemcpyHostToDevice));
+  }
+  for (int i = 0; i < 2; ++i) {
+    HIP_TRY(dev_alloc(&dU[i], npx));
+    HIP_TRY(hipMemcpy(dU[i].get(), hU[i], npx * sizeof(uint32_t), hipMemcpyHostToDevice));
+  }
+  HIP_TRY(dev_alloc(&dOut, 3 * npx));
+  HIP_TRY(dev_alloc(&dLen, npx));
+  rt_motion dc = {};
+  dc.motion = dF[1].get(), dc.prev_position = dF[2].get(), dc.mesh = dU[0].get();
+  rt_history dh = {};
+  dh.rgb = dF[3].get(), dh.position = dF[4].get(), dh.length = dF[5].get(), dh.mesh = dU[1].get();
+  rc = rt_temporal_accumulate_device(c, t, dF[0].get(), &dc, &dh, dOut.get(), dLen.get(), nullptr);
+  if (rc != RT_OK) return rc;
+  HIP_TRY(hipMemcpy(out_rgb, dOut.get(), 3 * npx * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_length, dLen.get(), npx * sizeof(float), hipMemcpyDeviceToHost));
   return RT_OK;
 }
 

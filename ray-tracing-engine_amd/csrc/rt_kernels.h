@@ -122,6 +122,42 @@ struct AovArgs {
   uint32_t width, height, spp, seed, s0, s1;
 };
 hipError_t launch_aov(bool brute_force, const DevScene& S, const AovArgs& A, hipStream_t stream);
+// the motion pass (motion_kernels.h, rt_render_motion): per pixel, for the primary ray of sample s0, the hit point over the
+// context's positions and over prevVpos (never null: the context's own when the geometry did not move), and the screen
+// motion between prevCam and S.cam; null channels are not written
+struct MotionArgs {
+  float *motion, *position, *prevPosition;  // [h][w][2], [h][w][3], [h][w][3]
+  uint32_t* mesh;                           // [h][w]
+  const float* prevVpos;                    // [n_vertices][3]
+  rt_camera prevCam;
+  uint32_t width, height, spp, seed, s0;
+};
+hipError_t launch_motion(bool brute_force, const DevScene& S, const MotionArgs& A, hipStream_t stream);
+// temporal accumulation (temporal.hip, rt_temporal_accumulate): the history reprojected along the motion vectors and
+// blended with the current frame; all buffers device memory.  sigmaPosition 0: derived on the device from the extent of
+// the vertices the triangles reference (the denoiser's reduction) into scratch (temporal_scratch_words uint32 words)
+struct TemporalArgs {
+  uint32_t width, height, maxHistory;
+  float alphaMin, sigmaPosition;  // sigmaPosition 0: sigmaScale times the diagonal of that extent
+  float sigmaScale;
+  const float *curRgb, *motion, *prevPosition;  // the current frame: [h][w][3], rt_motion.motion, rt_motion.prev_position
+  const uint32_t* mesh;                         // rt_motion.mesh
+  const float *hRgb, *hPosition, *hLength;      // the history
+  const uint32_t* hMesh;
+  float *outRgb, *outLength;
+  uint32_t* scratch;
+};
+constexpr size_t temporal_scratch_words = 10;  // 6 extent words, pad, then sigma_position^2 as a double (8-byte aligned)
+hipError_t launch_temporal(const DevScene& S, const TemporalArgs& T, hipStream_t stream);
+// the box of the vertices the triangles reference, as order-preserving words (denoise.hip k_dn_extent): ext[0..2] =
+// min x, y, z, ext[3..5] = max
+hipError_t launch_ref_extent(const DevScene& S, uint32_t* ext, hipStream_t stream);
+// order-preserving float <-> uint32 (atomicMin / atomicMax on the bits)
+__device__ __forceinline__ uint32_t f2o(float f) {
+  const uint32_t u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float o2f(uint32_t u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u); }
 // the edge-avoiding a-trous filter (denoise.hip, rt_denoise): inputs and output [h][w][3] / [h][w], device memory;
 // scratch = 5 * w * h + 4 float4 (rtk::denoise_scratch)
 struct DenoiseArgs {

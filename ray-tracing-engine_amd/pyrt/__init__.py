@@ -112,6 +112,43 @@ class DenoiseParams(C.Structure):
                 ("sigma_normal", C.c_float), ("sigma_position", C.c_float), ("reserved", C.c_uint32 * 6)]
 
 
+class MotionPrev(C.Structure):
+    """rt_motion_prev: last frame's vertex positions (host or device pointer) and camera (host), None = the context's own."""
+    _fields_ = [("vertex_pos", C.c_void_p), ("camera", C.POINTER(Camera)), ("reserved", C.c_uint32 * 6)]
+
+
+class Motion(C.Structure):
+    """rt_motion: channel pointers (host or device), None = channel not wanted."""
+    _fields_ = [("motion", C.c_void_p), ("position", C.c_void_p), ("prev_position", C.c_void_p), ("mesh", C.c_void_p),
+                ("reserved", C.c_uint32 * 4)]
+
+
+class TemporalParams(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("max_history", C.c_uint32), ("alpha_min", C.c_float),
+                ("sigma_position", C.c_float), ("reserved", C.c_uint32 * 6)]
+
+
+class History(C.Structure):
+    """rt_history: one frame's history (host or device pointers), all four required."""
+    _fields_ = [("rgb", C.c_void_p), ("position", C.c_void_p), ("mesh", C.c_void_p), ("length", C.c_void_p)]
+
+
+MOTION_CHANNELS = ("motion", "position", "prev_position", "mesh")
+HISTORY_CHANNELS = ("rgb", "position", "mesh", "length")
+
+
+def make_temporal(width, height, max_history=0, alpha_min=0., sigma_position=0.):
+    t = TemporalParams()
+    t.width, t.height, t.max_history, t.alpha_min, t.sigma_position = width, height, max_history, alpha_min, sigma_position
+    return t
+
+
+def empty_history(width, height):
+    """The history the first frame of a sequence passes: length 0 everywhere."""
+    return dict(rgb=np.zeros((height, width, 3), np.float32), position=np.zeros((height, width, 3), np.float32),
+                mesh=np.full((height, width), 0xffffffff, np.uint32), length=np.zeros((height, width), np.float32))
+
+
 class AdaptiveParams(C.Structure):
     _fields_ = [("max_passes", C.c_uint32), ("min_passes", C.c_uint32), ("threshold", C.c_float), ("floor", C.c_float),
                 ("reserved", C.c_uint32 * 6)]
@@ -185,7 +222,8 @@ AMD_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_create", "rt_destroy", "rt
                "rt_group_size", "rt_group_uses_rccl", "rt_group_ctx", "rt_group_set_photons", "rt_group_render",
                "rt_update", "rt_update_vertices_device", "rt_group_update", "rt_render_aov", "rt_render_aov_device",
                "rt_denoise", "rt_denoise_device", "rt_render_adaptive", "rt_render_adaptive_device", "rt_render_views",
-               "rt_render_views_device"]
+               "rt_render_views_device", "rt_render_motion", "rt_render_motion_device", "rt_temporal_accumulate",
+               "rt_temporal_accumulate_device"]
 HOST_SYMBOLS = ["rt_host_scene_build", "rt_host_scene_desc", "rt_host_scene_free", "rt_host_last_error",
                 "rt_host_fill_background", "rt_host_save_ppm", "rt_host_kd_order", "rt_host_light_basis"]
 
@@ -275,6 +313,13 @@ def amd():
                                              C.POINTER(Stats)]
         L.rt_denoise_device.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.POINTER(Aov), C.c_void_p,
                                         C.c_void_p]
+        L.rt_render_motion.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(MotionPrev), C.POINTER(Motion)]
+        L.rt_render_motion_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(MotionPrev), C.POINTER(Motion),
+                                              C.c_void_p]
+        L.rt_temporal_accumulate.argtypes = [C.c_void_p, C.POINTER(TemporalParams), C.c_void_p, C.POINTER(Motion),
+                                             C.POINTER(History), C.c_void_p, C.c_void_p]
+        L.rt_temporal_accumulate_device.argtypes = [C.c_void_p, C.POINTER(TemporalParams), C.c_void_p, C.POINTER(Motion),
+                                                    C.POINTER(History), C.c_void_p, C.c_void_p, C.c_void_p]
         _amd = L
     return _amd
 
@@ -619,6 +664,77 @@ class Context:
         for k, v in ptrs.items():
             setattr(a, k, v or None)
         _check(amd().rt_render_aov_device(self._h, C.byref(params), C.byref(a), C.c_void_p(stream or None)))
+
+    @staticmethod
+    def _motion_prev(prev_pos, prev_camera):
+        """An rt_motion_prev: prev_pos a numpy array [n_vertices][3] (host form), a device pointer (int) or None;
+        prev_camera [4][3] floats or None.  Returns it and the arrays it points into."""
+        m, keep = MotionPrev(), []
+        if prev_pos is not None:
+            if isinstance(prev_pos, int):
+                m.vertex_pos = prev_pos
+            else:
+                keep.append(np.ascontiguousarray(prev_pos, np.float32).reshape(-1, 3))
+                m.vertex_pos = keep[-1].ctypes.data
+        if prev_camera is not None:
+            keep.append(np.ascontiguousarray(prev_camera, np.float32).reshape(4, 3))
+            m.camera = C.cast(keep[-1].ctypes.data, C.POINTER(Camera))
+        return m, keep
+
+    def render_motion(self, params, prev_pos=None, prev_camera=None, channels=MOTION_CHANNELS):
+        """rt_render_motion: per pixel, where the surface point the frame's first primary ray hits was last frame —
+        dict of motion [h][w][2], position, prev_position [h][w][3] (float32) and mesh [h][w] (uint32).  prev_pos
+        [n_vertices][3] / prev_camera [4][3]: last frame's (None = the context's own)."""
+        w, h = params.width, params.height
+        shape = dict(motion=(h, w, 2), position=(h, w, 3), prev_position=(h, w, 3), mesh=(h, w))
+        out, m = {}, Motion()
+        for k in channels:
+            out[k] = np.zeros(shape[k], np.uint32 if k == "mesh" else np.float32)
+            setattr(m, k, out[k].ctypes.data)
+        prev, _keep = self._motion_prev(prev_pos, prev_camera)
+        _check(amd().rt_render_motion(self._h, C.byref(params), C.byref(prev), C.byref(m)))
+        return out
+
+    def render_motion_device(self, params, ptrs, d_prev_pos=None, prev_camera=None, stream=0):
+        """rt_render_motion_device: into device buffers; ptrs = {channel: device pointer} (missing = not wanted),
+        d_prev_pos a device pointer or None."""
+        m = Motion()
+        for k, v in ptrs.items():
+            setattr(m, k, v or None)
+        prev, _keep = self._motion_prev(int(d_prev_pos) if d_prev_pos else None, prev_camera)
+        _check(amd().rt_render_motion_device(self._h, C.byref(params), C.byref(prev), C.byref(m), C.c_void_p(stream or None)))
+
+    def temporal_accumulate(self, cur_rgb, cur, prev, max_history=0, alpha_min=0., sigma_position=0.):
+        """rt_temporal_accumulate: cur_rgb [h][w][3] the current frame, cur = render_motion's dict for it, prev = the
+        history dict (rgb, position, mesh, length; pyrt.empty_history for the first frame).  Returns (out_rgb,
+        out_length); the next frame's history is dict(rgb=out_rgb, position=cur["position"], mesh=cur["mesh"],
+        length=out_length)."""
+        rgb = np.ascontiguousarray(cur_rgb, np.float32)
+        h, w = rgb.shape[:2]
+        ck = {k: np.ascontiguousarray(cur[k], np.uint32 if k == "mesh" else np.float32) for k in ("motion", "prev_position", "mesh")}
+        hk = {k: np.ascontiguousarray(prev[k], np.uint32 if k == "mesh" else np.float32) for k in HISTORY_CHANNELS}
+        m, hs = Motion(), History()
+        for k, v in ck.items():
+            setattr(m, k, v.ctypes.data)
+        for k, v in hk.items():
+            setattr(hs, k, v.ctypes.data)
+        out, length = np.empty((h, w, 3), np.float32), np.empty((h, w), np.float32)
+        t = make_temporal(w, h, max_history, alpha_min, sigma_position)
+        _check(amd().rt_temporal_accumulate(self._h, C.byref(t), _ptr(rgb), C.byref(m), C.byref(hs), _ptr(out), _ptr(length)))
+        return out, length
+
+    def temporal_accumulate_device(self, width, height, d_cur_rgb, cur_ptrs, prev_ptrs, d_out_rgb, d_out_length, stream=0,
+                                   max_history=0, alpha_min=0., sigma_position=0.):
+        """rt_temporal_accumulate_device: device pointers (cur_ptrs = {"motion", "prev_position", "mesh"}, prev_ptrs =
+        {"rgb", "position", "mesh", "length"}), on `stream`."""
+        m, hs = Motion(), History()
+        for k, v in cur_ptrs.items():
+            setattr(m, k, v or None)
+        for k, v in prev_ptrs.items():
+            setattr(hs, k, v or None)
+        t = make_temporal(width, height, max_history, alpha_min, sigma_position)
+        _check(amd().rt_temporal_accumulate_device(self._h, C.byref(t), C.c_void_p(d_cur_rgb), C.byref(m), C.byref(hs),
+                                                   C.c_void_p(d_out_rgb), C.c_void_p(d_out_length), C.c_void_p(stream or None)))
 
     def render_adaptive(self, params, bg, threshold, max_passes, min_passes=0, floor=0.):
         """rt_render_adaptive: passes of params.spp samples over the granules not yet converged (DESIGN.md "Adaptive
