@@ -409,6 +409,79 @@ int rt_temporal_accumulate(rt_ctx* ctx, const rt_temporal_params* t, const float
 int rt_temporal_accumulate_device(rt_ctx* ctx, const rt_temporal_params* t, const void* d_cur_rgb, const rt_motion* d_cur,
                                   const rt_history* d_prev, void* d_out_rgb, void* d_out_length, void* stream);
 
+/* ---- variance-guided spatiotemporal filtering (DESIGN.md "Variance-guided spatiotemporal filtering") ----------------
+ * rt_svgf (Schied et al., HPG 2017) accumulates the demodulated frame and its luminance moments in time, turns the moments
+ * into a per-pixel variance and lets that variance steer an a-trous filter.  Stateless like the calls above: the caller
+ * ping-pongs two rt_svgf_history sets.  Guides n = normal/hits, x = position/hits (float32); a pixel is VALID iff hits > 0.
+ *
+ * Stage A, per pixel, every pixel alike; float64 from the float32 inputs, in this order, no contraction:
+ *   f = max(albedo/hits, 1e-3) per channel and d = cur_rgb / f, both in float32 (rt_denoise's); hits == 0: f = 1, d = cur_rgb.
+ *   l = (0.2126 d.r + 0.7152 d.g) + 0.0722 d.b.
+ *   Steps 1-4 of rt_temporal_accumulate with sigma_reproject for its sigma_position and prev->color for its rgb: the same
+ *   tap order, acceptance test and W.  No history: accum = d, moments = (l, l l), length = 1.  Otherwise, h, hm1, hm2, L the
+ *   weighted means sum(w tap) / W of prev->color, prev->moments and prev->length:
+ *     Ln = min(L + 1, max_history);  alpha = max(1 / Ln, alpha_min);  alpha_m = max(1 / Ln, alpha_min_moments)
+ *     accum = h + alpha (d - h);  m1 = hm1 + alpha_m (l - hm1);  m2 = hm2 + alpha_m (l l - hm2);  length = Ln
+ *   out->accum, out->moments = (m1, m2) and out->length are these values rounded to float32, never filtered in space.
+ * Stage B, float32 from here on, from the float32 m1, m2, Ln of stage A; sums run in tap order, rows first (dy outer):
+ *   not VALID: var = 0.  Ln >= 4: var = max(0, m2 - m1 m1).  Otherwise over the taps q = p + (dx, dy), dx, dy in -3..3,
+ *   inside the image and VALID: w = expf(-(|n_p-n_q|^2 / sn^2 + |x_p-x_q|^2 / sx^2)), M1 = sum(w m1_q) / sum(w), M2 likewise,
+ *   var = max(0, M2 - M1 M1) * (4 / Ln).   (|a|^2 = (a.x a.x + a.y a.y) + a.z a.z; 1 / sn^2 = 1 / (sn sn), 1 / sx^2 likewise,
+ *   formed once and multiplied.)
+ * Stage C: iteration i (from 0) has step s = 2^i and works on (c, var), at first (accum, var).  A pixel that is not VALID
+ *   keeps (c, var).  Otherwise g = sum(k var_q) / sum(k) over q = p + (dx, dy), dx, dy in -1..1 (whatever s is), inside the
+ *   image and VALID, k = {1/4, 1/2, 1/4}[dx] {1/4, 1/2, 1/4}[dy]; lum(c) = (0.2126 c.r + 0.7152 c.g) + 0.0722 c.b; over the
+ *   taps q = p + s (dx, dy), dx, dy in -2..2, inside the image and VALID, h = {1/16, 1/4, 3/8, 1/4, 1/16}:
+ *     w = (h[dx] h[dy]) expf(-((|n_p-n_q|^2 / sn^2 + |x_p-x_q|^2 / sx^2) + |lum(c_p) - lum(c_q)| / (sl sqrtf(g) + 1e-4)))
+ *     c' = sum(w c_q) / sum(w);  var' = sum((w w) var_q) / (sum(w) sum(w))
+ *   out->color is iteration 0's c' (the history the next frame accumulates onto: the paper's feedback), out->rgb the last
+ *   c' times f, out->variance the last var'.
+ * The next frame's history is {out->color, out->moments, cur->position, cur->mesh, out->length}; the first frame of a
+ * sequence passes a history whose length is all 0.  Defaults (0), chosen on two turntable sequences:
+ * iterations 5, max_history 2, sigma_luminance 2, sigma_normal 0.5, sigma_position and sigma_reproject 2 % of the diagonal
+ * of the bounding box of the vertices the context's triangles reference (rt_denoise's and rt_temporal_accumulate's).
+ * Validation comes first and a rejected call writes nothing: RT_ERR_INVALID for null arguments, required channels or
+ * required outputs, a size outside 1..65535, iterations above 8, a negative or non-finite sigma or alpha, an alpha above 1,
+ * non-zero reserved words, an output overlapping a history buffer or another output.  out->rgb may equal cur_rgb.  A call
+ * that passes them answers RT_ERR_NO_DEVICE where there is no HIP device.                                              */
+typedef struct rt_svgf_params {
+  uint32_t width, height;
+  uint32_t iterations;        /* 0 = 5; at most 8                                                            */
+  uint32_t max_history;       /* 0 = default; the history length saturates here                              */
+  float alpha_min;            /* colour: 0 = none: pure 1 / length; otherwise finite, in (0, 1]              */
+  float alpha_min_moments;    /* the same for the two moments                                                */
+  float sigma_luminance;      /* 0 = default; in standard deviations of the pixel's luminance                */
+  float sigma_normal;         /* 0 = default                                                                 */
+  float sigma_position;       /* the spatial guide; 0 = rt_denoise's default                                 */
+  float sigma_reproject;      /* the tap acceptance; 0 = rt_temporal_accumulate's default                    */
+  uint32_t reserved[6];       /* zero */
+} rt_svgf_params;
+typedef struct rt_svgf_history {  /* one frame's history; all five required                                  */
+  float* color;      /* [h][w][3] DEMODULATED colour (rt_svgf_out.color)                                    */
+  float* moments;    /* [h][w][2] first and second luminance moment                                         */
+  float* position;   /* [h][w][3] rt_motion.position of the frame that wrote it                            */
+  uint32_t* mesh;    /* [h][w]    rt_motion.mesh of that frame                                              */
+  float* length;     /* [h][w]    frames accumulated; 0 = no history                                        */
+} rt_svgf_history;
+typedef struct rt_svgf_out {
+  float* rgb;        /* [h][w][3] the filtered frame, required                                              */
+  float* color;      /* [h][w][3] required: the next history's colour                                       */
+  float* moments;    /* [h][w][2] required: the next history's moments                                      */
+  float* length;     /* [h][w]    required: the next history's length                                       */
+  float* accum;      /* [h][w][3] optional: stage A's colour, before any spatial filter                     */
+  float* variance;   /* [h][w]    optional: the variance after the last iteration                           */
+  uint32_t reserved[4];  /* zero */
+} rt_svgf_out;
+/* cur_rgb: a resolved frame [h][w][3]; aov_sums: the SUMS of rt_render_aov for the same params (albedo, normal, position,
+ * hits required); cur: rt_render_motion's channels for it (motion, prev_position, mesh required; position is what the
+ * caller keeps for the next history).  Host buffers. */
+int rt_svgf(rt_ctx* ctx, const rt_svgf_params* s, const float* cur_rgb, const rt_aov* aov_sums, const rt_motion* cur,
+            const rt_svgf_history* prev, const rt_svgf_out* out);
+/* The same on DEVICE buffers, ordered on `stream` (may be NULL); no synchronisation.  The context's scratch serves one
+ * call at a time. */
+int rt_svgf_device(rt_ctx* ctx, const rt_svgf_params* s, const void* d_cur_rgb, const rt_aov* d_aov_sums,
+                   const rt_motion* d_cur, const rt_svgf_history* d_prev, const rt_svgf_out* d_out, void* stream);
+
 /* ---- adaptive sampling (DESIGN.md "Adaptive sampling") -----------------------------------------------------------
  * A frame of passes of P = p->spp samples per pixel.  Pass k renders the frame rt_render renders for p with seed
  * p->seed + k (uint32 wrap-around), over the 8x8-pixel granules still active only; each pass is a full stratified set

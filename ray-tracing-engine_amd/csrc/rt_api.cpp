@@ -25,6 +25,7 @@
 #include "bvh_build.h"
 #include "rt_amd.h"
 #include "rt_kernels.h"
+#include "svgf.h"
 
 namespace {
 
@@ -2311,6 +2312,138 @@ int rt_temporal_accumulate(rt_ctx* c, const rt_temporal_params* t, const float* 
   if (rc != RT_OK) return rc;
   HIP_TRY(hipMemcpy(out_rgb, dOut.get(), 3 * npx * sizeof(float), hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(out_length, dLen.get(), npx * sizeof(float), hipMemcpyDeviceToHost));
+  return RT_OK;
+}
+
+}  // extern "C"
+
+// ---- variance-guided spatiotemporal filtering --------------------------------------------------------------------------
+namespace {
+
+// the defaults of rt_svgf_params (rt_amd.h, DESIGN.md "Variance-guided spatiotemporal filtering": chosen on two turntable
+// sequences); the two position sigmas default to the denoiser's and the accumulation's fraction of the box diagonal
+constexpr uint32_t kSvgfIterations = 5, kSvgfMaxHistory = 2;
+constexpr float kSvgfSigmaLuminance = 2.f, kSvgfSigmaNormal = 0.5f, kSvgfSigmaScale = 0.02f;
+
+// Everything rt_svgf checks before it touches the device (and before it looks at the context).
+int svgf_checks(const rt_ctx* c, const rt_svgf_params* s, const float* cur_rgb, const rt_aov* aov, const rt_motion* cur,
+                const rt_svgf_history* prev, const rt_svgf_out* out) {
+  if (!c || !s || !cur_rgb || !aov || !cur || !prev || !out) return fail(RT_ERR_INVALID, "null argument");
+  if (!aov->albedo || !aov->normal || !aov->position || !aov->hits)
+    return fail(RT_ERR_INVALID, "the filter needs the albedo, normal, position and hits channels");
+  if (!cur->motion || !cur->prev_position || !cur->mesh)
+    return fail(RT_ERR_INVALID, "the current frame needs the motion, prev_position and mesh channels");
+  if (!prev->color || !prev->moments || !prev->position || !prev->mesh || !prev->length)
+    return fail(RT_ERR_INVALID, "the history needs color, moments, position, mesh and length");
+  if (!out->rgb || !out->color || !out->moments || !out->length)
+    return fail(RT_ERR_INVALID, "the outputs rgb, color, moments and length are required");
+  if (s->width == 0 || s->height == 0 || s->width > 65535u || s->height > 65535u)
+    return fail(RT_ERR_INVALID, "image size %ux%u out of range", s->width, s->height);
+  if (s->iterations > 8) return fail(RT_ERR_INVALID, "iterations %u > 8", s->iterations);
+  const float sg[4] = {s->sigma_luminance, s->sigma_normal, s->sigma_position, s->sigma_reproject};
+  for (float v : sg)
+    if (!(v >= 0.f) || !std::isfinite(v)) return fail(RT_ERR_INVALID, "sigmas must be finite and >= 0");
+  const float al[2] = {s->alpha_min, s->alpha_min_moments};
+  for (float v : al)
+    if (!(v >= 0.f) || !(v <= 1.f)) return fail(RT_ERR_INVALID, "alpha_min and alpha_min_moments must be 0 or in (0, 1]");
+  if (any_set(s->reserved, 6) || any_set(aov->reserved, 4) || any_set(cur->reserved, 4) || any_set(out->reserved, 4))
+    return fail(RT_ERR_INVALID, "reserved words must be zero");
+  const size_t px = (size_t)s->width * s->height * sizeof(float);
+  const void* const hist[5] = {prev->color, prev->moments, prev->position, prev->mesh, prev->length};
+  const size_t histBytes[5] = {3 * px, 2 * px, 3 * px, px, px};
+  const void* const outs[6] = {out->rgb, out->color, out->moments, out->length, out->accum, out->variance};
+  const size_t outBytes[6] = {3 * px, 3 * px, 2 * px, px, 3 * px, px};
+  for (int i = 0; i < 6; ++i) {
+    if (!outs[i]) continue;
+    for (int j = 0; j < 5; ++j)
+      if (overlap(outs[i], outBytes[i], hist[j], histBytes[j]))
+        return fail(RT_ERR_INVALID, "the outputs must not alias the history (taps read neighbouring pixels)");
+    for (int j = i + 1; j < 6; ++j)
+      if (outs[j] && overlap(outs[i], outBytes[i], outs[j], outBytes[j])) return fail(RT_ERR_INVALID, "the outputs must not alias one another");
+  }
+  // (the context exists only where a device does; a handle is not looked at before this)
+  int n = 0;
+  const hipError_t e = hipGetDeviceCount(&n);
+  if (e != hipSuccess || n <= 0)
+    return fail(RT_ERR_NO_DEVICE, "no HIP device available (%s); this library has no CPU path",
+                e == hipSuccess ? "device count is 0" : hipGetErrorString(e));
+  return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_svgf_device(rt_ctx* c, const rt_svgf_params* s, const void* d_cur_rgb, const rt_aov* aov, const rt_motion* cur,
+                   const rt_svgf_history* prev, const rt_svgf_out* out, void* stream) {
+  int rc = svgf_checks(c, s, static_cast<const float*>(d_cur_rgb), aov, cur, prev, out);
+  if (rc != RT_OK) return rc;
+  if (c->broken) return fail(RT_ERR_STATE, "the context's device tree is in an unknown state: destroy it");
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t need = rtk::svgf_scratch(s->width, s->height);  // (the denoiser's scratch: one call at a time)
+  if (need > c->dnCap) {
+    c->dnCap = 0;
+    if (c->dnScratch) HIP_TRY(hipFree(c->dnScratch.release()));
+    HIP_TRY(dev_alloc(&c->dnScratch, need));
+    c->dnCap = need;
+  }
+  rtk::SvgfArgs A;
+  A.width = s->width, A.height = s->height;
+  A.iterations = s->iterations ? s->iterations : kSvgfIterations;
+  A.maxHistory = s->max_history ? s->max_history : kSvgfMaxHistory;
+  A.alphaMin = s->alpha_min, A.alphaMinMoments = s->alpha_min_moments;
+  A.sigmaLuminance = s->sigma_luminance > 0.f ? s->sigma_luminance : kSvgfSigmaLuminance;
+  A.sigmaNormal = s->sigma_normal > 0.f ? s->sigma_normal : kSvgfSigmaNormal;
+  A.sigmaPosition = s->sigma_position, A.sigmaReproject = s->sigma_reproject, A.sigmaScale = kSvgfSigmaScale;
+  A.curRgb = static_cast<const float*>(d_cur_rgb), A.albedo = aov->albedo, A.normal = aov->normal, A.position = aov->position;
+  A.hits = aov->hits, A.motion = cur->motion, A.prevPosition = cur->prev_position, A.mesh = cur->mesh;
+  A.hColor = prev->color, A.hMoments = prev->moments, A.hPosition = prev->position, A.hLength = prev->length, A.hMesh = prev->mesh;
+  A.outRgb = out->rgb, A.outColor = out->color, A.outMoments = out->moments, A.outLength = out->length;
+  A.outAccum = out->accum, A.outVariance = out->variance, A.scratch = c->dnScratch.get();
+  const hipError_t he = rtk::launch_svgf(c->S, A, static_cast<hipStream_t>(stream));
+  if (he != hipSuccess) return fail(RT_ERR_HIP, "svgf launch failed: %s", hipGetErrorString(he));
+  return RT_OK;
+}
+
+int rt_svgf(rt_ctx* c, const rt_svgf_params* s, const float* cur_rgb, const rt_aov* aov, const rt_motion* cur,
+            const rt_svgf_history* prev, const rt_svgf_out* out) {
+  int rc = svgf_checks(c, s, cur_rgb, aov, cur, prev, out);
+  if (rc != RT_OK) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t npx = (size_t)s->width * s->height;
+  // inputs: cur_rgb, albedo, normal, position, motion, prev_position, history colour, moments, position, length; hits, mesh,
+  // history mesh
+  const float* const hF[10] = {cur_rgb,     aov->albedo,   aov->normal,    aov->position, cur->motion, cur->prev_position,
+                               prev->color, prev->moments, prev->position, prev->length};
+  const size_t wF[10] = {3, 3, 3, 3, 2, 3, 3, 2, 3, 1};
+  const uint32_t* const hU[3] = {aov->hits, cur->mesh, prev->mesh};
+  DevBuf<float> dF[10], dO[6];
+  DevBuf<uint32_t> dU[3];
+  for (int i = 0; i < 10; ++i) {
+    HIP_TRY(dev_alloc(&dF[i], npx * wF[i]));
+    HIP_TRY(hipMemcpy(dF[i].get(), hF[i], npx * wF[i] * sizeof(float), hipMemcpyHostToDevice));
+  }
+  for (int i = 0; i < 3; ++i) {
+    HIP_TRY(dev_alloc(&dU[i], npx));
+    HIP_TRY(hipMemcpy(dU[i].get(), hU[i], npx * sizeof(uint32_t), hipMemcpyHostToDevice));
+  }
+  float* const hO[6] = {out->rgb, out->color, out->moments, out->length, out->accum, out->variance};
+  const size_t wO[6] = {3, 3, 2, 1, 3, 1};
+  for (int i = 0; i < 6; ++i)
+    if (hO[i]) HIP_TRY(dev_alloc(&dO[i], npx * wO[i]));
+  rt_aov da = {};
+  da.albedo = dF[1].get(), da.normal = dF[2].get(), da.position = dF[3].get(), da.hits = dU[0].get();
+  rt_motion dc = {};
+  dc.motion = dF[4].get(), dc.prev_position = dF[5].get(), dc.mesh = dU[1].get();
+  rt_svgf_history dh = {};
+  dh.color = dF[6].get(), dh.moments = dF[7].get(), dh.position = dF[8].get(), dh.length = dF[9].get(), dh.mesh = dU[2].get();
+  rt_svgf_out dout = {};
+  dout.rgb = dO[0].get(), dout.color = dO[1].get(), dout.moments = dO[2].get(), dout.length = dO[3].get();
+  dout.accum = dO[4].get(), dout.variance = dO[5].get();
+  rc = rt_svgf_device(c, s, dF[0].get(), &da, &dc, &dh, &dout, nullptr);
+  if (rc != RT_OK) return rc;
+  for (int i = 0; i < 6; ++i)
+    if (hO[i]) HIP_TRY(hipMemcpy(hO[i], dO[i].get(), npx * wO[i] * sizeof(float), hipMemcpyDeviceToHost));
   return RT_OK;
 }
 

@@ -149,6 +149,48 @@ def empty_history(width, height):
                 mesh=np.full((height, width), 0xffffffff, np.uint32), length=np.zeros((height, width), np.float32))
 
 
+class SvgfParams(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("iterations", C.c_uint32), ("max_history", C.c_uint32),
+                ("alpha_min", C.c_float), ("alpha_min_moments", C.c_float), ("sigma_luminance", C.c_float),
+                ("sigma_normal", C.c_float), ("sigma_position", C.c_float), ("sigma_reproject", C.c_float),
+                ("reserved", C.c_uint32 * 6)]
+
+
+class SvgfHistory(C.Structure):
+    """rt_svgf_history: one frame's history (host or device pointers), all five required."""
+    _fields_ = [("color", C.c_void_p), ("moments", C.c_void_p), ("position", C.c_void_p), ("mesh", C.c_void_p),
+                ("length", C.c_void_p)]
+
+
+class SvgfOut(C.Structure):
+    """rt_svgf_out: output pointers (host or device); accum and variance may be None."""
+    _fields_ = [("rgb", C.c_void_p), ("color", C.c_void_p), ("moments", C.c_void_p), ("length", C.c_void_p),
+                ("accum", C.c_void_p), ("variance", C.c_void_p), ("reserved", C.c_uint32 * 4)]
+
+
+SVGF_HISTORY_CHANNELS = ("color", "moments", "position", "mesh", "length")
+SVGF_OUT_CHANNELS = (("rgb", 3), ("color", 3), ("moments", 2), ("length", 1), ("accum", 3), ("variance", 1))
+SVGF_FIELDS = ("iterations", "max_history", "alpha_min", "alpha_min_moments", "sigma_luminance", "sigma_normal",
+               "sigma_position", "sigma_reproject")
+
+
+def make_svgf(width, height, **kw):
+    """rt_svgf_params: kw of SVGF_FIELDS, 0 (the default of each) = the library's default."""
+    s = SvgfParams()
+    s.width, s.height = width, height
+    for k, v in kw.items():
+        assert k in SVGF_FIELDS, k
+        setattr(s, k, v)
+    return s
+
+
+def empty_svgf_history(width, height):
+    """The history the first frame of a sequence passes to Context.svgf: length 0 everywhere."""
+    z = lambda *shape: np.zeros(shape, np.float32)
+    return dict(color=z(height, width, 3), moments=z(height, width, 2), position=z(height, width, 3),
+                mesh=np.full((height, width), 0xffffffff, np.uint32), length=z(height, width))
+
+
 class AdaptiveParams(C.Structure):
     _fields_ = [("max_passes", C.c_uint32), ("min_passes", C.c_uint32), ("threshold", C.c_float), ("floor", C.c_float),
                 ("reserved", C.c_uint32 * 6)]
@@ -223,7 +265,7 @@ AMD_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_create", "rt_destroy", "rt
                "rt_update", "rt_update_vertices_device", "rt_group_update", "rt_render_aov", "rt_render_aov_device",
                "rt_denoise", "rt_denoise_device", "rt_render_adaptive", "rt_render_adaptive_device", "rt_render_views",
                "rt_render_views_device", "rt_render_motion", "rt_render_motion_device", "rt_temporal_accumulate",
-               "rt_temporal_accumulate_device"]
+               "rt_temporal_accumulate_device", "rt_svgf", "rt_svgf_device"]
 HOST_SYMBOLS = ["rt_host_scene_build", "rt_host_scene_desc", "rt_host_scene_free", "rt_host_last_error",
                 "rt_host_fill_background", "rt_host_save_ppm", "rt_host_kd_order", "rt_host_light_basis"]
 
@@ -320,6 +362,9 @@ def amd():
                                              C.POINTER(History), C.c_void_p, C.c_void_p]
         L.rt_temporal_accumulate_device.argtypes = [C.c_void_p, C.POINTER(TemporalParams), C.c_void_p, C.POINTER(Motion),
                                                     C.POINTER(History), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rt_svgf.argtypes = [C.c_void_p, C.POINTER(SvgfParams), C.c_void_p, C.POINTER(Aov), C.POINTER(Motion),
+                              C.POINTER(SvgfHistory), C.POINTER(SvgfOut)]
+        L.rt_svgf_device.argtypes = L.rt_svgf.argtypes + [C.c_void_p]
         _amd = L
     return _amd
 
@@ -735,6 +780,45 @@ class Context:
         t = make_temporal(width, height, max_history, alpha_min, sigma_position)
         _check(amd().rt_temporal_accumulate_device(self._h, C.byref(t), C.c_void_p(d_cur_rgb), C.byref(m), C.byref(hs),
                                                    C.c_void_p(d_out_rgb), C.c_void_p(d_out_length), C.c_void_p(stream or None)))
+
+    def svgf(self, cur_rgb, aov_sums, cur, prev, want=("accum", "variance"), out_rgb=None, **kw):
+        """rt_svgf: cur_rgb [h][w][3] the current frame, aov_sums = render_aov(raw=True)'s sums for it, cur =
+        render_motion's dict, prev = the history dict (color, moments, position, mesh, length; pyrt.empty_svgf_history
+        for the first frame); kw: make_svgf's.  Returns a dict of rgb, color, moments, length and the optional outputs
+        named in `want`; the next frame's history is dict(color=out["color"], moments=out["moments"],
+        position=cur["position"], mesh=cur["mesh"], length=out["length"]).  out_rgb may be cur_rgb itself (in place)."""
+        rgb = np.ascontiguousarray(cur_rgb, np.float32)
+        h, w = rgb.shape[:2]
+        u32 = ("hits", "mesh")
+        keep = [{k: np.ascontiguousarray(src[k], np.uint32 if k in u32 else np.float32) for k in names}
+                for src, names in ((aov_sums, ("albedo", "normal", "position", "hits")),
+                                   (cur, ("motion", "prev_position", "mesh")), (prev, SVGF_HISTORY_CHANNELS))]
+        a, m, hs, o = Aov(), Motion(), SvgfHistory(), SvgfOut()
+        for st, d in zip((a, m, hs), keep):
+            for k, v in d.items():
+                setattr(st, k, v.ctypes.data)
+        out = {k: np.empty((h, w, n) if n > 1 else (h, w), np.float32) for k, n in SVGF_OUT_CHANNELS
+               if k in ("rgb", "color", "moments", "length") or k in want}
+        if out_rgb is not None:
+            assert out_rgb.dtype == np.float32 and out_rgb.flags["C_CONTIGUOUS"] and out_rgb.shape == rgb.shape
+            out["rgb"] = out_rgb
+        for k, v in out.items():
+            setattr(o, k, v.ctypes.data)
+        s = make_svgf(w, h, **kw)
+        _check(amd().rt_svgf(self._h, C.byref(s), _ptr(rgb), C.byref(a), C.byref(m), C.byref(hs), C.byref(o)))
+        return out
+
+    def svgf_device(self, width, height, d_cur_rgb, aov_ptrs, cur_ptrs, prev_ptrs, out_ptrs, stream=0, **kw):
+        """rt_svgf_device: device pointers (aov_ptrs = {"albedo", "normal", "position", "hits": sums}, cur_ptrs =
+        {"motion", "prev_position", "mesh"}, prev_ptrs = the five history channels, out_ptrs = {"rgb", "color",
+        "moments", "length"} and optionally "accum", "variance"), on `stream`; kw: make_svgf's."""
+        a, m, hs, o = Aov(), Motion(), SvgfHistory(), SvgfOut()
+        for st, d in ((a, aov_ptrs), (m, cur_ptrs), (hs, prev_ptrs), (o, out_ptrs)):
+            for k, v in d.items():
+                setattr(st, k, v or None)
+        s = make_svgf(width, height, **kw)
+        _check(amd().rt_svgf_device(self._h, C.byref(s), C.c_void_p(d_cur_rgb), C.byref(a), C.byref(m), C.byref(hs), C.byref(o),
+                                    C.c_void_p(stream or None)))
 
     def render_adaptive(self, params, bg, threshold, max_passes, min_passes=0, floor=0.):
         """rt_render_adaptive: passes of params.spp samples over the granules not yet converged (DESIGN.md "Adaptive

@@ -1,9 +1,9 @@
 #!/bin/bash
 # Registers, scratch and LDS of every kernel instance (compiler remarks; runs without a GPU).
-# usage: tools/kernel_resources.sh [filter-regex]  -> table on stdout
+# usage: tools/kernel_resources.sh [filter-regex] [source under csrc/, default rt_kernels.hip]  -> table on stdout
 cd "$(dirname "$0")/../ray-tracing-engine_amd"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-slp-vectorize -I../include -Icsrc -Ihost \
-  -c csrc/rt_kernels.hip -o /tmp/rk_res.o -Rpass-analysis=kernel-resource-usage 2>&1 |
+  -c "csrc/${2:-rt_kernels.hip}" -o /tmp/rk_res.o -Rpass-analysis=kernel-resource-usage 2>&1 |
 python3 -c '
 import re,sys,subprocess
 rows=[];cur=None
@@ -18,7 +18,7 @@ names=subprocess.run(["c++filt"]+[r["name"] for r in rows],capture_output=True,t
 flt=re.compile(sys.argv[1]) if len(sys.argv)>1 else None
 print("%-72s %5s %7s %6s %6s %4s"%("kernel","VGPR","scratch","vspill","sspill","occ"))
 for r,n in zip(rows,names):
-    n=n.split("(")[0].replace("void rtk::","")
+    n=n.replace("(anonymous namespace)::","").split("(")[0].replace("void rtk::","")
     if flt and not flt.search(n): continue
     print("%-72s %5d %7d %6d %6d %4d"%(n[:72],r.get("vgpr",0),r.get("scratch",0),r.get("vspill",0),r.get("sspill",0),r.get("occ",0)))
 ' "$@"
