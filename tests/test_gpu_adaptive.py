@@ -9,6 +9,7 @@ import pytest
 
 import adaptive_ref
 import pyrt
+from adaptive_cases import bits, chain_of, check_frame, pick_threshold
 
 pytestmark = pytest.mark.gpu
 
@@ -16,50 +17,6 @@ P = 4
 PASSES = 8
 SEED = 17
 INVALID, UNSUPPORTED, STATE = 1, 4, 5  # rt_amd.h RT_ERR_*
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def chain_of(ctx, p, bg, passes):
-    """accumulators after passes 0..passes-1 of the reference chain (rt_render_passes, seed + j, full ranges)."""
-    acc = np.zeros((p.height, p.width, 4), np.float32)
-    out = []
-    for j in range(passes):
-        q = pyrt.Params.from_buffer_copy(p)
-        q.seed = (p.seed + j) & 0xffffffff
-        ctx.render_passes(q, bg, acc)
-        out.append(acc.copy())
-    return out
-
-
-def check_frame(ctx, p, bg, chain, threshold, max_passes, min_passes=0, floor=0.):
-    """Run the adaptive frame and compare everything with the restatement; returns K per granule."""
-    w, h = p.width, p.height
-    K, active = adaptive_ref.run_rule(chain, bg, p.spp, threshold, max_passes, min_passes, floor)
-    out, acc, spp, rep, st = ctx.render_adaptive(p, bg, threshold, max_passes, min_passes, floor)
-    Kp = adaptive_ref.per_pixel(K, w, h)
-    assert np.array_equal(spp, (Kp * p.spp).astype(np.uint32)), "per-pixel sample counts differ from the rule's"
-    exp_acc = adaptive_ref.assemble(chain, K, w, h)
-    assert np.array_equal(bits(acc), bits(exp_acc)), "accumulator differs from the chain at %d pixels" % int(
-        np.any(bits(acc) != bits(exp_acc), axis=2).sum())
-    exp_out = adaptive_ref.resolve(exp_acc, bg, Kp * p.spp)
-    assert np.array_equal(bits(out), bits(exp_out)), "image differs from the per-pixel resolve"
-    assert rep.passes == len(active) and list(rep.active)[:len(active)] == active
-    assert rep.granules == K.size and rep.pixel_samples == int(spp.astype(np.uint64).sum())
-    assert st.samples == rep.pixel_samples and st.rays_closest > 0
-    assert rep.render_ms > 0 and rep.adapt_ms > 0 and rep.total_ms >= rep.render_ms
-    return K, out, acc, spp, rep
-
-
-def pick_threshold(chain, bg, max_passes, P_):
-    """A threshold at which granules retire after at least three different pass counts."""
-    for t in (0.5, 0.3, 0.2, 0.15, 0.1, 0.07, 0.05, 0.03, 0.02, 0.01):
-        K, _ = adaptive_ref.run_rule(chain, bg, P_, t, max_passes)
-        if len(np.unique(K)) >= 3:
-            return t, K
-    raise AssertionError("no threshold retires granules at three different passes")
 
 
 @pytest.mark.parametrize("kind,w,h", [("cubes", 64, 64), ("lowres", 96, 64), ("cubes", 70, 45)],
