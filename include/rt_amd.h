@@ -13,6 +13,8 @@
  *   rt_emit_photons             <- PhotonMap::PhotonMap (PhotonMap.h:14-50,92-155)
  *   rt_update                   <- a scene changed between frames (Main.cpp:88-99 rotationY, a moving
  *                                  camera or light): the resident context follows it, tree refit
+ *   rt_update_transforms        <- the same with one matrix per mesh (Main.cpp:88-99): the device transforms a
+ *                                  resident rest pose, nothing per vertex crosses the bus
  *   rt_render                   <- the spp/y/x loop + resolve (Renderer.cpp:219-271)
  *   rt_render_device/_resolve_device : same, on caller-owned DEVICE buffers and a
  *                                  caller stream (multi-GPU tile sharding, bench)
@@ -233,6 +235,48 @@ int rt_update(rt_ctx* ctx, const rt_scene_update* u, rt_update_report* rep /* ma
  * `stream` (a hipStream_t, may be NULL); either pointer may be NULL.  Synchronises once to read the magnitude summary
  * back (the finiteness check and the rules above need it) and once at the end. */
 int rt_update_vertices_device(rt_ctx* ctx, const void* d_pos, const void* d_nrm, void* stream, rt_update_report* rep);
+
+/* ---- animating rigid meshes by matrices (Main.cpp:88-99: "mesh 3 is now at this matrix") ---------------------------
+ * rt_update whose positions and normals the DEVICE computes from a resident rest pose and one record per mesh: the host
+ * sends 88 bytes per mesh instead of every vertex.
+ * Rest pose: the context's positions and normals as the last call that was NOT rt_update_transforms left them — rt_create,
+ * or an rt_update / rt_update_vertices_device that gave positions or normals (such a call makes the live arrays, both of
+ * them, the new rest pose).  Transforms are absolute, from the rest pose, never cumulative: frame 100 carries no rounding
+ * of frames 1-99, and the same records give the same bits whatever came between.
+ * Per vertex of mesh j, rest position (x, y, z) and rest normal (a, b, c), all in float32, in this order, nothing fused:
+ *   X'_i = ((m[i][0] x + m[i][1] y) + m[i][2] z) + m[i][3]        N'_i = (n[i][0] a + n[i][1] b) + n[i][2] c
+ * — the association of `dot` in the reference's Vec3.h, so m = n = rotationY's rows reproduces rotationY.  Normals are not
+ * renormalised: n is the caller's normal matrix (identity = "normals are left as loaded").  An RT_XF_STATIC mesh keeps
+ * its rest arrays bit for bit and its m and n are not read.  An identity matrix is NOT RT_XF_STATIC: -0 + 0 = +0, so a
+ * rest coordinate of -0 comes out as +0.
+ * After a successful call the context is, bit for bit, what rt_update with vertex_pos / vertex_nrm = those arrays and the
+ * same camera and lights would leave (tree, rt_bvh_info, every frame and pass, the photon map released, the report); the
+ * rules above apply through the same code.
+ * Validation comes first and a rejected call leaves the context and d_prev_pos untouched.  RT_ERR_INVALID: a null ctx, u
+ * or transforms; non-zero reserved words; unknown flag bits, or a non-finite entry of m or n of a mesh that is not
+ * RT_XF_STATIC (rt_last_error names the mesh); lights NULL with n_lights > 0; n_meshes different from the context's; a
+ * transformed position a triangle references coming out non-finite ("non-finite vertex position", as rt_update).
+ * RT_ERR_UNSUPPORTED: RT_NODES_Q8 contexts.  RT_ERR_STATE: a context that refuses launches.
+ * Ordered on `stream` (a hipStream_t, may be NULL); synchronises it as rt_update_vertices_device does, once for the
+ * magnitude summary and once at the end. */
+enum { RT_XF_STATIC = 1 };   /* flags bit 0: this mesh keeps its rest arrays, bits copied verbatim; m and n ignored */
+typedef struct rt_mesh_transform {
+  float m[3][4];       /* positions: row i = (m[i][0], m[i][1], m[i][2] | m[i][3])                                  */
+  float n[3][3];       /* normals: the caller's normal matrix                                                       */
+  uint32_t flags;      /* RT_XF_*; other bits zero                                                                  */
+} rt_mesh_transform;
+typedef struct rt_transform_update {
+  const rt_mesh_transform* transforms;  /* [n_meshes], HOST memory, required                                       */
+  uint32_t n_meshes;                    /* must equal the context's                                                */
+  uint32_t n_lights;
+  const rt_camera* camera;              /* or NULL = unchanged, as rt_scene_update                                 */
+  const rt_light* lights;               /* [n_lights] or NULL = unchanged                                          */
+  void* d_prev_pos;                     /* DEVICE [n_vertices][3] or NULL: receives the context's positions as they
+                                           were BEFORE this call, ordered on `stream` (the prev->vertex_pos of
+                                           rt_render_motion_device)                                                */
+  uint32_t reserved[6];                 /* zero                                                                    */
+} rt_transform_update;
+int rt_update_transforms(rt_ctx* ctx, const rt_transform_update* u, void* stream, rt_update_report* rep /* may be NULL */);
 
 /* Photon arrays already in the host-built kd-tree (median-implicit) order. */
 int rt_set_photons(rt_ctx* ctx, const float* pos3, const float* dir3, uint32_t n);

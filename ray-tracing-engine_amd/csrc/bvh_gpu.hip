@@ -633,6 +633,85 @@ __global__ __launch_bounds__(256) void k_magnitudes(const float* __restrict__ po
   }
 }
 
+// rt_update_transforms: the rest pose under one record per mesh, in one pass.  A workgroup takes tiles of 256 vertices: the
+// tile's 768 + 768 floats come in and go out as whole dwords in address order (lane i at base + 4 i) through LDS, where a
+// thread works on its own vertex (a stride of three dwords: no bank is shared), and the magnitudes of everything written
+// are folded on the way out — out[1] all positions, out[2] all normals, as k_magnitudes ([0] needs the finished array:
+// launch_transform runs k_magnitudes' triangle loop over it).  A vertex finds its mesh by upper bound in meshVtxBegin (an
+// empty mesh owns no vertex; a vertex outside every mesh is copied); a wave inside one mesh reads that record through a
+// uniform index (every lane the same address: one cache line, broadcast), a wave across meshes each lane its own — the same
+// values into the same expression either way.  (The compiler folds the two into one vector load of a selected index; the
+// record does not come through scalar loads or LDS, and at 22 dwords per 96-byte vertex it does not need to.)
+// The arithmetic is rt_amd.h's, spelt with the _rn intrinsics so that no flag can fuse it.
+constexpr uint32_t kXfTile = 256;
+
+__device__ __forceinline__ void xf_apply(const rt_mesh_transform& R, float x, float y, float z, float a, float b, float c,
+                                         float* __restrict__ p, float* __restrict__ q) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    p[i] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(R.m[i][0], x), __fmul_rn(R.m[i][1], y)), __fmul_rn(R.m[i][2], z)), R.m[i][3]);
+    q[i] = __fadd_rn(__fadd_rn(__fmul_rn(R.n[i][0], a), __fmul_rn(R.n[i][1], b)), __fmul_rn(R.n[i][2], c));
+  }
+}
+
+__global__ __launch_bounds__(kXfTile) void k_transform(const float* __restrict__ restPos, const float* __restrict__ restNrm,
+                                                       const rt_mesh_transform* __restrict__ table,
+                                                       const uint32_t* __restrict__ meshVtxBegin, uint32_t nMeshes, uint32_t nVerts,
+                                                       float* __restrict__ outPos, float* __restrict__ outNrm,
+                                                       uint32_t* __restrict__ out) {
+  __shared__ float sP[3 * kXfTile], sN[3 * kXfTile];
+  const uint32_t tid = threadIdx.x;
+  const uint32_t nTiles = (nVerts + kXfTile - 1) / kXfTile;
+  const size_t nFloats = 3 * (size_t)nVerts;
+  uint32_t mPos = 0, mNrm = 0;
+  for (uint32_t tile = blockIdx.x; tile < nTiles; tile += gridDim.x) {
+    const size_t base = 3 * (size_t)tile * kXfTile;
+#pragma unroll
+    for (uint32_t r = 0; r < 3; ++r) {
+      const size_t k = base + r * kXfTile + tid;
+      if (k < nFloats) sP[r * kXfTile + tid] = restPos[k], sN[r * kXfTile + tid] = restNrm[k];
+    }
+    __syncthreads();
+    const uint32_t v = tile * kXfTile + tid;
+    // (lanes past the end look the last vertex up, so that the whole wave takes part in the vote below)
+    const uint32_t vq = min(v, nVerts - 1u);
+    uint32_t lo = 0, hi = nMeshes + 1u;  // upper bound: the first entry of meshVtxBegin above vq
+    while (lo < hi) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (meshVtxBegin[mid] <= vq) lo = mid + 1u; else hi = mid;
+    }
+    const bool inMesh = lo >= 1u && lo <= nMeshes;
+    const uint32_t j = inMesh ? lo - 1u : 0u;
+    const uint32_t j0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)j);
+    const rt_mesh_transform R = __all(j == j0) ? table[j0] : table[j];
+    if (v < nVerts && inMesh && !(R.flags & RT_XF_STATIC)) {
+      float p[3], q[3];
+      xf_apply(R, sP[3 * tid], sP[3 * tid + 1], sP[3 * tid + 2], sN[3 * tid], sN[3 * tid + 1], sN[3 * tid + 2], p, q);
+#pragma unroll
+      for (int i = 0; i < 3; ++i) sP[3 * tid + i] = p[i], sN[3 * tid + i] = q[i];
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t r = 0; r < 3; ++r) {
+      const size_t k = base + r * kXfTile + tid;
+      if (k < nFloats) {
+        const float p = sP[r * kXfTile + tid], q = sN[r * kXfTile + tid];
+        outPos[k] = p, outNrm[k] = q;
+        mPos = max(mPos, __float_as_uint(p) & 0x7fffffffu), mNrm = max(mNrm, __float_as_uint(q) & 0x7fffffffu);
+      }
+    }
+    __syncthreads();
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    mPos = max(mPos, (uint32_t)__shfl_xor((int)mPos, off));
+    mNrm = max(mNrm, (uint32_t)__shfl_xor((int)mNrm, off));
+  }
+  if ((tid & 63u) == 0u) {
+    if (mPos) atomicMax(out + 1, mPos);
+    if (mNrm) atomicMax(out + 2, mNrm);
+  }
+}
+
 // the leaf-order records again: each record keeps its triangle (the id it holds), its vertices are read anew
 __global__ void k_refit_tris(const float* __restrict__ vpos, const uint4* __restrict__ triShade, uint32_t n, float4* __restrict__ recs) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1761,6 +1840,20 @@ hipError_t launch_magnitudes(const float* dPos, const float* dNrm, const uint4* 
   const uint32_t work = std::max(nTris, 3u * nVerts);
   const uint32_t blocks = std::max(1u, std::min(4096u, (work + 255u) / 256u));
   hipLaunchKernelGGL(k_magnitudes, dim3(blocks), dim3(256), 0, stream, dPos, dNrm, dTriShade, nTris, nVerts, dOut3);
+  return hipGetLastError();
+}
+
+hipError_t launch_transform(const float* dRestPos, const float* dRestNrm, const rt_mesh_transform* dTable, const uint32_t* dMeshVtxBegin,
+                            uint32_t nMeshes, uint32_t nVerts, float* dOutPos, float* dOutNrm, const uint4* dTriShade, uint32_t nTris,
+                            uint32_t* dOut3, hipStream_t stream) {
+  hipError_t e = hipMemsetAsync(dOut3, 0, 3 * sizeof(uint32_t), stream);
+  if (e != hipSuccess || nVerts == 0 || nMeshes == 0) return e;
+  const uint32_t tiles = (nVerts + kXfTile - 1) / kXfTile;
+  hipLaunchKernelGGL(k_transform, dim3(std::min(4096u, tiles)), dim3(kXfTile), 0, stream, dRestPos, dRestNrm, dTable, dMeshVtxBegin, nMeshes,
+                     nVerts, dOutPos, dOutNrm, dOut3);
+  // word 0 over the finished positions: k_magnitudes' triangle loop alone (no vertices, no normals: words 1 and 2 stay)
+  const uint32_t blocks = std::max(1u, std::min(4096u, (nTris + 255u) / 256u));
+  hipLaunchKernelGGL(k_magnitudes, dim3(blocks), dim3(256), 0, stream, (const float*)dOutPos, (const float*)nullptr, dTriShade, nTris, 0u, dOut3);
   return hipGetLastError();
 }
 

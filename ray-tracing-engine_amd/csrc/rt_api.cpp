@@ -186,6 +186,11 @@ struct rt_ctx {
   uint32_t refitMaxDepth = 0;
   DevBuf<float> updPos, updNrm;
   DevBuf<uint32_t> dMag;
+  // rt_update_transforms (allocated on first use): the rest pose — a snapshot of vpos / vnrm taken at the first transforms
+  // call after a call that gave vertex arrays (restValid) — and the per-mesh records
+  DevBuf<float> restPos, restNrm;
+  bool restValid = false;
+  DevBuf<rt_mesh_transform> xfTable;
   // scratch of rt_denoise_device (guides, albedo factors, two colour buffers; grows on demand)
   DevBuf<float4> dnScratch;
   size_t dnCap = 0;
@@ -1856,6 +1861,10 @@ struct Update {
   uint32_t nLights = 0;
   const rt_material* materials = nullptr;
   const rtbvh::Padding* padding = nullptr;  // rt_render_views: its farthest view's padding in place of the camera's rule
+  // rt_update_transforms: dPos / dNrm come from the rest pose (which stays), their summary is already on its way into
+  // c->dMag on the stream, and the positions the update replaces go to dPrevPos first
+  bool fromRest = false, magQueued = false;
+  void* dPrevPos = nullptr;
 };
 
 int update_checks(rt_ctx* c, const rt_light* lights, uint32_t nLights) {
@@ -1875,7 +1884,7 @@ int update_ctx(rt_ctx* c, const Update& u, hipStream_t stream, std::chrono::stea
   if (u.dPos || u.dNrm) {
     if (!c->dMag) HIP_TRY(dev_alloc(&c->dMag, 3));
     uint32_t h[3] = {0, 0, 0};
-    hipError_t he = rtk::launch_magnitudes(u.dPos, u.dNrm, c->triShade.get(), S.n_tris, c->nVertices, c->dMag.get(), stream);
+    hipError_t he = u.magQueued ? hipSuccess : rtk::launch_magnitudes(u.dPos, u.dNrm, c->triShade.get(), S.n_tris, c->nVertices, c->dMag.get(), stream);
     if (he == hipSuccess) he = hipMemcpyAsync(h, c->dMag.get(), sizeof h, hipMemcpyDeviceToHost, stream);
     if (he == hipSuccess) he = hipStreamSynchronize(stream);
     if (he != hipSuccess) return fail(RT_ERR_HIP, "update: magnitude pass failed: %s", hipGetErrorString(he));
@@ -1917,7 +1926,8 @@ int update_ctx(rt_ctx* c, const Update& u, hipStream_t stream, std::chrono::stea
   c->broken = true;
   const size_t nv = 3 * (size_t)c->nVertices;
   hipError_t he = hipSuccess;
-  if (u.dPos && u.dPos != c->vpos.get()) he = hipMemcpyAsync(c->vpos.get(), u.dPos, nv * sizeof(float), hipMemcpyDeviceToDevice, stream);
+  if (u.dPrevPos) he = hipMemcpyAsync(u.dPrevPos, c->vpos.get(), nv * sizeof(float), hipMemcpyDeviceToDevice, stream);
+  if (he == hipSuccess && u.dPos && u.dPos != c->vpos.get()) he = hipMemcpyAsync(c->vpos.get(), u.dPos, nv * sizeof(float), hipMemcpyDeviceToDevice, stream);
   if (he == hipSuccess && u.dNrm && u.dNrm != c->vnrm.get())
     he = hipMemcpyAsync(c->vnrm.get(), u.dNrm, nv * sizeof(float), hipMemcpyDeviceToDevice, stream);
   if (refit) {
@@ -1955,6 +1965,7 @@ int update_ctx(rt_ctx* c, const Update& u, hipStream_t stream, std::chrono::stea
     S.mats = c->mats.get(), S.matsDev = c->matsDev.get();
   }
   vouch_short_forms(c);
+  if ((u.dPos || u.dNrm) && !u.fromRest) c->restValid = false;  // the live arrays are the new rest pose of rt_update_transforms
   // the photon map was emitted from the old geometry, normals, lights and materials
   if (u.dPos || u.dNrm || u.lights || u.materials) {
     r.photons_dropped = S.n_photons > 0 ? 1u : 0u;
@@ -2005,6 +2016,54 @@ int rt_update_vertices_device(rt_ctx* c, const void* d_pos, const void* d_nrm, v
   Update x;
   x.dPos = static_cast<const float*>(d_pos), x.dNrm = static_cast<const float*>(d_nrm);
   return update_ctx(c, x, static_cast<hipStream_t>(stream), t0, rep);
+}
+
+int rt_update_transforms(rt_ctx* c, const rt_transform_update* u, void* stream_, rt_update_report* rep) {
+  const auto t0 = std::chrono::steady_clock::now();
+  if (rep) memset(rep, 0, sizeof *rep);
+  // what the update says of itself comes before anything of the context
+  if (!u) return fail(RT_ERR_INVALID, "ctx/update is null");
+  if (!u->transforms) return fail(RT_ERR_INVALID, "update: transforms is null");
+  for (uint32_t r : u->reserved)
+    if (r) return fail(RT_ERR_INVALID, "update: reserved words must be zero");
+  for (uint32_t j = 0; j < u->n_meshes; ++j) {
+    const rt_mesh_transform& t = u->transforms[j];
+    if (t.flags & ~(uint32_t)RT_XF_STATIC) return fail(RT_ERR_INVALID, "update: mesh %u: unknown transform flags 0x%x", j, t.flags);
+    if (t.flags & RT_XF_STATIC) continue;
+    bool finite = true;
+    for (int i = 0; i < 12; ++i) finite = finite && std::isfinite(t.m[i / 4][i % 4]);
+    for (int i = 0; i < 9; ++i) finite = finite && std::isfinite(t.n[i / 3][i % 3]);
+    if (!finite) return fail(RT_ERR_INVALID, "update: mesh %u: non-finite entry in its transform", j);
+  }
+  if (!u->lights && u->n_lights) return fail(RT_ERR_INVALID, "update: lights is null but n_lights is %u", u->n_lights);
+  if (!c) return fail(RT_ERR_INVALID, "ctx/update is null");
+  if (u->n_meshes != c->nMeshes) return fail(RT_ERR_INVALID, "update: %u transforms for a context of %u meshes", u->n_meshes, c->nMeshes);
+  int rc = update_checks(c, u->lights, u->n_lights);
+  if (rc != RT_OK) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const size_t nv = 3 * (size_t)c->nVertices;
+  // nothing below is visible until update_ctx's own validation has passed: the rest pose is a copy of the live arrays,
+  // the result goes to the scratch of rt_update's host form
+  if (!c->restPos) HIP_TRY(dev_alloc(&c->restPos, nv));
+  if (!c->restNrm) HIP_TRY(dev_alloc(&c->restNrm, nv));
+  if (!c->updPos) HIP_TRY(dev_alloc(&c->updPos, nv));
+  if (!c->updNrm) HIP_TRY(dev_alloc(&c->updNrm, nv));
+  if (!c->xfTable) HIP_TRY(dev_alloc(&c->xfTable, c->nMeshes));
+  if (!c->dMag) HIP_TRY(dev_alloc(&c->dMag, 3));
+  if (!c->restValid) {
+    HIP_TRY(hipMemcpyAsync(c->restPos.get(), c->vpos.get(), nv * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(c->restNrm.get(), c->vnrm.get(), nv * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    c->restValid = true;
+  }
+  HIP_TRY(hipMemcpyAsync(c->xfTable.get(), u->transforms, c->nMeshes * sizeof(rt_mesh_transform), hipMemcpyHostToDevice, stream));
+  HIP_TRY(rtk::launch_transform(c->restPos.get(), c->restNrm.get(), c->xfTable.get(), c->meshVtxBegin.get(), c->nMeshes, c->nVertices,
+                                c->updPos.get(), c->updNrm.get(), c->triShade.get(), c->S.n_tris, c->dMag.get(), stream));
+  Update x;
+  x.dPos = c->updPos.get(), x.dNrm = c->updNrm.get();
+  x.camera = u->camera, x.lights = u->lights, x.nLights = u->n_lights;
+  x.fromRest = x.magQueued = true, x.dPrevPos = u->d_prev_pos;
+  return update_ctx(c, x, stream, t0, rep);
 }
 
 int rt_group_update(rt_group* g, const rt_scene_update* u, rt_update_report* rep) {

@@ -234,6 +234,12 @@ hipError_t gpu_bvh_build_over_top(const float* dVpos, const uint4* dTriShade, co
 // with boxScale (slot order, refs and numbering untouched)
 hipError_t launch_magnitudes(const float* dPos, const float* dNrm, const uint4* dTriShade, uint32_t nTris, uint32_t nVerts,
                              uint32_t* dOut3, hipStream_t stream);
+// rt_update_transforms: dOutPos / dOutNrm = the rest arrays under the per-mesh records of dTable (rt_amd.h's arithmetic;
+// RT_XF_STATIC meshes copied), and dOut3 = launch_magnitudes' three words of the result, positions and normals folded in
+// the same pass.  The out arrays must not alias the rest arrays.
+hipError_t launch_transform(const float* dRestPos, const float* dRestNrm, const rt_mesh_transform* dTable, const uint32_t* dMeshVtxBegin,
+                            uint32_t nMeshes, uint32_t nVerts, float* dOutPos, float* dOutNrm, const uint4* dTriShade, uint32_t nTris,
+                            uint32_t* dOut3, hipStream_t stream);
 hipError_t gpu_bvh_depths(const float4* nodesF, uint32_t n, uint8_t* dDepth, uint32_t* maxDepthOut, hipStream_t stream);
 hipError_t gpu_bvh_refit(const float* dVpos, const uint4* dTriShade, uint32_t nTris, bool records, float4* tris, float4* trisRef,
                          float4* nodesF, uint4* nodes16, uint32_t nNodes, const uint8_t* dDepth, uint32_t maxDepth, float pad,

@@ -101,6 +101,34 @@ class UpdateReport(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
 
 
+XF_STATIC = 1
+
+
+class MeshTransform(C.Structure):
+    """rt_mesh_transform: m [3][4] (positions, last column the translation), n [3][3] (normals), flags (XF_*)."""
+    _fields_ = [("m", (C.c_float * 4) * 3), ("n", (C.c_float * 3) * 3), ("flags", C.c_uint32)]
+
+
+class TransformUpdate(C.Structure):
+    _fields_ = [("transforms", C.POINTER(MeshTransform)), ("n_meshes", C.c_uint32), ("n_lights", C.c_uint32),
+                ("camera", C.POINTER(Camera)), ("lights", C.POINTER(Light)), ("d_prev_pos", C.c_void_p),
+                ("reserved", C.c_uint32 * 6)]
+
+
+# rt_mesh_transform as a numpy record (make_transforms)
+TRANSFORM_DTYPE = np.dtype([("m", "<f4", (3, 4)), ("n", "<f4", (3, 3)), ("flags", "<u4")])
+
+
+def make_transforms(n_meshes):
+    """[n_meshes] rt_mesh_transform records to fill in (fields m, n, flags): identity matrices, every mesh XF_STATIC —
+    clear a mesh's flags to move it."""
+    t = np.zeros(n_meshes, TRANSFORM_DTYPE)
+    t["m"][:, :, :3] = np.eye(3, dtype=np.float32)
+    t["n"][:] = np.eye(3, dtype=np.float32)
+    t["flags"] = XF_STATIC
+    return t
+
+
 class Aov(C.Structure):
     """rt_aov: channel pointers (host or device), None = channel not wanted."""
     _fields_ = [("albedo", C.c_void_p), ("normal", C.c_void_p), ("position", C.c_void_p), ("depth", C.c_void_p),
@@ -262,7 +290,7 @@ AMD_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_create", "rt_destroy", "rt
                "rt_bvh_export", "rt_bvh_build_host", "rt_bvh_check_host", "rt_bvh_top_check_host", "rt_bvh_tune", "rt_profile_reset", "rt_profile_collect", "rt_test_unit",
                "rt_trace_stream_device", "rt_build_photon_map", "rt_get_photons", "rt_test_kd_order", "rt_owned_granules", "rt_pack_owned_device", "rt_unpack_owned_device", "rt_group_create", "rt_group_destroy",
                "rt_group_size", "rt_group_uses_rccl", "rt_group_ctx", "rt_group_set_photons", "rt_group_render",
-               "rt_update", "rt_update_vertices_device", "rt_group_update", "rt_render_aov", "rt_render_aov_device",
+               "rt_update", "rt_update_vertices_device", "rt_update_transforms", "rt_group_update", "rt_render_aov", "rt_render_aov_device",
                "rt_denoise", "rt_denoise_device", "rt_render_adaptive", "rt_render_adaptive_device", "rt_render_views",
                "rt_render_views_device", "rt_render_motion", "rt_render_motion_device", "rt_temporal_accumulate",
                "rt_temporal_accumulate_device", "rt_svgf", "rt_svgf_device"]
@@ -340,6 +368,7 @@ def amd():
         L.rt_group_render.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         L.rt_update.argtypes = [C.c_void_p, C.POINTER(SceneUpdate), C.POINTER(UpdateReport)]
         L.rt_update_vertices_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(UpdateReport)]
+        L.rt_update_transforms.argtypes = [C.c_void_p, C.POINTER(TransformUpdate), C.c_void_p, C.POINTER(UpdateReport)]
         L.rt_group_update.argtypes = [C.c_void_p, C.POINTER(SceneUpdate), C.POINTER(UpdateReport)]
         L.rt_render_aov.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Aov)]
         L.rt_render_aov_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Aov), C.c_void_p]
@@ -574,6 +603,21 @@ class Context:
         rep = UpdateReport()
         _check(amd().rt_update_vertices_device(self._h, C.c_void_p(d_pos or None), C.c_void_p(d_nrm or None),
                                                C.c_void_p(stream or None), C.byref(rep)))
+        return rep.as_dict()
+
+    def update_transforms(self, transforms, camera=None, lights=None, d_prev_pos=None, stream=0):
+        """rt_update_transforms: the rest pose under one record per mesh (make_transforms' array, or anything of its
+        layout), computed on the device; camera / lights as update's.  d_prev_pos: a device pointer [n_vertices][3] that
+        receives the positions this call replaces (render_motion_device's d_prev_pos), ordered on `stream`.  Returns the
+        report as a dict."""
+        t = np.ascontiguousarray(transforms, TRANSFORM_DTYPE).reshape(-1)
+        u, _keep = _scene_update(None, None, camera, lights, None)
+        x = TransformUpdate()
+        x.transforms = C.cast(t.ctypes.data, C.POINTER(MeshTransform))
+        x.n_meshes, x.n_lights, x.camera, x.lights = len(t), u.n_lights, u.camera, u.lights
+        x.d_prev_pos = int(d_prev_pos) if d_prev_pos else None
+        rep = UpdateReport()
+        _check(amd().rt_update_transforms(self._h, C.byref(x), C.c_void_p(stream or None), C.byref(rep)))
         return rep.as_dict()
 
     def bvh_export(self):
