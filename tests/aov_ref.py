@@ -91,10 +91,59 @@ def default_sigma_position(scene):
     return float(np.float32(SIGMA_POSITION_SCALE) * np.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]))
 
 
-def atrous(rgb, sums, iterations=0, sigma_color=0., sigma_normal=0., sigma_position=0., scene=None):
+def _sq3(a, b):
+    d = a - b
+    return (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+
+
+def _atrous_f32(rgb, sums, iterations, sigma_color, sigma_normal, sigma_position):
+    """atrous with every operation in float32 in k_dn_iter's order: the taps row by row, the three terms of the exponent
+    summed left to right, one exp per tap, the sums running in tap order."""
+    f = np.float32
+    rgb = np.asarray(rgb, f)
+    hits = np.asarray(sums["hits"])
+    valid = hits > 0
+    fh = np.maximum(hits, 1).astype(f)[..., None]
+    n = (np.asarray(sums["normal"], f) / fh).astype(f)
+    x = (np.asarray(sums["position"], f) / fh).astype(f)
+    fac = np.maximum(np.asarray(sums["albedo"], f) / fh, f(1e-3)).astype(f)
+    c = np.where(valid[..., None], rgb / fac, rgb).astype(f)
+    h, w = hits.shape
+    ys, xs = np.arange(h), np.arange(w)
+    isn, isx = f(1) / (f(sigma_normal) * f(sigma_normal)), f(1) / (f(sigma_position) * f(sigma_position))
+    for i in range(iterations):
+        s = 1 << i
+        sc = f(sigma_color) * f(2.0 ** -i)
+        isc = f(1) / (sc * sc)
+        num, den = np.zeros((h, w, 3), f), np.zeros((h, w), f)
+        for dy in range(-2, 3):
+            qy = ys + dy * s
+            iny = (qy >= 0) & (qy < h)
+            qy = np.clip(qy, 0, h - 1)
+            for dx in range(-2, 3):
+                qx = xs + dx * s
+                inx = (qx >= 0) & (qx < w)
+                qx = np.clip(qx, 0, w - 1)
+                ok = iny[:, None] & inx[None, :] & valid[qy][:, qx]
+                cq = c[qy][:, qx]
+                with np.errstate(over="ignore", invalid="ignore"):
+                    e = (_sq3(c, cq) * isc + _sq3(n, n[qy][:, qx]) * isn) + _sq3(x, x[qy][:, qx]) * isx
+                    wt = np.where(ok, (f(H5[dx + 2]) * f(H5[dy + 2])) * np.exp(-e), f(0)).astype(f)
+                num += wt[..., None] * cq
+                den += wt
+        with np.errstate(divide="ignore", invalid="ignore"):
+            c = np.where(valid[..., None], num / den[..., None], c).astype(f)
+    return np.where(valid[..., None], c * fac, rgb).astype(f)
+
+
+def atrous(rgb, sums, iterations=0, sigma_color=0., sigma_normal=0., sigma_position=0., scene=None, f32=False):
     """The filter of rt_denoise on a resolved frame rgb [h][w][3] and rt_render_aov's sums (0 = the defaults; the default
-    sigma_position needs the scene)."""
+    sigma_position needs the scene).  f32: every operation in float32 in k_dn_iter's order, the exponent summed as the
+    kernel sums it, with one exp; otherwise float64 with the three exponentials apart."""
     iterations = iterations or ITERATIONS
+    if f32:
+        return _atrous_f32(rgb, sums, iterations, sigma_color or SIGMA_COLOR, sigma_normal or SIGMA_NORMAL,
+                           sigma_position or default_sigma_position(scene))
     sc, sn = sigma_color or SIGMA_COLOR, sigma_normal or SIGMA_NORMAL
     sx = sigma_position or default_sigma_position(scene)
     rgb = np.asarray(rgb, np.float32)

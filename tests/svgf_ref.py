@@ -68,6 +68,7 @@ def stage_a(cur_rgb, sums, cur, prev, max_history=0, alpha_min=0., alpha_min_mom
     W, SL, S = np.zeros((h, w)), np.zeros((h, w)), np.zeros((h, w, 5))
     info = dict(miss=int(miss.sum()), nonfinite=int(nonfinite.sum()), outside=int(outside.sum()), tap_mesh=0, tap_position=0,
                 tap_nolength=0)
+    info.update(tr.edge_counts(cand, rx, x0, ax, ay, w))
     h5 = np.concatenate([np.asarray(prev["color"], np.float32), np.asarray(prev["moments"], np.float32)], axis=-1)
     hpos = np.asarray(prev["position"], np.float32)
     hmesh, hlen = np.asarray(prev["mesh"], np.uint32), np.asarray(prev["length"], np.float32)
@@ -82,8 +83,10 @@ def stage_a(cur_rgb, sums, cur, prev, max_history=0, alpha_min=0., alpha_min_mom
         meshok = hmesh[yc, xc] == mesh
         dd = hpos[yc, xc].astype(np.float64) - X
         with np.errstate(invalid="ignore", over="ignore"):
-            posok = (dd[..., 0] * dd[..., 0] + dd[..., 1] * dd[..., 1]) + dd[..., 2] * dd[..., 2] <= s2
+            d2 = (dd[..., 0] * dd[..., 0] + dd[..., 1] * dd[..., 1]) + dd[..., 2] * dd[..., 2]
+            posok = d2 <= s2
         ok = base & haslen & meshok & posok
+        info["position_on_sigma"] += int((ok & (d2 == s2)).sum())
         info["tap_nolength"] += int((base & ~haslen).sum())
         info["tap_mesh"] += int((base & haslen & ~meshok).sum())
         info["tap_position"] += int((base & haslen & meshok & ~posok).sum())
@@ -101,7 +104,9 @@ def stage_a(cur_rgb, sums, cur, prev, max_history=0, alpha_min=0., alpha_min_mom
         info.update(no_weight=int((cand & ~hist).sum()), history=int(hist.sum()), saturated=int((hist & (L + 1.0 > maxh)).sum()),
                     alpha_bound=int((hist & (amin > 1.0 / Ln)).sum()), alpha_moments_bound=int((hist & (aminm > 1.0 / Ln)).sum()))
     info.update(invalid=int((~valid).sum()), window=int((valid & (length < LONG_HISTORY)).sum()),
-                long_history=int((valid & (length >= LONG_HISTORY)).sum()))
+                long_history=int((valid & (length >= LONG_HISTORY)).sum()),
+                length_exactly_long=int((valid & hist & (length == np.float32(LONG_HISTORY))).sum()),
+                length_just_short=int((valid & hist & (length == np.nextafter(np.float32(LONG_HISTORY), np.float32(0)))).sum()))
     return dict(fac=fac, valid=valid, accum=np.ascontiguousarray(out5[..., :3]), moments=np.ascontiguousarray(out5[..., 3:]),
                 length=length, info=info)
 
@@ -117,7 +122,10 @@ def _shift(a, qy, qx):
 
 def filter_stages(A, sums, iterations=0, sigma_luminance=0., sigma_normal=0., sigma_position=0., scene=None, f32=False):
     """Stages B and C on stage_a's result A: dict of rgb, color [h][w][3], variance [h][w] (float32) and variance0 (stage
-    B's).  f32: every operation in float32 in the device's order; otherwise float64."""
+    B's).  f32: every operation in float32 in the device's order; otherwise float64.  filter_info counts the edges the
+    frame met: isolated_valid (valid pixels whose 3x3 neighbourhood holds no other valid pixel: gk == 0.25),
+    zero_variance_centre (valid pixels whose pre-filtered variance is 0 in the first iteration: den == 1e-4) and
+    far_tap_in_range[step] (the taps other than the centre that are accepted at that step)."""
     ft = np.float32 if f32 else np.float64
     iterations = iterations or ITERATIONS
     sl = ft(np.float32(sigma_luminance or SIGMA_LUMINANCE))
@@ -165,6 +173,7 @@ def filter_stages(A, sums, iterations=0, sigma_luminance=0., sigma_normal=0., si
     # stage C
     c = A["accum"].astype(ft)
     color = None
+    finfo = dict(isolated_valid=0, zero_variance_centre=0, far_tap_in_range={})
     for it in range(iterations):
         s = 1 << it
         sg, sk = np.zeros((h, w), ft), np.zeros((h, w), ft)
@@ -174,6 +183,9 @@ def filter_stages(A, sums, iterations=0, sigma_luminance=0., sigma_normal=0., si
             sk += np.where(ok, k, zero)
         with np.errstate(divide="ignore", invalid="ignore"):
             den = sl * np.sqrt(sg / sk) + ft(1e-4)
+        if it == 0:
+            finfo.update(isolated_valid=int((valid & (sk == ft(0.25))).sum()), zero_variance_centre=int((valid & (sg == zero)).sum()))
+        far = 0
         lp = luminance(c)
         num, nv, sw = np.zeros((h, w, 3), ft), np.zeros((h, w), ft), np.zeros((h, w), ft)
         for dy, dx, qy, qx, ok in taps(2, s):
@@ -181,16 +193,18 @@ def filter_stages(A, sums, iterations=0, sigma_luminance=0., sigma_normal=0., si
             with np.errstate(over="ignore", invalid="ignore"):
                 e = (_sq3(n, _shift(n, qy, qx)) * isn + _sq3(x, _shift(x, qy, qx)) * isx) + np.abs(lp - luminance(cq)) / den
                 wt = np.where(ok, ft(H5[dx + 2] * H5[dy + 2]) * np.exp(-e), zero).astype(ft)
+            far += int((ok & valid).sum()) if (dy or dx) else 0
             num += wt[..., None] * cq
             nv += (wt * wt) * _shift(var, qy, qx)
             sw += wt
         with np.errstate(divide="ignore", invalid="ignore"):
             c = np.where(valid[..., None], num / sw[..., None], c).astype(ft)
             var = np.where(valid, nv / (sw * sw), var).astype(ft)
+        finfo["far_tap_in_range"][s] = far
         if it == 0:
             color = c.astype(np.float32)
     rgb = (c * A["fac"].astype(ft)).astype(np.float32)
-    return dict(rgb=rgb, color=color, variance=var.astype(np.float32), variance0=variance0)
+    return dict(rgb=rgb, color=color, variance=var.astype(np.float32), variance0=variance0, filter_info=finfo)
 
 
 def svgf_ref(cur_rgb, sums, cur, prev, iterations=0, max_history=0, alpha_min=0., alpha_min_moments=0., sigma_luminance=0.,
@@ -282,5 +296,9 @@ def measure_tolerance(seq, **kw):
     return T, seen
 
 
+# the exact comparison edges of the rule, counted by stage_a (EDGES) and by filter_stages (FILTER_EDGES, in filter_info);
+# tests/filter_cases.py constructs every one of them
+EDGES = tr.EDGES + ("length_exactly_long", "length_just_short")
+FILTER_EDGES = ("isolated_valid", "zero_variance_centre", "far_tap_in_range")
 BRANCHES = ("miss", "nonfinite", "outside", "no_weight", "tap_mesh", "tap_position", "tap_nolength", "history", "saturated",
             "alpha_bound", "alpha_moments_bound", "invalid", "window", "long_history")

@@ -86,6 +86,18 @@ def default_sigma_position(scene):
     return np.float32(SIGMA_POSITION_SCALE) * np.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2])
 
 
+# the exact comparison edges of the reprojection (rt_svgf's stage A counts the same ones)
+EDGES = ("rx_minus_one", "last_column_tap_outside", "single_tap", "position_on_sigma")
+
+
+def edge_counts(cand, rx, x0, ax, ay, w):
+    """Counts of the reprojected pixels on the rule's edges: rx == -1 (the tap of weight 1 lies outside: no weight),
+    x0 == w - 1 with a fraction (the right-hand taps lie outside, rx == nextafter(w, 0) among them), and a whole-pixel
+    position (one tap of weight 1, rx == w - 1 among them); position_on_sigma counts the taps at d^2 == sigma^2."""
+    return dict(rx_minus_one=int((cand & (rx == -1.0)).sum()), last_column_tap_outside=int((cand & (x0 == w - 1) & (ax > 0)).sum()),
+                single_tap=int((cand & (ax == 0) & (ay == 0)).sum()), position_on_sigma=0)
+
+
 def accumulate_ref(cur_rgb, cur, prev, max_history=0, alpha_min=0., sigma_position=0., scene=None):
     """rt_temporal_accumulate: (out_rgb [h][w][3], out_length [h][w], info).  cur: motion, prev_position, mesh; prev: rgb,
     position, mesh, length; 0 = the defaults (the default sigma_position needs the CURRENT scene).  info counts the
@@ -114,6 +126,7 @@ def accumulate_ref(cur_rgb, cur, prev, max_history=0, alpha_min=0., sigma_positi
     W, SL, S = np.zeros((h, w)), np.zeros((h, w)), np.zeros((h, w, 3))
     info = dict(miss=int(miss.sum()), nonfinite=int(nonfinite.sum()), outside=int(outside.sum()), tap_mesh=0, tap_position=0,
                 tap_nolength=0)
+    info.update(edge_counts(cand, rx, x0, ax, ay, w))
     hrgb, hpos = np.asarray(prev["rgb"], np.float32), np.asarray(prev["position"], np.float32)
     hmesh, hlen = np.asarray(prev["mesh"], np.uint32), np.asarray(prev["length"], np.float32)
     for i, j in TAPS:
@@ -127,8 +140,10 @@ def accumulate_ref(cur_rgb, cur, prev, max_history=0, alpha_min=0., sigma_positi
         meshok = hmesh[yc, xc] == mesh
         d = hpos[yc, xc].astype(np.float64) - X
         with np.errstate(invalid="ignore", over="ignore"):
-            posok = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2] <= s2
+            d2 = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+            posok = d2 <= s2
         ok = base & haslen & meshok & posok
+        info["position_on_sigma"] += int((ok & (d2 == s2)).sum())
         info["tap_nolength"] += int((base & ~haslen).sum())
         info["tap_mesh"] += int((base & haslen & ~meshok).sum())
         info["tap_position"] += int((base & haslen & meshok & ~posok).sum())
