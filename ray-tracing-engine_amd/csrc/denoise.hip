@@ -1,24 +1,24 @@
 // denoise.hip — the edge-avoiding a-trous wavelet filter (Dammertz et al., HPG 2010) guided by the first-hit AOVs of
 // rt_render_aov, with albedo demodulation: rt_denoise.  DESIGN.md "AOVs and the a-trous denoiser" defines it; every
-// kernel here is one lane per pixel.
+// kernel here is one lane per pixel.  The first two serve all three filters (filters.h).
 //
-//   k_dn_extent  bounding box of the vertices the triangles reference (only when the caller leaves sigma_position 0)
-//   k_dn_sigma   1 / sigma_position^2 into device memory (default: 2 % of that box's diagonal), read by every iteration
-//   k_dn_pack    per pixel the guides as two float4 (normal + validity flag, position), the albedo factor
-//                max(albedo / hits, 1e-3) and the demodulated colour rgb / factor (pixels without a hit: rgb itself)
-//   k_dn_iter    one iteration (step 2^i): 5x5 taps straight from global memory through L1 / L2; the last one
-//                multiplies the factor back and writes the [h][w][3] output
+//   k_ref_extent     bounding box of the vertices the triangles reference (only when a caller leaves a sigma 0)
+//   k_filter_sigmas  1 / sigma_position^2 (float) and the tap acceptance's sigma^2 (double) into the filter's block: the
+//                    caller's sigmas, or a fraction of that box's diagonal (the denoiser: 2 %)
+//   k_dn_pack        per pixel the guides, the albedo factor and the demodulated colour (filters_device.h demodulate)
+//   k_dn_iter        one iteration (step 2^i): 5x5 taps straight from global memory through L1 / L2; the last one
+//                    multiplies the factor back and writes the [h][w][3] output
 #include <hip/hip_runtime.h>
 
 #include <math.h>
 
-#include "rt_kernels.h"
+#include "filters_device.h"
 
 namespace rtk {
 namespace {
 
 // ext[0..2] = min x, y, z (initialised to 0xffffffff), ext[3..5] = max (initialised to 0)
-__global__ __launch_bounds__(256) void k_dn_extent(const float* __restrict__ vpos, const uint4* __restrict__ triShade,
+__global__ __launch_bounds__(256) void k_ref_extent(const float* __restrict__ vpos, const uint4* __restrict__ triShade,
                                                    uint32_t nTris, uint32_t* __restrict__ ext) {
   float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
   for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < nTris; t += gridDim.x * blockDim.x) {
@@ -36,13 +36,17 @@ __global__ __launch_bounds__(256) void k_dn_extent(const float* __restrict__ vpo
     for (int a = 0; a < 3; a++) atomicMin(&ext[a], f2o(lo[a])), atomicMax(&ext[3 + a], f2o(hi[a]));
 }
 
-__global__ void k_dn_sigma(const uint32_t* __restrict__ ext, float sigma, float* __restrict__ isx) {
-  if (sigma <= 0.f) {
+__global__ void k_filter_sigmas(FilterBlock* __restrict__ blk, float sigmaPos, float sigmaRep, float scale) {
+  if (sigmaPos <= 0.f || sigmaRep <= 0.f) {
+    const uint32_t* ext = blk->ext;
     const float dx = o2f(ext[3]) - o2f(ext[0]), dy = o2f(ext[4]) - o2f(ext[1]), dz = o2f(ext[5]) - o2f(ext[2]);
-    sigma = 0.02f * sqrtf((dx * dx + dy * dy) + dz * dz);
+    float sigma = scale * sqrtf((dx * dx + dy * dy) + dz * dz);
     if (!(sigma > 0.f) || !(sigma < INFINITY)) sigma = 1.f;  // (a flat or empty scene: any scale does)
+    if (sigmaPos <= 0.f) sigmaPos = sigma;
+    if (sigmaRep <= 0.f) sigmaRep = sigma;
   }
-  *isx = 1.f / (sigma * sigma);
+  blk->isx = 1.f / (sigmaPos * sigmaPos);
+  blk->s2 = (double)sigmaRep * (double)sigmaRep;
 }
 
 __global__ __launch_bounds__(256) void k_dn_pack(uint32_t n, const float* __restrict__ rgb, const float* __restrict__ alb,
@@ -51,25 +55,8 @@ __global__ __launch_bounds__(256) void k_dn_pack(uint32_t n, const float* __rest
                                                  float4* __restrict__ g1, float4* __restrict__ fac, float4* __restrict__ col) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const size_t i3 = 3 * (size_t)i;
-  const float r = rgb[i3], g = rgb[i3 + 1], b = rgb[i3 + 2];
-  const uint32_t h = hits[i];
-  if (h == 0) {  // passes through, weight 0 as a tap
-    g0[i] = make_float4(0.f, 0.f, 0.f, 0.f), g1[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    fac[i] = make_float4(1.f, 1.f, 1.f, 0.f), col[i] = make_float4(r, g, b, 0.f);
-    return;
-  }
-  const float fh = (float)h;
-  const float ax = fmaxf(alb[i3] / fh, 1e-3f), ay = fmaxf(alb[i3 + 1] / fh, 1e-3f), az = fmaxf(alb[i3 + 2] / fh, 1e-3f);
-  g0[i] = make_float4(nrm[i3] / fh, nrm[i3 + 1] / fh, nrm[i3 + 2] / fh, 1.f);
-  g1[i] = make_float4(pos[i3] / fh, pos[i3 + 1] / fh, pos[i3 + 2] / fh, 0.f);
-  fac[i] = make_float4(ax, ay, az, 0.f);
-  col[i] = make_float4(r / ax, g / ay, b / az, 0.f);
-}
-
-__device__ __forceinline__ float sq3(float4 a, float4 b) {
-  const float x = a.x - b.x, y = a.y - b.y, z = a.z - b.z;
-  return (x * x + y * y) + z * z;
+  const Demodulated d = demodulate(i, rgb, alb, nrm, pos, hits[i]);
+  g0[i] = d.g0, g1[i] = d.g1, fac[i] = d.fac, col[i] = make_float4(d.r, d.g, d.b, 0.f);
 }
 
 // 16x16 pixels per workgroup (four waves of 16x4)
@@ -86,7 +73,6 @@ __global__ __launch_bounds__(256) void k_dn_iter(uint32_t W, uint32_t H, int ste
   if (np.w != 0.f) {
     const float4 xp = g1[p];
     const float isx = *isxp;
-    const float kh[5] = {1.f / 16.f, 1.f / 4.f, 3.f / 8.f, 1.f / 4.f, 1.f / 16.f};
     float sr = 0.f, sg = 0.f, sb = 0.f, sw = 0.f;
     for (int j = 0; j < 5; j++) {
       const int yy = y + (j - 2) * step;
@@ -98,7 +84,7 @@ __global__ __launch_bounds__(256) void k_dn_iter(uint32_t W, uint32_t H, int ste
         const float4 nq = g0[q];
         if (nq.w == 0.f) continue;
         const float4 cq = cin[q], xq = g1[q];
-        const float w = kh[i] * kh[j] * expf(-(sq3(cp, cq) * isc + sq3(np, nq) * isn + sq3(xp, xq) * isx));
+        const float w = atrous5(i) * atrous5(j) * expf(-(sq3(cp, cq) * isc + sq3(np, nq) * isn + sq3(xp, xq) * isx));
         sr += w * cq.x, sg += w * cq.y, sb += w * cq.z, sw += w;
       }
     }
@@ -121,32 +107,36 @@ hipError_t launch_ref_extent(const DevScene& S, uint32_t* ext, hipStream_t strea
   if ((e = hipMemsetAsync(ext, 0xff, 3 * sizeof(uint32_t), stream)) != hipSuccess) return e;
   if ((e = hipMemsetAsync(ext + 3, 0, 3 * sizeof(uint32_t), stream)) != hipSuccess) return e;
   const uint32_t blocks = S.n_tris ? (S.n_tris + 255u) / 256u < 1024u ? (S.n_tris + 255u) / 256u : 1024u : 1u;
-  hipLaunchKernelGGL(k_dn_extent, dim3(blocks), dim3(256), 0, stream, S.vpos, S.triShade, S.n_tris, ext);
+  hipLaunchKernelGGL(k_ref_extent, dim3(blocks), dim3(256), 0, stream, S.vpos, S.triShade, S.n_tris, ext);
+  return hipGetLastError();
+}
+
+hipError_t launch_filter_sigmas(const DevScene& S, FilterBlock* block, float sigmaPos, float sigmaRep, float scale, hipStream_t stream) {
+  if (sigmaPos <= 0.f || sigmaRep <= 0.f) {
+    const hipError_t e = launch_ref_extent(S, block->ext, stream);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(k_filter_sigmas, dim3(1), dim3(1), 0, stream, block, sigmaPos, sigmaRep, scale);
   return hipGetLastError();
 }
 
 hipError_t launch_denoise(const DevScene& S, const DenoiseArgs& D, hipStream_t stream) {
   const size_t n = (size_t)D.width * D.height;
   if (n == 0) return hipSuccess;
-  float4 *g0 = D.scratch, *g1 = g0 + n, *fac = g1 + n, *ca = fac + n, *cb = ca + n;
-  uint32_t* ext = reinterpret_cast<uint32_t*>(cb + n);  // 6 words, then 1 / sigma_position^2
-  float* isx = reinterpret_cast<float*>(ext + 8);
-  hipError_t e;
-  if (D.sigma_position <= 0.f) {
-    if ((e = launch_ref_extent(S, ext, stream)) != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(k_dn_sigma, dim3(1), dim3(1), 0, stream, ext, D.sigma_position, isx);
+  FilterScratch s = carve_filter_scratch(D.scratch, n);
+  const hipError_t e = launch_filter_sigmas(S, s.block, D.sigma_position, D.sigma_position, 0.02f, stream);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_dn_pack, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, (uint32_t)n, D.rgb, D.albedo, D.normal,
-                     D.position, D.hits, g0, g1, fac, ca);
+                     D.position, D.hits, s.g0, s.g1, s.fac, s.ca);
   const dim3 grid((D.width + 15u) / 16u, (D.height + 15u) / 16u);
   const float isn = 1.f / (D.sigma_normal * D.sigma_normal);
   for (uint32_t it = 0; it < D.iterations; it++) {
     const float sc = D.sigma_color * ldexpf(1.f, -(int)it);  // the colour sigma halves every iteration
     const bool last = it + 1 == D.iterations;
-    hipLaunchKernelGGL(k_dn_iter, grid, dim3(256), 0, stream, D.width, D.height, 1 << it, 1.f / (sc * sc), isn, isx, g0, g1, fac,
-                       ca, cb, last ? D.out : nullptr);
-    float4* t = ca;
-    ca = cb, cb = t;
+    hipLaunchKernelGGL(k_dn_iter, grid, dim3(256), 0, stream, D.width, D.height, 1 << it, 1.f / (sc * sc), isn, &s.block->isx, s.g0,
+                       s.g1, s.fac, s.ca, s.cb, last ? D.out : nullptr);
+    float4* t = s.ca;
+    s.ca = s.cb, s.cb = t;
   }
   return hipGetLastError();
 }

@@ -17,15 +17,16 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <thread>
 #include <type_traits>
 #include <vector>
 
 #include "bvh_build.h"
+#include "filters.h"
 #include "rt_amd.h"
 #include "rt_kernels.h"
-#include "svgf.h"
 
 namespace {
 
@@ -191,13 +192,14 @@ struct rt_ctx {
   DevBuf<float> restPos, restNrm;
   bool restValid = false;
   DevBuf<rt_mesh_transform> xfTable;
-  // scratch of rt_denoise_device (guides, albedo factors, two colour buffers; grows on demand)
+  // scratch of rt_denoise_device and rt_svgf_device (rtk::filter_scratch; grows on demand: ensure_filter_scratch)
   DevBuf<float4> dnScratch;
   size_t dnCap = 0;
   // scratch of the motion pass and the temporal accumulation (allocated on first use): last frame's positions as the
-  // host form of rt_render_motion uploads them, and rtk::temporal_scratch_words words for the default sigma_position
+  // host form of rt_render_motion uploads them, and the accumulation's own block for its sigma_position (not a part of
+  // dnScratch: the accumulation and the denoiser may run on different streams)
   DevBuf<float> mvPrev;
-  DevBuf<uint32_t> tpScratch;
+  DevBuf<rtk::FilterBlock> tpScratch;
   // scratch of rt_render_adaptive_device (moments, granule state and lists, tile list, counts; grows on demand)
   DevBuf<char> adScratch;
   size_t adCap = 0;
@@ -2091,6 +2093,85 @@ namespace {
 constexpr uint32_t kDenoiseIterations = 5;
 constexpr float kDenoiseSigmaColor = 2.f, kDenoiseSigmaNormal = 0.5f;
 
+// Device copies of a host form's buffers, freed with the scope: in() uploads an input, out() makes room for an output
+// the caller asked for (null otherwise), download() copies every such output back.  After a failure in() and out()
+// answer null and rc holds what the entry point returns; it is looked at once, after the last of them.
+struct Staging {
+  struct Out {
+    void* host;
+    const void* dev;
+    size_t bytes;
+  };
+  std::vector<DevBuf<char>> bufs;
+  std::vector<Out> outs;
+  int rc = RT_OK;
+
+  int stage(void** d, const void* src, size_t bytes) {
+    DevBuf<char> b;
+    HIP_TRY(dev_alloc(&b, bytes));
+    if (src) HIP_TRY(hipMemcpy(b.get(), src, bytes, hipMemcpyHostToDevice));
+    *d = b.get();
+    bufs.push_back(std::move(b));
+    return RT_OK;
+  }
+  template <class T>
+  T* in(const T* host, size_t count) {
+    void* d = nullptr;
+    if (rc == RT_OK) rc = stage(&d, host, count * sizeof(T));
+    return static_cast<T*>(d);
+  }
+  template <class T>
+  T* out(T* host, size_t count) {
+    void* d = nullptr;
+    if (host && rc == RT_OK) rc = stage(&d, nullptr, count * sizeof(T));
+    if (d) outs.push_back({host, d, count * sizeof(T)});
+    return static_cast<T*>(d);
+  }
+  int download() {
+    for (const Out& o : outs) HIP_TRY(hipMemcpy(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost));
+    return RT_OK;
+  }
+};
+
+// checks the three filters share (the texts are part of what the callers see)
+int check_image_size(uint32_t w, uint32_t h) {
+  return w == 0 || h == 0 || w > 65535u || h > 65535u ? fail(RT_ERR_INVALID, "image size %ux%u out of range", w, h) : RT_OK;
+}
+int check_sigmas(std::initializer_list<float> sigmas) {
+  for (float s : sigmas)
+    if (!(s >= 0.f) || !std::isfinite(s)) return fail(RT_ERR_INVALID, "sigmas must be finite and >= 0");
+  return RT_OK;
+}
+int check_aov_channels(const rt_aov* aov, const char* who) {
+  return aov->albedo && aov->normal && aov->position && aov->hits
+             ? RT_OK
+             : fail(RT_ERR_INVALID, "the %s needs the albedo, normal, position and hits channels", who);
+}
+int check_motion_channels(const rt_motion* cur) {
+  return cur->motion && cur->prev_position && cur->mesh
+             ? RT_OK
+             : fail(RT_ERR_INVALID, "the current frame needs the motion, prev_position and mesh channels");
+}
+int check_not_broken(const rt_ctx* c) {
+  return c->broken ? fail(RT_ERR_STATE, "the context's device tree is in an unknown state: destroy it") : RT_OK;
+}
+
+// Everything rt_denoise and rt_denoise_device check before they look at the context.
+int denoise_checks(const rt_ctx* c, const rt_denoise_params* d, const void* rgb, const rt_aov* aov, const void* out) {
+  if (!c || !d || !rgb || !aov || !out) return fail(RT_ERR_INVALID, "null argument");
+  return check_aov_channels(aov, "denoiser");
+}
+
+// c->dnScratch with room for `need` float4 (rt_denoise_device and rt_svgf_device: one call at a time)
+int ensure_filter_scratch(rt_ctx* c, size_t need) {
+  if (need <= c->dnCap) return RT_OK;
+  c->dnCap = 0;
+  if (c->dnScratch) HIP_TRY(hipFree(c->dnScratch.release()));
+  HIP_TRY(dev_alloc(&c->dnScratch, need));
+  c->dnCap = need;
+  return RT_OK;
+}
+
 // rt_render_aov's own view of p: the fields that do not affect the pass are neutralised before rt_render's checks
 int aov_checks(const rt_ctx* c, const rt_params* p, rt_params* q) {
   if (!c) return fail(RT_ERR_INVALID, "ctx is null");
@@ -2131,45 +2212,24 @@ int rt_render_aov(rt_ctx* c, const rt_params* p, const rt_aov* out) {
   if (!out) return fail(RT_ERR_INVALID, "aov is null");
   HIP_TRY(hipSetDevice(c->device));
   const size_t npx = (size_t)q.width * q.height;
-  DevBuf<float> dF[4];
-  DevBuf<uint32_t> dU[3];
-  float* const hF[4] = {out->albedo, out->normal, out->position, out->depth};
-  uint32_t* const hU[3] = {out->hits, out->mesh, out->tri};
-  const size_t wF[4] = {3, 3, 3, 1};
-  for (int i = 0; i < 4; ++i)
-    if (hF[i]) HIP_TRY(dev_alloc(&dF[i], npx * wF[i]));
-  for (int i = 0; i < 3; ++i)
-    if (hU[i]) HIP_TRY(dev_alloc(&dU[i], npx));
+  Staging st;
   rt_aov d = {};
-  d.albedo = dF[0].get(), d.normal = dF[1].get(), d.position = dF[2].get(), d.depth = dF[3].get();
-  d.hits = dU[0].get(), d.mesh = dU[1].get(), d.tri = dU[2].get();
+  d.albedo = st.out(out->albedo, 3 * npx), d.normal = st.out(out->normal, 3 * npx), d.position = st.out(out->position, 3 * npx);
+  d.depth = st.out(out->depth, npx), d.hits = st.out(out->hits, npx), d.mesh = st.out(out->mesh, npx), d.tri = st.out(out->tri, npx);
+  if (st.rc != RT_OK) return st.rc;
   if ((rc = rt_render_aov_device(c, &q, &d, nullptr)) != RT_OK) return rc;
-  for (int i = 0; i < 4; ++i)
-    if (hF[i]) HIP_TRY(hipMemcpy(hF[i], dF[i].get(), npx * wF[i] * sizeof(float), hipMemcpyDeviceToHost));
-  for (int i = 0; i < 3; ++i)
-    if (hU[i]) HIP_TRY(hipMemcpy(hU[i], dU[i].get(), npx * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  return RT_OK;
+  return st.download();
 }
 
 int rt_denoise_device(rt_ctx* c, const rt_denoise_params* d, const void* d_rgb, const rt_aov* aov, void* d_out, void* stream) {
-  if (!c || !d || !d_rgb || !aov || !d_out) return fail(RT_ERR_INVALID, "null argument");
-  if (!aov->albedo || !aov->normal || !aov->position || !aov->hits)
-    return fail(RT_ERR_INVALID, "the denoiser needs the albedo, normal, position and hits channels");
-  if (c->broken) return fail(RT_ERR_STATE, "the context's device tree is in an unknown state: destroy it");
-  if (d->width == 0 || d->height == 0 || d->width > 65535u || d->height > 65535u)
-    return fail(RT_ERR_INVALID, "image size %ux%u out of range", d->width, d->height);
+  int rc = denoise_checks(c, d, d_rgb, aov, d_out);
+  if (rc != RT_OK) return rc;
+  if ((rc = check_not_broken(c)) != RT_OK) return rc;
+  if ((rc = check_image_size(d->width, d->height)) != RT_OK) return rc;
   if (d->iterations > 8) return fail(RT_ERR_INVALID, "iterations %u > 8", d->iterations);
-  const float sg[3] = {d->sigma_color, d->sigma_normal, d->sigma_position};
-  for (float s : sg)
-    if (!(s >= 0.f) || !std::isfinite(s)) return fail(RT_ERR_INVALID, "sigmas must be finite and >= 0");
+  if ((rc = check_sigmas({d->sigma_color, d->sigma_normal, d->sigma_position})) != RT_OK) return rc;
   HIP_TRY(hipSetDevice(c->device));
-  const size_t need = rtk::denoise_scratch(d->width, d->height);
-  if (need > c->dnCap) {
-    c->dnCap = 0;
-    if (c->dnScratch) HIP_TRY(hipFree(c->dnScratch.release()));
-    HIP_TRY(dev_alloc(&c->dnScratch, need));
-    c->dnCap = need;
-  }
+  if ((rc = ensure_filter_scratch(c, rtk::filter_scratch(d->width, d->height))) != RT_OK) return rc;
   rtk::DenoiseArgs D;
   D.width = d->width, D.height = d->height;
   D.iterations = d->iterations ? d->iterations : kDenoiseIterations;
@@ -2184,32 +2244,20 @@ int rt_denoise_device(rt_ctx* c, const rt_denoise_params* d, const void* d_rgb, 
 }
 
 int rt_denoise(rt_ctx* c, const rt_denoise_params* d, const float* rgb, const rt_aov* aov, float* out) {
-  if (!c || !d || !rgb || !aov || !out) return fail(RT_ERR_INVALID, "null argument");
-  if (!aov->albedo || !aov->normal || !aov->position || !aov->hits)
-    return fail(RT_ERR_INVALID, "the denoiser needs the albedo, normal, position and hits channels");
-  if (d->width == 0 || d->height == 0 || d->width > 65535u || d->height > 65535u)
-    return fail(RT_ERR_INVALID, "image size %ux%u out of range", d->width, d->height);
+  int rc = denoise_checks(c, d, rgb, aov, out);
+  if (rc != RT_OK) return rc;
+  if ((rc = check_image_size(d->width, d->height)) != RT_OK) return rc;
   HIP_TRY(hipSetDevice(c->device));
   const size_t npx = (size_t)d->width * d->height;
-  DevBuf<float> dRgb, dAlb, dNrm, dPos, dOut;
-  DevBuf<uint32_t> dHits;
-  HIP_TRY(dev_alloc(&dRgb, 3 * npx));
-  HIP_TRY(dev_alloc(&dAlb, 3 * npx));
-  HIP_TRY(dev_alloc(&dNrm, 3 * npx));
-  HIP_TRY(dev_alloc(&dPos, 3 * npx));
-  HIP_TRY(dev_alloc(&dOut, 3 * npx));
-  HIP_TRY(dev_alloc(&dHits, npx));
-  HIP_TRY(hipMemcpy(dRgb.get(), rgb, 3 * npx * sizeof(float), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dAlb.get(), aov->albedo, 3 * npx * sizeof(float), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dNrm.get(), aov->normal, 3 * npx * sizeof(float), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dPos.get(), aov->position, 3 * npx * sizeof(float), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dHits.get(), aov->hits, npx * sizeof(uint32_t), hipMemcpyHostToDevice));
+  Staging st;
+  const float* dRgb = st.in(rgb, 3 * npx);
   rt_aov da = {};
-  da.albedo = dAlb.get(), da.normal = dNrm.get(), da.position = dPos.get(), da.hits = dHits.get();
-  int rc = rt_denoise_device(c, d, dRgb.get(), &da, dOut.get(), nullptr);
-  if (rc != RT_OK) return rc;
-  HIP_TRY(hipMemcpy(out, dOut.get(), 3 * npx * sizeof(float), hipMemcpyDeviceToHost));
-  return RT_OK;
+  da.albedo = st.in(aov->albedo, 3 * npx), da.normal = st.in(aov->normal, 3 * npx), da.position = st.in(aov->position, 3 * npx);
+  da.hits = st.in(aov->hits, npx);
+  float* dOut = st.out(out, 3 * npx);
+  if (st.rc != RT_OK) return st.rc;
+  if ((rc = rt_denoise_device(c, d, dRgb, &da, dOut, nullptr)) != RT_OK) return rc;
+  return st.download();
 }
 
 }  // extern "C"
@@ -2259,12 +2307,11 @@ bool overlap(const void* a, size_t na, const void* b, size_t nb) {
 int temporal_checks(const rt_ctx* c, const rt_temporal_params* t, const float* cur_rgb, const rt_motion* cur, const rt_history* prev,
                     const float* out_rgb, const float* out_length) {
   if (!c || !t || !cur_rgb || !cur || !prev || !out_rgb || !out_length) return fail(RT_ERR_INVALID, "null argument");
-  if (!cur->motion || !cur->prev_position || !cur->mesh)
-    return fail(RT_ERR_INVALID, "the current frame needs the motion, prev_position and mesh channels");
+  int rc = check_motion_channels(cur);
+  if (rc != RT_OK) return rc;
   if (!prev->rgb || !prev->position || !prev->mesh || !prev->length)
     return fail(RT_ERR_INVALID, "the history needs rgb, position, mesh and length");
-  if (t->width == 0 || t->height == 0 || t->width > 65535u || t->height > 65535u)
-    return fail(RT_ERR_INVALID, "image size %ux%u out of range", t->width, t->height);
+  if ((rc = check_image_size(t->width, t->height)) != RT_OK) return rc;
   if (!(t->sigma_position >= 0.f) || !std::isfinite(t->sigma_position))
     return fail(RT_ERR_INVALID, "sigma_position must be finite and >= 0");
   if (!(t->alpha_min >= 0.f) || !(t->alpha_min <= 1.f)) return fail(RT_ERR_INVALID, "alpha_min must be 0 or in (0, 1]");
@@ -2303,22 +2350,15 @@ int rt_render_motion(rt_ctx* c, const rt_params* p, const rt_motion_prev* prev, 
     if (!c->mvPrev) HIP_TRY(dev_alloc(&c->mvPrev, nv));
     HIP_TRY(hipMemcpy(c->mvPrev.get(), prev->vertex_pos, nv * sizeof(float), hipMemcpyHostToDevice));
   }
-  DevBuf<float> dF[3];
-  DevBuf<uint32_t> dMesh;
-  float* const hF[3] = {out->motion, out->position, out->prev_position};
-  const size_t wF[3] = {2, 3, 3};
-  for (int i = 0; i < 3; ++i)
-    if (hF[i]) HIP_TRY(dev_alloc(&dF[i], npx * wF[i]));
-  if (out->mesh) HIP_TRY(dev_alloc(&dMesh, npx));
+  Staging st;
   rt_motion d = {};
-  d.motion = dF[0].get(), d.position = dF[1].get(), d.prev_position = dF[2].get(), d.mesh = dMesh.get();
+  d.motion = st.out(out->motion, 2 * npx), d.position = st.out(out->position, 3 * npx);
+  d.prev_position = st.out(out->prev_position, 3 * npx), d.mesh = st.out(out->mesh, npx);
+  if (st.rc != RT_OK) return st.rc;
   const rtk::MotionArgs A = motion_args(c, q, prev, prev->vertex_pos ? c->mvPrev.get() : nullptr, d);
   const hipError_t he = rtk::launch_motion(q.accel == RT_ACCEL_BRUTE, c->S, A, nullptr);
   if (he != hipSuccess) return fail(RT_ERR_HIP, "motion launch failed: %s", hipGetErrorString(he));
-  for (int i = 0; i < 3; ++i)
-    if (hF[i]) HIP_TRY(hipMemcpy(hF[i], dF[i].get(), npx * wF[i] * sizeof(float), hipMemcpyDeviceToHost));
-  if (out->mesh) HIP_TRY(hipMemcpy(out->mesh, dMesh.get(), npx * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  return RT_OK;
+  return st.download();
 }
 
 int rt_temporal_accumulate_device(rt_ctx* c, const rt_temporal_params* t, const void* d_cur_rgb, const rt_motion* cur,
@@ -2326,16 +2366,16 @@ int rt_temporal_accumulate_device(rt_ctx* c, const rt_temporal_params* t, const 
   int rc = temporal_checks(c, t, static_cast<const float*>(d_cur_rgb), cur, prev, static_cast<const float*>(d_out_rgb),
                            static_cast<const float*>(d_out_length));
   if (rc != RT_OK) return rc;
-  if (c->broken) return fail(RT_ERR_STATE, "the context's device tree is in an unknown state: destroy it");
+  if ((rc = check_not_broken(c)) != RT_OK) return rc;
   HIP_TRY(hipSetDevice(c->device));
-  if (!c->tpScratch) HIP_TRY(dev_alloc(&c->tpScratch, rtk::temporal_scratch_words));
+  if (!c->tpScratch) HIP_TRY(dev_alloc(&c->tpScratch, 1));
   rtk::TemporalArgs T;
   T.width = t->width, T.height = t->height;
   T.maxHistory = t->max_history ? t->max_history : kTemporalMaxHistory;
   T.alphaMin = t->alpha_min, T.sigmaPosition = t->sigma_position, T.sigmaScale = kTemporalSigmaScale;
   T.curRgb = static_cast<const float*>(d_cur_rgb), T.motion = cur->motion, T.prevPosition = cur->prev_position, T.mesh = cur->mesh;
   T.hRgb = prev->rgb, T.hPosition = prev->position, T.hLength = prev->length, T.hMesh = prev->mesh;
-  T.outRgb = static_cast<float*>(d_out_rgb), T.outLength = static_cast<float*>(d_out_length), T.scratch = c->tpScratch.get();
+  T.outRgb = static_cast<float*>(d_out_rgb), T.outLength = static_cast<float*>(d_out_length), T.block = c->tpScratch.get();
   const hipError_t he = rtk::launch_temporal(c->S, T, static_cast<hipStream_t>(stream));
   if (he != hipSuccess) return fail(RT_ERR_HIP, "temporal launch failed: %s", hipGetErrorString(he));
   return RT_OK;
@@ -2347,31 +2387,17 @@ int rt_temporal_accumulate(rt_ctx* c, const rt_temporal_params* t, const float* 
   if (rc != RT_OK) return rc;
   HIP_TRY(hipSetDevice(c->device));
   const size_t npx = (size_t)t->width * t->height;
-  // inputs: cur_rgb, motion, prev_position, history rgb, history position, history length; mesh, history mesh
-  const float* const hF[6] = {cur_rgb, cur->motion, cur->prev_position, prev->rgb, prev->position, prev->length};
-  const size_t wF[6] = {3, 2, 3, 3, 3, 1};
-  const uint32_t* const hU[2] = {cur->mesh, prev->mesh};
-  DevBuf<float> dF[6], dOut, dLen;
-  DevBuf<uint32_t> dU[2];
-  for (int i = 0; i < 6; ++i) {
-    HIP_TRY(dev_alloc(&dF[i], npx * wF[i]));
-    HIP_TRY(hipMemcpy(dF[i].get(), hF[i], npx * wF[i] * sizeof(float), hipMemcpyHostToDevice));
-  }
-  for (int i = 0; i < 2; ++i) {
-    HIP_TRY(dev_alloc(&dU[i], npx));
-    HIP_TRY(hipMemcpy(dU[i].get(), hU[i], npx * sizeof(uint32_t), hipMemcpyHostToDevice));
-  }
-  HIP_TRY(dev_alloc(&dOut, 3 * npx));
-  HIP_TRY(dev_alloc(&dLen, npx));
+  Staging st;
+  const float* dRgb = st.in(cur_rgb, 3 * npx);
   rt_motion dc = {};
-  dc.motion = dF[1].get(), dc.prev_position = dF[2].get(), dc.mesh = dU[0].get();
+  dc.motion = st.in(cur->motion, 2 * npx), dc.prev_position = st.in(cur->prev_position, 3 * npx), dc.mesh = st.in(cur->mesh, npx);
   rt_history dh = {};
-  dh.rgb = dF[3].get(), dh.position = dF[4].get(), dh.length = dF[5].get(), dh.mesh = dU[1].get();
-  rc = rt_temporal_accumulate_device(c, t, dF[0].get(), &dc, &dh, dOut.get(), dLen.get(), nullptr);
-  if (rc != RT_OK) return rc;
-  HIP_TRY(hipMemcpy(out_rgb, dOut.get(), 3 * npx * sizeof(float), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(out_length, dLen.get(), npx * sizeof(float), hipMemcpyDeviceToHost));
-  return RT_OK;
+  dh.rgb = st.in(prev->rgb, 3 * npx), dh.position = st.in(prev->position, 3 * npx), dh.length = st.in(prev->length, npx);
+  dh.mesh = st.in(prev->mesh, npx);
+  float *dOut = st.out(out_rgb, 3 * npx), *dLen = st.out(out_length, npx);
+  if (st.rc != RT_OK) return st.rc;
+  if ((rc = rt_temporal_accumulate_device(c, t, dRgb, &dc, &dh, dOut, dLen, nullptr)) != RT_OK) return rc;
+  return st.download();
 }
 
 }  // extern "C"
@@ -2388,20 +2414,16 @@ constexpr float kSvgfSigmaLuminance = 2.f, kSvgfSigmaNormal = 0.5f, kSvgfSigmaSc
 int svgf_checks(const rt_ctx* c, const rt_svgf_params* s, const float* cur_rgb, const rt_aov* aov, const rt_motion* cur,
                 const rt_svgf_history* prev, const rt_svgf_out* out) {
   if (!c || !s || !cur_rgb || !aov || !cur || !prev || !out) return fail(RT_ERR_INVALID, "null argument");
-  if (!aov->albedo || !aov->normal || !aov->position || !aov->hits)
-    return fail(RT_ERR_INVALID, "the filter needs the albedo, normal, position and hits channels");
-  if (!cur->motion || !cur->prev_position || !cur->mesh)
-    return fail(RT_ERR_INVALID, "the current frame needs the motion, prev_position and mesh channels");
+  int rc = check_aov_channels(aov, "filter");
+  if (rc != RT_OK) return rc;
+  if ((rc = check_motion_channels(cur)) != RT_OK) return rc;
   if (!prev->color || !prev->moments || !prev->position || !prev->mesh || !prev->length)
     return fail(RT_ERR_INVALID, "the history needs color, moments, position, mesh and length");
   if (!out->rgb || !out->color || !out->moments || !out->length)
     return fail(RT_ERR_INVALID, "the outputs rgb, color, moments and length are required");
-  if (s->width == 0 || s->height == 0 || s->width > 65535u || s->height > 65535u)
-    return fail(RT_ERR_INVALID, "image size %ux%u out of range", s->width, s->height);
+  if ((rc = check_image_size(s->width, s->height)) != RT_OK) return rc;
   if (s->iterations > 8) return fail(RT_ERR_INVALID, "iterations %u > 8", s->iterations);
-  const float sg[4] = {s->sigma_luminance, s->sigma_normal, s->sigma_position, s->sigma_reproject};
-  for (float v : sg)
-    if (!(v >= 0.f) || !std::isfinite(v)) return fail(RT_ERR_INVALID, "sigmas must be finite and >= 0");
+  if ((rc = check_sigmas({s->sigma_luminance, s->sigma_normal, s->sigma_position, s->sigma_reproject})) != RT_OK) return rc;
   const float al[2] = {s->alpha_min, s->alpha_min_moments};
   for (float v : al)
     if (!(v >= 0.f) || !(v <= 1.f)) return fail(RT_ERR_INVALID, "alpha_min and alpha_min_moments must be 0 or in (0, 1]");
@@ -2437,15 +2459,9 @@ int rt_svgf_device(rt_ctx* c, const rt_svgf_params* s, const void* d_cur_rgb, co
                    const rt_svgf_history* prev, const rt_svgf_out* out, void* stream) {
   int rc = svgf_checks(c, s, static_cast<const float*>(d_cur_rgb), aov, cur, prev, out);
   if (rc != RT_OK) return rc;
-  if (c->broken) return fail(RT_ERR_STATE, "the context's device tree is in an unknown state: destroy it");
+  if ((rc = check_not_broken(c)) != RT_OK) return rc;
   HIP_TRY(hipSetDevice(c->device));
-  const size_t need = rtk::svgf_scratch(s->width, s->height);  // (the denoiser's scratch: one call at a time)
-  if (need > c->dnCap) {
-    c->dnCap = 0;
-    if (c->dnScratch) HIP_TRY(hipFree(c->dnScratch.release()));
-    HIP_TRY(dev_alloc(&c->dnScratch, need));
-    c->dnCap = need;
-  }
+  if ((rc = ensure_filter_scratch(c, rtk::filter_scratch(s->width, s->height))) != RT_OK) return rc;
   rtk::SvgfArgs A;
   A.width = s->width, A.height = s->height;
   A.iterations = s->iterations ? s->iterations : kSvgfIterations;
@@ -2470,40 +2486,22 @@ int rt_svgf(rt_ctx* c, const rt_svgf_params* s, const float* cur_rgb, const rt_a
   if (rc != RT_OK) return rc;
   HIP_TRY(hipSetDevice(c->device));
   const size_t npx = (size_t)s->width * s->height;
-  // inputs: cur_rgb, albedo, normal, position, motion, prev_position, history colour, moments, position, length; hits, mesh,
-  // history mesh
-  const float* const hF[10] = {cur_rgb,     aov->albedo,   aov->normal,    aov->position, cur->motion, cur->prev_position,
-                               prev->color, prev->moments, prev->position, prev->length};
-  const size_t wF[10] = {3, 3, 3, 3, 2, 3, 3, 2, 3, 1};
-  const uint32_t* const hU[3] = {aov->hits, cur->mesh, prev->mesh};
-  DevBuf<float> dF[10], dO[6];
-  DevBuf<uint32_t> dU[3];
-  for (int i = 0; i < 10; ++i) {
-    HIP_TRY(dev_alloc(&dF[i], npx * wF[i]));
-    HIP_TRY(hipMemcpy(dF[i].get(), hF[i], npx * wF[i] * sizeof(float), hipMemcpyHostToDevice));
-  }
-  for (int i = 0; i < 3; ++i) {
-    HIP_TRY(dev_alloc(&dU[i], npx));
-    HIP_TRY(hipMemcpy(dU[i].get(), hU[i], npx * sizeof(uint32_t), hipMemcpyHostToDevice));
-  }
-  float* const hO[6] = {out->rgb, out->color, out->moments, out->length, out->accum, out->variance};
-  const size_t wO[6] = {3, 3, 2, 1, 3, 1};
-  for (int i = 0; i < 6; ++i)
-    if (hO[i]) HIP_TRY(dev_alloc(&dO[i], npx * wO[i]));
+  Staging st;
+  const float* dRgb = st.in(cur_rgb, 3 * npx);
   rt_aov da = {};
-  da.albedo = dF[1].get(), da.normal = dF[2].get(), da.position = dF[3].get(), da.hits = dU[0].get();
+  da.albedo = st.in(aov->albedo, 3 * npx), da.normal = st.in(aov->normal, 3 * npx), da.position = st.in(aov->position, 3 * npx);
+  da.hits = st.in(aov->hits, npx);
   rt_motion dc = {};
-  dc.motion = dF[4].get(), dc.prev_position = dF[5].get(), dc.mesh = dU[1].get();
+  dc.motion = st.in(cur->motion, 2 * npx), dc.prev_position = st.in(cur->prev_position, 3 * npx), dc.mesh = st.in(cur->mesh, npx);
   rt_svgf_history dh = {};
-  dh.color = dF[6].get(), dh.moments = dF[7].get(), dh.position = dF[8].get(), dh.length = dF[9].get(), dh.mesh = dU[2].get();
+  dh.color = st.in(prev->color, 3 * npx), dh.moments = st.in(prev->moments, 2 * npx), dh.position = st.in(prev->position, 3 * npx);
+  dh.length = st.in(prev->length, npx), dh.mesh = st.in(prev->mesh, npx);
   rt_svgf_out dout = {};
-  dout.rgb = dO[0].get(), dout.color = dO[1].get(), dout.moments = dO[2].get(), dout.length = dO[3].get();
-  dout.accum = dO[4].get(), dout.variance = dO[5].get();
-  rc = rt_svgf_device(c, s, dF[0].get(), &da, &dc, &dh, &dout, nullptr);
-  if (rc != RT_OK) return rc;
-  for (int i = 0; i < 6; ++i)
-    if (hO[i]) HIP_TRY(hipMemcpy(hO[i], dO[i].get(), npx * wO[i] * sizeof(float), hipMemcpyDeviceToHost));
-  return RT_OK;
+  dout.rgb = st.out(out->rgb, 3 * npx), dout.color = st.out(out->color, 3 * npx), dout.moments = st.out(out->moments, 2 * npx);
+  dout.length = st.out(out->length, npx), dout.accum = st.out(out->accum, 3 * npx), dout.variance = st.out(out->variance, npx);
+  if (st.rc != RT_OK) return st.rc;
+  if ((rc = rt_svgf_device(c, s, dRgb, &da, &dc, &dh, &dout, nullptr)) != RT_OK) return rc;
+  return st.download();
 }
 
 }  // extern "C"

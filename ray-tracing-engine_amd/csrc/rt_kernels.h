@@ -133,43 +133,6 @@ struct MotionArgs {
   uint32_t width, height, spp, seed, s0;
 };
 hipError_t launch_motion(bool brute_force, const DevScene& S, const MotionArgs& A, hipStream_t stream);
-// temporal accumulation (temporal.hip, rt_temporal_accumulate): the history reprojected along the motion vectors and
-// blended with the current frame; all buffers device memory.  sigmaPosition 0: derived on the device from the extent of
-// the vertices the triangles reference (the denoiser's reduction) into scratch (temporal_scratch_words uint32 words)
-struct TemporalArgs {
-  uint32_t width, height, maxHistory;
-  float alphaMin, sigmaPosition;  // sigmaPosition 0: sigmaScale times the diagonal of that extent
-  float sigmaScale;
-  const float *curRgb, *motion, *prevPosition;  // the current frame: [h][w][3], rt_motion.motion, rt_motion.prev_position
-  const uint32_t* mesh;                         // rt_motion.mesh
-  const float *hRgb, *hPosition, *hLength;      // the history
-  const uint32_t* hMesh;
-  float *outRgb, *outLength;
-  uint32_t* scratch;
-};
-constexpr size_t temporal_scratch_words = 10;  // 6 extent words, pad, then sigma_position^2 as a double (8-byte aligned)
-hipError_t launch_temporal(const DevScene& S, const TemporalArgs& T, hipStream_t stream);
-// the box of the vertices the triangles reference, as order-preserving words (denoise.hip k_dn_extent): ext[0..2] =
-// min x, y, z, ext[3..5] = max
-hipError_t launch_ref_extent(const DevScene& S, uint32_t* ext, hipStream_t stream);
-// order-preserving float <-> uint32 (atomicMin / atomicMax on the bits)
-__device__ __forceinline__ uint32_t f2o(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float o2f(uint32_t u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u); }
-// the edge-avoiding a-trous filter (denoise.hip, rt_denoise): inputs and output [h][w][3] / [h][w], device memory;
-// scratch = 5 * w * h + 4 float4 (rtk::denoise_scratch)
-struct DenoiseArgs {
-  uint32_t width, height, iterations;
-  float sigma_color, sigma_normal, sigma_position;  // sigma_position 0: 2 % of the referenced vertices' box diagonal
-  const float *rgb, *albedo, *normal, *position;
-  const uint32_t* hits;
-  float* out;
-  float4* scratch;
-};
-inline size_t denoise_scratch(uint32_t w, uint32_t h) { return 5 * (size_t)w * h + 4; }
-hipError_t launch_denoise(const DevScene& S, const DenoiseArgs& D, hipStream_t stream);
 // adaptive sampling (adaptive.hip, rt_render_adaptive): per-pixel running moments and per-granule pass counts, the
 // compaction of the active granules into the next pass's wave tiles, and the resolve with per-pixel sample counts
 enum { ADAPT_CNT_GRANULES = 0, ADAPT_CNT_PIXELS = 1, ADAPT_CNT_TILES = 2, ADAPT_CNT_WORDS = 16 };  // counts[2 + sshift]

@@ -1,13 +1,11 @@
 // svgf.hip — variance-guided spatiotemporal filtering (Schied et al., HPG 2017): rt_svgf.  DESIGN.md "Variance-guided
 // spatiotemporal filtering" defines the rule; rt_amd.h states it operation by operation.
 //
-//   k_svgf_sigma     1 / sigma_position^2 (float) and sigma_reproject^2 (double) into device memory: the caller's sigmas,
-//                    or (default) a fraction of the diagonal of the box of the vertices the triangles reference
-//                    (launch_ref_extent, the denoiser's reduction)
-//   k_svgf_temporal  stage A, one lane per pixel, 64x4 pixels per workgroup as k_tp_blend: demodulation as k_dn_pack,
-//                    the four bilinear taps of the history (colour, both moments, length) in float64; writes the next
-//                    history's moments and length, the packed guides and factor, and the working (r, g, b, var) with the
-//                    variance the temporal moments give
+//   k_svgf_temporal  stage A, one lane per pixel, 64x4 pixels per workgroup as k_tp_blend: the demodulation and the
+//                    reprojection of filters_device.h, the latter over five channels (colour, both moments) and the
+//                    length in float64; writes the next history's moments and length, the packed guides and factor, and
+//                    the working (r, g, b, var) with the variance the temporal moments give.  The two position sigmas
+//                    come from the block launch_filter_sigmas fills
 //   k_svgf_variance  stage B for pixels with a history shorter than 4 frames: the 7x7 window over a 22x22 apron of
 //                    guides and moments staged in LDS; a workgroup in which no lane needs the window leaves after one
 //                    block-wide vote, before the staging
@@ -18,23 +16,10 @@
 
 #include <math.h>
 
-#include "svgf.h"
+#include "filters_device.h"
 
 namespace rtk {
 namespace {
-
-__global__ void k_svgf_sigma(const uint32_t* __restrict__ ext, float sigmaPos, float sigmaRep, float scale,
-                             float* __restrict__ isx, double* __restrict__ s2) {
-  if (sigmaPos <= 0.f || sigmaRep <= 0.f) {
-    const float dx = o2f(ext[3]) - o2f(ext[0]), dy = o2f(ext[4]) - o2f(ext[1]), dz = o2f(ext[5]) - o2f(ext[2]);
-    float sigma = scale * sqrtf((dx * dx + dy * dy) + dz * dz);
-    if (!(sigma > 0.f) || !(sigma < INFINITY)) sigma = 1.f;  // (a flat or empty scene: any scale does)
-    if (sigmaPos <= 0.f) sigmaPos = sigma;
-    if (sigmaRep <= 0.f) sigmaRep = sigma;
-  }
-  *isx = 1.f / (sigmaPos * sigmaPos);
-  *s2 = (double)sigmaRep * (double)sigmaRep;
-}
 
 __global__ __launch_bounds__(256) void k_svgf_temporal(SvgfArgs A, float4* __restrict__ g0, float4* __restrict__ g1,
                                                        float4* __restrict__ fac, float4* __restrict__ col,
@@ -42,65 +27,16 @@ __global__ __launch_bounds__(256) void k_svgf_temporal(SvgfArgs A, float4* __res
   const uint32_t px = blockIdx.x * 64u + (threadIdx.x & 63u), py = blockIdx.y * 4u + (threadIdx.x >> 6);
   if (px >= A.width || py >= A.height) return;
   const size_t p = (size_t)py * A.width + px, p3 = 3 * p;
-  const float r = A.curRgb[p3], g = A.curRgb[p3 + 1], b = A.curRgb[p3 + 2];
   const uint32_t nh = A.hits[p];
-  float d[3] = {r, g, b};
-  if (nh == 0) {  // passes through the spatial stages, weight 0 as a tap
-    g0[p] = make_float4(0.f, 0.f, 0.f, 0.f), g1[p] = make_float4(0.f, 0.f, 0.f, 0.f);
-    fac[p] = make_float4(1.f, 1.f, 1.f, 0.f);
-  } else {
-    const float fh = (float)nh;
-    const float ax = fmaxf(A.albedo[p3] / fh, 1e-3f), ay = fmaxf(A.albedo[p3 + 1] / fh, 1e-3f),
-                az = fmaxf(A.albedo[p3 + 2] / fh, 1e-3f);
-    g0[p] = make_float4(A.normal[p3] / fh, A.normal[p3 + 1] / fh, A.normal[p3 + 2] / fh, 1.f);
-    g1[p] = make_float4(A.position[p3] / fh, A.position[p3 + 1] / fh, A.position[p3 + 2] / fh, 0.f);
-    fac[p] = make_float4(ax, ay, az, 0.f);
-    d[0] = r / ax, d[1] = g / ay, d[2] = b / az;
-  }
-  double c[5] = {(double)d[0], (double)d[1], (double)d[2], 0.0, 0.0};  // colour, then the two luminance moments
+  const Demodulated d = demodulate(p, A.curRgb, A.albedo, A.normal, A.position, nh);
+  g0[p] = d.g0, g1[p] = d.g1, fac[p] = d.fac;
+  double c[5] = {(double)d.r, (double)d.g, (double)d.b, 0.0, 0.0};  // colour, then the two luminance moments
   c[3] = (0.2126 * c[0] + 0.7152 * c[1]) + 0.0722 * c[2];
   c[4] = c[3] * c[3];
-  const uint32_t mesh = A.mesh[p];
-  const float mx = A.motion[2 * p], my = A.motion[2 * p + 1];
-  double out[5] = {c[0], c[1], c[2], c[3], c[4]}, len = 1.0;  // no history: the current frame, length 1
-  const double rx = (double)px + (double)mx, ry = (double)py + (double)my;
-  // rt_temporal_accumulate's steps 1-4 (temporal.hip k_tp_blend), over five channels and the length
-  if (mesh != 0xffffffffu && isfinite(mx) && isfinite(my) && !(rx < -1.0) && !(rx >= (double)A.width) && !(ry < -1.0) &&
-      !(ry >= (double)A.height)) {
-    const double s2 = *s2p;
-    const double fx = floor(rx), fy = floor(ry);
-    const double ax = rx - fx, ay = ry - fy;
-    const int x0 = (int)fx, y0 = (int)fy;
-    const double wx[2] = {1.0 - ax, ax}, wy[2] = {1.0 - ay, ay};
-    const double X[3] = {(double)A.prevPosition[p3], (double)A.prevPosition[p3 + 1], (double)A.prevPosition[p3 + 2]};
-    double W = 0.0, s[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, sl = 0.0;
-    for (int j = 0; j < 2; j++)
-      for (int i = 0; i < 2; i++) {
-        const double w = wx[i] * wy[j];
-        const int x = x0 + i, y = y0 + j;
-        if (!(w > 0.0) || x < 0 || x >= (int)A.width || y < 0 || y >= (int)A.height) continue;
-        const size_t q = (size_t)y * A.width + (size_t)x;
-        const float hl = A.hLength[q];
-        if (!(hl > 0.f) || A.hMesh[q] != mesh) continue;
-        const double dx = (double)A.hPosition[3 * q] - X[0], dy = (double)A.hPosition[3 * q + 1] - X[1],
-                     dz = (double)A.hPosition[3 * q + 2] - X[2];
-        if (!((dx * dx + dy * dy) + dz * dz <= s2)) continue;
-        W += w;
-        s[0] += w * (double)A.hColor[3 * q], s[1] += w * (double)A.hColor[3 * q + 1], s[2] += w * (double)A.hColor[3 * q + 2];
-        s[3] += w * (double)A.hMoments[2 * q], s[4] += w * (double)A.hMoments[2 * q + 1];
-        sl += w * (double)hl;
-      }
-    if (W > 0.0) {
-      const double L = sl / W;
-      const double Ln = fmin(L + 1.0, (double)A.maxHistory);
-      const double alpha = fmax(1.0 / Ln, (double)A.alphaMin), alphaM = fmax(1.0 / Ln, (double)A.alphaMinMoments);
-      for (int k = 0; k < 5; k++) {
-        const double h = s[k] / W;
-        out[k] = h + (k < 3 ? alpha : alphaM) * (c[k] - h);
-      }
-      len = Ln;
-    }
-  }
+  const float alphaMin[5] = {A.alphaMin, A.alphaMin, A.alphaMin, A.alphaMinMoments, A.alphaMinMoments};
+  double out[5];
+  const double len = reproject_blend<5>(
+      A, px, py, s2p, c, alphaMin, [&](int k, size_t q) { return k < 3 ? A.hColor[3 * q + k] : A.hMoments[2 * q + (k - 3)]; }, out);
   const float m1 = (float)out[3], m2 = (float)out[4];
   A.outMoments[2 * p] = m1, A.outMoments[2 * p + 1] = m2;
   A.outLength[p] = (float)len;
@@ -109,13 +45,6 @@ __global__ __launch_bounds__(256) void k_svgf_temporal(SvgfArgs A, float4* __res
   // the variance of a long history; k_svgf_variance replaces it where the history is shorter than 4 frames
   col[p] = make_float4(cr, cg, cb, nh ? fmaxf(0.f, m2 - m1 * m1) : 0.f);
 }
-
-__device__ __forceinline__ float sq3(float4 a, float4 b) {
-  const float x = a.x - b.x, y = a.y - b.y, z = a.z - b.z;
-  return (x * x + y * y) + z * z;
-}
-
-__device__ __forceinline__ float lum(float4 c) { return (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z; }
 
 // 16x16 pixels per workgroup (four waves of 16x4) and their 3-pixel apron
 constexpr int kVarTile = 22;
@@ -214,7 +143,6 @@ __global__ __launch_bounds__(256) void k_svgf_atrous(uint32_t W, uint32_t H, int
     }
     const float den = sl * sqrtf(gs / gk) + 1e-4f;
     const float lp = lum(cp);
-    const float kh[5] = {1.f / 16.f, 1.f / 4.f, 3.f / 8.f, 1.f / 4.f, 1.f / 16.f};
     float sr = 0.f, sg = 0.f, sb = 0.f, sv = 0.f, sw = 0.f;
     for (int j = 0; j < 5; j++) {
       const int yy = y + (j - 2) * step;
@@ -225,7 +153,7 @@ __global__ __launch_bounds__(256) void k_svgf_atrous(uint32_t W, uint32_t H, int
         const float4 nq = N(xx, yy);
         if (nq.w == 0.f) continue;
         const float4 cq = C(xx, yy), xq = X(xx, yy);
-        const float w = kh[i] * kh[j] * expf(-((sq3(np, nq) * isn + sq3(xp, xq) * isx) + fabsf(lp - lum(cq)) / den));
+        const float w = atrous5(i) * atrous5(j) * expf(-((sq3(np, nq) * isn + sq3(xp, xq) * isx) + fabsf(lp - lum(cq)) / den));
         sr += w * cq.x, sg += w * cq.y, sb += w * cq.z, sv += (w * w) * cq.w, sw += w;
       }
     }
@@ -246,26 +174,22 @@ __global__ __launch_bounds__(256) void k_svgf_atrous(uint32_t W, uint32_t H, int
 hipError_t launch_svgf(const DevScene& S, const SvgfArgs& A, hipStream_t stream) {
   const size_t n = (size_t)A.width * A.height;
   if (n == 0) return hipSuccess;
-  float4 *g0 = A.scratch, *g1 = g0 + n, *fac = g1 + n, *ca = fac + n, *cb = ca + n;
-  uint32_t* ext = reinterpret_cast<uint32_t*>(cb + n);  // 6 words; word 8: 1 / sigma_position^2; words 10-11: sigma_reproject^2
-  float* isx = reinterpret_cast<float*>(ext + 8);
-  double* s2 = reinterpret_cast<double*>(ext + 10);
-  hipError_t e;
-  if (A.sigmaPosition <= 0.f || A.sigmaReproject <= 0.f) {
-    if ((e = launch_ref_extent(S, ext, stream)) != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(k_svgf_sigma, dim3(1), dim3(1), 0, stream, ext, A.sigmaPosition, A.sigmaReproject, A.sigmaScale, isx, s2);
-  hipLaunchKernelGGL(k_svgf_temporal, dim3((A.width + 63u) / 64u, (A.height + 3u) / 4u), dim3(256), 0, stream, A, g0, g1, fac, ca, s2);
+  FilterScratch s = carve_filter_scratch(A.scratch, n);
+  const float* isx = &s.block->isx;
+  const hipError_t e = launch_filter_sigmas(S, s.block, A.sigmaPosition, A.sigmaReproject, A.sigmaScale, stream);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_svgf_temporal, dim3((A.width + 63u) / 64u, (A.height + 3u) / 4u), dim3(256), 0, stream, A, s.g0, s.g1, s.fac,
+                     s.ca, &s.block->s2);
   const dim3 grid((A.width + 15u) / 16u, (A.height + 15u) / 16u);
   const float isn = 1.f / (A.sigmaNormal * A.sigmaNormal);
-  hipLaunchKernelGGL(k_svgf_variance, grid, dim3(256), 0, stream, A.width, A.height, isn, isx, g0, g1, A.outMoments, A.outLength, ca);
+  hipLaunchKernelGGL(k_svgf_variance, grid, dim3(256), 0, stream, A.width, A.height, isn, isx, s.g0, s.g1, A.outMoments, A.outLength, s.ca);
   for (uint32_t it = 0; it < A.iterations; it++) {
     const bool last = it + 1 == A.iterations;
     hipLaunchKernelGGL(it == 0 ? k_svgf_atrous<true> : k_svgf_atrous<false>, grid, dim3(256), 0, stream, A.width, A.height,
-                       1 << it, isn, A.sigmaLuminance, isx, g0, g1, fac, ca, cb, it == 0 ? A.outColor : nullptr,
+                       1 << it, isn, A.sigmaLuminance, isx, s.g0, s.g1, s.fac, s.ca, s.cb, it == 0 ? A.outColor : nullptr,
                        last ? A.outRgb : nullptr, last ? A.outVariance : nullptr);
-    float4* t = ca;
-    ca = cb, cb = t;
+    float4* t = s.ca;
+    s.ca = s.cb, s.cb = t;
   }
   return hipGetLastError();
 }
