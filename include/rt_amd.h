@@ -15,6 +15,8 @@
  *                                  camera or light): the resident context follows it, tree refit
  *   rt_update_transforms        <- the same with one matrix per mesh (Main.cpp:88-99): the device transforms a
  *                                  resident rest pose, nothing per vertex crosses the bus
+ *   rt_bvh_quality_get / rt_rebuild <- (no counterpart) the surface-area cost of the refit tree against the tree as built,
+ *                                  and the tree built again in place from the resident arrays when it has degraded
  *   rt_render                   <- the spp/y/x loop + resolve (Renderer.cpp:219-271)
  *   rt_render_device/_resolve_device : same, on caller-owned DEVICE buffers and a
  *                                  caller stream (multi-GPU tile sharding, bench)
@@ -277,6 +279,72 @@ typedef struct rt_transform_update {
   uint32_t reserved[6];                 /* zero                                                                    */
 } rt_transform_update;
 int rt_update_transforms(rt_ctx* ctx, const rt_transform_update* u, void* stream, rt_update_report* rep /* may be NULL */);
+
+/* ---- rebuilding a refit tree ----------------------------------------------------------------------------
+ * A refit keeps the topology rt_create built, so over a long animation the tree drifts from the geometry.  The two calls
+ * below measure that and undo it without rt_destroy + rt_create: nothing crosses the bus towards the device, and the
+ * handle, the photon map, the rest pose of rt_update_transforms and the profile events stay.
+ *
+ * rt_bvh_quality_get: the surface-area cost of the resident tree, one device pass over its float node records (the
+ * rt_bvh_export form: node i has two slots k with a box lo, hi in float32 and a ref child[k]; ref >= 0 an inner node,
+ * ref < 0 a leaf of cnt = ((~ref) & 7) + 1 triangle records).  With A(lo, hi) = dx dy + dy dz + dz dx in double from
+ * the float planes (dx = (double)hi.x - lo.x, ...) — the area measure of rt_bvh_check_host's est2 — and
+ * A_root = max(A(union of node 0's two slots), 1e-300):
+ *   nodes = 1 + sum over inner slots of A / A_root        tris = sum over leaf slots of (cnt A) / A_root
+ *   cost  = nodes + 1.5 tris                              (the weights of rt_bvh_tune's probe cost)
+ * The sums are double sums of fixed shape (no floating-point atomics): two calls on the same tree return the same bits.
+ * cost_built is the same measure of the tree as last BUILT (rt_create, rt_rebuild, an accepted rt_bvh_tune) on the boxes
+ * it was built with, taken lazily: right before the first refit that follows a build (that rt_update* gains one pass over
+ * the nodes), or at the first quality call if none has run yet; rt_create, rt_bvh_tune and the render paths do no work
+ * for it.  ratio = cost / cost_built is 1.0 exactly on a tree never refit.
+ * A PROXY, NOT AN ORACLE: the ratio compares the refit tree on today's geometry with the built tree on the build's
+ * geometry (the ratio renderers commonly use to decide on a rebuild); it is not the cost of a fresh tree of today's
+ * geometry, which only a build can give.  It is a launch like any other (one in flight per context) and synchronises.
+ * RT_ERR_INVALID: a null ctx or out; RT_ERR_UNSUPPORTED: RT_NODES_Q8 contexts (as rt_update); RT_ERR_STATE: a context
+ * that refuses launches. */
+typedef struct rt_bvh_quality {
+  double cost;          /* of the tree as it is now                                                         */
+  double nodes, tris;   /* its two parts                                                                    */
+  double cost_built;    /* the same measure of this topology before its first refit                         */
+  double ratio;         /* cost / cost_built; 1.0 exactly on a tree never refit                             */
+  uint32_t n_nodes;
+  uint32_t refits;      /* refits (updates that recomputed the boxes) since the last build                  */
+  uint64_t reserved[4];
+} rt_bvh_quality;
+int rt_bvh_quality_get(rt_ctx* ctx, rt_bvh_quality* out);
+
+/* rt_rebuild: the tree built again from the context's resident arrays.  After a successful rebuild the tree, the triangle
+ * records, rt_bvh_info (except build_ms) and every derived value — padding, origin bound, plane scale, depth cap, the
+ * short-form vouching, the pool thresholds, the most-visited-first numbering of trees of at most 65,536 nodes — are what
+ * rt_create would produce from the context's CURRENT description (live positions and normals, camera, lights, materials)
+ * and the rt_options it was created with, under rt_create's builder rule (bvh_builder, RT_BVH_GPU, RT_BVH_AUTO_FROM, the
+ * 16- and 1,024-triangle special cases): the same code builds both.  The refit depth table and any rt_bvh_tune result are
+ * dropped; cost_built and refits start again.  Hits do not depend on the tree, so — unlike an update — a rebuild KEEPS
+ * the photon map, the rest pose of rt_update_transforms, the profile events and the handle: every frame and pass is
+ * bit-identical before and after.
+ * The host passes of a build (validation, the size keys from the host's log2, the host builder for small scenes) read the
+ * positions, vertex ids and mesh tables back for the duration of the call; the new tree is built into staging buffers
+ * and swapped in only when everything has succeeded, so TWO TREES ARE RESIDENT during the call and a failure leaves the
+ * context exactly as it was.  The call synchronises and takes no stream: it reads only the context's own arrays.
+ * min_ratio: 0 = always rebuild; otherwise finite and >= 1: rebuild only if rt_bvh_quality_get's ratio >= min_ratio.
+ * RT_ERR_INVALID: non-zero reserved words, min_ratio non-finite or in (0, 1) (checked first), a null ctx;
+ * RT_ERR_UNSUPPORTED: RT_NODES_Q8 contexts; RT_ERR_STATE: a context that refuses launches. */
+typedef struct rt_rebuild_params {
+  float min_ratio;
+  uint32_t reserved[7];   /* zero */
+} rt_rebuild_params;
+typedef struct rt_rebuild_report {
+  uint32_t rebuilt;       /* 0: the ratio was below min_ratio, nothing changed                                        */
+  uint32_t builder;       /* RT_BVH_* that ran (0 when nothing was rebuilt)                                           */
+  double ratio_before;    /* rt_bvh_quality.ratio on entry (computed only when min_ratio > 0 or the report is asked for) */
+  double cost_after;      /* cost of the new tree (== its cost_built); 0 when nothing was rebuilt                      */
+  double build_ms;        /* the build: host plan + device build + renumbering (rt_bvh_info.build_ms)                 */
+  double total_ms;        /* wall time of the call                                                                    */
+  double readback_ms;     /* of total_ms: reading the arrays of the host passes back                                  */
+  double plan_ms;         /* of build_ms: the host passes (validation + size keys, the hybrid top, or the host build)  */
+  uint64_t reserved[4];
+} rt_rebuild_report;
+int rt_rebuild(rt_ctx* ctx, const rt_rebuild_params* p /* NULL = always */, rt_rebuild_report* rep /* may be NULL */);
 
 /* Photon arrays already in the host-built kd-tree (median-implicit) order. */
 int rt_set_photons(rt_ctx* ctx, const float* pos3, const float* dir3, uint32_t n);

@@ -1504,4 +1504,20 @@ void build(const rt_scene_desc& sc, uint32_t leafMax, Built& out, uint32_t threa
   }
 }
 
+void triVtxFromShade(const uint32_t* shade4, uint32_t nTris, std::vector<uint32_t>& triVtx) {
+  triVtx.resize(3 * static_cast<size_t>(nTris));
+  for (size_t t = 0; t < nTris; ++t)
+    for (int k = 0; k < 3; ++k) triVtx[3 * t + k] = shade4[4 * t + k];
+}
+
+rt_scene_desc residentDesc(uint32_t nMeshes, uint32_t nVertices, uint32_t nTris, const float* pos, const uint32_t* triVtx,
+                           const uint32_t* meshTriBegin, const uint32_t* meshVtxBegin, const rt_light* lights, uint32_t nLights,
+                           const rt_camera& camera) {
+  rt_scene_desc sc{};
+  sc.n_meshes = nMeshes, sc.n_vertices = nVertices, sc.n_triangles = nTris, sc.n_lights = nLights;
+  sc.vertex_pos = pos, sc.tri_vtx = triVtx, sc.mesh_tri_begin = meshTriBegin, sc.mesh_vtx_begin = meshVtxBegin;
+  sc.lights = lights, sc.camera = camera;
+  return sc;
+}
+
 }  // namespace rtbvh

@@ -190,6 +190,15 @@ struct TopBuilt {
 constexpr uint32_t kPartFlag = 0x40000000u;
 void buildTop(const rt_scene_desc& scene, uint32_t leafMax, uint32_t cutoff, TopBuilt& out, uint32_t threads = 0);
 
+// What rt_rebuild hands the passes above: the description they read — positions, vertex ids, mesh tables, lights, camera —
+// over arrays read back from a context.  triVtxFromShade: [n][3] global vertex ids out of the per-triangle shading records
+// {v0, v1, v2, mesh} (shade4: [n][4] words).  residentDesc: the rt_scene_desc over the caller's arrays; vertex_nrm and
+// materials, which no builder reads, stay null.
+void triVtxFromShade(const uint32_t* shade4, uint32_t nTris, std::vector<uint32_t>& triVtx);
+rt_scene_desc residentDesc(uint32_t nMeshes, uint32_t nVertices, uint32_t nTris, const float* pos, const uint32_t* triVtx,
+                           const uint32_t* meshTriBegin, const uint32_t* meshVtxBegin, const rt_light* lights, uint32_t nLights,
+                           const rt_camera& camera);
+
 // Throws std::runtime_error on an inconsistent scene description.
 // threads: builder threads (0 = one per hardware thread, at most 16); the result does not
 // depend on it.

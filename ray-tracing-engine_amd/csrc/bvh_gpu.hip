@@ -754,6 +754,62 @@ __global__ void k_refit_pack(const RNode* __restrict__ nodes, uint32_t n, float 
   pack_record(nodes[i], boxScale, nodes16 + 2 * (size_t)i);
 }
 
+// ---------------------------------------------------------------- the surface-area cost of a resident tree (rt_bvh_quality_get)
+// One pass over the float records, one 64-byte record per lane.  Per slot the box area A = dx dy + dy dz + dz dx in double
+// from the float planes, divided by the root's (the union of node 0's two slots, at least 1e-300): an inner slot adds
+// A / A_root to the node term, a leaf slot of cnt records cnt A / A_root to the triangle term.  Every sum has a fixed shape
+// — a lane's records in index order, the wave by xor shuffles, the workgroup's waves in order, one pair per workgroup —
+// and k_quality_sum, a single workgroup, adds the pairs in contiguous runs in index order: no floating-point atomics, so
+// two calls on the same records return the same bits whatever the schedule.
+constexpr uint32_t kQualityBlock = 256, kQualityMaxBlocks = kQualityPartials;
+
+__device__ __forceinline__ double quality_area(const float* lo, const float* hi) {
+  const double dx = (double)hi[0] - lo[0], dy = (double)hi[1] - lo[1], dz = (double)hi[2] - lo[2];
+  return dx * dy + dy * dz + dz * dx;
+}
+// the sum of v over the workgroup's threads, returned to thread 0 (sh: one slot per wave)
+__device__ __forceinline__ double quality_block_sum(double v, double* sh) {
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  if ((threadIdx.x & 63u) == 0u) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = 0.0;
+  if (threadIdx.x == 0u)
+    for (uint32_t w = 0; w < blockDim.x / 64u; ++w) s += sh[w];
+  __syncthreads();
+  return s;
+}
+__global__ __launch_bounds__(kQualityBlock) void k_quality_partial(const RNode* __restrict__ nodes, uint32_t n, double2* __restrict__ partial) {
+  __shared__ double sh[kQualityBlock / 64];
+  const RNode R = nodes[0];  // (every lane the same address: one line, broadcast)
+  const float rlo[3] = {fminf(R.lo0[0], R.lo1[0]), fminf(R.lo0[1], R.lo1[1]), fminf(R.lo0[2], R.lo1[2])};
+  const float rhi[3] = {fmaxf(R.hi0[0], R.hi1[0]), fmaxf(R.hi0[1], R.hi1[1]), fmaxf(R.hi0[2], R.hi1[2])};
+  const double rootArea = fmax(quality_area(rlo, rhi), 1e-300);
+  double nodeTerm = 0.0, triTerm = 0.0;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const RNode N = nodes[i];
+    for (int c = 0; c < 2; ++c) {
+      const double a = c ? quality_area(N.lo1, N.hi1) : quality_area(N.lo0, N.hi0);
+      const int32_t ref = N.child[c];
+      if (ref >= 0) nodeTerm += a / rootArea;
+      else triTerm += ((double)((~(uint32_t)ref & 7u) + 1u) * a) / rootArea;
+    }
+  }
+  const double sn = quality_block_sum(nodeTerm, sh), st = quality_block_sum(triTerm, sh);
+  if (threadIdx.x == 0u) partial[blockIdx.x] = make_double2(sn, st);
+}
+__global__ __launch_bounds__(kQualityBlock) void k_quality_sum(const double2* __restrict__ partial, uint32_t count, double2* __restrict__ out) {
+  __shared__ double2 sh[kQualityBlock];
+  const uint32_t per = (count + kQualityBlock - 1u) / kQualityBlock, b = threadIdx.x * per;
+  double2 s = make_double2(0.0, 0.0);
+  for (uint32_t i = b; i < b + per && i < count; ++i) s.x += partial[i].x, s.y += partial[i].y;
+  sh[threadIdx.x] = s;
+  __syncthreads();
+  if (threadIdx.x != 0u) return;
+  double2 t = make_double2(0.0, 0.0);
+  for (uint32_t k = 0; k < kQualityBlock; ++k) t.x += sh[k].x, t.y += sh[k].y;
+  *out = t;
+}
+
 // Pre-order renumbering after the rotations (what the host builder's relayout leaves below its top, and what the
 // traversal's locality was tuned on): subtree sizes bottom-up, new indices top-down — a node's first inner child follows
 // it, the second follows the first one's subtree —, then a scatter with the refs rewritten.
@@ -1891,6 +1947,16 @@ hipError_t gpu_bvh_refit(const float* dVpos, const uint4* dTriShade, uint32_t nT
   for (int d = (int)maxDepth; d >= 0; --d)
     hipLaunchKernelGGL(k_refit_level, grd, blk, 0, stream, nodes, nNodes, dDepth, (uint32_t)d, tris, dVpos, dTriShade, pad);
   hipLaunchKernelGGL(k_refit_pack, grd, blk, 0, stream, nodes, nNodes, boxScale, nodes16);
+  return hipGetLastError();
+}
+
+hipError_t gpu_bvh_quality(const float4* nodesF, uint32_t nNodes, double* dPartial, double* dOut2, hipStream_t stream) {
+  if (nNodes == 0) return hipErrorInvalidValue;
+  const uint32_t blocks = std::min(kQualityMaxBlocks, (nNodes + kQualityBlock - 1u) / kQualityBlock);
+  hipLaunchKernelGGL(k_quality_partial, dim3(blocks), dim3(kQualityBlock), 0, stream, reinterpret_cast<const RNode*>(nodesF), nNodes,
+                     reinterpret_cast<double2*>(dPartial));
+  hipLaunchKernelGGL(k_quality_sum, dim3(1), dim3(kQualityBlock), 0, stream, reinterpret_cast<const double2*>(dPartial), blocks,
+                     reinterpret_cast<double2*>(dOut2));
   return hipGetLastError();
 }
 

@@ -185,6 +185,15 @@ struct rt_ctx {
   // uploaded to nodesF then and kept), and scratch for host-given arrays and the magnitude read-back
   DevBuf<uint8_t> refitDepth;
   uint32_t refitMaxDepth = 0;
+  // rt_rebuild builds under the rt_options the context was created with
+  uint32_t optLeafMax = 0, optBuilder = RT_BVH_AUTO, optNodeFormat = RT_NODES_AUTO;
+  // rt_bvh_quality_get: the cost of the tree as last built (taken before the first refit that follows a build, or at the
+  // first quality call), the refits since, and the reduction's block (2 x kQualityPartials partial sums, then the pair of
+  // the tree as it is and the pair of the baseline; allocated on first use)
+  double costBuilt = 0.0;
+  bool costBuiltValid = false;
+  uint32_t refits = 0;
+  DevBuf<double> dQuality;
   DevBuf<float> updPos, updNrm;
   DevBuf<uint32_t> dMag;
   // rt_update_transforms (allocated on first use): the rest pose — a snapshot of vpos / vnrm taken at the first transforms
@@ -557,14 +566,24 @@ void par_chunks(size_t b, size_t e, F f) {
   for (std::thread& x : th) x.join();
 }
 
-// The tree the device builder left on the device, read back into c->bvh: its float nodes, and with nTris > 0 its
+// A built tree before it belongs to a context (build_tree makes it, install_tree hands it over): the host copy kept for
+// rt_bvh_export, the device arrays (DevScene's fields of the same names) and what rt_bvh_info reports of it
+struct Tree {
+  rtbvh::Built bvh;
+  DevBuf<uint4> nodes, q8;
+  DevBuf<float4> tris, trisRef, nodesF;
+  uint32_t nNodes = 0, builder = RT_BVH_HOST, nodeFormat = RT_NODES_F16, q8ShiftBytes = 0;
+  float buildMs = 0.f, planMs = 0.f;  // planMs: the host passes' share of buildMs
+};
+
+// The tree the device builder left on the device, read back into t->bvh: its float nodes, and with nTris > 0 its
 // triangle records in both orders (throws: the callers report it as their step's failure)
-void read_back_tree(rt_ctx* c, uint32_t nTris) {
-  const size_t nn = c->S.n_nodes;
-  c->bvh.nodes.resize(nn), c->bvh.tris.resize(nTris), c->bvh.trisRef.resize(nTris);
-  if (hipMemcpy(c->bvh.nodes.data(), c->nodesF.get(), nn * sizeof(rtbvh::Node), hipMemcpyDeviceToHost) != hipSuccess ||
-      (nTris && (hipMemcpy(c->bvh.tris.data(), c->tris.get(), (size_t)nTris * sizeof(rtbvh::TriRec), hipMemcpyDeviceToHost) != hipSuccess ||
-                 hipMemcpy(c->bvh.trisRef.data(), c->trisRef.get(), (size_t)nTris * sizeof(rtbvh::TriRec), hipMemcpyDeviceToHost) != hipSuccess)))
+void read_back_tree(Tree* t, uint32_t nTris) {
+  const size_t nn = t->nNodes;
+  t->bvh.nodes.resize(nn), t->bvh.tris.resize(nTris), t->bvh.trisRef.resize(nTris);
+  if (hipMemcpy(t->bvh.nodes.data(), t->nodesF.get(), nn * sizeof(rtbvh::Node), hipMemcpyDeviceToHost) != hipSuccess ||
+      (nTris && (hipMemcpy(t->bvh.tris.data(), t->tris.get(), (size_t)nTris * sizeof(rtbvh::TriRec), hipMemcpyDeviceToHost) != hipSuccess ||
+                 hipMemcpy(t->bvh.trisRef.data(), t->trisRef.get(), (size_t)nTris * sizeof(rtbvh::TriRec), hipMemcpyDeviceToHost) != hipSuccess)))
     throw std::runtime_error("reading the device-built tree back failed");
 }
 
@@ -657,6 +676,153 @@ void vouch_short_forms(rt_ctx* c) {
   c->recipCheck = it->second ? 1u : 2u;
 }
 
+// The tree part of rt_create, which rt_rebuild runs again: the builder choice, the host passes over the description
+// (validation, the host build, the hybrid top or the size keys), then — `resident` gives the positions and the shading
+// records on the device: rt_create uploads them there, a rebuild has them — the device build, the renumbering and the
+// node format.  Everything lands in *t; no context is touched.
+template <class Resident>
+int build_tree(const rt_scene_desc* sc, uint32_t leafMax, uint32_t builderOpt, uint32_t nodeFormatOpt, const rtbvh::Built* prebuilt,
+               Resident resident, Tree* t) {
+  int rc = RT_OK;
+  // the tree: host SAH builder, or the device builder (tiny scenes always take the host's
+  // special cases)
+  // (RT_BVH_GPU=1 / 2 / 3: the device / hybrid / host builder whatever the options say — the test suites run whole on each)
+  const char* gpuEnv = getenv("RT_BVH_GPU");
+  uint32_t wantBuilder = gpuEnv ? (uint32_t)atoi(gpuEnv) : builderOpt;
+  if (wantBuilder > RT_BVH_HOST) return fail(RT_ERR_INVALID, "unknown bvh_builder %u", wantBuilder);
+  // AUTO: the device builder gives the host builder's tree (tests/treedigest.py; profiles/r04_builders.txt) 2 ... 14 x sooner,
+  // so every scene it is faster on takes it (from 8,192 triangles: below that a build is 1-3 ms either way and the host needs no
+  // device round trip); a group of contexts given a host-built tree shares it
+  static const uint32_t autoFrom = getenv("RT_BVH_AUTO_FROM") ? (uint32_t)atoi(getenv("RT_BVH_AUTO_FROM")) : 8192u;
+  if (wantBuilder == RT_BVH_AUTO) wantBuilder = (sc->n_triangles >= autoFrom && !prebuilt) ? (uint32_t)RT_BVH_DEVICE : (uint32_t)RT_BVH_HOST;
+  // (a scene of a single part has no top to build on the host: the device builder's own path handles it)
+  const bool hybrid = wantBuilder == RT_BVH_HYBRID && sc->n_triangles > 1024u;
+  const bool gpuBuild = (wantBuilder == RT_BVH_DEVICE || wantBuilder == RT_BVH_HYBRID) && sc->n_triangles >= 16;
+  rtbvh::TopBuilt topBuilt;
+  rtbvh::ScenePlan plan;
+  std::vector<float> sizeKey;
+  const auto tBuild0 = std::chrono::steady_clock::now();
+  auto msSince = [&tBuild0] { return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - tBuild0).count(); };
+  try {
+    if (hybrid) {
+      rtbvh::buildTop(*sc, leafMax, 1024u, topBuilt);
+      if (getenv("RT_BVH_VERBOSE"))
+        fprintf(stderr, "hybrid builder: host top of %zu nodes over %zu parts in %.1f ms\n", topBuilt.nodes.size(), topBuilt.parts.size(), msSince());
+      t->bvh.leafMax = topBuilt.leafMax, t->bvh.pad = topBuilt.pad, t->bvh.originBound = topBuilt.originBound, t->bvh.boxScale = topBuilt.boxScale;
+      t->bvh.maxAbs = topBuilt.maxAbs;
+      t->bvh.depthCap = topBuilt.depthCap;
+      (void)rtbvh::planSceneExact(*sc, leafMax, sizeKey);  // (the size keys of the subtrees' sweeps)
+    } else if (gpuBuild) {
+      // (the device build restates the host builder's splits: it takes the host's depth cap and size keys)
+      plan = rtbvh::planSceneExact(*sc, leafMax, sizeKey);
+      if (getenv("RT_BVH_VERBOSE")) fprintf(stderr, "device builder: validation + size keys in %.2f ms\n", msSince());
+      t->bvh.leafMax = plan.leafMax, t->bvh.pad = plan.pad, t->bvh.originBound = plan.originBound, t->bvh.boxScale = plan.boxScale;
+      t->bvh.maxAbs = plan.maxAbs;
+      t->bvh.depthCap = plan.depthCap;
+    } else if (prebuilt) {
+      t->bvh = *prebuilt;
+    } else {
+      rtbvh::build(*sc, leafMax, t->bvh);
+    }
+  } catch (const std::exception& e) {
+    return fail(RT_ERR_INVALID, "scene rejected: %s", e.what());
+  }
+  t->planMs = msSince();
+  static_assert(sizeof(rtbvh::Node16) == 2 * sizeof(uint4), "node layout");
+  static_assert(sizeof(rtbvh::TriRec) == 3 * sizeof(float4), "triangle layout");
+  const float* dVpos = nullptr;
+  const uint4* dTriShade = nullptr;
+  if ((rc = resident(&dVpos, &dTriShade)) != RT_OK) return rc;
+  if (gpuBuild) {
+    if (getenv("RT_BVH_VERBOSE")) fprintf(stderr, "scene arrays on the device %.2f ms after the start\n", msSince());
+    rtk::GpuBvh G;
+    hipError_t he = hipSuccess;
+    if (hybrid) {
+      he = rtk::gpu_bvh_build_over_top(dVpos, dTriShade, sizeKey.data(), sc->n_triangles, topBuilt, &G, nullptr);
+    } else {
+      he = rtk::gpu_bvh_build_exact(dVpos, dTriShade, sizeKey.data(), sc->n_triangles, plan, &G, nullptr);
+    }
+    if (he != hipSuccess) return fail(RT_ERR_HIP, "device BVH build failed: %s", hipGetErrorString(he));
+    t->nodes.reset(G.nodes16), t->tris.reset(G.tris), t->trisRef.reset(G.trisRef), t->nodesF.reset(G.nodesF);
+    t->bvh.maxDepth = G.maxDepth;
+    t->nNodes = G.n_nodes;
+    t->builder = hybrid ? RT_BVH_HYBRID : RT_BVH_DEVICE;
+    // Trees whose top the render kernel may keep in LDS (rt_kernels.hip plan_persist: a prefix of the node array) get the host
+    // builder's final numbering — the most-visited nodes first, greedily by box area from the root (bvh_build.cpp
+    // relayoutTop) — instead of the device's pre-order: C4 loses 2 % on a pre-order tree.  64 KB ... 4 MB back and forth.
+    if (t->nNodes >= 2u && t->nNodes <= 65536u) {
+      try {
+        read_back_tree(t, 0);
+        rtbvh::relayoutAndPack(t->bvh);
+        if (hipMemcpy(t->nodesF.get(), t->bvh.nodes.data(), (size_t)t->nNodes * sizeof(rtbvh::Node), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(t->nodes.get(), t->bvh.nodes16.data(), (size_t)t->nNodes * sizeof(rtbvh::Node16), hipMemcpyHostToDevice) != hipSuccess)
+          throw std::runtime_error("writing the renumbered tree failed");
+        t->bvh.nodes.clear(), t->bvh.nodes16.clear();  // (rt_bvh_export reads the device copies)
+      } catch (const std::exception& e) {
+        return fail(RT_ERR_HIP, "device BVH build: %s", e.what());
+      }
+    }
+  } else {
+    if ((rc = upload(&t->nodes, t->bvh.nodes16.data(), t->bvh.nodes16.size() * 2)) != RT_OK ||
+        (rc = upload(&t->tris, t->bvh.tris.data(), t->bvh.tris.size() * 3)) != RT_OK ||
+        (rc = upload(&t->trisRef, t->bvh.trisRef.data(), t->bvh.trisRef.size() * 3)) != RT_OK)
+      return rc;
+    t->nNodes = static_cast<uint32_t>(t->bvh.nodes.size());
+  }
+  // The node records the pooled render kernel and rt_trace traverse (rt_options.node_format; RT_NODES=f16|q8 overrides).
+  // RT_NODES_Q8 — 16-byte records, ONE vector-memory request per visit (bvh_build.h Slot16) — is for trees the caches do
+  // not hold, where the traversal sits on the vector L1's request rate.  The other kernels (photon emission, ray streams,
+  // the wavefront integrator, the one-wave-per-workgroup render instances) keep the 32-byte records, so both forms are resident.
+  uint32_t wantNodes = nodeFormatOpt;
+  if (const char* e = getenv("RT_NODES")) wantNodes = !strcmp(e, "q8") ? (uint32_t)RT_NODES_Q8 : !strcmp(e, "f16") ? (uint32_t)RT_NODES_F16 : wantNodes;
+  if (wantNodes > RT_NODES_Q8) return fail(RT_ERR_INVALID, "unknown node_format %u", wantNodes);
+  if (wantNodes == RT_NODES_Q8) {
+    try {
+      if (gpuBuild) read_back_tree(t, sc->n_triangles);  // the packer works from the float records
+      if (t->bvh.q8.empty()) rtbvh::packQ8(t->bvh);
+      if (gpuBuild) t->bvh.nodes.clear(), t->bvh.tris.clear(), t->bvh.trisRef.clear();  // (rt_bvh_export reads the device copies)
+    } catch (const std::exception& e) {
+      return fail(RT_ERR_UNSUPPORTED, "node_format RT_NODES_Q8: %s", e.what());
+    }
+    static_assert(sizeof(rtbvh::Slot16) == sizeof(uint4), "slot layout");
+    if ((rc = upload(&t->q8, t->bvh.q8.data(), t->bvh.q8.size())) != RT_OK) return rc;
+    t->q8ShiftBytes = t->bvh.q8Shift + 4u;
+    t->nodeFormat = RT_NODES_Q8;
+    std::vector<rtbvh::Slot16>().swap(t->bvh.q8);  // (the host copy is not needed again)
+  }
+  t->buildMs = msSince();
+  if (getenv("RT_BVH_VERBOSE")) fprintf(stderr, "tree resident %.2f ms after the start\n", t->buildMs);
+  return RT_OK;
+}
+
+// *t becomes the context's tree, with every value derived from it; the tree it replaces (a rebuild) is freed, and what
+// was derived from that one's topology — the refit depth table, the quality baseline — goes with it.  Nothing here can fail.
+void install_tree(rt_ctx* c, Tree* t) {
+  rtk::DevScene& S = c->S;
+  c->bvh = std::move(t->bvh);
+  c->nodes = std::move(t->nodes), c->q8 = std::move(t->q8), c->tris = std::move(t->tris), c->trisRef = std::move(t->trisRef);
+  c->nodesF = std::move(t->nodesF);
+  c->builder = t->builder, c->nodeFormat = t->nodeFormat, c->buildMs = t->buildMs;
+  S.nodes = c->nodes.get(), S.q8 = c->q8.get(), S.tris = c->tris.get(), S.trisRef = c->trisRef.get();
+  S.n_nodes = t->nNodes, S.q8ShiftBytes = t->q8ShiftBytes;
+  S.invBoxScale = 1.f / c->bvh.boxScale;
+  S.originBound = c->bvh.originBound;
+  memcpy(&c->magRef, &c->bvh.maxAbs, 4);
+  // Pool thresholds (Trav::round's descent early exit, the steal and refill levels).  Two scene
+  // classes, as for the samples-of-a-pixel-per-wave rule: trees the caches hold (<= 65,536 nodes)
+  // are issue-bound and want long descents (12 / 8 / 24: C2 50.5 ms; 16 or 24 lanes cost 0.2-1 %);
+  // beyond that every step waits on the vector L1, and leaving the descent with up to 24 lanes still
+  // in it plus refilling at 32 hands out work sooner (C5 328.5 -> 317.4 ms, C5x8 55.0 -> 52.4 ms;
+  // profiles/r03_pool_thresholds.txt).
+  const bool bigTree = S.n_nodes > 65536;
+  S.leafT = getenv("RT_LEAFT") ? atoi(getenv("RT_LEAFT")) : bigTree ? 32 : 12;
+  S.leafMul = getenv("RT_LEAFMUL") ? atoi(getenv("RT_LEAFMUL")) : bigTree ? 32 : 22;
+  S.stealT = getenv("RT_STEALT") ? atoi(getenv("RT_STEALT")) : 8;
+  S.refillT = getenv("RT_REFILLT") ? atoi(getenv("RT_REFILLT")) : bigTree ? 32 : 24;
+  c->refitDepth.reset(), c->refitMaxDepth = 0;
+  c->costBuiltValid = false, c->refits = 0;
+}
+
 int create_ctx(const rt_scene_desc* sc, const rt_options* opt, const rtbvh::Built* prebuilt, rt_ctx** out) {
   if (!sc || !out) return fail(RT_ERR_INVALID, "scene/out is null");
   *out = nullptr;
@@ -673,126 +839,29 @@ int create_ctx(const rt_scene_desc* sc, const rt_options* opt, const rtbvh::Buil
   // (every exit before the release at the end frees what the context holds so far, on this device)
   std::unique_ptr<rt_ctx> c(new rt_ctx());
   c->device = opt ? opt->device : 0;
-  // the tree: host SAH builder, or the device builder (tiny scenes always take the host's
-  // special cases)
-  // (RT_BVH_GPU=1 / 2 / 3: the device / hybrid / host builder whatever the options say — the test suites run whole on each)
-  const char* gpuEnv = getenv("RT_BVH_GPU");
-  uint32_t wantBuilder = gpuEnv ? (uint32_t)atoi(gpuEnv) : (opt ? opt->bvh_builder : (uint32_t)RT_BVH_AUTO);
-  if (wantBuilder > RT_BVH_HOST) return fail(RT_ERR_INVALID, "unknown bvh_builder %u", wantBuilder);
-  // AUTO: the device builder gives the host builder's tree (tests/treedigest.py; profiles/r04_builders.txt) 2 ... 14 x sooner,
-  // so every scene it is faster on takes it (from 8,192 triangles: below that a build is 1-3 ms either way and the host needs no
-  // device round trip); a group of contexts given a host-built tree shares it
-  static const uint32_t autoFrom = getenv("RT_BVH_AUTO_FROM") ? (uint32_t)atoi(getenv("RT_BVH_AUTO_FROM")) : 8192u;
-  if (wantBuilder == RT_BVH_AUTO) wantBuilder = (sc->n_triangles >= autoFrom && !prebuilt) ? (uint32_t)RT_BVH_DEVICE : (uint32_t)RT_BVH_HOST;
-  // (a scene of a single part has no top to build on the host: the device builder's own path handles it)
-  const bool hybrid = wantBuilder == RT_BVH_HYBRID && sc->n_triangles > 1024u;
-  const bool gpuBuild = (wantBuilder == RT_BVH_DEVICE || wantBuilder == RT_BVH_HYBRID) && sc->n_triangles >= 16;
-  rtbvh::TopBuilt topBuilt;
-  rtbvh::ScenePlan plan;
-  std::vector<float> sizeKey;
-  const auto tBuild0 = std::chrono::steady_clock::now();
-  try {
-    if (hybrid) {
-      rtbvh::buildTop(*sc, opt ? opt->bvh_leaf_max : 0, 1024u, topBuilt);
-      if (getenv("RT_BVH_VERBOSE"))
-        fprintf(stderr, "hybrid builder: host top of %zu nodes over %zu parts in %.1f ms\n", topBuilt.nodes.size(), topBuilt.parts.size(),
-                std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - tBuild0).count());
-      c->bvh.leafMax = topBuilt.leafMax, c->bvh.pad = topBuilt.pad, c->bvh.originBound = topBuilt.originBound, c->bvh.boxScale = topBuilt.boxScale;
-      c->bvh.maxAbs = topBuilt.maxAbs;
-      c->bvh.depthCap = topBuilt.depthCap;
-      (void)rtbvh::planSceneExact(*sc, opt ? opt->bvh_leaf_max : 0, sizeKey);  // (the size keys of the subtrees' sweeps)
-    } else if (gpuBuild) {
-      // (the device build restates the host builder's splits: it takes the host's depth cap and size keys)
-      plan = rtbvh::planSceneExact(*sc, opt ? opt->bvh_leaf_max : 0, sizeKey);
-      if (getenv("RT_BVH_VERBOSE"))
-        fprintf(stderr, "device builder: validation + size keys in %.2f ms\n", std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - tBuild0).count());
-      c->bvh.leafMax = plan.leafMax, c->bvh.pad = plan.pad, c->bvh.originBound = plan.originBound, c->bvh.boxScale = plan.boxScale;
-      c->bvh.maxAbs = plan.maxAbs;
-      c->bvh.depthCap = plan.depthCap;
-    } else if (prebuilt) {
-      c->bvh = *prebuilt;
-    } else {
-      rtbvh::build(*sc, opt ? opt->bvh_leaf_max : 0, c->bvh);
-    }
-  } catch (const std::exception& e) {
-    return fail(RT_ERR_INVALID, "scene rejected: %s", e.what());
-  }
-  static_assert(sizeof(rtbvh::Node16) == 2 * sizeof(uint4), "node layout");
-  static_assert(sizeof(rtbvh::TriRec) == 3 * sizeof(float4), "triangle layout");
-  // (big scenes: the per-triangle and per-vertex host passes of rt_create are shared by a few threads — 8 M triangles
-  // spent 60 ms in them on one)
-  std::unique_ptr<uint4[]> shade(new uint4[sc->n_triangles]);
-  for (uint32_t m = 0; m < sc->n_meshes; ++m)
-    par_chunks(sc->mesh_tri_begin[m], sc->mesh_tri_begin[m + 1], [&](uint32_t, size_t tb, size_t te) {
-      for (size_t t = tb; t < te; ++t) shade[t] = make_uint4(sc->tri_vtx[3 * t], sc->tri_vtx[3 * t + 1], sc->tri_vtx[3 * t + 2], m);
-    });
-
+  c->optLeafMax = opt ? opt->bvh_leaf_max : 0u, c->optBuilder = opt ? opt->bvh_builder : (uint32_t)RT_BVH_AUTO;
+  c->optNodeFormat = opt ? opt->node_format : (uint32_t)RT_NODES_AUTO;
   rtk::DevScene& S = c->S;
-  if ((rc = upload(&c->triShade, shade.get(), (size_t)sc->n_triangles)) != RT_OK) return rc;
-  shade.reset();
-  if ((rc = upload(&c->vpos, sc->vertex_pos, (size_t)sc->n_vertices * 3)) != RT_OK ||
-      (rc = upload(&c->vnrm, sc->vertex_nrm, (size_t)sc->n_vertices * 3)) != RT_OK)
-    return rc;
-  if (gpuBuild) {
-    if (getenv("RT_BVH_VERBOSE"))
-      fprintf(stderr, "scene arrays on the device %.2f ms after the start\n", std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - tBuild0).count());
-    rtk::GpuBvh G;
-    hipError_t he = hipSuccess;
-    if (hybrid) {
-      he = rtk::gpu_bvh_build_over_top(c->vpos.get(), c->triShade.get(), sizeKey.data(), sc->n_triangles, topBuilt, &G, nullptr);
-    } else {
-      he = rtk::gpu_bvh_build_exact(c->vpos.get(), c->triShade.get(), sizeKey.data(), sc->n_triangles, plan, &G, nullptr);
-    }
-    if (he != hipSuccess) return fail(RT_ERR_HIP, "device BVH build failed: %s", hipGetErrorString(he));
-    c->nodes.reset(G.nodes16), c->tris.reset(G.tris), c->trisRef.reset(G.trisRef), c->nodesF.reset(G.nodesF);
-    c->bvh.maxDepth = G.maxDepth;
-    S.n_nodes = G.n_nodes;
-    c->builder = hybrid ? RT_BVH_HYBRID : RT_BVH_DEVICE;
-    // Trees whose top the render kernel may keep in LDS (rt_kernels.hip plan_persist: a prefix of the node array) get the host
-    // builder's final numbering — the most-visited nodes first, greedily by box area from the root (bvh_build.cpp
-    // relayoutTop) — instead of the device's pre-order: C4 loses 2 % on a pre-order tree.  64 KB ... 4 MB back and forth.
-    if (S.n_nodes >= 2u && S.n_nodes <= 65536u) {
-      try {
-        read_back_tree(c.get(), 0);
-        rtbvh::relayoutAndPack(c->bvh);
-        if (hipMemcpy(c->nodesF.get(), c->bvh.nodes.data(), (size_t)S.n_nodes * sizeof(rtbvh::Node), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(c->nodes.get(), c->bvh.nodes16.data(), (size_t)S.n_nodes * sizeof(rtbvh::Node16), hipMemcpyHostToDevice) != hipSuccess)
-          throw std::runtime_error("writing the renumbered tree failed");
-        c->bvh.nodes.clear(), c->bvh.nodes16.clear();  // (rt_bvh_export reads the device copies)
-      } catch (const std::exception& e) {
-        return fail(RT_ERR_HIP, "device BVH build: %s", e.what());
-      }
-    }
-  } else {
-    if ((rc = upload(&c->nodes, c->bvh.nodes16.data(), c->bvh.nodes16.size() * 2)) != RT_OK ||
-        (rc = upload(&c->tris, c->bvh.tris.data(), c->bvh.tris.size() * 3)) != RT_OK ||
-        (rc = upload(&c->trisRef, c->bvh.trisRef.data(), c->bvh.trisRef.size() * 3)) != RT_OK)
-      return rc;
-    S.n_nodes = static_cast<uint32_t>(c->bvh.nodes.size());
-  }
-  // The node records the pooled render kernel and rt_trace traverse (rt_options.node_format; RT_NODES=f16|q8 overrides).
-  // RT_NODES_Q8 — 16-byte records, ONE vector-memory request per visit (bvh_build.h Slot16) — is for trees the caches do
-  // not hold, where the traversal sits on the vector L1's request rate.  The other kernels (photon emission, ray streams,
-  // the wavefront integrator, the one-wave-per-workgroup render instances) keep the 32-byte records, so both forms are resident.
-  uint32_t wantNodes = opt ? opt->node_format : (uint32_t)RT_NODES_AUTO;
-  if (const char* e = getenv("RT_NODES")) wantNodes = !strcmp(e, "q8") ? (uint32_t)RT_NODES_Q8 : !strcmp(e, "f16") ? (uint32_t)RT_NODES_F16 : wantNodes;
-  if (wantNodes > RT_NODES_Q8) return fail(RT_ERR_INVALID, "unknown node_format %u", wantNodes);
-  if (wantNodes == RT_NODES_Q8) {
-    try {
-      if (gpuBuild) read_back_tree(c.get(), sc->n_triangles);  // the packer works from the float records
-      if (c->bvh.q8.empty()) rtbvh::packQ8(c->bvh);
-      if (gpuBuild) c->bvh.nodes.clear(), c->bvh.tris.clear(), c->bvh.trisRef.clear();  // (rt_bvh_export reads the device copies)
-    } catch (const std::exception& e) {
-      return fail(RT_ERR_UNSUPPORTED, "node_format RT_NODES_Q8: %s", e.what());
-    }
-    static_assert(sizeof(rtbvh::Slot16) == sizeof(uint4), "slot layout");
-    if ((rc = upload(&c->q8, c->bvh.q8.data(), c->bvh.q8.size())) != RT_OK) return rc;
-    S.q8ShiftBytes = c->bvh.q8Shift + 4u;
-    c->nodeFormat = RT_NODES_Q8;
-    std::vector<rtbvh::Slot16>().swap(c->bvh.q8);  // (the host copy is not needed again)
-  }
-  c->buildMs = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - tBuild0).count();
-  if (getenv("RT_BVH_VERBOSE")) fprintf(stderr, "tree resident %.2f ms after the start\n", c->buildMs);
+  Tree tree;
+  // (the scene's arrays go to the device once the host passes have accepted the description)
+  rc = build_tree(sc, c->optLeafMax, c->optBuilder, c->optNodeFormat, prebuilt, [&](const float** dVpos, const uint4** dTriShade) {
+    // (big scenes: the per-triangle and per-vertex host passes of rt_create are shared by a few threads — 8 M triangles
+    // spent 60 ms in them on one)
+    std::unique_ptr<uint4[]> shade(new uint4[sc->n_triangles]);
+    for (uint32_t m = 0; m < sc->n_meshes; ++m)
+      par_chunks(sc->mesh_tri_begin[m], sc->mesh_tri_begin[m + 1], [&](uint32_t, size_t tb, size_t te) {
+        for (size_t t = tb; t < te; ++t) shade[t] = make_uint4(sc->tri_vtx[3 * t], sc->tri_vtx[3 * t + 1], sc->tri_vtx[3 * t + 2], m);
+      });
+    int r = upload(&c->triShade, shade.get(), (size_t)sc->n_triangles);
+    shade.reset();
+    if (r != RT_OK || (r = upload(&c->vpos, sc->vertex_pos, (size_t)sc->n_vertices * 3)) != RT_OK ||
+        (r = upload(&c->vnrm, sc->vertex_nrm, (size_t)sc->n_vertices * 3)) != RT_OK)
+      return r;
+    *dVpos = c->vpos.get(), *dTriShade = c->triShade.get();
+    return (int)RT_OK;
+  }, &tree);
+  if (rc != RT_OK) return rc;
+  install_tree(c.get(), &tree);
   std::vector<rtd::DevMat> dm(sc->n_meshes);
   for (uint32_t m = 0; m < sc->n_meshes; ++m) dm[m] = rtd::make_dev_mat(sc->materials[m]);
   if ((rc = upload(&c->mats, sc->materials, sc->n_meshes)) != RT_OK || (rc = upload(&c->matsDev, dm.data(), dm.size())) != RT_OK ||
@@ -801,32 +870,17 @@ int create_ctx(const rt_scene_desc* sc, const rt_options* opt, const rtbvh::Buil
       (rc = upload(&c->meshVtxBegin, sc->mesh_vtx_begin, sc->n_meshes + 1)) != RT_OK)
     return rc;
   S.triShade = c->triShade.get(), S.vpos = c->vpos.get(), S.vnrm = c->vnrm.get();
-  S.nodes = c->nodes.get(), S.q8 = c->q8.get(), S.tris = c->tris.get(), S.trisRef = c->trisRef.get();
   S.mats = c->mats.get(), S.matsDev = c->matsDev.get(), S.lights = c->lights.get();
   S.meshTriBegin = c->meshTriBegin.get(), S.meshVtxBegin = c->meshVtxBegin.get();
   S.n_tris = sc->n_triangles;
   S.n_lights = sc->n_lights;
   S.n_photons = 0;
-  S.invBoxScale = 1.f / c->bvh.boxScale;
-  S.originBound = c->bvh.originBound;
   S.cam = sc->camera;
   c->hostLights.assign(sc->lights, sc->lights + sc->n_lights);
   c->nMeshes = sc->n_meshes, c->nVertices = sc->n_vertices;
-  memcpy(&c->magRef, &c->bvh.maxAbs, 4);
   c->magPos = max_abs_bits(sc->vertex_pos, 3 * (size_t)sc->n_vertices);
   c->magNrm = max_abs_bits(sc->vertex_nrm, 3 * (size_t)sc->n_vertices);
   vouch_short_forms(c.get());
-  // Pool thresholds (Trav::round's descent early exit, the steal and refill levels).  Two scene
-  // classes, as for the samples-of-a-pixel-per-wave rule: trees the caches hold (<= 65,536 nodes)
-  // are issue-bound and want long descents (12 / 8 / 24: C2 50.5 ms; 16 or 24 lanes cost 0.2-1 %);
-  // beyond that every step waits on the vector L1, and leaving the descent with up to 24 lanes still
-  // in it plus refilling at 32 hands out work sooner (C5 328.5 -> 317.4 ms, C5x8 55.0 -> 52.4 ms;
-  // profiles/r03_pool_thresholds.txt).
-  const bool bigTree = S.n_nodes > 65536;
-  S.leafT = getenv("RT_LEAFT") ? atoi(getenv("RT_LEAFT")) : bigTree ? 32 : 12;
-  S.leafMul = getenv("RT_LEAFMUL") ? atoi(getenv("RT_LEAFMUL")) : bigTree ? 32 : 22;
-  S.stealT = getenv("RT_STEALT") ? atoi(getenv("RT_STEALT")) : 8;
-  S.refillT = getenv("RT_REFILLT") ? atoi(getenv("RT_REFILLT")) : bigTree ? 32 : 24;
   S.phPos = S.phDir = nullptr, S.phTopo = nullptr;
   S.topK = 0;
   int cus = 0;
@@ -1302,6 +1356,7 @@ int rt_bvh_tune(rt_ctx* c, const rt_params* probe, double budget_seconds, uint32
   HIP_TRY(hipSetDevice(c->device));
   // (the tree may change: rt_update uploads it again)
   c->nodesF.reset(), c->refitDepth.reset();
+  if (c->refits == 0) c->costBuiltValid = false;  // (rt_bvh_quality's baseline of a tree never refit is taken again: the numbering may change)
   DevBuf<float4> dAcc;
   HIP_TRY(dev_alloc(&dAcc, (size_t)probe->width * probe->height));
   rt_params p = *probe;
@@ -1380,6 +1435,7 @@ int rt_bvh_tune(rt_ctx* c, const rt_params* probe, double budget_seconds, uint32
     c->broken = true;
     return fail(RT_ERR_STATE, "rt_bvh_tune: %s: the context is unusable", err.c_str());
   }
+  if (kept && rep.accepted) c->costBuiltValid = false, c->refits = 0;  // an accepted tuning is a build (rt_bvh_quality)
   if (out) out->probes = rep.probes, out->accepted = kept ? rep.accepted : 0u, out->cost_before = rep.cost0, out->cost_after = kept ? rep.cost1 : rep.cost0, out->seconds = rep.seconds;
   return RT_OK;
 }
@@ -1854,6 +1910,45 @@ int rt_group_render(rt_group* g, const rt_params* p, const float* bg, float* out
 // ---------------------------------------------------------------- rt_update: a resident scene follows its description
 namespace {
 
+// rt_bvh_quality_get's reduction over the context's float nodes, queued on `stream`: the pair {inner-slot sum, leaf-slot
+// sum} lands in c->dQuality at kQualityNow (the tree as it is) or kQualityBuilt (the baseline rt_update takes before its
+// first refit).  A host-built or tuned tree's float nodes go to the device first, as for a refit, and stay.
+constexpr size_t kQualityNow = 2 * (size_t)rtk::kQualityPartials, kQualityBuilt = kQualityNow + 2;
+int queue_quality(rt_ctx* c, size_t slot, hipStream_t stream) {
+  int rc = RT_OK;
+  if (!c->nodesF && (rc = upload(&c->nodesF, c->bvh.nodes.data(), c->bvh.nodes.size() * 4)) != RT_OK) return rc;
+  if (!c->dQuality) HIP_TRY(dev_alloc(&c->dQuality, kQualityBuilt + 2));
+  HIP_TRY(rtk::gpu_bvh_quality(c->nodesF.get(), c->S.n_nodes, c->dQuality.get(), c->dQuality.get() + slot, stream));
+  return RT_OK;
+}
+// cost = nodes + 1.5 tris of a pair read back from c->dQuality (the stream that wrote it has been synchronised)
+int read_quality(rt_ctx* c, size_t slot, rt_bvh_quality* q) {
+  double h[2];
+  HIP_TRY(hipMemcpy(h, c->dQuality.get() + slot, sizeof h, hipMemcpyDeviceToHost));
+  q->nodes = 1.0 + h[0], q->tris = h[1];
+  q->cost = q->nodes + 1.5 * q->tris;
+  return RT_OK;
+}
+// the whole call, after the argument checks: one launch bracketed by an event pair like a frame's, then the baseline rule
+int tree_quality(rt_ctx* c, rt_bvh_quality* q) {
+  rt_bvh_quality r{};
+  const int e = c->evUsed % kEventPairs;
+  HIP_TRY(hipEventRecord(c->ev[e][0].get(), nullptr));
+  int rc = queue_quality(c, kQualityNow, nullptr);
+  if (rc != RT_OK) return rc;
+  HIP_TRY(hipEventRecord(c->ev[e][1].get(), nullptr));
+  c->evUsed++;
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  if ((rc = read_quality(c, kQualityNow, &r)) != RT_OK) return rc;
+  // (no refit since the build: the tree as it is IS the tree as built)
+  if (!c->costBuiltValid && c->refits == 0) c->costBuilt = r.cost, c->costBuiltValid = true;
+  r.cost_built = c->costBuilt;
+  r.ratio = r.cost / r.cost_built;
+  r.n_nodes = c->S.n_nodes, r.refits = c->refits;
+  *q = r;
+  return RT_OK;
+}
+
 // what an update changes; positions / normals already on the device (the caller's arrays or the context's scratch)
 struct Update {
   const float* dPos = nullptr;
@@ -1923,7 +2018,10 @@ int update_ctx(rt_ctx* c, const Update& u, hipStream_t stream, std::chrono::stea
     }
     HIP_TRY(make_event(&e0));
     HIP_TRY(make_event(&e1));
+    // (the first refit after a build: the cost of the tree as built, rt_bvh_quality's baseline, while its boxes still stand)
+    if (!c->costBuiltValid && (rc = queue_quality(c, kQualityBuilt, stream)) != RT_OK) return rc;
   }
+  const bool baseline = refit && !c->costBuiltValid;
   // 3. the context changes: a failure from here on leaves it refusing launches
   c->broken = true;
   const size_t nv = 3 * (size_t)c->nVertices;
@@ -1954,6 +2052,12 @@ int update_ctx(rt_ctx* c, const Update& u, hipStream_t stream, std::chrono::stea
     if (he == hipSuccess && u.dPos) he = hipMemcpy(b.trisRef.data(), c->trisRef.get(), b.trisRef.size() * sizeof(rtbvh::TriRec), hipMemcpyDeviceToHost);
   }
   if (he != hipSuccess) return fail(RT_ERR_HIP, "update failed after the context had started to change (%s): it refuses launches", hipGetErrorString(he));
+  if (baseline) {
+    rt_bvh_quality built{};
+    if ((rc = read_quality(c, kQualityBuilt, &built)) != RT_OK) return rc;
+    c->costBuilt = built.cost, c->costBuiltValid = true;
+  }
+  if (refit) c->refits++;
   c->bvh.maxAbs = bits_float(magRef), c->bvh.pad = P.pad, c->bvh.originBound = P.originBound, c->bvh.boxScale = P.boxScale;
   S.invBoxScale = 1.f / P.boxScale, S.originBound = P.originBound;
   c->magRef = magRef, c->magPos = magPos, c->magNrm = magNrm;
@@ -2081,6 +2185,90 @@ int rt_group_update(rt_group* g, const rt_scene_update* u, rt_update_report* rep
   (void)hipSetDevice(g->dev[0]);
   first.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (rep) *rep = first;
+  return RT_OK;
+}
+
+}  // extern "C"
+
+// ---- rt_bvh_quality_get / rt_rebuild: a refit tree measured, and built again in place ---------------------------------
+extern "C" {
+
+int rt_bvh_quality_get(rt_ctx* c, rt_bvh_quality* out) {
+  if (!c || !out) return fail(RT_ERR_INVALID, "quality: ctx/out is null");
+  memset(out, 0, sizeof *out);
+  if (c->nodeFormat == RT_NODES_Q8) return fail(RT_ERR_UNSUPPORTED, "quality: RT_NODES_Q8 contexts keep no float nodes to measure");
+  if (c->broken) return fail(RT_ERR_STATE, "the context is in an unknown state (a failed rt_bvh_tune or rt_update): destroy it");
+  HIP_TRY(hipSetDevice(c->device));
+  return tree_quality(c, out);
+}
+
+int rt_rebuild(rt_ctx* c, const rt_rebuild_params* p, rt_rebuild_report* rep) {
+  const auto t0 = std::chrono::steady_clock::now();
+  auto msSince = [&t0] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
+  if (rep) memset(rep, 0, sizeof *rep);
+  // what the parameters say of themselves comes before anything of the context
+  if (p) {
+    for (uint32_t r : p->reserved)
+      if (r) return fail(RT_ERR_INVALID, "rebuild: reserved words must be zero");
+    if (p->min_ratio != 0.f && !(std::isfinite(p->min_ratio) && p->min_ratio >= 1.f))
+      return fail(RT_ERR_INVALID, "rebuild: min_ratio must be 0 or finite and >= 1");
+  }
+  if (!c) return fail(RT_ERR_INVALID, "rebuild: ctx is null");
+  if (c->nodeFormat == RT_NODES_Q8) return fail(RT_ERR_UNSUPPORTED, "rebuild: RT_NODES_Q8 contexts cannot be rebuilt (create the context again)");
+  if (c->broken) return fail(RT_ERR_STATE, "the context is in an unknown state (a failed rt_bvh_tune or rt_update): destroy it");
+  HIP_TRY(hipSetDevice(c->device));
+  rt_rebuild_report r{};
+  const float minRatio = p ? p->min_ratio : 0.f;
+  int rc = RT_OK;
+  if (minRatio > 0.f || rep) {
+    rt_bvh_quality q;
+    if ((rc = tree_quality(c, &q)) != RT_OK) return rc;
+    r.ratio_before = q.ratio;
+    if (minRatio > 0.f && !(q.ratio >= (double)minRatio)) {
+      r.total_ms = msSince();
+      if (rep) *rep = r;
+      return RT_OK;
+    }
+  }
+  // the description the host passes read: positions, vertex ids and mesh tables come back for the duration of the call (the
+  // builders read neither normals nor materials); the lights and the camera are the context's
+  const rtk::DevScene& S = c->S;
+  const double tRead0 = msSince();
+  std::vector<float> pos(3 * (size_t)c->nVertices);
+  std::vector<uint32_t> triVtx, meshTriBegin(c->nMeshes + 1u), meshVtxBegin(c->nMeshes + 1u);
+  {
+    std::vector<uint4> shade(S.n_tris);
+    HIP_TRY(hipMemcpy(shade.data(), c->triShade.get(), shade.size() * sizeof(uint4), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(pos.data(), c->vpos.get(), pos.size() * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(meshTriBegin.data(), c->meshTriBegin.get(), meshTriBegin.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(meshVtxBegin.data(), c->meshVtxBegin.get(), meshVtxBegin.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    rtbvh::triVtxFromShade(reinterpret_cast<const uint32_t*>(shade.data()), S.n_tris, triVtx);
+  }
+  const rt_scene_desc sc = rtbvh::residentDesc(c->nMeshes, c->nVertices, S.n_tris, pos.data(), triVtx.data(), meshTriBegin.data(),
+                                               meshVtxBegin.data(), c->hostLights.data(), (uint32_t)c->hostLights.size(), S.cam);
+  r.readback_ms = msSince() - tRead0;
+  // the new tree, beside the one the context renders with; a failure up to here leaves the context as it was
+  Tree tree;
+  rc = build_tree(&sc, c->optLeafMax, c->optBuilder, c->optNodeFormat, nullptr, [&](const float** dVpos, const uint4** dTriShade) {
+    *dVpos = c->vpos.get(), *dTriShade = c->triShade.get();
+    return (int)RT_OK;
+  }, &tree);
+  if (rc != RT_OK) return rc;
+  if (tree.nodeFormat != RT_NODES_F16) return fail(RT_ERR_UNSUPPORTED, "rebuild: the build produced RT_NODES_Q8 records (RT_NODES changed since rt_create)");
+  HIP_TRY(hipDeviceSynchronize());
+  r.build_ms = tree.buildMs, r.plan_ms = tree.planMs;
+  // the swap: moves only, then the values derived from the tree by rt_create's rules
+  install_tree(c, &tree);
+  vouch_short_forms(c);
+  r.rebuilt = 1u, r.builder = c->builder;
+  if (rep) {
+    // (from here on a failure is a failed quality call on a whole context)
+    rt_bvh_quality q;
+    if ((rc = tree_quality(c, &q)) != RT_OK) return rc;
+    r.cost_after = q.cost;
+    r.total_ms = msSince();
+    *rep = r;
+  }
   return RT_OK;
 }
 

@@ -207,6 +207,11 @@ hipError_t gpu_bvh_depths(const float4* nodesF, uint32_t n, uint8_t* dDepth, uin
 hipError_t gpu_bvh_refit(const float* dVpos, const uint4* dTriShade, uint32_t nTris, bool records, float4* tris, float4* trisRef,
                          float4* nodesF, uint4* nodes16, uint32_t nNodes, const uint8_t* dDepth, uint32_t maxDepth, float pad,
                          float boxScale, hipStream_t stream);
+// the surface-area cost of a resident tree (rt_bvh_quality_get): dOut2 = {sum over inner slots of A / A_root, sum over leaf
+// slots of cnt A / A_root} in double, through dPartial (2 x kQualityPartials doubles, 16-byte aligned as dOut2); the same
+// records give the same bits (fixed summation shape, no atomics)
+constexpr uint32_t kQualityPartials = 1024;
+hipError_t gpu_bvh_quality(const float4* nodesF, uint32_t nNodes, double* dPartial, double* dOut2, hipStream_t stream);
 // photon map on the device (kd_build.hip)
 hipError_t launch_photon_compact(const float4* slots, uint32_t n, float4* items, uint32_t* count, hipStream_t stream);
 hipError_t launch_kd_build(float4* items, uint32_t n, int depthOverride, hipStream_t stream);

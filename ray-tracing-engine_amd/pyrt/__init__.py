@@ -101,6 +101,27 @@ class UpdateReport(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
 
 
+class BvhQuality(C.Structure):
+    _fields_ = [("cost", C.c_double), ("nodes", C.c_double), ("tris", C.c_double), ("cost_built", C.c_double),
+                ("ratio", C.c_double), ("n_nodes", C.c_uint32), ("refits", C.c_uint32), ("reserved", C.c_uint64 * 4)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
+
+
+class RebuildParams(C.Structure):
+    _fields_ = [("min_ratio", C.c_float), ("reserved", C.c_uint32 * 7)]
+
+
+class RebuildReport(C.Structure):
+    _fields_ = [("rebuilt", C.c_uint32), ("builder", C.c_uint32), ("ratio_before", C.c_double), ("cost_after", C.c_double),
+                ("build_ms", C.c_double), ("total_ms", C.c_double), ("readback_ms", C.c_double), ("plan_ms", C.c_double),
+                ("reserved", C.c_uint64 * 4)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
+
+
 XF_STATIC = 1
 
 
@@ -293,7 +314,7 @@ AMD_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_create", "rt_destroy", "rt
                "rt_update", "rt_update_vertices_device", "rt_update_transforms", "rt_group_update", "rt_render_aov", "rt_render_aov_device",
                "rt_denoise", "rt_denoise_device", "rt_render_adaptive", "rt_render_adaptive_device", "rt_render_views",
                "rt_render_views_device", "rt_render_motion", "rt_render_motion_device", "rt_temporal_accumulate",
-               "rt_temporal_accumulate_device", "rt_svgf", "rt_svgf_device"]
+               "rt_temporal_accumulate_device", "rt_svgf", "rt_svgf_device", "rt_bvh_quality_get", "rt_rebuild"]
 HOST_SYMBOLS = ["rt_host_scene_build", "rt_host_scene_desc", "rt_host_scene_free", "rt_host_last_error",
                 "rt_host_fill_background", "rt_host_save_ppm", "rt_host_kd_order", "rt_host_light_basis"]
 
@@ -370,6 +391,8 @@ def amd():
         L.rt_update_vertices_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(UpdateReport)]
         L.rt_update_transforms.argtypes = [C.c_void_p, C.POINTER(TransformUpdate), C.c_void_p, C.POINTER(UpdateReport)]
         L.rt_group_update.argtypes = [C.c_void_p, C.POINTER(SceneUpdate), C.POINTER(UpdateReport)]
+        L.rt_bvh_quality_get.argtypes = [C.c_void_p, C.POINTER(BvhQuality)]
+        L.rt_rebuild.argtypes = [C.c_void_p, C.POINTER(RebuildParams), C.POINTER(RebuildReport)]
         L.rt_render_aov.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Aov)]
         L.rt_render_aov_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Aov), C.c_void_p]
         L.rt_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.POINTER(Aov), C.c_void_p]
@@ -618,6 +641,22 @@ class Context:
         x.d_prev_pos = int(d_prev_pos) if d_prev_pos else None
         rep = UpdateReport()
         _check(amd().rt_update_transforms(self._h, C.byref(x), C.c_void_p(stream or None), C.byref(rep)))
+        return rep.as_dict()
+
+    def bvh_quality(self):
+        """rt_bvh_quality_get: the surface-area cost of the resident tree (cost, nodes, tris), the same measure of the tree
+        as last built (cost_built), their ratio, n_nodes and the refits since the build, as a dict."""
+        q = BvhQuality()
+        _check(amd().rt_bvh_quality_get(self._h, C.byref(q)))
+        return q.as_dict()
+
+    def rebuild(self, min_ratio=0.0):
+        """rt_rebuild: the tree built again from the resident arrays — always (min_ratio 0), or only if bvh_quality's
+        ratio has reached min_ratio (>= 1).  Returns the report as a dict."""
+        p = RebuildParams()
+        p.min_ratio = min_ratio
+        rep = RebuildReport()
+        _check(amd().rt_rebuild(self._h, C.byref(p), C.byref(rep)))
         return rep.as_dict()
 
     def bvh_export(self):
