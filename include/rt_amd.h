@@ -28,6 +28,8 @@
  *                                  not yet converged (+ _device form)
  *   rt_render_views             <- (no counterpart) the frames of many cameras of one resident scene in one launch
  *                                  (+ _device form)
+ *   rt_render_aov_views / rt_render_motion_views / rt_denoise_batch <- (no counterpart) the AOVs, motion vectors and
+ *                                  denoised frames of those views, one launch each (+ _device forms)
  *   rt_trace                    <- RayTracer::rayTrace (RayTracer.h:27-53) test hook
  *   rt_knn / rt_knn_wide        <- kdtree::knearest (kdtree.h:180-195) test hooks
  *
@@ -669,6 +671,47 @@ int rt_render_views(rt_ctx* ctx, const rt_params* p, const rt_views* v, const fl
  * call's upload of the view records. */
 int rt_render_views_device(rt_ctx* ctx, const rt_params* p, const rt_views* v, void* d_accum, void* stream,
                            rt_stats* stats);
+
+/* Per-view AOVs, motion vectors and a batched denoiser for the same views: one launch each where a caller would loop over
+ * the views with rt_update(camera), rt_render_aov, rt_render_motion and rt_denoise.  Every output is [n_views] slices of
+ * its single-view shape: slice j of a channel of c floats or words per pixel starts at j * h * w * c (formed in 64 bits).
+ *
+ * rt_render_aov_views: slice j of every non-NULL channel is, bit for bit, what rt_render_aov writes for the same p on this
+ * context after a camera-only rt_update to cameras[j], with p->seed replaced by seeds[j] (p->seed when seeds is NULL); the
+ * pixel index of the RNG stream is local to the view.  NULL channels are not written and shift nothing.
+ * rt_render_motion_views: slice j is, bit for bit, rt_render_motion after that update with seeds[j] and
+ * prev->camera = &prev->cameras[j] (NULL cameras: last frame's cameras are v->cameras; with a NULL vertex_pos too, every hit
+ * has motion (0, 0) exactly).
+ * The context's own camera does not change.  A view camera that needs a wider box padding refits once to the widest
+ * padding any view needs, which the context keeps, exactly as rt_render_views does — RT_ERR_UNSUPPORTED on RT_NODES_Q8
+ * contexts, which otherwise walk their resident 32-byte records as rt_render_aov does.  RT_ACCEL_BRUTE works.
+ * Validation comes first; a rejected call writes nothing and leaves the context as it was.  RT_ERR_INVALID: a null ctx, p,
+ * v, cameras, prev or output struct; non-zero reserved words; rt_render_aov's size and range checks (mode, max_depth, the
+ * photon fields and the wavefront bit do not affect the passes); rt_render_views' checks of v (n_views 1..65535,
+ * n_views * width * height < 2^31, the camera rule); a non-finite view camera or previous camera, naming the view in
+ * rt_last_error.  RT_ERR_UNSUPPORTED: world > 1.  With valid arguments and no device: RT_ERR_NO_DEVICE.
+ * The device forms do not synchronise, except to refit and for the previous call's upload of the view tables, as
+ * rt_render_views_device; the context's view scratch serves one call at a time.                                       */
+int rt_render_aov_views(rt_ctx* ctx, const rt_params* p, const rt_views* v, const rt_aov* host_out);
+int rt_render_aov_views_device(rt_ctx* ctx, const rt_params* p, const rt_views* v, const rt_aov* device_out, void* stream);
+typedef struct rt_motion_prev_views {
+  const float* vertex_pos;        /* as rt_motion_prev: last frame's positions, or NULL = the context's own            */
+  const rt_camera* cameras;       /* [n_views] HOST memory: last frame's camera of each view, or NULL = v->cameras     */
+  uint32_t reserved[6];           /* zero */
+} rt_motion_prev_views;
+int rt_render_motion_views(rt_ctx* ctx, const rt_params* p, const rt_views* v, const rt_motion_prev_views* prev,
+                           const rt_motion* host_out);
+int rt_render_motion_views_device(rt_ctx* ctx, const rt_params* p, const rt_views* v, const rt_motion_prev_views* prev,
+                                  const rt_motion* device_out, void* stream);
+/* rt_denoise over n_frames frames of d->width x d->height: rgb, out and the four guide channels hold [n_frames] slices.
+ * Frame j of out is, bit for bit, rt_denoise of slice j: the taps never leave their frame (a stack is not a tall image),
+ * and the default sigma_position is computed once, by rt_denoise's reduction.  One packing launch and one launch per
+ * iteration over all frames; the context's filter scratch grows to n_frames x a frame's need and serves one call at a
+ * time.  rgb may equal out.  RT_ERR_INVALID: rt_denoise's cases, non-zero reserved words, n_frames of 0 or
+ * n_frames * width * height of 2^31 or more; with valid arguments and no device: RT_ERR_NO_DEVICE.                    */
+int rt_denoise_batch(rt_ctx* ctx, const rt_denoise_params* d, uint32_t n_frames, const float* rgb, const rt_aov* aov, float* out);
+int rt_denoise_batch_device(rt_ctx* ctx, const rt_denoise_params* d, uint32_t n_frames, const void* d_rgb, const rt_aov* d_aov,
+                            void* d_out, void* stream);
 
 /* ---- multi-GPU (Renderer.cpp:219-265 sharded by pixel tiles) -------------
  * A tile-sharded frame: rank r of `world` integrates the pixels whose `tile`-pixel granule

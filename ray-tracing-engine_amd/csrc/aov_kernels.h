@@ -1,4 +1,5 @@
-// aov_kernels.h — first-hit AOVs (arbitrary output variables) of a frame's primary rays: rt_render_aov.
+// aov_kernels.h — first-hit AOVs (arbitrary output variables) of a frame's primary rays: rt_render_aov, and of the frames
+// of many cameras in one launch: rt_render_aov_views.
 //
 // The primary rays of wf_generate (RNG stream of (pixel, sample), jitter_sample, camera_ray), cast through the same
 // closest-hit walk (or the exhaustive loop), and at the hit vertex_setup_ray: the shading normal, the hit point and the
@@ -7,22 +8,49 @@
 // nothing.  Channels whose pointer is null are not written.
 // (included by rt_kernels.hip inside namespace rtk: shares its device functions)
 
-template <bool BRUTE>
+// The view of a wave of a multi-view pass (k_aov<.., true>, k_motion<.., true>): workgroup b of the launch is tile
+// b % tilesPerView of view b / tilesPerView.  The block index is wave-uniform, so the view's record is read with scalar
+// loads through the constant address space and stays in SGPRs, as render_tile reads it.
+struct ViewOfWave {
+  uint32_t view, tile;
+  rt_camera cam;
+  uint32_t seed;
+};
+RT_DEV ViewOfWave view_of_wave(const ViewRec* views, uint32_t tilesPerView) {
+  typedef const __attribute__((address_space(4))) ViewRec* const_view_ptr;
+  ViewOfWave w;
+  w.view = blockIdx.x / tilesPerView, w.tile = blockIdx.x - w.view * tilesPerView;
+  const const_view_ptr R = (const_view_ptr)views + w.view;
+  for (int j = 0; j < 3; ++j)
+    w.cam.position[j] = R->cam.position[j], w.cam.lower_left[j] = R->cam.lower_left[j],
+    w.cam.horizontal[j] = R->cam.horizontal[j], w.cam.vertical[j] = R->cam.vertical[j];
+  w.seed = R->seed;
+  return w;
+}
+
+// VIEWS = false: the frame of S.cam and A.seed, one workgroup per tile (rt_render_aov; the instance reads none of the view
+// fields and is the kernel it was before they existed).  VIEWS = true: n_views x A.tilesPerView workgroups, view-major; the tile,
+// the camera and the seed are the wave's view's, the pixel index that feeds the RNG stream is local to the view, and every
+// channel is written into the view's slice (view_slice, in 64 bits).
+template <bool BRUTE, bool VIEWS>
 __global__ __launch_bounds__(64) void k_aov(DevScene S, AovArgs A) {
   __shared__ uint32_t lds[(rtbvh::kMaxDepth + 1) * 64];
+  ViewOfWave vw;
+  if constexpr (VIEWS) vw = view_of_wave(A.views, A.tilesPerView);
   const uint32_t tilesX = (A.width + 7u) / 8u;
-  const uint32_t px = (blockIdx.x % tilesX) * 8u + (threadIdx.x & 7u), py = (blockIdx.x / tilesX) * 8u + (threadIdx.x >> 3);
+  const uint32_t tile = VIEWS ? vw.tile : blockIdx.x;
+  const uint32_t px = (tile % tilesX) * 8u + (threadIdx.x & 7u), py = (tile / tilesX) * 8u + (threadIdx.x >> 3);
   const bool in = px < A.width && py < A.height;
   const uint32_t pix = py * A.width + px;
   f3 alb = mk(0.f, 0.f, 0.f), nsum = mk(0.f, 0.f, 0.f), psum = mk(0.f, 0.f, 0.f);
   float dsum = 0.f;
   uint32_t nhit = 0, mesh0 = 0xffffffffu, tri0 = 0xffffffffu;
   for (uint32_t smp = A.s0; smp < A.s1; smp++) {  // (wave-uniform: the walk below needs every lane of the wave)
-    Rng g{rt_stream_seed(A.seed, RT_STREAM_PIXEL, pix, smp)};
+    Rng g{rt_stream_seed(VIEWS ? vw.seed : A.seed, RT_STREAM_PIXEL, pix, smp)};
     float sx, sy;
     jitter_sample(g, (int)smp, (int)A.spp, sx, sy);
     f3 o, d;
-    camera_ray(S.cam, ((float)px + sx) / (float)A.width, 1.f - ((float)py + sy) / (float)A.height, o, d);
+    camera_ray(VIEWS ? vw.cam : S.cam, ((float)px + sx) / (float)A.width, 1.f - ((float)py + sy) / (float)A.height, o, d);
     HitRec h;
     LaneStats st;
     const bool hit = cast<BRUTE, false, false, LT_NONE>(S, in, o, d, lds + threadIdx.x, h, st);
@@ -40,20 +68,30 @@ __global__ __launch_bounds__(64) void k_aov(DevScene S, AovArgs A) {
     }
   }
   if (!in) return;
-  const size_t p3 = 3 * (size_t)pix;
+  const size_t p1 = (VIEWS ? view_slice(vw.view, A.width, A.height, 1) : 0) + pix, p3 = 3 * p1;
   if (A.albedo) A.albedo[p3] = alb.x, A.albedo[p3 + 1] = alb.y, A.albedo[p3 + 2] = alb.z;
   if (A.normal) A.normal[p3] = nsum.x, A.normal[p3 + 1] = nsum.y, A.normal[p3 + 2] = nsum.z;
   if (A.position) A.position[p3] = psum.x, A.position[p3 + 1] = psum.y, A.position[p3 + 2] = psum.z;
-  if (A.depth) A.depth[pix] = dsum;
-  if (A.hits) A.hits[pix] = nhit;
-  if (A.mesh) A.mesh[pix] = mesh0;
-  if (A.tri) A.tri[pix] = tri0;
+  if (A.depth) A.depth[p1] = dsum;
+  if (A.hits) A.hits[p1] = nhit;
+  if (A.mesh) A.mesh[p1] = mesh0;
+  if (A.tri) A.tri[p1] = tri0;
 }
 
 hipError_t launch_aov(bool brute_force, const DevScene& S, const AovArgs& A, hipStream_t stream) {
   const uint32_t tiles = ((A.width + 7u) / 8u) * ((A.height + 7u) / 8u);
   if (tiles == 0 || A.s1 <= A.s0) return hipSuccess;
-  if (brute_force) hipLaunchKernelGGL(k_aov<true>, dim3(tiles), dim3(64), 0, stream, S, A);
-  else hipLaunchKernelGGL(k_aov<false>, dim3(tiles), dim3(64), 0, stream, S, A);
+  if (brute_force) hipLaunchKernelGGL((k_aov<true, false>), dim3(tiles), dim3(64), 0, stream, S, A);
+  else hipLaunchKernelGGL((k_aov<false, false>), dim3(tiles), dim3(64), 0, stream, S, A);
+  return hipGetLastError();
+}
+
+hipError_t launch_aov_views(bool brute_force, const DevScene& S, const AovArgs& A, const ViewRec* views, uint32_t nViews, hipStream_t stream) {
+  AovArgs V = A;
+  V.views = views, V.tilesPerView = ((A.width + 7u) / 8u) * ((A.height + 7u) / 8u);
+  if (V.tilesPerView == 0 || nViews == 0 || A.s1 <= A.s0) return hipSuccess;
+  if ((uint64_t)V.tilesPerView * nViews > 0x7fffffffull) return hipErrorInvalidValue;  // (a tile holds a pixel: n w h < 2^31 keeps it below)
+  if (brute_force) hipLaunchKernelGGL((k_aov<true, true>), dim3(V.tilesPerView * nViews), dim3(64), 0, stream, S, V);
+  else hipLaunchKernelGGL((k_aov<false, true>), dim3(V.tilesPerView * nViews), dim3(64), 0, stream, S, V);
   return hipGetLastError();
 }

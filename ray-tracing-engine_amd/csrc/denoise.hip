@@ -8,6 +8,7 @@
 //   k_dn_pack        per pixel the guides, the albedo factor and the demodulated colour (filters_device.h demodulate)
 //   k_dn_iter        one iteration (step 2^i): 5x5 taps straight from global memory through L1 / L2; the last one
 //                    multiplies the factor back and writes the [h][w][3] output
+//   k_dn_iter_batch  the same iteration over a stack of frames (rt_denoise_batch): one launch, the frame a grid dimension
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -59,14 +60,12 @@ __global__ __launch_bounds__(256) void k_dn_pack(uint32_t n, const float* __rest
   g0[i] = d.g0, g1[i] = d.g1, fac[i] = d.fac, col[i] = make_float4(d.r, d.g, d.b, 0.f);
 }
 
-// 16x16 pixels per workgroup (four waves of 16x4)
-__global__ __launch_bounds__(256) void k_dn_iter(uint32_t W, uint32_t H, int step, float isc, float isn,
-                                                 const float* __restrict__ isxp, const float4* __restrict__ g0,
-                                                 const float4* __restrict__ g1, const float4* __restrict__ fac,
-                                                 const float4* __restrict__ cin, float4* __restrict__ cout,
-                                                 float* __restrict__ out) {
-  const int x = (int)(blockIdx.x * 16u + (threadIdx.x & 15u)), y = (int)(blockIdx.y * 16u + (threadIdx.x >> 4));
-  if (x >= (int)W || y >= (int)H) return;
+// Pixel (x, y) of one iteration over ONE frame of W x H pixels: every plane pointer is the frame's own (its first
+// pixel), so no tap leaves the frame.  k_dn_iter hands in the image, k_dn_iter_batch a frame's slice of a stack.
+__device__ __forceinline__ void dn_iter_pixel(int x, int y, uint32_t W, uint32_t H, int step, float isc, float isn,
+                                              const float* __restrict__ isxp, const float4* __restrict__ g0,
+                                              const float4* __restrict__ g1, const float4* __restrict__ fac,
+                                              const float4* __restrict__ cin, float4* __restrict__ cout, float* __restrict__ out) {
   const size_t p = (size_t)y * W + x;
   const float4 np = g0[p], cp = cin[p];
   float4 res = cp;
@@ -100,6 +99,32 @@ __global__ __launch_bounds__(256) void k_dn_iter(uint32_t W, uint32_t H, int ste
   out[3 * p + 2] = np.w != 0.f ? res.z * f.z : res.z;
 }
 
+// 16x16 pixels per workgroup (four waves of 16x4)
+__global__ __launch_bounds__(256) void k_dn_iter(uint32_t W, uint32_t H, int step, float isc, float isn,
+                                                 const float* __restrict__ isxp, const float4* __restrict__ g0,
+                                                 const float4* __restrict__ g1, const float4* __restrict__ fac,
+                                                 const float4* __restrict__ cin, float4* __restrict__ cout,
+                                                 float* __restrict__ out) {
+  const int x = (int)(blockIdx.x * 16u + (threadIdx.x & 15u)), y = (int)(blockIdx.y * 16u + (threadIdx.x >> 4));
+  if (x >= (int)W || y >= (int)H) return;
+  dn_iter_pixel(x, y, W, H, step, isc, isn, isxp, g0, g1, fac, cin, cout, out);
+}
+
+// The same over a stack of nFrames frames (rt_denoise_batch): the frame is the grid's z dimension (a stride loop past
+// 65,535 frames) and a slice base added to every plane, in 64 bits; x, y and the taps stay inside the frame.
+__global__ __launch_bounds__(256) void k_dn_iter_batch(uint32_t W, uint32_t H, uint32_t nFrames, int step, float isc, float isn,
+                                                       const float* __restrict__ isxp, const float4* __restrict__ g0,
+                                                       const float4* __restrict__ g1, const float4* __restrict__ fac,
+                                                       const float4* __restrict__ cin, float4* __restrict__ cout,
+                                                       float* __restrict__ out) {
+  const int x = (int)(blockIdx.x * 16u + (threadIdx.x & 15u)), y = (int)(blockIdx.y * 16u + (threadIdx.x >> 4));
+  if (x >= (int)W || y >= (int)H) return;
+  for (uint32_t f = blockIdx.z; f < nFrames; f += gridDim.z) {
+    const size_t b = view_slice(f, W, H, 1);
+    dn_iter_pixel(x, y, W, H, step, isc, isn, isxp, g0 + b, g1 + b, fac + b, cin + b, cout + b, out ? out + 3 * b : nullptr);
+  }
+}
+
 }  // namespace
 
 hipError_t launch_ref_extent(const DevScene& S, uint32_t* ext, hipStream_t stream) {
@@ -120,25 +145,37 @@ hipError_t launch_filter_sigmas(const DevScene& S, FilterBlock* block, float sig
   return hipGetLastError();
 }
 
-hipError_t launch_denoise(const DevScene& S, const DenoiseArgs& D, hipStream_t stream) {
-  const size_t n = (size_t)D.width * D.height;
+// nFrames frames of D.width x D.height stacked in every buffer; batch: the frame-indexed iteration kernel
+static hipError_t denoise_frames(const DevScene& S, const DenoiseArgs& D, uint32_t nFrames, bool batch, hipStream_t stream) {
+  const size_t n = (size_t)D.width * D.height * nFrames;
   if (n == 0) return hipSuccess;
   FilterScratch s = carve_filter_scratch(D.scratch, n);
   const hipError_t e = launch_filter_sigmas(S, s.block, D.sigma_position, D.sigma_position, 0.02f, stream);
   if (e != hipSuccess) return e;
+  // (the guides, the factor and the demodulated colour are per pixel: a stack packs as one image does)
   hipLaunchKernelGGL(k_dn_pack, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, (uint32_t)n, D.rgb, D.albedo, D.normal,
                      D.position, D.hits, s.g0, s.g1, s.fac, s.ca);
-  const dim3 grid((D.width + 15u) / 16u, (D.height + 15u) / 16u);
+  const dim3 grid((D.width + 15u) / 16u, (D.height + 15u) / 16u, batch ? (nFrames < 65535u ? nFrames : 65535u) : 1u);
   const float isn = 1.f / (D.sigma_normal * D.sigma_normal);
   for (uint32_t it = 0; it < D.iterations; it++) {
     const float sc = D.sigma_color * ldexpf(1.f, -(int)it);  // the colour sigma halves every iteration
     const bool last = it + 1 == D.iterations;
-    hipLaunchKernelGGL(k_dn_iter, grid, dim3(256), 0, stream, D.width, D.height, 1 << it, 1.f / (sc * sc), isn, &s.block->isx, s.g0,
-                       s.g1, s.fac, s.ca, s.cb, last ? D.out : nullptr);
+    if (batch)
+      hipLaunchKernelGGL(k_dn_iter_batch, grid, dim3(256), 0, stream, D.width, D.height, nFrames, 1 << it, 1.f / (sc * sc), isn,
+                         &s.block->isx, s.g0, s.g1, s.fac, s.ca, s.cb, last ? D.out : nullptr);
+    else
+      hipLaunchKernelGGL(k_dn_iter, grid, dim3(256), 0, stream, D.width, D.height, 1 << it, 1.f / (sc * sc), isn, &s.block->isx, s.g0,
+                         s.g1, s.fac, s.ca, s.cb, last ? D.out : nullptr);
     float4* t = s.ca;
     s.ca = s.cb, s.cb = t;
   }
   return hipGetLastError();
+}
+
+hipError_t launch_denoise(const DevScene& S, const DenoiseArgs& D, hipStream_t stream) { return denoise_frames(S, D, 1, false, stream); }
+
+hipError_t launch_denoise_batch(const DevScene& S, const DenoiseArgs& D, uint32_t nFrames, hipStream_t stream) {
+  return denoise_frames(S, D, nFrames, true, stream);
 }
 
 }  // namespace rtk

@@ -54,6 +54,10 @@ struct DenoiseArgs {
   float4* scratch;
 };
 hipError_t launch_denoise(const DevScene& S, const DenoiseArgs& D, hipStream_t stream);
+// the same filter over nFrames frames of width x height stacked in every buffer (rt_denoise_batch): one pack launch and
+// one launch per iteration over all frames, no tap across a frame boundary, the sigma reduction once; scratch =
+// nFrames * filter_scratch(width, height) float4, nFrames * width * height < 2^31
+hipError_t launch_denoise_batch(const DevScene& S, const DenoiseArgs& D, uint32_t nFrames, hipStream_t stream);
 
 // temporal accumulation (temporal.hip, rt_temporal_accumulate): the history reprojected along the motion vectors and
 // blended with the current frame; all buffers device memory.  filters_device.h reproject_blend reads the fields from

@@ -222,6 +222,11 @@ struct rt_ctx {
   uint32_t vwCap = 0;
   Event vwStaged;
   bool vwStagedSet = false;
+  // rt_render_motion_views_device: last frame's camera of every view, a table beside vwRecs (ViewRec stays 64 bytes) with
+  // its own pinned copy; uploaded ahead of the view records on the same stream, so vwStaged covers both
+  DevBuf<rt_camera> vwPrevCams;
+  PinnedBuf<rt_camera> vwPrevHost;
+  uint32_t vwPrevCap = 0;
 };
 
 namespace {
@@ -353,9 +358,8 @@ int ensure_granules(rt_ctx* c, const rt_params* p, uint32_t rank, const rt_ctx::
   return RT_OK;
 }
 
-int check_params(const rt_ctx* c, const rt_params* p) {
-  if (!p) return fail(RT_ERR_INVALID, "params is null");
-  if (c->broken) return fail(RT_ERR_STATE, "the context's device tree is in an unknown state (a failed rt_bvh_tune or rt_update): destroy it");
+// The checks of check_params that look at p alone (the multi-view passes answer them before they look at the context).
+int check_params_shape(const rt_params* p) {
   if (p->width == 0 || p->height == 0 || p->width > 65535u || p->height > 65535u)
     return fail(RT_ERR_INVALID, "image size %ux%u out of range", p->width, p->height);
   if (p->spp == 0) return fail(RT_ERR_INVALID, "spp must be >= 1");
@@ -369,6 +373,14 @@ int check_params(const rt_ctx* c, const rt_params* p) {
   if (p->tile % 8 != 0) return fail(RT_ERR_INVALID, "tile must be a multiple of 8");
   if (p->spp_count && (uint64_t)p->spp_begin + p->spp_count > p->spp)
     return fail(RT_ERR_INVALID, "sample range [%u,+%u) exceeds spp %u", p->spp_begin, p->spp_count, p->spp);
+  return RT_OK;
+}
+
+int check_params(const rt_ctx* c, const rt_params* p) {
+  if (!p) return fail(RT_ERR_INVALID, "params is null");
+  if (c->broken) return fail(RT_ERR_STATE, "the context's device tree is in an unknown state (a failed rt_bvh_tune or rt_update): destroy it");
+  const int rc = check_params_shape(p);
+  if (rc != RT_OK) return rc;
   if (p->use_photons) {
     if (c->S.n_photons == 0) return fail(RT_ERR_STATE, "use_photons set but no photons were uploaded (rt_set_photons)");
     if (p->k < 1 || p->k > RT_KNN_KMAX) return fail(RT_ERR_UNSUPPORTED, "k must be in 1..%d", RT_KNN_KMAX);
@@ -2344,6 +2356,16 @@ int check_not_broken(const rt_ctx* c) {
   return c->broken ? fail(RT_ERR_STATE, "the context's device tree is in an unknown state: destroy it") : RT_OK;
 }
 
+// (a context exists only where a device does: the entry points that take a handle unchecked up to here ask this first)
+int check_device_present() {
+  int n = 0;
+  const hipError_t e = hipGetDeviceCount(&n);
+  if (e != hipSuccess || n <= 0)
+    return fail(RT_ERR_NO_DEVICE, "no HIP device available (%s); this library has no CPU path",
+                e == hipSuccess ? "device count is 0" : hipGetErrorString(e));
+  return RT_OK;
+}
+
 // Everything rt_denoise and rt_denoise_device check before they look at the context.
 int denoise_checks(const rt_ctx* c, const rt_denoise_params* d, const void* rgb, const rt_aov* aov, const void* out) {
   if (!c || !d || !rgb || !aov || !out) return fail(RT_ERR_INVALID, "null argument");
@@ -2361,15 +2383,29 @@ int ensure_filter_scratch(rt_ctx* c, size_t need) {
 }
 
 // rt_render_aov's own view of p: the fields that do not affect the pass are neutralised before rt_render's checks
+rt_params aov_params(const rt_params& p) {
+  rt_params q = p;
+  q.mode = RT_MODE_RAY, q.max_depth = 1, q.use_photons = 0, q.k = 0, q.photons_requested = 0;
+  return q;
+}
 int aov_checks(const rt_ctx* c, const rt_params* p, rt_params* q) {
   if (!c) return fail(RT_ERR_INVALID, "ctx is null");
   if (!p) return fail(RT_ERR_INVALID, "params is null");
-  *q = *p;
-  q->mode = RT_MODE_RAY, q->max_depth = 1, q->use_photons = 0, q->k = 0, q->photons_requested = 0;
+  *q = aov_params(*p);
   int rc = check_params(c, q);
   if (rc != RT_OK) return rc;
   if (q->world > 1) return fail(RT_ERR_UNSUPPORTED, "tile-sharded AOVs (world %u) are not supported", q->world);
   return RT_OK;
+}
+
+rtk::AovArgs aov_args(const rt_params& q, const rt_aov& out) {
+  rtk::AovArgs A;
+  A.albedo = out.albedo, A.normal = out.normal, A.position = out.position, A.depth = out.depth;
+  A.hits = out.hits, A.mesh = out.mesh, A.tri = out.tri;
+  A.width = q.width, A.height = q.height, A.spp = q.spp, A.seed = q.seed;
+  A.s0 = q.spp_count ? q.spp_begin : 0;
+  A.s1 = q.spp_count ? q.spp_begin + q.spp_count : q.spp;
+  return A;
 }
 
 }  // namespace
@@ -2382,12 +2418,7 @@ int rt_render_aov_device(rt_ctx* c, const rt_params* p, const rt_aov* out, void*
   if (rc != RT_OK) return rc;
   if (!out) return fail(RT_ERR_INVALID, "aov is null");
   HIP_TRY(hipSetDevice(c->device));
-  rtk::AovArgs A;
-  A.albedo = out->albedo, A.normal = out->normal, A.position = out->position, A.depth = out->depth;
-  A.hits = out->hits, A.mesh = out->mesh, A.tri = out->tri;
-  A.width = q.width, A.height = q.height, A.spp = q.spp, A.seed = q.seed;
-  A.s0 = q.spp_count ? q.spp_begin : 0;
-  A.s1 = q.spp_count ? q.spp_begin + q.spp_count : q.spp;
+  const rtk::AovArgs A = aov_args(q, *out);
   const hipError_t he = rtk::launch_aov(q.accel == RT_ACCEL_BRUTE, c->S, A, static_cast<hipStream_t>(stream));
   if (he != hipSuccess) return fail(RT_ERR_HIP, "AOV launch failed: %s", hipGetErrorString(he));
   return RT_OK;
@@ -2631,12 +2662,7 @@ int svgf_checks(const rt_ctx* c, const rt_svgf_params* s, const float* cur_rgb, 
       if (outs[j] && overlap(outs[i], outBytes[i], outs[j], outBytes[j])) return fail(RT_ERR_INVALID, "the outputs must not alias one another");
   }
   // (the context exists only where a device does; a handle is not looked at before this)
-  int n = 0;
-  const hipError_t e = hipGetDeviceCount(&n);
-  if (e != hipSuccess || n <= 0)
-    return fail(RT_ERR_NO_DEVICE, "no HIP device available (%s); this library has no CPU path",
-                e == hipSuccess ? "device count is 0" : hipGetErrorString(e));
-  return RT_OK;
+  return check_device_present();
 }
 
 }  // namespace
@@ -2875,12 +2901,8 @@ int rt_render_adaptive(rt_ctx* c, const rt_params* p, const rt_adaptive_params* 
 // ---- many views of one scene (DESIGN.md "Multi-view frames") --------------------------------------------------------
 namespace {
 
-// Everything a multi-view frame checks before it touches the device, and the padding its farthest view needs:
-// *refit = true when that is wider than the context's (rt_amd.h: the camera rule).
-int views_checks(rt_ctx* c, const rt_params* p, const rt_views* v, rtbvh::Padding* pad, bool* refit) {
-  if (!c || !p || !v || !v->cameras) return fail(RT_ERR_INVALID, "ctx/params/views/cameras is null");
-  int rc = check_params(c, p);
-  if (rc != RT_OK) return rc;
+// What a multi-view frame checks in p and v alone ...
+int views_shape_checks(const rt_params* p, const rt_views* v) {
   if (v->reserved0) return fail(RT_ERR_INVALID, "rt_views.reserved0 must be zero");
   for (uint32_t r : v->reserved)
     if (r) return fail(RT_ERR_INVALID, "rt_views.reserved must be zero");
@@ -2889,6 +2911,15 @@ int views_checks(rt_ctx* c, const rt_params* p, const rt_views* v, rtbvh::Paddin
     return fail(RT_ERR_INVALID, "%u views of %ux%u pixels: 2^31 pixels or more", v->n_views, p->width, p->height);
   if (p->world > 1) return fail(RT_ERR_UNSUPPORTED, "tile-sharded multi-view frames (world %u) are not supported", p->world);
   if (p->reserved[2] & 1u) return fail(RT_ERR_UNSUPPORTED, "multi-view frames do not run the wavefront integrator");
+  return RT_OK;
+}
+// ... and everything it checks before it touches the device, and the padding its farthest view needs:
+// *refit = true when that is wider than the context's (rt_amd.h: the camera rule).
+int views_checks(rt_ctx* c, const rt_params* p, const rt_views* v, rtbvh::Padding* pad, bool* refit) {
+  if (!c || !p || !v || !v->cameras) return fail(RT_ERR_INVALID, "ctx/params/views/cameras is null");
+  int rc = check_params(c, p);
+  if (rc != RT_OK) return rc;
+  if ((rc = views_shape_checks(p, v)) != RT_OK) return rc;
   // rt_update's rules, per view camera in place of the context's
   const float magRef = bits_float(c->magRef);
   *pad = rtbvh::Padding{c->bvh.pad, c->bvh.originBound, c->bvh.boxScale};
@@ -3025,6 +3056,201 @@ int rt_render_views(rt_ctx* c, const rt_params* p, const rt_views* v, const floa
   }
   if (accum_out) HIP_TRY(hipMemcpy(accum_out, dAccum.get(), all * sizeof(float4), hipMemcpyDeviceToHost));
   return RT_OK;
+}
+
+}  // extern "C"
+
+// ---- per-view AOVs and motion vectors, and the batched denoiser (DESIGN.md "Multi-view frames") ----------------------
+namespace {
+
+// What rt_render_aov_views and rt_render_motion_views check once their own pointers and reserved words are in order: p
+// as rt_render_aov sees it (*q; the wavefront bit selects an integrator and does not matter here either), then
+// rt_render_views' checks.  Everything that can be told from the arguments alone is answered before the context is looked
+// at, and a context exists only where a device does.  prevCams: last frame's camera of each view, or null.
+int views_pass_checks(rt_ctx* c, const rt_params* p, const rt_views* v, const rt_camera* prevCams, rt_params* q, rtbvh::Padding* pad,
+                      bool* refit) {
+  *q = aov_params(*p);
+  q->reserved[2] &= ~1u;
+  int rc = check_params_shape(q);
+  if (rc != RT_OK) return rc;
+  if (q->world > 1) return fail(RT_ERR_UNSUPPORTED, "tile-sharded AOVs (world %u) are not supported", q->world);
+  if ((rc = views_shape_checks(q, v)) != RT_OK) return rc;
+  for (uint32_t j = 0; j < v->n_views; ++j) {
+    if (max_abs_bits(v->cameras[j].position, 12) >= 0x7f800000u) return fail(RT_ERR_INVALID, "view %u: non-finite camera", j);
+    if (prevCams && max_abs_bits(prevCams[j].position, 12) >= 0x7f800000u)
+      return fail(RT_ERR_INVALID, "view %u: the previous camera is not finite", j);
+  }
+  if ((rc = check_device_present()) != RT_OK) return rc;
+  return views_checks(c, q, v, pad, refit);
+}
+
+int aov_views_checks(rt_ctx* c, const rt_params* p, const rt_views* v, const rt_aov* out, rt_params* q, rtbvh::Padding* pad, bool* refit) {
+  if (!c || !p || !v || !v->cameras || !out) return fail(RT_ERR_INVALID, "ctx/params/views/cameras/aov is null");
+  if (any_set(out->reserved, 4)) return fail(RT_ERR_INVALID, "reserved words must be zero");
+  return views_pass_checks(c, p, v, nullptr, q, pad, refit);
+}
+
+int motion_views_checks(rt_ctx* c, const rt_params* p, const rt_views* v, const rt_motion_prev_views* prev, const rt_motion* out,
+                        rt_params* q, rtbvh::Padding* pad, bool* refit) {
+  if (!c || !p || !v || !v->cameras || !prev || !out) return fail(RT_ERR_INVALID, "ctx/params/views/cameras/prev/out is null");
+  if (any_set(prev->reserved, 6) || any_set(out->reserved, 4)) return fail(RT_ERR_INVALID, "reserved words must be zero");
+  return views_pass_checks(c, p, v, prev->cameras, q, pad, refit);
+}
+
+// What the device forms do between their checks and their launch: the refit a farther view asks for (as
+// rt_render_views_device: the context keeps the padding, not the camera), last frame's cameras when the motion pass runs
+// (prev: null for the AOV pass), and the view records.
+int stage_views(rt_ctx* c, const rt_params* q, const rt_views* v, const rt_motion_prev_views* prev, const rtbvh::Padding& pad, bool refit,
+                hipStream_t s) {
+  int rc;
+  if (refit) {
+    if ((rc = update_checks(c, nullptr, 0)) != RT_OK) return rc;
+    Update x;
+    x.padding = &pad;
+    if ((rc = update_ctx(c, x, s, std::chrono::steady_clock::now(), nullptr)) != RT_OK) return rc;
+  }
+  if (prev) {
+    const uint32_t n = v->n_views;
+    if (c->vwStagedSet) HIP_TRY(hipEventSynchronize(c->vwStaged.get()));  // the previous call's upload has read the pinned copy
+    if (n > c->vwPrevCap) {
+      c->vwPrevCap = 0;
+      c->vwPrevCams.reset(), c->vwPrevHost.reset();
+      HIP_TRY(dev_alloc(&c->vwPrevCams, n));
+      void* h = nullptr;
+      HIP_TRY(hipHostMalloc(&h, n * sizeof(rt_camera)));
+      c->vwPrevHost.reset(static_cast<rt_camera*>(h));
+      c->vwPrevCap = n;
+    }
+    memcpy(c->vwPrevHost.get(), prev->cameras ? prev->cameras : v->cameras, n * sizeof(rt_camera));
+    HIP_TRY(hipMemcpyAsync(c->vwPrevCams.get(), c->vwPrevHost.get(), n * sizeof(rt_camera), hipMemcpyHostToDevice, s));
+  }
+  return upload_views(c, q, v, s);  // (records vwStaged behind both copies)
+}
+
+// Everything rt_denoise_batch checks, the context last (it exists only where a device does).
+int denoise_batch_checks(const rt_ctx* c, const rt_denoise_params* d, uint32_t nFrames, const void* rgb, const rt_aov* aov, const void* out) {
+  int rc = denoise_checks(c, d, rgb, aov, out);
+  if (rc != RT_OK) return rc;
+  if (any_set(d->reserved, 6) || any_set(aov->reserved, 4)) return fail(RT_ERR_INVALID, "reserved words must be zero");
+  if ((rc = check_image_size(d->width, d->height)) != RT_OK) return rc;
+  if (d->iterations > 8) return fail(RT_ERR_INVALID, "iterations %u > 8", d->iterations);
+  if ((rc = check_sigmas({d->sigma_color, d->sigma_normal, d->sigma_position})) != RT_OK) return rc;
+  if (nFrames == 0) return fail(RT_ERR_INVALID, "n_frames is 0");
+  if ((uint64_t)nFrames * d->width * d->height >= (1ull << 31))
+    return fail(RT_ERR_INVALID, "%u frames of %ux%u pixels: 2^31 pixels or more", nFrames, d->width, d->height);
+  if ((rc = check_device_present()) != RT_OK) return rc;
+  return check_not_broken(c);
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_render_aov_views_device(rt_ctx* c, const rt_params* p, const rt_views* v, const rt_aov* out, void* stream) {
+  rt_params q;
+  rtbvh::Padding pad;
+  bool refit = false;
+  int rc = aov_views_checks(c, p, v, out, &q, &pad, &refit);
+  if (rc != RT_OK) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if ((rc = stage_views(c, &q, v, nullptr, pad, refit, s)) != RT_OK) return rc;
+  const hipError_t he = rtk::launch_aov_views(q.accel == RT_ACCEL_BRUTE, c->S, aov_args(q, *out), c->vwRecs.get(), v->n_views, s);
+  if (he != hipSuccess) return fail(RT_ERR_HIP, "AOV launch failed: %s", hipGetErrorString(he));
+  return RT_OK;
+}
+
+int rt_render_aov_views(rt_ctx* c, const rt_params* p, const rt_views* v, const rt_aov* out) {
+  rt_params q;
+  rtbvh::Padding pad;
+  bool refit = false;
+  int rc = aov_views_checks(c, p, v, out, &q, &pad, &refit);
+  if (rc != RT_OK) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t all = rtk::view_slice(v->n_views, q.width, q.height, 1);
+  Staging st;
+  rt_aov d = {};
+  d.albedo = st.out(out->albedo, 3 * all), d.normal = st.out(out->normal, 3 * all), d.position = st.out(out->position, 3 * all);
+  d.depth = st.out(out->depth, all), d.hits = st.out(out->hits, all), d.mesh = st.out(out->mesh, all), d.tri = st.out(out->tri, all);
+  if (st.rc != RT_OK) return st.rc;
+  if ((rc = rt_render_aov_views_device(c, &q, v, &d, nullptr)) != RT_OK) return rc;
+  return st.download();
+}
+
+int rt_render_motion_views_device(rt_ctx* c, const rt_params* p, const rt_views* v, const rt_motion_prev_views* prev,
+                                  const rt_motion* out, void* stream) {
+  rt_params q;
+  rtbvh::Padding pad;
+  bool refit = false;
+  int rc = motion_views_checks(c, p, v, prev, out, &q, &pad, &refit);
+  if (rc != RT_OK) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if ((rc = stage_views(c, &q, v, prev, pad, refit, s)) != RT_OK) return rc;
+  const rt_motion_prev one = {};  // (the launcher reads the cameras from the tables: only prevVpos matters below)
+  const rtk::MotionArgs A = motion_args(c, q, &one, prev->vertex_pos, *out);
+  const hipError_t he =
+      rtk::launch_motion_views(q.accel == RT_ACCEL_BRUTE, c->S, A, c->vwRecs.get(), c->vwPrevCams.get(), v->n_views, s);
+  if (he != hipSuccess) return fail(RT_ERR_HIP, "motion launch failed: %s", hipGetErrorString(he));
+  return RT_OK;
+}
+
+int rt_render_motion_views(rt_ctx* c, const rt_params* p, const rt_views* v, const rt_motion_prev_views* prev, const rt_motion* out) {
+  rt_params q;
+  rtbvh::Padding pad;
+  bool refit = false;
+  int rc = motion_views_checks(c, p, v, prev, out, &q, &pad, &refit);
+  if (rc != RT_OK) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t all = rtk::view_slice(v->n_views, q.width, q.height, 1), nv = 3 * (size_t)c->nVertices;
+  rt_motion_prev_views dp = *prev;
+  if (prev->vertex_pos) {
+    if (!c->mvPrev) HIP_TRY(dev_alloc(&c->mvPrev, nv));
+    HIP_TRY(hipMemcpy(c->mvPrev.get(), prev->vertex_pos, nv * sizeof(float), hipMemcpyHostToDevice));
+    dp.vertex_pos = c->mvPrev.get();
+  }
+  Staging st;
+  rt_motion d = {};
+  d.motion = st.out(out->motion, 2 * all), d.position = st.out(out->position, 3 * all);
+  d.prev_position = st.out(out->prev_position, 3 * all), d.mesh = st.out(out->mesh, all);
+  if (st.rc != RT_OK) return st.rc;
+  if ((rc = rt_render_motion_views_device(c, &q, v, &dp, &d, nullptr)) != RT_OK) return rc;
+  return st.download();
+}
+
+int rt_denoise_batch_device(rt_ctx* c, const rt_denoise_params* d, uint32_t n_frames, const void* d_rgb, const rt_aov* aov, void* d_out,
+                            void* stream) {
+  int rc = denoise_batch_checks(c, d, n_frames, d_rgb, aov, d_out);
+  if (rc != RT_OK) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  if ((rc = ensure_filter_scratch(c, n_frames * rtk::filter_scratch(d->width, d->height))) != RT_OK) return rc;
+  rtk::DenoiseArgs D;
+  D.width = d->width, D.height = d->height;
+  D.iterations = d->iterations ? d->iterations : kDenoiseIterations;
+  D.sigma_color = d->sigma_color > 0.f ? d->sigma_color : kDenoiseSigmaColor;
+  D.sigma_normal = d->sigma_normal > 0.f ? d->sigma_normal : kDenoiseSigmaNormal;
+  D.sigma_position = d->sigma_position;  // 0: the device derives it from the scene's extent, once for the stack
+  D.rgb = static_cast<const float*>(d_rgb), D.albedo = aov->albedo, D.normal = aov->normal, D.position = aov->position;
+  D.hits = aov->hits, D.out = static_cast<float*>(d_out), D.scratch = c->dnScratch.get();
+  const hipError_t he = rtk::launch_denoise_batch(c->S, D, n_frames, static_cast<hipStream_t>(stream));
+  if (he != hipSuccess) return fail(RT_ERR_HIP, "denoise launch failed: %s", hipGetErrorString(he));
+  return RT_OK;
+}
+
+int rt_denoise_batch(rt_ctx* c, const rt_denoise_params* d, uint32_t n_frames, const float* rgb, const rt_aov* aov, float* out) {
+  int rc = denoise_batch_checks(c, d, n_frames, rgb, aov, out);
+  if (rc != RT_OK) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t all = rtk::view_slice(n_frames, d->width, d->height, 1);
+  Staging st;
+  const float* dRgb = st.in(rgb, 3 * all);
+  rt_aov da = {};
+  da.albedo = st.in(aov->albedo, 3 * all), da.normal = st.in(aov->normal, 3 * all), da.position = st.in(aov->position, 3 * all);
+  da.hits = st.in(aov->hits, all);
+  float* dOut = st.out(out, 3 * all);
+  if (st.rc != RT_OK) return st.rc;
+  if ((rc = rt_denoise_batch_device(c, d, n_frames, dRgb, &da, dOut, nullptr)) != RT_OK) return rc;
+  return st.download();
 }
 
 }  // extern "C"

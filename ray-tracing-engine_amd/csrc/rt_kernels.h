@@ -120,8 +120,19 @@ struct AovArgs {
   float *albedo, *normal, *position, *depth;  // [h][w][3], [h][w][3], [h][w][3], [h][w]
   uint32_t *hits, *mesh, *tri;                // [h][w] each
   uint32_t width, height, spp, seed, s0, s1;
+  // multi-view launches only (launch_aov_views sets them; the single-view instances do not read them)
+  const ViewRec* views = nullptr;
+  uint32_t tilesPerView = 0;
 };
 hipError_t launch_aov(bool brute_force, const DevScene& S, const AovArgs& A, hipStream_t stream);
+// First element of view j's slice of a per-view output with c floats or words per pixel (rt_render_aov_views,
+// rt_render_motion_views, rt_denoise_batch): formed in 64 bits — n w h may reach 2^31 - 1 and 3 x that is not 32-bit.
+__host__ __device__ inline size_t view_slice(uint32_t j, uint32_t width, uint32_t height, uint32_t c) {
+  return (size_t)j * width * height * c;
+}
+// the same pass over nViews views in one launch (rt_render_aov_views): view j renders with views[j]'s camera and seed (A.seed
+// is not read) into slice j of every channel
+hipError_t launch_aov_views(bool brute_force, const DevScene& S, const AovArgs& A, const ViewRec* views, uint32_t nViews, hipStream_t stream);
 // the motion pass (motion_kernels.h, rt_render_motion): per pixel, for the primary ray of sample s0, the hit point over the
 // context's positions and over prevVpos (never null: the context's own when the geometry did not move), and the screen
 // motion between prevCam and S.cam; null channels are not written
@@ -131,8 +142,16 @@ struct MotionArgs {
   const float* prevVpos;                    // [n_vertices][3]
   rt_camera prevCam;
   uint32_t width, height, spp, seed, s0;
+  // multi-view launches only (launch_motion_views sets them; the single-view instances do not read them)
+  const ViewRec* views = nullptr;
+  const rt_camera* prevCams = nullptr;
+  uint32_t tilesPerView = 0;
 };
 hipError_t launch_motion(bool brute_force, const DevScene& S, const MotionArgs& A, hipStream_t stream);
+// the same pass over nViews views in one launch (rt_render_motion_views): view j with views[j]'s camera and seed and
+// prevCams[j] as last frame's camera (a device table of its own: ViewRec stays 64 bytes) into slice j of every channel
+hipError_t launch_motion_views(bool brute_force, const DevScene& S, const MotionArgs& A, const ViewRec* views, const rt_camera* prevCams,
+                               uint32_t nViews, hipStream_t stream);
 // adaptive sampling (adaptive.hip, rt_render_adaptive): per-pixel running moments and per-granule pass counts, the
 // compaction of the active granules into the next pass's wave tiles, and the resolve with per-pixel sample counts
 enum { ADAPT_CNT_GRANULES = 0, ADAPT_CNT_PIXELS = 1, ADAPT_CNT_TILES = 2, ADAPT_CNT_WORDS = 16 };  // counts[2 + sshift]

@@ -166,6 +166,12 @@ class MotionPrev(C.Structure):
     _fields_ = [("vertex_pos", C.c_void_p), ("camera", C.POINTER(Camera)), ("reserved", C.c_uint32 * 6)]
 
 
+class MotionPrevViews(C.Structure):
+    """rt_motion_prev_views: last frame's vertex positions (host or device pointer) and one camera per view (host), None =
+    the context's positions / the views' own cameras."""
+    _fields_ = [("vertex_pos", C.c_void_p), ("cameras", C.POINTER(Camera)), ("reserved", C.c_uint32 * 6)]
+
+
 class Motion(C.Structure):
     """rt_motion: channel pointers (host or device), None = channel not wanted."""
     _fields_ = [("motion", C.c_void_p), ("position", C.c_void_p), ("prev_position", C.c_void_p), ("mesh", C.c_void_p),
@@ -314,7 +320,9 @@ AMD_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_create", "rt_destroy", "rt
                "rt_update", "rt_update_vertices_device", "rt_update_transforms", "rt_group_update", "rt_render_aov", "rt_render_aov_device",
                "rt_denoise", "rt_denoise_device", "rt_render_adaptive", "rt_render_adaptive_device", "rt_render_views",
                "rt_render_views_device", "rt_render_motion", "rt_render_motion_device", "rt_temporal_accumulate",
-               "rt_temporal_accumulate_device", "rt_svgf", "rt_svgf_device", "rt_bvh_quality_get", "rt_rebuild"]
+               "rt_temporal_accumulate_device", "rt_svgf", "rt_svgf_device", "rt_bvh_quality_get", "rt_rebuild",
+               "rt_render_aov_views", "rt_render_aov_views_device", "rt_render_motion_views", "rt_render_motion_views_device",
+               "rt_denoise_batch", "rt_denoise_batch_device"]
 HOST_SYMBOLS = ["rt_host_scene_build", "rt_host_scene_desc", "rt_host_scene_free", "rt_host_last_error",
                 "rt_host_fill_background", "rt_host_save_ppm", "rt_host_kd_order", "rt_host_light_basis"]
 
@@ -417,6 +425,16 @@ def amd():
         L.rt_svgf.argtypes = [C.c_void_p, C.POINTER(SvgfParams), C.c_void_p, C.POINTER(Aov), C.POINTER(Motion),
                               C.POINTER(SvgfHistory), C.POINTER(SvgfOut)]
         L.rt_svgf_device.argtypes = L.rt_svgf.argtypes + [C.c_void_p]
+        views_aov = [C.c_void_p, C.POINTER(Params), C.POINTER(Views), C.POINTER(Aov)]
+        views_motion = [C.c_void_p, C.POINTER(Params), C.POINTER(Views), C.POINTER(MotionPrevViews), C.POINTER(Motion)]
+        batch = [C.c_void_p, C.POINTER(DenoiseParams), C.c_uint32, C.c_void_p, C.POINTER(Aov), C.c_void_p]
+        for name, types in (("rt_render_aov_views", views_aov), ("rt_render_aov_views_device", views_aov + [C.c_void_p]),
+                            ("rt_render_motion_views", views_motion), ("rt_render_motion_views_device", views_motion + [C.c_void_p]),
+                            ("rt_denoise_batch", batch), ("rt_denoise_batch_device", batch + [C.c_void_p])):
+            # (a library named by RT_AMD_LIB may be an older build without them, as tools/aov_views_bench.py times the
+            # per-view loop on; the package's own library must have every one)
+            if hasattr(L, name) or not os.environ.get("RT_AMD_LIB"):
+                getattr(L, name).argtypes = types
         _amd = L
     return _amd
 
@@ -961,6 +979,98 @@ class Context:
         d = self._denoise_params(width, height, iterations, sigma_color, sigma_normal, sigma_position)
         _check(amd().rt_denoise_device(self._h, C.byref(d), C.c_void_p(d_rgb), C.byref(a), C.c_void_p(d_out),
                                        C.c_void_p(stream or None)))
+
+    def render_aov_views(self, params, cameras, seeds=None, channels=AOV_CHANNELS):
+        """rt_render_aov_views: the SUMS of render_aov(raw=True) for every camera of cameras [n][4][3] (seeds [n] or None =
+        params.seed) in one launch, as a dict of arrays with a leading view axis ([n][h][w][3] / [n][h][w]).
+        `channels`: the ones wanted (the others are not computed)."""
+        v, _keep = make_views(cameras, seeds)
+        w, h, n = params.width, params.height, v.n_views
+        sums, a = {}, Aov()
+        for k in channels:
+            sums[k] = np.zeros((n, h, w, 3) if k in AOV_FLOAT3 else (n, h, w), np.float32 if k in AOV_FLOAT3 or k == "depth" else np.uint32)
+            setattr(a, k, sums[k].ctypes.data)
+        _check(amd().rt_render_aov_views(self._h, C.byref(params), C.byref(v), C.byref(a)))
+        return sums
+
+    def render_aov_views_device(self, params, cameras, ptrs, stream=0, seeds=None):
+        """rt_render_aov_views_device: the sums into device buffers [n][h][w][..]; ptrs = {channel: device pointer}."""
+        v, _keep = make_views(cameras, seeds)
+        a = Aov()
+        for k, p in ptrs.items():
+            setattr(a, k, p or None)
+        _check(amd().rt_render_aov_views_device(self._h, C.byref(params), C.byref(v), C.byref(a), C.c_void_p(stream or None)))
+
+    @staticmethod
+    def _motion_prev_views(prev_pos, prev_cameras, n):
+        """An rt_motion_prev_views: prev_pos as _motion_prev's; prev_cameras [n][4][3] floats or None."""
+        m, keep = MotionPrevViews(), []
+        if prev_pos is not None:
+            if isinstance(prev_pos, int):
+                m.vertex_pos = prev_pos
+            else:
+                keep.append(np.ascontiguousarray(prev_pos, np.float32).reshape(-1, 3))
+                m.vertex_pos = keep[-1].ctypes.data
+        if prev_cameras is not None:
+            keep.append(np.ascontiguousarray(prev_cameras, np.float32).reshape(-1, 12))
+            if len(keep[-1]) != n:
+                raise ValueError("%d previous cameras for %d views" % (len(keep[-1]), n))
+            m.cameras = C.cast(keep[-1].ctypes.data, C.POINTER(Camera))
+        return m, keep
+
+    def render_motion_views(self, params, cameras, prev_pos=None, prev_cameras=None, seeds=None, channels=MOTION_CHANNELS):
+        """rt_render_motion_views: render_motion's dict for every camera of cameras [n][4][3] in one launch, each array with
+        a leading view axis.  prev_pos [n_vertices][3] / prev_cameras [n][4][3]: last frame's (None = the context's
+        positions / the views' own cameras)."""
+        v, _keep = make_views(cameras, seeds)
+        w, h, n = params.width, params.height, v.n_views
+        shape = dict(motion=(n, h, w, 2), position=(n, h, w, 3), prev_position=(n, h, w, 3), mesh=(n, h, w))
+        out, m = {}, Motion()
+        for k in channels:
+            out[k] = np.zeros(shape[k], np.uint32 if k == "mesh" else np.float32)
+            setattr(m, k, out[k].ctypes.data)
+        prev, _keep2 = self._motion_prev_views(prev_pos, prev_cameras, n)
+        _check(amd().rt_render_motion_views(self._h, C.byref(params), C.byref(v), C.byref(prev), C.byref(m)))
+        return out
+
+    def render_motion_views_device(self, params, cameras, ptrs, d_prev_pos=None, prev_cameras=None, stream=0, seeds=None):
+        """rt_render_motion_views_device: into device buffers [n][h][w][..]; ptrs = {channel: device pointer}, d_prev_pos a
+        device pointer or None."""
+        v, _keep = make_views(cameras, seeds)
+        m = Motion()
+        for k, p in ptrs.items():
+            setattr(m, k, p or None)
+        prev, _keep2 = self._motion_prev_views(int(d_prev_pos) if d_prev_pos else None, prev_cameras, v.n_views)
+        _check(amd().rt_render_motion_views_device(self._h, C.byref(params), C.byref(v), C.byref(prev), C.byref(m),
+                                                   C.c_void_p(stream or None)))
+
+    def denoise_batch(self, rgb, aov_sums, iterations=0, sigma_color=0., sigma_normal=0., sigma_position=0., out=None):
+        """rt_denoise_batch: denoise() of every frame of rgb [n][h][w][3] guided by the stacked SUMS of render_aov_views, in
+        one launch per stage.  `out` may be rgb itself (in place)."""
+        rgb = np.ascontiguousarray(rgb, np.float32)
+        n, h, w = rgb.shape[:3]
+        out = np.empty_like(rgb) if out is None else out
+        assert out.dtype == np.float32 and out.flags["C_CONTIGUOUS"] and out.shape == rgb.shape
+        keep = {k: np.ascontiguousarray(aov_sums[k], np.uint32 if k == "hits" else np.float32)
+                for k in ("albedo", "normal", "position", "hits")}
+        a = Aov()
+        for k, x in keep.items():
+            assert x.shape[:3] == (n, h, w), k
+            setattr(a, k, x.ctypes.data)
+        d = self._denoise_params(w, h, iterations, sigma_color, sigma_normal, sigma_position)
+        _check(amd().rt_denoise_batch(self._h, C.byref(d), n, _ptr(rgb), C.byref(a), _ptr(out)))
+        return out
+
+    def denoise_batch_device(self, width, height, n_frames, d_rgb, ptrs, d_out, stream=0, iterations=0, sigma_color=0.,
+                             sigma_normal=0., sigma_position=0.):
+        """rt_denoise_batch_device: device pointers to [n_frames] stacked buffers (ptrs = {"albedo", "normal", "position",
+        "hits": sums}), on `stream`."""
+        a = Aov()
+        for k, p in ptrs.items():
+            setattr(a, k, p or None)
+        d = self._denoise_params(width, height, iterations, sigma_color, sigma_normal, sigma_position)
+        _check(amd().rt_denoise_batch_device(self._h, C.byref(d), n_frames, C.c_void_p(d_rgb), C.byref(a), C.c_void_p(d_out),
+                                             C.c_void_p(stream or None)))
 
     def knn(self, queries, k):
         q = np.ascontiguousarray(queries, np.float32)
