@@ -213,7 +213,9 @@ constexpr uint32_t kPrioMaxNodes = 65536;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(3))) u32x4* lds_u4_ptr;
 
-template <int MODE, int LTX = LT_NONE>
+// POOL: the walker of a vertex pool (its rounds end at the pool loop's wave priority); the mixed walker always is, the
+// any-hit one when the pool holds shadow rays only.
+template <int MODE, int LTX = LT_NONE, bool POOL = (MODE == TRAV_MIXED)>
 struct Trav {
   static constexpr int LT = LTX & 3;
   static constexpr bool PRIO = (LTX & LT_NOPRIO) == 0;
@@ -425,7 +427,7 @@ struct Trav {
       cur = stop ? TERM : (int32_t)peek();
       pop();
     }
-    if (PRIO && MODE == TRAV_MIXED) __builtin_amdgcn_s_setprio(1);  // back in the pool loop
+    if (PRIO && POOL) __builtin_amdgcn_s_setprio(1);  // back in the pool loop
     PH(PH_LEAF);
   }
 
@@ -859,9 +861,16 @@ static_assert(VpLayout<1>::KEY % 2 == 0 && VpLayout<2>::KEY % 2 == 0, "64-bit ke
 static_assert(VP_KEY % 2 == 0, "64-bit keys need 8-byte alignment");
 static_assert(VP_WORDS == (int)rtbvh::kWavePoolWords && BLOCK == (int)rtbvh::kStackRowWords, "bvh_build.h sizes the depth cap with these");
 
-template <bool STATS, int LT>
-RT_DEV f3 vertex_pool(const DevScene& S, bool alive, bool bounce, Rng& g, f3 rayDir, uint32_t mesh, f3 hitNormal,
+// BOUNCE = false: the body for a pool that is known to hold shadow rays only — the pool of a path's deepest vertex, and
+// every pool of a frame without bounces (`bounceRay` is false and not read).  Its walker is the any-hit one (no candidate
+// distance or id, no acceptance chains, no keys to publish or adopt) and the bounce kind is gone from the rank arithmetic,
+// the hand-out and the direction fetch; hand-out order, thresholds, stealing and the shared result bits are the same code,
+// so the schedule — and the counted pass's node and triangle totals — are the same.  BOUNCE = true is the general body:
+// `bounceRay` says at run time whether a bounce ray is sent.
+template <bool STATS, int LT, bool BOUNCE>
+RT_DEV f3 vertex_pool(const DevScene& S, bool alive, bool bounceRay, Rng& g, f3 rayDir, uint32_t mesh, f3 hitNormal,
                       f3& point, f3& bdir, uint32_t* stack, uint32_t* pool, HitRec& next, bool& nextFound, LaneStats& st) {
+  const bool bounce = BOUNCE && bounceRay;
   constexpr bool FR = (LT & LT_FASTDET) != 0;  // 1 / length by rtd::recip_fast (see rtd::unit3)
   const uint32_t lane = threadIdx.x & 63u, nl = S.n_lights;
   constexpr bool CP3 = (LT & LT_COMPACT3) != 0, CP2 = CP3 || (LT & LT_COMPACT2) != 0, CP = CP2 || (LT & LT_COMPACT) != 0;
@@ -915,9 +924,9 @@ RT_DEV f3 vertex_pool(const DevScene& S, bool alive, bool bounce, Rng& g, f3 ray
   PH(PH_FILL);
   const uint32_t kinds = nl + (bounce ? 1u : 0u), R = n * kinds;
   uint32_t head = 0, myK = 0, myJ = 0;
-  Trav<TRAV_MIXED, LT> T;
+  Trav<BOUNCE ? TRAV_MIXED : TRAV_ANY, LT, true> T;
   T.idle(stack);
-  T.sharedKey = keys, T.pj = 0;
+  if constexpr (BOUNCE) T.sharedKey = keys, T.pj = 0;
   uint32_t* stackBase = stack - lane;
   if (!(LT & LT_NOPRIO)) __builtin_amdgcn_s_setprio(1);
   for (;;) {
@@ -987,7 +996,9 @@ RT_DEV f3 vertex_pool(const DevScene& S, bool alive, bool bounce, Rng& g, f3 ray
         given += (uint32_t)__popcll(vmask);
       }
       if (gave) {
-        if (!T.shared && !T.anyHit && T.found) T.publish();  // what it has found so far
+        if constexpr (BOUNCE) {
+          if (!T.shared && !T.anyHit && T.found) T.publish();  // what it has found so far
+        }
         T.shared = true;
         T.stolen += gave;
       }
@@ -999,7 +1010,7 @@ RT_DEV f3 vertex_pool(const DevScene& S, bool alive, bool bounce, Rng& g, f3 ray
         const uint32_t w = thief ? (uint32_t)list16[q] : lane;
         const uint32_t v = w & 63u, e = w >> 6;
         const uint32_t kj = (uint32_t)__shfl((int)(myK | (myJ << 8)), (int)v, 64);  // (all lanes take part)
-        if (CP2) dv = mk(__shfl(T.d.x, (int)v, 64), __shfl(T.d.y, (int)v, 64), __shfl(T.d.z, (int)v, 64));
+        if (CP2 && BOUNCE) dv = mk(__shfl(T.d.x, (int)v, 64), __shfl(T.d.y, (int)v, 64), __shfl(T.d.z, (int)v, 64));
         if (thief) {
           uint32_t* slot = stackBase + (e + 1u) * BLOCK + v;  // (row 0 is the sentinel)
           newNode = (int32_t)*slot;
@@ -1016,7 +1027,7 @@ RT_DEV f3 vertex_pool(const DevScene& S, bool alive, bool bounce, Rng& g, f3 ray
       const f3 pj = CP3 ? pj3 : mk(fp[VP_PT + newJ], fp[VP_PT + 64 + newJ], fp[VP_PT + 128 + newJ]);
       f3 dj;
       if (CP) {
-        if (newK < nl) {  // rebuild the direction from the light sample's two parameters
+        if (!BOUNCE || newK < nl) {  // rebuild the direction from the light sample's two parameters
           const rt_light& Lt = S.lights[newK];
           float rh, rv;
           if (CP3) {  // ... which are re-drawn: the pixel lane's engine state before its light draws, 2 calls per earlier light
@@ -1033,12 +1044,13 @@ RT_DEV f3 vertex_pool(const DevScene& S, bool alive, bool bounce, Rng& g, f3 ray
           dj = mk(fp[VP::BDIR + newJ], fp[VP::BDIR + 64 + newJ], fp[VP::BDIR + 128 + newJ]);
         }
       } else {
-        const uint32_t src = newK < nl ? VP_DIR + 192 * newK : VP::BDIR;
+        const uint32_t src = !BOUNCE || newK < nl ? VP_DIR + 192 * newK : VP::BDIR;
         dj = mk(fp[src + newJ], fp[src + 64 + newJ], fp[src + 128 + newJ]);
       }
       T.start(pj, dj, S.invBoxScale);
       if (T.live()) T.cur = newNode;  // (a NaN ray stays dead)
-      T.anyHit = newK < nl, T.pj = newJ, T.shared = newShared;
+      if constexpr (BOUNCE) T.anyHit = newK < nl, T.pj = newJ;
+      T.shared = newShared;
       myK = newK, myJ = newJ;
     }
     if (wave_ballot(T.live()) == 0) break;
@@ -1050,7 +1062,7 @@ RT_DEV f3 vertex_pool(const DevScene& S, bool alive, bool bounce, Rng& g, f3 ray
       if (T.shared && T.live()) {
         // several lanes may now serve this ray: stop at a decided any-hit
         // ray, prune with the closest hit anyone has found so far
-        if (T.anyHit) {
+        if (!BOUNCE || T.anyHit) {
           if ((res[myK * 2 + (myJ >> 5)] >> (myJ & 31)) & 1u) T.cur = TERM;
         } else {
           T.refresh_best();
@@ -1061,7 +1073,7 @@ RT_DEV f3 vertex_pool(const DevScene& S, bool alive, bool bounce, Rng& g, f3 ray
       if (head >= R) PHC(PH_TAIL);
       T.template round<STATS>(S, st);
       if (was && !T.live() && T.found) {
-        if (myK < nl) atomicOr(&res[myK * 2 + (myJ >> 5)], 1u << (myJ & 31));
+        if (!BOUNCE || myK < nl) atomicOr(&res[myK * 2 + (myJ >> 5)], 1u << (myJ & 31));
         else if (!T.shared) T.publish();  // shared rays publish every improvement as it happens
       }
       if (__popcll(wave_ballot(!T.live())) >= need) break;
@@ -1245,7 +1257,16 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
         // stream ends there — the pool only draws it when a bounce ray follows)
         HitRec nh;
         bool nfound;
-        const f3 c = vertex_pool<STATS, LT>(S, alive, bounce, g, d, mesh, nrm, pt, bdir, L.stack, pool, nh, nfound, st);
+        // A pool without a bounce ray holds any-hit rays only and runs the body compiled for that — in the instances
+        // with the whole tree in LDS (LT_ALL: plan_persist's class of the small scenes, whose frames are bound by
+        // instruction issue).  In the other instances (a partial top, trees in HBM / L2, the compact pools) the
+        // second body costs the timed kernels registers they do not have: `<false, 257>` and `<false, 280>` spill
+        // with it where they have no scratch without, `k_render_persist5<false, 328>` spills more; they keep the
+        // general body alone.
+        constexpr bool SHADOW_BODY = (LT & 3) == LT_ALL;
+        const f3 c = SHADOW_BODY && !bounce
+                         ? vertex_pool<STATS, LT, false>(S, alive, false, g, d, mesh, nrm, pt, bdir, L.stack, pool, nh, nfound, st)
+                         : vertex_pool<STATS, LT, true>(S, alive, bounce, g, d, mesh, nrm, pt, bdir, L.stack, pool, nh, nfound, st);
         if (alive) {
           if (depth == 0) c0 = c;
           else if (depth == 1) c1 = c;
