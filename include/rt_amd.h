@@ -28,6 +28,8 @@
  *                                  not yet converged (+ _device form)
  *   rt_render_views             <- (no counterpart) the frames of many cameras of one resident scene in one launch
  *                                  (+ _device form)
+ *   rt_render_ao                <- (no counterpart) ambient occlusion and bent normals at the frame's first hit
+ *                                  (+ _device form)
  *   rt_render_aov_views / rt_render_motion_views / rt_denoise_batch <- (no counterpart) the AOVs, motion vectors and
  *                                  denoised frames of those views, one launch each (+ _device forms)
  *   rt_trace                    <- RayTracer::rayTrace (RayTracer.h:27-53) test hook
@@ -438,6 +440,39 @@ int rt_denoise(rt_ctx* ctx, const rt_denoise_params* d, const float* rgb, const 
  * context's scratch serves one call at a time. */
 int rt_denoise_device(rt_ctx* ctx, const rt_denoise_params* d, const void* d_rgb, const rt_aov* d_aov, void* d_out,
                       void* stream);
+
+/* ---- ambient occlusion and bent normals at the first hit ---------------------------------------------
+ * rt_render_ao casts rt_render_aov's primary rays — the same stream, jitter_sample, camera_ray and walk (or the exhaustive
+ * loop for RT_ACCEL_BRUTE), so the same hits, shading normal n and point X — and at every hit n_rays occlusion rays.  Ray
+ * j of sample i of pixel pix draws d = hemisphere_sample(n), the frame's own bounce distribution, from a stream of its
+ * own: rt_stream_seed(seed, RT_STREAM_AO, pix, i * n_rays + j).  It starts at o = X + bias * d (per component in float32:
+ * the product, then the sum) and is occluded iff a triangle passes the library's triangle test with t > 0 and, when
+ * max_distance > 0, t < max_distance.  A direction with a non-finite component is not occluded: it is counted, and adds
+ * nothing to bent.  A miss of the primary ray adds nothing.  unoccluded and hits are counts, so sample ranges chain
+ * exactly (occluded = hits * n_rays - unoccluded); bent is a float32 sum per component in (sample, j) order.  mode,
+ * max_depth, the photon fields and the wavefront bit do not affect the pass; RT_NODES_Q8 contexts walk their resident
+ * 32-byte records, as rt_render_aov does.
+ * RT_ERR_INVALID, before any device work and with nothing written: a null ctx, p, a or output struct; non-zero reserved
+ * words; n_rays 0 or above RT_AO_MAX_RAYS; spp * n_rays >= 2^32; a negative or non-finite bias or max_distance;
+ * rt_render_aov's size and range checks.  RT_ERR_UNSUPPORTED: world > 1, the legacy RNG.                             */
+#define RT_AO_MAX_RAYS 256
+typedef struct rt_ao_params {
+  uint32_t n_rays;       /* occlusion rays per primary hit: 1..RT_AO_MAX_RAYS                          */
+  float bias;            /* 0 = 1e-4f x the diagonal of the bounding box of the vertices the context's
+                            triangles reference (rt_denoise's reduction, float32); else finite, > 0   */
+  float max_distance;    /* 0 = unbounded; else finite, > 0, measured from the biased origin          */
+  uint32_t reserved[5];  /* zero */
+} rt_ao_params;
+typedef struct rt_ao {   /* every pointer may be NULL; the others are overwritten                     */
+  uint32_t* unoccluded;  /* [h][w]    occlusion rays that escaped, over the hit samples of the range   */
+  uint32_t* hits;        /* [h][w]    == rt_aov.hits for the same params                               */
+  float* bent;           /* [h][w][3] float32 sum of the escaped rays' directions                      */
+  uint32_t reserved[4];  /* zero */
+} rt_ao;
+int rt_render_ao(rt_ctx* ctx, const rt_params* p, const rt_ao_params* a, const rt_ao* host_out);
+/* The same into DEVICE buffers on `stream` (may be NULL); no synchronisation.  With the default bias the box is reduced
+ * on the stream into a block the context owns: such calls run one at a time, as rt_denoise_device's do.                */
+int rt_render_ao_device(rt_ctx* ctx, const rt_params* p, const rt_ao_params* a, const rt_ao* device_out, void* stream);
 
 /* ---- motion vectors and temporal accumulation (DESIGN.md "Motion vectors and temporal accumulation") ----------------
  * Two stateless calls for animated frames.  The library keeps nothing between frames: the caller hands in last frame's
@@ -857,6 +892,7 @@ int rt_profile_collect(rt_ctx* ctx, double* total_kernel_ms, uint32_t* launches)
  *                        square root (the render instances' FAST flavour), and RT_UNIT_BSDF's one-piece form FAST.
  *                        FAST is only promised for vectors whose squared length is below 2^100 (rt_create vouches for
  *                        that bound before it picks a FAST instance); all three then equal RT_UNIT_BSDF bit for bit.
+ *   RT_UNIT_HEMISPHERE   in: state normal3 (4 words)      out: hemisphere dir3, end state (rt_render_ao's sampler)
  */
 enum {
   RT_UNIT_ASIN = 0,
@@ -871,7 +907,8 @@ enum {
   RT_UNIT_LIGHT_SAMPLE = 9,
   RT_UNIT_POW = 10,
   RT_UNIT_RECIP = 11,
-  RT_UNIT_BSDF_HOISTED = 12
+  RT_UNIT_BSDF_HOISTED = 12,
+  RT_UNIT_HEMISPHERE = 13
 };
 int rt_test_unit(int32_t device, uint32_t which, const void* in, void* out, uint32_t n);
 

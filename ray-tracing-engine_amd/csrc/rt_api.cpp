@@ -227,6 +227,9 @@ struct rt_ctx {
   DevBuf<rt_camera> vwPrevCams;
   PinnedBuf<rt_camera> vwPrevHost;
   uint32_t vwPrevCap = 0;
+  // rt_render_ao_device with the default bias (allocated on first use): the box of the referenced vertices, reduced on the
+  // call's stream and read by the kernel behind it
+  DevBuf<uint32_t> aoExt;
 };
 
 namespace {
@@ -1474,9 +1477,9 @@ int rt_profile_collect(rt_ctx* c, double* total_ms, uint32_t* launches) {
 }
 
 int rt_test_unit(int32_t device, uint32_t which, const void* in, void* out, uint32_t n) {
-  static const uint32_t inBytes[] = {8, 4, 4, 16, 60, 68, 56, 96, 112, 88, 8, 4, 68};
-  static const uint32_t outBytes[] = {8, 4, 4, 4, 16, 12, 24, 12, 48, 16, 16, 16, 36};
-  if (which > RT_UNIT_BSDF_HOISTED) return fail(RT_ERR_INVALID, "unknown unit %u", which);
+  static const uint32_t inBytes[] = {8, 4, 4, 16, 60, 68, 56, 96, 112, 88, 8, 4, 68, 16};
+  static const uint32_t outBytes[] = {8, 4, 4, 4, 16, 12, 24, 12, 48, 16, 16, 16, 36, 16};
+  if (which > RT_UNIT_HEMISPHERE) return fail(RT_ERR_INVALID, "unknown unit %u", which);
   if (n && (!in || !out)) return fail(RT_ERR_INVALID, "null argument");
   if (n == 0) return RT_OK;
   int rc = select_device(device);
@@ -3056,6 +3059,75 @@ int rt_render_views(rt_ctx* c, const rt_params* p, const rt_views* v, const floa
   }
   if (accum_out) HIP_TRY(hipMemcpy(accum_out, dAccum.get(), all * sizeof(float4), hipMemcpyDeviceToHost));
   return RT_OK;
+}
+
+}  // extern "C"
+
+// ---- ambient occlusion and bent normals at the first hit ----------------------------------------------
+namespace {
+
+// Everything rt_render_ao checks, in the header's order.  What can be told from the arguments alone is answered before
+// the context is looked at, and a context exists only where a device does.  *q: p as rt_render_aov sees it (the wavefront
+// bit selects an integrator and does not matter here either).
+int ao_checks(const rt_ctx* c, const rt_params* p, const rt_ao_params* a, const rt_ao* out, rt_params* q) {
+  if (!c || !p || !a || !out) return fail(RT_ERR_INVALID, "ctx/params/ao params/ao is null");
+  if (any_set(a->reserved, 5) || any_set(out->reserved, 4)) return fail(RT_ERR_INVALID, "reserved words must be zero");
+  if (a->n_rays == 0 || a->n_rays > RT_AO_MAX_RAYS) return fail(RT_ERR_INVALID, "n_rays %u outside 1..%d", a->n_rays, RT_AO_MAX_RAYS);
+  if ((uint64_t)p->spp * a->n_rays >= (1ull << 32)) return fail(RT_ERR_INVALID, "spp * n_rays (%u * %u) does not fit 32 bits", p->spp, a->n_rays);
+  if (!(a->bias >= 0.f) || !std::isfinite(a->bias)) return fail(RT_ERR_INVALID, "bias must be finite and >= 0");
+  if (!(a->max_distance >= 0.f) || !std::isfinite(a->max_distance)) return fail(RT_ERR_INVALID, "max_distance must be finite and >= 0");
+  *q = aov_params(*p);
+  q->reserved[2] &= ~1u;
+  int rc = check_params_shape(q);
+  if (rc != RT_OK) return rc;
+  if (q->world > 1) return fail(RT_ERR_UNSUPPORTED, "tile-sharded ambient occlusion (world %u) is not supported", q->world);
+  if ((rc = check_device_present()) != RT_OK) return rc;
+  return check_not_broken(c);
+}
+
+// The launch behind both forms: q and a have passed ao_checks, out holds device pointers.
+int ao_launch(rt_ctx* c, const rt_params& q, const rt_ao_params* a, const rt_ao* out, hipStream_t s) {
+  HIP_TRY(hipSetDevice(c->device));
+  rtk::AoArgs A{};
+  A.unoccluded = out->unoccluded, A.hits = out->hits, A.bent = out->bent;
+  A.width = q.width, A.height = q.height, A.spp = q.spp, A.seed = q.seed;
+  A.s0 = q.spp_count ? q.spp_begin : 0;
+  A.s1 = q.spp_count ? q.spp_begin + q.spp_count : q.spp;
+  A.nRays = a->n_rays, A.bias = a->bias, A.maxDistance = a->max_distance;
+  if (a->bias == 0.f) {
+    if (!c->aoExt) HIP_TRY(dev_alloc(&c->aoExt, 6));
+    const hipError_t he = rtk::launch_ref_extent(c->S, c->aoExt.get(), s);
+    if (he != hipSuccess) return fail(RT_ERR_HIP, "extent reduction failed: %s", hipGetErrorString(he));
+    A.ext = c->aoExt.get();
+  }
+  const hipError_t he = rtk::launch_ao(q.accel == RT_ACCEL_BRUTE, c->S, A, s);
+  if (he != hipSuccess) return fail(RT_ERR_HIP, "ambient occlusion launch failed: %s", hipGetErrorString(he));
+  return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_render_ao_device(rt_ctx* c, const rt_params* p, const rt_ao_params* a, const rt_ao* out, void* stream) {
+  rt_params q;
+  const int rc = ao_checks(c, p, a, out, &q);
+  if (rc != RT_OK) return rc;
+  return ao_launch(c, q, a, out, static_cast<hipStream_t>(stream));
+}
+
+int rt_render_ao(rt_ctx* c, const rt_params* p, const rt_ao_params* a, const rt_ao* out) {
+  rt_params q;
+  int rc = ao_checks(c, p, a, out, &q);
+  if (rc != RT_OK) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t npx = (size_t)q.width * q.height;
+  Staging st;
+  rt_ao d = {};
+  d.unoccluded = st.out(out->unoccluded, npx), d.hits = st.out(out->hits, npx), d.bent = st.out(out->bent, 3 * npx);
+  if (st.rc != RT_OK) return st.rc;
+  if ((rc = ao_launch(c, q, a, &d, nullptr)) != RT_OK) return rc;
+  return st.download();
 }
 
 }  // extern "C"

@@ -125,6 +125,18 @@ struct AovArgs {
   uint32_t tilesPerView = 0;
 };
 hipError_t launch_aov(bool brute_force, const DevScene& S, const AovArgs& A, hipStream_t stream);
+// ambient occlusion and bent normals at the first hit (ao_kernels.h, rt_render_ao): per pixel, over the samples [s0, s1),
+// the occlusion rays that escaped, the hit samples, and the float32 sum of the escaped directions; null channels are not written
+struct AoArgs {
+  uint32_t *unoccluded, *hits;  // [h][w] each
+  float* bent;                  // [h][w][3]
+  uint32_t width, height, spp, seed, s0, s1;
+  uint32_t nRays;               // occlusion rays per primary hit
+  float bias;                   // 0: 1e-4 of the diagonal of the box in ext
+  float maxDistance;            // 0: unbounded
+  const uint32_t* ext;          // the referenced vertices' box as launch_ref_extent leaves it (read when bias == 0)
+};
+hipError_t launch_ao(bool brute_force, const DevScene& S, const AoArgs& A, hipStream_t stream);
 // First element of view j's slice of a per-view output with c floats or words per pixel (rt_render_aov_views,
 // rt_render_motion_views, rt_denoise_batch): formed in 64 bits — n w h may reach 2^31 - 1 and 3 x that is not 32-bit.
 __host__ __device__ inline size_t view_slice(uint32_t j, uint32_t width, uint32_t height, uint32_t c) {

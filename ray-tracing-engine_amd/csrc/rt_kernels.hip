@@ -30,6 +30,7 @@
 #include <type_traits>
 
 #include "bvh_build.h"
+#include "filters.h"
 #include "rt_device.h"
 #include "rt_kernels.h"
 
@@ -1532,6 +1533,9 @@ __global__ __launch_bounds__(1024, 8) void k_trace_stream(DevScene S, const floa
 // ---------------------------------------------------------------- motion vectors (rt_render_motion)
 #include "motion_kernels.h"
 
+// ---------------------------------------------------------------- ambient occlusion (rt_render_ao)
+#include "ao_kernels.h"
+
 // ---------------------------------------------------------------- frame assembly (multi-GPU)
 // A rank's owned 8x8-pixel granules, packed [granule][64 pixels] (row-major inside the
 // granule; slots outside the image are never read back), and the inverse on the rank
@@ -2180,6 +2184,10 @@ hipError_t launch_selfcheck_recip(uint32_t* dBad, hipStream_t stream) {
 
 hipError_t launch_unit(uint32_t which, const void* in, void* out, uint32_t n, hipStream_t stream) {
   if (n == 0) return hipSuccess;
+  if (which == RT_UNIT_HEMISPHERE) {
+    hipLaunchKernelGGL(k_unit_hemisphere, dim3((n + 255) / 256), dim3(256), 0, stream, (const uint32_t*)in, (uint32_t*)out, n);
+    return hipGetLastError();
+  }
   hipLaunchKernelGGL(k_unit, dim3((n + 255) / 256), dim3(256), 0, stream, which, in, out, n);
   return hipGetLastError();
 }

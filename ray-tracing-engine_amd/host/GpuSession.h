@@ -81,6 +81,8 @@ struct GpuSettings {
   bool aov = false;       // also the first-hit AOV means (Renderer::albedo() / normal(); single device only)
   double adaptive = -1.;  // >= 0: adaptive sampling with this threshold (rt_render_adaptive; single device only)
   unsigned pass = 16;     // samples per adaptive pass (the frame's spp is the per-pixel maximum, a multiple of it)
+  unsigned ao = 0;        // > 0: also the ambient occlusion of this many rays per primary hit (Renderer::ao(); single device only)
+  double aoDistance = 0.; // ... with occluders up to this distance in scene units (0 = unbounded)
   std::vector<int> devices;  // more than one entry: Renderer::render tile-shards the frame over them (rt_group)
   static GpuSettings& get() {
     static GpuSettings s;

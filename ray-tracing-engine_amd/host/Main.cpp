@@ -31,6 +31,8 @@ int main(int argc, char** argv) {
   GpuSettings::get().aov = args.aov() != 0;
   GpuSettings::get().adaptive = args.adaptive();
   GpuSettings::get().pass = static_cast<unsigned>(args.pass());
+  GpuSettings::get().ao = static_cast<unsigned>(args.ao());
+  GpuSettings::get().aoDistance = args.aoDist();
   // -gpus N: devices gpu..gpu+N-1; -devices a,b,c: an explicit list (may repeat a device:
   // rehearsal of the N-rank flow on one GPU)
   if (!args.devices().empty()) {
@@ -48,6 +50,19 @@ int main(int argc, char** argv) {
 
   if ((args.denoise() || args.aov()) && GpuSettings::get().devices.size() > 1) {
     std::cerr << "error: -denoise / -aov run on one GPU only (not with -gpus > 1)" << std::endl;
+    return 1;
+  }
+  if (args.ao() && GpuSettings::get().devices.size() > 1) {
+    std::cerr << "error: -ao runs on one GPU only (not with -gpus > 1)" << std::endl;
+    return 1;
+  }
+  // (before the frame is rendered: rt_render_ao would refuse these after it)
+  if (args.ao() > RT_AO_MAX_RAYS) {  // (a negative value wraps far above)
+    std::cerr << "error: -ao must be in 0.." << RT_AO_MAX_RAYS << " (0 = off)" << std::endl;
+    return 1;
+  }
+  if (!(args.aoDist() >= 0.) || !(args.aoDist() < 3.0e38)) {
+    std::cerr << "error: -aodist must be a finite distance >= 0 (0 = unbounded)" << std::endl;
     return 1;
   }
   if (args.adaptive() >= 0.) {
@@ -75,12 +90,13 @@ int main(int argc, char** argv) {
     image.fillBackground();
     renderer.render(image);
     image.savePPM(args.outputFilename());
-    // -denoise / -aov: <stem>_denoised.ppm, <stem>_albedo.ppm, <stem>_normal.ppm next to the output
+    // -denoise / -aov / -ao: <stem>_denoised.ppm, <stem>_albedo.ppm, <stem>_normal.ppm, <stem>_ao.ppm next to the output
     const std::string& of = args.outputFilename();
     const std::string stem = of.size() > 4 && of.compare(of.size() - 4, 4, ".ppm") == 0 ? of.substr(0, of.size() - 4) : of;
     if (args.denoise()) renderer.denoised().savePPM(stem + "_denoised.ppm");
     if (args.aov()) renderer.albedo().savePPM(stem + "_albedo.ppm"), renderer.normal().savePPM(stem + "_normal.ppm");
     if (args.adaptive() >= 0.) renderer.sppMap().savePPM(stem + "_spp.ppm");
+    if (args.ao()) renderer.ao().savePPM(stem + "_ao.ppm");
 
     const rt_stats& st = renderer.lastStats();
     const double rays = static_cast<double>(st.rays_closest + st.rays_shadow);

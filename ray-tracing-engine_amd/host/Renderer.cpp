@@ -163,4 +163,25 @@ inline void Renderer::render(Image& image) {
       GpuSession::check(rt_denoise(ctx0, &dp, image.data(), &aov, m_denoised.data()), "rt_denoise");
     }
   }
+
+  // -ao N [-aodist D] (extension): N occlusion rays at every primary hit of this frame (rt_render_ao, the default bias),
+  // as the grey mean unoccluded / (hits N), 1 where no sample hit.  The frame itself stays as it is.
+  const uint32_t aoRays = GpuSettings::get().ao;
+  if (aoRays && multi) throw std::runtime_error("-ao runs on one GPU only (not with -gpus > 1)");
+  if (aoRays && p.spp > 0) {
+    p.spp_begin = 0, p.spp_count = 0;
+    const size_t npx = static_cast<size_t>(w) * h;
+    std::vector<uint32_t> un(npx), hits(npx);
+    rt_ao_params ap = {};
+    ap.n_rays = aoRays, ap.max_distance = static_cast<float>(GpuSettings::get().aoDistance);
+    rt_ao out = {};
+    out.unoccluded = un.data(), out.hits = hits.data();
+    GpuSession::check(rt_render_ao(ctx0, &p, &ap, &out), "rt_render_ao");
+    m_ao = Image(w, h);
+    for (size_t i = 0; i < npx; ++i) {
+      const float den = static_cast<float>(hits[i]) * static_cast<float>(aoRays);
+      const float v = hits[i] ? static_cast<float>(un[i]) / den : 1.f;
+      for (int k = 0; k < 3; ++k) m_ao.data()[3 * i + k] = v;
+    }
+  }
 }

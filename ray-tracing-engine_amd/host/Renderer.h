@@ -47,6 +47,8 @@ class Renderer {
   const Image& normal() const { return m_normal; }
   // GpuSettings::adaptive: samples per pixel of the last render() over the maximum (grey, spp / N)
   const Image& sppMap() const { return m_spp; }
+  // GpuSettings::ao: the share of the occlusion rays that escaped (grey; 1 where no sample hit) of the last render()
+  const Image& ao() const { return m_ao; }
 
  private:
   int m_numRays, m_mode, m_numPhotons, m_k;
@@ -55,5 +57,5 @@ class Renderer {
   Scene m_scene;
   float m_factor = 100.f;
   rt_stats m_stats = {};
-  Image m_denoised, m_albedo, m_normal, m_spp;
+  Image m_denoised, m_albedo, m_normal, m_spp, m_ao;
 };

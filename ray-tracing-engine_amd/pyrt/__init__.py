@@ -22,7 +22,7 @@ ACCEL_BVH, ACCEL_BRUTE = 0, 1
 BVH_AUTO, BVH_DEVICE, BVH_HYBRID, BVH_HOST = 0, 1, 2, 3
 TRACE_CLOSEST, TRACE_ANY = 0, 1
 (UNIT_ASIN, UNIT_SINF, UNIT_COSF, UNIT_STREAM_SEED, UNIT_TRIANGLE, UNIT_BSDF, UNIT_RAY_AT, UNIT_LIGHT_EVAL,
- UNIT_SAMPLERS, UNIT_LIGHT_SAMPLE, UNIT_POW, UNIT_RECIP, UNIT_BSDF_HOISTED) = range(13)
+ UNIT_SAMPLERS, UNIT_LIGHT_SAMPLE, UNIT_POW, UNIT_RECIP, UNIT_BSDF_HOISTED, UNIT_HEMISPHERE) = range(14)
 KMAX = 16  # rt_knn
 KMAX_WIDE = 256  # rt_knn_wide and photon frames (RT_KNN_KMAX)
 
@@ -154,6 +154,20 @@ class Aov(C.Structure):
     """rt_aov: channel pointers (host or device), None = channel not wanted."""
     _fields_ = [("albedo", C.c_void_p), ("normal", C.c_void_p), ("position", C.c_void_p), ("depth", C.c_void_p),
                 ("hits", C.c_void_p), ("mesh", C.c_void_p), ("tri", C.c_void_p), ("reserved", C.c_uint32 * 4)]
+
+
+AO_MAX_RAYS = 256
+
+
+class AoParams(C.Structure):
+    """rt_ao_params: occlusion rays per primary hit, the origin bias (0 = 1e-4 of the scene's diagonal) and the distance
+    limit (0 = unbounded)."""
+    _fields_ = [("n_rays", C.c_uint32), ("bias", C.c_float), ("max_distance", C.c_float), ("reserved", C.c_uint32 * 5)]
+
+
+class Ao(C.Structure):
+    """rt_ao: channel pointers (host or device), None = channel not wanted."""
+    _fields_ = [("unoccluded", C.c_void_p), ("hits", C.c_void_p), ("bent", C.c_void_p), ("reserved", C.c_uint32 * 4)]
 
 
 class DenoiseParams(C.Structure):
@@ -307,6 +321,20 @@ def aov_means(sums):
     return out
 
 
+AO_CHANNELS = ("unoccluded", "hits", "bent")
+
+
+def ao_means(sums, n_rays):
+    """The means of rt_render_ao's sums: ao = unoccluded / (hits * n_rays), 1 where hits == 0 (float32 [h][w]), and bent =
+    bent / max(unoccluded, 1) (float32 [h][w][3])."""
+    un, hits = sums["unoccluded"], sums["hits"]
+    den = hits.astype(np.float32) * np.float32(n_rays)
+    out = {"ao": np.where(hits > 0, un.astype(np.float32) / np.maximum(den, np.float32(1)), np.float32(1)).astype(np.float32)}
+    if "bent" in sums:
+        out["bent"] = (sums["bent"] / np.maximum(un, 1).astype(np.float32)[..., None]).astype(np.float32)
+    return out
+
+
 RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("direction", "<f4", 3)])
 HIT_DTYPE = np.dtype([("hit", "<i4"), ("mesh", "<u4"), ("tri", "<u4"), ("vtx", "<u4", 3), ("u", "<f4"),
                       ("v", "<f4"), ("d", "<f4")])
@@ -322,7 +350,7 @@ AMD_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_create", "rt_destroy", "rt
                "rt_render_views_device", "rt_render_motion", "rt_render_motion_device", "rt_temporal_accumulate",
                "rt_temporal_accumulate_device", "rt_svgf", "rt_svgf_device", "rt_bvh_quality_get", "rt_rebuild",
                "rt_render_aov_views", "rt_render_aov_views_device", "rt_render_motion_views", "rt_render_motion_views_device",
-               "rt_denoise_batch", "rt_denoise_batch_device"]
+               "rt_denoise_batch", "rt_denoise_batch_device", "rt_render_ao", "rt_render_ao_device"]
 HOST_SYMBOLS = ["rt_host_scene_build", "rt_host_scene_desc", "rt_host_scene_free", "rt_host_last_error",
                 "rt_host_fill_background", "rt_host_save_ppm", "rt_host_kd_order", "rt_host_light_basis"]
 
@@ -403,6 +431,8 @@ def amd():
         L.rt_rebuild.argtypes = [C.c_void_p, C.POINTER(RebuildParams), C.POINTER(RebuildReport)]
         L.rt_render_aov.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Aov)]
         L.rt_render_aov_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Aov), C.c_void_p]
+        L.rt_render_ao.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(AoParams), C.POINTER(Ao)]
+        L.rt_render_ao_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(AoParams), C.POINTER(Ao), C.c_void_p]
         L.rt_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.POINTER(Aov), C.c_void_p]
         L.rt_render_adaptive.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(AdaptiveParams), C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.POINTER(AdaptiveReport), C.POINTER(Stats)]
@@ -812,6 +842,32 @@ class Context:
         _check(amd().rt_render_aov_device(self._h, C.byref(params), C.byref(a), C.c_void_p(stream or None)))
 
     @staticmethod
+    def _ao_params(n_rays, bias, max_distance):
+        a = AoParams()
+        a.n_rays, a.bias, a.max_distance = n_rays, bias, max_distance
+        return a
+
+    def render_ao(self, params, n_rays, bias=0., max_distance=0., channels=AO_CHANNELS):
+        """rt_render_ao: n_rays occlusion rays at every primary hit of the frame `params` describes.  The SUMS as a dict
+        of numpy arrays: unoccluded, hits [h][w] uint32 and bent [h][w][3] float32 (ao_means turns them into means).
+        bias 0: 1e-4 of the scene's diagonal; max_distance 0: unbounded.  `channels`: the ones wanted."""
+        w, h = params.width, params.height
+        sums, o = {}, Ao()
+        for k in channels:
+            sums[k] = np.zeros((h, w, 3), np.float32) if k == "bent" else np.zeros((h, w), np.uint32)
+            setattr(o, k, sums[k].ctypes.data)
+        _check(amd().rt_render_ao(self._h, C.byref(params), C.byref(self._ao_params(n_rays, bias, max_distance)), C.byref(o)))
+        return sums
+
+    def render_ao_device(self, params, n_rays, ptrs, bias=0., max_distance=0., stream=0):
+        """rt_render_ao_device: the sums into device buffers; ptrs = {channel: device pointer} (missing = not wanted)."""
+        o = Ao()
+        for k, v in ptrs.items():
+            setattr(o, k, v or None)
+        _check(amd().rt_render_ao_device(self._h, C.byref(params), C.byref(self._ao_params(n_rays, bias, max_distance)), C.byref(o),
+                                         C.c_void_p(stream or None)))
+
+    @staticmethod
     def _motion_prev(prev_pos, prev_camera):
         """An rt_motion_prev: prev_pos a numpy array [n_vertices][3] (host form), a device pointer (int) or None;
         prev_camera [4][3] floats or None.  Returns it and the arrays it points into."""
@@ -1165,7 +1221,7 @@ _UNIT_IO = {UNIT_ASIN: (np.float64, 1, np.float64, 1), UNIT_SINF: (np.float32, 1
             UNIT_RAY_AT: (np.float32, 14, np.float32, 6), UNIT_LIGHT_EVAL: (np.float32, 24, np.float32, 3),
             UNIT_SAMPLERS: (np.uint32, 28, np.uint32, 12), UNIT_LIGHT_SAMPLE: (np.uint32, 22, np.uint32, 4),
             UNIT_POW: (np.float64, 1, np.float64, 2), UNIT_RECIP: (np.float32, 1, np.float32, 4),
-            UNIT_BSDF_HOISTED: (np.float32, 17, np.float32, 9)}
+            UNIT_BSDF_HOISTED: (np.float32, 17, np.float32, 9), UNIT_HEMISPHERE: (np.uint32, 4, np.uint32, 4)}
 
 
 def unit(which, inp, out_init=None, device=0):
