@@ -30,6 +30,8 @@
  *                                  (+ _device form)
  *   rt_render_ao                <- (no counterpart) ambient occlusion and bent normals at the frame's first hit
  *                                  (+ _device form)
+ *   rt_render_rays              <- (no counterpart) the integrator over ray batches of the caller's: probes, baking,
+ *                                  cameras of any kind (+ _device form)
  *   rt_render_aov_views / rt_render_motion_views / rt_denoise_batch <- (no counterpart) the AOVs, motion vectors and
  *                                  denoised frames of those views, one launch each (+ _device forms)
  *   rt_trace                    <- RayTracer::rayTrace (RayTracer.h:27-53) test hook
@@ -473,6 +475,54 @@ int rt_render_ao(rt_ctx* ctx, const rt_params* p, const rt_ao_params* a, const r
 /* The same into DEVICE buffers on `stream` (may be NULL); no synchronisation.  With the default bias the box is reduced
  * on the stream into a block the context owns: such calls run one at a time, as rt_denoise_device's do.                */
 int rt_render_ao_device(rt_ctx* ctx, const rt_params* p, const rt_ao_params* a, const rt_ao* device_out, void* stream);
+
+/* ---- the integrator over ray batches of the caller's -------------------------------------------------
+ * rt_render_rays integrates p->mode / p->max_depth along n primary rays that the caller gives, where every other entry
+ * point casts a pinhole camera's: light probes, lightmap or per-vertex baking, orthographic, fisheye or thin-lens
+ * cameras, a batch a pipeline already holds in device memory.
+ *
+ * Row r of the accumulator is, bit for bit, what pixel (0, 0) of a frame that rt_render_device renders for p holds if
+ * that frame's camera_ray returned origin o_r and direction unit3(d_r) for every sample, the frame's pixel index in the
+ * RNG stream was stream_index[r] (r when stream_index is NULL), and its sample range was p's.  Sample i
+ *   - seeds the engine with rt_stream_seed(p->seed, RT_STREAM_PIXEL, stream_index[r], i),
+ *   - draws jitter_sample(engine, i, p->spp) and DISCARDS the result, so that the stream is then where the frame's is,
+ *   - casts the primary ray (o_r, unit3(d_r)) — Vec3.h:170-178 in float32: the division and the square root, never the
+ *     short forms,
+ *   - integrates exactly as the frame does: the vertices, the light samples in light order, the hemisphere draw after
+ *     every shaded vertex, c0 + (c1 + (c2 + 0)) and the clamp to [0, 1],
+ *   - adds in float32, in sample order: rgb into .xyz, and 1 into .w when the primary ray hit.
+ * Resolve a batch with rt_resolve_device(ctx, n, 1, spp, ...): an image n wide and 1 high.
+ * Far origins: a primary ray whose origin has a component beyond the context's origin bound (rt_trace's rule) takes
+ * the exhaustive loop over the triangles; its secondary rays start on surfaces and walk the tree.
+ * Degenerate directions — unit3(d_r) has a non-finite component or is the null vector: a zero direction, a non-finite
+ * one, or a finite one so long that its squared length overflows float32 — hit nothing.  The host form refuses them
+ * (RT_ERR_INVALID, naming the ray); the device form, which cannot look, counts the ray as a primary miss: it adds nothing
+ * and casts nothing.
+ * p->width and p->height are ignored; every other field of p is checked as rt_render checks it.  RT_NODES_Q8 contexts
+ * walk their resident 32-byte records, as rt_render_aov does.  The call changes nothing in the context: not the camera,
+ * not the box padding.
+ * stats: samples = n * (samples of the range); rays_closest, rays_shadow, kernel_ms and, with collect_stats,
+ * nodes_visited and tris_tested as for a frame; an exhaustive primary cast counts one closest ray and every triangle.
+ * Validation comes first and a rejected call writes nothing.  RT_ERR_INVALID: a null ctx, p, b or rays; n of 0 or of
+ * 2^31 and more; non-zero reserved words; rt_render's checks of p; host form: neither out_rgb nor accum_out, out_rgb
+ * without background_rgb, a non-finite origin, a degenerate direction; device form: a null d_accum.
+ * RT_ERR_UNSUPPORTED: world > 1, use_photons, the wavefront integrator (reserved[2] bit 0), the legacy RNG.
+ * The host form stages rays and indices in scratch the context owns: one call at a time.                               */
+typedef struct rt_ray_batch {
+  uint32_t n;                    /* 1 .. 2^31 - 1                                                          */
+  uint32_t reserved0;            /* zero                                                                   */
+  const rt_ray* rays;            /* [n]; host form: HOST memory, device form: DEVICE memory                */
+  const uint32_t* stream_index;  /* [n] or NULL = r; the same memory space as rays                         */
+  uint32_t reserved[6];          /* zero                                                                   */
+} rt_ray_batch;
+/* background_rgb [n][3] (required when out_rgb is given, as rt_render); out_rgb [n][3] or NULL; accum_out [n][4] or
+ * NULL; stats may be NULL. */
+int rt_render_rays(rt_ctx* ctx, const rt_params* p, const rt_ray_batch* b, const float* background_rgb, float* out_rgb,
+                   float* accum_out, rt_stats* stats);
+/* Accumulate into caller-zeroed DEVICE d_accum [n][4] on `stream` (a hipStream_t, may be NULL), as rt_render_device
+ * does: sample ranges chain.  The host waits only to read stats back. */
+int rt_render_rays_device(rt_ctx* ctx, const rt_params* p, const rt_ray_batch* b, void* d_accum, void* stream,
+                          rt_stats* stats);
 
 /* ---- motion vectors and temporal accumulation (DESIGN.md "Motion vectors and temporal accumulation") ----------------
  * Two stateless calls for animated frames.  The library keeps nothing between frames: the caller hands in last frame's

@@ -230,6 +230,10 @@ struct rt_ctx {
   // rt_render_ao_device with the default bias (allocated on first use): the box of the referenced vertices, reduced on the
   // call's stream and read by the kernel behind it
   DevBuf<uint32_t> aoExt;
+  // scratch of rt_render_rays' host form (grows on demand): the batch's rays and stream indices on the device
+  DevBuf<rt_ray> rbRays;
+  DevBuf<uint32_t> rbIndex;
+  size_t rbCap = 0, rbIndexCap = 0;
 };
 
 namespace {
@@ -3128,6 +3132,133 @@ int rt_render_ao(rt_ctx* c, const rt_params* p, const rt_ao_params* a, const rt_
   if (st.rc != RT_OK) return st.rc;
   if ((rc = ao_launch(c, q, a, &d, nullptr)) != RT_OK) return rc;
   return st.download();
+}
+
+}  // extern "C"
+
+// ---- the integrator over ray batches of the caller's --------------------------------------------------
+namespace {
+
+// Everything both forms of rt_render_rays check in their arguments, in the header's order; the device is asked for by
+// the caller, behind its own checks.  *q: p with the ignored size neutralised.
+int rays_checks(const rt_ctx* c, const rt_params* p, const rt_ray_batch* b, rt_params* q) {
+  if (!c || !p || !b || !b->rays) return fail(RT_ERR_INVALID, "ctx/params/batch/rays is null");
+  if (b->reserved0 || any_set(b->reserved, 6)) return fail(RT_ERR_INVALID, "rt_ray_batch: reserved words must be zero");
+  if (b->n == 0 || b->n >= (1u << 31)) return fail(RT_ERR_INVALID, "n %u outside 1..2^31-1", b->n);
+  *q = *p;
+  q->width = q->height = 1;
+  const int rc = check_params_shape(q);
+  if (rc != RT_OK) return rc;
+  if (q->world > 1) return fail(RT_ERR_UNSUPPORTED, "tile-sharded ray batches (world %u) are not supported", q->world);
+  if (q->use_photons) return fail(RT_ERR_UNSUPPORTED, "ray batches do not shade from the photon map");
+  if (q->reserved[2] & 1u) return fail(RT_ERR_UNSUPPORTED, "ray batches do not run the wavefront integrator");
+  return RT_OK;
+}
+
+// unit3(d) (rt_device.h) has a non-finite component or is the null vector: d is null or not finite, or its squared
+// length — (x x + y y) + z z in float32, as dot3 forms it — overflows
+bool degenerate_direction(const float* d) {
+  if (!std::isfinite(d[0]) || !std::isfinite(d[1]) || !std::isfinite(d[2])) return true;
+  if (d[0] == 0.f && d[1] == 0.f && d[2] == 0.f) return true;
+  const float xx = d[0] * d[0], yy = d[1] * d[1], zz = d[2] * d[2];
+  const float xy = xx + yy;
+  const float len2 = xy + zz;
+  return !std::isfinite(len2);
+}
+
+// The launch behind both forms: q and b have passed rays_checks, b holds device pointers.  Bracketed by an event pair.
+int rays_launch(rt_ctx* c, const rt_params& q, const rt_ray_batch& b, float4* dAccum, hipStream_t s, rt_stats* stats) {
+  if (stats) HIP_TRY(hipMemsetAsync(c->dCounters.get(), 0, RTK_CNT_COUNT * sizeof(unsigned long long), s));
+  rtk::RaysArgs A{};
+  A.rays = b.rays, A.streamIndex = b.stream_index, A.n = b.n;
+  A.spp = q.spp, A.mode = q.mode, A.max_depth = q.max_depth, A.seed = q.seed;
+  A.s0 = q.spp_count ? q.spp_begin : 0;
+  A.s1 = q.spp_count ? q.spp_begin + q.spp_count : q.spp;
+  A.flags = (q.reserved[1] & 1u) ? 0u : 1u;
+  A.stackLevels = stack_levels(c->bvh.maxDepth > 1 ? c->bvh.maxDepth : 1);
+  const int e = c->evUsed % kEventPairs;
+  HIP_TRY(hipEventRecord(c->ev[e][0].get(), s));
+  const hipError_t he = rtk::launch_render_rays(q.accel == RT_ACCEL_BRUTE, q.collect_stats != 0, c->S, A, dAccum, c->dCounters.get(), s);
+  if (he != hipSuccess) return fail(RT_ERR_HIP, "ray batch launch failed: %s", hipGetErrorString(he));
+  HIP_TRY(hipEventRecord(c->ev[e][1].get(), s));
+  c->evUsed++;
+  if (stats) {
+    memset(stats, 0, sizeof *stats);
+    HIP_TRY(hipStreamSynchronize(s));
+    const int rc = read_counters(c, stats);
+    if (rc != RT_OK) return rc;
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev[e][0].get(), c->ev[e][1].get()));
+    stats->kernel_ms = ms;
+    stats->samples = (uint64_t)b.n * (A.s1 - A.s0);
+  }
+  return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_render_rays_device(rt_ctx* c, const rt_params* p, const rt_ray_batch* b, void* d_accum, void* stream, rt_stats* stats) {
+  rt_params q;
+  int rc = rays_checks(c, p, b, &q);
+  if (rc != RT_OK) return rc;
+  if (!d_accum) return fail(RT_ERR_INVALID, "d_accum is null");
+  if ((rc = check_device_present()) != RT_OK) return rc;
+  if ((rc = check_not_broken(c)) != RT_OK) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  return rays_launch(c, q, *b, static_cast<float4*>(d_accum), static_cast<hipStream_t>(stream), stats);
+}
+
+int rt_render_rays(rt_ctx* c, const rt_params* p, const rt_ray_batch* b, const float* bg, float* out_rgb, float* accum_out,
+                   rt_stats* stats) {
+  rt_params q;
+  int rc = rays_checks(c, p, b, &q);
+  if (rc != RT_OK) return rc;
+  if (!out_rgb && !accum_out) return fail(RT_ERR_INVALID, "neither out_rgb nor accum_out is given");
+  if (out_rgb && !bg) return fail(RT_ERR_INVALID, "out_rgb requested without a background");
+  const size_t n = b->n;
+  for (size_t r = 0; r < n; ++r) {
+    const rt_ray& ray = b->rays[r];
+    if (!std::isfinite(ray.origin[0]) || !std::isfinite(ray.origin[1]) || !std::isfinite(ray.origin[2]))
+      return fail(RT_ERR_INVALID, "ray %zu: non-finite origin", r);
+    if (degenerate_direction(ray.direction))
+      return fail(RT_ERR_INVALID, "ray %zu: direction (%g, %g, %g) cannot be normalised", r, ray.direction[0], ray.direction[1], ray.direction[2]);
+  }
+  if ((rc = check_device_present()) != RT_OK) return rc;
+  if ((rc = check_not_broken(c)) != RT_OK) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  if (n > c->rbCap) {
+    c->rbCap = 0;
+    if (c->rbRays) HIP_TRY(hipFree(c->rbRays.release()));
+    HIP_TRY(dev_alloc(&c->rbRays, n));
+    c->rbCap = n;
+  }
+  if (b->stream_index && n > c->rbIndexCap) {
+    c->rbIndexCap = 0;
+    if (c->rbIndex) HIP_TRY(hipFree(c->rbIndex.release()));
+    HIP_TRY(dev_alloc(&c->rbIndex, n));
+    c->rbIndexCap = n;
+  }
+  HIP_TRY(hipMemcpy(c->rbRays.get(), b->rays, n * sizeof(rt_ray), hipMemcpyHostToDevice));
+  if (b->stream_index) HIP_TRY(hipMemcpy(c->rbIndex.get(), b->stream_index, n * sizeof(uint32_t), hipMemcpyHostToDevice));
+  rt_ray_batch d = *b;
+  d.rays = c->rbRays.get(), d.stream_index = b->stream_index ? c->rbIndex.get() : nullptr;
+  DevBuf<float4> dAccum;
+  DevBuf<float> dBg, dOut;
+  HIP_TRY(dev_alloc(&dAccum, n));
+  HIP_TRY(hipMemset(dAccum.get(), 0, n * sizeof(float4)));
+  rt_stats local;
+  if ((rc = rays_launch(c, q, d, dAccum.get(), nullptr, stats ? stats : &local)) != RT_OK) return rc;
+  if (out_rgb) {  // the batch as an image n wide and 1 high
+    HIP_TRY(dev_alloc(&dBg, n * 3));
+    HIP_TRY(dev_alloc(&dOut, n * 3));
+    HIP_TRY(hipMemcpy(dBg.get(), bg, n * 3 * sizeof(float), hipMemcpyHostToDevice));
+    if ((rc = rt_resolve_device(c, b->n, 1, q.spp, dAccum.get(), dBg.get(), dOut.get(), nullptr)) != RT_OK) return rc;
+    HIP_TRY(hipMemcpy(out_rgb, dOut.get(), n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  }
+  if (accum_out) HIP_TRY(hipMemcpy(accum_out, dAccum.get(), n * sizeof(float4), hipMemcpyDeviceToHost));
+  return RT_OK;
 }
 
 }  // extern "C"

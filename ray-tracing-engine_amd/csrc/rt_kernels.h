@@ -137,6 +137,18 @@ struct AoArgs {
   const uint32_t* ext;          // the referenced vertices' box as launch_ref_extent leaves it (read when bias == 0)
 };
 hipError_t launch_ao(bool brute_force, const DevScene& S, const AoArgs& A, hipStream_t stream);
+// the integrator over a batch of the caller's rays (rays_kernels.h, rt_render_rays): row r of accum gains the samples
+// [s0, s1) of ray r, whose RNG stream is keyed by streamIndex[r] (null: r)
+struct RaysArgs {
+  const rt_ray* rays;           // [n], device memory; directions of any length
+  const uint32_t* streamIndex;  // [n] or null
+  uint32_t n;                   // 1 .. 2^31 - 1
+  uint32_t spp, s0, s1, mode, max_depth, seed;
+  uint32_t flags;               // bit 0: shadow and bounce rays through the wave-level pool (RenderArgs::flags)
+  uint32_t stackLevels;         // LDS traversal-stack rows per wave (RenderArgs::stackLevels)
+};
+hipError_t launch_render_rays(bool brute_force, bool stats, const DevScene& S, const RaysArgs& A, float4* accum,
+                              unsigned long long* counters, hipStream_t stream);
 // First element of view j's slice of a per-view output with c floats or words per pixel (rt_render_aov_views,
 // rt_render_motion_views, rt_denoise_batch): formed in 64 bits — n w h may reach 2^31 - 1 and 3 x that is not 32-bit.
 __host__ __device__ inline size_t view_slice(uint32_t j, uint32_t width, uint32_t height, uint32_t c) {

@@ -170,6 +170,13 @@ class Ao(C.Structure):
     _fields_ = [("unoccluded", C.c_void_p), ("hits", C.c_void_p), ("bent", C.c_void_p), ("reserved", C.c_uint32 * 4)]
 
 
+class RayBatch(C.Structure):
+    """rt_ray_batch: n rays (RAY_DTYPE records) and, optionally, the pixel index each ray's RNG stream is keyed by; host
+    pointers for rt_render_rays, device pointers for rt_render_rays_device."""
+    _fields_ = [("n", C.c_uint32), ("reserved0", C.c_uint32), ("rays", C.c_void_p), ("stream_index", C.c_void_p),
+                ("reserved", C.c_uint32 * 6)]
+
+
 class DenoiseParams(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("iterations", C.c_uint32), ("sigma_color", C.c_float),
                 ("sigma_normal", C.c_float), ("sigma_position", C.c_float), ("reserved", C.c_uint32 * 6)]
@@ -339,6 +346,22 @@ RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("direction", "<f4", 3)])
 HIT_DTYPE = np.dtype([("hit", "<i4"), ("mesh", "<u4"), ("tri", "<u4"), ("vtx", "<u4", 3), ("u", "<f4"),
                       ("v", "<f4"), ("d", "<f4")])
 
+
+def pixel_rays(camera, width, height):
+    """The pixel-centre primary rays of a pinhole camera ([4][3]: position, lower-left corner, horizontal, vertical) on
+    a width x height grid, row-major from the top row, as RAY_DTYPE [height * width]: Camera.h:27-30 in float32 at u =
+    (x + 0.5) / width, v = 1 - (y + 0.5) / height, the direction left UN-normalised (rt_render_rays normalises)."""
+    f = np.float32
+    cam = np.asarray(camera, f).reshape(4, 3)
+    u = ((np.arange(width, dtype=f) + f(0.5)) / f(width)).astype(f)
+    v = (f(1) - (np.arange(height, dtype=f) + f(0.5)) / f(height)).astype(f)
+    d = ((cam[1] + u[None, :, None] * cam[2]) + v[:, None, None] * cam[3]) - cam[0]
+    rays = np.zeros(width * height, RAY_DTYPE)
+    rays["origin"] = cam[0]
+    rays["direction"] = d.astype(f).reshape(-1, 3)
+    return rays
+
+
 # every symbol include/rt_amd.h / include/rt_host.h declares
 AMD_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_create", "rt_destroy", "rt_set_photons", "rt_emit_photons",
                "rt_render", "rt_render_passes", "rt_render_device", "rt_resolve_device", "rt_trace", "rt_knn", "rt_knn_wide", "rt_bvh_info_get",
@@ -350,7 +373,8 @@ AMD_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_create", "rt_destroy", "rt
                "rt_render_views_device", "rt_render_motion", "rt_render_motion_device", "rt_temporal_accumulate",
                "rt_temporal_accumulate_device", "rt_svgf", "rt_svgf_device", "rt_bvh_quality_get", "rt_rebuild",
                "rt_render_aov_views", "rt_render_aov_views_device", "rt_render_motion_views", "rt_render_motion_views_device",
-               "rt_denoise_batch", "rt_denoise_batch_device", "rt_render_ao", "rt_render_ao_device"]
+               "rt_denoise_batch", "rt_denoise_batch_device", "rt_render_ao", "rt_render_ao_device", "rt_render_rays",
+               "rt_render_rays_device"]
 HOST_SYMBOLS = ["rt_host_scene_build", "rt_host_scene_desc", "rt_host_scene_free", "rt_host_last_error",
                 "rt_host_fill_background", "rt_host_save_ppm", "rt_host_kd_order", "rt_host_light_basis"]
 
@@ -433,6 +457,10 @@ def amd():
         L.rt_render_aov_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Aov), C.c_void_p]
         L.rt_render_ao.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(AoParams), C.POINTER(Ao)]
         L.rt_render_ao_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(AoParams), C.POINTER(Ao), C.c_void_p]
+        L.rt_render_rays.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(RayBatch), C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.POINTER(Stats)]
+        L.rt_render_rays_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(RayBatch), C.c_void_p, C.c_void_p,
+                                            C.POINTER(Stats)]
         L.rt_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.POINTER(Aov), C.c_void_p]
         L.rt_render_adaptive.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(AdaptiveParams), C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.POINTER(AdaptiveReport), C.POINTER(Stats)]
@@ -866,6 +894,34 @@ class Context:
             setattr(o, k, v or None)
         _check(amd().rt_render_ao_device(self._h, C.byref(params), C.byref(self._ao_params(n_rays, bias, max_distance)), C.byref(o),
                                          C.c_void_p(stream or None)))
+
+    def render_rays(self, params, rays, bg=None, stream_index=None, want_accum=True):
+        """rt_render_rays: the integrator along `rays` (RAY_DTYPE [n], directions of any length) in place of a camera's
+        pixel grid; params.width / height are ignored.  stream_index [n] uint32: the pixel index each ray's RNG stream is
+        keyed by (None: the ray's own index).  Returns (out [n][3] or None without bg [n][3], accum [n][4] or None, stats)."""
+        rays = np.ascontiguousarray(rays, RAY_DTYPE).reshape(-1)
+        n = len(rays)
+        idx = None if stream_index is None else np.ascontiguousarray(stream_index, np.uint32).reshape(-1)
+        assert idx is None or len(idx) == n
+        b = RayBatch()
+        b.n, b.rays, b.stream_index = n, rays.ctypes.data, None if idx is None else idx.ctypes.data
+        out = np.empty((n, 3), np.float32) if bg is not None else None
+        acc = np.empty((n, 4), np.float32) if want_accum else None
+        bgc = None if bg is None else np.ascontiguousarray(bg, np.float32)
+        assert bgc is None or bgc.size == 3 * n
+        st = Stats()
+        _check(amd().rt_render_rays(self._h, C.byref(params), C.byref(b), _ptr(bgc), _ptr(out), _ptr(acc), C.byref(st)))
+        return out, acc, st
+
+    def render_rays_device(self, params, d_rays, n, d_accum, d_stream_index=None, stream=0, stats=False):
+        """rt_render_rays_device: accumulate the rays at device pointer d_rays ([n] rt_ray) into the caller-zeroed device
+        d_accum [n][4] on `stream`; sample ranges chain.  Resolve with resolve_device(n, 1, spp, ...)."""
+        b = RayBatch()
+        b.n, b.rays, b.stream_index = n, d_rays, d_stream_index or None
+        st = Stats() if stats else None
+        _check(amd().rt_render_rays_device(self._h, C.byref(params), C.byref(b), C.c_void_p(d_accum), C.c_void_p(stream or None),
+                                           C.byref(st) if stats else None))
+        return st
 
     @staticmethod
     def _motion_prev(prev_pos, prev_camera):
