@@ -39,11 +39,33 @@
  *
  * Conventions: plain C, int status (0 = RT_OK), caller-owned buffers, no C++
  * types or exceptions across the boundary, one host thread per context and ONE LAUNCH IN
- * FLIGHT per context: a context owns one work-queue head, one counter block and one
- * wavefront state block, so rt_render_device / rt_trace_stream_device calls on the same
+ * FLIGHT per context: a context owns one work-queue head, one counter block, one
+ * wavefront state block and the scratch of its filters and passes, so the calls on one
  * context must be ordered on one stream (or synchronised) — use one context per stream.  There
  * is NO CPU fallback: every compute entry point fails with RT_ERR_NO_DEVICE if
  * no gfx950 device is usable.
+ *
+ * Stream order of the `_device` forms (tests/test_gpu_stream_order.py issues every one of them on a
+ * non-blocking stream that is still busy, back to back):
+ *   ASYNCHRONOUS — everything the call does is queued on `stream`, device inputs are read and outputs
+ *   written in stream order, and the call returns without waiting for the stream:
+ *     rt_render_device, rt_render_views_device and rt_render_rays_device with stats == NULL; rt_resolve_device;
+ *     rt_render_aov_device, rt_render_ao_device, rt_render_motion_device; rt_temporal_accumulate_device,
+ *     rt_svgf_device, rt_denoise_device, rt_denoise_batch_device; rt_render_aov_views_device,
+ *     rt_render_motion_views_device; rt_pack_owned_device, rt_unpack_owned_device; rt_trace_stream_device.
+ *     Host arguments (params, cameras, seeds, previous cameras) are copied before the call returns.
+ *     Two exceptions, neither of which changes a result: a call that needs MORE scratch than the context holds
+ *     (another frame size, rank or sample-per-wave choice for the tile list; more views; a larger frame for the
+ *     filters; a larger wavefront batch) frees the old block, and hipFree waits for the device; and the fifth
+ *     multi-view call in a row waits for the upload of the first (four pinned staging copies).
+ *   SYNCHRONISE `stream`, and only it, before they return, because the host reads a result back:
+ *     rt_render_device, rt_render_views_device, rt_render_rays_device with stats != NULL;
+ *     rt_render_adaptive_device (every pass); rt_update_vertices_device and rt_update_transforms (twice);
+ *     the three multi-view forms when a view lies far enough out to need a wider box padding (a refit).
+ *   HOST forms (rt_render, rt_render_aov, rt_denoise, rt_update, rt_trace, rt_knn, rt_bvh_quality_get, rt_rebuild,
+ *     the photon calls ...) run on the NULL stream and return when their result is in host memory.  The null
+ *     stream does not wait for a non-blocking stream: a host form must not follow an unfinished asynchronous call on
+ *     such a stream without a synchronisation of that stream.
  */
 #ifndef RT_AMD_H
 #define RT_AMD_H

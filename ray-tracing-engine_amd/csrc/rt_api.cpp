@@ -115,6 +115,49 @@ int upload(DevBuf<T>* out, const void* src, size_t count) {
   return RT_OK;
 }
 
+template <class T>
+hipError_t pinned_alloc(PinnedBuf<T>* out, size_t count) {
+  void* h = nullptr;
+  const hipError_t e = hipHostMalloc(&h, count * sizeof(T));
+  out->reset(e == hipSuccess ? static_cast<T*>(h) : nullptr);
+  return e;
+}
+
+// A list of words that the host makes and kernels read (wave tiles, granules), sent on the CALLER's stream through a pinned
+// copy that lives as long as the device copy.  upload() would not do on the asynchronous paths: its blocking copy runs on
+// the null stream, and the runtime multiplexes streams onto a few hardware queues — when the null stream and the caller's
+// share one, the copy waits for everything the caller has queued (DESIGN.md "Stream order").  `ready` is recorded behind
+// the copy: a launch that reads the list on another stream waits for it on the device (use_on).
+struct StreamList {
+  DevBuf<uint32_t> d;
+  PinnedBuf<uint32_t> h;
+  Event ready;
+  hipStream_t on = nullptr;
+  uint32_t n = 0;
+};
+// (releases what L held: hipFree waits for the launches that may still read it)
+int stream_upload(StreamList* L, const std::vector<uint32_t>& v, hipStream_t stream) {
+  L->n = 0;
+  if (L->d) {
+    HIP_TRY(hipEventSynchronize(L->ready.get()));  // the copy has read the pinned words
+    HIP_TRY(hipFree(L->d.release()));
+  }
+  L->h.reset();
+  if (v.empty()) return RT_OK;
+  HIP_TRY(dev_alloc(&L->d, v.size()));
+  HIP_TRY(pinned_alloc(&L->h, v.size()));
+  memcpy(L->h.get(), v.data(), v.size() * sizeof(uint32_t));
+  if (!L->ready) HIP_TRY(make_event(&L->ready, hipEventDisableTiming));
+  HIP_TRY(hipMemcpyAsync(L->d.get(), L->h.get(), v.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipEventRecord(L->ready.get(), stream));
+  L->on = stream, L->n = static_cast<uint32_t>(v.size());
+  return RT_OK;
+}
+int use_on(const StreamList& L, hipStream_t stream) {
+  if (L.d && stream != L.on) HIP_TRY(hipStreamWaitEvent(stream, L.ready.get(), 0));
+  return RT_OK;
+}
+
 struct TileKey {
   uint32_t w = 0, h = 0, rank = 0, world = 0, tile = 0, sshift = 0;
   bool operator==(const TileKey& o) const {
@@ -152,16 +195,12 @@ struct rt_ctx {
   // the photon map (install_photons / drop_photons)
   DevBuf<float4> phPos, phDir;
   DevBuf<uint4> phTopo;  // explicit kd topology over phPos (rtk::launch_kd_topology)
-  DevBuf<uint32_t> dTiles;
-  uint32_t nTiles = 0;
+  StreamList tiles;  // the frame's wave tiles, for tileKey
   TileKey tileKey;
   DevBuf<unsigned long long> dCounters;
   DevBuf<uint32_t> dTileCounter;  // work queue head of the persistent render kernel
   // owned-granule lists of the ranks of a tile-sharded frame (multi-GPU assembly), by key
-  struct GranList {
-    DevBuf<uint32_t> d;
-    uint32_t n = 0;
-  };
+  using GranList = StreamList;
   std::map<std::string, GranList> granules;
   // path state + ray queues of the wavefront integrator (allocated on first use)
   rtk::WfArgs wf{};
@@ -212,21 +251,30 @@ struct rt_ctx {
   // scratch of rt_render_adaptive_device (moments, granule state and lists, tile list, counts; grows on demand)
   DevBuf<char> adScratch;
   size_t adCap = 0;
-  // scratch of rt_render_views_device: the view-major wave tiles and their views (for vwKey and vwViews views), the view
-  // records and their pinned staging copy (vwStaged: recorded after the upload that last read it)
-  DevBuf<uint32_t> vwTiles, vwTileView;
+  // scratch of rt_render_views_device: the view-major wave tiles and their views (for vwKey and vwViews views) and the view
+  // records
+  StreamList vwTiles, vwTileView;
   uint32_t vwNTiles = 0, vwViews = 0;
   TileKey vwKey;
   DevBuf<rtk::ViewRec> vwRecs;
-  PinnedBuf<rtk::ViewRec> vwHost;
   uint32_t vwCap = 0;
-  Event vwStaged;
-  bool vwStagedSet = false;
-  // rt_render_motion_views_device: last frame's camera of every view, a table beside vwRecs (ViewRec stays 64 bytes) with
-  // its own pinned copy; uploaded ahead of the view records on the same stream, so vwStaged covers both
+  // rt_render_motion_views_device: last frame's camera of every view, a table beside vwRecs (ViewRec stays 64 bytes),
+  // uploaded ahead of the view records on the same stream
   DevBuf<rt_camera> vwPrevCams;
-  PinnedBuf<rt_camera> vwPrevHost;
   uint32_t vwPrevCap = 0;
+  // The pinned copies those uploads read, a ring of kViewStages: a call takes the next slot and waits only for the uploads
+  // of the call kViewStages back (`read`: recorded behind the uploads that last read the slot), so back-to-back calls on
+  // a busy stream do not wait for one another (DESIGN.md "Stream order")
+  struct ViewStage {
+    PinnedBuf<rtk::ViewRec> recs;
+    PinnedBuf<rt_camera> prevCams;
+    uint32_t cap = 0, prevCap = 0;
+    Event read;
+    bool readSet = false;
+  };
+  static constexpr uint32_t kViewStages = 4;
+  ViewStage vwStage[kViewStages];
+  uint32_t vwStageNext = 0;
   // rt_render_ao_device with the default bias (allocated on first use): the box of the referenced vertices, reduced on the
   // call's stream and read by the kernel behind it
   DevBuf<uint32_t> aoExt;
@@ -336,19 +384,16 @@ std::vector<uint32_t> wave_tiles(const TileKey& k) {
   return tiles;
 }
 
-int ensure_tiles(rt_ctx* c, const rt_params* p, uint32_t sshift) {
+int ensure_tiles(rt_ctx* c, const rt_params* p, uint32_t sshift, hipStream_t stream) {
   const TileKey k = tile_key(p, sshift);
-  if (c->dTiles && k == c->tileKey) return RT_OK;
-  const std::vector<uint32_t> tiles = wave_tiles(k);
-  if (c->dTiles) HIP_TRY(hipFree(c->dTiles.release()));
-  int rc = upload(&c->dTiles, tiles.data(), tiles.size());
+  if (c->tiles.d && k == c->tileKey) return use_on(c->tiles, stream);
+  const int rc = stream_upload(&c->tiles, wave_tiles(k), stream);
   if (rc != RT_OK) return rc;
-  c->nTiles = static_cast<uint32_t>(tiles.size());
   c->tileKey = k;
   return RT_OK;
 }
 
-int ensure_granules(rt_ctx* c, const rt_params* p, uint32_t rank, const rt_ctx::GranList** out) {
+int ensure_granules(rt_ctx* c, const rt_params* p, uint32_t rank, hipStream_t stream, const rt_ctx::GranList** out) {
   char key[96];
   snprintf(key, sizeof key, "%u.%u.%u.%u.%u", p->width, p->height, rank, p->world ? p->world : 1, p->tile ? p->tile : 8);
   auto it = c->granules.find(key);
@@ -356,10 +401,12 @@ int ensure_granules(rt_ctx* c, const rt_params* p, uint32_t rank, const rt_ctx::
     std::vector<uint32_t> g;
     owned_granules(p->width, p->height, rank, p->world, p->tile, [&](uint32_t x8, uint32_t y8) { g.push_back(x8 | (y8 << 16)); });
     rt_ctx::GranList L;
-    int rc = upload(&L.d, g.data(), g.size());
+    int rc = stream_upload(&L, g, stream);
     if (rc != RT_OK) return rc;
-    L.n = static_cast<uint32_t>(g.size());
     it = c->granules.emplace(key, std::move(L)).first;
+  } else {
+    const int rc = use_on(it->second, stream);
+    if (rc != RT_OK) return rc;
   }
   *out = &it->second;
   return RT_OK;
@@ -446,7 +493,7 @@ uint32_t stack_levels(uint32_t levels) {
 int wavefront_args(rt_ctx* c, const rt_params* p, const rtk::RenderArgs& A, uint32_t sppCount, hipStream_t stream,
                    rtk::WfArgs* out) {
   const rt_ctx::GranList* G = nullptr;
-  int rc = ensure_granules(c, p, p->rank, &G);
+  int rc = ensure_granules(c, p, p->rank, stream, &G);
   if (rc != RT_OK) return rc;
   const size_t perSample = (size_t)G->n * 64u;
   if (perSample == 0) return RT_OK;
@@ -497,12 +544,12 @@ int launch_frame(rt_ctx* c, const rt_params* p, float4* dAccum, hipStream_t stre
                  const TileList* own = nullptr) {
   const uint32_t sppCount = p->spp_count ? p->spp_count : p->spp;
   const uint32_t sshift = own ? own->sshift : choose_sshift(c, p, sppCount);
-  int rc = own ? RT_OK : ensure_tiles(c, p, sshift);
+  int rc = own ? RT_OK : ensure_tiles(c, p, sshift, stream);
   if (rc != RT_OK) return rc;
   rtk::RenderArgs A;
   A.sshift = sshift;
   wave_tile_shape(sshift, A.tileW, A.tileH);
-  A.tiles = own ? own->tiles : c->dTiles.get(), A.n_tiles = own ? own->n : c->nTiles;
+  A.tiles = own ? own->tiles : c->tiles.d.get(), A.n_tiles = own ? own->n : c->tiles.n;
   A.tileView = own ? own->tileView : nullptr, A.views = own ? own->views : nullptr;
   A.width = p->width, A.height = p->height, A.spp = p->spp;
   A.s0 = p->spp_count ? p->spp_begin : 0;
@@ -1645,7 +1692,7 @@ int rt_pack_owned_device(rt_ctx* c, const rt_params* p, const void* d_accum, voi
   if (p->tile % 8 != 0 || (p->world > 1 && p->rank >= p->world)) return fail(RT_ERR_INVALID, "bad rank/world/tile");
   HIP_TRY(hipSetDevice(c->device));
   const rt_ctx::GranList* L = nullptr;
-  int rc = ensure_granules(c, p, p->rank, &L);
+  int rc = ensure_granules(c, p, p->rank, static_cast<hipStream_t>(stream), &L);
   if (rc != RT_OK) return rc;
   hipError_t he = rtk::launch_pack(false, static_cast<const float4*>(d_accum), static_cast<float4*>(d_packed), L->d.get(), L->n, p->width,
                                    p->height, static_cast<hipStream_t>(stream));
@@ -1658,7 +1705,7 @@ int rt_unpack_owned_device(rt_ctx* c, const rt_params* p, uint32_t from_rank, co
   if (p->tile % 8 != 0 || from_rank >= (p->world ? p->world : 1)) return fail(RT_ERR_INVALID, "bad rank/world/tile");
   HIP_TRY(hipSetDevice(c->device));
   const rt_ctx::GranList* L = nullptr;
-  int rc = ensure_granules(c, p, from_rank, &L);
+  int rc = ensure_granules(c, p, from_rank, static_cast<hipStream_t>(stream), &L);
   if (rc != RT_OK) return rc;
   hipError_t he = rtk::launch_pack(true, static_cast<const float4*>(d_packed), static_cast<float4*>(d_accum), L->d.get(), L->n, p->width,
                                    p->height, static_cast<hipStream_t>(stream));
@@ -2946,10 +2993,13 @@ int views_checks(rt_ctx* c, const rt_params* p, const rt_views* v, rtbvh::Paddin
 
 // The view-major wave tiles of n views (each view's as a single-view frame has them) and each tile's view, cached on the
 // context by (frame, sshift, n)
-int ensure_view_tiles(rt_ctx* c, const rt_params* p, uint32_t sshift, uint32_t n) {
+int ensure_view_tiles(rt_ctx* c, const rt_params* p, uint32_t sshift, uint32_t n, hipStream_t stream) {
   const TileKey k = tile_key(p, sshift);
-  if (c->vwTiles && k == c->vwKey && n == c->vwViews) return RT_OK;
-  c->vwTiles.reset(), c->vwTileView.reset(), c->vwNTiles = 0, c->vwViews = 0;
+  if (c->vwTiles.d && k == c->vwKey && n == c->vwViews) {
+    const int rc = use_on(c->vwTiles, stream);
+    return rc != RT_OK ? rc : use_on(c->vwTileView, stream);
+  }
+  c->vwNTiles = 0, c->vwViews = 0;
   const std::vector<uint32_t> one = wave_tiles(k);
   std::vector<uint32_t> tiles, view;
   tiles.reserve(one.size() * n), view.reserve(one.size() * n);
@@ -2957,29 +3007,50 @@ int ensure_view_tiles(rt_ctx* c, const rt_params* p, uint32_t sshift, uint32_t n
     tiles.insert(tiles.end(), one.begin(), one.end());
     view.insert(view.end(), one.size(), j);
   }
-  int rc = upload(&c->vwTiles, tiles.data(), tiles.size());
-  if (rc == RT_OK) rc = upload(&c->vwTileView, view.data(), view.size());
+  int rc = stream_upload(&c->vwTiles, tiles, stream);
+  if (rc == RT_OK) rc = stream_upload(&c->vwTileView, view, stream);
   if (rc != RT_OK) return rc;
   c->vwNTiles = static_cast<uint32_t>(tiles.size()), c->vwViews = n, c->vwKey = k;
   return RT_OK;
 }
 
-// The view records to the device on `stream`, through a pinned copy that the previous call's upload has finished reading
-int upload_views(rt_ctx* c, const rt_params* p, const rt_views* v, hipStream_t stream) {
+// The view records — and, for the motion pass, last frame's camera of every view (prevCams, else null), ahead of them —
+// to the device on `stream`, through the next slot of the ring of pinned copies: the host waits only until the uploads that
+// last read that slot, kViewStages calls ago, have finished.  The device tables are written and read in stream order;
+// where they grow, the old ones are freed under launches that may still read them, which hipFree waits for.
+int upload_views(rt_ctx* c, const rt_params* p, const rt_views* v, const rt_camera* prevCams, hipStream_t stream) {
   const uint32_t n = v->n_views;
+  rt_ctx::ViewStage& g = c->vwStage[c->vwStageNext++ % rt_ctx::kViewStages];
+  if (!g.read) HIP_TRY(make_event(&g.read, hipEventDisableTiming));
+  if (g.readSet) HIP_TRY(hipEventSynchronize(g.read.get()));
+  g.readSet = false;
+  if (n > g.cap) {
+    g.cap = 0;
+    HIP_TRY(pinned_alloc(&g.recs, n));
+    g.cap = n;
+  }
+  if (prevCams && n > g.prevCap) {
+    g.prevCap = 0;
+    HIP_TRY(pinned_alloc(&g.prevCams, n));
+    g.prevCap = n;
+  }
   if (n > c->vwCap) {
-    if (c->vwStagedSet) HIP_TRY(hipEventSynchronize(c->vwStaged.get()));
-    c->vwCap = 0, c->vwStagedSet = false;
-    c->vwRecs.reset(), c->vwHost.reset();
+    c->vwCap = 0;
+    if (c->vwRecs) HIP_TRY(hipFree(c->vwRecs.release()));
     HIP_TRY(dev_alloc(&c->vwRecs, n));
-    void* h = nullptr;
-    HIP_TRY(hipHostMalloc(&h, n * sizeof(rtk::ViewRec)));
-    c->vwHost.reset(static_cast<rtk::ViewRec*>(h));
     c->vwCap = n;
   }
-  if (!c->vwStaged) HIP_TRY(make_event(&c->vwStaged, hipEventDisableTiming));
-  if (c->vwStagedSet) HIP_TRY(hipEventSynchronize(c->vwStaged.get()));
-  rtk::ViewRec* h = c->vwHost.get();
+  if (prevCams && n > c->vwPrevCap) {
+    c->vwPrevCap = 0;
+    if (c->vwPrevCams) HIP_TRY(hipFree(c->vwPrevCams.release()));
+    HIP_TRY(dev_alloc(&c->vwPrevCams, n));
+    c->vwPrevCap = n;
+  }
+  if (prevCams) {
+    memcpy(g.prevCams.get(), prevCams, n * sizeof(rt_camera));
+    HIP_TRY(hipMemcpyAsync(c->vwPrevCams.get(), g.prevCams.get(), n * sizeof(rt_camera), hipMemcpyHostToDevice, stream));
+  }
+  rtk::ViewRec* h = g.recs.get();
   const uint32_t px = p->width * p->height;
   for (uint32_t j = 0; j < n; ++j) {
     h[j] = rtk::ViewRec{};
@@ -2988,8 +3059,8 @@ int upload_views(rt_ctx* c, const rt_params* p, const rt_views* v, hipStream_t s
     h[j].accumOff = j * px;
   }
   HIP_TRY(hipMemcpyAsync(c->vwRecs.get(), h, n * sizeof(rtk::ViewRec), hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipEventRecord(c->vwStaged.get(), stream));
-  c->vwStagedSet = true;
+  HIP_TRY(hipEventRecord(g.read.get(), stream));
+  g.readSet = true;
   return RT_OK;
 }
 
@@ -3014,11 +3085,11 @@ int rt_render_views_device(rt_ctx* c, const rt_params* p, const rt_views* v, voi
   const uint32_t n = v->n_views;
   const uint32_t sppCount = p->spp_count ? p->spp_count : p->spp;
   const uint32_t sshift = choose_sshift_px(c, p, (uint64_t)n * p->width * p->height, sppCount);
-  if ((rc = ensure_view_tiles(c, p, sshift, n)) != RT_OK) return rc;
-  if ((rc = upload_views(c, p, v, s)) != RT_OK) return rc;
+  if ((rc = ensure_view_tiles(c, p, sshift, n, s)) != RT_OK) return rc;
+  if ((rc = upload_views(c, p, v, nullptr, s)) != RT_OK) return rc;
   if (stats) HIP_TRY(hipMemsetAsync(c->dCounters.get(), 0, RTK_CNT_COUNT * sizeof(unsigned long long), s));
-  TileList own = {c->vwTiles.get(), c->vwNTiles, sshift};
-  own.tileView = c->vwTileView.get(), own.views = c->vwRecs.get();
+  TileList own = {c->vwTiles.d.get(), c->vwNTiles, sshift};
+  own.tileView = c->vwTileView.d.get(), own.views = c->vwRecs.get();
   int e = 0;
   if ((rc = launch_frame(c, p, static_cast<float4*>(d_accum), s, &e, &own)) != RT_OK) return rc;
   if (stats) {
@@ -3312,22 +3383,7 @@ int stage_views(rt_ctx* c, const rt_params* q, const rt_views* v, const rt_motio
     x.padding = &pad;
     if ((rc = update_ctx(c, x, s, std::chrono::steady_clock::now(), nullptr)) != RT_OK) return rc;
   }
-  if (prev) {
-    const uint32_t n = v->n_views;
-    if (c->vwStagedSet) HIP_TRY(hipEventSynchronize(c->vwStaged.get()));  // the previous call's upload has read the pinned copy
-    if (n > c->vwPrevCap) {
-      c->vwPrevCap = 0;
-      c->vwPrevCams.reset(), c->vwPrevHost.reset();
-      HIP_TRY(dev_alloc(&c->vwPrevCams, n));
-      void* h = nullptr;
-      HIP_TRY(hipHostMalloc(&h, n * sizeof(rt_camera)));
-      c->vwPrevHost.reset(static_cast<rt_camera*>(h));
-      c->vwPrevCap = n;
-    }
-    memcpy(c->vwPrevHost.get(), prev->cameras ? prev->cameras : v->cameras, n * sizeof(rt_camera));
-    HIP_TRY(hipMemcpyAsync(c->vwPrevCams.get(), c->vwPrevHost.get(), n * sizeof(rt_camera), hipMemcpyHostToDevice, s));
-  }
-  return upload_views(c, q, v, s);  // (records vwStaged behind both copies)
+  return upload_views(c, q, v, prev ? (prev->cameras ? prev->cameras : v->cameras) : nullptr, s);
 }
 
 // Everything rt_denoise_batch checks, the context last (it exists only where a device does).
