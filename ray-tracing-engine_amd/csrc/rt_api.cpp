@@ -123,6 +123,79 @@ hipError_t pinned_alloc(PinnedBuf<T>* out, size_t count) {
   return e;
 }
 
+// Scratch that grows on demand: *buf gets room for `need` elements when *cap is less (*grew says whether it did).  *cap is
+// 0 while there is no valid buffer; a device buffer is freed first and a failing hipFree reported, a pinned one goes once
+// its successor is there.
+template <class T>
+int renew(DevBuf<T>* buf, size_t count) {
+  if (*buf) HIP_TRY(hipFree(buf->release()));
+  HIP_TRY(dev_alloc(buf, count));
+  return RT_OK;
+}
+template <class T>
+int renew(PinnedBuf<T>* buf, size_t count) {
+  HIP_TRY(pinned_alloc(buf, count));
+  return RT_OK;
+}
+template <class Owner, class Cap>
+int grow(Owner* buf, Cap* cap, size_t need, bool* grew = nullptr) {
+  const bool g = need > *cap;
+  if (grew) *grew = g;
+  if (!g) return RT_OK;
+  *cap = 0;
+  const int rc = renew(buf, need);
+  if (rc != RT_OK) return rc;
+  *cap = static_cast<Cap>(need);
+  return RT_OK;
+}
+
+// Device copies of a host form's buffers, freed with the scope.  in() uploads an input; out() makes room for an output
+// the caller asked for (null otherwise); work() makes room the device form needs either way and zeroed() fills it with
+// zeros (an integrator's accumulator); inout() uploads what the device form updates in place.  download() copies back
+// every one of these whose host pointer was given, in() apart.  After a failure they all answer null and rc holds what the
+// entry point returns; it is looked at once, after the last of them.
+struct Staging {
+  struct Out {
+    void* host;
+    const void* dev;
+    size_t bytes;
+  };
+  std::vector<DevBuf<char>> bufs;
+  std::vector<Out> outs;
+  int rc = RT_OK;
+
+  int stage(void** d, const void* src, void* dst, size_t bytes, bool zero) {
+    DevBuf<char> b;
+    HIP_TRY(dev_alloc(&b, bytes));
+    if (src) HIP_TRY(hipMemcpy(b.get(), src, bytes, hipMemcpyHostToDevice));
+    if (zero) HIP_TRY(hipMemset(b.get(), 0, bytes));
+    *d = b.get();
+    bufs.push_back(std::move(b));
+    if (dst) outs.push_back({dst, *d, bytes});
+    return RT_OK;
+  }
+  template <class T>
+  T* staged(const void* src, void* dst, size_t count, bool zero = false) {
+    void* d = nullptr;
+    if (rc == RT_OK) rc = stage(&d, src, dst, count * sizeof(T), zero);
+    return static_cast<T*>(d);
+  }
+  template <class T>
+  T* in(const T* host, size_t count) { return staged<T>(host, nullptr, count); }
+  template <class T>
+  T* out(T* host, size_t count) { return host ? staged<T>(nullptr, host, count) : nullptr; }
+  template <class T>
+  T* work(void* host, size_t count) { return staged<T>(nullptr, host, count); }
+  template <class T>
+  T* zeroed(void* host, size_t count) { return staged<T>(nullptr, host, count, true); }
+  template <class T>
+  T* inout(void* host, size_t count) { return staged<T>(host, host, count); }
+  int download() {
+    for (const Out& o : outs) HIP_TRY(hipMemcpy(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost));
+    return RT_OK;
+  }
+};
+
 // A list of words that the host makes and kernels read (wave tiles, granules), sent on the CALLER's stream through a pinned
 // copy that lives as long as the device copy.  upload() would not do on the asynchronous paths: its blocking copy runs on
 // the null stream, and the runtime multiplexes streams onto a few hardware queues — when the null stream and the caller's
@@ -204,7 +277,7 @@ struct rt_ctx {
   std::map<std::string, GranList> granules;
   // path state + ray queues of the wavefront integrator (allocated on first use)
   rtk::WfArgs wf{};
-  size_t wfCap = 0;
+  size_t wfCap = 0;  // bytes of wfBlock
   DevBuf<char> wfBlock;
   uint32_t builder = RT_BVH_HOST;
   bool broken = false;  // the device tree is in an unknown state (rt_bvh_tune could not restore it, rt_update failed partway): launches are refused
@@ -445,7 +518,18 @@ int check_params(const rt_ctx* c, const rt_params* p) {
   return RT_OK;
 }
 
+// The samples of a pixel a call integrates: [s0, s1), all spp of them unless p gives a range
+struct SampleRange {
+  uint32_t s0, s1, count;
+};
+SampleRange sample_range(const rt_params& p) {
+  if (p.spp_count) return {p.spp_begin, p.spp_begin + p.spp_count, p.spp_count};
+  return {0u, p.spp, p.spp};
+}
+
+// *st zeroed but for the device counters
 int read_counters(rt_ctx* c, rt_stats* st) {
+  memset(st, 0, sizeof *st);
   unsigned long long h[RTK_CNT_COUNT];
   HIP_TRY(hipMemcpy(h, c->dCounters.get(), sizeof h, hipMemcpyDeviceToHost));
   st->rays_closest = h[RTK_CNT_CLOSEST];
@@ -465,6 +549,34 @@ int read_counters(rt_ctx* c, rt_stats* st) {
     for (int i = 16; i < RTK_CNT_COUNT; ++i) fprintf(stderr, "%llu%s", h[i], i + 1 < RTK_CNT_COUNT ? ", " : "]}\n");
   }
 #endif
+  return RT_OK;
+}
+
+// The ring of event pairs that time the integrators' launches (rt_profile_collect reads pairs 0 .. evUsed - 1): the next
+// pair is recorded on `stream` around what `launch` queues there; *evIndex gets its index.
+template <class Launch>
+int timed_launch(rt_ctx* c, hipStream_t stream, int* evIndex, Launch launch) {
+  const int e = c->evUsed % kEventPairs;
+  HIP_TRY(hipEventRecord(c->ev[e][0].get(), stream));
+  const int rc = launch();
+  if (rc != RT_OK) return rc;
+  HIP_TRY(hipEventRecord(c->ev[e][1].get(), stream));
+  c->evUsed++;
+  if (evIndex) *evIndex = e;
+  return RT_OK;
+}
+hipError_t event_pair_ms(const rt_ctx* c, int e, float* ms) {
+  return hipEventElapsedTime(ms, c->ev[e][0].get(), c->ev[e][1].get());
+}
+// *stats of the launch that event pair e brackets, once `stream` has run it: the counters, the kernel time and the
+// caller's count of samples
+int frame_stats(rt_ctx* c, hipStream_t stream, int e, uint64_t samples, rt_stats* stats) {
+  HIP_TRY(hipStreamSynchronize(stream));
+  const int rc = read_counters(c, stats);
+  if (rc != RT_OK) return rc;
+  float ms = 0.f;
+  HIP_TRY(event_pair_ms(c, e, &ms));
+  stats->kernel_ms = ms, stats->samples = samples;
   return RT_OK;
 }
 
@@ -500,12 +612,10 @@ int wavefront_args(rt_ctx* c, const rt_params* p, const rtk::RenderArgs& A, uint
   size_t batch = (4u << 20) / perSample;  // ~4 M paths per batch (1.1 GB of state + queues)
   batch = batch < 1 ? 1 : batch > sppCount ? sppCount : batch;
   const size_t P = batch * perSample;
-  if (P > c->wfCap) {
-    c->wfCap = 0;
-    if (c->wfBlock) HIP_TRY(hipFree(c->wfBlock.release()));
-    // rng 4, org 16, dir 16, key 8, nrm 16, pnt 16, col 48, rayO 64, rayD 64, res 32 = 284 B per path
-    const size_t bytes = P * 284 + 4096 + 2048 * sizeof(unsigned long long);
-    HIP_TRY(dev_alloc(&c->wfBlock, bytes));
+  // rng 4, org 16, dir 16, key 8, nrm 16, pnt 16, col 48, rayO 64, rayD 64, res 32 = 284 B per path
+  bool grew = false;
+  if ((rc = grow(&c->wfBlock, &c->wfCap, P * 284 + 4096 + 2048 * sizeof(unsigned long long), &grew)) != RT_OK) return rc;
+  if (grew) {  // carved again for P paths
     char* q = c->wfBlock.get();
     auto take = [&](size_t n) {
       char* r = q;
@@ -520,8 +630,11 @@ int wavefront_args(rt_ctx* c, const rt_params* p, const rtk::RenderArgs& A, uint
     W.res = reinterpret_cast<uint2*>(take(P * 32)), W.key = reinterpret_cast<uint2*>(take(P * 8));
     W.rng = reinterpret_cast<uint32_t*>(take(P * 4));
     W.stripes = reinterpret_cast<unsigned long long*>(take(2048 * sizeof(unsigned long long)));
-    HIP_TRY(hipMemsetAsync(W.stripes, 0, 2048 * sizeof(unsigned long long), stream));
-    c->wfCap = P;
+    const hipError_t he = hipMemsetAsync(W.stripes, 0, 2048 * sizeof(unsigned long long), stream);
+    if (he != hipSuccess) {
+      c->wfCap = 0;  // (the block is not usable before its stripes are zero)
+      return fail(RT_ERR_HIP, "wavefront stripes reset failed: %s", hipGetErrorString(he));
+    }
   }
   rtk::WfArgs W = c->wf;
   W.gran = G->d.get(), W.nGran = G->n, W.width = p->width, W.height = p->height, W.spp = p->spp, W.seed = p->seed;
@@ -542,8 +655,8 @@ struct TileList {
 // Launch the integrate kernel for p on `stream`, bracketed by an event pair.  own: render those wave tiles only.
 int launch_frame(rt_ctx* c, const rt_params* p, float4* dAccum, hipStream_t stream, int* evIndex,
                  const TileList* own = nullptr) {
-  const uint32_t sppCount = p->spp_count ? p->spp_count : p->spp;
-  const uint32_t sshift = own ? own->sshift : choose_sshift(c, p, sppCount);
+  const SampleRange sr = sample_range(*p);
+  const uint32_t sshift = own ? own->sshift : choose_sshift(c, p, sr.count);
   int rc = own ? RT_OK : ensure_tiles(c, p, sshift, stream);
   if (rc != RT_OK) return rc;
   rtk::RenderArgs A;
@@ -552,8 +665,7 @@ int launch_frame(rt_ctx* c, const rt_params* p, float4* dAccum, hipStream_t stre
   A.tiles = own ? own->tiles : c->tiles.d.get(), A.n_tiles = own ? own->n : c->tiles.n;
   A.tileView = own ? own->tileView : nullptr, A.views = own ? own->views : nullptr;
   A.width = p->width, A.height = p->height, A.spp = p->spp;
-  A.s0 = p->spp_count ? p->spp_begin : 0;
-  A.s1 = p->spp_count ? p->spp_begin + p->spp_count : p->spp;
+  A.s0 = sr.s0, A.s1 = sr.s1;
   A.mode = p->mode, A.max_depth = p->max_depth, A.seed = p->seed;
   A.k = p->k, A.photons_requested = p->photons_requested;
   static const bool noPool = getenv("RT_NO_POOL") != nullptr;
@@ -575,22 +687,19 @@ int launch_frame(rt_ctx* c, const rt_params* p, float4* dAccum, hipStream_t stre
   // at most 3 lights, like the pooled kernel; same frame bit for bit
   const bool wavefront = (p->reserved[2] & 1u) && !p->use_photons && p->accel != RT_ACCEL_BRUTE && c->S.n_lights <= 3u;
   rtk::WfArgs W{};
-  if (wavefront && (rc = wavefront_args(c, p, A, sppCount, stream, &W)) != RT_OK) return rc;
-  const int e = c->evUsed % kEventPairs;
-  HIP_TRY(hipEventRecord(c->ev[e][0].get(), stream));
-  if (!wavefront) {
-    hipError_t he = rtk::launch_render(p->accel == RT_ACCEL_BRUTE, p->use_photons != 0, p->collect_stats != 0, c->S, A,
-                                       dAccum, c->dCounters.get(), stream);
-    if (he != hipSuccess) return fail(RT_ERR_HIP, "render launch failed: %s", hipGetErrorString(he));
-  } else if (W.nGran) {
-    hipError_t hw = rtk::launch_wavefront(c->S, W, p->mode, p->max_depth, dAccum, c->dCounters.get(), c->dTileCounter.get(),
-                                          A.stackLevels, c->numCUs, stream);
-    if (hw != hipSuccess) return fail(RT_ERR_HIP, "wavefront launch failed: %s", hipGetErrorString(hw));
-  }
-  HIP_TRY(hipEventRecord(c->ev[e][1].get(), stream));
-  c->evUsed++;
-  if (evIndex) *evIndex = e;
-  return RT_OK;
+  if (wavefront && (rc = wavefront_args(c, p, A, sr.count, stream, &W)) != RT_OK) return rc;
+  return timed_launch(c, stream, evIndex, [&] {
+    if (!wavefront) {
+      hipError_t he = rtk::launch_render(p->accel == RT_ACCEL_BRUTE, p->use_photons != 0, p->collect_stats != 0, c->S, A,
+                                         dAccum, c->dCounters.get(), stream);
+      if (he != hipSuccess) return fail(RT_ERR_HIP, "render launch failed: %s", hipGetErrorString(he));
+    } else if (W.nGran) {
+      hipError_t hw = rtk::launch_wavefront(c->S, W, p->mode, p->max_depth, dAccum, c->dCounters.get(), c->dTileCounter.get(),
+                                            A.stackLevels, c->numCUs, stream);
+      if (hw != hipSuccess) return fail(RT_ERR_HIP, "wavefront launch failed: %s", hipGetErrorString(hw));
+    }
+    return (int)RT_OK;
+  });
 }
 
 }  // namespace
@@ -962,6 +1071,20 @@ int create_ctx(const rt_scene_desc* sc, const rt_options* opt, const rtbvh::Buil
   *out = c.release();
   return RT_OK;
 }
+
+// The image of a host form of an integrator, when the caller asked for one: bg goes up, the n slices of npx pixels of
+// dAccum are resolved at spp samples over it, each into its slice of the staged out_rgb.
+int stage_resolve(Staging* st, const float* bg, float* out_rgb, const float4* dAccum, uint32_t n, size_t npx, uint32_t spp) {
+  if (!out_rgb) return RT_OK;
+  const float* dBg = st->in(bg, 3 * npx);
+  float* dOut = st->out(out_rgb, 3 * n * npx);
+  if (st->rc != RT_OK) return st->rc;
+  for (uint32_t j = 0; j < n; ++j) {
+    const hipError_t he = rtk::launch_resolve((uint32_t)npx, spp, dAccum + j * npx, dBg, dOut + 3 * j * npx, nullptr);
+    if (he != hipSuccess) return fail(RT_ERR_HIP, "resolve launch failed: %s", hipGetErrorString(he));
+  }
+  return RT_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1037,22 +1160,13 @@ int rt_render_device(rt_ctx* c, const rt_params* p, void* d_accum, void* stream,
   int e = 0;
   rc = launch_frame(c, p, static_cast<float4*>(d_accum), s, &e);
   if (rc != RT_OK) return rc;
-  if (stats) {
-    memset(stats, 0, sizeof *stats);
-    HIP_TRY(hipStreamSynchronize(s));
-    rc = read_counters(c, stats);
-    if (rc != RT_OK) return rc;
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev[e][0].get(), c->ev[e][1].get()));
-    stats->kernel_ms = ms;
-    // samples of the pixels this rank owns: its granules, clipped to the image
-    uint64_t px = 0;
-    owned_granules(p->width, p->height, p->rank, p->world, p->tile, [&](uint32_t x8, uint32_t y8) {
-      px += (uint64_t)std::min(8u, p->width - x8 * 8) * std::min(8u, p->height - y8 * 8);
-    });
-    stats->samples = px * (p->spp_count ? p->spp_count : p->spp);
-  }
-  return RT_OK;
+  if (!stats) return RT_OK;
+  // samples of the pixels this rank owns: its granules, clipped to the image
+  uint64_t px = 0;
+  owned_granules(p->width, p->height, p->rank, p->world, p->tile, [&](uint32_t x8, uint32_t y8) {
+    px += (uint64_t)std::min(8u, p->width - x8 * 8) * std::min(8u, p->height - y8 * 8);
+  });
+  return frame_stats(c, s, e, px * sample_range(*p).count, stats);
 }
 
 int rt_resolve_device(rt_ctx* c, uint32_t width, uint32_t height, uint32_t spp, const void* d_accum,
@@ -1074,27 +1188,13 @@ int rt_render(rt_ctx* c, const rt_params* p, const float* bg, float* out_rgb, fl
   if (out_rgb && !bg) return fail(RT_ERR_INVALID, "out_rgb requested without a background image");
   HIP_TRY(hipSetDevice(c->device));
   const size_t npx = (size_t)p->width * p->height;
-  DevBuf<float4> dAccum;
-  DevBuf<float> dBg, dOut;
-  HIP_TRY(dev_alloc(&dAccum, npx));
-  hipError_t he = hipMemset(dAccum.get(), 0, npx * sizeof(float4));
-  if (he != hipSuccess) return fail(RT_ERR_HIP, "memset failed: %s", hipGetErrorString(he));
+  Staging st;
+  float4* dAccum = st.zeroed<float4>(accum_out, npx);
+  if (st.rc != RT_OK) return st.rc;
   rt_stats local;
-  rc = rt_render_device(c, p, dAccum.get(), nullptr, stats ? stats : &local);
-  if (rc != RT_OK) return rc;
-  if (out_rgb) {
-    if ((he = dev_alloc(&dBg, npx * 3)) == hipSuccess && (he = dev_alloc(&dOut, npx * 3)) == hipSuccess &&
-        (he = hipMemcpy(dBg.get(), bg, npx * 3 * sizeof(float), hipMemcpyHostToDevice)) == hipSuccess) {
-      rc = rt_resolve_device(c, p->width, p->height, p->spp, dAccum.get(), dBg.get(), dOut.get(), nullptr);
-      if (rc == RT_OK) he = hipMemcpy(out_rgb, dOut.get(), npx * 3 * sizeof(float), hipMemcpyDeviceToHost);
-    }
-    if (rc == RT_OK && he != hipSuccess) rc = fail(RT_ERR_HIP, "resolve failed: %s", hipGetErrorString(he));
-  }
-  if (rc == RT_OK && accum_out) {
-    he = hipMemcpy(accum_out, dAccum.get(), npx * sizeof(float4), hipMemcpyDeviceToHost);
-    if (he != hipSuccess) rc = fail(RT_ERR_HIP, "accumulator read-back failed: %s", hipGetErrorString(he));
-  }
-  return rc;
+  if ((rc = rt_render_device(c, p, dAccum, nullptr, stats ? stats : &local)) != RT_OK) return rc;
+  if ((rc = stage_resolve(&st, bg, out_rgb, dAccum, 1, npx, p->spp)) != RT_OK) return rc;
+  return st.download();
 }
 
 int rt_render_passes(rt_ctx* c, const rt_params* p, const float* bg, float* accum_io, float* out_rgb, rt_stats* stats) {
@@ -1103,38 +1203,29 @@ int rt_render_passes(rt_ctx* c, const rt_params* p, const float* bg, float* accu
   if (rc != RT_OK) return rc;
   HIP_TRY(hipSetDevice(c->device));
   const size_t npx = (size_t)p->width * p->height;
-  const uint32_t soFar = p->spp_count ? p->spp_begin + p->spp_count : p->spp;
-  DevBuf<float4> dAccum;
-  DevBuf<float> dBg, dOut;
-  hipError_t he = dev_alloc(&dAccum, npx);
-  if (he == hipSuccess) he = dev_alloc(&dBg, npx * 3);
-  if (he == hipSuccess) he = dev_alloc(&dOut, npx * 3);
-  if (he == hipSuccess) he = hipMemcpy(dAccum.get(), accum_io, npx * sizeof(float4), hipMemcpyHostToDevice);
-  if (he == hipSuccess) he = hipMemcpy(dBg.get(), bg, npx * 3 * sizeof(float), hipMemcpyHostToDevice);
+  Staging st;
+  float4* dAccum = st.inout<float4>(accum_io, npx);
+  if (st.rc != RT_OK) return st.rc;
   rt_stats local;
-  if (he == hipSuccess) rc = rt_render_device(c, p, dAccum.get(), nullptr, stats ? stats : &local);
-  if (he == hipSuccess && rc == RT_OK) rc = rt_resolve_device(c, p->width, p->height, soFar, dAccum.get(), dBg.get(), dOut.get(), nullptr);
-  if (he == hipSuccess && rc == RT_OK) he = hipMemcpy(accum_io, dAccum.get(), npx * sizeof(float4), hipMemcpyDeviceToHost);
-  if (he == hipSuccess && rc == RT_OK) he = hipMemcpy(out_rgb, dOut.get(), npx * 3 * sizeof(float), hipMemcpyDeviceToHost);
-  if (he != hipSuccess) return fail(RT_ERR_HIP, "progressive render failed: %s", hipGetErrorString(he));
-  return rc;
+  if ((rc = rt_render_device(c, p, dAccum, nullptr, stats ? stats : &local)) != RT_OK) return rc;
+  // (resolved over the samples the accumulator holds so far)
+  if ((rc = stage_resolve(&st, bg, out_rgb, dAccum, 1, npx, sample_range(*p).s1)) != RT_OK) return rc;
+  return st.download();
 }
 
 int rt_trace(rt_ctx* c, const rt_ray* rays, uint32_t n, uint32_t accel, uint32_t kind, rt_hit* hits) {
   if (!c || (n && (!rays || !hits))) return fail(RT_ERR_INVALID, "null argument");
   if (n == 0) return RT_OK;
   HIP_TRY(hipSetDevice(c->device));
-  DevBuf<rt_ray> dR;
-  DevBuf<rt_hit> dH;
-  int rc = upload(&dR, rays, n);
-  if (rc != RT_OK) return rc;
-  if (dev_alloc(&dH, n) != hipSuccess) return fail(RT_ERR_HIP, "hit buffer allocation failed");
+  Staging st;
+  const rt_ray* dR = st.in(rays, n);
+  rt_hit* dH = st.out(hits, n);
+  if (st.rc != RT_OK) return st.rc;
   rtk::DevScene Su = c->S;
   Su.slowRecip = 1u;  // the caller's rays: any length
-  hipError_t he = rtk::launch_trace(accel == RT_ACCEL_BRUTE, kind == RT_TRACE_ANY, Su, dR.get(), n, dH.get(), c->dCounters.get(), nullptr);
-  if (he == hipSuccess) he = hipMemcpy(hits, dH.get(), n * sizeof(rt_hit), hipMemcpyDeviceToHost);
+  const hipError_t he = rtk::launch_trace(accel == RT_ACCEL_BRUTE, kind == RT_TRACE_ANY, Su, dR, n, dH, c->dCounters.get(), nullptr);
   if (he != hipSuccess) return fail(RT_ERR_HIP, "trace failed: %s", hipGetErrorString(he));
-  return RT_OK;
+  return st.download();
 }
 
 // rt_knn (k in 1..RTK_KMAX) and rt_knn_wide (1..RT_KNN_KMAX) differ in the cap only: launch_knn_wide runs rt_knn's
@@ -1147,21 +1238,17 @@ static int knn_common(rt_ctx* c, const float* q3, uint32_t n, uint32_t k, uint32
   if (k > c->S.n_photons) return fail(RT_ERR_STATE, "k is greater than the number of nodes");  // kdtree.h:182-183
   if (n == 0) return RT_OK;
   HIP_TRY(hipSetDevice(c->device));
-  DevBuf<float> dQ, dD;
-  DevBuf<uint32_t> dI, dV;
-  int rc = upload(&dQ, q3, (size_t)n * 3);
-  if (rc != RT_OK) return rc;
-  hipError_t he = dev_alloc(&dI, (size_t)n * k);
-  if (he == hipSuccess) he = dev_alloc(&dD, (size_t)n * k);
-  if (he == hipSuccess) he = dev_alloc(&dV, n);
+  Staging st;
+  const float* dQ = st.in(q3, (size_t)n * 3);
+  uint32_t* dI = st.out(idx, (size_t)n * k);
+  float* dD = st.out(dist, (size_t)n * k);
+  uint32_t* dV = st.work<uint32_t>(visited, n);  // (the walk counts its visits either way)
+  if (st.rc != RT_OK) return st.rc;
   // the walk a photon frame runs, on the frame's layout when the BVH is shallower than the kd tree (the tightest one)
   const KdStack ks = kd_stack(c->S.n_photons);
-  if (he == hipSuccess) he = rtk::launch_knn_wide(c->S, dQ.get(), n, k, ks.kd16, stack_levels(ks.rows), dI.get(), dD.get(), dV.get(), nullptr);
-  if (he == hipSuccess) he = hipMemcpy(idx, dI.get(), (size_t)n * k * sizeof(uint32_t), hipMemcpyDeviceToHost);
-  if (he == hipSuccess) he = hipMemcpy(dist, dD.get(), (size_t)n * k * sizeof(float), hipMemcpyDeviceToHost);
-  if (he == hipSuccess && visited) he = hipMemcpy(visited, dV.get(), (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost);
+  const hipError_t he = rtk::launch_knn_wide(c->S, dQ, n, k, ks.kd16, stack_levels(ks.rows), dI, dD, dV, nullptr);
   if (he != hipSuccess) return fail(RT_ERR_HIP, "knn failed: %s", hipGetErrorString(he));
-  return RT_OK;
+  return st.download();
 }
 
 int rt_knn(rt_ctx* c, const float* q3, uint32_t n, uint32_t k, uint32_t* idx, float* dist, uint32_t* visited) {
@@ -1520,7 +1607,7 @@ int rt_profile_collect(rt_ctx* c, double* total_ms, uint32_t* launches) {
   double sum = 0;
   for (int i = 0; i < n; ++i) {
     float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev[i][0].get(), c->ev[i][1].get()));
+    HIP_TRY(event_pair_ms(c, i, &ms));
     sum += ms;
   }
   *total_ms = sum, *launches = static_cast<uint32_t>(n);
@@ -1954,19 +2041,19 @@ int rt_group_render(rt_group* g, const rt_params* p, const float* bg, float* out
   HIP_TRY(hipSetDevice(g->dev[0]));
   HIP_TRY(hipStreamSynchronize(g->xstream.get()));
   if (stats) {
-    memset(stats, 0, sizeof *stats);
+    *stats = rt_stats{};
     for (uint32_t r = 0; r < n; ++r) {
       HIP_TRY(hipSetDevice(g->dev[r]));
-      rt_stats s{};
+      rt_stats s;
       rc = read_counters(g->ctx[r], &s);
       if (rc != RT_OK) return rc;
       float ms = 0.f;
-      HIP_TRY(hipEventElapsedTime(&ms, g->ctx[r]->ev[ev[r]][0].get(), g->ctx[r]->ev[ev[r]][1].get()));
+      HIP_TRY(event_pair_ms(g->ctx[r], ev[r], &ms));
       stats->rays_closest += s.rays_closest, stats->rays_shadow += s.rays_shadow, stats->knn_queries += s.knn_queries;
       stats->nodes_visited += s.nodes_visited, stats->tris_tested += s.tris_tested, stats->kd_visited += s.kd_visited;
       stats->kernel_ms = ms > stats->kernel_ms ? ms : stats->kernel_ms;  // the slowest rank
     }
-    stats->samples = (uint64_t)npx * (p->spp_count ? p->spp_count : p->spp);
+    stats->samples = (uint64_t)npx * sample_range(*p).count;
   }
   return RT_OK;
 }
@@ -2347,46 +2434,6 @@ namespace {
 constexpr uint32_t kDenoiseIterations = 5;
 constexpr float kDenoiseSigmaColor = 2.f, kDenoiseSigmaNormal = 0.5f;
 
-// Device copies of a host form's buffers, freed with the scope: in() uploads an input, out() makes room for an output
-// the caller asked for (null otherwise), download() copies every such output back.  After a failure in() and out()
-// answer null and rc holds what the entry point returns; it is looked at once, after the last of them.
-struct Staging {
-  struct Out {
-    void* host;
-    const void* dev;
-    size_t bytes;
-  };
-  std::vector<DevBuf<char>> bufs;
-  std::vector<Out> outs;
-  int rc = RT_OK;
-
-  int stage(void** d, const void* src, size_t bytes) {
-    DevBuf<char> b;
-    HIP_TRY(dev_alloc(&b, bytes));
-    if (src) HIP_TRY(hipMemcpy(b.get(), src, bytes, hipMemcpyHostToDevice));
-    *d = b.get();
-    bufs.push_back(std::move(b));
-    return RT_OK;
-  }
-  template <class T>
-  T* in(const T* host, size_t count) {
-    void* d = nullptr;
-    if (rc == RT_OK) rc = stage(&d, host, count * sizeof(T));
-    return static_cast<T*>(d);
-  }
-  template <class T>
-  T* out(T* host, size_t count) {
-    void* d = nullptr;
-    if (host && rc == RT_OK) rc = stage(&d, nullptr, count * sizeof(T));
-    if (d) outs.push_back({host, d, count * sizeof(T)});
-    return static_cast<T*>(d);
-  }
-  int download() {
-    for (const Out& o : outs) HIP_TRY(hipMemcpy(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost));
-    return RT_OK;
-  }
-};
-
 // checks the three filters share (the texts are part of what the callers see)
 int check_image_size(uint32_t w, uint32_t h) {
   return w == 0 || h == 0 || w > 65535u || h > 65535u ? fail(RT_ERR_INVALID, "image size %ux%u out of range", w, h) : RT_OK;
@@ -2426,14 +2473,17 @@ int denoise_checks(const rt_ctx* c, const rt_denoise_params* d, const void* rgb,
   return check_aov_channels(aov, "denoiser");
 }
 
+// ... and what they check in d's numbers (both after their own earlier checks: the header gives each form's order)
+int denoise_param_checks(const rt_denoise_params* d) {
+  int rc = check_image_size(d->width, d->height);
+  if (rc != RT_OK) return rc;
+  if (d->iterations > 8) return fail(RT_ERR_INVALID, "iterations %u > 8", d->iterations);
+  return check_sigmas({d->sigma_color, d->sigma_normal, d->sigma_position});
+}
+
 // c->dnScratch with room for `need` float4 (rt_denoise_device and rt_svgf_device: one call at a time)
 int ensure_filter_scratch(rt_ctx* c, size_t need) {
-  if (need <= c->dnCap) return RT_OK;
-  c->dnCap = 0;
-  if (c->dnScratch) HIP_TRY(hipFree(c->dnScratch.release()));
-  HIP_TRY(dev_alloc(&c->dnScratch, need));
-  c->dnCap = need;
-  return RT_OK;
+  return grow(&c->dnScratch, &c->dnCap, need);
 }
 
 // rt_render_aov's own view of p: the fields that do not affect the pass are neutralised before rt_render's checks
@@ -2452,13 +2502,25 @@ int aov_checks(const rt_ctx* c, const rt_params* p, rt_params* q) {
   return RT_OK;
 }
 
+// The denoiser's arguments (one frame or a stack of them) with d's defaults applied; the scratch is the context's
+rtk::DenoiseArgs denoise_args(const rt_ctx* c, const rt_denoise_params* d, const void* d_rgb, const rt_aov* aov, void* d_out) {
+  rtk::DenoiseArgs D;
+  D.width = d->width, D.height = d->height;
+  D.iterations = d->iterations ? d->iterations : kDenoiseIterations;
+  D.sigma_color = d->sigma_color > 0.f ? d->sigma_color : kDenoiseSigmaColor;
+  D.sigma_normal = d->sigma_normal > 0.f ? d->sigma_normal : kDenoiseSigmaNormal;
+  D.sigma_position = d->sigma_position;  // 0: the device derives it from the scene's extent (once for a stack)
+  D.rgb = static_cast<const float*>(d_rgb), D.albedo = aov->albedo, D.normal = aov->normal, D.position = aov->position;
+  D.hits = aov->hits, D.out = static_cast<float*>(d_out), D.scratch = c->dnScratch.get();
+  return D;
+}
+
 rtk::AovArgs aov_args(const rt_params& q, const rt_aov& out) {
   rtk::AovArgs A;
   A.albedo = out.albedo, A.normal = out.normal, A.position = out.position, A.depth = out.depth;
   A.hits = out.hits, A.mesh = out.mesh, A.tri = out.tri;
   A.width = q.width, A.height = q.height, A.spp = q.spp, A.seed = q.seed;
-  A.s0 = q.spp_count ? q.spp_begin : 0;
-  A.s1 = q.spp_count ? q.spp_begin + q.spp_count : q.spp;
+  A.s0 = sample_range(q).s0, A.s1 = sample_range(q).s1;
   return A;
 }
 
@@ -2498,20 +2560,10 @@ int rt_denoise_device(rt_ctx* c, const rt_denoise_params* d, const void* d_rgb, 
   int rc = denoise_checks(c, d, d_rgb, aov, d_out);
   if (rc != RT_OK) return rc;
   if ((rc = check_not_broken(c)) != RT_OK) return rc;
-  if ((rc = check_image_size(d->width, d->height)) != RT_OK) return rc;
-  if (d->iterations > 8) return fail(RT_ERR_INVALID, "iterations %u > 8", d->iterations);
-  if ((rc = check_sigmas({d->sigma_color, d->sigma_normal, d->sigma_position})) != RT_OK) return rc;
+  if ((rc = denoise_param_checks(d)) != RT_OK) return rc;
   HIP_TRY(hipSetDevice(c->device));
   if ((rc = ensure_filter_scratch(c, rtk::filter_scratch(d->width, d->height))) != RT_OK) return rc;
-  rtk::DenoiseArgs D;
-  D.width = d->width, D.height = d->height;
-  D.iterations = d->iterations ? d->iterations : kDenoiseIterations;
-  D.sigma_color = d->sigma_color > 0.f ? d->sigma_color : kDenoiseSigmaColor;
-  D.sigma_normal = d->sigma_normal > 0.f ? d->sigma_normal : kDenoiseSigmaNormal;
-  D.sigma_position = d->sigma_position;  // 0: the device derives it from the scene's extent
-  D.rgb = static_cast<const float*>(d_rgb), D.albedo = aov->albedo, D.normal = aov->normal, D.position = aov->position;
-  D.hits = aov->hits, D.out = static_cast<float*>(d_out), D.scratch = c->dnScratch.get();
-  const hipError_t he = rtk::launch_denoise(c->S, D, static_cast<hipStream_t>(stream));
+  const hipError_t he = rtk::launch_denoise(c->S, denoise_args(c, d, d_rgb, aov, d_out), static_cast<hipStream_t>(stream));
   if (he != hipSuccess) return fail(RT_ERR_HIP, "denoise launch failed: %s", hipGetErrorString(he));
   return RT_OK;
 }
@@ -2567,8 +2619,19 @@ rtk::MotionArgs motion_args(const rt_ctx* c, const rt_params& q, const rt_motion
   A.prevVpos = dPrevPos ? dPrevPos : c->S.vpos;
   A.prevCam = prev->camera ? *prev->camera : c->S.cam;
   A.width = q.width, A.height = q.height, A.spp = q.spp, A.seed = q.seed;
-  A.s0 = q.spp_count ? q.spp_begin : 0;
+  A.s0 = sample_range(q).s0;
   return A;
+}
+
+// Last frame's positions as a host form was given them (null: the scene's own), in the context's copy on the device
+int upload_prev_positions(rt_ctx* c, const float* hostPos, const float** dPos) {
+  *dPos = nullptr;
+  if (!hostPos) return RT_OK;
+  const size_t nv = 3 * (size_t)c->nVertices;
+  if (!c->mvPrev) HIP_TRY(dev_alloc(&c->mvPrev, nv));
+  HIP_TRY(hipMemcpy(c->mvPrev.get(), hostPos, nv * sizeof(float), hipMemcpyHostToDevice));
+  *dPos = c->mvPrev.get();
+  return RT_OK;
 }
 
 bool overlap(const void* a, size_t na, const void* b, size_t nb) {
@@ -2618,17 +2681,15 @@ int rt_render_motion(rt_ctx* c, const rt_params* p, const rt_motion_prev* prev, 
   int rc = motion_checks(c, p, prev, out, &q);
   if (rc != RT_OK) return rc;
   HIP_TRY(hipSetDevice(c->device));
-  const size_t npx = (size_t)q.width * q.height, nv = 3 * (size_t)c->nVertices;
-  if (prev->vertex_pos) {
-    if (!c->mvPrev) HIP_TRY(dev_alloc(&c->mvPrev, nv));
-    HIP_TRY(hipMemcpy(c->mvPrev.get(), prev->vertex_pos, nv * sizeof(float), hipMemcpyHostToDevice));
-  }
+  const size_t npx = (size_t)q.width * q.height;
+  const float* dPrevPos = nullptr;
+  if ((rc = upload_prev_positions(c, prev->vertex_pos, &dPrevPos)) != RT_OK) return rc;
   Staging st;
   rt_motion d = {};
   d.motion = st.out(out->motion, 2 * npx), d.position = st.out(out->position, 3 * npx);
   d.prev_position = st.out(out->prev_position, 3 * npx), d.mesh = st.out(out->mesh, npx);
   if (st.rc != RT_OK) return st.rc;
-  const rtk::MotionArgs A = motion_args(c, q, prev, prev->vertex_pos ? c->mvPrev.get() : nullptr, d);
+  const rtk::MotionArgs A = motion_args(c, q, prev, dPrevPos, d);
   const hipError_t he = rtk::launch_motion(q.accel == RT_ACCEL_BRUTE, c->S, A, nullptr);
   if (he != hipSuccess) return fail(RT_ERR_HIP, "motion launch failed: %s", hipGetErrorString(he));
   return st.download();
@@ -2833,12 +2894,7 @@ int rt_render_adaptive_device(rt_ctx* c, const rt_params* p, const rt_adaptive_p
   const size_t oMom = up(npx * sizeof(float4)), oPass = oMom + up(npx * sizeof(double2)), oRet = oPass + up(nG * 4ull);
   const size_t oList = oRet + up(nG * 4ull), oTiles = oList + up(nG * 4ull), oCnt = oTiles + up(nG * 64ull * 4);
   const size_t need = oCnt + rtk::ADAPT_CNT_WORDS * 4;
-  if (need > c->adCap) {
-    c->adCap = 0;
-    if (c->adScratch) HIP_TRY(hipFree(c->adScratch.release()));
-    HIP_TRY(dev_alloc(&c->adScratch, need));
-    c->adCap = need;
-  }
+  if ((rc = grow(&c->adScratch, &c->adCap, need)) != RT_OK) return rc;
   char* b = c->adScratch.get();
   rtk::AdaptArgs A;
   A.width = W, A.height = H, A.gx = gx, A.gy = gy, A.P = p->spp, A.minPasses = R.minPasses;
@@ -2911,7 +2967,6 @@ int rt_render_adaptive_device(rt_ctx* c, const rt_params* p, const rt_adaptive_p
     }
   }
   if (stats) {
-    memset(stats, 0, sizeof *stats);
     if ((rc = read_counters(c, stats)) != RT_OK) return rc;
     stats->kernel_ms = renderMs;
     stats->samples = out.pixel_samples;
@@ -2933,19 +2988,14 @@ int rt_render_adaptive(rt_ctx* c, const rt_params* p, const rt_adaptive_params* 
   if (!bg || !out_rgb) return fail(RT_ERR_INVALID, "null argument");
   HIP_TRY(hipSetDevice(c->device));
   const size_t npx = (size_t)p->width * p->height;
-  DevBuf<float4> dAccum;
-  DevBuf<float> dBg, dOut;
-  DevBuf<uint32_t> dSpp;
-  HIP_TRY(dev_alloc(&dAccum, npx));
-  HIP_TRY(dev_alloc(&dBg, npx * 3));
-  HIP_TRY(dev_alloc(&dOut, npx * 3));
-  if (spp_out) HIP_TRY(dev_alloc(&dSpp, npx));
-  HIP_TRY(hipMemcpy(dBg.get(), bg, npx * 3 * sizeof(float), hipMemcpyHostToDevice));
-  rc = rt_render_adaptive_device(c, p, a, dBg.get(), dAccum.get(), dOut.get(), dSpp.get(), nullptr, rep, stats);
-  if (rc != RT_OK) return rc;
-  HIP_TRY(hipMemcpy(out_rgb, dOut.get(), npx * 3 * sizeof(float), hipMemcpyDeviceToHost));
-  if (accum_out) HIP_TRY(hipMemcpy(accum_out, dAccum.get(), npx * sizeof(float4), hipMemcpyDeviceToHost));
-  if (spp_out) HIP_TRY(hipMemcpy(spp_out, dSpp.get(), npx * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  Staging st;
+  float4* dAccum = st.work<float4>(accum_out, npx);  // (the device form zeroes it)
+  const float* dBg = st.in(bg, 3 * npx);
+  float* dOut = st.out(out_rgb, 3 * npx);
+  uint32_t* dSpp = st.out(spp_out, npx);
+  if (st.rc != RT_OK) return st.rc;
+  if ((rc = rt_render_adaptive_device(c, p, a, dBg, dAccum, dOut, dSpp, nullptr, rep, stats)) != RT_OK) return rc;
+  if ((rc = st.download()) != RT_OK) return rc;
   if (rep) rep->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return RT_OK;
 }
@@ -2991,6 +3041,16 @@ int views_checks(rt_ctx* c, const rt_params* p, const rt_views* v, rtbvh::Paddin
   return RT_OK;
 }
 
+// A camera-only rt_update on `stream` to the padding the farthest view of a multi-view call needs; the context does not
+// take that view's camera.
+int refit_to_padding(rt_ctx* c, const rtbvh::Padding& pad, hipStream_t stream) {
+  const int rc = update_checks(c, nullptr, 0);
+  if (rc != RT_OK) return rc;
+  Update x;
+  x.padding = &pad;
+  return update_ctx(c, x, stream, std::chrono::steady_clock::now(), nullptr);
+}
+
 // The view-major wave tiles of n views (each view's as a single-view frame has them) and each tile's view, cached on the
 // context by (frame, sshift, n)
 int ensure_view_tiles(rt_ctx* c, const rt_params* p, uint32_t sshift, uint32_t n, hipStream_t stream) {
@@ -3024,28 +3084,11 @@ int upload_views(rt_ctx* c, const rt_params* p, const rt_views* v, const rt_came
   if (!g.read) HIP_TRY(make_event(&g.read, hipEventDisableTiming));
   if (g.readSet) HIP_TRY(hipEventSynchronize(g.read.get()));
   g.readSet = false;
-  if (n > g.cap) {
-    g.cap = 0;
-    HIP_TRY(pinned_alloc(&g.recs, n));
-    g.cap = n;
-  }
-  if (prevCams && n > g.prevCap) {
-    g.prevCap = 0;
-    HIP_TRY(pinned_alloc(&g.prevCams, n));
-    g.prevCap = n;
-  }
-  if (n > c->vwCap) {
-    c->vwCap = 0;
-    if (c->vwRecs) HIP_TRY(hipFree(c->vwRecs.release()));
-    HIP_TRY(dev_alloc(&c->vwRecs, n));
-    c->vwCap = n;
-  }
-  if (prevCams && n > c->vwPrevCap) {
-    c->vwPrevCap = 0;
-    if (c->vwPrevCams) HIP_TRY(hipFree(c->vwPrevCams.release()));
-    HIP_TRY(dev_alloc(&c->vwPrevCams, n));
-    c->vwPrevCap = n;
-  }
+  int rc = grow(&g.recs, &g.cap, n);
+  if (rc == RT_OK && prevCams) rc = grow(&g.prevCams, &g.prevCap, n);
+  if (rc == RT_OK) rc = grow(&c->vwRecs, &c->vwCap, n);
+  if (rc == RT_OK && prevCams) rc = grow(&c->vwPrevCams, &c->vwPrevCap, n);
+  if (rc != RT_OK) return rc;
   if (prevCams) {
     memcpy(g.prevCams.get(), prevCams, n * sizeof(rt_camera));
     HIP_TRY(hipMemcpyAsync(c->vwPrevCams.get(), g.prevCams.get(), n * sizeof(rt_camera), hipMemcpyHostToDevice, stream));
@@ -3076,14 +3119,9 @@ int rt_render_views_device(rt_ctx* c, const rt_params* p, const rt_views* v, voi
   if (!d_accum) return fail(RT_ERR_INVALID, "d_accum is null");
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (refit) {  // a camera-only rt_update to the farthest view, whose camera the context does not take
-    if ((rc = update_checks(c, nullptr, 0)) != RT_OK) return rc;
-    Update x;
-    x.padding = &pad;
-    if ((rc = update_ctx(c, x, s, std::chrono::steady_clock::now(), nullptr)) != RT_OK) return rc;
-  }
+  if (refit && (rc = refit_to_padding(c, pad, s)) != RT_OK) return rc;
   const uint32_t n = v->n_views;
-  const uint32_t sppCount = p->spp_count ? p->spp_count : p->spp;
+  const uint32_t sppCount = sample_range(*p).count;
   const uint32_t sshift = choose_sshift_px(c, p, (uint64_t)n * p->width * p->height, sppCount);
   if ((rc = ensure_view_tiles(c, p, sshift, n, s)) != RT_OK) return rc;
   if ((rc = upload_views(c, p, v, nullptr, s)) != RT_OK) return rc;
@@ -3092,16 +3130,7 @@ int rt_render_views_device(rt_ctx* c, const rt_params* p, const rt_views* v, voi
   own.tileView = c->vwTileView.d.get(), own.views = c->vwRecs.get();
   int e = 0;
   if ((rc = launch_frame(c, p, static_cast<float4*>(d_accum), s, &e, &own)) != RT_OK) return rc;
-  if (stats) {
-    memset(stats, 0, sizeof *stats);
-    HIP_TRY(hipStreamSynchronize(s));
-    if ((rc = read_counters(c, stats)) != RT_OK) return rc;
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev[e][0].get(), c->ev[e][1].get()));
-    stats->kernel_ms = ms;
-    stats->samples = (uint64_t)n * p->width * p->height * sppCount;
-  }
-  return RT_OK;
+  return stats ? frame_stats(c, s, e, (uint64_t)n * p->width * p->height * sppCount, stats) : (int)RT_OK;
 }
 
 int rt_render_views(rt_ctx* c, const rt_params* p, const rt_views* v, const float* bg, float* out_rgb, float* accum_out,
@@ -3113,27 +3142,14 @@ int rt_render_views(rt_ctx* c, const rt_params* p, const rt_views* v, const floa
   if (out_rgb && !bg) return fail(RT_ERR_INVALID, "out_rgb requested without a background image");
   HIP_TRY(hipSetDevice(c->device));
   const size_t npx = (size_t)p->width * p->height, all = npx * v->n_views;
-  DevBuf<float4> dAccum;
-  DevBuf<float> dBg, dOut;
-  HIP_TRY(dev_alloc(&dAccum, all));
-  HIP_TRY(hipMemset(dAccum.get(), 0, all * sizeof(float4)));
-  if (out_rgb) {
-    HIP_TRY(dev_alloc(&dBg, npx * 3));
-    HIP_TRY(dev_alloc(&dOut, all * 3));
-    HIP_TRY(hipMemcpy(dBg.get(), bg, npx * 3 * sizeof(float), hipMemcpyHostToDevice));
-  }
+  Staging st;
+  float4* dAccum = st.zeroed<float4>(accum_out, all);
+  if (st.rc != RT_OK) return st.rc;
   rt_stats local;
-  if ((rc = rt_render_views_device(c, p, v, dAccum.get(), nullptr, stats ? stats : &local)) != RT_OK) return rc;
-  if (out_rgb) {
-    // each view resolved over its slice, with the shared background
-    for (uint32_t j = 0; j < v->n_views; ++j) {
-      const hipError_t he = rtk::launch_resolve((uint32_t)npx, p->spp, dAccum.get() + j * npx, dBg.get(), dOut.get() + 3 * j * npx, nullptr);
-      if (he != hipSuccess) return fail(RT_ERR_HIP, "resolve launch failed: %s", hipGetErrorString(he));
-    }
-    HIP_TRY(hipMemcpy(out_rgb, dOut.get(), all * 3 * sizeof(float), hipMemcpyDeviceToHost));
-  }
-  if (accum_out) HIP_TRY(hipMemcpy(accum_out, dAccum.get(), all * sizeof(float4), hipMemcpyDeviceToHost));
-  return RT_OK;
+  if ((rc = rt_render_views_device(c, p, v, dAccum, nullptr, stats ? stats : &local)) != RT_OK) return rc;
+  // each view resolved over its slice, with the shared background
+  if ((rc = stage_resolve(&st, bg, out_rgb, dAccum, v->n_views, npx, p->spp)) != RT_OK) return rc;
+  return st.download();
 }
 
 }  // extern "C"
@@ -3166,8 +3182,7 @@ int ao_launch(rt_ctx* c, const rt_params& q, const rt_ao_params* a, const rt_ao*
   rtk::AoArgs A{};
   A.unoccluded = out->unoccluded, A.hits = out->hits, A.bent = out->bent;
   A.width = q.width, A.height = q.height, A.spp = q.spp, A.seed = q.seed;
-  A.s0 = q.spp_count ? q.spp_begin : 0;
-  A.s1 = q.spp_count ? q.spp_begin + q.spp_count : q.spp;
+  A.s0 = sample_range(q).s0, A.s1 = sample_range(q).s1;
   A.nRays = a->n_rays, A.bias = a->bias, A.maxDistance = a->max_distance;
   if (a->bias == 0.f) {
     if (!c->aoExt) HIP_TRY(dev_alloc(&c->aoExt, 6));
@@ -3243,27 +3258,16 @@ int rays_launch(rt_ctx* c, const rt_params& q, const rt_ray_batch& b, float4* dA
   rtk::RaysArgs A{};
   A.rays = b.rays, A.streamIndex = b.stream_index, A.n = b.n;
   A.spp = q.spp, A.mode = q.mode, A.max_depth = q.max_depth, A.seed = q.seed;
-  A.s0 = q.spp_count ? q.spp_begin : 0;
-  A.s1 = q.spp_count ? q.spp_begin + q.spp_count : q.spp;
+  A.s0 = sample_range(q).s0, A.s1 = sample_range(q).s1;
   A.flags = (q.reserved[1] & 1u) ? 0u : 1u;
   A.stackLevels = stack_levels(c->bvh.maxDepth > 1 ? c->bvh.maxDepth : 1);
-  const int e = c->evUsed % kEventPairs;
-  HIP_TRY(hipEventRecord(c->ev[e][0].get(), s));
-  const hipError_t he = rtk::launch_render_rays(q.accel == RT_ACCEL_BRUTE, q.collect_stats != 0, c->S, A, dAccum, c->dCounters.get(), s);
-  if (he != hipSuccess) return fail(RT_ERR_HIP, "ray batch launch failed: %s", hipGetErrorString(he));
-  HIP_TRY(hipEventRecord(c->ev[e][1].get(), s));
-  c->evUsed++;
-  if (stats) {
-    memset(stats, 0, sizeof *stats);
-    HIP_TRY(hipStreamSynchronize(s));
-    const int rc = read_counters(c, stats);
-    if (rc != RT_OK) return rc;
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev[e][0].get(), c->ev[e][1].get()));
-    stats->kernel_ms = ms;
-    stats->samples = (uint64_t)b.n * (A.s1 - A.s0);
-  }
-  return RT_OK;
+  int e = 0;
+  const int rc = timed_launch(c, s, &e, [&] {
+    const hipError_t he = rtk::launch_render_rays(q.accel == RT_ACCEL_BRUTE, q.collect_stats != 0, c->S, A, dAccum, c->dCounters.get(), s);
+    return he != hipSuccess ? fail(RT_ERR_HIP, "ray batch launch failed: %s", hipGetErrorString(he)) : (int)RT_OK;
+  });
+  if (rc != RT_OK || !stats) return rc;
+  return frame_stats(c, s, e, (uint64_t)b.n * (A.s1 - A.s0), stats);
 }
 
 }  // namespace
@@ -3299,37 +3303,20 @@ int rt_render_rays(rt_ctx* c, const rt_params* p, const rt_ray_batch* b, const f
   if ((rc = check_device_present()) != RT_OK) return rc;
   if ((rc = check_not_broken(c)) != RT_OK) return rc;
   HIP_TRY(hipSetDevice(c->device));
-  if (n > c->rbCap) {
-    c->rbCap = 0;
-    if (c->rbRays) HIP_TRY(hipFree(c->rbRays.release()));
-    HIP_TRY(dev_alloc(&c->rbRays, n));
-    c->rbCap = n;
-  }
-  if (b->stream_index && n > c->rbIndexCap) {
-    c->rbIndexCap = 0;
-    if (c->rbIndex) HIP_TRY(hipFree(c->rbIndex.release()));
-    HIP_TRY(dev_alloc(&c->rbIndex, n));
-    c->rbIndexCap = n;
-  }
+  if ((rc = grow(&c->rbRays, &c->rbCap, n)) != RT_OK) return rc;
+  if (b->stream_index && (rc = grow(&c->rbIndex, &c->rbIndexCap, n)) != RT_OK) return rc;
   HIP_TRY(hipMemcpy(c->rbRays.get(), b->rays, n * sizeof(rt_ray), hipMemcpyHostToDevice));
   if (b->stream_index) HIP_TRY(hipMemcpy(c->rbIndex.get(), b->stream_index, n * sizeof(uint32_t), hipMemcpyHostToDevice));
   rt_ray_batch d = *b;
   d.rays = c->rbRays.get(), d.stream_index = b->stream_index ? c->rbIndex.get() : nullptr;
-  DevBuf<float4> dAccum;
-  DevBuf<float> dBg, dOut;
-  HIP_TRY(dev_alloc(&dAccum, n));
-  HIP_TRY(hipMemset(dAccum.get(), 0, n * sizeof(float4)));
+  Staging st;
+  float4* dAccum = st.zeroed<float4>(accum_out, n);
+  if (st.rc != RT_OK) return st.rc;
   rt_stats local;
-  if ((rc = rays_launch(c, q, d, dAccum.get(), nullptr, stats ? stats : &local)) != RT_OK) return rc;
-  if (out_rgb) {  // the batch as an image n wide and 1 high
-    HIP_TRY(dev_alloc(&dBg, n * 3));
-    HIP_TRY(dev_alloc(&dOut, n * 3));
-    HIP_TRY(hipMemcpy(dBg.get(), bg, n * 3 * sizeof(float), hipMemcpyHostToDevice));
-    if ((rc = rt_resolve_device(c, b->n, 1, q.spp, dAccum.get(), dBg.get(), dOut.get(), nullptr)) != RT_OK) return rc;
-    HIP_TRY(hipMemcpy(out_rgb, dOut.get(), n * 3 * sizeof(float), hipMemcpyDeviceToHost));
-  }
-  if (accum_out) HIP_TRY(hipMemcpy(accum_out, dAccum.get(), n * sizeof(float4), hipMemcpyDeviceToHost));
-  return RT_OK;
+  if ((rc = rays_launch(c, q, d, dAccum, nullptr, stats ? stats : &local)) != RT_OK) return rc;
+  // the batch as an image n wide and 1 high
+  if ((rc = stage_resolve(&st, bg, out_rgb, dAccum, 1, n, q.spp)) != RT_OK) return rc;
+  return st.download();
 }
 
 }  // extern "C"
@@ -3377,12 +3364,7 @@ int motion_views_checks(rt_ctx* c, const rt_params* p, const rt_views* v, const 
 int stage_views(rt_ctx* c, const rt_params* q, const rt_views* v, const rt_motion_prev_views* prev, const rtbvh::Padding& pad, bool refit,
                 hipStream_t s) {
   int rc;
-  if (refit) {
-    if ((rc = update_checks(c, nullptr, 0)) != RT_OK) return rc;
-    Update x;
-    x.padding = &pad;
-    if ((rc = update_ctx(c, x, s, std::chrono::steady_clock::now(), nullptr)) != RT_OK) return rc;
-  }
+  if (refit && (rc = refit_to_padding(c, pad, s)) != RT_OK) return rc;
   return upload_views(c, q, v, prev ? (prev->cameras ? prev->cameras : v->cameras) : nullptr, s);
 }
 
@@ -3391,9 +3373,7 @@ int denoise_batch_checks(const rt_ctx* c, const rt_denoise_params* d, uint32_t n
   int rc = denoise_checks(c, d, rgb, aov, out);
   if (rc != RT_OK) return rc;
   if (any_set(d->reserved, 6) || any_set(aov->reserved, 4)) return fail(RT_ERR_INVALID, "reserved words must be zero");
-  if ((rc = check_image_size(d->width, d->height)) != RT_OK) return rc;
-  if (d->iterations > 8) return fail(RT_ERR_INVALID, "iterations %u > 8", d->iterations);
-  if ((rc = check_sigmas({d->sigma_color, d->sigma_normal, d->sigma_position})) != RT_OK) return rc;
+  if ((rc = denoise_param_checks(d)) != RT_OK) return rc;
   if (nFrames == 0) return fail(RT_ERR_INVALID, "n_frames is 0");
   if ((uint64_t)nFrames * d->width * d->height >= (1ull << 31))
     return fail(RT_ERR_INVALID, "%u frames of %ux%u pixels: 2^31 pixels or more", nFrames, d->width, d->height);
@@ -3461,13 +3441,9 @@ int rt_render_motion_views(rt_ctx* c, const rt_params* p, const rt_views* v, con
   int rc = motion_views_checks(c, p, v, prev, out, &q, &pad, &refit);
   if (rc != RT_OK) return rc;
   HIP_TRY(hipSetDevice(c->device));
-  const size_t all = rtk::view_slice(v->n_views, q.width, q.height, 1), nv = 3 * (size_t)c->nVertices;
+  const size_t all = rtk::view_slice(v->n_views, q.width, q.height, 1);
   rt_motion_prev_views dp = *prev;
-  if (prev->vertex_pos) {
-    if (!c->mvPrev) HIP_TRY(dev_alloc(&c->mvPrev, nv));
-    HIP_TRY(hipMemcpy(c->mvPrev.get(), prev->vertex_pos, nv * sizeof(float), hipMemcpyHostToDevice));
-    dp.vertex_pos = c->mvPrev.get();
-  }
+  if ((rc = upload_prev_positions(c, prev->vertex_pos, &dp.vertex_pos)) != RT_OK) return rc;
   Staging st;
   rt_motion d = {};
   d.motion = st.out(out->motion, 2 * all), d.position = st.out(out->position, 3 * all);
@@ -3483,15 +3459,7 @@ int rt_denoise_batch_device(rt_ctx* c, const rt_denoise_params* d, uint32_t n_fr
   if (rc != RT_OK) return rc;
   HIP_TRY(hipSetDevice(c->device));
   if ((rc = ensure_filter_scratch(c, n_frames * rtk::filter_scratch(d->width, d->height))) != RT_OK) return rc;
-  rtk::DenoiseArgs D;
-  D.width = d->width, D.height = d->height;
-  D.iterations = d->iterations ? d->iterations : kDenoiseIterations;
-  D.sigma_color = d->sigma_color > 0.f ? d->sigma_color : kDenoiseSigmaColor;
-  D.sigma_normal = d->sigma_normal > 0.f ? d->sigma_normal : kDenoiseSigmaNormal;
-  D.sigma_position = d->sigma_position;  // 0: the device derives it from the scene's extent, once for the stack
-  D.rgb = static_cast<const float*>(d_rgb), D.albedo = aov->albedo, D.normal = aov->normal, D.position = aov->position;
-  D.hits = aov->hits, D.out = static_cast<float*>(d_out), D.scratch = c->dnScratch.get();
-  const hipError_t he = rtk::launch_denoise_batch(c->S, D, n_frames, static_cast<hipStream_t>(stream));
+  const hipError_t he = rtk::launch_denoise_batch(c->S, denoise_args(c, d, d_rgb, aov, d_out), n_frames, static_cast<hipStream_t>(stream));
   if (he != hipSuccess) return fail(RT_ERR_HIP, "denoise launch failed: %s", hipGetErrorString(he));
   return RT_OK;
 }
