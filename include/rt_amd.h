@@ -32,6 +32,8 @@
  *                                  (+ _device form)
  *   rt_render_rays              <- (no counterpart) the integrator over ray batches of the caller's: probes, baking,
  *                                  cameras of any kind (+ _device form)
+ *   rt_render_lens              <- (no counterpart) the frame through a thin lens: depth of field, one lens sample
+ *                                  per pixel sample (+ _device form)
  *   rt_render_aov_views / rt_render_motion_views / rt_denoise_batch <- (no counterpart) the AOVs, motion vectors and
  *                                  denoised frames of those views, one launch each (+ _device forms)
  *   rt_trace                    <- RayTracer::rayTrace (RayTracer.h:27-53) test hook
@@ -46,10 +48,11 @@
  * no gfx950 device is usable.
  *
  * Stream order of the `_device` forms (tests/test_gpu_stream_order.py issues every one of them on a
- * non-blocking stream that is still busy, back to back):
+ * non-blocking stream that is still busy, back to back; rt_render_lens_device: tests/test_gpu_lens.py):
  *   ASYNCHRONOUS — everything the call does is queued on `stream`, device inputs are read and outputs
  *   written in stream order, and the call returns without waiting for the stream:
- *     rt_render_device, rt_render_views_device and rt_render_rays_device with stats == NULL; rt_resolve_device;
+ *     rt_render_device, rt_render_views_device, rt_render_rays_device and rt_render_lens_device with stats == NULL;
+ *     rt_resolve_device;
  *     rt_render_aov_device, rt_render_ao_device, rt_render_motion_device; rt_temporal_accumulate_device,
  *     rt_svgf_device, rt_denoise_device, rt_denoise_batch_device; rt_render_aov_views_device,
  *     rt_render_motion_views_device; rt_pack_owned_device, rt_unpack_owned_device; rt_trace_stream_device.
@@ -59,7 +62,7 @@
  *     filters; a larger wavefront batch) frees the old block, and hipFree waits for the device; and the fifth
  *     multi-view call in a row waits for the upload of the first (four pinned staging copies).
  *   SYNCHRONISE `stream`, and only it, before they return, because the host reads a result back:
- *     rt_render_device, rt_render_views_device, rt_render_rays_device with stats != NULL;
+ *     rt_render_device, rt_render_views_device, rt_render_rays_device, rt_render_lens_device with stats != NULL;
  *     rt_render_adaptive_device (every pass); rt_update_vertices_device and rt_update_transforms (twice);
  *     the three multi-view forms when a view lies far enough out to need a wider box padding (a refit).
  *   HOST forms (rt_render, rt_render_aov, rt_denoise, rt_update, rt_trace, rt_knn, rt_bvh_quality_get, rt_rebuild,
@@ -544,6 +547,65 @@ int rt_render_rays(rt_ctx* ctx, const rt_params* p, const rt_ray_batch* b, const
 /* Accumulate into caller-zeroed DEVICE d_accum [n][4] on `stream` (a hipStream_t, may be NULL), as rt_render_device
  * does: sample ranges chain.  The host waits only to read stats back. */
 int rt_render_rays_device(rt_ctx* ctx, const rt_params* p, const rt_ray_batch* b, void* d_accum, void* stream,
+                          rt_stats* stats);
+
+/* ---- the frame through a thin lens: depth of field ---------------------------------------------------
+ * rt_render_lens renders the frame p describes as rt_render does, except that the primary ray of every SAMPLE leaves a
+ * point of its own on a lens disc of radius `aperture` around the camera position and passes through the point where the
+ * pinhole ray of that sample meets the plane of focus.  Points at focus_distance (measured along the optical axis, the
+ * normal of the image plane) are sharp; everything else is blurred by the disc.
+ *
+ * Host-derived constants, computed once per call from the context's camera (pos, ll, H, V; float32 inputs):
+ *   Hu = unit3(H), Vu = unit3(V) in float32 (Vec3.h:170-178: l = sqrt((x x + y y) + z z), inv = 1 / l, a inv);
+ *   in float64, with cross and dot associated as the motion-vector section below defines them:
+ *     c = ((ll + 0.5 H) + 0.5 V) - pos;  n = cross(H, V);  plane = |dot(c, n)| / sqrt(dot(n, n));
+ *     fs = (float)(focus_distance / plane).
+ * Sample i of pixel (x, y), pix = y * width + x:
+ *   1. g is seeded with rt_stream_seed(seed, RT_STREAM_PIXEL, pix, i); jitter_sample(g, i, spp) gives (cu, cv) exactly
+ *      as the frame forms them.
+ *   2. aperture == 0: the ray is the frame's own camera_ray(cam, cu, cv).  No lens stream is drawn; fs is neither
+ *      computed nor checked.
+ *   3. aperture > 0, all in float32, nothing fused:
+ *        q = ((ll + cu H) + cv V) - pos               (camera_ray's operand before unit3)
+ *        F = pos + fs q                               (per component: the product, then the sum)
+ *        e is seeded with rt_stream_seed(seed, RT_STREAM_LENS, pix, i); up to 32 times: lx = e.uniformF(-1, 1), then
+ *        ly = e.uniformF(-1, 1); the first pair with lx lx + ly ly <= 1 is taken; if none is, lx = ly = 0
+ *        o' = (pos + (aperture lx) Hu) + (aperture ly) Vu   (per component)
+ *        the primary ray is (o', unit3(F - o')) with the division and the square root, never the short forms
+ *        (rt_render_rays' rule).
+ *   4. From the primary cast on the sample is the frame's, and g is where the frame's stream is (the lens draws came from
+ *      e): the vertices, the light samples in light order, the hemisphere draw after every shaded vertex, c0 + (c1 +
+ *      (c2 + 0)), the clamp, the float32 adds in sample order into .xyz and the hit count into .w.
+ * Guarantees:
+ *   - aperture == 0: accum, out and the ray counts are bit-identical to rt_render / rt_render_device for the same p.
+ *   - aperture > 0: what sample i adds to pixel pix is, bit for bit, row pix of rt_render_rays for the ray (o', F - o')
+ *     with stream_index = pix, spp_begin = i, spp_count = 1.
+ *   - sample ranges, reserved[0] (lanes per pixel) and reserved[1] bit 0 (no pool) change the schedule, never the bits,
+ *     at either aperture.
+ * RT_NODES_Q8 contexts walk their resident 32-byte records, as rt_render_aov does.  The call changes nothing in the
+ * context.  Stats are a frame's.  The frame runs on the one-wave-per-workgroup kernel family of rt_render (there are no
+ * persistent lens instances).
+ * Validation comes first and a rejected call writes nothing.  RT_ERR_INVALID: a null ctx, p or lens; host form: neither
+ * out_rgb nor accum_out, or out_rgb without background_rgb; device form: a null d_accum; non-zero reserved words; an
+ * unknown model; a negative or non-finite aperture; with aperture > 0 a non-finite or non-positive focus_distance, a
+ * null H or V, or an fs that is not finite or not > 0; max_c |pos_c| + 2 aperture above the context's origin bound
+ * (16 x the padding reference: the bound of rt_trace and rt_render_rays, inside which every lens origin walks the tree
+ * as a row of rt_render_rays does); every check rt_render applies to p.  RT_ERR_UNSUPPORTED: world > 1, use_photons, the
+ * wavefront integrator (reserved[2] bit 0), the legacy RNG.  The checks that read the camera follow the others, and a
+ * context exists only where a device does.                                                                              */
+enum { RT_LENS_THIN = 0 };
+typedef struct rt_lens {
+  uint32_t model;          /* RT_LENS_THIN; anything else RT_ERR_INVALID                               */
+  float aperture;          /* lens RADIUS in scene units; 0 = pinhole; finite, >= 0                    */
+  float focus_distance;    /* along the optical axis; finite, > 0; ignored when aperture == 0          */
+  uint32_t reserved[5];    /* zero */
+} rt_lens;
+/* buffers as rt_render's */
+int rt_render_lens(rt_ctx* ctx, const rt_params* p, const rt_lens* lens, const float* background_rgb, float* out_rgb,
+                   float* accum_out, rt_stats* stats);
+/* Accumulate into caller-zeroed DEVICE d_accum [h][w][4] on `stream` (a hipStream_t, may be NULL), as rt_render_device
+ * does: sample ranges chain.  p and lens are copied before the call returns; the host waits only to read stats back. */
+int rt_render_lens_device(rt_ctx* ctx, const rt_params* p, const rt_lens* lens, void* d_accum, void* stream,
                           rt_stats* stats);
 
 /* ---- motion vectors and temporal accumulation (DESIGN.md "Motion vectors and temporal accumulation") ----------------

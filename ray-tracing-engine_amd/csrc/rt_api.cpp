@@ -653,8 +653,9 @@ struct TileList {
 };
 
 // Launch the integrate kernel for p on `stream`, bracketed by an event pair.  own: render those wave tiles only.
+// lens: the frame through a thin lens (rt_render_lens; the caller has refused photons and the wavefront bit).
 int launch_frame(rt_ctx* c, const rt_params* p, float4* dAccum, hipStream_t stream, int* evIndex,
-                 const TileList* own = nullptr) {
+                 const TileList* own = nullptr, const rtk::LensRec* lens = nullptr) {
   const SampleRange sr = sample_range(*p);
   const uint32_t sshift = own ? own->sshift : choose_sshift(c, p, sr.count);
   int rc = own ? RT_OK : ensure_tiles(c, p, sshift, stream);
@@ -689,7 +690,11 @@ int launch_frame(rt_ctx* c, const rt_params* p, float4* dAccum, hipStream_t stre
   rtk::WfArgs W{};
   if (wavefront && (rc = wavefront_args(c, p, A, sr.count, stream, &W)) != RT_OK) return rc;
   return timed_launch(c, stream, evIndex, [&] {
-    if (!wavefront) {
+    if (lens) {
+      hipError_t he = rtk::launch_render_lens(p->accel == RT_ACCEL_BRUTE, p->collect_stats != 0, c->S, A, *lens, dAccum,
+                                              c->dCounters.get(), stream);
+      if (he != hipSuccess) return fail(RT_ERR_HIP, "lens render launch failed: %s", hipGetErrorString(he));
+    } else if (!wavefront) {
       hipError_t he = rtk::launch_render(p->accel == RT_ACCEL_BRUTE, p->use_photons != 0, p->collect_stats != 0, c->S, A,
                                          dAccum, c->dCounters.get(), stream);
       if (he != hipSuccess) return fail(RT_ERR_HIP, "render launch failed: %s", hipGetErrorString(he));
@@ -1085,6 +1090,23 @@ int stage_resolve(Staging* st, const float* bg, float* out_rgb, const float4* dA
   }
   return RT_OK;
 }
+
+// The frame of a checked p into d_accum on `stream`, with a frame's stats: rt_render_device, and (lens) rt_render_lens_device.
+int frame_device(rt_ctx* c, const rt_params* p, const rtk::LensRec* lens, void* d_accum, void* stream, rt_stats* stats) {
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (stats) HIP_TRY(hipMemsetAsync(c->dCounters.get(), 0, RTK_CNT_COUNT * sizeof(unsigned long long), s));
+  int e = 0;
+  const int rc = launch_frame(c, p, static_cast<float4*>(d_accum), s, &e, nullptr, lens);
+  if (rc != RT_OK) return rc;
+  if (!stats) return RT_OK;
+  // samples of the pixels this rank owns: its granules, clipped to the image
+  uint64_t px = 0;
+  owned_granules(p->width, p->height, p->rank, p->world, p->tile, [&](uint32_t x8, uint32_t y8) {
+    px += (uint64_t)std::min(8u, p->width - x8 * 8) * std::min(8u, p->height - y8 * 8);
+  });
+  return frame_stats(c, s, e, px * sample_range(*p).count, stats);
+}
 }  // namespace
 
 extern "C" {
@@ -1152,21 +1174,9 @@ int rt_emit_photons(rt_ctx* c, uint32_t n_requested, uint32_t seed, float* pos3,
 
 int rt_render_device(rt_ctx* c, const rt_params* p, void* d_accum, void* stream, rt_stats* stats) {
   if (!c || !d_accum) return fail(RT_ERR_INVALID, "ctx/d_accum is null");
-  int rc = check_params(c, p);
+  const int rc = check_params(c, p);
   if (rc != RT_OK) return rc;
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (stats) HIP_TRY(hipMemsetAsync(c->dCounters.get(), 0, RTK_CNT_COUNT * sizeof(unsigned long long), s));
-  int e = 0;
-  rc = launch_frame(c, p, static_cast<float4*>(d_accum), s, &e);
-  if (rc != RT_OK) return rc;
-  if (!stats) return RT_OK;
-  // samples of the pixels this rank owns: its granules, clipped to the image
-  uint64_t px = 0;
-  owned_granules(p->width, p->height, p->rank, p->world, p->tile, [&](uint32_t x8, uint32_t y8) {
-    px += (uint64_t)std::min(8u, p->width - x8 * 8) * std::min(8u, p->height - y8 * 8);
-  });
-  return frame_stats(c, s, e, px * sample_range(*p).count, stats);
+  return frame_device(c, p, nullptr, d_accum, stream, stats);
 }
 
 int rt_resolve_device(rt_ctx* c, uint32_t width, uint32_t height, uint32_t spp, const void* d_accum,
@@ -3316,6 +3326,95 @@ int rt_render_rays(rt_ctx* c, const rt_params* p, const rt_ray_batch* b, const f
   if ((rc = rays_launch(c, q, d, dAccum, nullptr, stats ? stats : &local)) != RT_OK) return rc;
   // the batch as an image n wide and 1 high
   if ((rc = stage_resolve(&st, bg, out_rgb, dAccum, 1, n, q.spp)) != RT_OK) return rc;
+  return st.download();
+}
+
+}  // extern "C"
+
+// ---- the frame through a thin lens --------------------------------------------------------------------
+namespace {
+
+// Vec3.h:170-178 in float32 as the device forms it (rt_device.h unit3); false for a null or non-finite vector
+bool unit3_host(const float* a, float* u) {
+  const float xx = a[0] * a[0], yy = a[1] * a[1], zz = a[2] * a[2];
+  const float xy = xx + yy;
+  const float l = std::sqrt(xy + zz);
+  if (!(l > 0.f) || !std::isfinite(l)) return false;
+  const float inv = 1.0f / l;
+  for (int k = 0; k < 3; ++k) u[k] = a[k] * inv;
+  return true;
+}
+
+// Everything both forms of rt_render_lens check, in the header's order, and the record the kernels take.  outputs: what is
+// wrong with the form's own buffers, or null.  What can be told from the arguments alone is answered before the device is
+// asked for, and the camera is read last: a context exists only where a device does.
+int lens_checks(const rt_ctx* c, const rt_params* p, const rt_lens* l, const char* outputs, rtk::LensRec* R) {
+  if (!c || !p || !l) return fail(RT_ERR_INVALID, "ctx/params/lens is null");
+  if (outputs) return fail(RT_ERR_INVALID, "%s", outputs);
+  if (any_set(l->reserved, 5)) return fail(RT_ERR_INVALID, "rt_lens: reserved words must be zero");
+  if (l->model != RT_LENS_THIN) return fail(RT_ERR_INVALID, "unknown lens model %u", l->model);
+  if (!(l->aperture >= 0.f) || !std::isfinite(l->aperture)) return fail(RT_ERR_INVALID, "aperture must be finite and >= 0");
+  const bool open = l->aperture > 0.f;
+  if (open && (!(l->focus_distance > 0.f) || !std::isfinite(l->focus_distance)))
+    return fail(RT_ERR_INVALID, "focus_distance must be finite and > 0");
+  int rc = check_params_shape(p);
+  if (rc != RT_OK) return rc;
+  if (p->world > 1) return fail(RT_ERR_UNSUPPORTED, "tile-sharded lens frames (world %u) are not supported", p->world);
+  if (p->use_photons) return fail(RT_ERR_UNSUPPORTED, "lens frames do not shade from the photon map");
+  if (p->reserved[2] & 1u) return fail(RT_ERR_UNSUPPORTED, "lens frames do not run the wavefront integrator");
+  if ((rc = check_device_present()) != RT_OK) return rc;
+  if ((rc = check_not_broken(c)) != RT_OK) return rc;
+  const rt_camera& cam = c->S.cam;
+  float m = 0.f;
+  for (int k = 0; k < 3; ++k) m = std::max(m, std::fabs(cam.position[k]));
+  const float reach = m + 2.f * l->aperture;
+  if (reach > c->bvh.originBound)
+    return fail(RT_ERR_INVALID, "the lens reaches %g from the origin, beyond the context's origin bound %g", reach, c->bvh.originBound);
+  *R = rtk::LensRec{};
+  R->aperture = l->aperture;
+  if (!open) return RT_OK;  // (the frame's own camera_ray: fs is neither computed nor checked)
+  if (!unit3_host(cam.horizontal, R->hu) || !unit3_host(cam.vertical, R->vu))
+    return fail(RT_ERR_INVALID, "the camera's horizontal or vertical axis cannot be normalised");
+  // the distance of the image plane along the optical axis, in float64 (rt_amd.h states the order)
+  double cc[3], H[3], V[3];
+  for (int k = 0; k < 3; ++k) {
+    H[k] = cam.horizontal[k], V[k] = cam.vertical[k];
+    cc[k] = (((double)cam.lower_left[k] + 0.5 * H[k]) + 0.5 * V[k]) - (double)cam.position[k];
+  }
+  const double n[3] = {H[1] * V[2] - H[2] * V[1], H[2] * V[0] - H[0] * V[2], H[0] * V[1] - H[1] * V[0]};
+  const double cn = (cc[0] * n[0] + cc[1] * n[1]) + cc[2] * n[2], nn = (n[0] * n[0] + n[1] * n[1]) + n[2] * n[2];
+  const double plane = std::fabs(cn) / std::sqrt(nn);
+  R->fs = (float)((double)l->focus_distance / plane);
+  if (!(R->fs > 0.f) || !std::isfinite(R->fs))
+    return fail(RT_ERR_INVALID, "focus_distance %g over the image plane's distance %g is not a finite positive float", l->focus_distance, plane);
+  return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_render_lens_device(rt_ctx* c, const rt_params* p, const rt_lens* l, void* d_accum, void* stream, rt_stats* stats) {
+  rtk::LensRec R;
+  const int rc = lens_checks(c, p, l, d_accum ? nullptr : "d_accum is null", &R);
+  if (rc != RT_OK) return rc;
+  return frame_device(c, p, &R, d_accum, stream, stats);
+}
+
+int rt_render_lens(rt_ctx* c, const rt_params* p, const rt_lens* l, const float* bg, float* out_rgb, float* accum_out, rt_stats* stats) {
+  rtk::LensRec R;
+  int rc = lens_checks(c, p, l, !out_rgb && !accum_out ? "neither out_rgb nor accum_out is given"
+                                : out_rgb && !bg     ? "out_rgb requested without a background image"
+                                                     : nullptr, &R);
+  if (rc != RT_OK) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t npx = (size_t)p->width * p->height;
+  Staging st;
+  float4* dAccum = st.zeroed<float4>(accum_out, npx);
+  if (st.rc != RT_OK) return st.rc;
+  rt_stats local;
+  if ((rc = frame_device(c, p, &R, dAccum, nullptr, stats ? stats : &local)) != RT_OK) return rc;
+  if ((rc = stage_resolve(&st, bg, out_rgb, dAccum, 1, npx, p->spp)) != RT_OK) return rc;
   return st.download();
 }
 

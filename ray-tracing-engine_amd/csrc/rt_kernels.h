@@ -149,6 +149,16 @@ struct RaysArgs {
 };
 hipError_t launch_render_rays(bool brute_force, bool stats, const DevScene& S, const RaysArgs& A, float4* accum,
                               unsigned long long* counters, hipStream_t stream);
+// the frame through a thin lens (lens_kernels.h, rt_render_lens): the host-derived constants of rt_amd.h, by value.
+// aperture == 0: the frame's own camera_ray (a wave-uniform test on the record), the other fields are not read.
+struct LensRec {
+  float aperture, fs;  // lens radius; focus_distance / distance of the image plane
+  float hu[3], vu[3];  // unit3(cam.horizontal), unit3(cam.vertical)
+};
+// launch_render's one-wave-per-workgroup family (brute, sequential, pooled; counted or timed) with the lens generator in
+// place of camera_ray; A as launch_render takes it (tileView null)
+hipError_t launch_render_lens(bool brute_force, bool stats, const DevScene& S, const RenderArgs& A, const LensRec& R,
+                              float4* accum, unsigned long long* counters, hipStream_t stream);
 // First element of view j's slice of a per-view output with c floats or words per pixel (rt_render_aov_views,
 // rt_render_motion_views, rt_denoise_batch): formed in 64 bits — n w h may reach 2^31 - 1 and 3 x that is not 32-bit.
 __host__ __device__ inline size_t view_slice(uint32_t j, uint32_t width, uint32_t height, uint32_t c) {

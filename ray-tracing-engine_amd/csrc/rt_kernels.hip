@@ -210,6 +210,9 @@ constexpr int LT_FASTDET = 256;
 // and accumulator slice.  Only render_tile reads it (it strips the bit before it passes LT on).  Its own instances: read
 // at run time, the choice costs every single-view instance SGPR spills and one of them a wave.
 constexpr int LT_VIEWS = 512;
+// A frame through a thin lens (rt_render_lens): render_tile takes a LensRec and, where its aperture is not zero, forms the
+// primary ray by lens_ray instead of camera_ray.  Only render_tile reads the bit; its own instances (lens_kernels.h).
+constexpr int LT_LENS = 1024;
 constexpr uint32_t kPrioMaxNodes = 65536;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(3))) u32x4* lds_u4_ptr;
@@ -1190,11 +1193,34 @@ RT_DEV Lds carve_lds(uint32_t* base, uint32_t levels = STACK, uint32_t kslots = 
 // One wave tile: lane = (pixel pl of the tile, sample slot sj).  The wave integrates
 // S = 1 << sshift consecutive samples of P = 64 >> sshift pixels side by side.
 
+// The primary ray of a sample through a thin lens (rt_amd.h, rt_render_lens; R.aperture > 0): from a point of the lens
+// disc, drawn by rejection from a stream of its own, through the point where the pinhole ray of (u, v) meets the plane
+// of focus.  Float32, nothing fused; the direction by the division and the square root (rt_render_rays' rule).
+RT_DEV void lens_ray(const rt_camera& c, const LensRec& R, uint32_t lensSeed, float u, float v, f3& o, f3& d) {
+  const f3 pos = ld(c.position);
+  const f3 q = ld(c.lower_left) + u * ld(c.horizontal) + v * ld(c.vertical) - pos;  // camera_ray's operand
+  const f3 F = pos + R.fs * q;
+  Rng e{lensSeed};
+  float lx = 0.f, ly = 0.f;
+  for (int t = 0; t < 32; ++t) {  // (a pair is accepted with probability pi / 4)
+    const float x = e.uniformF(-1.f, 1.f);
+    const float y = e.uniformF(-1.f, 1.f);
+    if (x * x + y * y <= 1.f) {
+      lx = x, ly = y;
+      break;
+    }
+  }
+  o = (pos + (R.aperture * lx) * ld(R.hu)) + (R.aperture * ly) * ld(R.vu);
+  d = unit3(F - o);
+}
+
 template <bool BRUTE, bool PHOTON, bool POOLED, bool STATS, int LTV, class HP = Heap>
 RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restrict__ accum, const Lds& L, uint32_t* pool,
-                        float* ex, uint32_t wave, LaneStats& st) {
-  constexpr int LT = LTV & ~LT_VIEWS;
+                        float* ex, uint32_t wave, LaneStats& st, const LensRec* lens = nullptr) {
+  constexpr int LT = LTV & ~(LT_VIEWS | LT_LENS);
   constexpr bool VIEWS = (LTV & LT_VIEWS) != 0;
+  constexpr bool LENS = (LTV & LT_LENS) != 0;
+  static_assert(!LENS || !VIEWS, "no multi-view lens frames");
   constexpr bool FR = (LT & LT_FASTDET) != 0;  // 1 / length by rtd::recip_fast (see rtd::unit3)
   const uint32_t lane = threadIdx.x & 63u;
   // lane = (pixel pl of the wave tile, sample slot sj): the wave integrates
@@ -1235,7 +1261,11 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
     f3 o, d;
     const float cu = ((float)px + sx) / (float)A.width, cv = 1.f - ((float)py + sy) / (float)A.height;
     if constexpr (VIEWS) camera_ray<FR>(cam, cu, cv, o, d);
-    else camera_ray<FR>(S.cam, cu, cv, o, d);
+    else if constexpr (LENS) {
+      // (wave-uniform: the record is a kernel argument)
+      if (lens->aperture > 0.f) lens_ray(S.cam, *lens, rt_stream_seed(A.seed, RT_STREAM_LENS, pix, i), cu, cv, o, d);
+      else camera_ray<FR>(S.cam, cu, cv, o, d);
+    } else camera_ray<FR>(S.cam, cu, cv, o, d);
     f3 c0 = mk(0.f, 0.f, 0.f), c1 = c0, c2 = c0;
     bool primary = true, alive = active;
     if constexpr (pooled) {
@@ -1538,6 +1568,9 @@ __global__ __launch_bounds__(1024, 8) void k_trace_stream(DevScene S, const floa
 
 // ---------------------------------------------------------------- ray batches (rt_render_rays)
 #include "rays_kernels.h"
+
+// ---------------------------------------------------------------- thin-lens frames (rt_render_lens)
+#include "lens_kernels.h"
 
 // ---------------------------------------------------------------- frame assembly (multi-GPU)
 // A rank's owned 8x8-pixel granules, packed [granule][64 pixels] (row-major inside the

@@ -5,7 +5,7 @@
 // value is "Missing argument" unless it is -help; unknown flags throw; a mode other
 // than 0/1 silently becomes 0), plus build-defined extensions the reference has
 // no equivalent for: -scene, -meshdir, -seed, -gpu, -gpus, -devices, -accel,
-// -progress, -tune, -denoise, -aov, -adaptive, -pass, -ao, -aodist.
+// -progress, -tune, -denoise, -aov, -adaptive, -pass, -ao, -aodist, -aperture, -focus.
 #pragma once
 
 #include <cstdlib>
@@ -19,7 +19,7 @@ class CommandLine {
  public:
   CommandLine()
       : m_width(380), m_height(270), m_numRays(16), m_mode(0), m_numPhotons(0), m_k(5), m_seed(1), m_gpu(0),
-        m_accel(0), m_progress(0), m_gpus(1), m_denoise(0), m_aov(0), m_pass(16), m_ao(0), m_tune(0.), m_adaptive(-1.), m_aoDist(0.), m_outputFilename("output.ppm"), m_scene("cubes"), m_meshDir("../meshes") {}
+        m_accel(0), m_progress(0), m_gpus(1), m_denoise(0), m_aov(0), m_pass(16), m_ao(0), m_tune(0.), m_adaptive(-1.), m_aoDist(0.), m_aperture(0.), m_focus(0.), m_outputFilename("output.ppm"), m_scene("cubes"), m_meshDir("../meshes") {}
   virtual ~CommandLine() {}
 
   size_t width() const { return m_width; }
@@ -41,6 +41,8 @@ class CommandLine {
   size_t pass() const { return m_pass; }
   size_t ao() const { return m_ao; }
   double aoDist() const { return m_aoDist; }
+  double aperture() const { return m_aperture; }
+  double focus() const { return m_focus; }
   size_t gpus() const { return m_gpus; }
   const std::string& devices() const { return m_devices; }
   const std::string& scene() const { return m_scene; }
@@ -63,6 +65,8 @@ class CommandLine {
                  "<output stem>_spp.ppm>][-pass <samples per adaptive pass (default 16; -N must be a multiple)>]"
                  "[-ao <N: also write <output stem>_ao.ppm, the ambient occlusion of N rays per primary hit (1..256)>]"
                  "[-aodist <D: occluders count up to distance D in scene units (default 0 = unbounded)>]"
+                 "[-aperture <A: render through a thin lens of radius A in scene units (depth of field; default 0 = pinhole)>]"
+                 "[-focus <D: distance of the plane of focus along the optical axis; required with -aperture>]"
               << std::endl;
   }
 
@@ -99,6 +103,8 @@ class CommandLine {
       else if (flag == "-pass") m_pass = std::atoi(value);
       else if (flag == "-ao") m_ao = std::atoi(value);
       else if (flag == "-aodist") m_aoDist = std::atof(value);
+      else if (flag == "-aperture") m_aperture = std::atof(value);
+      else if (flag == "-focus") m_focus = std::atof(value);
       else throw std::runtime_error("Unknown argument <" + flag + ">");
     }
     if (m_mode != 0 && m_mode != 1) m_mode = 0;
@@ -114,6 +120,6 @@ class CommandLine {
 
  private:
   size_t m_width, m_height, m_numRays, m_mode, m_numPhotons, m_k, m_seed, m_gpu, m_accel, m_progress, m_gpus, m_denoise, m_aov, m_pass, m_ao;
-  double m_tune, m_adaptive, m_aoDist;
+  double m_tune, m_adaptive, m_aoDist, m_aperture, m_focus;
   std::string m_outputFilename, m_scene, m_meshDir, m_devices;
 };

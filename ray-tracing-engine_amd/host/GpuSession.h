@@ -83,6 +83,8 @@ struct GpuSettings {
   unsigned pass = 16;     // samples per adaptive pass (the frame's spp is the per-pixel maximum, a multiple of it)
   unsigned ao = 0;        // > 0: also the ambient occlusion of this many rays per primary hit (Renderer::ao(); single device only)
   double aoDistance = 0.; // ... with occluders up to this distance in scene units (0 = unbounded)
+  double aperture = 0.;   // > 0: the frame through a thin lens of this radius (rt_render_lens; single device, no photons, not adaptive)
+  double focus = 0.;      // ... focused at this distance along the optical axis
   std::vector<int> devices;  // more than one entry: Renderer::render tile-shards the frame over them (rt_group)
   static GpuSettings& get() {
     static GpuSettings s;

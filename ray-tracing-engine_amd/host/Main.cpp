@@ -33,6 +33,8 @@ int main(int argc, char** argv) {
   GpuSettings::get().pass = static_cast<unsigned>(args.pass());
   GpuSettings::get().ao = static_cast<unsigned>(args.ao());
   GpuSettings::get().aoDistance = args.aoDist();
+  GpuSettings::get().aperture = args.aperture();
+  GpuSettings::get().focus = args.focus();
   // -gpus N: devices gpu..gpu+N-1; -devices a,b,c: an explicit list (may repeat a device:
   // rehearsal of the N-rank flow on one GPU)
   if (!args.devices().empty()) {
@@ -64,6 +66,20 @@ int main(int argc, char** argv) {
   if (!(args.aoDist() >= 0.) || !(args.aoDist() < 3.0e38)) {
     std::cerr << "error: -aodist must be a finite distance >= 0 (0 = unbounded)" << std::endl;
     return 1;
+  }
+  if (!(args.aperture() >= 0.) || !(args.aperture() < 3.0e38)) {
+    std::cerr << "error: -aperture must be a finite lens radius >= 0 (0 = pinhole)" << std::endl;
+    return 1;
+  }
+  if (args.aperture() > 0.) {
+    if (!(args.focus() > 0.) || !(args.focus() < 3.0e38)) {
+      std::cerr << "error: -aperture needs -focus, a finite distance > 0" << std::endl;
+      return 1;
+    }
+    if (GpuSettings::get().devices.size() > 1 || args.numPhotons() > 0 || args.adaptive() >= 0.) {
+      std::cerr << "error: -aperture runs on one GPU, without -p and without -adaptive" << std::endl;
+      return 1;
+    }
   }
   if (args.adaptive() >= 0.) {
     if (GpuSettings::get().devices.size() > 1) {

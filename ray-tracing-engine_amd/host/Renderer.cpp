@@ -112,6 +112,21 @@ inline void Renderer::render(Image& image) {
               << maxSpp << ")" << std::endl;
     std::cout << "Raytracing... [" << std::string(50, '#') << "] 100%" << std::endl;
     image = result;
+  } else if (p.spp > 0 && GpuSettings::get().aperture > 0.) {
+    // -aperture A -focus D (extension): the frame through a thin lens (rt_render_lens), in one launch; update.ppm is
+    // written once.  Without -aperture this branch is not taken and the path below is unchanged.
+    if (p.use_photons) throw std::runtime_error("-aperture does not shade from the photon map (not with -p)");
+    rt_lens lens = {};
+    lens.model = RT_LENS_THIN;
+    lens.aperture = static_cast<float>(GpuSettings::get().aperture);
+    lens.focus_distance = static_cast<float>(GpuSettings::get().focus);
+    rt_stats st = {};
+    GpuSession::check(rt_render_lens(ctx0, &p, &lens, image.data(), result.data(), nullptr, &st), "rt_render_lens");
+    m_stats = st;
+    result.savePPM("update.ppm");
+    std::cout << "Raytracing through a lens of radius " << lens.aperture << " focused at " << lens.focus_distance << "... ["
+              << std::string(50, '#') << "] 100%" << std::endl;
+    image = result;
   } else if (p.spp > 0) {
     // The reference re-saves update.ppm after EVERY pass (Renderer.cpp:261-269).  Here a
     // "pass" is a sample range of one launch; GpuSettings::progress = P > 0 renders P

@@ -19,6 +19,7 @@ RT_OK = 0
 MODE_RAY, MODE_PATH = 0, 1
 RNG_LEGACY, RNG_PIXEL = 0, 1
 ACCEL_BVH, ACCEL_BRUTE = 0, 1
+LENS_THIN = 0
 BVH_AUTO, BVH_DEVICE, BVH_HYBRID, BVH_HOST = 0, 1, 2, 3
 TRACE_CLOSEST, TRACE_ANY = 0, 1
 (UNIT_ASIN, UNIT_SINF, UNIT_COSF, UNIT_STREAM_SEED, UNIT_TRIANGLE, UNIT_BSDF, UNIT_RAY_AT, UNIT_LIGHT_EVAL,
@@ -175,6 +176,12 @@ class RayBatch(C.Structure):
     pointers for rt_render_rays, device pointers for rt_render_rays_device."""
     _fields_ = [("n", C.c_uint32), ("reserved0", C.c_uint32), ("rays", C.c_void_p), ("stream_index", C.c_void_p),
                 ("reserved", C.c_uint32 * 6)]
+
+
+class Lens(C.Structure):
+    """rt_lens: the thin lens of rt_render_lens — its radius (0 = pinhole) and the distance of the plane of focus along
+    the optical axis."""
+    _fields_ = [("model", C.c_uint32), ("aperture", C.c_float), ("focus_distance", C.c_float), ("reserved", C.c_uint32 * 5)]
 
 
 class DenoiseParams(C.Structure):
@@ -374,7 +381,7 @@ AMD_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_create", "rt_destroy", "rt
                "rt_temporal_accumulate_device", "rt_svgf", "rt_svgf_device", "rt_bvh_quality_get", "rt_rebuild",
                "rt_render_aov_views", "rt_render_aov_views_device", "rt_render_motion_views", "rt_render_motion_views_device",
                "rt_denoise_batch", "rt_denoise_batch_device", "rt_render_ao", "rt_render_ao_device", "rt_render_rays",
-               "rt_render_rays_device"]
+               "rt_render_rays_device", "rt_render_lens", "rt_render_lens_device"]
 HOST_SYMBOLS = ["rt_host_scene_build", "rt_host_scene_desc", "rt_host_scene_free", "rt_host_last_error",
                 "rt_host_fill_background", "rt_host_save_ppm", "rt_host_kd_order", "rt_host_light_basis"]
 
@@ -393,6 +400,14 @@ def make_params(width, height, spp, mode=MODE_PATH, seed=1, accel=ACCEL_BVH, max
     p.reserved[1] = 1 if no_pool else 0  # schedule only: sequential shading instead of the wave's ray pool
     p.reserved[2] = 1 if wavefront else 0  # schedule only: the queue-based integrator
     return p
+
+
+def make_lens(aperture, focus_distance):
+    """An rt_lens: a thin lens of radius `aperture` (scene units; 0 = pinhole) focused at `focus_distance` along the
+    optical axis."""
+    l = Lens()
+    l.model, l.aperture, l.focus_distance = LENS_THIN, aperture, focus_distance
+    return l
 
 
 def amd():
@@ -460,6 +475,10 @@ def amd():
         L.rt_render_rays.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(RayBatch), C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.POINTER(Stats)]
         L.rt_render_rays_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(RayBatch), C.c_void_p, C.c_void_p,
+                                            C.POINTER(Stats)]
+        L.rt_render_lens.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Lens), C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.POINTER(Stats)]
+        L.rt_render_lens_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Lens), C.c_void_p, C.c_void_p,
                                             C.POINTER(Stats)]
         L.rt_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.POINTER(Aov), C.c_void_p]
         L.rt_render_adaptive.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(AdaptiveParams), C.c_void_p, C.c_void_p,
@@ -920,6 +939,24 @@ class Context:
         b.n, b.rays, b.stream_index = n, d_rays, d_stream_index or None
         st = Stats() if stats else None
         _check(amd().rt_render_rays_device(self._h, C.byref(params), C.byref(b), C.c_void_p(d_accum), C.c_void_p(stream or None),
+                                           C.byref(st) if stats else None))
+        return st
+
+    def render_lens(self, params, lens, bg=None, want_accum=True):
+        """rt_render_lens: the frame through the thin lens `lens` (make_lens); returns (out or None without bg, accum or
+        None, stats) as render does."""
+        w, h = params.width, params.height
+        out = np.empty((h, w, 3), np.float32) if bg is not None else None
+        acc = np.empty((h, w, 4), np.float32) if want_accum else None
+        st = Stats()
+        bgc = None if bg is None else np.ascontiguousarray(bg, np.float32)
+        _check(amd().rt_render_lens(self._h, C.byref(params), C.byref(lens), _ptr(bgc), _ptr(out), _ptr(acc), C.byref(st)))
+        return out, acc, st
+
+    def render_lens_device(self, params, lens, d_accum, stream=0, stats=False):
+        """rt_render_lens_device: accumulate into the caller-zeroed device d_accum [h][w][4] on `stream`; sample ranges chain."""
+        st = Stats() if stats else None
+        _check(amd().rt_render_lens_device(self._h, C.byref(params), C.byref(lens), C.c_void_p(d_accum), C.c_void_p(stream or None),
                                            C.byref(st) if stats else None))
         return st
 
