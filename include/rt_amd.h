@@ -34,6 +34,8 @@
  *                                  cameras of any kind (+ _device form)
  *   rt_render_lens              <- (no counterpart) the frame through a thin lens: depth of field, one lens sample
  *                                  per pixel sample (+ _device form)
+ *   rt_render_shutter           <- (no counterpart) the frame under an open shutter while the camera moves: one time
+ *                                  per pixel sample, with or without the lens (+ _device form)
  *   rt_render_aov_views / rt_render_motion_views / rt_denoise_batch <- (no counterpart) the AOVs, motion vectors and
  *                                  denoised frames of those views, one launch each (+ _device forms)
  *   rt_trace                    <- RayTracer::rayTrace (RayTracer.h:27-53) test hook
@@ -48,10 +50,12 @@
  * no gfx950 device is usable.
  *
  * Stream order of the `_device` forms (tests/test_gpu_stream_order.py issues every one of them on a
- * non-blocking stream that is still busy, back to back; rt_render_lens_device: tests/test_gpu_lens.py):
+ * non-blocking stream that is still busy, back to back; rt_render_lens_device: tests/test_gpu_lens.py;
+ * rt_render_shutter_device: tests/test_gpu_shutter.py):
  *   ASYNCHRONOUS — everything the call does is queued on `stream`, device inputs are read and outputs
  *   written in stream order, and the call returns without waiting for the stream:
- *     rt_render_device, rt_render_views_device, rt_render_rays_device and rt_render_lens_device with stats == NULL;
+ *     rt_render_device, rt_render_views_device, rt_render_rays_device, rt_render_shutter_device and
+ *     rt_render_lens_device with stats == NULL;
  *     rt_resolve_device;
  *     rt_render_aov_device, rt_render_ao_device, rt_render_motion_device; rt_temporal_accumulate_device,
  *     rt_svgf_device, rt_denoise_device, rt_denoise_batch_device; rt_render_aov_views_device,
@@ -62,7 +66,8 @@
  *     filters; a larger wavefront batch) frees the old block, and hipFree waits for the device; and the fifth
  *     multi-view call in a row waits for the upload of the first (four pinned staging copies).
  *   SYNCHRONISE `stream`, and only it, before they return, because the host reads a result back:
- *     rt_render_device, rt_render_views_device, rt_render_rays_device, rt_render_lens_device with stats != NULL;
+ *     rt_render_device, rt_render_views_device, rt_render_rays_device, rt_render_shutter_device,
+ *     rt_render_lens_device with stats != NULL;
  *     rt_render_adaptive_device (every pass); rt_update_vertices_device and rt_update_transforms (twice);
  *     the three multi-view forms when a view lies far enough out to need a wider box padding (a refit).
  *   HOST forms (rt_render, rt_render_aov, rt_denoise, rt_update, rt_trace, rt_knn, rt_bvh_quality_get, rt_rebuild,
@@ -607,6 +612,68 @@ int rt_render_lens(rt_ctx* ctx, const rt_params* p, const rt_lens* lens, const f
  * does: sample ranges chain.  p and lens are copied before the call returns; the host waits only to read stats back. */
 int rt_render_lens_device(rt_ctx* ctx, const rt_params* p, const rt_lens* lens, void* d_accum, void* stream,
                           rt_stats* stats);
+
+/* ---- the frame under an open shutter: camera motion blur ----------------------------------------------
+ * rt_render_shutter renders the frame p describes as rt_render does, except that every SAMPLE draws a time of its own in
+ * the shutter interval and sees the camera of that time: the context's camera A when the move begins (time 0),
+ * camera_close B when it ends (time 1), every one of the twelve components interpolated linearly between them.  With
+ * aperture > 0 the thin lens of rt_render_lens sits on that moving camera.  Geometry does not move.
+ *
+ * Host-derived constants, computed once per call (A, B: twelve float32 components each, position, lower_left,
+ * horizontal, vertical):
+ *   D = B - A per component in float32;
+ *   with aperture > 0: fs0 and fs1 by rt_render_lens' fs rule (the plane distance in float64, focus_distance over it
+ *   rounded to float32) for A and for B, and dfs = fs1 - fs0 in float32.
+ * Sample i of pixel (x, y), pix = y * width + x, all in float32, nothing fused:
+ *   1. g is seeded with rt_stream_seed(seed, RT_STREAM_PIXEL, pix, i); jitter_sample(g, i, spp) gives (cu, cv) exactly
+ *      as the frame forms them.
+ *   2. e is seeded with rt_stream_seed(seed, RT_STREAM_SHUTTER, pix, i); t = e.uniformF(open, close), one draw
+ *      (canonF() * (close - open) + open).
+ *   3. C(t): every component c is A_c + (t * D_c), the product, then the sum; pos(t), ll(t), H(t), V(t) are its parts.
+ *   4. aperture == 0: the ray is (pos(t), unit3(((ll(t) + cu H(t)) + cv V(t)) - pos(t))), with the division and the
+ *      square root, never the short reciprocal forms (the operand bounds rt_create proved hold for A only).
+ *   5. aperture > 0:
+ *        Hu = unit3(H(t)), Vu = unit3(V(t)) (division and square root);  fs = fs0 + (t * dfs);
+ *        then steps 3 and 4 of the rt_render_lens contract over C(t) with these Hu, Vu and fs: q, F, the lens point
+ *        (lx, ly) from rt_stream_seed(seed, RT_STREAM_LENS, pix, i) as there, o' and the ray (o', unit3(F - o')).
+ *   6. From the primary cast on the sample is the frame's, and g is where the frame's stream is.
+ * Guarantees:
+ *   - G1, rows: what sample i adds to pixel pix is, bit for bit, row pix of rt_render_rays for that sample's (o, F - o)
+ *     — at aperture 0 (pos(t), ((ll(t) + cu H(t)) + cv V(t)) - pos(t)) — with stream_index = pix, spp_begin = i,
+ *     spp_count = 1.
+ *   - G2, still shutter: open == close == s and aperture == 0: accum, out and both ray counts are bit-identical to
+ *     rt_render on a context whose camera rt_update set to C(s), C(s) computed by step 3.  This holds for cameras A, B
+ *     with no -0 component (A_c + 0 * D_c turns a -0 into +0).
+ *   - G3, lens at rest: open == close == 0 and aperture > 0: bit-identical to rt_render_lens with the same aperture and
+ *     focus_distance on the same context (under the same condition on A).
+ *   - G4, schedule: sample ranges, reserved[0] (lanes per pixel) and reserved[1] bit 0 (no pool) change the schedule,
+ *     never the bits.
+ * RT_NODES_Q8 contexts walk their resident 32-byte records.  The call changes nothing in the context.  Stats are a
+ * frame's.  The frame runs on the one-wave-per-workgroup kernel family of rt_render (no persistent instances).
+ * Validation comes first and a rejected call writes nothing; what the arguments alone decide is answered before the
+ * device is asked for, and the checks that read the context's camera come last.  RT_ERR_INVALID: a null ctx, p or
+ * shutter; host form: neither out_rgb nor accum_out, or out_rgb without background_rgb; device form: a null d_accum;
+ * non-zero reserved words; a non-finite component of camera_close; open or close not finite or outside
+ * 0 <= open <= close <= 1; a negative or non-finite aperture; with aperture > 0 a non-finite or non-positive
+ * focus_distance; every check rt_render applies to p.  RT_ERR_UNSUPPORTED: world > 1, use_photons, the wavefront
+ * integrator (reserved[2] bit 0), the legacy RNG.  Then, reading the camera, RT_ERR_INVALID: the origin bound: nextafterf(max_c max(|posA_c|, |posB_c|), +inf) + 2 aperture above the context's origin
+ * bound (the interpolation may overshoot an end point by one rounding); an H or V that cannot be normalised at either
+ * end, or that turns by 90 degrees or more — in float64, dot(H_A, H_B) <= 0 or dot(V_A, V_B) <= 0: an interpolated axis
+ * could then vanish; with aperture > 0 an fs0 or fs1 that is not finite and > 0.                                        */
+typedef struct rt_shutter {
+  rt_camera camera_close;  /* the camera when the shutter closes; the context's camera is the one when it opens */
+  float open, close;       /* the exposure, as fractions of the move: finite, 0 <= open <= close <= 1            */
+  float aperture;          /* thin-lens radius, 0 = pinhole (rt_lens.aperture's rules)                           */
+  float focus_distance;    /* as rt_lens; ignored when aperture == 0                                             */
+  uint32_t reserved[4];    /* zero */
+} rt_shutter;
+/* buffers as rt_render's */
+int rt_render_shutter(rt_ctx* ctx, const rt_params* p, const rt_shutter* shutter, const float* background_rgb,
+                      float* out_rgb, float* accum_out, rt_stats* stats);
+/* Accumulate into caller-zeroed DEVICE d_accum [h][w][4] on `stream` (a hipStream_t, may be NULL), as rt_render_device
+ * does: sample ranges chain.  p and shutter are copied before the call returns; the host waits only to read stats back. */
+int rt_render_shutter_device(rt_ctx* ctx, const rt_params* p, const rt_shutter* shutter, void* d_accum, void* stream,
+                             rt_stats* stats);
 
 /* ---- motion vectors and temporal accumulation (DESIGN.md "Motion vectors and temporal accumulation") ----------------
  * Two stateless calls for animated frames.  The library keeps nothing between frames: the caller hands in last frame's

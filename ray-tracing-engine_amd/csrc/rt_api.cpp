@@ -652,10 +652,17 @@ struct TileList {
   const rtk::ViewRec* views = nullptr;
 };
 
+// What forms a frame's primary rays in place of camera_ray, if anything: the thin lens of rt_render_lens or the open
+// shutter of rt_render_shutter, at most one of them (their callers have refused photons and the wavefront bit).
+struct FrameGen {
+  const rtk::LensRec* lens = nullptr;
+  const rtk::ShutterRec* shutter = nullptr;
+};
+
 // Launch the integrate kernel for p on `stream`, bracketed by an event pair.  own: render those wave tiles only.
-// lens: the frame through a thin lens (rt_render_lens; the caller has refused photons and the wavefront bit).
+// gen: the frame through a thin lens or under an open shutter.
 int launch_frame(rt_ctx* c, const rt_params* p, float4* dAccum, hipStream_t stream, int* evIndex,
-                 const TileList* own = nullptr, const rtk::LensRec* lens = nullptr) {
+                 const TileList* own = nullptr, const FrameGen& gen = FrameGen()) {
   const SampleRange sr = sample_range(*p);
   const uint32_t sshift = own ? own->sshift : choose_sshift(c, p, sr.count);
   int rc = own ? RT_OK : ensure_tiles(c, p, sshift, stream);
@@ -690,10 +697,14 @@ int launch_frame(rt_ctx* c, const rt_params* p, float4* dAccum, hipStream_t stre
   rtk::WfArgs W{};
   if (wavefront && (rc = wavefront_args(c, p, A, sr.count, stream, &W)) != RT_OK) return rc;
   return timed_launch(c, stream, evIndex, [&] {
-    if (lens) {
-      hipError_t he = rtk::launch_render_lens(p->accel == RT_ACCEL_BRUTE, p->collect_stats != 0, c->S, A, *lens, dAccum,
+    if (gen.lens) {
+      hipError_t he = rtk::launch_render_lens(p->accel == RT_ACCEL_BRUTE, p->collect_stats != 0, c->S, A, *gen.lens, dAccum,
                                               c->dCounters.get(), stream);
       if (he != hipSuccess) return fail(RT_ERR_HIP, "lens render launch failed: %s", hipGetErrorString(he));
+    } else if (gen.shutter) {
+      hipError_t he = rtk::launch_render_shutter(p->accel == RT_ACCEL_BRUTE, p->collect_stats != 0, c->S, A, *gen.shutter,
+                                                 dAccum, c->dCounters.get(), stream);
+      if (he != hipSuccess) return fail(RT_ERR_HIP, "shutter render launch failed: %s", hipGetErrorString(he));
     } else if (!wavefront) {
       hipError_t he = rtk::launch_render(p->accel == RT_ACCEL_BRUTE, p->use_photons != 0, p->collect_stats != 0, c->S, A,
                                          dAccum, c->dCounters.get(), stream);
@@ -1091,13 +1102,14 @@ int stage_resolve(Staging* st, const float* bg, float* out_rgb, const float4* dA
   return RT_OK;
 }
 
-// The frame of a checked p into d_accum on `stream`, with a frame's stats: rt_render_device, and (lens) rt_render_lens_device.
-int frame_device(rt_ctx* c, const rt_params* p, const rtk::LensRec* lens, void* d_accum, void* stream, rt_stats* stats) {
+// The frame of a checked p into d_accum on `stream`, with a frame's stats: rt_render_device, and (gen) rt_render_lens_device
+// and rt_render_shutter_device.
+int frame_device(rt_ctx* c, const rt_params* p, const FrameGen& gen, void* d_accum, void* stream, rt_stats* stats) {
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (stats) HIP_TRY(hipMemsetAsync(c->dCounters.get(), 0, RTK_CNT_COUNT * sizeof(unsigned long long), s));
   int e = 0;
-  const int rc = launch_frame(c, p, static_cast<float4*>(d_accum), s, &e, nullptr, lens);
+  const int rc = launch_frame(c, p, static_cast<float4*>(d_accum), s, &e, nullptr, gen);
   if (rc != RT_OK) return rc;
   if (!stats) return RT_OK;
   // samples of the pixels this rank owns: its granules, clipped to the image
@@ -1176,7 +1188,7 @@ int rt_render_device(rt_ctx* c, const rt_params* p, void* d_accum, void* stream,
   if (!c || !d_accum) return fail(RT_ERR_INVALID, "ctx/d_accum is null");
   const int rc = check_params(c, p);
   if (rc != RT_OK) return rc;
-  return frame_device(c, p, nullptr, d_accum, stream, stats);
+  return frame_device(c, p, FrameGen(), d_accum, stream, stats);
 }
 
 int rt_resolve_device(rt_ctx* c, uint32_t width, uint32_t height, uint32_t spp, const void* d_accum,
@@ -3345,6 +3357,23 @@ bool unit3_host(const float* a, float* u) {
   return true;
 }
 
+// The fs rule of rt_amd.h for one camera: the distance of the image plane along the optical axis in float64 (the header
+// states the order), focus_distance over it rounded to float32; RT_ERR_INVALID unless that is finite and > 0.
+int focus_scale(const rt_camera& cam, float focus_distance, float* fs) {
+  double cc[3], H[3], V[3];
+  for (int k = 0; k < 3; ++k) {
+    H[k] = cam.horizontal[k], V[k] = cam.vertical[k];
+    cc[k] = (((double)cam.lower_left[k] + 0.5 * H[k]) + 0.5 * V[k]) - (double)cam.position[k];
+  }
+  const double n[3] = {H[1] * V[2] - H[2] * V[1], H[2] * V[0] - H[0] * V[2], H[0] * V[1] - H[1] * V[0]};
+  const double cn = (cc[0] * n[0] + cc[1] * n[1]) + cc[2] * n[2], nn = (n[0] * n[0] + n[1] * n[1]) + n[2] * n[2];
+  const double plane = std::fabs(cn) / std::sqrt(nn);
+  *fs = (float)((double)focus_distance / plane);
+  if (!(*fs > 0.f) || !std::isfinite(*fs))
+    return fail(RT_ERR_INVALID, "focus_distance %g over the image plane's distance %g is not a finite positive float", focus_distance, plane);
+  return RT_OK;
+}
+
 // Everything both forms of rt_render_lens check, in the header's order, and the record the kernels take.  outputs: what is
 // wrong with the form's own buffers, or null.  What can be told from the arguments alone is answered before the device is
 // asked for, and the camera is read last: a context exists only where a device does.
@@ -3375,18 +3404,56 @@ int lens_checks(const rt_ctx* c, const rt_params* p, const rt_lens* l, const cha
   if (!open) return RT_OK;  // (the frame's own camera_ray: fs is neither computed nor checked)
   if (!unit3_host(cam.horizontal, R->hu) || !unit3_host(cam.vertical, R->vu))
     return fail(RT_ERR_INVALID, "the camera's horizontal or vertical axis cannot be normalised");
-  // the distance of the image plane along the optical axis, in float64 (rt_amd.h states the order)
-  double cc[3], H[3], V[3];
-  for (int k = 0; k < 3; ++k) {
-    H[k] = cam.horizontal[k], V[k] = cam.vertical[k];
-    cc[k] = (((double)cam.lower_left[k] + 0.5 * H[k]) + 0.5 * V[k]) - (double)cam.position[k];
-  }
-  const double n[3] = {H[1] * V[2] - H[2] * V[1], H[2] * V[0] - H[0] * V[2], H[0] * V[1] - H[1] * V[0]};
-  const double cn = (cc[0] * n[0] + cc[1] * n[1]) + cc[2] * n[2], nn = (n[0] * n[0] + n[1] * n[1]) + n[2] * n[2];
-  const double plane = std::fabs(cn) / std::sqrt(nn);
-  R->fs = (float)((double)l->focus_distance / plane);
-  if (!(R->fs > 0.f) || !std::isfinite(R->fs))
-    return fail(RT_ERR_INVALID, "focus_distance %g over the image plane's distance %g is not a finite positive float", l->focus_distance, plane);
+  return focus_scale(cam, l->focus_distance, &R->fs);
+}
+
+// max_c |a_c| of a 3-vector
+float max_abs3(const float* a) { return std::max(std::fabs(a[0]), std::max(std::fabs(a[1]), std::fabs(a[2]))); }
+
+// Everything both forms of rt_render_shutter check, in the header's order, and the record the kernels take (lens_checks'
+// shape: the arguments alone first, then the device, the context's camera last).
+int shutter_checks(const rt_ctx* c, const rt_params* p, const rt_shutter* s, const char* outputs, rtk::ShutterRec* R) {
+  if (!c || !p || !s) return fail(RT_ERR_INVALID, "ctx/params/shutter is null");
+  if (outputs) return fail(RT_ERR_INVALID, "%s", outputs);
+  if (any_set(s->reserved, 4)) return fail(RT_ERR_INVALID, "rt_shutter: reserved words must be zero");
+  const rt_camera& B = s->camera_close;
+  const float* b = reinterpret_cast<const float*>(&B);  // (the twelve components: rt_camera is four float[3])
+  static_assert(sizeof(rt_camera) == 12 * sizeof(float), "rt_camera is twelve floats");
+  for (int k = 0; k < 12; ++k)
+    if (!std::isfinite(b[k])) return fail(RT_ERR_INVALID, "camera_close: component %d is not finite", k);
+  if (!std::isfinite(s->open) || !std::isfinite(s->close) || !(0.f <= s->open && s->open <= s->close && s->close <= 1.f))
+    return fail(RT_ERR_INVALID, "the exposure must be finite with 0 <= open <= close <= 1");
+  if (!(s->aperture >= 0.f) || !std::isfinite(s->aperture)) return fail(RT_ERR_INVALID, "aperture must be finite and >= 0");
+  const bool lens = s->aperture > 0.f;
+  if (lens && (!(s->focus_distance > 0.f) || !std::isfinite(s->focus_distance)))
+    return fail(RT_ERR_INVALID, "focus_distance must be finite and > 0");
+  int rc = check_params_shape(p);
+  if (rc != RT_OK) return rc;
+  if (p->world > 1) return fail(RT_ERR_UNSUPPORTED, "tile-sharded shutter frames (world %u) are not supported", p->world);
+  if (p->use_photons) return fail(RT_ERR_UNSUPPORTED, "shutter frames do not shade from the photon map");
+  if (p->reserved[2] & 1u) return fail(RT_ERR_UNSUPPORTED, "shutter frames do not run the wavefront integrator");
+  if ((rc = check_device_present()) != RT_OK) return rc;
+  if ((rc = check_not_broken(c)) != RT_OK) return rc;
+  const rt_camera& A = c->S.cam;
+  const float* a = reinterpret_cast<const float*>(&A);
+  *R = rtk::ShutterRec{};
+  for (int k = 0; k < 12; ++k) R->d[k] = b[k] - a[k];  // (finite: both ends are, and the context's camera lies within the scene's input bound)
+  R->open = s->open, R->close = s->close, R->aperture = s->aperture;
+  // pos(t) = posA + t D may pass an end point by one rounding: one float above the larger end covers every value
+  const float reach = std::nextafter(std::max(max_abs3(A.position), max_abs3(B.position)), INFINITY) + 2.f * s->aperture;
+  if (reach > c->bvh.originBound)
+    return fail(RT_ERR_INVALID, "the moving camera reaches %g from the origin, beyond the context's origin bound %g", reach, c->bvh.originBound);
+  float u[3];
+  if (!unit3_host(A.horizontal, u) || !unit3_host(A.vertical, u) || !unit3_host(B.horizontal, u) || !unit3_host(B.vertical, u))
+    return fail(RT_ERR_INVALID, "a horizontal or vertical axis of the context's camera or of camera_close cannot be normalised");
+  double hh = 0., vv = 0.;
+  for (int k = 0; k < 3; ++k) hh += (double)A.horizontal[k] * (double)B.horizontal[k], vv += (double)A.vertical[k] * (double)B.vertical[k];
+  if (!(hh > 0.) || !(vv > 0.))
+    return fail(RT_ERR_INVALID, "the camera's horizontal or vertical axis turns by 90 degrees or more between open and close: an interpolated axis could vanish");
+  if (!lens) return RT_OK;
+  float fs1;
+  if ((rc = focus_scale(A, s->focus_distance, &R->fs0)) != RT_OK || (rc = focus_scale(B, s->focus_distance, &fs1)) != RT_OK) return rc;
+  R->dfs = fs1 - R->fs0;
   return RT_OK;
 }
 
@@ -3398,7 +3465,7 @@ int rt_render_lens_device(rt_ctx* c, const rt_params* p, const rt_lens* l, void*
   rtk::LensRec R;
   const int rc = lens_checks(c, p, l, d_accum ? nullptr : "d_accum is null", &R);
   if (rc != RT_OK) return rc;
-  return frame_device(c, p, &R, d_accum, stream, stats);
+  return frame_device(c, p, FrameGen{&R, nullptr}, d_accum, stream, stats);
 }
 
 int rt_render_lens(rt_ctx* c, const rt_params* p, const rt_lens* l, const float* bg, float* out_rgb, float* accum_out, rt_stats* stats) {
@@ -3413,7 +3480,32 @@ int rt_render_lens(rt_ctx* c, const rt_params* p, const rt_lens* l, const float*
   float4* dAccum = st.zeroed<float4>(accum_out, npx);
   if (st.rc != RT_OK) return st.rc;
   rt_stats local;
-  if ((rc = frame_device(c, p, &R, dAccum, nullptr, stats ? stats : &local)) != RT_OK) return rc;
+  if ((rc = frame_device(c, p, FrameGen{&R, nullptr}, dAccum, nullptr, stats ? stats : &local)) != RT_OK) return rc;
+  if ((rc = stage_resolve(&st, bg, out_rgb, dAccum, 1, npx, p->spp)) != RT_OK) return rc;
+  return st.download();
+}
+
+// ---- the frame under an open shutter
+int rt_render_shutter_device(rt_ctx* c, const rt_params* p, const rt_shutter* sh, void* d_accum, void* stream, rt_stats* stats) {
+  rtk::ShutterRec R;
+  const int rc = shutter_checks(c, p, sh, d_accum ? nullptr : "d_accum is null", &R);
+  if (rc != RT_OK) return rc;
+  return frame_device(c, p, FrameGen{nullptr, &R}, d_accum, stream, stats);
+}
+
+int rt_render_shutter(rt_ctx* c, const rt_params* p, const rt_shutter* sh, const float* bg, float* out_rgb, float* accum_out, rt_stats* stats) {
+  rtk::ShutterRec R;
+  int rc = shutter_checks(c, p, sh, !out_rgb && !accum_out ? "neither out_rgb nor accum_out is given"
+                                    : out_rgb && !bg     ? "out_rgb requested without a background image"
+                                                         : nullptr, &R);
+  if (rc != RT_OK) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t npx = (size_t)p->width * p->height;
+  Staging st;
+  float4* dAccum = st.zeroed<float4>(accum_out, npx);
+  if (st.rc != RT_OK) return st.rc;
+  rt_stats local;
+  if ((rc = frame_device(c, p, FrameGen{nullptr, &R}, dAccum, nullptr, stats ? stats : &local)) != RT_OK) return rc;
   if ((rc = stage_resolve(&st, bg, out_rgb, dAccum, 1, npx, p->spp)) != RT_OK) return rc;
   return st.download();
 }

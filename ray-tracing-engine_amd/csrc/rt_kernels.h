@@ -159,6 +159,18 @@ struct LensRec {
 // place of camera_ray; A as launch_render takes it (tileView null)
 hipError_t launch_render_lens(bool brute_force, bool stats, const DevScene& S, const RenderArgs& A, const LensRec& R,
                               float4* accum, unsigned long long* counters, hipStream_t stream);
+// the frame under an open shutter (shutter_kernels.h, rt_render_shutter): the host-derived constants of rt_amd.h, by
+// value.  The camera of a sample is S.cam + t d, t drawn in [open, close]; aperture > 0 puts rt_render_lens' lens on it.
+struct ShutterRec {
+  float d[12];          // camera_close - the context's camera, component by component (position, lower_left, H, V)
+  float open, close;    // the exposure: t = uniformF(open, close)
+  float aperture;       // lens radius, 0 = pinhole (fs0 and dfs are then not read)
+  float fs0, dfs;       // fs of the context's camera, and fs of camera_close minus it
+};
+// launch_render_lens' six instances with the shutter generator in place of camera_ray; A as launch_render takes it
+// (tileView null)
+hipError_t launch_render_shutter(bool brute_force, bool stats, const DevScene& S, const RenderArgs& A, const ShutterRec& R,
+                                 float4* accum, unsigned long long* counters, hipStream_t stream);
 // First element of view j's slice of a per-view output with c floats or words per pixel (rt_render_aov_views,
 // rt_render_motion_views, rt_denoise_batch): formed in 64 bits — n w h may reach 2^31 - 1 and 3 x that is not 32-bit.
 __host__ __device__ inline size_t view_slice(uint32_t j, uint32_t width, uint32_t height, uint32_t c) {

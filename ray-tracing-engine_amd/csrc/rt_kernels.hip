@@ -213,6 +213,9 @@ constexpr int LT_VIEWS = 512;
 // A frame through a thin lens (rt_render_lens): render_tile takes a LensRec and, where its aperture is not zero, forms the
 // primary ray by lens_ray instead of camera_ray.  Only render_tile reads the bit; its own instances (lens_kernels.h).
 constexpr int LT_LENS = 1024;
+// A frame under an open shutter (rt_render_shutter): render_tile takes a ShutterRec and forms every sample's camera, then
+// its primary ray, by shutter_ray.  Only render_tile reads the bit; its own instances (shutter_kernels.h).
+constexpr int LT_SHUTTER = 2048;
 constexpr uint32_t kPrioMaxNodes = 65536;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(3))) u32x4* lds_u4_ptr;
@@ -1214,13 +1217,41 @@ RT_DEV void lens_ray(const rt_camera& c, const LensRec& R, uint32_t lensSeed, fl
   d = unit3(F - o);
 }
 
+// The primary ray of a sample under an open shutter (rt_amd.h, rt_render_shutter): the sample's time t from a stream of
+// its own, its camera c + t D in registers, then the dividing camera_ray on that camera or, with a lens, lens_ray with
+// the axes and the focus scale of that time.  Float32, nothing fused.  t, the camera and the engine die here.
+RT_DEV void shutter_ray(const rt_camera& c, const ShutterRec& R, uint32_t seed, uint32_t pix, uint32_t i, float u, float v,
+                        f3& o, f3& d) {
+  Rng e{rt_stream_seed(seed, RT_STREAM_SHUTTER, pix, i)};
+  const float t = e.uniformF(R.open, R.close);
+  rt_camera ct;
+  for (int k = 0; k < 3; ++k) {
+    ct.position[k] = c.position[k] + t * R.d[k];
+    ct.lower_left[k] = c.lower_left[k] + t * R.d[3 + k];
+    ct.horizontal[k] = c.horizontal[k] + t * R.d[6 + k];
+    ct.vertical[k] = c.vertical[k] + t * R.d[9 + k];
+  }
+  // (wave-uniform: the record is a kernel argument)
+  if (R.aperture > 0.f) {
+    LensRec l;
+    l.aperture = R.aperture, l.fs = R.fs0 + t * R.dfs;
+    const f3 hu = unit3(ld(ct.horizontal)), vu = unit3(ld(ct.vertical));
+    l.hu[0] = hu.x, l.hu[1] = hu.y, l.hu[2] = hu.z;
+    l.vu[0] = vu.x, l.vu[1] = vu.y, l.vu[2] = vu.z;
+    lens_ray(ct, l, rt_stream_seed(seed, RT_STREAM_LENS, pix, i), u, v, o, d);
+  } else camera_ray<false>(ct, u, v, o, d);
+}
+
 template <bool BRUTE, bool PHOTON, bool POOLED, bool STATS, int LTV, class HP = Heap>
 RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restrict__ accum, const Lds& L, uint32_t* pool,
-                        float* ex, uint32_t wave, LaneStats& st, const LensRec* lens = nullptr) {
-  constexpr int LT = LTV & ~(LT_VIEWS | LT_LENS);
+                        float* ex, uint32_t wave, LaneStats& st, const LensRec* lens = nullptr,
+                        const ShutterRec* shutter = nullptr) {
+  constexpr int LT = LTV & ~(LT_VIEWS | LT_LENS | LT_SHUTTER);
   constexpr bool VIEWS = (LTV & LT_VIEWS) != 0;
   constexpr bool LENS = (LTV & LT_LENS) != 0;
+  constexpr bool SHUTTER = (LTV & LT_SHUTTER) != 0;
   static_assert(!LENS || !VIEWS, "no multi-view lens frames");
+  static_assert(!SHUTTER || (!VIEWS && !LENS), "the shutter's lens is its own: LT_SHUTTER goes with neither LT_VIEWS nor LT_LENS");
   constexpr bool FR = (LT & LT_FASTDET) != 0;  // 1 / length by rtd::recip_fast (see rtd::unit3)
   const uint32_t lane = threadIdx.x & 63u;
   // lane = (pixel pl of the wave tile, sample slot sj): the wave integrates
@@ -1265,7 +1296,8 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
       // (wave-uniform: the record is a kernel argument)
       if (lens->aperture > 0.f) lens_ray(S.cam, *lens, rt_stream_seed(A.seed, RT_STREAM_LENS, pix, i), cu, cv, o, d);
       else camera_ray<FR>(S.cam, cu, cv, o, d);
-    } else camera_ray<FR>(S.cam, cu, cv, o, d);
+    } else if constexpr (SHUTTER) shutter_ray(S.cam, *shutter, A.seed, pix, i, cu, cv, o, d);
+    else camera_ray<FR>(S.cam, cu, cv, o, d);
     f3 c0 = mk(0.f, 0.f, 0.f), c1 = c0, c2 = c0;
     bool primary = true, alive = active;
     if constexpr (pooled) {
@@ -1571,6 +1603,9 @@ __global__ __launch_bounds__(1024, 8) void k_trace_stream(DevScene S, const floa
 
 // ---------------------------------------------------------------- thin-lens frames (rt_render_lens)
 #include "lens_kernels.h"
+
+// ---------------------------------------------------------------- open-shutter frames (rt_render_shutter)
+#include "shutter_kernels.h"
 
 // ---------------------------------------------------------------- frame assembly (multi-GPU)
 // A rank's owned 8x8-pixel granules, packed [granule][64 pixels] (row-major inside the

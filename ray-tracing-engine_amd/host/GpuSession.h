@@ -85,6 +85,8 @@ struct GpuSettings {
   double aoDistance = 0.; // ... with occluders up to this distance in scene units (0 = unbounded)
   double aperture = 0.;   // > 0: the frame through a thin lens of this radius (rt_render_lens; single device, no photons, not adaptive)
   double focus = 0.;      // ... focused at this distance along the optical axis
+  bool shutter = false;   // the frame under an open shutter (rt_render_shutter; single device, no photons, not adaptive) ...
+  float shutterMove[3] = {0.f, 0.f, 0.f};  // ... while the camera translates by this vector; -aperture / -focus put the lens on it
   std::vector<int> devices;  // more than one entry: Renderer::render tile-shards the frame over them (rt_group)
   static GpuSettings& get() {
     static GpuSettings s;

@@ -4,6 +4,8 @@
 // render, save the PPM, print the total time); the scene script itself lives in
 // ScenePresets.cpp so that tests and bench.py build the identical scene.
 #include <chrono>
+#include <cmath>
+#include <cstdio>
 #include <exception>
 #include <iostream>
 
@@ -80,6 +82,22 @@ int main(int argc, char** argv) {
       std::cerr << "error: -aperture runs on one GPU, without -p and without -adaptive" << std::endl;
       return 1;
     }
+  }
+  if (!args.shutter().empty()) {
+    // -shutter dx,dy,dz: three finite numbers and nothing else
+    double m[3];
+    char rest;
+    if (std::sscanf(args.shutter().c_str(), "%lf,%lf,%lf%c", &m[0], &m[1], &m[2], &rest) != 3 || !(std::fabs(m[0]) < 3.0e38) ||
+        !(std::fabs(m[1]) < 3.0e38) || !(std::fabs(m[2]) < 3.0e38)) {
+      std::cerr << "error: -shutter must be dx,dy,dz, three finite numbers (the camera's move while the shutter is open)" << std::endl;
+      return 1;
+    }
+    if (GpuSettings::get().devices.size() > 1 || args.numPhotons() > 0 || args.adaptive() >= 0.) {
+      std::cerr << "error: -shutter runs on one GPU, without -p and without -adaptive" << std::endl;
+      return 1;
+    }
+    GpuSettings::get().shutter = true;
+    for (int k = 0; k < 3; ++k) GpuSettings::get().shutterMove[k] = static_cast<float>(m[k]);
   }
   if (args.adaptive() >= 0.) {
     if (GpuSettings::get().devices.size() > 1) {

@@ -112,6 +112,29 @@ inline void Renderer::render(Image& image) {
               << maxSpp << ")" << std::endl;
     std::cout << "Raytracing... [" << std::string(50, '#') << "] 100%" << std::endl;
     image = result;
+  } else if (p.spp > 0 && GpuSettings::get().shutter) {
+    // -shutter dx,dy,dz (extension): the frame under a shutter that stays open while the camera translates by that
+    // vector (rt_render_shutter), in one launch; -aperture A -focus D put the thin lens on the moving camera.
+    // update.ppm is written once.  Without -shutter this branch is not taken.
+    if (p.use_photons) throw std::runtime_error("-shutter does not shade from the photon map (not with -p)");
+    rt_shutter sh = {};
+    sh.camera_close = single->flat().desc.camera;
+    for (int k = 0; k < 3; ++k) {
+      sh.camera_close.position[k] += GpuSettings::get().shutterMove[k];
+      sh.camera_close.lower_left[k] += GpuSettings::get().shutterMove[k];
+    }
+    sh.open = 0.f, sh.close = 1.f;
+    sh.aperture = static_cast<float>(GpuSettings::get().aperture);
+    sh.focus_distance = static_cast<float>(GpuSettings::get().focus);
+    rt_stats st = {};
+    GpuSession::check(rt_render_shutter(ctx0, &p, &sh, image.data(), result.data(), nullptr, &st), "rt_render_shutter");
+    m_stats = st;
+    result.savePPM("update.ppm");
+    std::cout << "Raytracing under an open shutter, the camera moving by (" << GpuSettings::get().shutterMove[0] << ", "
+              << GpuSettings::get().shutterMove[1] << ", " << GpuSettings::get().shutterMove[2] << ")";
+    if (sh.aperture > 0.f) std::cout << ", through a lens of radius " << sh.aperture << " focused at " << sh.focus_distance;
+    std::cout << "... [" << std::string(50, '#') << "] 100%" << std::endl;
+    image = result;
   } else if (p.spp > 0 && GpuSettings::get().aperture > 0.) {
     // -aperture A -focus D (extension): the frame through a thin lens (rt_render_lens), in one launch; update.ppm is
     // written once.  Without -aperture this branch is not taken and the path below is unchanged.

@@ -184,6 +184,13 @@ class Lens(C.Structure):
     _fields_ = [("model", C.c_uint32), ("aperture", C.c_float), ("focus_distance", C.c_float), ("reserved", C.c_uint32 * 5)]
 
 
+class Shutter(C.Structure):
+    """rt_shutter: the open shutter of rt_render_shutter — the camera when it closes (the context's is the one when it
+    opens), the exposure as fractions of the move, and the thin lens on the moving camera (aperture 0 = pinhole)."""
+    _fields_ = [("camera_close", Camera), ("open", C.c_float), ("close", C.c_float), ("aperture", C.c_float),
+                ("focus_distance", C.c_float), ("reserved", C.c_uint32 * 4)]
+
+
 class DenoiseParams(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("iterations", C.c_uint32), ("sigma_color", C.c_float),
                 ("sigma_normal", C.c_float), ("sigma_position", C.c_float), ("reserved", C.c_uint32 * 6)]
@@ -381,7 +388,8 @@ AMD_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_create", "rt_destroy", "rt
                "rt_temporal_accumulate_device", "rt_svgf", "rt_svgf_device", "rt_bvh_quality_get", "rt_rebuild",
                "rt_render_aov_views", "rt_render_aov_views_device", "rt_render_motion_views", "rt_render_motion_views_device",
                "rt_denoise_batch", "rt_denoise_batch_device", "rt_render_ao", "rt_render_ao_device", "rt_render_rays",
-               "rt_render_rays_device", "rt_render_lens", "rt_render_lens_device"]
+               "rt_render_rays_device", "rt_render_lens", "rt_render_lens_device", "rt_render_shutter",
+               "rt_render_shutter_device"]
 HOST_SYMBOLS = ["rt_host_scene_build", "rt_host_scene_desc", "rt_host_scene_free", "rt_host_last_error",
                 "rt_host_fill_background", "rt_host_save_ppm", "rt_host_kd_order", "rt_host_light_basis"]
 
@@ -408,6 +416,16 @@ def make_lens(aperture, focus_distance):
     l = Lens()
     l.model, l.aperture, l.focus_distance = LENS_THIN, aperture, focus_distance
     return l
+
+
+def make_shutter(camera_close, open=0.0, close=1.0, aperture=0.0, focus_distance=0.0):
+    """An rt_shutter: the camera moves from the context's to `camera_close` ([4][3]: position, lower_left, horizontal,
+    vertical) and the shutter is open over [open, close] of that move; aperture > 0 puts make_lens' lens on it."""
+    s = Shutter()
+    cam = np.ascontiguousarray(camera_close, np.float32).reshape(12)
+    C.memmove(C.byref(s.camera_close), cam.ctypes.data, 48)
+    s.open, s.close, s.aperture, s.focus_distance = open, close, aperture, focus_distance
+    return s
 
 
 def amd():
@@ -480,6 +498,10 @@ def amd():
                                      C.POINTER(Stats)]
         L.rt_render_lens_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Lens), C.c_void_p, C.c_void_p,
                                             C.POINTER(Stats)]
+        L.rt_render_shutter.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Shutter), C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.POINTER(Stats)]
+        L.rt_render_shutter_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Shutter), C.c_void_p, C.c_void_p,
+                                               C.POINTER(Stats)]
         L.rt_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.POINTER(Aov), C.c_void_p]
         L.rt_render_adaptive.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(AdaptiveParams), C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.POINTER(AdaptiveReport), C.POINTER(Stats)]
@@ -958,6 +980,24 @@ class Context:
         st = Stats() if stats else None
         _check(amd().rt_render_lens_device(self._h, C.byref(params), C.byref(lens), C.c_void_p(d_accum), C.c_void_p(stream or None),
                                            C.byref(st) if stats else None))
+        return st
+
+    def render_shutter(self, params, shutter, bg=None, want_accum=True):
+        """rt_render_shutter: the frame under the open shutter `shutter` (make_shutter) while the camera moves; returns
+        (out or None without bg, accum or None, stats) as render does."""
+        w, h = params.width, params.height
+        out = np.empty((h, w, 3), np.float32) if bg is not None else None
+        acc = np.empty((h, w, 4), np.float32) if want_accum else None
+        st = Stats()
+        bgc = None if bg is None else np.ascontiguousarray(bg, np.float32)
+        _check(amd().rt_render_shutter(self._h, C.byref(params), C.byref(shutter), _ptr(bgc), _ptr(out), _ptr(acc), C.byref(st)))
+        return out, acc, st
+
+    def render_shutter_device(self, params, shutter, d_accum, stream=0, stats=False):
+        """rt_render_shutter_device: accumulate into the caller-zeroed device d_accum [h][w][4] on `stream`; sample ranges chain."""
+        st = Stats() if stats else None
+        _check(amd().rt_render_shutter_device(self._h, C.byref(params), C.byref(shutter), C.c_void_p(d_accum), C.c_void_p(stream or None),
+                                              C.byref(st) if stats else None))
         return st
 
     @staticmethod
