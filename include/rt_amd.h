@@ -36,6 +36,8 @@
  *                                  per pixel sample (+ _device form)
  *   rt_render_shutter           <- (no counterpart) the frame under an open shutter while the camera moves: one time
  *                                  per pixel sample, with or without the lens (+ _device form)
+ *   rt_render_views_shutter / rt_render_adaptive_shutter <- (no counterpart) that shutter per view of a multi-view
+ *                                  frame, and in the passes of an adaptive frame (+ _device forms)
  *   rt_render_aov_views / rt_render_motion_views / rt_denoise_batch <- (no counterpart) the AOVs, motion vectors and
  *                                  denoised frames of those views, one launch each (+ _device forms)
  *   rt_trace                    <- RayTracer::rayTrace (RayTracer.h:27-53) test hook
@@ -54,8 +56,8 @@
  * rt_render_shutter_device: tests/test_gpu_shutter.py):
  *   ASYNCHRONOUS — everything the call does is queued on `stream`, device inputs are read and outputs
  *   written in stream order, and the call returns without waiting for the stream:
- *     rt_render_device, rt_render_views_device, rt_render_rays_device, rt_render_shutter_device and
- *     rt_render_lens_device with stats == NULL;
+ *     rt_render_device, rt_render_views_device, rt_render_rays_device, rt_render_shutter_device,
+ *     rt_render_views_shutter_device (tests/test_gpu_views_shutter.py) and rt_render_lens_device with stats == NULL;
  *     rt_resolve_device;
  *     rt_render_aov_device, rt_render_ao_device, rt_render_motion_device; rt_temporal_accumulate_device,
  *     rt_svgf_device, rt_denoise_device, rt_denoise_batch_device; rt_render_aov_views_device,
@@ -67,9 +69,10 @@
  *     multi-view call in a row waits for the upload of the first (four pinned staging copies).
  *   SYNCHRONISE `stream`, and only it, before they return, because the host reads a result back:
  *     rt_render_device, rt_render_views_device, rt_render_rays_device, rt_render_shutter_device,
- *     rt_render_lens_device with stats != NULL;
- *     rt_render_adaptive_device (every pass); rt_update_vertices_device and rt_update_transforms (twice);
- *     the three multi-view forms when a view lies far enough out to need a wider box padding (a refit).
+ *     rt_render_views_shutter_device, rt_render_lens_device with stats != NULL;
+ *     rt_render_adaptive_device and rt_render_adaptive_shutter_device (every pass); rt_update_vertices_device and
+ *     rt_update_transforms (twice);
+ *     the four multi-view forms when a view lies far enough out to need a wider box padding (a refit).
  *   HOST forms (rt_render, rt_render_aov, rt_denoise, rt_update, rt_trace, rt_knn, rt_bvh_quality_get, rt_rebuild,
  *     the photon calls ...) run on the NULL stream and return when their result is in host memory.  The null
  *     stream does not wait for a non-blocking stream: a host form must not follow an unfinished asynchronous call on
@@ -907,6 +910,70 @@ int rt_render_views(rt_ctx* ctx, const rt_params* p, const rt_views* v, const fl
  * call's upload of the view records. */
 int rt_render_views_device(rt_ctx* ctx, const rt_params* p, const rt_views* v, void* d_accum, void* stream,
                            rt_stats* stats);
+
+/* ---- lens and shutter per view, and in adaptive passes ------------------------------------------------
+ * rt_render_views_shutter is rt_render_views with an open shutter of its own on every view: view j sees cameras[j] when
+ * its shutter opens and shutters[j].camera_close when it closes, with shutters[j]'s exposure and lens.  shutters is HOST
+ * memory, [n_views] records; rt_views, rt_shutter and their rules are the ones above.  A lens without motion is a record
+ * with camera_close == cameras[j], open == close == 0 and aperture > 0 (rt_render_shutter's G3): there is no separate lens
+ * variant, and views with and without a lens share the launch.
+ * Host-derived constants, per view, in rt_render_shutter's arithmetic with A = cameras[j], B = shutters[j].camera_close:
+ * D = B - A in float32; with aperture > 0, fs0 and fs1 by the fs rule in float64, rounded, and dfs = fs1 - fs0 in float32.
+ * Every sample of view j is then formed by steps 1 to 6 of the rt_render_shutter contract with seed seeds[j] (p->seed when
+ * seeds is NULL), pix local to the view, and these constants.
+ * Guarantees (all bit for bit: accumulator words and both ray counts):
+ *   - V1, slices: slice j of the accumulator is what rt_render_shutter_device leaves for the same p with p->seed replaced
+ *     by seeds[j] and the record shutters[j], on this context after a camera-only rt_update to cameras[j]; the image is
+ *     rt_resolve_device of that slice.  Through G1 every sample is a row of rt_render_rays.
+ *   - V2, no optics: if every shutters[j] has camera_close == cameras[j], open == close == 0 and aperture == 0, the call
+ *     equals rt_render_views / rt_render_views_device (cameras with no -0 component: G2's condition).
+ *   - V3, schedule: sample ranges chain; reserved[0] (lanes per pixel) and reserved[1] bit 0 (no pool) never change the
+ *     bits.
+ *   - V4: n_views == 1 with cameras[0] equal to the context's camera is rt_render_shutter.
+ * Stats are sums over the views, as for rt_render_views.  The context's camera does not change.  The frame runs on the
+ * one-wave-per-workgroup kernel family (no persistent instances); RT_NODES_Q8 contexts walk their resident 32-byte
+ * records.
+ * The camera rule is rt_render_views', applied to cameras[j] in full and to camera_close for finiteness and for the
+ * padding: the call refits once, to the widest padding any end camera of any view needs, which the context keeps —
+ * RT_ERR_UNSUPPORTED on RT_NODES_Q8 contexts.
+ * Validation comes first and a rejected call writes nothing; what the arguments alone decide is answered before the
+ * device is asked for, in this order.  RT_ERR_INVALID: a null ctx, p, v or cameras; a null shutters; host form: neither
+ * out_rgb nor accum_out, or out_rgb without background_rgb; device form: a null d_accum; every check rt_render applies to
+ * p; rt_render_views' checks of v (reserved words, n_views 1..65535, n_views * width * height < 2^31) — with
+ * RT_ERR_UNSUPPORTED for world > 1, the wavefront integrator (reserved[2] bit 0), use_photons and the legacy RNG, as
+ * rt_render_shutter; then view by view, naming the view in rt_last_error ("view j: ..."): a non-finite cameras[j], and
+ * rt_render_shutter's checks of shutters[j] (reserved words, a non-finite camera_close, the open / close range, aperture,
+ * focus_distance).  Then the device: RT_ERR_NO_DEVICE.  Then, reading the context: rt_render_views' camera rule with the
+ * padding as above; and view by view, naming the view, rt_render_shutter's camera checks with cameras[j] in the place of
+ * the context's camera: the origin bound over both ends plus 2 aperture (against the bound the frame runs under: the
+ * context's, or the refit's), the axes (an H or V that cannot be normalised, or dot(H_A, H_B) <= 0 or dot(V_A, V_B) <= 0),
+ * and with aperture > 0 the fs rule at both ends.
+ * Buffers as rt_render_views': background_rgb [h][w][3] shared by every view; out_rgb [n][h][w][3] or NULL; accum_out
+ * [n][h][w][4] or NULL. */
+int rt_render_views_shutter(rt_ctx* ctx, const rt_params* p, const rt_views* v, const rt_shutter* shutters,
+                            const float* background_rgb, float* out_rgb, float* accum_out, rt_stats* stats);
+/* Accumulate into caller-zeroed DEVICE d_accum [n][h][w][4] on `stream` (may be NULL), as rt_render_views_device does:
+ * sample ranges chain, and the view and shutter records go up through the same ring of pinned copies.  The host waits only
+ * to refit, to read stats back, and for the upload of the call four multi-view calls back. */
+int rt_render_views_shutter_device(rt_ctx* ctx, const rt_params* p, const rt_views* v, const rt_shutter* shutters,
+                                   void* d_accum, void* stream, rt_stats* stats);
+/* rt_render_adaptive_shutter is rt_render_adaptive whose passes are rt_render_shutter frames: the context's camera when
+ * the shutter opens, shutter->camera_close when it closes.
+ *   - A1: a granule that ran K passes holds in accum exactly what K calls of rt_render_shutter_device leave on a zero
+ *     accumulator (call k: seed p->seed + k, spp P, the whole range, the same shutter), bit for bit.
+ * Retirement, spp_out, out_rgb and the report are rt_render_adaptive's rule over those passes.  A record that changes
+ * nothing (camera_close equal to the context's camera, aperture 0; cameras with no -0 component) makes the call
+ * rt_render_adaptive itself.  Validation comes first and a rejected call writes nothing: RT_ERR_INVALID for a null ctx, p,
+ * a or shutter; then rt_render_shutter's checks of the record and of p (RT_ERR_UNSUPPORTED for world > 1, use_photons, the
+ * wavefront bit, the legacy RNG); rt_render_adaptive's checks of p and a; null buffers (background_rgb / out_rgb; d_bg /
+ * d_accum / d_out); then the device (RT_ERR_NO_DEVICE); then the context's state and rt_render_shutter's camera checks.
+ * Buffers, the synchronisation per pass and the scratch are rt_render_adaptive's / rt_render_adaptive_device's. */
+int rt_render_adaptive_shutter(rt_ctx* ctx, const rt_params* p, const rt_adaptive_params* a, const rt_shutter* shutter,
+                               const float* background_rgb, float* out_rgb, float* accum_out, uint32_t* spp_out,
+                               rt_adaptive_report* rep, rt_stats* stats);
+int rt_render_adaptive_shutter_device(rt_ctx* ctx, const rt_params* p, const rt_adaptive_params* a,
+                                      const rt_shutter* shutter, const void* d_bg, void* d_accum, void* d_out,
+                                      void* d_spp, void* stream, rt_adaptive_report* rep, rt_stats* stats);
 
 /* Per-view AOVs, motion vectors and a batched denoiser for the same views: one launch each where a caller would loop over
  * the views with rt_update(camera), rt_render_aov, rt_render_motion and rt_denoise.  Every output is [n_views] slices of

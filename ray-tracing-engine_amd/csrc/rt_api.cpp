@@ -335,13 +335,17 @@ struct rt_ctx {
   // uploaded ahead of the view records on the same stream
   DevBuf<rt_camera> vwPrevCams;
   uint32_t vwPrevCap = 0;
+  // rt_render_views_shutter_device: the shutter record of every view, one more table beside vwRecs, uploaded the same way
+  DevBuf<rtk::ViewShutterRec> vwShutters;
+  uint32_t vwShutterCap = 0;
   // The pinned copies those uploads read, a ring of kViewStages: a call takes the next slot and waits only for the uploads
   // of the call kViewStages back (`read`: recorded behind the uploads that last read the slot), so back-to-back calls on
   // a busy stream do not wait for one another (DESIGN.md "Stream order")
   struct ViewStage {
     PinnedBuf<rtk::ViewRec> recs;
     PinnedBuf<rt_camera> prevCams;
-    uint32_t cap = 0, prevCap = 0;
+    PinnedBuf<rtk::ViewShutterRec> shutters;
+    uint32_t cap = 0, prevCap = 0, shutterCap = 0;
     Event read;
     bool readSet = false;
   };
@@ -644,16 +648,19 @@ int wavefront_args(rt_ctx* c, const rt_params* p, const rtk::RenderArgs& A, uint
 }
 
 // A wave-tile list of the caller's (an adaptive pass, a multi-view frame) instead of the frame's cached one: device
-// memory, for `sshift`; a multi-view frame also gives each tile's view and the view records (rtk::RenderArgs).
+// memory, for `sshift`; a multi-view frame also gives each tile's view and the view records (rtk::RenderArgs), and a
+// multi-view shutter frame the views' shutter records beside them.
 struct TileList {
   const uint32_t* tiles;
   uint32_t n, sshift;
   const uint32_t* tileView = nullptr;
   const rtk::ViewRec* views = nullptr;
+  const rtk::ViewShutterRec* viewShutters = nullptr;
 };
 
 // What forms a frame's primary rays in place of camera_ray, if anything: the thin lens of rt_render_lens or the open
-// shutter of rt_render_shutter, at most one of them (their callers have refused photons and the wavefront bit).
+// shutter of rt_render_shutter, at most one of them (their callers have refused photons and the wavefront bit).  A
+// multi-view shutter frame carries its records in its TileList instead.
 struct FrameGen {
   const rtk::LensRec* lens = nullptr;
   const rtk::ShutterRec* shutter = nullptr;
@@ -672,6 +679,7 @@ int launch_frame(rt_ctx* c, const rt_params* p, float4* dAccum, hipStream_t stre
   wave_tile_shape(sshift, A.tileW, A.tileH);
   A.tiles = own ? own->tiles : c->tiles.d.get(), A.n_tiles = own ? own->n : c->tiles.n;
   A.tileView = own ? own->tileView : nullptr, A.views = own ? own->views : nullptr;
+  A.viewShutters = own ? own->viewShutters : nullptr;
   A.width = p->width, A.height = p->height, A.spp = p->spp;
   A.s0 = sr.s0, A.s1 = sr.s1;
   A.mode = p->mode, A.max_depth = p->max_depth, A.seed = p->seed;
@@ -697,7 +705,11 @@ int launch_frame(rt_ctx* c, const rt_params* p, float4* dAccum, hipStream_t stre
   rtk::WfArgs W{};
   if (wavefront && (rc = wavefront_args(c, p, A, sr.count, stream, &W)) != RT_OK) return rc;
   return timed_launch(c, stream, evIndex, [&] {
-    if (gen.lens) {
+    if (A.viewShutters) {
+      hipError_t he = rtk::launch_render_views_shutter(p->accel == RT_ACCEL_BRUTE, p->collect_stats != 0, c->S, A, dAccum,
+                                                       c->dCounters.get(), stream);
+      if (he != hipSuccess) return fail(RT_ERR_HIP, "multi-view shutter render launch failed: %s", hipGetErrorString(he));
+    } else if (gen.lens) {
       hipError_t he = rtk::launch_render_lens(p->accel == RT_ACCEL_BRUTE, p->collect_stats != 0, c->S, A, *gen.lens, dAccum,
                                               c->dCounters.get(), stream);
       if (he != hipSuccess) return fail(RT_ERR_HIP, "lens render launch failed: %s", hipGetErrorString(he));
@@ -2869,13 +2881,18 @@ struct AdaptiveRule {
   float threshold, floor;
 };
 
+int adaptive_rule_checks(const rt_params* p, const rt_adaptive_params* a, AdaptiveRule* r);
 // Everything an adaptive frame checks before it touches the device; *r gets the rule with its defaults applied.
 int adaptive_checks(const rt_ctx* c, const rt_params* p, const rt_adaptive_params* a, AdaptiveRule* r) {
   if (!c) return fail(RT_ERR_INVALID, "ctx is null");
   if (!p) return fail(RT_ERR_INVALID, "params is null");
   if (!a) return fail(RT_ERR_INVALID, "adaptive params are null");
-  int rc = check_params(c, p);
+  const int rc = check_params(c, p);
   if (rc != RT_OK) return rc;
+  return adaptive_rule_checks(p, a, r);
+}
+// ... of them, what p and a alone decide once p has a frame's shape (rt_render_adaptive_shutter asks this before the device)
+int adaptive_rule_checks(const rt_params* p, const rt_adaptive_params* a, AdaptiveRule* r) {
   if (p->spp_begin || p->spp_count)
     return fail(RT_ERR_INVALID, "an adaptive frame runs whole passes of spp samples: spp_begin and spp_count must be 0");
   if (a->max_passes == 0) return fail(RT_ERR_INVALID, "max_passes must be >= 1");
@@ -2896,17 +2913,12 @@ int adaptive_checks(const rt_ctx* c, const rt_params* p, const rt_adaptive_param
   return RT_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int rt_render_adaptive_device(rt_ctx* c, const rt_params* p, const rt_adaptive_params* a, const void* d_bg, void* d_accum,
-                              void* d_out, void* d_spp, void* stream, rt_adaptive_report* rep, rt_stats* stats) {
-  const auto t0 = std::chrono::steady_clock::now();
-  AdaptiveRule R;
-  int rc = adaptive_checks(c, p, a, &R);
-  if (rc != RT_OK) return rc;
-  if (!d_bg || !d_accum || !d_out) return fail(RT_ERR_INVALID, "null argument");
+// The pass loop behind every adaptive entry point, on device buffers, after the checks: rule R over passes of the frame p
+// describes, its primary rays formed by gen (rt_render_adaptive_shutter: the open shutter; else the frame's own).
+int adaptive_run(rt_ctx* c, const rt_params* p, const AdaptiveRule& R, const FrameGen& gen, const void* d_bg, void* d_accum,
+                 void* d_out, void* d_spp, void* stream, rt_adaptive_report* rep, rt_stats* stats,
+                 std::chrono::steady_clock::time_point t0) {
+  int rc;
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const uint32_t W = p->width, H = p->height, gx = (W + 7) / 8, gy = (H + 7) / 8, nG = gx * gy;
@@ -2970,7 +2982,7 @@ int rt_render_adaptive_device(rt_ctx* c, const rt_params* p, const rt_adaptive_p
     if ((he = rtk::launch_adapt_expand(A, nAct, tw, th, s)) != hipSuccess) return fail(RT_ERR_HIP, "adaptive tile list failed: %s", hipGetErrorString(he));
     HIP_TRY(hipEventRecord(ev[3].get(), s));
     const TileList own = {A.tiles, cnt[rtk::ADAPT_CNT_TILES + sshift], sshift};
-    if ((rc = launch_frame(c, &q, static_cast<float4*>(d_accum), s, nullptr, &own)) != RT_OK) return rc;
+    if ((rc = launch_frame(c, &q, static_cast<float4*>(d_accum), s, nullptr, &own, gen)) != RT_OK) return rc;
     HIP_TRY(hipEventRecord(ev[4].get(), s));
     if ((he = rtk::launch_adapt_update(A, nAct, s)) != hipSuccess) return fail(RT_ERR_HIP, "adaptive update failed: %s", hipGetErrorString(he));
     HIP_TRY(hipEventRecord(ev[5].get(), s));
@@ -3001,25 +3013,89 @@ int rt_render_adaptive_device(rt_ctx* c, const rt_params* p, const rt_adaptive_p
   return RT_OK;
 }
 
-int rt_render_adaptive(rt_ctx* c, const rt_params* p, const rt_adaptive_params* a, const float* bg, float* out_rgb,
-                       float* accum_out, uint32_t* spp_out, rt_adaptive_report* rep, rt_stats* stats) {
-  const auto t0 = std::chrono::steady_clock::now();
-  AdaptiveRule R;
-  int rc = adaptive_checks(c, p, a, &R);
-  if (rc != RT_OK) return rc;
-  if (!bg || !out_rgb) return fail(RT_ERR_INVALID, "null argument");
+// The host forms: adaptive_run on device copies of the caller's buffers, on the null stream
+int adaptive_host(rt_ctx* c, const rt_params* p, const AdaptiveRule& R, const FrameGen& gen, const float* bg, float* out_rgb,
+                  float* accum_out, uint32_t* spp_out, rt_adaptive_report* rep, rt_stats* stats,
+                  std::chrono::steady_clock::time_point t0) {
   HIP_TRY(hipSetDevice(c->device));
   const size_t npx = (size_t)p->width * p->height;
   Staging st;
-  float4* dAccum = st.work<float4>(accum_out, npx);  // (the device form zeroes it)
+  float4* dAccum = st.work<float4>(accum_out, npx);  // (the pass loop zeroes it)
   const float* dBg = st.in(bg, 3 * npx);
   float* dOut = st.out(out_rgb, 3 * npx);
   uint32_t* dSpp = st.out(spp_out, npx);
   if (st.rc != RT_OK) return st.rc;
-  if ((rc = rt_render_adaptive_device(c, p, a, dBg, dAccum, dOut, dSpp, nullptr, rep, stats)) != RT_OK) return rc;
+  int rc = adaptive_run(c, p, R, gen, dBg, dAccum, dOut, dSpp, nullptr, rep, stats, t0);
+  if (rc != RT_OK) return rc;
   if ((rc = st.download()) != RT_OK) return rc;
   if (rep) rep->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return RT_OK;
+}
+
+int shutter_record_checks(const rt_shutter* s, const char* who);
+int shutter_params_checks(const rt_params* p);
+int shutter_camera_checks(const rt_camera& A, float originBound, const rt_shutter* s, const char* who, rtk::ShutterRec* R);
+
+// Everything both forms of rt_render_adaptive_shutter check, in the header's order: the arguments alone (rt_render_shutter's
+// of the record and of p, then rt_render_adaptive's of p and a, then the form's own buffers), the device, then the context
+// (rt_render's state checks) and its camera.
+int adaptive_shutter_checks(const rt_ctx* c, const rt_params* p, const rt_adaptive_params* a, const rt_shutter* sh, bool buffers,
+                            AdaptiveRule* r, rtk::ShutterRec* S) {
+  if (!c || !p || !a || !sh) return fail(RT_ERR_INVALID, "ctx/params/adaptive params/shutter is null");
+  int rc = shutter_record_checks(sh, "");
+  if (rc != RT_OK) return rc;
+  if ((rc = shutter_params_checks(p)) != RT_OK) return rc;
+  if ((rc = adaptive_rule_checks(p, a, r)) != RT_OK) return rc;
+  if (!buffers) return fail(RT_ERR_INVALID, "null argument");
+  if ((rc = check_device_present()) != RT_OK) return rc;
+  if ((rc = check_params(c, p)) != RT_OK) return rc;
+  return shutter_camera_checks(c->S.cam, c->bvh.originBound, sh, "", S);
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_render_adaptive_device(rt_ctx* c, const rt_params* p, const rt_adaptive_params* a, const void* d_bg, void* d_accum,
+                              void* d_out, void* d_spp, void* stream, rt_adaptive_report* rep, rt_stats* stats) {
+  const auto t0 = std::chrono::steady_clock::now();
+  AdaptiveRule R;
+  const int rc = adaptive_checks(c, p, a, &R);
+  if (rc != RT_OK) return rc;
+  if (!d_bg || !d_accum || !d_out) return fail(RT_ERR_INVALID, "null argument");
+  return adaptive_run(c, p, R, FrameGen(), d_bg, d_accum, d_out, d_spp, stream, rep, stats, t0);
+}
+
+int rt_render_adaptive(rt_ctx* c, const rt_params* p, const rt_adaptive_params* a, const float* bg, float* out_rgb,
+                       float* accum_out, uint32_t* spp_out, rt_adaptive_report* rep, rt_stats* stats) {
+  const auto t0 = std::chrono::steady_clock::now();
+  AdaptiveRule R;
+  const int rc = adaptive_checks(c, p, a, &R);
+  if (rc != RT_OK) return rc;
+  if (!bg || !out_rgb) return fail(RT_ERR_INVALID, "null argument");
+  return adaptive_host(c, p, R, FrameGen(), bg, out_rgb, accum_out, spp_out, rep, stats, t0);
+}
+
+// ---- adaptive frames under an open shutter
+int rt_render_adaptive_shutter_device(rt_ctx* c, const rt_params* p, const rt_adaptive_params* a, const rt_shutter* sh,
+                                      const void* d_bg, void* d_accum, void* d_out, void* d_spp, void* stream,
+                                      rt_adaptive_report* rep, rt_stats* stats) {
+  const auto t0 = std::chrono::steady_clock::now();
+  AdaptiveRule R;
+  rtk::ShutterRec S;
+  const int rc = adaptive_shutter_checks(c, p, a, sh, d_bg && d_accum && d_out, &R, &S);
+  if (rc != RT_OK) return rc;
+  return adaptive_run(c, p, R, FrameGen{nullptr, &S}, d_bg, d_accum, d_out, d_spp, stream, rep, stats, t0);
+}
+
+int rt_render_adaptive_shutter(rt_ctx* c, const rt_params* p, const rt_adaptive_params* a, const rt_shutter* sh, const float* bg,
+                               float* out_rgb, float* accum_out, uint32_t* spp_out, rt_adaptive_report* rep, rt_stats* stats) {
+  const auto t0 = std::chrono::steady_clock::now();
+  AdaptiveRule R;
+  rtk::ShutterRec S;
+  const int rc = adaptive_shutter_checks(c, p, a, sh, bg && out_rgb, &R, &S);
+  if (rc != RT_OK) return rc;
+  return adaptive_host(c, p, R, FrameGen{nullptr, &S}, bg, out_rgb, accum_out, spp_out, rep, stats, t0);
 }
 
 }  // extern "C"
@@ -3100,7 +3176,9 @@ int ensure_view_tiles(rt_ctx* c, const rt_params* p, uint32_t sshift, uint32_t n
 // to the device on `stream`, through the next slot of the ring of pinned copies: the host waits only until the uploads that
 // last read that slot, kViewStages calls ago, have finished.  The device tables are written and read in stream order;
 // where they grow, the old ones are freed under launches that may still read them, which hipFree waits for.
-int upload_views(rt_ctx* c, const rt_params* p, const rt_views* v, const rt_camera* prevCams, hipStream_t stream) {
+// shutters: the views' shutter records of a multi-view shutter frame (else null), a third table through the same slot.
+int upload_views(rt_ctx* c, const rt_params* p, const rt_views* v, const rt_camera* prevCams, hipStream_t stream,
+                 const rtk::ViewShutterRec* shutters = nullptr) {
   const uint32_t n = v->n_views;
   rt_ctx::ViewStage& g = c->vwStage[c->vwStageNext++ % rt_ctx::kViewStages];
   if (!g.read) HIP_TRY(make_event(&g.read, hipEventDisableTiming));
@@ -3110,7 +3188,13 @@ int upload_views(rt_ctx* c, const rt_params* p, const rt_views* v, const rt_came
   if (rc == RT_OK && prevCams) rc = grow(&g.prevCams, &g.prevCap, n);
   if (rc == RT_OK) rc = grow(&c->vwRecs, &c->vwCap, n);
   if (rc == RT_OK && prevCams) rc = grow(&c->vwPrevCams, &c->vwPrevCap, n);
+  if (rc == RT_OK && shutters) rc = grow(&g.shutters, &g.shutterCap, n);
+  if (rc == RT_OK && shutters) rc = grow(&c->vwShutters, &c->vwShutterCap, n);
   if (rc != RT_OK) return rc;
+  if (shutters) {
+    memcpy(g.shutters.get(), shutters, n * sizeof(rtk::ViewShutterRec));
+    HIP_TRY(hipMemcpyAsync(c->vwShutters.get(), g.shutters.get(), n * sizeof(rtk::ViewShutterRec), hipMemcpyHostToDevice, stream));
+  }
   if (prevCams) {
     memcpy(g.prevCams.get(), prevCams, n * sizeof(rt_camera));
     HIP_TRY(hipMemcpyAsync(c->vwPrevCams.get(), g.prevCams.get(), n * sizeof(rt_camera), hipMemcpyHostToDevice, stream));
@@ -3359,7 +3443,7 @@ bool unit3_host(const float* a, float* u) {
 
 // The fs rule of rt_amd.h for one camera: the distance of the image plane along the optical axis in float64 (the header
 // states the order), focus_distance over it rounded to float32; RT_ERR_INVALID unless that is finite and > 0.
-int focus_scale(const rt_camera& cam, float focus_distance, float* fs) {
+int focus_scale(const rt_camera& cam, float focus_distance, float* fs, const char* who = "") {
   double cc[3], H[3], V[3];
   for (int k = 0; k < 3; ++k) {
     H[k] = cam.horizontal[k], V[k] = cam.vertical[k];
@@ -3370,7 +3454,7 @@ int focus_scale(const rt_camera& cam, float focus_distance, float* fs) {
   const double plane = std::fabs(cn) / std::sqrt(nn);
   *fs = (float)((double)focus_distance / plane);
   if (!(*fs > 0.f) || !std::isfinite(*fs))
-    return fail(RT_ERR_INVALID, "focus_distance %g over the image plane's distance %g is not a finite positive float", focus_distance, plane);
+    return fail(RT_ERR_INVALID, "%sfocus_distance %g over the image plane's distance %g is not a finite positive float", who, focus_distance, plane);
   return RT_OK;
 }
 
@@ -3410,51 +3494,68 @@ int lens_checks(const rt_ctx* c, const rt_params* p, const rt_lens* l, const cha
 // max_c |a_c| of a 3-vector
 float max_abs3(const float* a) { return std::max(std::fabs(a[0]), std::max(std::fabs(a[1]), std::fabs(a[2]))); }
 
+// rt_render_shutter's checks in three parts, so that rt_render_views_shutter applies them per view: who prefixes every
+// message ("" or "view j: ").  First what the record alone decides ...
+int shutter_record_checks(const rt_shutter* s, const char* who) {
+  if (any_set(s->reserved, 4)) return fail(RT_ERR_INVALID, "%srt_shutter: reserved words must be zero", who);
+  const float* b = reinterpret_cast<const float*>(&s->camera_close);  // (the twelve components: rt_camera is four float[3])
+  static_assert(sizeof(rt_camera) == 12 * sizeof(float), "rt_camera is twelve floats");
+  for (int k = 0; k < 12; ++k)
+    if (!std::isfinite(b[k])) return fail(RT_ERR_INVALID, "%scamera_close: component %d is not finite", who, k);
+  if (!std::isfinite(s->open) || !std::isfinite(s->close) || !(0.f <= s->open && s->open <= s->close && s->close <= 1.f))
+    return fail(RT_ERR_INVALID, "%sthe exposure must be finite with 0 <= open <= close <= 1", who);
+  if (!(s->aperture >= 0.f) || !std::isfinite(s->aperture)) return fail(RT_ERR_INVALID, "%saperture must be finite and >= 0", who);
+  if (s->aperture > 0.f && (!(s->focus_distance > 0.f) || !std::isfinite(s->focus_distance)))
+    return fail(RT_ERR_INVALID, "%sfocus_distance must be finite and > 0", who);
+  return RT_OK;
+}
+// ... then what p alone decides ...
+int shutter_params_checks(const rt_params* p) {
+  const int rc = check_params_shape(p);
+  if (rc != RT_OK) return rc;
+  if (p->world > 1) return fail(RT_ERR_UNSUPPORTED, "tile-sharded shutter frames (world %u) are not supported", p->world);
+  if (p->use_photons) return fail(RT_ERR_UNSUPPORTED, "shutter frames do not shade from the photon map");
+  if (p->reserved[2] & 1u) return fail(RT_ERR_UNSUPPORTED, "shutter frames do not run the wavefront integrator");
+  return RT_OK;
+}
+// ... and last what reads the camera A the shutter opens on (the context's, or a view's) and the origin bound the frame
+// runs under, and the record the kernels take.
+int shutter_camera_checks(const rt_camera& A, float originBound, const rt_shutter* s, const char* who, rtk::ShutterRec* R) {
+  const rt_camera& B = s->camera_close;
+  const float *a = reinterpret_cast<const float*>(&A), *b = reinterpret_cast<const float*>(&B);
+  *R = rtk::ShutterRec{};
+  for (int k = 0; k < 12; ++k) R->d[k] = b[k] - a[k];  // (finite: both ends are, and the open camera lies within the scene's input bound)
+  R->open = s->open, R->close = s->close, R->aperture = s->aperture;
+  // pos(t) = posA + t D may pass an end point by one rounding: one float above the larger end covers every value
+  const float reach = std::nextafter(std::max(max_abs3(A.position), max_abs3(B.position)), INFINITY) + 2.f * s->aperture;
+  if (reach > originBound)
+    return fail(RT_ERR_INVALID, "%sthe moving camera reaches %g from the origin, beyond the context's origin bound %g", who, reach, originBound);
+  float u[3];
+  if (!unit3_host(A.horizontal, u) || !unit3_host(A.vertical, u) || !unit3_host(B.horizontal, u) || !unit3_host(B.vertical, u))
+    return fail(RT_ERR_INVALID, "%sa horizontal or vertical axis of the open camera or of camera_close cannot be normalised", who);
+  double hh = 0., vv = 0.;
+  for (int k = 0; k < 3; ++k) hh += (double)A.horizontal[k] * (double)B.horizontal[k], vv += (double)A.vertical[k] * (double)B.vertical[k];
+  if (!(hh > 0.) || !(vv > 0.))
+    return fail(RT_ERR_INVALID, "%sthe camera's horizontal or vertical axis turns by 90 degrees or more between open and close: an interpolated axis could vanish", who);
+  if (!(s->aperture > 0.f)) return RT_OK;
+  float fs1;
+  int rc;
+  if ((rc = focus_scale(A, s->focus_distance, &R->fs0, who)) != RT_OK || (rc = focus_scale(B, s->focus_distance, &fs1, who)) != RT_OK) return rc;
+  R->dfs = fs1 - R->fs0;
+  return RT_OK;
+}
+
 // Everything both forms of rt_render_shutter check, in the header's order, and the record the kernels take (lens_checks'
 // shape: the arguments alone first, then the device, the context's camera last).
 int shutter_checks(const rt_ctx* c, const rt_params* p, const rt_shutter* s, const char* outputs, rtk::ShutterRec* R) {
   if (!c || !p || !s) return fail(RT_ERR_INVALID, "ctx/params/shutter is null");
   if (outputs) return fail(RT_ERR_INVALID, "%s", outputs);
-  if (any_set(s->reserved, 4)) return fail(RT_ERR_INVALID, "rt_shutter: reserved words must be zero");
-  const rt_camera& B = s->camera_close;
-  const float* b = reinterpret_cast<const float*>(&B);  // (the twelve components: rt_camera is four float[3])
-  static_assert(sizeof(rt_camera) == 12 * sizeof(float), "rt_camera is twelve floats");
-  for (int k = 0; k < 12; ++k)
-    if (!std::isfinite(b[k])) return fail(RT_ERR_INVALID, "camera_close: component %d is not finite", k);
-  if (!std::isfinite(s->open) || !std::isfinite(s->close) || !(0.f <= s->open && s->open <= s->close && s->close <= 1.f))
-    return fail(RT_ERR_INVALID, "the exposure must be finite with 0 <= open <= close <= 1");
-  if (!(s->aperture >= 0.f) || !std::isfinite(s->aperture)) return fail(RT_ERR_INVALID, "aperture must be finite and >= 0");
-  const bool lens = s->aperture > 0.f;
-  if (lens && (!(s->focus_distance > 0.f) || !std::isfinite(s->focus_distance)))
-    return fail(RT_ERR_INVALID, "focus_distance must be finite and > 0");
-  int rc = check_params_shape(p);
+  int rc = shutter_record_checks(s, "");
   if (rc != RT_OK) return rc;
-  if (p->world > 1) return fail(RT_ERR_UNSUPPORTED, "tile-sharded shutter frames (world %u) are not supported", p->world);
-  if (p->use_photons) return fail(RT_ERR_UNSUPPORTED, "shutter frames do not shade from the photon map");
-  if (p->reserved[2] & 1u) return fail(RT_ERR_UNSUPPORTED, "shutter frames do not run the wavefront integrator");
+  if ((rc = shutter_params_checks(p)) != RT_OK) return rc;
   if ((rc = check_device_present()) != RT_OK) return rc;
   if ((rc = check_not_broken(c)) != RT_OK) return rc;
-  const rt_camera& A = c->S.cam;
-  const float* a = reinterpret_cast<const float*>(&A);
-  *R = rtk::ShutterRec{};
-  for (int k = 0; k < 12; ++k) R->d[k] = b[k] - a[k];  // (finite: both ends are, and the context's camera lies within the scene's input bound)
-  R->open = s->open, R->close = s->close, R->aperture = s->aperture;
-  // pos(t) = posA + t D may pass an end point by one rounding: one float above the larger end covers every value
-  const float reach = std::nextafter(std::max(max_abs3(A.position), max_abs3(B.position)), INFINITY) + 2.f * s->aperture;
-  if (reach > c->bvh.originBound)
-    return fail(RT_ERR_INVALID, "the moving camera reaches %g from the origin, beyond the context's origin bound %g", reach, c->bvh.originBound);
-  float u[3];
-  if (!unit3_host(A.horizontal, u) || !unit3_host(A.vertical, u) || !unit3_host(B.horizontal, u) || !unit3_host(B.vertical, u))
-    return fail(RT_ERR_INVALID, "a horizontal or vertical axis of the context's camera or of camera_close cannot be normalised");
-  double hh = 0., vv = 0.;
-  for (int k = 0; k < 3; ++k) hh += (double)A.horizontal[k] * (double)B.horizontal[k], vv += (double)A.vertical[k] * (double)B.vertical[k];
-  if (!(hh > 0.) || !(vv > 0.))
-    return fail(RT_ERR_INVALID, "the camera's horizontal or vertical axis turns by 90 degrees or more between open and close: an interpolated axis could vanish");
-  if (!lens) return RT_OK;
-  float fs1;
-  if ((rc = focus_scale(A, s->focus_distance, &R->fs0)) != RT_OK || (rc = focus_scale(B, s->focus_distance, &fs1)) != RT_OK) return rc;
-  R->dfs = fs1 - R->fs0;
-  return RT_OK;
+  return shutter_camera_checks(c->S.cam, c->bvh.originBound, s, "", R);
 }
 
 }  // namespace
@@ -3507,6 +3608,108 @@ int rt_render_shutter(rt_ctx* c, const rt_params* p, const rt_shutter* sh, const
   rt_stats local;
   if ((rc = frame_device(c, p, FrameGen{nullptr, &R}, dAccum, nullptr, stats ? stats : &local)) != RT_OK) return rc;
   if ((rc = stage_resolve(&st, bg, out_rgb, dAccum, 1, npx, p->spp)) != RT_OK) return rc;
+  return st.download();
+}
+
+}  // extern "C"
+
+// ---- many views, each under its own open shutter ------------------------------------------------------
+namespace {
+
+// Everything both forms of rt_render_views_shutter check, in the header's order.  The arguments alone first: p and v as
+// rt_render_views checks them, the view cameras' finiteness, then rt_render_shutter's checks of p and, view by view, of the
+// record; then the device; then the context: rt_render_views' camera rule with every camera_close counted in the padding,
+// and rt_render_shutter's camera checks per view with cameras[j] in the place of the context's camera, under the origin
+// bound the frame runs with (*pad's).  recs: the records the kernels take.
+int views_shutter_checks(rt_ctx* c, const rt_params* p, const rt_views* v, const rt_shutter* sh, const char* outputs,
+                         rtbvh::Padding* pad, bool* refit, std::vector<rtk::ViewShutterRec>* recs) {
+  if (!c || !p || !v || !v->cameras) return fail(RT_ERR_INVALID, "ctx/params/views/cameras is null");
+  if (!sh) return fail(RT_ERR_INVALID, "shutters is null");
+  if (outputs) return fail(RT_ERR_INVALID, "%s", outputs);
+  int rc = check_params_shape(p);
+  if (rc != RT_OK) return rc;
+  if ((rc = views_shape_checks(p, v)) != RT_OK) return rc;
+  if ((rc = shutter_params_checks(p)) != RT_OK) return rc;
+  char who[32];
+  for (uint32_t j = 0; j < v->n_views; ++j) {
+    if (max_abs_bits(v->cameras[j].position, 12) >= 0x7f800000u) return fail(RT_ERR_INVALID, "view %u: non-finite camera", j);
+    snprintf(who, sizeof who, "view %u: ", j);
+    if ((rc = shutter_record_checks(&sh[j], who)) != RT_OK) return rc;
+  }
+  if ((rc = check_device_present()) != RT_OK) return rc;
+  if ((rc = views_checks(c, p, v, pad, refit)) != RT_OK) return rc;
+  const float magRef = bits_float(c->magRef);
+  for (uint32_t j = 0; j < v->n_views; ++j) {
+    const rtbvh::Padding P = rtbvh::paddingRule(magRef, sh[j].camera_close, c->hostLights.data(), (uint32_t)c->hostLights.size());
+    if (P.pad > pad->pad) *pad = P, *refit = true;
+  }
+  if (*refit && c->nodeFormat == RT_NODES_Q8)
+    return fail(RT_ERR_UNSUPPORTED, "views need a wider box padding (%g) and RT_NODES_Q8 contexts cannot be refit", pad->pad);
+  recs->resize(v->n_views);
+  for (uint32_t j = 0; j < v->n_views; ++j) {
+    snprintf(who, sizeof who, "view %u: ", j);
+    rtk::ShutterRec R;
+    if ((rc = shutter_camera_checks(v->cameras[j], pad->originBound, &sh[j], who, &R)) != RT_OK) return rc;
+    rtk::ViewShutterRec& Q = (*recs)[j];
+    Q = rtk::ViewShutterRec{};
+    memcpy(Q.d, R.d, sizeof Q.d);
+    Q.open = R.open, Q.close = R.close, Q.aperture = R.aperture, Q.fs0 = R.fs0, Q.dfs = R.dfs;
+  }
+  return RT_OK;
+}
+
+// The launch behind both forms, after the checks (rt_render_views_device's steps with the third table)
+int views_shutter_device(rt_ctx* c, const rt_params* p, const rt_views* v, const std::vector<rtk::ViewShutterRec>& recs,
+                         const rtbvh::Padding& pad, bool refit, void* d_accum, void* stream, rt_stats* stats) {
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  int rc;
+  if (refit && (rc = refit_to_padding(c, pad, s)) != RT_OK) return rc;
+  const uint32_t n = v->n_views;
+  const uint32_t sppCount = sample_range(*p).count;
+  const uint32_t sshift = choose_sshift_px(c, p, (uint64_t)n * p->width * p->height, sppCount);
+  if ((rc = ensure_view_tiles(c, p, sshift, n, s)) != RT_OK) return rc;
+  if ((rc = upload_views(c, p, v, nullptr, s, recs.data())) != RT_OK) return rc;
+  if (stats) HIP_TRY(hipMemsetAsync(c->dCounters.get(), 0, RTK_CNT_COUNT * sizeof(unsigned long long), s));
+  TileList own = {c->vwTiles.d.get(), c->vwNTiles, sshift};
+  own.tileView = c->vwTileView.d.get(), own.views = c->vwRecs.get(), own.viewShutters = c->vwShutters.get();
+  int e = 0;
+  if ((rc = launch_frame(c, p, static_cast<float4*>(d_accum), s, &e, &own)) != RT_OK) return rc;
+  return stats ? frame_stats(c, s, e, (uint64_t)n * p->width * p->height * sppCount, stats) : (int)RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_render_views_shutter_device(rt_ctx* c, const rt_params* p, const rt_views* v, const rt_shutter* shutters, void* d_accum,
+                                   void* stream, rt_stats* stats) {
+  rtbvh::Padding pad;
+  bool refit = false;
+  std::vector<rtk::ViewShutterRec> recs;
+  const int rc = views_shutter_checks(c, p, v, shutters, d_accum ? nullptr : "d_accum is null", &pad, &refit, &recs);
+  if (rc != RT_OK) return rc;
+  return views_shutter_device(c, p, v, recs, pad, refit, d_accum, stream, stats);
+}
+
+int rt_render_views_shutter(rt_ctx* c, const rt_params* p, const rt_views* v, const rt_shutter* shutters, const float* bg,
+                            float* out_rgb, float* accum_out, rt_stats* stats) {
+  rtbvh::Padding pad;
+  bool refit = false;
+  std::vector<rtk::ViewShutterRec> recs;
+  int rc = views_shutter_checks(c, p, v, shutters, !out_rgb && !accum_out ? "neither out_rgb nor accum_out is given"
+                                                   : out_rgb && !bg     ? "out_rgb requested without a background image"
+                                                                        : nullptr, &pad, &refit, &recs);
+  if (rc != RT_OK) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t npx = (size_t)p->width * p->height, all = npx * v->n_views;
+  Staging st;
+  float4* dAccum = st.zeroed<float4>(accum_out, all);
+  if (st.rc != RT_OK) return st.rc;
+  rt_stats local;
+  if ((rc = views_shutter_device(c, p, v, recs, pad, refit, dAccum, nullptr, stats ? stats : &local)) != RT_OK) return rc;
+  // each view resolved over its slice, with the shared background
+  if ((rc = stage_resolve(&st, bg, out_rgb, dAccum, v->n_views, npx, p->spp)) != RT_OK) return rc;
   return st.download();
 }
 

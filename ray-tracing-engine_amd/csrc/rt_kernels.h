@@ -70,6 +70,18 @@ struct ViewRec {
 };
 static_assert(sizeof(ViewRec) == 64, "ViewRec is four 16-byte scalar loads");
 
+// The shutter of one view of a multi-view shutter frame (rt_render_views_shutter): ShutterRec's host-derived constants
+// (below) with the view's camera in the place of the context's, in a table parallel to the views' (ViewRec stays 64
+// bytes).  80 bytes, read by scalar loads.
+struct ViewShutterRec {
+  float d[12];        // camera_close - cameras[view], component by component (position, lower_left, H, V)
+  float open, close;  // the exposure: t = uniformF(open, close)
+  float aperture;     // lens radius, 0 = pinhole (fs0 and dfs are then not read)
+  float fs0, dfs;     // fs of cameras[view], and fs of camera_close minus it
+  uint32_t pad[3];
+};
+static_assert(sizeof(ViewShutterRec) == 80 && sizeof(ViewShutterRec) % 16 == 0, "ViewShutterRec is five 16-byte scalar loads");
+
 struct RenderArgs {
   const uint32_t* tiles;  // owned wave tiles: x0 | y0 << 16 (pixels, top-left corner)
   uint32_t n_tiles;
@@ -89,6 +101,8 @@ struct RenderArgs {
   // views' records; null: one view, S.cam, seed and accum as given
   const uint32_t* tileView;
   const ViewRec* views;
+  // multi-view shutter frames (rt_render_views_shutter): the views' shutter records, indexed as views; else null
+  const ViewShutterRec* viewShutters;
 };
 
 hipError_t launch_render(bool brute_force, bool photon, bool stats, const DevScene& S, const RenderArgs& A,
@@ -171,6 +185,11 @@ struct ShutterRec {
 // (tileView null)
 hipError_t launch_render_shutter(bool brute_force, bool stats, const DevScene& S, const RenderArgs& A, const ShutterRec& R,
                                  float4* accum, unsigned long long* counters, hipStream_t stream);
+// the same six instances over the wave tiles of many views (views_shutter_kernels.h, rt_render_views_shutter): tile t
+// renders with views[tileView[t]]'s camera, seed and slice under viewShutters[tileView[t]]; A as launch_render takes a
+// multi-view frame's, with the three tables set
+hipError_t launch_render_views_shutter(bool brute_force, bool stats, const DevScene& S, const RenderArgs& A, float4* accum,
+                                       unsigned long long* counters, hipStream_t stream);
 // First element of view j's slice of a per-view output with c floats or words per pixel (rt_render_aov_views,
 // rt_render_motion_views, rt_denoise_batch): formed in 64 bits — n w h may reach 2^31 - 1 and 3 x that is not 32-bit.
 __host__ __device__ inline size_t view_slice(uint32_t j, uint32_t width, uint32_t height, uint32_t c) {

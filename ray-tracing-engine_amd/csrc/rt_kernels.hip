@@ -214,7 +214,9 @@ constexpr int LT_VIEWS = 512;
 // primary ray by lens_ray instead of camera_ray.  Only render_tile reads the bit; its own instances (lens_kernels.h).
 constexpr int LT_LENS = 1024;
 // A frame under an open shutter (rt_render_shutter): render_tile takes a ShutterRec and forms every sample's camera, then
-// its primary ray, by shutter_ray.  Only render_tile reads the bit; its own instances (shutter_kernels.h).
+// its primary ray, by shutter_ray.  Only render_tile reads the bit; its own instances (shutter_kernels.h).  With LT_VIEWS
+// (rt_render_views_shutter): the record is the view's, from RenderArgs::viewShutters, and shutter_ray runs on the view's
+// camera and seed; its own instances again (views_shutter_kernels.h).
 constexpr int LT_SHUTTER = 2048;
 constexpr uint32_t kPrioMaxNodes = 65536;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -1251,7 +1253,7 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
   constexpr bool LENS = (LTV & LT_LENS) != 0;
   constexpr bool SHUTTER = (LTV & LT_SHUTTER) != 0;
   static_assert(!LENS || !VIEWS, "no multi-view lens frames");
-  static_assert(!SHUTTER || (!VIEWS && !LENS), "the shutter's lens is its own: LT_SHUTTER goes with neither LT_VIEWS nor LT_LENS");
+  static_assert(!SHUTTER || !LENS, "the shutter's lens is its own: LT_SHUTTER does not go with LT_LENS");
   constexpr bool FR = (LT & LT_FASTDET) != 0;  // 1 / length by rtd::recip_fast (see rtd::unit3)
   const uint32_t lane = threadIdx.x & 63u;
   // lane = (pixel pl of the wave tile, sample slot sj): the wave integrates
@@ -1263,7 +1265,22 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
   // (single-view instances read S.cam and A.seed as they always did)
   rt_camera cam;
   uint32_t seed = A.seed;
-  if constexpr (VIEWS) {
+  ShutterRec vsh;  // (LT_VIEWS | LT_SHUTTER) the view's shutter record, from the table parallel to views, in SGPRs too
+  if constexpr (VIEWS && SHUTTER) {
+    typedef const __attribute__((address_space(4))) uint32_t* const_u32_ptr;
+    typedef const __attribute__((address_space(4))) ViewRec* const_view_ptr;
+    typedef const __attribute__((address_space(4))) ViewShutterRec* const_shutter_ptr;
+    const uint32_t view = ((const_u32_ptr)A.tileView)[wave];
+    const const_view_ptr R = (const_view_ptr)A.views + view;
+    const const_shutter_ptr Q = (const_shutter_ptr)A.viewShutters + view;
+    for (int j = 0; j < 3; ++j)
+      cam.position[j] = R->cam.position[j], cam.lower_left[j] = R->cam.lower_left[j],
+      cam.horizontal[j] = R->cam.horizontal[j], cam.vertical[j] = R->cam.vertical[j];
+    seed = R->seed;
+    accum += R->accumOff;
+    for (int j = 0; j < 12; ++j) vsh.d[j] = Q->d[j];
+    vsh.open = Q->open, vsh.close = Q->close, vsh.aperture = Q->aperture, vsh.fs0 = Q->fs0, vsh.dfs = Q->dfs;
+  } else if constexpr (VIEWS) {
     typedef const __attribute__((address_space(4))) uint32_t* const_u32_ptr;
     typedef const __attribute__((address_space(4))) ViewRec* const_view_ptr;
     const const_view_ptr R = (const_view_ptr)A.views + ((const_u32_ptr)A.tileView)[wave];
@@ -1291,7 +1308,8 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
     jitter_sample(g, (int)i, (int)A.spp, sx, sy);
     f3 o, d;
     const float cu = ((float)px + sx) / (float)A.width, cv = 1.f - ((float)py + sy) / (float)A.height;
-    if constexpr (VIEWS) camera_ray<FR>(cam, cu, cv, o, d);
+    if constexpr (VIEWS && SHUTTER) shutter_ray(cam, vsh, seed, pix, i, cu, cv, o, d);
+    else if constexpr (VIEWS) camera_ray<FR>(cam, cu, cv, o, d);
     else if constexpr (LENS) {
       // (wave-uniform: the record is a kernel argument)
       if (lens->aperture > 0.f) lens_ray(S.cam, *lens, rt_stream_seed(A.seed, RT_STREAM_LENS, pix, i), cu, cv, o, d);
@@ -1606,6 +1624,9 @@ __global__ __launch_bounds__(1024, 8) void k_trace_stream(DevScene S, const floa
 
 // ---------------------------------------------------------------- open-shutter frames (rt_render_shutter)
 #include "shutter_kernels.h"
+
+// ---------------------------------------------------------------- multi-view open-shutter frames (rt_render_views_shutter)
+#include "views_shutter_kernels.h"
 
 // ---------------------------------------------------------------- frame assembly (multi-GPU)
 // A rank's owned 8x8-pixel granules, packed [granule][64 pixels] (row-major inside the

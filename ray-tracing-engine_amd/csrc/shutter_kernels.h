@@ -44,7 +44,7 @@ static hipError_t launch_render_shutter2(bool stats, const DevScene& S, const Re
 
 hipError_t launch_render_shutter(bool brute_force, bool stats, const DevScene& S, const RenderArgs& A, const ShutterRec& R,
                                  float4* accum, unsigned long long* counters, hipStream_t stream) {
-  if (A.tileView) return hipErrorInvalidValue;  // (no multi-view shutter frames)
+  if (A.tileView) return hipErrorInvalidValue;  // (multi-view shutter frames: launch_render_views_shutter)
   if (brute_force) return launch_render_shutter2<true, false>(stats, S, A, R, accum, counters, stream);
   // the vertex pool handles up to POOL_L lights, as in launch_render
   if ((A.flags & 1u) && S.n_lights <= (uint32_t)POOL_L) return launch_render_shutter2<false, true>(stats, S, A, R, accum, counters, stream);

@@ -389,7 +389,8 @@ AMD_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_create", "rt_destroy", "rt
                "rt_render_aov_views", "rt_render_aov_views_device", "rt_render_motion_views", "rt_render_motion_views_device",
                "rt_denoise_batch", "rt_denoise_batch_device", "rt_render_ao", "rt_render_ao_device", "rt_render_rays",
                "rt_render_rays_device", "rt_render_lens", "rt_render_lens_device", "rt_render_shutter",
-               "rt_render_shutter_device"]
+               "rt_render_shutter_device", "rt_render_views_shutter", "rt_render_views_shutter_device",
+               "rt_render_adaptive_shutter", "rt_render_adaptive_shutter_device"]
 HOST_SYMBOLS = ["rt_host_scene_build", "rt_host_scene_desc", "rt_host_scene_free", "rt_host_last_error",
                 "rt_host_fill_background", "rt_host_save_ppm", "rt_host_kd_order", "rt_host_light_basis"]
 
@@ -426,6 +427,17 @@ def make_shutter(camera_close, open=0.0, close=1.0, aperture=0.0, focus_distance
     C.memmove(C.byref(s.camera_close), cam.ctypes.data, 48)
     s.open, s.close, s.aperture, s.focus_distance = open, close, aperture, focus_distance
     return s
+
+
+def make_shutters(shutters, n):
+    """The [n] rt_shutter array rt_render_views_shutter takes, from a sequence of n make_shutter records (copied)."""
+    shutters = list(shutters)
+    if len(shutters) != n:
+        raise ValueError("%d shutter records for %d views" % (len(shutters), n))
+    arr = (Shutter * n)()
+    for j, s in enumerate(shutters):
+        C.memmove(C.byref(arr[j]), C.byref(s), C.sizeof(Shutter))
+    return arr
 
 
 def amd():
@@ -512,6 +524,16 @@ def amd():
                                       C.POINTER(Stats)]
         L.rt_render_views_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Views), C.c_void_p, C.c_void_p,
                                              C.POINTER(Stats)]
+        L.rt_render_views_shutter.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Views), C.POINTER(Shutter), C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        L.rt_render_views_shutter_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Views), C.POINTER(Shutter),
+                                                     C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        L.rt_render_adaptive_shutter.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(AdaptiveParams), C.POINTER(Shutter),
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AdaptiveReport),
+                                                 C.POINTER(Stats)]
+        L.rt_render_adaptive_shutter_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(AdaptiveParams),
+                                                        C.POINTER(Shutter), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p, C.POINTER(AdaptiveReport), C.POINTER(Stats)]
         L.rt_denoise_device.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.POINTER(Aov), C.c_void_p,
                                         C.c_void_p]
         L.rt_render_motion.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(MotionPrev), C.POINTER(Motion)]
@@ -999,6 +1021,55 @@ class Context:
         _check(amd().rt_render_shutter_device(self._h, C.byref(params), C.byref(shutter), C.c_void_p(d_accum), C.c_void_p(stream or None),
                                               C.byref(st) if stats else None))
         return st
+
+    def render_views_shutter(self, params, cameras, shutters, bg=None, seeds=None, want_accum=True):
+        """rt_render_views_shutter: render_views with view j under the open shutter shutters[j] (a sequence of
+        make_shutter records, one per camera: cameras[j] when it opens, its camera_close when it closes); returns
+        (out [n][h][w][3] or None without bg, accum [n][h][w][4] or None, stats)."""
+        v, _keep = make_views(cameras, seeds)
+        sh = make_shutters(shutters, v.n_views)
+        w, h, n = params.width, params.height, v.n_views
+        out = np.empty((n, h, w, 3), np.float32) if bg is not None else None
+        acc = np.empty((n, h, w, 4), np.float32) if want_accum else None
+        st = Stats()
+        bgc = None if bg is None else np.ascontiguousarray(bg, np.float32)
+        _check(amd().rt_render_views_shutter(self._h, C.byref(params), C.byref(v), sh, _ptr(bgc), _ptr(out), _ptr(acc), C.byref(st)))
+        return out, acc, st
+
+    def render_views_shutter_device(self, params, cameras, shutters, d_accum_ptr, stream=0, seeds=None, stats=False):
+        """rt_render_views_shutter_device: accumulate into the caller-zeroed device d_accum [n][h][w][4] on `stream`."""
+        v, _keep = make_views(cameras, seeds)
+        sh = make_shutters(shutters, v.n_views)
+        st = Stats() if stats else None
+        _check(amd().rt_render_views_shutter_device(self._h, C.byref(params), C.byref(v), sh, C.c_void_p(d_accum_ptr),
+                                                    C.c_void_p(stream or None), C.byref(st) if stats else None))
+        return st
+
+    def render_adaptive_shutter(self, params, shutter, bg, threshold, max_passes, min_passes=0, floor=0.):
+        """rt_render_adaptive_shutter: render_adaptive whose passes are render_shutter frames under `shutter`.  Returns
+        (out [h][w][3], accum [h][w][4], spp [h][w] uint32, AdaptiveReport, Stats)."""
+        w, h = params.width, params.height
+        out = np.empty((h, w, 3), np.float32)
+        acc = np.empty((h, w, 4), np.float32)
+        spp = np.empty((h, w), np.uint32)
+        rep, st = AdaptiveReport(), Stats()
+        bgc = np.ascontiguousarray(bg, np.float32)
+        a = make_adaptive(threshold, max_passes, min_passes, floor)
+        _check(amd().rt_render_adaptive_shutter(self._h, C.byref(params), C.byref(a), C.byref(shutter), _ptr(bgc), _ptr(out),
+                                                _ptr(acc), _ptr(spp), C.byref(rep), C.byref(st)))
+        return out, acc, spp, rep, st
+
+    def render_adaptive_shutter_device(self, params, shutter, d_bg, d_accum, d_out, threshold, max_passes, min_passes=0,
+                                       floor=0., d_spp=None, stream=0, stats=False):
+        """rt_render_adaptive_shutter_device on device pointers (d_accum is overwritten; d_spp may be None), on `stream`.
+        Returns (AdaptiveReport, Stats or None)."""
+        rep = AdaptiveReport()
+        st = Stats() if stats else None
+        a = make_adaptive(threshold, max_passes, min_passes, floor)
+        _check(amd().rt_render_adaptive_shutter_device(self._h, C.byref(params), C.byref(a), C.byref(shutter), C.c_void_p(d_bg),
+                                                       C.c_void_p(d_accum), C.c_void_p(d_out), C.c_void_p(d_spp or None),
+                                                       C.c_void_p(stream or None), C.byref(rep), C.byref(st) if stats else None))
+        return rep, st
 
     @staticmethod
     def _motion_prev(prev_pos, prev_camera):
