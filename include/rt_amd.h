@@ -38,6 +38,8 @@
  *                                  per pixel sample, with or without the lens (+ _device form)
  *   rt_render_views_shutter / rt_render_adaptive_shutter <- (no counterpart) that shutter per view of a multi-view
  *                                  frame, and in the passes of an adaptive frame (+ _device forms)
+ *   rt_render_lights            <- (no counterpart) the frame split by light group: one accumulator per group of
+ *                                  lights for the rays of one frame (+ _device form)
  *   rt_render_aov_views / rt_render_motion_views / rt_denoise_batch <- (no counterpart) the AOVs, motion vectors and
  *                                  denoised frames of those views, one launch each (+ _device forms)
  *   rt_trace                    <- RayTracer::rayTrace (RayTracer.h:27-53) test hook
@@ -57,7 +59,8 @@
  *   ASYNCHRONOUS — everything the call does is queued on `stream`, device inputs are read and outputs
  *   written in stream order, and the call returns without waiting for the stream:
  *     rt_render_device, rt_render_views_device, rt_render_rays_device, rt_render_shutter_device,
- *     rt_render_views_shutter_device (tests/test_gpu_views_shutter.py) and rt_render_lens_device with stats == NULL;
+ *     rt_render_views_shutter_device (tests/test_gpu_views_shutter.py), rt_render_lights_device
+ *     (tests/test_gpu_lights.py) and rt_render_lens_device with stats == NULL;
  *     rt_resolve_device;
  *     rt_render_aov_device, rt_render_ao_device, rt_render_motion_device; rt_temporal_accumulate_device,
  *     rt_svgf_device, rt_denoise_device, rt_denoise_batch_device; rt_render_aov_views_device,
@@ -69,7 +72,7 @@
  *     multi-view call in a row waits for the upload of the first (four pinned staging copies).
  *   SYNCHRONISE `stream`, and only it, before they return, because the host reads a result back:
  *     rt_render_device, rt_render_views_device, rt_render_rays_device, rt_render_shutter_device,
- *     rt_render_views_shutter_device, rt_render_lens_device with stats != NULL;
+ *     rt_render_views_shutter_device, rt_render_lights_device, rt_render_lens_device with stats != NULL;
  *     rt_render_adaptive_device and rt_render_adaptive_shutter_device (every pass); rt_update_vertices_device and
  *     rt_update_transforms (twice);
  *     the four multi-view forms when a view lies far enough out to need a wider box padding (a refit).
@@ -677,6 +680,61 @@ int rt_render_shutter(rt_ctx* ctx, const rt_params* p, const rt_shutter* shutter
  * does: sample ranges chain.  p and shutter are copied before the call returns; the host waits only to read stats back. */
 int rt_render_shutter_device(rt_ctx* ctx, const rt_params* p, const rt_shutter* shutter, void* d_accum, void* stream,
                              rt_stats* stats);
+
+/* ---- the frame split by light group: per-light frames from one launch ---------------------------------
+ * rt_render_lights renders the frame p describes as rt_render does and leaves, instead of one accumulator, one per LIGHT
+ * GROUP: slice g holds the frame with only the lights of masks[g] lit.  Every primary, bounce and shadow ray and every
+ * random draw of the frame is made ONCE, whatever the number of groups: a light that is not lit still has its sample
+ * drawn and its shadow ray cast (Renderer.cpp:52-54), so the groups differ only in which terms a vertex adds.
+ *
+ * Sample i of pixel (x, y), pix = y * width + x, all in float32, nothing fused:
+ *   1. Up to the light loop of each vertex the sample is rt_render's, once for all groups: g seeded with
+ *      rt_stream_seed(seed, RT_STREAM_PIXEL, pix, i), jitter_sample, camera_ray, the primary cast; at every vertex the
+ *      light samples drawn in light order, one shadow ray per light, then (path mode, not after the last vertex traced)
+ *      the hemisphere draw and the bounce cast.
+ *   2. For group g the colour of a vertex is the sum of radiance_l * bsdf_l (the component-wise product rt_render adds)
+ *      over the lights l with bit l of masks[g] set whose shadow ray found nothing, started from +0 and added in light
+ *      order: color = color + radiance_l * bsdf_l.
+ *   3. Per group the sample is c0 + (c1 + (c2 + 0)) over the (up to three) vertices' colours of that group, clamped to
+ *      [0, 1] per component, and added in float32, in sample order, into .xyz of pixel pix of slice g; 1 is added into .w
+ *      of pixel pix of EVERY slice when the primary ray hit.  .w is therefore the same in every slice.  A slice resolves
+ *      with rt_resolve_device; the host form resolves every slice over the one background_rgb.
+ * Guarantees, all bit for bit, on accumulator words and on both ray counts:
+ *   - L1, slices: slice g is what rt_render_device leaves for the same p on a context whose lights outside masks[g] were
+ *     given color = (0, 0, 0) by rt_update — PROVIDED no unoccluded term radiance_l * bsdf_l of such a light is non-finite
+ *     on that context: the zeroed light's term must be 0 * x = +-0, which a NaN or infinite x (a non-finite bsdf_l or
+ *     attenuation) does not give.  x + +-0 = x and +0 + -0 = +0 do the rest.
+ *   - L2: a mask of all the context's lights gives rt_render's frame, unconditionally; n_groups == 1 with that mask also
+ *     reproduces rt_render's stats (samples and both ray counts).
+ *   - L3, the point of the call: samples, rays_closest and rays_shadow are ONE frame's, whatever n_groups is.
+ *   - L4, schedule: sample ranges chain (every slice, as rt_render_device's accumulator); reserved[0] (lanes per pixel)
+ *     and reserved[1] bit 0 (no pool) change the schedule, never the bits.
+ * RT_NODES_Q8 contexts walk their resident 32-byte records, as rt_render_lens does.  The call changes nothing in the
+ * context.  The frame runs on the one-wave-per-workgroup kernel family of rt_render (no persistent instances).
+ * Validation comes first and a rejected call writes nothing; what the arguments alone decide is answered before the
+ * device is asked for.  RT_ERR_INVALID: a null ctx, p or groups; n_groups 0 or above RT_LIGHT_GROUPS_MAX; non-zero
+ * reserved words; a non-zero masks[g] with g >= n_groups; host form: neither out_rgb nor accum_out, or out_rgb without
+ * background_rgb; device form: a null d_accum; every check rt_render applies to p.  RT_ERR_UNSUPPORTED: world > 1,
+ * use_photons, the wavefront integrator (reserved[2] bit 0), the legacy RNG.  Then the device (RT_ERR_NO_DEVICE); then,
+ * reading the context: RT_ERR_UNSUPPORTED for a context with more than 32 lights, RT_ERR_INVALID for a mask with a bit at
+ * or above the context's n_lights (rt_last_error names the group and the mask).
+ * Out of scope: unclamped per-group sums, more than RT_LIGHT_GROUPS_MAX groups per launch, groups combined with the lens,
+ * the shutter, views or adaptive passes, photon frames.                                                                  */
+#define RT_LIGHT_GROUPS_MAX 4
+typedef struct rt_light_groups {
+  uint32_t n_groups;                    /* 1..RT_LIGHT_GROUPS_MAX                                                     */
+  uint32_t masks[RT_LIGHT_GROUPS_MAX];  /* bit l: light l is lit in this group.  Masks may overlap, may be 0, may be
+                                           all lights; entries >= n_groups must be 0                                  */
+  uint32_t reserved[3];                 /* zero */
+} rt_light_groups;
+/* out_rgb [G][h][w][3] or NULL, accum_out [G][h][w][4] or NULL, G = n_groups; background_rgb [h][w][3] */
+int rt_render_lights(rt_ctx* ctx, const rt_params* p, const rt_light_groups* groups, const float* background_rgb,
+                     float* out_rgb, float* accum_out, rt_stats* stats);
+/* Accumulate into caller-zeroed DEVICE d_accum [G][h][w][4] on `stream` (a hipStream_t, may be NULL), as rt_render_device
+ * does: sample ranges chain.  p and groups are copied before the call returns; the host waits only to read stats back
+ * (stats == NULL: asynchronous; stats != NULL: synchronises `stream`, and only it). */
+int rt_render_lights_device(rt_ctx* ctx, const rt_params* p, const rt_light_groups* groups, void* d_accum, void* stream,
+                            rt_stats* stats);
 
 /* ---- motion vectors and temporal accumulation (DESIGN.md "Motion vectors and temporal accumulation") ----------------
  * Two stateless calls for animated frames.  The library keeps nothing between frames: the caller hands in last frame's

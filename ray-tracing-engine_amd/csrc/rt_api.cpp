@@ -660,10 +660,12 @@ struct TileList {
 
 // What forms a frame's primary rays in place of camera_ray, if anything: the thin lens of rt_render_lens or the open
 // shutter of rt_render_shutter, at most one of them (their callers have refused photons and the wavefront bit).  A
-// multi-view shutter frame carries its records in its TileList instead.
+// multi-view shutter frame carries its records in its TileList instead.  groups: the frame split by light group
+// (rt_render_lights), with camera_ray's primary rays: dAccum then holds one slice per group.
 struct FrameGen {
   const rtk::LensRec* lens = nullptr;
   const rtk::ShutterRec* shutter = nullptr;
+  const rtk::LightGroupsRec* groups = nullptr;
 };
 
 // Launch the integrate kernel for p on `stream`, bracketed by an event pair.  own: render those wave tiles only.
@@ -717,6 +719,10 @@ int launch_frame(rt_ctx* c, const rt_params* p, float4* dAccum, hipStream_t stre
       hipError_t he = rtk::launch_render_shutter(p->accel == RT_ACCEL_BRUTE, p->collect_stats != 0, c->S, A, *gen.shutter,
                                                  dAccum, c->dCounters.get(), stream);
       if (he != hipSuccess) return fail(RT_ERR_HIP, "shutter render launch failed: %s", hipGetErrorString(he));
+    } else if (gen.groups) {
+      hipError_t he = rtk::launch_render_lights(p->accel == RT_ACCEL_BRUTE, p->collect_stats != 0, c->S, A, *gen.groups, dAccum,
+                                                c->dCounters.get(), stream);
+      if (he != hipSuccess) return fail(RT_ERR_HIP, "light-group render launch failed: %s", hipGetErrorString(he));
     } else if (!wavefront) {
       hipError_t he = rtk::launch_render(p->accel == RT_ACCEL_BRUTE, p->use_photons != 0, p->collect_stats != 0, c->S, A,
                                          dAccum, c->dCounters.get(), stream);
@@ -3608,6 +3614,69 @@ int rt_render_shutter(rt_ctx* c, const rt_params* p, const rt_shutter* sh, const
   rt_stats local;
   if ((rc = frame_device(c, p, FrameGen{nullptr, &R}, dAccum, nullptr, stats ? stats : &local)) != RT_OK) return rc;
   if ((rc = stage_resolve(&st, bg, out_rgb, dAccum, 1, npx, p->spp)) != RT_OK) return rc;
+  return st.download();
+}
+
+}  // extern "C"
+
+// ---- the frame split by light group -------------------------------------------------------------------
+namespace {
+
+// Everything both forms of rt_render_lights check, in the header's order, and the record the kernels take (lens_checks'
+// shape: the arguments alone first, then the device, the context's lights last).
+int lights_checks(const rt_ctx* c, const rt_params* p, const rt_light_groups* g, const char* outputs, rtk::LightGroupsRec* R) {
+  if (!c || !p || !g) return fail(RT_ERR_INVALID, "ctx/params/groups is null");
+  if (g->n_groups < 1 || g->n_groups > RT_LIGHT_GROUPS_MAX)
+    return fail(RT_ERR_INVALID, "n_groups %u is not in 1..%d", g->n_groups, RT_LIGHT_GROUPS_MAX);
+  if (any_set(g->reserved, 3)) return fail(RT_ERR_INVALID, "rt_light_groups: reserved words must be zero");
+  for (uint32_t j = g->n_groups; j < RT_LIGHT_GROUPS_MAX; ++j)
+    if (g->masks[j]) return fail(RT_ERR_INVALID, "masks[%u] = 0x%x is set beyond n_groups %u", j, g->masks[j], g->n_groups);
+  if (outputs) return fail(RT_ERR_INVALID, "%s", outputs);
+  int rc = check_params_shape(p);
+  if (rc != RT_OK) return rc;
+  if (p->world > 1) return fail(RT_ERR_UNSUPPORTED, "tile-sharded light-group frames (world %u) are not supported", p->world);
+  if (p->use_photons) return fail(RT_ERR_UNSUPPORTED, "light-group frames do not shade from the photon map");
+  if (p->reserved[2] & 1u) return fail(RT_ERR_UNSUPPORTED, "light-group frames do not run the wavefront integrator");
+  if ((rc = check_device_present()) != RT_OK) return rc;
+  if ((rc = check_not_broken(c)) != RT_OK) return rc;
+  const uint32_t nl = c->S.n_lights;
+  if (nl > 32u) return fail(RT_ERR_UNSUPPORTED, "the context has %u lights: a group mask holds 32", nl);
+  *R = rtk::LightGroupsRec{};
+  R->n = g->n_groups;
+  for (uint32_t j = 0; j < g->n_groups; ++j) {
+    if (nl < 32u && (g->masks[j] >> nl))
+      return fail(RT_ERR_INVALID, "group %u: mask 0x%x names a light at or above the context's n_lights %u", j, g->masks[j], nl);
+    R->masks[j] = g->masks[j];
+  }
+  return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_render_lights_device(rt_ctx* c, const rt_params* p, const rt_light_groups* g, void* d_accum, void* stream, rt_stats* stats) {
+  rtk::LightGroupsRec R;
+  const int rc = lights_checks(c, p, g, d_accum ? nullptr : "d_accum is null", &R);
+  if (rc != RT_OK) return rc;
+  return frame_device(c, p, FrameGen{nullptr, nullptr, &R}, d_accum, stream, stats);
+}
+
+int rt_render_lights(rt_ctx* c, const rt_params* p, const rt_light_groups* g, const float* bg, float* out_rgb, float* accum_out,
+                     rt_stats* stats) {
+  rtk::LightGroupsRec R;
+  int rc = lights_checks(c, p, g, !out_rgb && !accum_out ? "neither out_rgb nor accum_out is given"
+                                  : out_rgb && !bg     ? "out_rgb requested without a background image"
+                                                       : nullptr, &R);
+  if (rc != RT_OK) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t npx = (size_t)p->width * p->height;
+  Staging st;
+  float4* dAccum = st.zeroed<float4>(accum_out, R.n * npx);
+  if (st.rc != RT_OK) return st.rc;
+  rt_stats local;
+  if ((rc = frame_device(c, p, FrameGen{nullptr, nullptr, &R}, dAccum, nullptr, stats ? stats : &local)) != RT_OK) return rc;
+  if ((rc = stage_resolve(&st, bg, out_rgb, dAccum, R.n, npx, p->spp)) != RT_OK) return rc;
   return st.download();
 }
 

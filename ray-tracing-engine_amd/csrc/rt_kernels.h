@@ -190,6 +190,16 @@ hipError_t launch_render_shutter(bool brute_force, bool stats, const DevScene& S
 // multi-view frame's, with the three tables set
 hipError_t launch_render_views_shutter(bool brute_force, bool stats, const DevScene& S, const RenderArgs& A, float4* accum,
                                        unsigned long long* counters, hipStream_t stream);
+// the frame split by light group (lights_kernels.h, rt_render_lights): rt_light_groups' count and masks, by value — a
+// kernel argument, so every mask test is a scalar one.  masks[g] is 0 for g >= n.
+struct LightGroupsRec {
+  uint32_t n;
+  uint32_t masks[RT_LIGHT_GROUPS_MAX];
+};
+// launch_render_lens' six instances with one colour sum per group at every vertex; A as launch_render takes it (tileView
+// null), accum [G.n][height][width]: slice g at accum + g * width * height
+hipError_t launch_render_lights(bool brute_force, bool stats, const DevScene& S, const RenderArgs& A, const LightGroupsRec& G,
+                                float4* accum, unsigned long long* counters, hipStream_t stream);
 // First element of view j's slice of a per-view output with c floats or words per pixel (rt_render_aov_views,
 // rt_render_motion_views, rt_denoise_batch): formed in 64 bits — n w h may reach 2^31 - 1 and 3 x that is not 32-bit.
 __host__ __device__ inline size_t view_slice(uint32_t j, uint32_t width, uint32_t height, uint32_t c) {

@@ -218,6 +218,10 @@ constexpr int LT_LENS = 1024;
 // (rt_render_views_shutter): the record is the view's, from RenderArgs::viewShutters, and shutter_ray runs on the view's
 // camera and seed; its own instances again (views_shutter_kernels.h).
 constexpr int LT_SHUTTER = 2048;
+// A frame split by light group (rt_render_lights): render_tile takes a LightGroupsRec, keeps one colour per group and
+// vertex and adds every sample into one accumulator slice per group; the vertex pool and shade_direct_seq form the
+// per-group sums (their GROUPS switch).  Only render_tile reads the bit; its own instances (lights_kernels.h).
+constexpr int LT_LIGHTS = 4096;
 constexpr uint32_t kPrioMaxNodes = 65536;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(3))) u32x4* lds_u4_ptr;
@@ -821,13 +825,31 @@ RT_DEV f3 shade_photon(const DevScene& S, const RenderArgs& A, f3 rayDir, const 
   return mk(0.f, 0.f, 0.f) + radiance * bsdf;
 }
 
+// A vertex's colour per light group (rt_render_lights): c[g] = the sum, from +0 and in light order, of the unoccluded
+// terms of the lights in masks[g].  Only ever indexed by the constants of a fully unrolled loop: registers, no scratch.
+struct GroupCols {
+  f3 c[RT_LIGHT_GROUPS_MAX];
+};
+RT_DEV void group_cols_zero(GroupCols& q) {
+#pragma unroll
+  for (int g = 0; g < RT_LIGHT_GROUPS_MAX; ++g) q.c[g] = mk(0.f, 0.f, 0.f);
+}
+// one unoccluded light's term into the groups that hold light l (G is a kernel argument and l wave-uniform: scalar tests)
+RT_DEV void group_cols_add(GroupCols& q, const LightGroupsRec& G, uint32_t l, f3 term) {
+#pragma unroll
+  for (int g = 0; g < RT_LIGHT_GROUPS_MAX; ++g)
+    if ((G.masks[g] >> l) & 1u) q.c[g] = q.c[g] + term;
+}
+
 // Renderer.cpp:49-60, one light after the other (brute-force variant and scenes
 // with more than POOL_L lights).  Called by lanes that own a vertex only.
-template <bool BRUTE, bool STATS>
+// GROUPS (rt_render_lights): the terms go into *gc by group instead of into the returned colour, which stays 0.
+template <bool BRUTE, bool STATS, bool GROUPS = false>
 RT_DEV f3 shade_direct_seq(const DevScene& S, Rng& g, f3 rayDir, const HitRec& h, uint32_t* stack, f3 hitNormal,
-                           f3 point, LaneStats& st) {
+                           f3 point, LaneStats& st, const LightGroupsRec* G = nullptr, GroupCols* gc = nullptr) {
   const BsdfBase base = bsdf_base(S.matsDev[h.mesh], hitNormal, -rayDir);  // the light-independent half, once
   f3 color = mk(0.f, 0.f, 0.f);
+  if constexpr (GROUPS) group_cols_zero(*gc);
   for (uint32_t li = 0; li < S.n_lights; li++) {
     const rt_light Lt = S.lights[li];
     const f3 toLight = light_sample(g, Lt) - point;
@@ -836,7 +858,8 @@ RT_DEV f3 shade_direct_seq(const DevScene& S, Rng& g, f3 rayDir, const HitRec& h
     if (cast<BRUTE, true, STATS>(S, true, point, toLight, stack, tmp, st)) continue;
     const f3 bsdf = bsdf_apply(base, toLight);
     const f3 radiance = light_eval(Lt, point);
-    color = color + radiance * bsdf;
+    if constexpr (GROUPS) group_cols_add(*gc, *G, li, radiance * bsdf);
+    else color = color + radiance * bsdf;
   }
   return color;
 }
@@ -876,10 +899,14 @@ static_assert(VP_WORDS == (int)rtbvh::kWavePoolWords && BLOCK == (int)rtbvh::kSt
 // the hand-out and the direction fetch; hand-out order, thresholds, stealing and the shared result bits are the same code,
 // so the schedule — and the counted pass's node and triangle totals — are the same.  BOUNCE = true is the general body:
 // `bounceRay` says at run time whether a bounce ray is sent.
-template <bool STATS, int LT, bool BOUNCE>
+// GROUPS (rt_render_lights): the loop after the pool adds every unoccluded term into *gc by group (G's masks) instead of
+// into the returned colour, which stays 0; nothing before that loop differs.
+template <bool STATS, int LT, bool BOUNCE, bool GROUPS = false>
 RT_DEV f3 vertex_pool(const DevScene& S, bool alive, bool bounceRay, Rng& g, f3 rayDir, uint32_t mesh, f3 hitNormal,
-                      f3& point, f3& bdir, uint32_t* stack, uint32_t* pool, HitRec& next, bool& nextFound, LaneStats& st) {
+                      f3& point, f3& bdir, uint32_t* stack, uint32_t* pool, HitRec& next, bool& nextFound, LaneStats& st,
+                      const LightGroupsRec* G = nullptr, GroupCols* gc = nullptr) {
   const bool bounce = BOUNCE && bounceRay;
+  if constexpr (GROUPS) group_cols_zero(*gc);
   constexpr bool FR = (LT & LT_FASTDET) != 0;  // 1 / length by rtd::recip_fast (see rtd::unit3)
   const uint32_t lane = threadIdx.x & 63u, nl = S.n_lights;
   constexpr bool CP3 = (LT & LT_COMPACT3) != 0, CP2 = CP3 || (LT & LT_COMPACT2) != 0, CP = CP2 || (LT & LT_COMPACT) != 0;
@@ -1108,7 +1135,8 @@ RT_DEV f3 vertex_pool(const DevScene& S, bool alive, bool bounceRay, Rng& g, f3 
                               : mk(fp[VP_DIR + (3 * l + 0) * 64 + lane], fp[VP_DIR + (3 * l + 1) * 64 + lane], fp[VP_DIR + (3 * l + 2) * 64 + lane]);
       const f3 bsdf = bsdf_apply<FR>(base, toLight);
       const f3 radiance = light_eval(S.lights[l], pt);
-      color = color + radiance * bsdf;
+      if constexpr (GROUPS) group_cols_add(*gc, *G, l, radiance * bsdf);
+      else color = color + radiance * bsdf;
     }
     if (bounce) {
       const unsigned long long key = keys[lane];
@@ -1244,14 +1272,70 @@ RT_DEV void shutter_ray(const rt_camera& c, const ShutterRec& R, uint32_t seed, 
   } else camera_ray<false>(ct, u, v, o, d);
 }
 
+// (LT_LIGHTS) One sample group of a frame split by light group into the accumulator: per group g < G.n the sample is
+// c0[g] + (c1[g] + (c2[g] + 0)), clamped, and the pixel's owner lane adds the wave's samples in sample order into slice g
+// (accum + g * width * height), with the hit count into .w — render_tile's own adds, once per slice.  The hand-over area
+// is (3 RT_LIGHT_GROUPS_MAX + 1) rows of ex: the colours of group g in rows 3 g .. 3 g + 2, the hit flag in the last.  The
+// owner reads its pixel of a slice, adds and writes it back here, per sample group, instead of carrying G float4 sums
+// across the vertex pools: the same float32 adds in the same order, one 16-byte load and store per slice.
+constexpr int LG_EX_ROWS = 3 * RT_LIGHT_GROUPS_MAX + 1;
+RT_DEV void group_samples_add(const RenderArgs& A, const LightGroupsRec& G, float4* __restrict__ accum, float* ex, const GroupCols& g0,
+                              const GroupCols& g1, const GroupCols& g2, bool primary, bool active, bool owner, uint32_t pix,
+                              uint32_t pl, uint32_t base) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t S_ = 1u << A.sshift, P_ = 64u >> A.sshift;
+  const size_t slice = (size_t)A.width * A.height;
+  constexpr int HIT = 3 * RT_LIGHT_GROUPS_MAX * 64;
+  if (A.sshift == 0) {
+#pragma unroll
+    for (int g = 0; g < RT_LIGHT_GROUPS_MAX; ++g) {
+      if ((uint32_t)g < G.n && active) {
+        const f3 total = g0.c[g] + (g1.c[g] + (g2.c[g] + mk(0.f, 0.f, 0.f)));
+        float4 s = accum[g * slice + pix];
+        s.x += clamp01(total.x), s.y += clamp01(total.y), s.z += clamp01(total.z);
+        if (primary) s.w += 1.f;
+        accum[g * slice + pix] = s;
+      }
+    }
+    return;
+  }
+#pragma unroll
+  for (int g = 0; g < RT_LIGHT_GROUPS_MAX; ++g) {
+    if ((uint32_t)g < G.n) {
+      const f3 total = g0.c[g] + (g1.c[g] + (g2.c[g] + mk(0.f, 0.f, 0.f)));
+      ex[(3 * g + 0) * 64 + lane] = clamp01(total.x), ex[(3 * g + 1) * 64 + lane] = clamp01(total.y), ex[(3 * g + 2) * 64 + lane] = clamp01(total.z);
+    }
+  }
+  ex[HIT + lane] = primary ? 1.f : 0.f;
+  wave_sync();
+  if (owner) {
+    const uint32_t cnt = A.s1 - base < S_ ? A.s1 - base : S_;
+#pragma unroll
+    for (int g = 0; g < RT_LIGHT_GROUPS_MAX; ++g) {
+      if ((uint32_t)g < G.n) {
+        float4 s = accum[g * slice + pix];
+        for (uint32_t jj = 0; jj < cnt; jj++) {
+          const uint32_t q = jj * P_ + pl;
+          s.x += ex[(3 * g + 0) * 64 + q], s.y += ex[(3 * g + 1) * 64 + q], s.z += ex[(3 * g + 2) * 64 + q];
+          s.w += ex[HIT + q];  // adds 1.0 or an exact 0.0
+        }
+        accum[g * slice + pix] = s;
+      }
+    }
+  }
+  wave_sync();
+}
+
 template <bool BRUTE, bool PHOTON, bool POOLED, bool STATS, int LTV, class HP = Heap>
 RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restrict__ accum, const Lds& L, uint32_t* pool,
                         float* ex, uint32_t wave, LaneStats& st, const LensRec* lens = nullptr,
-                        const ShutterRec* shutter = nullptr) {
-  constexpr int LT = LTV & ~(LT_VIEWS | LT_LENS | LT_SHUTTER);
+                        const ShutterRec* shutter = nullptr, const LightGroupsRec* groups = nullptr) {
+  constexpr int LT = LTV & ~(LT_VIEWS | LT_LENS | LT_SHUTTER | LT_LIGHTS);
   constexpr bool VIEWS = (LTV & LT_VIEWS) != 0;
   constexpr bool LENS = (LTV & LT_LENS) != 0;
   constexpr bool SHUTTER = (LTV & LT_SHUTTER) != 0;
+  constexpr bool LIGHTS = (LTV & LT_LIGHTS) != 0;
+  static_assert(!LIGHTS || (!VIEWS && !LENS && !SHUTTER && !PHOTON), "light groups go with the plain frame only");
   static_assert(!LENS || !VIEWS, "no multi-view lens frames");
   static_assert(!SHUTTER || !LENS, "the shutter's lens is its own: LT_SHUTTER does not go with LT_LENS");
   constexpr bool FR = (LT & LT_FASTDET) != 0;  // 1 / length by rtd::recip_fast (see rtd::unit3)
@@ -1317,6 +1401,8 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
     } else if constexpr (SHUTTER) shutter_ray(S.cam, *shutter, A.seed, pix, i, cu, cv, o, d);
     else camera_ray<FR>(S.cam, cu, cv, o, d);
     f3 c0 = mk(0.f, 0.f, 0.f), c1 = c0, c2 = c0;
+    GroupCols g0, g1, g2, gv;  // (LT_LIGHTS) the three vertices' colours per group, and the current vertex's
+    if constexpr (LIGHTS) group_cols_zero(g0), group_cols_zero(g1), group_cols_zero(g2);
     bool primary = true, alive = active;
     if constexpr (pooled) {
       // primary ray (coherent: traced in lock step), then one pool per vertex
@@ -1345,13 +1431,23 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
         // with it where they have no scratch without, `k_render_persist5<false, 328>` spills more; they keep the
         // general body alone.
         constexpr bool SHADOW_BODY = (LT & 3) == LT_ALL;
-        const f3 c = SHADOW_BODY && !bounce
+        f3 c;
+        if constexpr (LIGHTS) {
+          static_assert(!SHADOW_BODY, "the light-group instances keep their trees in HBM / L2");
+          c = vertex_pool<STATS, LT, true, true>(S, alive, bounce, g, d, mesh, nrm, pt, bdir, L.stack, pool, nh, nfound, st, groups, &gv);
+        } else
+        c = SHADOW_BODY && !bounce
                          ? vertex_pool<STATS, LT, false>(S, alive, false, g, d, mesh, nrm, pt, bdir, L.stack, pool, nh, nfound, st)
                          : vertex_pool<STATS, LT, true>(S, alive, bounce, g, d, mesh, nrm, pt, bdir, L.stack, pool, nh, nfound, st);
         if (alive) {
           if (depth == 0) c0 = c;
           else if (depth == 1) c1 = c;
           else c2 = c;
+          if constexpr (LIGHTS) {
+            if (depth == 0) g0 = gv;
+            else if (depth == 1) g1 = gv;
+            else g2 = gv;
+          }
           o = pt, d = bdir, h = nh;
           if (!nfound) alive = false;
         }
@@ -1370,6 +1466,8 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
       if (alive) vertex_setup<FR>(S, h, nrm, pt);
       if (PHOTON) {
         if (alive) c = shade_photon<STATS, HP>(S, A, d, h, L, nrm, pt, st);
+      } else if constexpr (LIGHTS) {
+        if (alive) c = shade_direct_seq<BRUTE, STATS, true>(S, g, d, h, L.stack, nrm, pt, st, groups, &gv);
       } else {
         if (alive) c = shade_direct_seq<BRUTE, STATS>(S, g, d, h, L.stack, nrm, pt, st);
       }
@@ -1377,6 +1475,11 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
         if (depth == 0) c0 = c;
         else if (depth == 1) c1 = c;
         else c2 = c;
+        if constexpr (LIGHTS) {
+          if (depth == 0) g0 = gv;
+          else if (depth == 1) g1 = gv;
+          else g2 = gv;
+        }
       }
       if (A.mode != RT_MODE_PATH) break;
       if (alive) {
@@ -1386,6 +1489,10 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
     }
     // calculateColorPath returns c0 + (c1 + (c2 + 0)) for finalDepth <= 3
     PH(PH_VSETUP);
+    if constexpr (LIGHTS) {
+      group_samples_add(A, *groups, accum, ex, g0, g1, g2, primary, active, owner, pix, pl, base);
+      continue;
+    }
     const f3 total = c0 + (c1 + (c2 + mk(0.f, 0.f, 0.f)));
     const float r0 = clamp01(total.x), r1 = clamp01(total.y), r2 = clamp01(total.z);
     if (A.sshift == 0) {
@@ -1410,6 +1517,7 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
     }
     PH(PH_ACCUM);
   }
+  if constexpr (LIGHTS) return;  // (group_samples_add has written every slice)
   if (owner) accum[pix] = sum;
 }
 
@@ -1627,6 +1735,9 @@ __global__ __launch_bounds__(1024, 8) void k_trace_stream(DevScene S, const floa
 
 // ---------------------------------------------------------------- multi-view open-shutter frames (rt_render_views_shutter)
 #include "views_shutter_kernels.h"
+
+// ---------------------------------------------------------------- frames split by light group (rt_render_lights)
+#include "lights_kernels.h"
 
 // ---------------------------------------------------------------- frame assembly (multi-GPU)
 // A rank's owned 8x8-pixel granules, packed [granule][64 pixels] (row-major inside the

@@ -5,7 +5,7 @@
 // value is "Missing argument" unless it is -help; unknown flags throw; a mode other
 // than 0/1 silently becomes 0), plus build-defined extensions the reference has
 // no equivalent for: -scene, -meshdir, -seed, -gpu, -gpus, -devices, -accel,
-// -progress, -tune, -denoise, -aov, -adaptive, -pass, -ao, -aodist, -aperture, -focus, -shutter.
+// -progress, -tune, -denoise, -aov, -adaptive, -pass, -ao, -aodist, -aperture, -focus, -shutter, -lights.
 #pragma once
 
 #include <cstdlib>
@@ -44,6 +44,7 @@ class CommandLine {
   double aperture() const { return m_aperture; }
   double focus() const { return m_focus; }
   const std::string& shutter() const { return m_shutter; }
+  const std::string& lights() const { return m_lights; }
   size_t gpus() const { return m_gpus; }
   const std::string& devices() const { return m_devices; }
   const std::string& scene() const { return m_scene; }
@@ -69,6 +70,8 @@ class CommandLine {
                  "[-aperture <A: render through a thin lens of radius A in scene units (depth of field; default 0 = pinhole)>]"
                  "[-focus <D: distance of the plane of focus along the optical axis; required with -aperture>]"
                  "[-shutter <dx,dy,dz: the camera translates by this vector while the shutter is open (camera motion blur)>]"
+                 "[-lights <each | M0,M1,...: also write <output stem>_g<k>.ppm, the frame with only one light lit (each) or "
+                 "only the lights of mask Mk lit (bit l: light l), from one launch; at most 4 groups>]"
               << std::endl;
   }
 
@@ -108,6 +111,7 @@ class CommandLine {
       else if (flag == "-aperture") m_aperture = std::atof(value);
       else if (flag == "-focus") m_focus = std::atof(value);
       else if (flag == "-shutter") m_shutter = value;
+      else if (flag == "-lights") m_lights = value;
       else throw std::runtime_error("Unknown argument <" + flag + ">");
     }
     if (m_mode != 0 && m_mode != 1) m_mode = 0;
@@ -124,5 +128,5 @@ class CommandLine {
  private:
   size_t m_width, m_height, m_numRays, m_mode, m_numPhotons, m_k, m_seed, m_gpu, m_accel, m_progress, m_gpus, m_denoise, m_aov, m_pass, m_ao;
   double m_tune, m_adaptive, m_aoDist, m_aperture, m_focus;
-  std::string m_outputFilename, m_scene, m_meshDir, m_devices, m_shutter;
+  std::string m_outputFilename, m_scene, m_meshDir, m_devices, m_shutter, m_lights;
 };

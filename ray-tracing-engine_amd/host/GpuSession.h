@@ -87,6 +87,8 @@ struct GpuSettings {
   double focus = 0.;      // ... focused at this distance along the optical axis
   bool shutter = false;   // the frame under an open shutter (rt_render_shutter; single device, no photons, not adaptive) ...
   float shutterMove[3] = {0.f, 0.f, 0.f};  // ... while the camera translates by this vector; -aperture / -focus put the lens on it
+  bool lightsEach = false;            // also one frame per light (rt_render_lights: Renderer::lightGroups(); single device, plain frames only) ...
+  std::vector<unsigned> lightMasks;   // ... or one per mask of lights (bit l: light l is lit); at most RT_LIGHT_GROUPS_MAX groups
   std::vector<int> devices;  // more than one entry: Renderer::render tile-shards the frame over them (rt_group)
   static GpuSettings& get() {
     static GpuSettings s;

@@ -6,8 +6,10 @@
 #include <chrono>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <exception>
 #include <iostream>
+#include <string>
 
 #include "CommandLine.h"
 #include "Image.cpp"
@@ -99,6 +101,34 @@ int main(int argc, char** argv) {
     GpuSettings::get().shutter = true;
     for (int k = 0; k < 3; ++k) GpuSettings::get().shutterMove[k] = static_cast<float>(m[k]);
   }
+  if (!args.lights().empty()) {
+    // -lights each | M0,M1,...: one group per light, or groups by masks (decimal, 0x.. or 0..), and nothing else
+    if (args.lights() == "each") {
+      GpuSettings::get().lightsEach = true;
+    } else {
+      const char* s = args.lights().c_str();
+      for (;;) {
+        char* end = nullptr;
+        const unsigned long long m = std::strtoull(s, &end, 0);
+        if (end == s || *s == '-' || *s == '+' || m > 0xffffffffull || (*end != ',' && *end != '\0')) {
+          std::cerr << "error: -lights must be `each` or M0,M1,...: masks of lights (bit l: light l is lit)" << std::endl;
+          return 1;
+        }
+        GpuSettings::get().lightMasks.push_back(static_cast<unsigned>(m));
+        if (*end == '\0') break;
+        s = end + 1;
+      }
+      if (GpuSettings::get().lightMasks.size() > RT_LIGHT_GROUPS_MAX) {
+        std::cerr << "error: -lights takes at most " << RT_LIGHT_GROUPS_MAX << " groups per frame" << std::endl;
+        return 1;
+      }
+    }
+    if (GpuSettings::get().devices.size() > 1 || args.numPhotons() > 0 || args.adaptive() >= 0. || !args.shutter().empty() ||
+        args.aperture() > 0.) {
+      std::cerr << "error: -lights runs on one GPU, without -p, -adaptive, -shutter and -aperture" << std::endl;
+      return 1;
+    }
+  }
   if (args.adaptive() >= 0.) {
     if (GpuSettings::get().devices.size() > 1) {
       std::cerr << "error: -adaptive runs on one GPU only (not with -gpus > 1)" << std::endl;
@@ -131,6 +161,7 @@ int main(int argc, char** argv) {
     if (args.aov()) renderer.albedo().savePPM(stem + "_albedo.ppm"), renderer.normal().savePPM(stem + "_normal.ppm");
     if (args.adaptive() >= 0.) renderer.sppMap().savePPM(stem + "_spp.ppm");
     if (args.ao()) renderer.ao().savePPM(stem + "_ao.ppm");
+    for (size_t g = 0; g < renderer.lightGroups().size(); ++g) renderer.lightGroups()[g].savePPM(stem + "_g" + std::to_string(g) + ".ppm");
 
     const rt_stats& st = renderer.lastStats();
     const double rays = static_cast<double>(st.rays_closest + st.rays_shadow);

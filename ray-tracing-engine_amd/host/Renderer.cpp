@@ -3,8 +3,11 @@
 #pragma once
 #include "Renderer.h"
 
+#include <algorithm>
 #include <iostream>
 #include <memory>
+#include <stdexcept>
+#include <string>
 #include <vector>
 
 inline void Renderer::render(Image& image) {
@@ -221,5 +224,41 @@ inline void Renderer::render(Image& image) {
       const float v = hits[i] ? static_cast<float>(un[i]) / den : 1.f;
       for (int k = 0; k < 3; ++k) m_ao.data()[3 * i + k] = v;
     }
+  }
+
+  // -lights each | M0,M1,... (extension): this frame split by light group (rt_render_lights) — the frame with only one
+  // light lit, or only the lights of a mask, every group from the rays of ONE launch, resolved over the frame's
+  // background.  The frame itself stays as it is.
+  const bool each = GpuSettings::get().lightsEach;
+  std::vector<unsigned> masks = GpuSettings::get().lightMasks;
+  if ((each || !masks.empty()) && (multi || p.use_photons || GpuSettings::get().adaptive >= 0. || GpuSettings::get().shutter ||
+                                   GpuSettings::get().aperture > 0.))
+    throw std::runtime_error("-lights runs on one GPU, without -p, -adaptive, -shutter and -aperture");
+  if (each) {
+    const size_t nl = m_scene.lightsources().size();
+    if (nl == 0 || nl > RT_LIGHT_GROUPS_MAX)
+      throw std::runtime_error("-lights each: the scene has " + std::to_string(nl) + " lights and a frame takes 1.." +
+                               std::to_string(RT_LIGHT_GROUPS_MAX) + " groups (use -lights M0,M1,...)");
+    for (size_t l = 0; l < nl; ++l) masks.push_back(1u << l);
+  }
+  m_groups.clear();
+  if (!masks.empty() && p.spp > 0) {
+    p.spp_begin = 0, p.spp_count = 0;
+    rt_light_groups lg = {};
+    lg.n_groups = static_cast<uint32_t>(masks.size());
+    for (size_t g = 0; g < masks.size(); ++g) lg.masks[g] = masks[g];
+    const size_t npx = static_cast<size_t>(w) * h;
+    std::vector<float> out(3 * npx * masks.size());
+    rt_stats st = {};
+    // (the background the frame was resolved over: `image` holds the frame by now)
+    Image bg(w, h);
+    bg.fillBackground();
+    GpuSession::check(rt_render_lights(ctx0, &p, &lg, bg.data(), out.data(), nullptr, &st), "rt_render_lights");
+    for (size_t g = 0; g < masks.size(); ++g) {
+      m_groups.emplace_back(w, h);
+      std::copy(out.begin() + 3 * npx * g, out.begin() + 3 * npx * (g + 1), m_groups.back().data());
+    }
+    std::cout << "Light groups: " << masks.size() << " frames from one launch, " << static_cast<double>(st.rays_closest + st.rays_shadow) / 1e6
+              << " Mrays in " << st.kernel_ms << " ms" << std::endl;
   }
 }

@@ -17,6 +17,7 @@
 #pragma once
 
 #include <string>
+#include <vector>
 
 #include "GpuSession.h"
 #include "Image.h"
@@ -49,6 +50,8 @@ class Renderer {
   const Image& sppMap() const { return m_spp; }
   // GpuSettings::ao: the share of the occlusion rays that escaped (grey; 1 where no sample hit) of the last render()
   const Image& ao() const { return m_ao; }
+  // GpuSettings::lightsEach / lightMasks: the frame with only the lights of group k lit, of the last render()
+  const std::vector<Image>& lightGroups() const { return m_groups; }
 
  private:
   int m_numRays, m_mode, m_numPhotons, m_k;
@@ -58,4 +61,5 @@ class Renderer {
   float m_factor = 100.f;
   rt_stats m_stats = {};
   Image m_denoised, m_albedo, m_normal, m_spp, m_ao;
+  std::vector<Image> m_groups;
 };

@@ -191,6 +191,14 @@ class Shutter(C.Structure):
                 ("focus_distance", C.c_float), ("reserved", C.c_uint32 * 4)]
 
 
+LIGHT_GROUPS_MAX = 4
+
+
+class LightGroups(C.Structure):
+    """rt_light_groups: the groups of rt_render_lights — bit l of masks[g] says that light l is lit in group g."""
+    _fields_ = [("n_groups", C.c_uint32), ("masks", C.c_uint32 * LIGHT_GROUPS_MAX), ("reserved", C.c_uint32 * 3)]
+
+
 class DenoiseParams(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("iterations", C.c_uint32), ("sigma_color", C.c_float),
                 ("sigma_normal", C.c_float), ("sigma_position", C.c_float), ("reserved", C.c_uint32 * 6)]
@@ -390,7 +398,8 @@ AMD_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_create", "rt_destroy", "rt
                "rt_denoise_batch", "rt_denoise_batch_device", "rt_render_ao", "rt_render_ao_device", "rt_render_rays",
                "rt_render_rays_device", "rt_render_lens", "rt_render_lens_device", "rt_render_shutter",
                "rt_render_shutter_device", "rt_render_views_shutter", "rt_render_views_shutter_device",
-               "rt_render_adaptive_shutter", "rt_render_adaptive_shutter_device"]
+               "rt_render_adaptive_shutter", "rt_render_adaptive_shutter_device", "rt_render_lights",
+               "rt_render_lights_device"]
 HOST_SYMBOLS = ["rt_host_scene_build", "rt_host_scene_desc", "rt_host_scene_free", "rt_host_last_error",
                 "rt_host_fill_background", "rt_host_save_ppm", "rt_host_kd_order", "rt_host_light_basis"]
 
@@ -427,6 +436,18 @@ def make_shutter(camera_close, open=0.0, close=1.0, aperture=0.0, focus_distance
     C.memmove(C.byref(s.camera_close), cam.ctypes.data, 48)
     s.open, s.close, s.aperture, s.focus_distance = open, close, aperture, focus_distance
     return s
+
+
+def make_light_groups(masks):
+    """An rt_light_groups: one group per entry of `masks` (bit l: light l is lit in that group), in that order."""
+    masks = [int(m) for m in masks]
+    if len(masks) > LIGHT_GROUPS_MAX:
+        raise ValueError("%d groups: rt_render_lights takes at most %d per call" % (len(masks), LIGHT_GROUPS_MAX))
+    g = LightGroups()
+    g.n_groups = len(masks)
+    for j, m in enumerate(masks):
+        g.masks[j] = m
+    return g
 
 
 def make_shutters(shutters, n):
@@ -514,6 +535,10 @@ def amd():
                                         C.POINTER(Stats)]
         L.rt_render_shutter_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Shutter), C.c_void_p, C.c_void_p,
                                                C.POINTER(Stats)]
+        L.rt_render_lights.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(LightGroups), C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.POINTER(Stats)]
+        L.rt_render_lights_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(LightGroups), C.c_void_p, C.c_void_p,
+                                              C.POINTER(Stats)]
         L.rt_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.POINTER(Aov), C.c_void_p]
         L.rt_render_adaptive.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(AdaptiveParams), C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.POINTER(AdaptiveReport), C.POINTER(Stats)]
@@ -1020,6 +1045,29 @@ class Context:
         st = Stats() if stats else None
         _check(amd().rt_render_shutter_device(self._h, C.byref(params), C.byref(shutter), C.c_void_p(d_accum), C.c_void_p(stream or None),
                                               C.byref(st) if stats else None))
+        return st
+
+    def render_lights(self, params, groups, bg=None, want_accum=True):
+        """rt_render_lights: the frame split by light group (`groups`: make_light_groups, or a sequence of masks); returns
+        (out [G][h][w][3] or None without bg, accum [G][h][w][4] or None, stats): slice g is the frame with only the
+        lights of masks[g] lit, and the stats are one frame's."""
+        if not isinstance(groups, LightGroups):
+            groups = make_light_groups(groups)
+        w, h, n = params.width, params.height, max(1, groups.n_groups)
+        out = np.empty((n, h, w, 3), np.float32) if bg is not None else None
+        acc = np.empty((n, h, w, 4), np.float32) if want_accum else None
+        st = Stats()
+        bgc = None if bg is None else np.ascontiguousarray(bg, np.float32)
+        _check(amd().rt_render_lights(self._h, C.byref(params), C.byref(groups), _ptr(bgc), _ptr(out), _ptr(acc), C.byref(st)))
+        return out, acc, st
+
+    def render_lights_device(self, params, groups, d_accum, stream=0, stats=False):
+        """rt_render_lights_device: accumulate into the caller-zeroed device d_accum [G][h][w][4] on `stream`; sample ranges chain."""
+        if not isinstance(groups, LightGroups):
+            groups = make_light_groups(groups)
+        st = Stats() if stats else None
+        _check(amd().rt_render_lights_device(self._h, C.byref(params), C.byref(groups), C.c_void_p(d_accum), C.c_void_p(stream or None),
+                                             C.byref(st) if stats else None))
         return st
 
     def render_views_shutter(self, params, cameras, shutters, bg=None, seeds=None, want_accum=True):
