@@ -1,0 +1,126 @@
+// frame_variants.h — the frame integrator with another generator or another split of its samples: rt_render_lens,
+// rt_render_shutter, rt_render_views_shutter and rt_render_lights (DESIGN.md §6m–§6p).
+//
+// Every variant is render_tile itself under one more LT_* bit, on the one-wave-per-workgroup family that k_render serves:
+// brute, sequential and pooled, each counted (STATS, one wave per SIMD) and timed (four waves per SIMD, k_render's target);
+// none with LT_FASTDET (they divide: the operand bounds of the short forms were proved for the context's camera only),
+// none persistent.  The lane layout, the sample hand-over and the vertex pool are the frame's, so reserved[0] and
+// reserved[1] mean what they mean there.  What a variant's kernels read beyond the frame's arguments travels as ONE
+// record, a kernel argument of its own (k_render_rec): RenderArgs and the frame's entry points stay as they are, and a
+// test on the record is a scalar one.
+//   lens          LT_LENS                LensRec: lens_ray in place of camera_ray where aperture > 0 (a wave-uniform test;
+//                                        aperture == 0 is rt_render's frame bit for bit)
+//   shutter       LT_SHUTTER             ShutterRec: every sample draws a time, forms its camera in registers and casts
+//                                        that camera's primary ray by shutter_ray, through the lens where aperture > 0
+//   light groups  LT_LIGHTS              LightGroupsRec: everything up to the light loop of a vertex runs ONCE for all
+//                                        groups, which differ only in the terms added (vertex_pool's and shade_direct_seq's
+//                                        GROUPS switch); the sample hand-over grows to LG_EX_ROWS rows (group_samples_add)
+//   views+shutter LT_VIEWS | LT_SHUTTER  no record: the tile's view picks its ViewRec and, from the table parallel to
+//                                        views (RenderArgs::viewShutters), its shutter record, by scalar loads; these are
+//                                        plain k_render instances
+// A new variant supplies a row of the same kind (a struct below, a FrameVariant kind, a case in launch_render_variant):
+// its LT_* bits, its record, the stack rows its sample hand-over needs, and its argument check.
+// (included by rt_kernels.hip inside namespace rtk: shares its device functions)
+
+static_assert(LG_EX_ROWS * BLOCK <= VP_WORDS, "the pooled instances hand the groups' samples over in the pool's words");
+
+// k_render (no photons) with the variant's record R beside its arguments
+template <bool BRUTE, bool POOLED, bool STATS, int MINW, int LTV, class REC>
+__global__ __launch_bounds__(BLOCK, MINW) void k_render_rec(DevScene S, RenderArgs A, REC R, float4* __restrict__ accum,
+                                                            unsigned long long* __restrict__ counters) {
+  static_assert(!POOLED || !BRUTE, "the vertex pool serves BVH direct lighting");
+  // dynamic LDS as k_render's: [levels][64] traversal stack, then (POOLED) the ray pool; without a pool the sample
+  // hand-over area lies in the first stack rows
+  uint32_t* lds = g_lds;
+  const Lds L = carve_lds<false>(lds, A.stackLevels, 0);
+  uint32_t* pool = lds + A.stackLevels * BLOCK;
+  float* ex = reinterpret_cast<float*>(POOLED ? pool : lds);
+  LaneStats st;
+  const uint32_t t0 = blockIdx.x * A.tilesPerBlock, t1 = min(A.n_tiles, t0 + A.tilesPerBlock);
+  for (uint32_t t = t0; t < t1; ++t) render_tile<BRUTE, false, POOLED, STATS, LTV>(S, A, accum, L, pool, ex, t, st, &R);
+  if (STATS) flush_stats(st, counters, true);
+  else flush_stats_striped(st, counters);  // (launch_variant2 folds the stripes)
+}
+
+// The variants' rows.  ROWS, ROWS_POOLED: the fewest stack rows a launch without / with a vertex pool allocates (the
+// hand-over area lies in the stack rows without a pool, in the pool's words with one: launch_render2's four in both
+// cases, LG_EX_ROWS and none for the light groups).  refused: the arguments the launcher answers hipErrorInvalidValue to.
+struct VariantLens {
+  static constexpr int LTV = LT_LENS;
+  using Rec = LensRec;
+  static constexpr uint32_t ROWS = 4, ROWS_POOLED = 4;
+  static bool refused(const DevScene&, const RenderArgs& A, const Rec&) { return A.tileView != nullptr; }  // (no multi-view lens frames)
+};
+struct VariantShutter {
+  static constexpr int LTV = LT_SHUTTER;
+  using Rec = ShutterRec;
+  static constexpr uint32_t ROWS = 4, ROWS_POOLED = 4;
+  static bool refused(const DevScene&, const RenderArgs& A, const Rec&) { return A.tileView != nullptr; }  // (those are VariantViewsShutter's)
+};
+struct VariantLights {
+  static constexpr int LTV = LT_LIGHTS;
+  using Rec = LightGroupsRec;
+  static constexpr uint32_t ROWS = LG_EX_ROWS, ROWS_POOLED = 0;
+  static bool refused(const DevScene& S, const RenderArgs& A, const Rec& G) {
+    return A.tileView || G.n < 1u || G.n > (uint32_t)RT_LIGHT_GROUPS_MAX || S.n_lights > 32u;
+  }
+};
+struct VariantViewsShutter {
+  static constexpr int LTV = LT_VIEWS | LT_SHUTTER;
+  using Rec = NoRec;
+  static constexpr uint32_t ROWS = 4, ROWS_POOLED = 4;
+  // (the three tables of a multi-view shutter frame)
+  static bool refused(const DevScene&, const RenderArgs& A, const Rec&) { return !A.tileView || !A.views || !A.viewShutters; }
+};
+
+template <class V, bool BRUTE, bool POOLED, bool STATS, int MINW>
+static void launch_variant_instance(size_t ldsBytes, hipStream_t stream, const DevScene& S, const RenderArgs& A,
+                                    const typename V::Rec& R, float4* accum, unsigned long long* counters) {
+  if constexpr (std::is_same_v<typename V::Rec, NoRec>)
+    hipLaunchKernelGGL((k_render<BRUTE, false, POOLED, STATS, MINW, V::LTV>), dim3(A.n_tiles), dim3(BLOCK), ldsBytes, stream, S, A, accum, counters);
+  else
+    hipLaunchKernelGGL((k_render_rec<BRUTE, POOLED, STATS, MINW, V::LTV, typename V::Rec>), dim3(A.n_tiles), dim3(BLOCK), ldsBytes, stream, S, A, R, accum, counters);
+}
+
+template <class V, bool BRUTE, bool POOLED>
+static hipError_t launch_variant2(bool stats, const DevScene& S, const RenderArgs& A, const typename V::Rec& R, float4* accum,
+                                  unsigned long long* counters, hipStream_t stream) {
+  if (A.n_tiles == 0) return hipSuccess;
+  constexpr uint32_t minRows = POOLED ? V::ROWS_POOLED : V::ROWS;
+  const size_t ldsBytes = 4u * ((A.stackLevels < minRows ? minRows : A.stackLevels) * BLOCK + (POOLED ? VP_WORDS : 0));
+  RenderArgs A1 = A;
+  A1.tilesPerBlock = 1u;
+  if (stats) {
+    launch_variant_instance<V, BRUTE, POOLED, true, 1>(ldsBytes, stream, S, A1, R, accum, counters);
+  } else {
+    launch_variant_instance<V, BRUTE, POOLED, false, 4>(ldsBytes, stream, S, A1, R, accum, counters);
+    hipLaunchKernelGGL(k_fold_stripes, dim3(1), dim3(1024), 0, stream, counters);
+  }
+  return hipGetLastError();
+}
+
+template <class V>
+static hipError_t launch_variant(bool brute_force, bool stats, const DevScene& S, const RenderArgs& A, const typename V::Rec& R,
+                                 float4* accum, unsigned long long* counters, hipStream_t stream) {
+  if (V::refused(S, A, R)) return hipErrorInvalidValue;
+  if (brute_force) return launch_variant2<V, true, false>(stats, S, A, R, accum, counters, stream);
+  // the vertex pool handles up to POOL_L lights, as in launch_render
+  if ((A.flags & 1u) && S.n_lights <= (uint32_t)POOL_L) return launch_variant2<V, false, true>(stats, S, A, R, accum, counters, stream);
+  return launch_variant2<V, false, false>(stats, S, A, R, accum, counters, stream);
+}
+
+hipError_t launch_render_variant(const FrameVariant& F, bool brute_force, bool stats, const DevScene& S, const RenderArgs& A,
+                                 float4* accum, unsigned long long* counters, hipStream_t stream) {
+  switch (F.kind) {
+    case FrameVariant::LENS:
+      return launch_variant<VariantLens>(brute_force, stats, S, A, *static_cast<const LensRec*>(F.rec), accum, counters, stream);
+    case FrameVariant::SHUTTER:
+      return launch_variant<VariantShutter>(brute_force, stats, S, A, *static_cast<const ShutterRec*>(F.rec), accum, counters, stream);
+    case FrameVariant::LIGHTS:
+      return launch_variant<VariantLights>(brute_force, stats, S, A, *static_cast<const LightGroupsRec*>(F.rec), accum, counters, stream);
+    case FrameVariant::VIEWS_SHUTTER:
+      return launch_variant<VariantViewsShutter>(brute_force, stats, S, A, NoRec(), accum, counters, stream);
+    case FrameVariant::NONE: break;
+  }
+  return hipErrorInvalidValue;  // (the plain frame is launch_render's)
+}

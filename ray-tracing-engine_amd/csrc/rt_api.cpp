@@ -658,18 +658,14 @@ struct TileList {
   const rtk::ViewShutterRec* viewShutters = nullptr;
 };
 
-// What forms a frame's primary rays in place of camera_ray, if anything: the thin lens of rt_render_lens or the open
-// shutter of rt_render_shutter, at most one of them (their callers have refused photons and the wavefront bit).  A
-// multi-view shutter frame carries its records in its TileList instead.  groups: the frame split by light group
-// (rt_render_lights), with camera_ray's primary rays: dAccum then holds one slice per group.
-struct FrameGen {
-  const rtk::LensRec* lens = nullptr;
-  const rtk::ShutterRec* shutter = nullptr;
-  const rtk::LightGroupsRec* groups = nullptr;
-};
+// What forms or splits a frame's samples in place of the plain frame, if anything: the thin lens of rt_render_lens, the
+// open shutter of rt_render_shutter or the light groups of rt_render_lights (dAccum then holds one slice per group), with
+// the record its kernels take; their callers have refused photons and the wavefront bit.  A multi-view shutter frame
+// carries its records in its TileList instead: launch_frame tells it from them.
+using FrameGen = rtk::FrameVariant;
 
 // Launch the integrate kernel for p on `stream`, bracketed by an event pair.  own: render those wave tiles only.
-// gen: the frame through a thin lens or under an open shutter.
+// gen: the frame's variant, if any.
 int launch_frame(rt_ctx* c, const rt_params* p, float4* dAccum, hipStream_t stream, int* evIndex,
                  const TileList* own = nullptr, const FrameGen& gen = FrameGen()) {
   const SampleRange sr = sample_range(*p);
@@ -707,22 +703,10 @@ int launch_frame(rt_ctx* c, const rt_params* p, float4* dAccum, hipStream_t stre
   rtk::WfArgs W{};
   if (wavefront && (rc = wavefront_args(c, p, A, sr.count, stream, &W)) != RT_OK) return rc;
   return timed_launch(c, stream, evIndex, [&] {
-    if (A.viewShutters) {
-      hipError_t he = rtk::launch_render_views_shutter(p->accel == RT_ACCEL_BRUTE, p->collect_stats != 0, c->S, A, dAccum,
-                                                       c->dCounters.get(), stream);
-      if (he != hipSuccess) return fail(RT_ERR_HIP, "multi-view shutter render launch failed: %s", hipGetErrorString(he));
-    } else if (gen.lens) {
-      hipError_t he = rtk::launch_render_lens(p->accel == RT_ACCEL_BRUTE, p->collect_stats != 0, c->S, A, *gen.lens, dAccum,
-                                              c->dCounters.get(), stream);
-      if (he != hipSuccess) return fail(RT_ERR_HIP, "lens render launch failed: %s", hipGetErrorString(he));
-    } else if (gen.shutter) {
-      hipError_t he = rtk::launch_render_shutter(p->accel == RT_ACCEL_BRUTE, p->collect_stats != 0, c->S, A, *gen.shutter,
-                                                 dAccum, c->dCounters.get(), stream);
-      if (he != hipSuccess) return fail(RT_ERR_HIP, "shutter render launch failed: %s", hipGetErrorString(he));
-    } else if (gen.groups) {
-      hipError_t he = rtk::launch_render_lights(p->accel == RT_ACCEL_BRUTE, p->collect_stats != 0, c->S, A, *gen.groups, dAccum,
-                                                c->dCounters.get(), stream);
-      if (he != hipSuccess) return fail(RT_ERR_HIP, "light-group render launch failed: %s", hipGetErrorString(he));
+    if (const FrameGen V = A.viewShutters ? FrameGen(FrameGen::VIEWS_SHUTTER) : gen) {
+      hipError_t he = rtk::launch_render_variant(V, p->accel == RT_ACCEL_BRUTE, p->collect_stats != 0, c->S, A, dAccum,
+                                                 c->dCounters.get(), stream);
+      if (he != hipSuccess) return fail(RT_ERR_HIP, "%s render launch failed: %s", V.name(), hipGetErrorString(he));
     } else if (!wavefront) {
       hipError_t he = rtk::launch_render(p->accel == RT_ACCEL_BRUTE, p->use_photons != 0, p->collect_stats != 0, c->S, A,
                                          dAccum, c->dCounters.get(), stream);
@@ -1137,6 +1121,30 @@ int frame_device(rt_ctx* c, const rt_params* p, const FrameGen& gen, void* d_acc
   });
   return frame_stats(c, s, e, px * sample_range(*p).count, stats);
 }
+
+// What a host form that may return the image, the accumulator or both refuses about its outputs (else null): the
+// `outputs` text its checks report in their place.
+const char* outputs_refused(const float* bg, const float* out_rgb, const float* accum_out) {
+  return !out_rgb && !accum_out ? "neither out_rgb nor accum_out is given"
+         : out_rgb && !bg       ? "out_rgb requested without a background image"
+                                : nullptr;
+}
+
+// The host form of a frame, after its checks: frame_device into a zeroed accumulator of nSlices slices (accum_out's
+// staging), every slice resolved over bg where out_rgb is asked for, and the results brought down.
+int frame_host(rt_ctx* c, const rt_params* p, const FrameGen& gen, uint32_t nSlices, const float* bg, float* out_rgb,
+               float* accum_out, rt_stats* stats) {
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t npx = (size_t)p->width * p->height;
+  Staging st;
+  float4* dAccum = st.zeroed<float4>(accum_out, nSlices * npx);
+  if (st.rc != RT_OK) return st.rc;
+  rt_stats local;
+  int rc = frame_device(c, p, gen, dAccum, nullptr, stats ? stats : &local);
+  if (rc != RT_OK) return rc;
+  if ((rc = stage_resolve(&st, bg, out_rgb, dAccum, nSlices, npx, p->spp)) != RT_OK) return rc;
+  return st.download();
+}
 }  // namespace
 
 extern "C" {
@@ -1226,15 +1234,7 @@ int rt_render(rt_ctx* c, const rt_params* p, const float* bg, float* out_rgb, fl
   int rc = check_params(c, p);
   if (rc != RT_OK) return rc;
   if (out_rgb && !bg) return fail(RT_ERR_INVALID, "out_rgb requested without a background image");
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t npx = (size_t)p->width * p->height;
-  Staging st;
-  float4* dAccum = st.zeroed<float4>(accum_out, npx);
-  if (st.rc != RT_OK) return st.rc;
-  rt_stats local;
-  if ((rc = rt_render_device(c, p, dAccum, nullptr, stats ? stats : &local)) != RT_OK) return rc;
-  if ((rc = stage_resolve(&st, bg, out_rgb, dAccum, 1, npx, p->spp)) != RT_OK) return rc;
-  return st.download();
+  return frame_host(c, p, FrameGen(), 1, bg, out_rgb, accum_out, stats);
 }
 
 int rt_render_passes(rt_ctx* c, const rt_params* p, const float* bg, float* accum_io, float* out_rgb, rt_stats* stats) {
@@ -3091,7 +3091,7 @@ int rt_render_adaptive_shutter_device(rt_ctx* c, const rt_params* p, const rt_ad
   rtk::ShutterRec S;
   const int rc = adaptive_shutter_checks(c, p, a, sh, d_bg && d_accum && d_out, &R, &S);
   if (rc != RT_OK) return rc;
-  return adaptive_run(c, p, R, FrameGen{nullptr, &S}, d_bg, d_accum, d_out, d_spp, stream, rep, stats, t0);
+  return adaptive_run(c, p, R, S, d_bg, d_accum, d_out, d_spp, stream, rep, stats, t0);
 }
 
 int rt_render_adaptive_shutter(rt_ctx* c, const rt_params* p, const rt_adaptive_params* a, const rt_shutter* sh, const float* bg,
@@ -3101,7 +3101,7 @@ int rt_render_adaptive_shutter(rt_ctx* c, const rt_params* p, const rt_adaptive_
   rtk::ShutterRec S;
   const int rc = adaptive_shutter_checks(c, p, a, sh, bg && out_rgb, &R, &S);
   if (rc != RT_OK) return rc;
-  return adaptive_host(c, p, R, FrameGen{nullptr, &S}, bg, out_rgb, accum_out, spp_out, rep, stats, t0);
+  return adaptive_host(c, p, R, S, bg, out_rgb, accum_out, spp_out, rep, stats, t0);
 }
 
 }  // extern "C"
@@ -3219,6 +3219,44 @@ int upload_views(rt_ctx* c, const rt_params* p, const rt_views* v, const rt_came
   return RT_OK;
 }
 
+// The multi-view frame of checked p and v into d_accum on `stream`, behind rt_render_views_device and both forms of
+// rt_render_views_shutter: pad and refit as views_checks (or views_shutter_checks) left them; shutters: the views'
+// shutter records, the third table of a multi-view shutter frame, or null.
+int views_frame_device(rt_ctx* c, const rt_params* p, const rt_views* v, const rtk::ViewShutterRec* shutters, const rtbvh::Padding& pad,
+                       bool refit, void* d_accum, void* stream, rt_stats* stats) {
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  int rc;
+  if (refit && (rc = refit_to_padding(c, pad, s)) != RT_OK) return rc;
+  const uint32_t n = v->n_views;
+  const uint32_t sppCount = sample_range(*p).count;
+  const uint32_t sshift = choose_sshift_px(c, p, (uint64_t)n * p->width * p->height, sppCount);
+  if ((rc = ensure_view_tiles(c, p, sshift, n, s)) != RT_OK) return rc;
+  if ((rc = upload_views(c, p, v, nullptr, s, shutters)) != RT_OK) return rc;
+  if (stats) HIP_TRY(hipMemsetAsync(c->dCounters.get(), 0, RTK_CNT_COUNT * sizeof(unsigned long long), s));
+  TileList own = {c->vwTiles.d.get(), c->vwNTiles, sshift};
+  own.tileView = c->vwTileView.d.get(), own.views = c->vwRecs.get(), own.viewShutters = shutters ? c->vwShutters.get() : nullptr;
+  int e = 0;
+  if ((rc = launch_frame(c, p, static_cast<float4*>(d_accum), s, &e, &own)) != RT_OK) return rc;
+  return stats ? frame_stats(c, s, e, (uint64_t)n * p->width * p->height * sppCount, stats) : (int)RT_OK;
+}
+
+// The host form of such a frame, after its checks: frame_host's steps over one accumulator slice per view, each view
+// resolved over its slice with the shared background.
+int views_frame_host(rt_ctx* c, const rt_params* p, const rt_views* v, const rtk::ViewShutterRec* shutters, const rtbvh::Padding& pad,
+                     bool refit, const float* bg, float* out_rgb, float* accum_out, rt_stats* stats) {
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t npx = (size_t)p->width * p->height, all = npx * v->n_views;
+  Staging st;
+  float4* dAccum = st.zeroed<float4>(accum_out, all);
+  if (st.rc != RT_OK) return st.rc;
+  rt_stats local;
+  int rc = views_frame_device(c, p, v, shutters, pad, refit, dAccum, nullptr, stats ? stats : &local);
+  if (rc != RT_OK) return rc;
+  if ((rc = stage_resolve(&st, bg, out_rgb, dAccum, v->n_views, npx, p->spp)) != RT_OK) return rc;
+  return st.download();
+}
+
 }  // namespace
 
 extern "C" {
@@ -3229,20 +3267,7 @@ int rt_render_views_device(rt_ctx* c, const rt_params* p, const rt_views* v, voi
   int rc = views_checks(c, p, v, &pad, &refit);
   if (rc != RT_OK) return rc;
   if (!d_accum) return fail(RT_ERR_INVALID, "d_accum is null");
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (refit && (rc = refit_to_padding(c, pad, s)) != RT_OK) return rc;
-  const uint32_t n = v->n_views;
-  const uint32_t sppCount = sample_range(*p).count;
-  const uint32_t sshift = choose_sshift_px(c, p, (uint64_t)n * p->width * p->height, sppCount);
-  if ((rc = ensure_view_tiles(c, p, sshift, n, s)) != RT_OK) return rc;
-  if ((rc = upload_views(c, p, v, nullptr, s)) != RT_OK) return rc;
-  if (stats) HIP_TRY(hipMemsetAsync(c->dCounters.get(), 0, RTK_CNT_COUNT * sizeof(unsigned long long), s));
-  TileList own = {c->vwTiles.d.get(), c->vwNTiles, sshift};
-  own.tileView = c->vwTileView.d.get(), own.views = c->vwRecs.get();
-  int e = 0;
-  if ((rc = launch_frame(c, p, static_cast<float4*>(d_accum), s, &e, &own)) != RT_OK) return rc;
-  return stats ? frame_stats(c, s, e, (uint64_t)n * p->width * p->height * sppCount, stats) : (int)RT_OK;
+  return views_frame_device(c, p, v, nullptr, pad, refit, d_accum, stream, stats);
 }
 
 int rt_render_views(rt_ctx* c, const rt_params* p, const rt_views* v, const float* bg, float* out_rgb, float* accum_out,
@@ -3252,16 +3277,7 @@ int rt_render_views(rt_ctx* c, const rt_params* p, const rt_views* v, const floa
   int rc = views_checks(c, p, v, &pad, &refit);
   if (rc != RT_OK) return rc;
   if (out_rgb && !bg) return fail(RT_ERR_INVALID, "out_rgb requested without a background image");
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t npx = (size_t)p->width * p->height, all = npx * v->n_views;
-  Staging st;
-  float4* dAccum = st.zeroed<float4>(accum_out, all);
-  if (st.rc != RT_OK) return st.rc;
-  rt_stats local;
-  if ((rc = rt_render_views_device(c, p, v, dAccum, nullptr, stats ? stats : &local)) != RT_OK) return rc;
-  // each view resolved over its slice, with the shared background
-  if ((rc = stage_resolve(&st, bg, out_rgb, dAccum, v->n_views, npx, p->spp)) != RT_OK) return rc;
-  return st.download();
+  return views_frame_host(c, p, v, nullptr, pad, refit, bg, out_rgb, accum_out, stats);
 }
 
 }  // extern "C"
@@ -3572,24 +3588,14 @@ int rt_render_lens_device(rt_ctx* c, const rt_params* p, const rt_lens* l, void*
   rtk::LensRec R;
   const int rc = lens_checks(c, p, l, d_accum ? nullptr : "d_accum is null", &R);
   if (rc != RT_OK) return rc;
-  return frame_device(c, p, FrameGen{&R, nullptr}, d_accum, stream, stats);
+  return frame_device(c, p, R, d_accum, stream, stats);
 }
 
 int rt_render_lens(rt_ctx* c, const rt_params* p, const rt_lens* l, const float* bg, float* out_rgb, float* accum_out, rt_stats* stats) {
   rtk::LensRec R;
-  int rc = lens_checks(c, p, l, !out_rgb && !accum_out ? "neither out_rgb nor accum_out is given"
-                                : out_rgb && !bg     ? "out_rgb requested without a background image"
-                                                     : nullptr, &R);
+  const int rc = lens_checks(c, p, l, outputs_refused(bg, out_rgb, accum_out), &R);
   if (rc != RT_OK) return rc;
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t npx = (size_t)p->width * p->height;
-  Staging st;
-  float4* dAccum = st.zeroed<float4>(accum_out, npx);
-  if (st.rc != RT_OK) return st.rc;
-  rt_stats local;
-  if ((rc = frame_device(c, p, FrameGen{&R, nullptr}, dAccum, nullptr, stats ? stats : &local)) != RT_OK) return rc;
-  if ((rc = stage_resolve(&st, bg, out_rgb, dAccum, 1, npx, p->spp)) != RT_OK) return rc;
-  return st.download();
+  return frame_host(c, p, R, 1, bg, out_rgb, accum_out, stats);
 }
 
 // ---- the frame under an open shutter
@@ -3597,24 +3603,14 @@ int rt_render_shutter_device(rt_ctx* c, const rt_params* p, const rt_shutter* sh
   rtk::ShutterRec R;
   const int rc = shutter_checks(c, p, sh, d_accum ? nullptr : "d_accum is null", &R);
   if (rc != RT_OK) return rc;
-  return frame_device(c, p, FrameGen{nullptr, &R}, d_accum, stream, stats);
+  return frame_device(c, p, R, d_accum, stream, stats);
 }
 
 int rt_render_shutter(rt_ctx* c, const rt_params* p, const rt_shutter* sh, const float* bg, float* out_rgb, float* accum_out, rt_stats* stats) {
   rtk::ShutterRec R;
-  int rc = shutter_checks(c, p, sh, !out_rgb && !accum_out ? "neither out_rgb nor accum_out is given"
-                                    : out_rgb && !bg     ? "out_rgb requested without a background image"
-                                                         : nullptr, &R);
+  const int rc = shutter_checks(c, p, sh, outputs_refused(bg, out_rgb, accum_out), &R);
   if (rc != RT_OK) return rc;
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t npx = (size_t)p->width * p->height;
-  Staging st;
-  float4* dAccum = st.zeroed<float4>(accum_out, npx);
-  if (st.rc != RT_OK) return st.rc;
-  rt_stats local;
-  if ((rc = frame_device(c, p, FrameGen{nullptr, &R}, dAccum, nullptr, stats ? stats : &local)) != RT_OK) return rc;
-  if ((rc = stage_resolve(&st, bg, out_rgb, dAccum, 1, npx, p->spp)) != RT_OK) return rc;
-  return st.download();
+  return frame_host(c, p, R, 1, bg, out_rgb, accum_out, stats);
 }
 
 }  // extern "C"
@@ -3659,25 +3655,15 @@ int rt_render_lights_device(rt_ctx* c, const rt_params* p, const rt_light_groups
   rtk::LightGroupsRec R;
   const int rc = lights_checks(c, p, g, d_accum ? nullptr : "d_accum is null", &R);
   if (rc != RT_OK) return rc;
-  return frame_device(c, p, FrameGen{nullptr, nullptr, &R}, d_accum, stream, stats);
+  return frame_device(c, p, R, d_accum, stream, stats);
 }
 
 int rt_render_lights(rt_ctx* c, const rt_params* p, const rt_light_groups* g, const float* bg, float* out_rgb, float* accum_out,
                      rt_stats* stats) {
   rtk::LightGroupsRec R;
-  int rc = lights_checks(c, p, g, !out_rgb && !accum_out ? "neither out_rgb nor accum_out is given"
-                                  : out_rgb && !bg     ? "out_rgb requested without a background image"
-                                                       : nullptr, &R);
+  const int rc = lights_checks(c, p, g, outputs_refused(bg, out_rgb, accum_out), &R);
   if (rc != RT_OK) return rc;
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t npx = (size_t)p->width * p->height;
-  Staging st;
-  float4* dAccum = st.zeroed<float4>(accum_out, R.n * npx);
-  if (st.rc != RT_OK) return st.rc;
-  rt_stats local;
-  if ((rc = frame_device(c, p, FrameGen{nullptr, nullptr, &R}, dAccum, nullptr, stats ? stats : &local)) != RT_OK) return rc;
-  if ((rc = stage_resolve(&st, bg, out_rgb, dAccum, R.n, npx, p->spp)) != RT_OK) return rc;
-  return st.download();
+  return frame_host(c, p, R, R.n, bg, out_rgb, accum_out, stats);
 }
 
 }  // extern "C"
@@ -3727,26 +3713,6 @@ int views_shutter_checks(rt_ctx* c, const rt_params* p, const rt_views* v, const
   return RT_OK;
 }
 
-// The launch behind both forms, after the checks (rt_render_views_device's steps with the third table)
-int views_shutter_device(rt_ctx* c, const rt_params* p, const rt_views* v, const std::vector<rtk::ViewShutterRec>& recs,
-                         const rtbvh::Padding& pad, bool refit, void* d_accum, void* stream, rt_stats* stats) {
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  int rc;
-  if (refit && (rc = refit_to_padding(c, pad, s)) != RT_OK) return rc;
-  const uint32_t n = v->n_views;
-  const uint32_t sppCount = sample_range(*p).count;
-  const uint32_t sshift = choose_sshift_px(c, p, (uint64_t)n * p->width * p->height, sppCount);
-  if ((rc = ensure_view_tiles(c, p, sshift, n, s)) != RT_OK) return rc;
-  if ((rc = upload_views(c, p, v, nullptr, s, recs.data())) != RT_OK) return rc;
-  if (stats) HIP_TRY(hipMemsetAsync(c->dCounters.get(), 0, RTK_CNT_COUNT * sizeof(unsigned long long), s));
-  TileList own = {c->vwTiles.d.get(), c->vwNTiles, sshift};
-  own.tileView = c->vwTileView.d.get(), own.views = c->vwRecs.get(), own.viewShutters = c->vwShutters.get();
-  int e = 0;
-  if ((rc = launch_frame(c, p, static_cast<float4*>(d_accum), s, &e, &own)) != RT_OK) return rc;
-  return stats ? frame_stats(c, s, e, (uint64_t)n * p->width * p->height * sppCount, stats) : (int)RT_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -3758,7 +3724,7 @@ int rt_render_views_shutter_device(rt_ctx* c, const rt_params* p, const rt_views
   std::vector<rtk::ViewShutterRec> recs;
   const int rc = views_shutter_checks(c, p, v, shutters, d_accum ? nullptr : "d_accum is null", &pad, &refit, &recs);
   if (rc != RT_OK) return rc;
-  return views_shutter_device(c, p, v, recs, pad, refit, d_accum, stream, stats);
+  return views_frame_device(c, p, v, recs.data(), pad, refit, d_accum, stream, stats);
 }
 
 int rt_render_views_shutter(rt_ctx* c, const rt_params* p, const rt_views* v, const rt_shutter* shutters, const float* bg,
@@ -3766,20 +3732,9 @@ int rt_render_views_shutter(rt_ctx* c, const rt_params* p, const rt_views* v, co
   rtbvh::Padding pad;
   bool refit = false;
   std::vector<rtk::ViewShutterRec> recs;
-  int rc = views_shutter_checks(c, p, v, shutters, !out_rgb && !accum_out ? "neither out_rgb nor accum_out is given"
-                                                   : out_rgb && !bg     ? "out_rgb requested without a background image"
-                                                                        : nullptr, &pad, &refit, &recs);
+  const int rc = views_shutter_checks(c, p, v, shutters, outputs_refused(bg, out_rgb, accum_out), &pad, &refit, &recs);
   if (rc != RT_OK) return rc;
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t npx = (size_t)p->width * p->height, all = npx * v->n_views;
-  Staging st;
-  float4* dAccum = st.zeroed<float4>(accum_out, all);
-  if (st.rc != RT_OK) return st.rc;
-  rt_stats local;
-  if ((rc = views_shutter_device(c, p, v, recs, pad, refit, dAccum, nullptr, stats ? stats : &local)) != RT_OK) return rc;
-  // each view resolved over its slice, with the shared background
-  if ((rc = stage_resolve(&st, bg, out_rgb, dAccum, v->n_views, npx, p->spp)) != RT_OK) return rc;
-  return st.download();
+  return views_frame_host(c, p, v, recs.data(), pad, refit, bg, out_rgb, accum_out, stats);
 }
 
 }  // extern "C"

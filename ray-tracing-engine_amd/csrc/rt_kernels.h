@@ -163,43 +163,53 @@ struct RaysArgs {
 };
 hipError_t launch_render_rays(bool brute_force, bool stats, const DevScene& S, const RaysArgs& A, float4* accum,
                               unsigned long long* counters, hipStream_t stream);
-// the frame through a thin lens (lens_kernels.h, rt_render_lens): the host-derived constants of rt_amd.h, by value.
+// ---- the frame's generator variants (frame_variants.h): the frame integrator with another generator or another split of
+// its samples.  What a variant's kernels read beyond the frame's arguments travels as one record, by value.
+// the frame through a thin lens (rt_render_lens): the host-derived constants of rt_amd.h.
 // aperture == 0: the frame's own camera_ray (a wave-uniform test on the record), the other fields are not read.
 struct LensRec {
   float aperture, fs;  // lens radius; focus_distance / distance of the image plane
   float hu[3], vu[3];  // unit3(cam.horizontal), unit3(cam.vertical)
 };
-// launch_render's one-wave-per-workgroup family (brute, sequential, pooled; counted or timed) with the lens generator in
-// place of camera_ray; A as launch_render takes it (tileView null)
-hipError_t launch_render_lens(bool brute_force, bool stats, const DevScene& S, const RenderArgs& A, const LensRec& R,
-                              float4* accum, unsigned long long* counters, hipStream_t stream);
-// the frame under an open shutter (shutter_kernels.h, rt_render_shutter): the host-derived constants of rt_amd.h, by
-// value.  The camera of a sample is S.cam + t d, t drawn in [open, close]; aperture > 0 puts rt_render_lens' lens on it.
+// the frame under an open shutter (rt_render_shutter): the host-derived constants of rt_amd.h.  The camera of a sample
+// is S.cam + t d, t drawn in [open, close]; aperture > 0 puts rt_render_lens' lens on it.
 struct ShutterRec {
   float d[12];          // camera_close - the context's camera, component by component (position, lower_left, H, V)
   float open, close;    // the exposure: t = uniformF(open, close)
   float aperture;       // lens radius, 0 = pinhole (fs0 and dfs are then not read)
   float fs0, dfs;       // fs of the context's camera, and fs of camera_close minus it
 };
-// launch_render_lens' six instances with the shutter generator in place of camera_ray; A as launch_render takes it
-// (tileView null)
-hipError_t launch_render_shutter(bool brute_force, bool stats, const DevScene& S, const RenderArgs& A, const ShutterRec& R,
-                                 float4* accum, unsigned long long* counters, hipStream_t stream);
-// the same six instances over the wave tiles of many views (views_shutter_kernels.h, rt_render_views_shutter): tile t
-// renders with views[tileView[t]]'s camera, seed and slice under viewShutters[tileView[t]]; A as launch_render takes a
-// multi-view frame's, with the three tables set
-hipError_t launch_render_views_shutter(bool brute_force, bool stats, const DevScene& S, const RenderArgs& A, float4* accum,
-                                       unsigned long long* counters, hipStream_t stream);
-// the frame split by light group (lights_kernels.h, rt_render_lights): rt_light_groups' count and masks, by value — a
-// kernel argument, so every mask test is a scalar one.  masks[g] is 0 for g >= n.
+// the frame split by light group (rt_render_lights): rt_light_groups' count and masks — a kernel argument, so every
+// mask test is a scalar one.  masks[g] is 0 for g >= n.
 struct LightGroupsRec {
   uint32_t n;
   uint32_t masks[RT_LIGHT_GROUPS_MAX];
 };
-// launch_render_lens' six instances with one colour sum per group at every vertex; A as launch_render takes it (tileView
-// null), accum [G.n][height][width]: slice g at accum + g * width * height
-hipError_t launch_render_lights(bool brute_force, bool stats, const DevScene& S, const RenderArgs& A, const LightGroupsRec& G,
-                                float4* accum, unsigned long long* counters, hipStream_t stream);
+// Which variant a frame is, with its record (which the caller keeps alive over the launch call).  VIEWS_SHUTTER, many
+// views each under its own open shutter (rt_render_views_shutter), has none: tile t renders with views[tileView[t]]'s
+// camera, seed and slice under viewShutters[tileView[t]], from RenderArgs' three tables.
+struct FrameVariant {
+  enum Kind { NONE, LENS, SHUTTER, LIGHTS, VIEWS_SHUTTER };
+  Kind kind = NONE;
+  const void* rec = nullptr;  // the LensRec, ShutterRec or LightGroupsRec of kind, else null
+  FrameVariant() = default;
+  explicit FrameVariant(Kind k) : kind(k) {}
+  FrameVariant(const LensRec& r) : kind(LENS), rec(&r) {}
+  FrameVariant(const ShutterRec& r) : kind(SHUTTER), rec(&r) {}
+  FrameVariant(const LightGroupsRec& r) : kind(LIGHTS), rec(&r) {}
+  explicit operator bool() const { return kind != NONE; }
+  // the variant in an error message: "<name> render launch failed"
+  const char* name() const {
+    static const char* const names[] = {"", "lens", "shutter", "light-group", "multi-view shutter"};
+    return names[kind];
+  }
+};
+// launch_render's one-wave-per-workgroup family (brute, sequential, pooled; counted or timed) for a variant (F.kind not
+// NONE); A as launch_render takes it: tileView null, but for VIEWS_SHUTTER a multi-view frame's with the three tables
+// set.  LIGHTS: accum is [G.n][height][width], slice g at accum + g * width * height.  hipErrorInvalidValue where A, the
+// record or the scene's light count do not fit the variant.
+hipError_t launch_render_variant(const FrameVariant& F, bool brute_force, bool stats, const DevScene& S, const RenderArgs& A,
+                                 float4* accum, unsigned long long* counters, hipStream_t stream);
 // First element of view j's slice of a per-view output with c floats or words per pixel (rt_render_aov_views,
 // rt_render_motion_views, rt_denoise_batch): formed in 64 bits — n w h may reach 2^31 - 1 and 3 x that is not 32-bit.
 __host__ __device__ inline size_t view_slice(uint32_t j, uint32_t width, uint32_t height, uint32_t c) {

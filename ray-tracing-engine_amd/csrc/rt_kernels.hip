@@ -210,17 +210,19 @@ constexpr int LT_FASTDET = 256;
 // and accumulator slice.  Only render_tile reads it (it strips the bit before it passes LT on).  Its own instances: read
 // at run time, the choice costs every single-view instance SGPR spills and one of them a wave.
 constexpr int LT_VIEWS = 512;
+// The frame's variants (frame_variants.h).  Only render_tile reads these bits, and it takes the one record that goes with
+// them (frame_rec_t); the record-carrying instances are k_render_rec's.
 // A frame through a thin lens (rt_render_lens): render_tile takes a LensRec and, where its aperture is not zero, forms the
-// primary ray by lens_ray instead of camera_ray.  Only render_tile reads the bit; its own instances (lens_kernels.h).
+// primary ray by lens_ray instead of camera_ray.
 constexpr int LT_LENS = 1024;
 // A frame under an open shutter (rt_render_shutter): render_tile takes a ShutterRec and forms every sample's camera, then
-// its primary ray, by shutter_ray.  Only render_tile reads the bit; its own instances (shutter_kernels.h).  With LT_VIEWS
-// (rt_render_views_shutter): the record is the view's, from RenderArgs::viewShutters, and shutter_ray runs on the view's
-// camera and seed; its own instances again (views_shutter_kernels.h).
+// its primary ray, by shutter_ray.  With LT_VIEWS (rt_render_views_shutter): the record is the view's, from
+// RenderArgs::viewShutters, and shutter_ray runs on the view's camera and seed; no record argument, so these are k_render
+// instances.
 constexpr int LT_SHUTTER = 2048;
 // A frame split by light group (rt_render_lights): render_tile takes a LightGroupsRec, keeps one colour per group and
 // vertex and adds every sample into one accumulator slice per group; the vertex pool and shade_direct_seq form the
-// per-group sums (their GROUPS switch).  Only render_tile reads the bit; its own instances (lights_kernels.h).
+// per-group sums (their GROUPS switch).
 constexpr int LT_LIGHTS = 4096;
 constexpr uint32_t kPrioMaxNodes = 65536;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -1326,10 +1328,23 @@ RT_DEV void group_samples_add(const RenderArgs& A, const LightGroupsRec& G, floa
   wave_sync();
 }
 
+// The record a frame variant's instances take as a kernel argument of their own, by its LT_* bits: the lens, the shutter
+// of a single-view frame (a multi-view one reads its records from RenderArgs' tables), the light groups — or none.
+struct NoRec {};
+template <int LTV>
+using frame_rec_t = std::conditional_t<(LTV & LT_LENS) != 0, LensRec,
+                    std::conditional_t<(LTV & LT_LIGHTS) != 0, LightGroupsRec,
+                    std::conditional_t<(LTV & LT_SHUTTER) != 0 && (LTV & LT_VIEWS) == 0, ShutterRec, NoRec>>>;
+// (what the instances without a record leave out; the others do not compile without theirs)
+template <int LTV>
+constexpr const frame_rec_t<LTV>* no_record() {
+  static_assert(std::is_same_v<frame_rec_t<LTV>, NoRec>, "this variant's instances pass their record to render_tile");
+  return nullptr;
+}
+
 template <bool BRUTE, bool PHOTON, bool POOLED, bool STATS, int LTV, class HP = Heap>
 RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restrict__ accum, const Lds& L, uint32_t* pool,
-                        float* ex, uint32_t wave, LaneStats& st, const LensRec* lens = nullptr,
-                        const ShutterRec* shutter = nullptr, const LightGroupsRec* groups = nullptr) {
+                        float* ex, uint32_t wave, LaneStats& st, const frame_rec_t<LTV>* rec = no_record<LTV>()) {
   constexpr int LT = LTV & ~(LT_VIEWS | LT_LENS | LT_SHUTTER | LT_LIGHTS);
   constexpr bool VIEWS = (LTV & LT_VIEWS) != 0;
   constexpr bool LENS = (LTV & LT_LENS) != 0;
@@ -1350,29 +1365,22 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
   rt_camera cam;
   uint32_t seed = A.seed;
   ShutterRec vsh;  // (LT_VIEWS | LT_SHUTTER) the view's shutter record, from the table parallel to views, in SGPRs too
-  if constexpr (VIEWS && SHUTTER) {
+  if constexpr (VIEWS) {
     typedef const __attribute__((address_space(4))) uint32_t* const_u32_ptr;
     typedef const __attribute__((address_space(4))) ViewRec* const_view_ptr;
     typedef const __attribute__((address_space(4))) ViewShutterRec* const_shutter_ptr;
     const uint32_t view = ((const_u32_ptr)A.tileView)[wave];
     const const_view_ptr R = (const_view_ptr)A.views + view;
-    const const_shutter_ptr Q = (const_shutter_ptr)A.viewShutters + view;
     for (int j = 0; j < 3; ++j)
       cam.position[j] = R->cam.position[j], cam.lower_left[j] = R->cam.lower_left[j],
       cam.horizontal[j] = R->cam.horizontal[j], cam.vertical[j] = R->cam.vertical[j];
     seed = R->seed;
     accum += R->accumOff;
-    for (int j = 0; j < 12; ++j) vsh.d[j] = Q->d[j];
-    vsh.open = Q->open, vsh.close = Q->close, vsh.aperture = Q->aperture, vsh.fs0 = Q->fs0, vsh.dfs = Q->dfs;
-  } else if constexpr (VIEWS) {
-    typedef const __attribute__((address_space(4))) uint32_t* const_u32_ptr;
-    typedef const __attribute__((address_space(4))) ViewRec* const_view_ptr;
-    const const_view_ptr R = (const_view_ptr)A.views + ((const_u32_ptr)A.tileView)[wave];
-    for (int j = 0; j < 3; ++j)
-      cam.position[j] = R->cam.position[j], cam.lower_left[j] = R->cam.lower_left[j],
-      cam.horizontal[j] = R->cam.horizontal[j], cam.vertical[j] = R->cam.vertical[j];
-    seed = R->seed;
-    accum += R->accumOff;
+    if constexpr (SHUTTER) {
+      const const_shutter_ptr Q = (const_shutter_ptr)A.viewShutters + view;
+      for (int j = 0; j < 12; ++j) vsh.d[j] = Q->d[j];
+      vsh.open = Q->open, vsh.close = Q->close, vsh.aperture = Q->aperture, vsh.fs0 = Q->fs0, vsh.dfs = Q->dfs;
+    }
   }
   const uint32_t S_ = 1u << A.sshift, P_ = 64u >> A.sshift;
   const uint32_t pl = lane & (P_ - 1u), sj = lane >> (6u - A.sshift);
@@ -1396,9 +1404,9 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
     else if constexpr (VIEWS) camera_ray<FR>(cam, cu, cv, o, d);
     else if constexpr (LENS) {
       // (wave-uniform: the record is a kernel argument)
-      if (lens->aperture > 0.f) lens_ray(S.cam, *lens, rt_stream_seed(A.seed, RT_STREAM_LENS, pix, i), cu, cv, o, d);
+      if (rec->aperture > 0.f) lens_ray(S.cam, *rec, rt_stream_seed(A.seed, RT_STREAM_LENS, pix, i), cu, cv, o, d);
       else camera_ray<FR>(S.cam, cu, cv, o, d);
-    } else if constexpr (SHUTTER) shutter_ray(S.cam, *shutter, A.seed, pix, i, cu, cv, o, d);
+    } else if constexpr (SHUTTER) shutter_ray(S.cam, *rec, A.seed, pix, i, cu, cv, o, d);
     else camera_ray<FR>(S.cam, cu, cv, o, d);
     f3 c0 = mk(0.f, 0.f, 0.f), c1 = c0, c2 = c0;
     GroupCols g0, g1, g2, gv;  // (LT_LIGHTS) the three vertices' colours per group, and the current vertex's
@@ -1434,7 +1442,7 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
         f3 c;
         if constexpr (LIGHTS) {
           static_assert(!SHADOW_BODY, "the light-group instances keep their trees in HBM / L2");
-          c = vertex_pool<STATS, LT, true, true>(S, alive, bounce, g, d, mesh, nrm, pt, bdir, L.stack, pool, nh, nfound, st, groups, &gv);
+          c = vertex_pool<STATS, LT, true, true>(S, alive, bounce, g, d, mesh, nrm, pt, bdir, L.stack, pool, nh, nfound, st, rec, &gv);
         } else
         c = SHADOW_BODY && !bounce
                          ? vertex_pool<STATS, LT, false>(S, alive, false, g, d, mesh, nrm, pt, bdir, L.stack, pool, nh, nfound, st)
@@ -1467,7 +1475,7 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
       if (PHOTON) {
         if (alive) c = shade_photon<STATS, HP>(S, A, d, h, L, nrm, pt, st);
       } else if constexpr (LIGHTS) {
-        if (alive) c = shade_direct_seq<BRUTE, STATS, true>(S, g, d, h, L.stack, nrm, pt, st, groups, &gv);
+        if (alive) c = shade_direct_seq<BRUTE, STATS, true>(S, g, d, h, L.stack, nrm, pt, st, rec, &gv);
       } else {
         if (alive) c = shade_direct_seq<BRUTE, STATS>(S, g, d, h, L.stack, nrm, pt, st);
       }
@@ -1490,7 +1498,7 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
     // calculateColorPath returns c0 + (c1 + (c2 + 0)) for finalDepth <= 3
     PH(PH_VSETUP);
     if constexpr (LIGHTS) {
-      group_samples_add(A, *groups, accum, ex, g0, g1, g2, primary, active, owner, pix, pl, base);
+      group_samples_add(A, *rec, accum, ex, g0, g1, g2, primary, active, owner, pix, pl, base);
       continue;
     }
     const f3 total = c0 + (c1 + (c2 + mk(0.f, 0.f, 0.f)));
@@ -1727,17 +1735,9 @@ __global__ __launch_bounds__(1024, 8) void k_trace_stream(DevScene S, const floa
 // ---------------------------------------------------------------- ray batches (rt_render_rays)
 #include "rays_kernels.h"
 
-// ---------------------------------------------------------------- thin-lens frames (rt_render_lens)
-#include "lens_kernels.h"
-
-// ---------------------------------------------------------------- open-shutter frames (rt_render_shutter)
-#include "shutter_kernels.h"
-
-// ---------------------------------------------------------------- multi-view open-shutter frames (rt_render_views_shutter)
-#include "views_shutter_kernels.h"
-
-// ---------------------------------------------------------------- frames split by light group (rt_render_lights)
-#include "lights_kernels.h"
+// ---------------------------------------------------------------- the frame's generator variants (rt_render_lens,
+// rt_render_shutter, rt_render_views_shutter, rt_render_lights)
+#include "frame_variants.h"
 
 // ---------------------------------------------------------------- frame assembly (multi-GPU)
 // A rank's owned 8x8-pixel granules, packed [granule][64 pixels] (row-major inside the
