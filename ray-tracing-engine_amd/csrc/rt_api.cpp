@@ -684,6 +684,7 @@ int launch_frame(rt_ctx* c, const rt_params* p, float4* dAccum, hipStream_t stre
   A.k = p->k, A.photons_requested = p->photons_requested;
   static const bool noPool = getenv("RT_NO_POOL") != nullptr;
   A.flags = (noPool || (p->reserved[1] & 1u)) ? 0u : 1u;
+  if (c->bvh.leafMax <= 2u) A.flags |= 2u;  // (the resident tree's, whoever built it last: rt_create, rt_rebuild)
   // stack entries: one per inner level on a root-to-leaf path; the photon k-NN
   // keeps one split distance per kd level in the same region
   // a root-to-leaf path of depth d passes d inner nodes and each stacks at most one

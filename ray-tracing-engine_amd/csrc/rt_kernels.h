@@ -86,7 +86,8 @@ struct RenderArgs {
   const uint32_t* tiles;  // owned wave tiles: x0 | y0 << 16 (pixels, top-left corner)
   uint32_t n_tiles;
   uint32_t width, height, spp, s0, s1, mode, max_depth, seed, k, photons_requested;
-  uint32_t flags;         // bit 0: shadow rays through the wave-level pool
+  uint32_t flags;         // bit 0: shadow rays through the wave-level pool; bit 1: no leaf of the resident tree holds more
+                          // than two records (the launcher's LT_LEAF2 instances)
   uint32_t stackLevels;   // LDS traversal-stack rows (64 words each) per wave: BVH depth + 1; with photons also the kd walk's
                           // pending entries (kd depth + 2: 32-bit, or two 16-bit entries per word when kd16)
   uint32_t kd16;          // the k-NN walk keeps 16-bit stack entries (fewer than 65,535 photons)

@@ -203,6 +203,11 @@ constexpr int LT_COMPACT2 = 32;
 // which is handed out in 1,280-byte units —, TWENTY waves per CU for trees of up to 27 levels, and the instance is compiled
 // for five waves per SIMD (96 VGPRs).
 constexpr int LT_COMPACT3 = 64;
+// The resident tree's leaves hold at most two records (rt_options.bvh_leaf_max <= 2, the default): the leaf phase is
+// test_pair alone — no loop over records 3 .. leaf_max, none of its masks.  The launcher picks these instances per launch
+// from RenderArgs::flags bit 1 (the timed single-view LT_ALL, LT_TOP and four-wave instances; RT_LEAF2=0 forces the
+// general ones).
+constexpr int LT_LEAF2 = 128;
 // 1 / det of the triangle test by rtd::recip_fast (3 instructions, the division's bits for |det| < 2^100) instead of the
 // division: only the instances the launcher picks when the host has bounded |det| for the launch's rays (DevScene::slowRecip == 0).
 constexpr int LT_FASTDET = 256;
@@ -236,6 +241,7 @@ struct Trav {
   static constexpr bool PRIO = (LTX & LT_NOPRIO) == 0;
   static constexpr bool DIVIDE = (LTX & LT_FASTDET) == 0;
   static constexpr bool Q8 = (LTX & LT_Q8) != 0;
+  static constexpr bool LEAF2 = (LTX & LT_LEAF2) != 0;
   static_assert(!Q8 || LT == LT_NONE, "Q8 records are fetched from HBM / L2");
   // any-hit rays enter child 0 (the smaller box) first: the big-scene instances and the whole-tree-in-LDS ones (measured:
   // C5 -2.5 %, C5x8 -1.9 %, C2 -0.7 %, C1 -3 %; the partial-top instance of C4 loses 0.7 % to the extra scalar op and keeps
@@ -435,9 +441,12 @@ struct Trav {
       const float4 a0 = r[0], a1 = r[1], a2 = r[2];
       const float4 b0 = r[second + 0], b1 = r[second + 1], b2 = r[second + 2];
       bool stop = test_pair<STATS>(a0, a1, a2, b0, b1, b2, cnt > 1, st);
-      for (uint32_t i = 2; i < cnt && !stop; i++) {
-        const float4* q = reinterpret_cast<const float4*>(leaf + 48u * i);
-        stop = test_record<STATS>(q[0], q[1], q[2], st);
+      // (LEAF2: no leaf of the tree holds a third record — no loop, none of its guard and mask bookkeeping)
+      if constexpr (!LEAF2) {
+        for (uint32_t i = 2; i < cnt && !stop; i++) {
+          const float4* q = reinterpret_cast<const float4*>(leaf + 48u * i);
+          stop = test_record<STATS>(q[0], q[1], q[2], st);
+        }
       }
       cur = stop ? TERM : (int32_t)peek();
       pop();
@@ -2189,6 +2198,16 @@ static hipError_t launch_render2(bool stats, const DevScene& S, const RenderArgs
     if (stats || S.slowRecip) RT_LAUNCH_PERSIST(true, LTV);      \
     else RT_LAUNCH_PERSIST(false, (LTV) | LT_FASTDET);           \
   } while (0)
+      // ... and, of the layouts the BASELINE configs run in, a second timed instance for trees whose leaves hold at most
+      // two records (LT_LEAF2: RenderArgs::flags bit 1, set per launch from the resident tree).  RT_LEAF2=0 forces the
+      // general instances; it is read at every launch, so one process can compare the two.
+      const char* const leaf2Env = getenv("RT_LEAF2");
+      const bool leaf2 = (A.flags & 2u) && !(leaf2Env && atoi(leaf2Env) == 0) && !stats && !S.slowRecip && !A.tileView;
+#define RT_LAUNCH_LEAF2(LTV)                                             \
+  do {                                                                   \
+    if (leaf2) RT_LAUNCH_PERSIST1(false, (LTV) | LT_FASTDET | LT_LEAF2); \
+    else RT_LAUNCH_EITHER(LTV);                                          \
+  } while (0)
       const int lt = P.topK == 0 ? LT_NONE : P.topK >= S.n_nodes ? LT_ALL : LT_TOP;
       if (P.compact == 3) {
 #define RT_LAUNCH_PERSIST5(ST, LTV)                                                                                       \
@@ -2198,7 +2217,8 @@ static hipError_t launch_render2(bool stats, const DevScene& S, const RenderArgs
     hipLaunchKernelGGL((k_render_persist5<ST, LTV>), dim3(wgs), dim3(256), P.ldsBytes, stream, S2, A2, accum, counters); \
   } while (0)
         constexpr int C3 = LT_NONE | LT_NOPRIO | LT_COMPACT3;
-        if (stats || S.slowRecip) {
+        if (leaf2) RT_LAUNCH_PERSIST5(false, C3 | LT_FASTDET | LT_LEAF2);
+        else if (stats || S.slowRecip) {
           if (A.tileView) RT_LAUNCH_PERSIST5(true, C3 | LT_VIEWS);
           else RT_LAUNCH_PERSIST5(true, C3);
         } else {
@@ -2212,9 +2232,10 @@ static hipError_t launch_render2(bool stats, const DevScene& S, const RenderArgs
         else RT_LAUNCH_EITHER(LT_Q8 | LT_NOPRIO);
       } else if (P.compact == 2) RT_LAUNCH_EITHER(LT_NONE | LT_NOPRIO | LT_COMPACT2);
       else if (P.compact) RT_LAUNCH_EITHER(LT_NONE | LT_NOPRIO | LT_COMPACT);
-      else if (lt == LT_ALL) RT_LAUNCH_EITHER(LT_ALL);
-      else if (lt == LT_TOP) RT_LAUNCH_EITHER(LT_TOP);
+      else if (lt == LT_ALL) RT_LAUNCH_LEAF2(LT_ALL);
+      else if (lt == LT_TOP) RT_LAUNCH_LEAF2(LT_TOP);
       else RT_LAUNCH_EITHER(LT_NONE | LT_NOPRIO);  // (a small tree beside stacks that leave no room for 256 of its nodes: rare)
+#undef RT_LAUNCH_LEAF2
 #undef RT_LAUNCH_EITHER
 #undef RT_LAUNCH_PERSIST
 #undef RT_LAUNCH_PERSIST1
