@@ -40,6 +40,8 @@
  *                                  frame, and in the passes of an adaptive frame (+ _device forms)
  *   rt_render_lights            <- (no counterpart) the frame split by light group: one accumulator per group of
  *                                  lights for the rays of one frame (+ _device form)
+ *   rt_render_pick              <- (no counterpart) sampled direct lighting for scenes of many lights: m <= 3 lights per
+ *                                  sample, picked by importance and weighted by 1 / (m p) (+ _device form)
  *   rt_render_aov_views / rt_render_motion_views / rt_denoise_batch <- (no counterpart) the AOVs, motion vectors and
  *                                  denoised frames of those views, one launch each (+ _device forms)
  *   rt_trace                    <- RayTracer::rayTrace (RayTracer.h:27-53) test hook
@@ -60,19 +62,23 @@
  *   written in stream order, and the call returns without waiting for the stream:
  *     rt_render_device, rt_render_views_device, rt_render_rays_device, rt_render_shutter_device,
  *     rt_render_views_shutter_device (tests/test_gpu_views_shutter.py), rt_render_lights_device
- *     (tests/test_gpu_lights.py) and rt_render_lens_device with stats == NULL;
+ *     (tests/test_gpu_lights.py), rt_render_pick_device (tests/test_gpu_pick.py) and
+ *     rt_render_lens_device with stats == NULL;
  *     rt_resolve_device;
  *     rt_render_aov_device, rt_render_ao_device, rt_render_motion_device; rt_temporal_accumulate_device,
  *     rt_svgf_device, rt_denoise_device, rt_denoise_batch_device; rt_render_aov_views_device,
  *     rt_render_motion_views_device; rt_pack_owned_device, rt_unpack_owned_device; rt_trace_stream_device.
- *     Host arguments (params, cameras, seeds, previous cameras) are copied before the call returns.
+ *     Host arguments (params, cameras, seeds, previous cameras, a pick's importance array) are copied before the call
+ *     returns.
  *     Two exceptions, neither of which changes a result: a call that needs MORE scratch than the context holds
  *     (another frame size, rank or sample-per-wave choice for the tile list; more views; a larger frame for the
- *     filters; a larger wavefront batch) frees the old block, and hipFree waits for the device; and the fifth
- *     multi-view call in a row waits for the upload of the first (four pinned staging copies).
+ *     filters; a larger wavefront batch; more lights for a pick table) frees the old block, and hipFree waits for the
+ *     device; and the fifth multi-view call in a row waits for the upload of the first (four pinned staging copies), as
+ *     does the fifth rt_render_pick_device call for the table of the first.
  *   SYNCHRONISE `stream`, and only it, before they return, because the host reads a result back:
  *     rt_render_device, rt_render_views_device, rt_render_rays_device, rt_render_shutter_device,
- *     rt_render_views_shutter_device, rt_render_lights_device, rt_render_lens_device with stats != NULL;
+ *     rt_render_views_shutter_device, rt_render_lights_device, rt_render_pick_device,
+ *     rt_render_lens_device with stats != NULL;
  *     rt_render_adaptive_device and rt_render_adaptive_shutter_device (every pass); rt_update_vertices_device and
  *     rt_update_transforms (twice);
  *     the four multi-view forms when a view lies far enough out to need a wider box padding (a refit).
@@ -735,6 +741,71 @@ int rt_render_lights(rt_ctx* ctx, const rt_params* p, const rt_light_groups* gro
  * (stats == NULL: asynchronous; stats != NULL: synchronises `stream`, and only it). */
 int rt_render_lights_device(rt_ctx* ctx, const rt_params* p, const rt_light_groups* groups, void* d_accum, void* stream,
                             rt_stats* stats);
+
+/* ---- sampled direct lighting for scenes of many lights --------------------------------------------------
+ * rt_render casts one shadow ray per light and vertex.  rt_render_pick renders the frame p describes with m = slots light
+ * samples per path vertex instead: every SAMPLE picks m of the context's n lights by importance, all of its vertices
+ * shade with those m, and each picked light is weighted by 1 / (m p_k).  A vertex then casts m <= RT_PICK_SLOTS_MAX shadow
+ * rays whatever n is, so the frame runs through the wave-level vertex pool.
+ *
+ * The table, derived by the host once per call, in float64 unless said otherwise; L_k are the context's lights:
+ *   - importance q_k: importance[k] where the caller gives the array; else the light's power proxy
+ *     (double)intensity * (double)factor * (((double)color[0] + color[1]) + color[2]) * (double)side * (double)side, where a
+ *     value that is not finite or not > 0 counts as 0; if every default q_k is 0, all q_k = 1.
+ *   - Q = the sum of q_k in index order, p_k = q_k / Q, C_k = the running sum of p in index order; the thresholds are
+ *     t_k = (float)C_k, and from the last k with q_k > 0 onwards t_k = 1.0f.
+ *   - pick(u) = the smallest k with u < t_k.  It exists for every u in [0, 1); a light with q_k = 0 shares its threshold
+ *     with its predecessor and is never picked.
+ *   - w_k = (float)(1.0 / ((double)m * p_k)) for p_k > 0; the picked light L'_k is L_k with color[c] = w_k * color[c], one
+ *     float32 product per component, computed on the host.  The kernels read L'_k from a device table of the call's own.
+ * Sample i of pixel (x, y), pix = y * width + x, all in float32, nothing fused:
+ *   1. e is seeded with rt_stream_seed(seed, RT_STREAM_PICK, pix, i); for slot j = 0 .. m - 1: u_j = e.canonF(), k_j =
+ *      pick(u_j).  The picks belong to the SAMPLE: all of its vertices use the same m slots.
+ *   2. From there the sample is rt_render's sample on the light list (L'_{k_0}, .., L'_{k_{m-1}}): g seeded with
+ *      rt_stream_seed(seed, RT_STREAM_PIXEL, pix, i), jitter_sample, camera_ray, the primary cast; at every vertex the m
+ *      light samples drawn from g in slot order (two engine calls each, whatever the light), one shadow ray per slot, the
+ *      unoccluded terms added from +0 in slot order, then the hemisphere draw.
+ *   3. The sample is c0 + (c1 + (c2 + 0)), clamped to [0, 1] per component, and added in float32 in sample order; .w
+ *      counts the primary hit.
+ * The estimator is unbiased BEFORE the clamp.  The per-sample clamp to [0, 1] bites more often with weights above 1, as
+ * with any such sampler: a picked frame of a scene whose samples come near 1 is darker there than rt_render's.
+ * Guarantees, all bit for bit, on accumulator words and on both ray counts:
+ *   - P1: what sample i adds to pixel pix is what rt_render_device adds to that pixel for the same p with spp_begin = i,
+ *     spp_count = 1 on a context of the same geometry whose light list is that sample's tuple (L'_{k_0}, .., L'_{k_{m-1}}).
+ *   - P2: with n = 1 and m = 1 the frame and the stats are rt_render's (w = 1).
+ *   - P3: .w, samples, rays_closest and rays_shadow do not depend on the picks (the main stream advances two calls per
+ *     slot whatever the light): they are those of rt_render on the same geometry with any m lights.
+ *   - P4, schedule: sample ranges chain; reserved[0] (lanes per pixel), reserved[1] bit 0 (no pool), collect_stats and
+ *     RT_ACCEL_BRUTE change the schedule, never the bits.
+ * RT_NODES_Q8 contexts walk their resident 32-byte records, as rt_render_lens does.  The call changes nothing in the
+ * context.  The frame runs on the one-wave-per-workgroup kernel family of rt_render (no persistent instances), pooled
+ * whatever n is.
+ * Validation comes first and a rejected call writes nothing; what the arguments alone decide is answered before the
+ * device is asked for.  RT_ERR_INVALID: a null ctx, p or pick; slots 0 or above RT_PICK_SLOTS_MAX; non-zero reserved
+ * words; importance without n_importance, or the reverse; a negative or non-finite importance[k] (rt_last_error names
+ * k); an all-zero importance; host form: neither out_rgb nor accum_out, or out_rgb without background_rgb; device form: a
+ * null d_accum; every check rt_render applies to p.  RT_ERR_UNSUPPORTED: world > 1, use_photons, the wavefront integrator
+ * (reserved[2] bit 0), the legacy RNG.  Then the device (RT_ERR_NO_DEVICE); then, reading the context, RT_ERR_INVALID
+ * for a context without lights, an n_importance that is not the context's n_lights, and a weight w_k that is not finite
+ * (rt_last_error names the numbers).  There is no cap on n beyond rt_create's.
+ * Out of scope: picks combined with the lens, the shutter, views, adaptive passes, light groups or rt_render_rays;
+ * position-dependent importance (light trees); per-vertex picks; photon frames; more than RT_PICK_SLOTS_MAX slots.        */
+#define RT_PICK_SLOTS_MAX 3          /* == the vertex pool's light count: a picked frame always fits the pool          */
+typedef struct rt_light_pick {
+  uint32_t slots;            /* m: light samples per path vertex, 1..RT_PICK_SLOTS_MAX           */
+  uint32_t n_importance;     /* 0, or the context's n_lights                                     */
+  const float* importance;   /* [n_importance] HOST memory or NULL = the default above           */
+  uint32_t reserved[5];      /* zero */
+} rt_light_pick;
+/* out_rgb [h][w][3] or NULL, accum_out [h][w][4] or NULL, background_rgb [h][w][3]: as rt_render's */
+int rt_render_pick(rt_ctx* ctx, const rt_params* p, const rt_light_pick* pick, const float* background_rgb, float* out_rgb,
+                   float* accum_out, rt_stats* stats);
+/* Accumulate into caller-zeroed DEVICE d_accum [h][w][4] on `stream` (a hipStream_t, may be NULL), as rt_render_device
+ * does: sample ranges chain.  p, pick and the importance array are copied, and the table is staged, before the call
+ * returns: the caller may overwrite the array at once.  The host waits only to read stats back (stats == NULL:
+ * asynchronous; stats != NULL: synchronises `stream`, and only it). */
+int rt_render_pick_device(rt_ctx* ctx, const rt_params* p, const rt_light_pick* pick, void* d_accum, void* stream,
+                          rt_stats* stats);
 
 /* ---- motion vectors and temporal accumulation (DESIGN.md "Motion vectors and temporal accumulation") ----------------
  * Two stateless calls for animated frames.  The library keeps nothing between frames: the caller hands in last frame's

@@ -39,6 +39,7 @@
 #define RT_STREAM_AO 2u     /* index = y*width + x, sub = i*n_rays + j       */
 #define RT_STREAM_LENS 3u   /* index = y*width + x, sub = sample i           */
 #define RT_STREAM_SHUTTER 4u /* index = y*width + x, sub = sample i          */
+#define RT_STREAM_PICK 5u   /* index = y*width + x, sub = sample i           */
 
 RT_HD uint64_t rt_mix64(uint64_t z) {
   z ^= z >> 30;

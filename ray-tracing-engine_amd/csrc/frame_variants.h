@@ -1,5 +1,5 @@
-// frame_variants.h — the frame integrator with another generator or another split of its samples: rt_render_lens,
-// rt_render_shutter, rt_render_views_shutter and rt_render_lights (DESIGN.md §6m–§6p).
+// frame_variants.h — the frame integrator with another generator, another split of its samples or another light list:
+// rt_render_lens, rt_render_shutter, rt_render_views_shutter, rt_render_lights (DESIGN.md §6m–§6p) and rt_render_pick (§6r).
 //
 // Every variant is render_tile itself under one more LT_* bit, on the one-wave-per-workgroup family that k_render serves:
 // brute, sequential and pooled, each counted (STATS, one wave per SIMD) and timed (four waves per SIMD, k_render's target);
@@ -18,6 +18,9 @@
 //   views+shutter LT_VIEWS | LT_SHUTTER  no record: the tile's view picks its ViewRec and, from the table parallel to
 //                                        views (RenderArgs::viewShutters), its shutter record, by scalar loads; these are
 //                                        plain k_render instances
+//   light picks   LT_PICK                PickRec: every sample draws m <= POOL_L indices into the record's table of scaled
+//                                        lights and all of its vertices shade with those (vertex_pool's and
+//                                        shade_direct_seq's PICK switch): pooled whatever the scene's light count
 // A new variant supplies a row of the same kind (a struct below, a FrameVariant kind, a case in launch_render_variant):
 // its LT_* bits, its record, the stack rows its sample hand-over needs, and its argument check.
 // (included by rt_kernels.hip inside namespace rtk: shares its device functions)
@@ -65,6 +68,14 @@ struct VariantLights {
     return A.tileView || G.n < 1u || G.n > (uint32_t)RT_LIGHT_GROUPS_MAX || S.n_lights > 32u;
   }
 };
+struct VariantPick {
+  static constexpr int LTV = LT_PICK;
+  using Rec = PickRec;
+  static constexpr uint32_t ROWS = 4, ROWS_POOLED = 4;
+  static bool refused(const DevScene&, const RenderArgs& A, const Rec& R) {
+    return A.tileView || R.m < 1u || R.m > (uint32_t)RT_PICK_SLOTS_MAX || R.n == 0u || !R.thresholds || !R.lights;
+  }
+};
 struct VariantViewsShutter {
   static constexpr int LTV = LT_VIEWS | LT_SHUTTER;
   using Rec = NoRec;
@@ -104,8 +115,10 @@ static hipError_t launch_variant(bool brute_force, bool stats, const DevScene& S
                                  float4* accum, unsigned long long* counters, hipStream_t stream) {
   if (V::refused(S, A, R)) return hipErrorInvalidValue;
   if (brute_force) return launch_variant2<V, true, false>(stats, S, A, R, accum, counters, stream);
-  // the vertex pool handles up to POOL_L lights, as in launch_render
-  if ((A.flags & 1u) && S.n_lights <= (uint32_t)POOL_L) return launch_variant2<V, false, true>(stats, S, A, R, accum, counters, stream);
+  // the vertex pool handles up to POOL_L lights, as in launch_render; a picked frame's vertex has m <= POOL_L of them
+  // whatever the scene's count
+  constexpr bool anyCount = (V::LTV & LT_PICK) != 0;
+  if ((A.flags & 1u) && (anyCount || S.n_lights <= (uint32_t)POOL_L)) return launch_variant2<V, false, true>(stats, S, A, R, accum, counters, stream);
   return launch_variant2<V, false, false>(stats, S, A, R, accum, counters, stream);
 }
 
@@ -118,6 +131,8 @@ hipError_t launch_render_variant(const FrameVariant& F, bool brute_force, bool s
       return launch_variant<VariantShutter>(brute_force, stats, S, A, *static_cast<const ShutterRec*>(F.rec), accum, counters, stream);
     case FrameVariant::LIGHTS:
       return launch_variant<VariantLights>(brute_force, stats, S, A, *static_cast<const LightGroupsRec*>(F.rec), accum, counters, stream);
+    case FrameVariant::PICK:
+      return launch_variant<VariantPick>(brute_force, stats, S, A, *static_cast<const PickRec*>(F.rec), accum, counters, stream);
     case FrameVariant::VIEWS_SHUTTER:
       return launch_variant<VariantViewsShutter>(brute_force, stats, S, A, NoRec(), accum, counters, stream);
     case FrameVariant::NONE: break;

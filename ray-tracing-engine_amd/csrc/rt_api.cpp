@@ -359,6 +359,19 @@ struct rt_ctx {
   DevBuf<rt_ray> rbRays;
   DevBuf<uint32_t> rbIndex;
   size_t rbCap = 0, rbIndexCap = 0;
+  // rt_render_pick (allocated on first use, grows with the light count): the call's table on the device — n PickLight
+  // records, then n thresholds — written and read in stream order, and the ring of pinned copies its uploads read
+  // (vwStage's rule: a call waits only for the upload of the call kViewStages back)
+  DevBuf<char> pkTable;
+  size_t pkCap = 0;
+  struct PickStage {
+    PinnedBuf<char> h;
+    size_t cap = 0;
+    Event read;
+    bool readSet = false;
+  };
+  PickStage pkStage[kViewStages];
+  uint32_t pkStageNext = 0;
 };
 
 namespace {
@@ -391,7 +404,8 @@ uint32_t photons_per_light(uint32_t n_requested, uint32_t n_lights) {
 // pixels still fills the GPU.
 // `pixels`: the pixels the launch renders (choose_sshift: the rank's share of the frame; an adaptive pass: its active
 // granules' in-image pixels).
-uint32_t choose_sshift_px(const rt_ctx* c, const rt_params* p, uint64_t pixels, uint32_t spp_count) {
+// `pick`: a frame of rt_render_pick, whose vertices send m <= 3 shadow rays whatever the context's light count.
+uint32_t choose_sshift_px(const rt_ctx* c, const rt_params* p, uint64_t pixels, uint32_t spp_count, bool pick = false) {
   if (p->reserved[0]) {  // explicit lanes-per-pixel (tests, experiments)
     uint32_t s = 0;
     while ((1u << (s + 1)) <= p->reserved[0] && s < 6) ++s;
@@ -411,7 +425,7 @@ uint32_t choose_sshift_px(const rt_ctx* c, const rt_params* p, uint64_t pixels, 
   // 348 / 339 / 334 / 328, 8 M triangles (32 spp) - / 59.7 / 57.6 / 55.8 / 55.1.  So: 16 on cache-resident scenes, as
   // many as the frame has (<= 64) beyond 65,536 nodes.  (The owner lane's in-order adds grow with the count: that is
   // what turns C2 and C4 around after 16.)  The image does not depend on it (test_frame_independent_of_samples_per_wave).
-  const bool pooled = !p->use_photons && p->accel != RT_ACCEL_BRUTE && c->S.n_lights <= 3u && !(p->reserved[1] & 1u) &&
+  const bool pooled = !p->use_photons && p->accel != RT_ACCEL_BRUTE && (pick || c->S.n_lights <= 3u) && !(p->reserved[1] & 1u) &&
                       !(p->reserved[2] & 1u);
   if (pooled) {
     const uint32_t want = c->S.n_nodes > 65536u ? 6u : 4u;
@@ -425,9 +439,9 @@ uint32_t choose_sshift_px(const rt_ctx* c, const rt_params* p, uint64_t pixels, 
     while (s < 6u && (2u << s) <= spp_count) ++s;
   return s;
 }
-uint32_t choose_sshift(const rt_ctx* c, const rt_params* p, uint32_t spp_count) {
+uint32_t choose_sshift(const rt_ctx* c, const rt_params* p, uint32_t spp_count, bool pick = false) {
   const uint64_t world = p->world ? p->world : 1;
-  return choose_sshift_px(c, p, (uint64_t)p->width * p->height / world, spp_count);
+  return choose_sshift_px(c, p, (uint64_t)p->width * p->height / world, spp_count, pick);
 }
 
 // f(x8, y8) for each 8x8-pixel granule rank `rank` of `world` owns, row-major — the order ensure_tiles
@@ -659,8 +673,8 @@ struct TileList {
 };
 
 // What forms or splits a frame's samples in place of the plain frame, if anything: the thin lens of rt_render_lens, the
-// open shutter of rt_render_shutter or the light groups of rt_render_lights (dAccum then holds one slice per group), with
-// the record its kernels take; their callers have refused photons and the wavefront bit.  A multi-view shutter frame
+// open shutter of rt_render_shutter, the light groups of rt_render_lights (dAccum then holds one slice per group) or the
+// light picks of rt_render_pick, with the record its kernels take; their callers have refused photons and the wavefront bit.  A multi-view shutter frame
 // carries its records in its TileList instead: launch_frame tells it from them.
 using FrameGen = rtk::FrameVariant;
 
@@ -669,7 +683,7 @@ using FrameGen = rtk::FrameVariant;
 int launch_frame(rt_ctx* c, const rt_params* p, float4* dAccum, hipStream_t stream, int* evIndex,
                  const TileList* own = nullptr, const FrameGen& gen = FrameGen()) {
   const SampleRange sr = sample_range(*p);
-  const uint32_t sshift = own ? own->sshift : choose_sshift(c, p, sr.count);
+  const uint32_t sshift = own ? own->sshift : choose_sshift(c, p, sr.count, gen.kind == FrameGen::PICK);
   int rc = own ? RT_OK : ensure_tiles(c, p, sshift, stream);
   if (rc != RT_OK) return rc;
   rtk::RenderArgs A;
@@ -3665,6 +3679,129 @@ int rt_render_lights(rt_ctx* c, const rt_params* p, const rt_light_groups* g, co
   const int rc = lights_checks(c, p, g, outputs_refused(bg, out_rgb, accum_out), &R);
   if (rc != RT_OK) return rc;
   return frame_host(c, p, R, R.n, bg, out_rgb, accum_out, stats);
+}
+
+}  // extern "C"
+
+// ---- sampled direct lighting for scenes of many lights ------------------------------------------------
+namespace {
+
+// The table of a call (rt_amd.h): the scaled lights L'_k and the thresholds t_k.
+struct PickTable {
+  std::vector<rtk::PickLight> lights;
+  std::vector<float> thresholds;
+};
+
+// Everything both forms of rt_render_pick check, in the header's order (lights_checks' shape: the arguments alone first,
+// then the device, the context's lights last), and the table the kernels read.
+int pick_checks(const rt_ctx* c, const rt_params* p, const rt_light_pick* k, const char* outputs, PickTable* T) {
+  if (!c || !p || !k) return fail(RT_ERR_INVALID, "ctx/params/pick is null");
+  if (k->slots < 1 || k->slots > RT_PICK_SLOTS_MAX) return fail(RT_ERR_INVALID, "slots %u is not in 1..%d", k->slots, RT_PICK_SLOTS_MAX);
+  if (any_set(k->reserved, 5)) return fail(RT_ERR_INVALID, "rt_light_pick: reserved words must be zero");
+  if (k->importance && !k->n_importance) return fail(RT_ERR_INVALID, "importance is given with n_importance 0");
+  if (!k->importance && k->n_importance) return fail(RT_ERR_INVALID, "n_importance is %u and importance is null", k->n_importance);
+  bool anyPositive = false;
+  for (uint32_t j = 0; j < k->n_importance; ++j) {
+    const float q = k->importance[j];
+    if (!std::isfinite(q) || q < 0.f) return fail(RT_ERR_INVALID, "importance[%u] = %g is negative or not finite", j, (double)q);
+    anyPositive = anyPositive || q > 0.f;
+  }
+  if (k->importance && !anyPositive) return fail(RT_ERR_INVALID, "all %u importance values are zero", k->n_importance);
+  if (outputs) return fail(RT_ERR_INVALID, "%s", outputs);
+  int rc = check_params_shape(p);
+  if (rc != RT_OK) return rc;
+  if (p->world > 1) return fail(RT_ERR_UNSUPPORTED, "tile-sharded light-pick frames (world %u) are not supported", p->world);
+  if (p->use_photons) return fail(RT_ERR_UNSUPPORTED, "light-pick frames do not shade from the photon map");
+  if (p->reserved[2] & 1u) return fail(RT_ERR_UNSUPPORTED, "light-pick frames do not run the wavefront integrator");
+  if ((rc = check_device_present()) != RT_OK) return rc;
+  if ((rc = check_not_broken(c)) != RT_OK) return rc;
+  const uint32_t n = (uint32_t)c->hostLights.size(), m = k->slots;
+  if (n == 0) return fail(RT_ERR_INVALID, "the context has no lights to pick from");
+  if (k->importance && k->n_importance != n) return fail(RT_ERR_INVALID, "n_importance %u is not the context's n_lights %u", k->n_importance, n);
+  // the importance q_k: the caller's, or the lights' power proxy
+  std::vector<double> q(n);
+  if (k->importance) {
+    for (uint32_t j = 0; j < n; ++j) q[j] = (double)k->importance[j];
+  } else {
+    bool any = false;
+    for (uint32_t j = 0; j < n; ++j) {
+      const rt_light& L = c->hostLights[j];
+      const double v = (double)L.intensity * (double)L.factor * (((double)L.color[0] + L.color[1]) + L.color[2]) * (double)L.side * (double)L.side;
+      q[j] = std::isfinite(v) && v > 0. ? v : 0.;
+      any = any || q[j] > 0.;
+    }
+    if (!any) std::fill(q.begin(), q.end(), 1.);
+  }
+  double Q = 0.;
+  uint32_t last = 0;  // the last light that can be picked
+  for (uint32_t j = 0; j < n; ++j) {
+    Q += q[j];
+    if (q[j] > 0.) last = j;
+  }
+  T->lights.assign(n, rtk::PickLight{});
+  T->thresholds.resize(n);
+  double C = 0.;
+  for (uint32_t j = 0; j < n; ++j) {
+    const double pj = q[j] / Q;
+    C += pj;
+    T->thresholds[j] = j >= last ? 1.0f : (float)C;
+    rt_light L = c->hostLights[j];
+    if (pj > 0.) {
+      const float w = (float)(1.0 / ((double)m * pj));
+      if (!std::isfinite(w))
+        return fail(RT_ERR_INVALID, "light %u: probability %g with %u slots gives a weight that is not finite", j, pj, m);
+      for (float& x : L.color) x = w * x;
+    }
+    T->lights[j].l = L;
+  }
+  return RT_OK;
+}
+
+// The table to the device on `stream` through the next slot of the ring of pinned copies (upload_views' rule), and the
+// record the kernels take.  The device block is written and read in stream order; where it grows, the old one is freed
+// under launches that may still read it, which hipFree waits for.
+int stage_pick(rt_ctx* c, const rt_light_pick* k, const PickTable& T, hipStream_t stream, rtk::PickRec* R) {
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t n = T.lights.size(), lightBytes = n * sizeof(rtk::PickLight), bytes = lightBytes + n * sizeof(float);
+  rt_ctx::PickStage& g = c->pkStage[c->pkStageNext++ % rt_ctx::kViewStages];
+  if (!g.read) HIP_TRY(make_event(&g.read, hipEventDisableTiming));
+  if (g.readSet) HIP_TRY(hipEventSynchronize(g.read.get()));
+  g.readSet = false;
+  int rc = grow(&g.h, &g.cap, bytes);
+  if (rc == RT_OK) rc = grow(&c->pkTable, &c->pkCap, bytes);
+  if (rc != RT_OK) return rc;
+  memcpy(g.h.get(), T.lights.data(), lightBytes);
+  memcpy(g.h.get() + lightBytes, T.thresholds.data(), n * sizeof(float));
+  HIP_TRY(hipMemcpyAsync(c->pkTable.get(), g.h.get(), bytes, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipEventRecord(g.read.get(), stream));
+  g.readSet = true;
+  R->m = k->slots, R->n = (uint32_t)n;
+  R->lights = reinterpret_cast<const rtk::PickLight*>(c->pkTable.get());
+  R->thresholds = reinterpret_cast<const float*>(c->pkTable.get() + lightBytes);
+  return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_render_pick_device(rt_ctx* c, const rt_params* p, const rt_light_pick* k, void* d_accum, void* stream, rt_stats* stats) {
+  PickTable T;
+  int rc = pick_checks(c, p, k, d_accum ? nullptr : "d_accum is null", &T);
+  if (rc != RT_OK) return rc;
+  rtk::PickRec R;
+  if ((rc = stage_pick(c, k, T, static_cast<hipStream_t>(stream), &R)) != RT_OK) return rc;
+  return frame_device(c, p, R, d_accum, stream, stats);
+}
+
+int rt_render_pick(rt_ctx* c, const rt_params* p, const rt_light_pick* k, const float* bg, float* out_rgb, float* accum_out,
+                   rt_stats* stats) {
+  PickTable T;
+  int rc = pick_checks(c, p, k, outputs_refused(bg, out_rgb, accum_out), &T);
+  if (rc != RT_OK) return rc;
+  rtk::PickRec R;
+  if ((rc = stage_pick(c, k, T, nullptr, &R)) != RT_OK) return rc;
+  return frame_host(c, p, R, 1, bg, out_rgb, accum_out, stats);
 }
 
 }  // extern "C"

@@ -186,28 +186,44 @@ struct LightGroupsRec {
   uint32_t n;
   uint32_t masks[RT_LIGHT_GROUPS_MAX];
 };
+// the frame with sampled direct lighting (rt_render_pick): every sample picks m of the context's n lights by the host's
+// threshold table and shades all of its vertices with those, each scaled by 1 / (m p_k) on the host.  PickLight is
+// rt_light padded to 24 floats: the index differs from lane to lane, so a lane fetches its light in 16-byte vector loads
+// (the table stays cache-resident).  Both tables are device memory that the launch reads in stream order.
+struct alignas(16) PickLight {
+  rt_light l;  // L_k with color[c] = w_k * color[c]
+  float pad[3];
+};
+static_assert(sizeof(PickLight) == 96, "PickLight is six 16-byte loads");
+struct PickRec {
+  uint32_t m, n;            // light samples per path vertex (1..RT_PICK_SLOTS_MAX); the context's light count
+  const float* thresholds;  // [n] t_k = (float)C_k, 1.0f from the last light with q_k > 0 onwards: pick(u) = the smallest k with u < t_k
+  const PickLight* lights;  // [n]
+};
 // Which variant a frame is, with its record (which the caller keeps alive over the launch call).  VIEWS_SHUTTER, many
 // views each under its own open shutter (rt_render_views_shutter), has none: tile t renders with views[tileView[t]]'s
 // camera, seed and slice under viewShutters[tileView[t]], from RenderArgs' three tables.
 struct FrameVariant {
-  enum Kind { NONE, LENS, SHUTTER, LIGHTS, VIEWS_SHUTTER };
+  enum Kind { NONE, LENS, SHUTTER, LIGHTS, VIEWS_SHUTTER, PICK };
   Kind kind = NONE;
-  const void* rec = nullptr;  // the LensRec, ShutterRec or LightGroupsRec of kind, else null
+  const void* rec = nullptr;  // the LensRec, ShutterRec, LightGroupsRec or PickRec of kind, else null
   FrameVariant() = default;
   explicit FrameVariant(Kind k) : kind(k) {}
   FrameVariant(const LensRec& r) : kind(LENS), rec(&r) {}
   FrameVariant(const ShutterRec& r) : kind(SHUTTER), rec(&r) {}
   FrameVariant(const LightGroupsRec& r) : kind(LIGHTS), rec(&r) {}
+  FrameVariant(const PickRec& r) : kind(PICK), rec(&r) {}
   explicit operator bool() const { return kind != NONE; }
   // the variant in an error message: "<name> render launch failed"
   const char* name() const {
-    static const char* const names[] = {"", "lens", "shutter", "light-group", "multi-view shutter"};
+    static const char* const names[] = {"", "lens", "shutter", "light-group", "multi-view shutter", "light-pick"};
     return names[kind];
   }
 };
 // launch_render's one-wave-per-workgroup family (brute, sequential, pooled; counted or timed) for a variant (F.kind not
 // NONE); A as launch_render takes it: tileView null, but for VIEWS_SHUTTER a multi-view frame's with the three tables
-// set.  LIGHTS: accum is [G.n][height][width], slice g at accum + g * width * height.  hipErrorInvalidValue where A, the
+// set.  LIGHTS: accum is [G.n][height][width], slice g at accum + g * width * height.  PICK: pooled whenever A.flags bit 0
+// is set, whatever the scene's light count (a vertex sends m <= POOL_L shadow rays).  hipErrorInvalidValue where A, the
 // record or the scene's light count do not fit the variant.
 hipError_t launch_render_variant(const FrameVariant& F, bool brute_force, bool stats, const DevScene& S, const RenderArgs& A,
                                  float4* accum, unsigned long long* counters, hipStream_t stream);

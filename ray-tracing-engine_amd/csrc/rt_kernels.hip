@@ -229,6 +229,10 @@ constexpr int LT_SHUTTER = 2048;
 // vertex and adds every sample into one accumulator slice per group; the vertex pool and shade_direct_seq form the
 // per-group sums (their GROUPS switch).
 constexpr int LT_LIGHTS = 4096;
+// A frame with sampled direct lighting (rt_render_pick): render_tile takes a PickRec and draws every sample's m light
+// indices from a stream of its own before the primary cast; the vertex pool and shade_direct_seq then run over those m
+// slots of the record's scaled lights instead of the scene's list (their PICK switch).
+constexpr int LT_PICK = 8192;
 constexpr uint32_t kPrioMaxNodes = 65536;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(3))) u32x4* lds_u4_ptr;
@@ -852,23 +856,73 @@ RT_DEV void group_cols_add(GroupCols& q, const LightGroupsRec& G, uint32_t l, f3
     if ((G.masks[g] >> l) & 1u) q.c[g] = q.c[g] + term;
 }
 
+// A sample's light indices (rt_render_pick): slot j < R.m holds pick(u_j).  Read by slot through selects (pick_at), never
+// indexed: registers, no scratch.
+struct Picks {
+  uint32_t k0, k1, k2;
+};
+static_assert(RT_PICK_SLOTS_MAX == 3 && RT_PICK_SLOTS_MAX == POOL_L, "a picked frame's slots are the pool's lights");
+RT_DEV uint32_t pick_at(const Picks& p, uint32_t slot) { return slot == 0u ? p.k0 : slot == 1u ? p.k1 : p.k2; }
+// pick(u): the smallest k with u < thresholds[k] — it exists for every u in [0, 1): thresholds[n - 1] is 1.0f.  The
+// index differs from lane to lane: vector loads, of a table that stays cache-resident.
+RT_DEV uint32_t pick_light(const PickRec& R, float u) {
+  uint32_t lo = 0u, hi = R.n - 1u;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (u < R.thresholds[mid]) hi = mid;
+    else lo = mid + 1u;
+  }
+  return lo;
+}
+// the m picks of sample i of pixel pix, from the sample's own stream (one draw per slot, in slot order)
+RT_DEV Picks draw_picks(const PickRec& R, uint32_t seed, uint32_t pix, uint32_t i) {
+  Rng e{rt_stream_seed(seed, RT_STREAM_PICK, pix, i)};
+  Picks p{0u, 0u, 0u};
+  p.k0 = pick_light(R, e.canonF());
+  if (R.m > 1u) p.k1 = pick_light(R, e.canonF());
+  if (R.m > 2u) p.k2 = pick_light(R, e.canonF());
+  return p;
+}
+// What the light loops of a picked frame take in place of the scene's list: the record and the lane's picks.  NoPick:
+// every other frame — an empty argument, so that the instances without picks keep the signatures (and the code) they had.
+struct NoPick {};
+struct PickArgs {
+  const PickRec* R;
+  Picks k;
+};
+template <class PK>
+constexpr bool is_pick = std::is_same_v<PK, PickArgs>;
+// light `slot` of the loop: the scene's, or the scaled light of the lane's slot — six 16-byte loads at most, of which the
+// compiler keeps what the caller reads
+RT_DEV rt_light loop_light(const DevScene& S, NoPick, uint32_t slot) { return S.lights[slot]; }
+RT_DEV rt_light loop_light(const DevScene&, const PickArgs& a, uint32_t slot) { return a.R->lights[pick_at(a.k, slot)].l; }
+RT_DEV uint32_t loop_lights(const DevScene& S, NoPick) { return S.n_lights; }
+RT_DEV uint32_t loop_lights(const DevScene&, const PickArgs& a) { return a.R->m; }
+
 // Renderer.cpp:49-60, one light after the other (brute-force variant and scenes
 // with more than POOL_L lights).  Called by lanes that own a vertex only.
 // GROUPS (rt_render_lights): the terms go into *gc by group instead of into the returned colour, which stays 0.
-template <bool BRUTE, bool STATS, bool GROUPS = false>
+// PK = PickArgs (rt_render_pick): the light list is the sample's picked lights, in slot order, instead of the scene's.
+template <bool BRUTE, bool STATS, bool GROUPS = false, class PK = NoPick>
 RT_DEV f3 shade_direct_seq(const DevScene& S, Rng& g, f3 rayDir, const HitRec& h, uint32_t* stack, f3 hitNormal,
-                           f3 point, LaneStats& st, const LightGroupsRec* G = nullptr, GroupCols* gc = nullptr) {
+                           f3 point, LaneStats& st, const LightGroupsRec* G = nullptr, GroupCols* gc = nullptr, PK pk = PK()) {
   const BsdfBase base = bsdf_base(S.matsDev[h.mesh], hitNormal, -rayDir);  // the light-independent half, once
   f3 color = mk(0.f, 0.f, 0.f);
   if constexpr (GROUPS) group_cols_zero(*gc);
-  for (uint32_t li = 0; li < S.n_lights; li++) {
-    const rt_light Lt = S.lights[li];
+  for (uint32_t li = 0; li < loop_lights(S, pk); li++) {
+    const rt_light Lt = loop_light(S, pk, li);
     const f3 toLight = light_sample(g, Lt) - point;
     HitRec tmp;
     st.shadow++;
     if (cast<BRUTE, true, STATS>(S, true, point, toLight, stack, tmp, st)) continue;
     const f3 bsdf = bsdf_apply(base, toLight);
-    const f3 radiance = light_eval(Lt, point);
+    f3 radiance;
+    if constexpr (is_pick<PK>) {
+      // (the lane's own light is fetched again behind the walk, as the pool's colour loop does: held, its eleven words
+      // that light_eval reads would sit in VGPRs across the traversal)
+      asm volatile("" ::: "memory");
+      radiance = light_eval(loop_light(S, pk, li), point);
+    } else radiance = light_eval(Lt, point);
     if constexpr (GROUPS) group_cols_add(*gc, *G, li, radiance * bsdf);
     else color = color + radiance * bsdf;
   }
@@ -912,15 +966,19 @@ static_assert(VP_WORDS == (int)rtbvh::kWavePoolWords && BLOCK == (int)rtbvh::kSt
 // `bounceRay` says at run time whether a bounce ray is sent.
 // GROUPS (rt_render_lights): the loop after the pool adds every unoccluded term into *gc by group (G's masks) instead of
 // into the returned colour, which stays 0; nothing before that loop differs.
-template <bool STATS, int LT, bool BOUNCE, bool GROUPS = false>
+// PK = PickArgs (rt_render_pick): the pool's lights are the lane's picked ones, in slot order: the fill loop samples
+// them and the colour loop evaluates them, each lane fetching its own from the record's table.  The workers read the full
+// layout's toLight directions only, so the rounds, the hand-out, the stealing and the result bits are the same code.
+template <bool STATS, int LT, bool BOUNCE, bool GROUPS = false, class PK = NoPick>
 RT_DEV f3 vertex_pool(const DevScene& S, bool alive, bool bounceRay, Rng& g, f3 rayDir, uint32_t mesh, f3 hitNormal,
                       f3& point, f3& bdir, uint32_t* stack, uint32_t* pool, HitRec& next, bool& nextFound, LaneStats& st,
-                      const LightGroupsRec* G = nullptr, GroupCols* gc = nullptr) {
+                      const LightGroupsRec* G = nullptr, GroupCols* gc = nullptr, PK pk = PK()) {
   const bool bounce = BOUNCE && bounceRay;
   if constexpr (GROUPS) group_cols_zero(*gc);
   constexpr bool FR = (LT & LT_FASTDET) != 0;  // 1 / length by rtd::recip_fast (see rtd::unit3)
-  const uint32_t lane = threadIdx.x & 63u, nl = S.n_lights;
+  const uint32_t lane = threadIdx.x & 63u, nl = loop_lights(S, pk);
   constexpr bool CP3 = (LT & LT_COMPACT3) != 0, CP2 = CP3 || (LT & LT_COMPACT2) != 0, CP = CP2 || (LT & LT_COMPACT) != 0;
+  static_assert(!is_pick<PK> || !CP, "the picked frames' instances use the full pool layout: workers read directions, never a light");
   using VP = VpLayout<CP3 ? 3 : CP2 ? 2 : CP ? 1 : 0>;
   float* fp = reinterpret_cast<float*>(pool);
   // 32 words: rank -> pixel lane (64 bytes) while rays are handed out; then rank -> victim
@@ -950,7 +1008,9 @@ RT_DEV f3 vertex_pool(const DevScene& S, bool alive, bool bounceRay, Rng& g, f3 
         light_sample_params(g, S.lights[l], rh, rv);
         fp[VP_DIR + (2 * l + 0) * 64 + lane] = rh, fp[VP_DIR + (2 * l + 1) * 64 + lane] = rv;
       } else {
-        const f3 tl = light_sample(g, S.lights[l]) - point;
+        f3 tl;
+        if constexpr (is_pick<PK>) tl = light_sample(g, loop_light(S, pk, l)) - point;
+        else tl = light_sample(g, S.lights[l]) - point;
         fp[VP_DIR + (3 * l + 0) * 64 + lane] = tl.x, fp[VP_DIR + (3 * l + 1) * 64 + lane] = tl.y, fp[VP_DIR + (3 * l + 2) * 64 + lane] = tl.z;
       }
     }
@@ -1145,7 +1205,9 @@ RT_DEV f3 vertex_pool(const DevScene& S, bool alive, bool bounceRay, Rng& g, f3 
                          : CP ? light_point(S.lights[l], fp[VP_DIR + (2 * l + 0) * 64 + lane], fp[VP_DIR + (2 * l + 1) * 64 + lane]) - pt
                               : mk(fp[VP_DIR + (3 * l + 0) * 64 + lane], fp[VP_DIR + (3 * l + 1) * 64 + lane], fp[VP_DIR + (3 * l + 2) * 64 + lane]);
       const f3 bsdf = bsdf_apply<FR>(base, toLight);
-      const f3 radiance = light_eval(S.lights[l], pt);
+      f3 radiance;
+      if constexpr (is_pick<PK>) radiance = light_eval(loop_light(S, pk, l), pt);
+      else radiance = light_eval(S.lights[l], pt);
       if constexpr (GROUPS) group_cols_add(*gc, *G, l, radiance * bsdf);
       else color = color + radiance * bsdf;
     }
@@ -1338,12 +1400,14 @@ RT_DEV void group_samples_add(const RenderArgs& A, const LightGroupsRec& G, floa
 }
 
 // The record a frame variant's instances take as a kernel argument of their own, by its LT_* bits: the lens, the shutter
-// of a single-view frame (a multi-view one reads its records from RenderArgs' tables), the light groups — or none.
+// of a single-view frame (a multi-view one reads its records from RenderArgs' tables), the light groups, the light
+// picks — or none.
 struct NoRec {};
 template <int LTV>
 using frame_rec_t = std::conditional_t<(LTV & LT_LENS) != 0, LensRec,
                     std::conditional_t<(LTV & LT_LIGHTS) != 0, LightGroupsRec,
-                    std::conditional_t<(LTV & LT_SHUTTER) != 0 && (LTV & LT_VIEWS) == 0, ShutterRec, NoRec>>>;
+                    std::conditional_t<(LTV & LT_PICK) != 0, PickRec,
+                    std::conditional_t<(LTV & LT_SHUTTER) != 0 && (LTV & LT_VIEWS) == 0, ShutterRec, NoRec>>>>;
 // (what the instances without a record leave out; the others do not compile without theirs)
 template <int LTV>
 constexpr const frame_rec_t<LTV>* no_record() {
@@ -1354,12 +1418,14 @@ constexpr const frame_rec_t<LTV>* no_record() {
 template <bool BRUTE, bool PHOTON, bool POOLED, bool STATS, int LTV, class HP = Heap>
 RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restrict__ accum, const Lds& L, uint32_t* pool,
                         float* ex, uint32_t wave, LaneStats& st, const frame_rec_t<LTV>* rec = no_record<LTV>()) {
-  constexpr int LT = LTV & ~(LT_VIEWS | LT_LENS | LT_SHUTTER | LT_LIGHTS);
+  constexpr int LT = LTV & ~(LT_VIEWS | LT_LENS | LT_SHUTTER | LT_LIGHTS | LT_PICK);
   constexpr bool VIEWS = (LTV & LT_VIEWS) != 0;
   constexpr bool LENS = (LTV & LT_LENS) != 0;
   constexpr bool SHUTTER = (LTV & LT_SHUTTER) != 0;
   constexpr bool LIGHTS = (LTV & LT_LIGHTS) != 0;
+  constexpr bool PICK = (LTV & LT_PICK) != 0;
   static_assert(!LIGHTS || (!VIEWS && !LENS && !SHUTTER && !PHOTON), "light groups go with the plain frame only");
+  static_assert(!PICK || (!VIEWS && !LENS && !SHUTTER && !LIGHTS && !PHOTON), "light picks go with the plain frame only");
   static_assert(!LENS || !VIEWS, "no multi-view lens frames");
   static_assert(!SHUTTER || !LENS, "the shutter's lens is its own: LT_SHUTTER does not go with LT_LENS");
   constexpr bool FR = (LT & LT_FASTDET) != 0;  // 1 / length by rtd::recip_fast (see rtd::unit3)
@@ -1421,6 +1487,9 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
     GroupCols g0, g1, g2, gv;  // (LT_LIGHTS) the three vertices' colours per group, and the current vertex's
     if constexpr (LIGHTS) group_cols_zero(g0), group_cols_zero(g1), group_cols_zero(g2);
     bool primary = true, alive = active;
+    // (LT_PICK) the sample's light indices: drawn once, before the primary cast, for all of its vertices
+    Picks pk{0u, 0u, 0u};
+    if constexpr (PICK) pk = draw_picks(*rec, A.seed, pix, i);
     if constexpr (pooled) {
       // primary ray (coherent: traced in lock step), then one pool per vertex
       HitRec h;
@@ -1452,6 +1521,9 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
         if constexpr (LIGHTS) {
           static_assert(!SHADOW_BODY, "the light-group instances keep their trees in HBM / L2");
           c = vertex_pool<STATS, LT, true, true>(S, alive, bounce, g, d, mesh, nrm, pt, bdir, L.stack, pool, nh, nfound, st, rec, &gv);
+        } else if constexpr (PICK) {
+          static_assert(!SHADOW_BODY, "the light-pick instances keep their trees in HBM / L2");
+          c = vertex_pool<STATS, LT, true, false, PickArgs>(S, alive, bounce, g, d, mesh, nrm, pt, bdir, L.stack, pool, nh, nfound, st, nullptr, nullptr, PickArgs{rec, pk});
         } else
         c = SHADOW_BODY && !bounce
                          ? vertex_pool<STATS, LT, false>(S, alive, false, g, d, mesh, nrm, pt, bdir, L.stack, pool, nh, nfound, st)
@@ -1485,6 +1557,8 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
         if (alive) c = shade_photon<STATS, HP>(S, A, d, h, L, nrm, pt, st);
       } else if constexpr (LIGHTS) {
         if (alive) c = shade_direct_seq<BRUTE, STATS, true>(S, g, d, h, L.stack, nrm, pt, st, rec, &gv);
+      } else if constexpr (PICK) {
+        if (alive) c = shade_direct_seq<BRUTE, STATS, false, PickArgs>(S, g, d, h, L.stack, nrm, pt, st, nullptr, nullptr, PickArgs{rec, pk});
       } else {
         if (alive) c = shade_direct_seq<BRUTE, STATS>(S, g, d, h, L.stack, nrm, pt, st);
       }
@@ -1745,7 +1819,7 @@ __global__ __launch_bounds__(1024, 8) void k_trace_stream(DevScene S, const floa
 #include "rays_kernels.h"
 
 // ---------------------------------------------------------------- the frame's generator variants (rt_render_lens,
-// rt_render_shutter, rt_render_views_shutter, rt_render_lights)
+// rt_render_shutter, rt_render_views_shutter, rt_render_lights, rt_render_pick)
 #include "frame_variants.h"
 
 // ---------------------------------------------------------------- frame assembly (multi-GPU)

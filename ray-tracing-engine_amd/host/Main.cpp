@@ -129,6 +129,19 @@ int main(int argc, char** argv) {
       return 1;
     }
   }
+  if (args.lightPick() != 0) {
+    // -lightpick M: M = 1..RT_PICK_SLOTS_MAX sampled lights per path vertex, and nothing else
+    if (args.lightPick() < 1 || args.lightPick() > RT_PICK_SLOTS_MAX) {
+      std::cerr << "error: -lightpick must be 1.." << RT_PICK_SLOTS_MAX << " light samples per path vertex" << std::endl;
+      return 1;
+    }
+    if (GpuSettings::get().devices.size() > 1 || args.numPhotons() > 0 || args.adaptive() >= 0. || !args.shutter().empty() ||
+        args.aperture() > 0. || !args.lights().empty()) {
+      std::cerr << "error: -lightpick runs on one GPU, without -p, -adaptive, -shutter, -aperture and -lights" << std::endl;
+      return 1;
+    }
+    GpuSettings::get().lightPick = static_cast<unsigned>(args.lightPick());
+  }
   if (args.adaptive() >= 0.) {
     if (GpuSettings::get().devices.size() > 1) {
       std::cerr << "error: -adaptive runs on one GPU only (not with -gpus > 1)" << std::endl;

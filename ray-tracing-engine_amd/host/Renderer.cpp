@@ -153,6 +153,19 @@ inline void Renderer::render(Image& image) {
     std::cout << "Raytracing through a lens of radius " << lens.aperture << " focused at " << lens.focus_distance << "... ["
               << std::string(50, '#') << "] 100%" << std::endl;
     image = result;
+  } else if (p.spp > 0 && GpuSettings::get().lightPick > 0) {
+    // -lightpick M (extension): the frame with M sampled lights per path vertex, picked by the lights' power
+    // (rt_render_pick), in one launch; update.ppm is written once.  Without -lightpick this branch is not taken.
+    if (multi || p.use_photons) throw std::runtime_error("-lightpick runs on one GPU, without -p");
+    rt_light_pick pick = {};
+    pick.slots = GpuSettings::get().lightPick;
+    rt_stats st = {};
+    GpuSession::check(rt_render_pick(ctx0, &p, &pick, image.data(), result.data(), nullptr, &st), "rt_render_pick");
+    m_stats = st;
+    result.savePPM("update.ppm");
+    std::cout << "Raytracing with " << pick.slots << " of " << m_scene.lightsources().size() << " lights sampled per path vertex... ["
+              << std::string(50, '#') << "] 100%" << std::endl;
+    image = result;
   } else if (p.spp > 0) {
     // The reference re-saves update.ppm after EVERY pass (Renderer.cpp:261-269).  Here a
     // "pass" is a sample range of one launch; GpuSettings::progress = P > 0 renders P

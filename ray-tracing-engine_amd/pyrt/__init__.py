@@ -199,6 +199,15 @@ class LightGroups(C.Structure):
     _fields_ = [("n_groups", C.c_uint32), ("masks", C.c_uint32 * LIGHT_GROUPS_MAX), ("reserved", C.c_uint32 * 3)]
 
 
+PICK_SLOTS_MAX = 3
+
+
+class LightPick(C.Structure):
+    """rt_light_pick: `slots` light samples per path vertex, picked by the caller's importance per light (host floats) or,
+    without one, by the lights' power."""
+    _fields_ = [("slots", C.c_uint32), ("n_importance", C.c_uint32), ("importance", C.c_void_p), ("reserved", C.c_uint32 * 5)]
+
+
 class DenoiseParams(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("iterations", C.c_uint32), ("sigma_color", C.c_float),
                 ("sigma_normal", C.c_float), ("sigma_position", C.c_float), ("reserved", C.c_uint32 * 6)]
@@ -399,7 +408,7 @@ AMD_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_create", "rt_destroy", "rt
                "rt_render_rays_device", "rt_render_lens", "rt_render_lens_device", "rt_render_shutter",
                "rt_render_shutter_device", "rt_render_views_shutter", "rt_render_views_shutter_device",
                "rt_render_adaptive_shutter", "rt_render_adaptive_shutter_device", "rt_render_lights",
-               "rt_render_lights_device"]
+               "rt_render_lights_device", "rt_render_pick", "rt_render_pick_device"]
 HOST_SYMBOLS = ["rt_host_scene_build", "rt_host_scene_desc", "rt_host_scene_free", "rt_host_last_error",
                 "rt_host_fill_background", "rt_host_save_ppm", "rt_host_kd_order", "rt_host_light_basis"]
 
@@ -448,6 +457,17 @@ def make_light_groups(masks):
     for j, m in enumerate(masks):
         g.masks[j] = m
     return g
+
+
+def make_light_pick(slots, importance=None):
+    """An rt_light_pick: `slots` light samples per path vertex; `importance`: one non-negative float per light of the
+    context (copied; the record keeps the copy alive), or None for the default, the lights' power."""
+    k = LightPick()
+    k.slots = int(slots)
+    if importance is not None:
+        k._importance = np.ascontiguousarray(importance, np.float32).reshape(-1).copy()
+        k.n_importance, k.importance = len(k._importance), k._importance.ctypes.data
+    return k
 
 
 def make_shutters(shutters, n):
@@ -537,6 +557,10 @@ def amd():
                                                C.POINTER(Stats)]
         L.rt_render_lights.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(LightGroups), C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.POINTER(Stats)]
+        L.rt_render_pick.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(LightPick), C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.POINTER(Stats)]
+        L.rt_render_pick_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(LightPick), C.c_void_p, C.c_void_p,
+                                            C.POINTER(Stats)]
         L.rt_render_lights_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(LightGroups), C.c_void_p, C.c_void_p,
                                               C.POINTER(Stats)]
         L.rt_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.POINTER(Aov), C.c_void_p]
@@ -1068,6 +1092,28 @@ class Context:
         st = Stats() if stats else None
         _check(amd().rt_render_lights_device(self._h, C.byref(params), C.byref(groups), C.c_void_p(d_accum), C.c_void_p(stream or None),
                                              C.byref(st) if stats else None))
+        return st
+
+    def render_pick(self, params, pick, bg=None, want_accum=True, importance=None):
+        """rt_render_pick: the frame with sampled direct lighting (`pick`: make_light_pick, or the slot count with
+        `importance` beside it); returns (out [h][w][3] or None without bg, accum [h][w][4] or None, stats)."""
+        if not isinstance(pick, LightPick):
+            pick = make_light_pick(pick, importance)
+        w, h = params.width, params.height
+        out = np.empty((h, w, 3), np.float32) if bg is not None else None
+        acc = np.empty((h, w, 4), np.float32) if want_accum else None
+        st = Stats()
+        bgc = None if bg is None else np.ascontiguousarray(bg, np.float32)
+        _check(amd().rt_render_pick(self._h, C.byref(params), C.byref(pick), _ptr(bgc), _ptr(out), _ptr(acc), C.byref(st)))
+        return out, acc, st
+
+    def render_pick_device(self, params, pick, d_accum, stream=0, stats=False, importance=None):
+        """rt_render_pick_device: accumulate into the caller-zeroed device d_accum [h][w][4] on `stream`; sample ranges chain."""
+        if not isinstance(pick, LightPick):
+            pick = make_light_pick(pick, importance)
+        st = Stats() if stats else None
+        _check(amd().rt_render_pick_device(self._h, C.byref(params), C.byref(pick), C.c_void_p(d_accum), C.c_void_p(stream or None),
+                                           C.byref(st) if stats else None))
         return st
 
     def render_views_shutter(self, params, cameras, shutters, bg=None, seeds=None, want_accum=True):
