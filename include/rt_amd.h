@@ -15,6 +15,8 @@
  *                                  camera or light): the resident context follows it, tree refit
  *   rt_update_transforms        <- the same with one matrix per mesh (Main.cpp:88-99): the device transforms a
  *                                  resident rest pose, nothing per vertex crosses the bus
+ *   rt_set_skin / rt_update_skin <- (no counterpart) deforming meshes: the device blends the rest pose under up to four
+ *                                  bones per vertex (linear blend skinning), one record per bone crosses the bus
  *   rt_bvh_quality_get / rt_rebuild <- (no counterpart) the surface-area cost of the refit tree against the tree as built,
  *                                  and the tree built again in place from the resident arrays when it has degraded
  *   rt_render                   <- the spp/y/x loop + resolve (Renderer.cpp:219-271)
@@ -79,8 +81,8 @@
  *     rt_render_device, rt_render_views_device, rt_render_rays_device, rt_render_shutter_device,
  *     rt_render_views_shutter_device, rt_render_lights_device, rt_render_pick_device,
  *     rt_render_lens_device with stats != NULL;
- *     rt_render_adaptive_device and rt_render_adaptive_shutter_device (every pass); rt_update_vertices_device and
- *     rt_update_transforms (twice);
+ *     rt_render_adaptive_device and rt_render_adaptive_shutter_device (every pass); rt_update_vertices_device,
+ *     rt_update_transforms and rt_update_skin (twice);
  *     the four multi-view forms when a view lies far enough out to need a wider box padding (a refit).
  *   HOST forms (rt_render, rt_render_aov, rt_denoise, rt_update, rt_trace, rt_knn, rt_bvh_quality_get, rt_rebuild,
  *     the photon calls ...) run on the NULL stream and return when their result is in host memory.  The null
@@ -328,10 +330,71 @@ typedef struct rt_transform_update {
 } rt_transform_update;
 int rt_update_transforms(rt_ctx* ctx, const rt_transform_update* u, void* stream, rt_update_report* rep /* may be NULL */);
 
+/* ---- animating deforming meshes by bones: linear blend skinning (no counterpart) -----------------------
+ * rt_update whose positions and normals the DEVICE blends from the resident rest pose, a resident skin — four bone
+ * indices and four weights per vertex, sent once — and one rt_mesh_transform record per BONE: a frame sends 88 bytes per
+ * bone instead of every vertex.
+ *
+ * rt_set_skin makes a skin resident (replacing the one before), or releases it (skin == NULL).  It changes nothing else
+ * in the context: the same frames before and after, the photon map and the rest pose kept.  The resident skin survives
+ * every update and rt_rebuild (the vertex count of a context never changes) until rt_set_skin replaces or releases it
+ * or rt_destroy runs.  A host form: it runs on the NULL stream and returns when the arrays are in device memory.
+ * Validation comes first and a rejected call leaves the skin that was resident in force.  In this order — what the
+ * arguments alone decide is answered before the context or a device is asked for —:
+ *   RT_ERR_INVALID  a null ctx with skin == NULL (nothing to release from);
+ *   RT_ERR_INVALID  bone or weight null; non-zero reserved words; n_bones outside 1..65536;
+ *   RT_ERR_INVALID  vertex by vertex, in order: a non-finite weight (rt_last_error names the vertex), then an index
+ *                   >= n_bones (it names the vertex and the slot) — the index of a zero-weight slot is validated too;
+ *   RT_ERR_INVALID  a null ctx; n_vertices different from the context's;
+ *   RT_ERR_UNSUPPORTED  RT_NODES_Q8 contexts;   RT_ERR_STATE  a context that refuses launches.
+ *
+ * rt_update_skin poses the rest pose of rt_update_transforms — the same arrays, the same lazy snapshot: the two calls
+ * share it.  Poses are absolute, from the rest pose, never cumulative; a transforms call between two skin calls changes
+ * nothing about the second; a call that gives vertex arrays makes the live arrays the new rest pose, as above.
+ * Per vertex, rest position (x, y, z) and rest normal (a, b, c), all in float32, every product and sum rounded, nothing
+ * fused: X' = N' = (+0, +0, +0), then for each slot k = 0..3 IN SLOT ORDER whose weight[k] != 0 (a zero of either sign is
+ * skipped and its bone's record is not read), with R = bones[bone[k]] and w = weight[k]:
+ *   P_i = ((R.m[i][0] x + R.m[i][1] y) + R.m[i][2] z) + R.m[i][3]      Q_i = (R.n[i][0] a + R.n[i][1] b) + R.n[i][2] c
+ *   X'_i = X'_i + (w P_i)                                              N'_i = N'_i + (w Q_i)
+ * — P and Q are rt_update_transforms' expression, unchanged.  Normals are not renormalised (the shader normalises the
+ * interpolated normal).  A vertex whose four weights are all zero keeps its rest arrays bit for bit, -0 included: the
+ * analogue of RT_XF_STATIC.  A vertex with the single weight 1 is NOT that: +0 + (1 P) turns a P of -0 into +0.
+ * After a successful call the context is, bit for bit, what rt_update with vertex_pos / vertex_nrm = those arrays and the
+ * same camera and lights would leave (tree, rt_bvh_info, every frame and pass, the photon map released, the report).
+ * Validation comes first and a rejected call leaves the context and d_prev_pos untouched.  In this order:
+ *   RT_ERR_INVALID  a null u or bones; non-zero reserved words;
+ *   RT_ERR_INVALID  bone by bone, in order: non-zero flags, then a non-finite entry of m or n (rt_last_error names the
+ *                   bone);
+ *   RT_ERR_INVALID  lights NULL with n_lights > 0;
+ *   RT_ERR_INVALID  a null ctx;   RT_ERR_STATE  no resident skin;   RT_ERR_INVALID  n_bones different from the skin's;
+ *   RT_ERR_UNSUPPORTED  RT_NODES_Q8 contexts;   RT_ERR_STATE  a context that refuses launches;
+ *   RT_ERR_INVALID  a blended position a triangle references coming out non-finite ("non-finite vertex position").
+ * Ordered on `stream` (a hipStream_t, may be NULL) and synchronises it as rt_update_transforms does, twice. */
+#define RT_SKIN_INFLUENCES 4
+typedef struct rt_skin {
+  uint32_t n_vertices;    /* must equal the context's                                                               */
+  uint32_t n_bones;       /* 1 .. 65536                                                                             */
+  const uint16_t* bone;   /* [n_vertices][4], HOST memory: the bone index of each slot, all of them < n_bones       */
+  const float* weight;    /* [n_vertices][4], HOST memory: the weight of each slot, finite; 0 = the slot is unused  */
+  uint32_t reserved[6];   /* zero                                                                                   */
+} rt_skin;
+int rt_set_skin(rt_ctx* ctx, const rt_skin* skin /* NULL: release the resident skin */);
+
+typedef struct rt_skin_update {
+  const rt_mesh_transform* bones;  /* [n_bones], HOST memory, required: m for positions, n for normals; flags 0    */
+  uint32_t n_bones;                /* must equal the resident skin's                                               */
+  uint32_t n_lights;
+  const rt_camera* camera;         /* or NULL = unchanged, as rt_transform_update                                  */
+  const rt_light* lights;          /* [n_lights] or NULL = unchanged                                               */
+  void* d_prev_pos;                /* DEVICE [n_vertices][3] or NULL, as rt_transform_update                       */
+  uint32_t reserved[6];            /* zero                                                                         */
+} rt_skin_update;
+int rt_update_skin(rt_ctx* ctx, const rt_skin_update* u, void* stream, rt_update_report* rep /* may be NULL */);
+
 /* ---- rebuilding a refit tree ----------------------------------------------------------------------------
  * A refit keeps the topology rt_create built, so over a long animation the tree drifts from the geometry.  The two calls
  * below measure that and undo it without rt_destroy + rt_create: nothing crosses the bus towards the device, and the
- * handle, the photon map, the rest pose of rt_update_transforms and the profile events stay.
+ * handle, the photon map, the rest pose of rt_update_transforms, the resident skin and the profile events stay.
  *
  * rt_bvh_quality_get: the surface-area cost of the resident tree, one device pass over its float node records (the
  * rt_bvh_export form: node i has two slots k with a box lo, hi in float32 and a ref child[k]; ref >= 0 an inner node,
@@ -368,7 +431,7 @@ int rt_bvh_quality_get(rt_ctx* ctx, rt_bvh_quality* out);
  * and the rt_options it was created with, under rt_create's builder rule (bvh_builder, RT_BVH_GPU, RT_BVH_AUTO_FROM, the
  * 16- and 1,024-triangle special cases): the same code builds both.  The refit depth table and any rt_bvh_tune result are
  * dropped; cost_built and refits start again.  Hits do not depend on the tree, so — unlike an update — a rebuild KEEPS
- * the photon map, the rest pose of rt_update_transforms, the profile events and the handle: every frame and pass is
+ * the photon map, the rest pose of rt_update_transforms, the resident skin, the profile events and the handle: every frame and pass is
  * bit-identical before and after.
  * The host passes of a build (validation, the size keys from the host's log2, the host builder for small scenes) read the
  * positions, vertex ids and mesh tables back for the duration of the call; the new tree is built into staging buffers

@@ -712,6 +712,76 @@ __global__ __launch_bounds__(kXfTile) void k_transform(const float* __restrict__
   }
 }
 
+// rt_update_skin: the rest pose blended under up to four bones per vertex, in k_transform's tile shape — 256 vertices per
+// tile, positions and normals in and out as whole dwords in address order through LDS, the magnitudes of everything written
+// folded on the way out (out[1], out[2]; launch_skin runs k_magnitudes' triangle loop for out[0]).  A lane loads its own
+// vertex's four 16-bit indices as one uint2 and its four weights as one float4 (both arrays are [n][4], so lane i reads
+// base + 8 i and base + 16 i: single aligned requests).  The bone records are gathered per lane from the table inside
+// the branch on the slot's weight: a zero-weight slot (either sign) loads nothing, so a vertex of one influence fetches
+// one record; the lanes of a wave mostly share a few bones and hit the same cache lines.  A vertex whose weights are all
+// zero keeps the rest bits.  rt_set_skin has checked every index against the table's size, zero-weight slots included.
+// The arithmetic is rt_amd.h's: both accumulators from +0, slot order, _rn intrinsics so that no flag can fuse it.
+__global__ __launch_bounds__(kXfTile) void k_skin(const float* __restrict__ restPos, const float* __restrict__ restNrm,
+                                                  const uint2* __restrict__ bone, const float4* __restrict__ weight,
+                                                  const rt_mesh_transform* __restrict__ table, uint32_t nVerts,
+                                                  float* __restrict__ outPos, float* __restrict__ outNrm, uint32_t* __restrict__ out) {
+  __shared__ float sP[3 * kXfTile], sN[3 * kXfTile];
+  const uint32_t tid = threadIdx.x;
+  const uint32_t nTiles = (nVerts + kXfTile - 1) / kXfTile;
+  const size_t nFloats = 3 * (size_t)nVerts;
+  uint32_t mPos = 0, mNrm = 0;
+  for (uint32_t tile = blockIdx.x; tile < nTiles; tile += gridDim.x) {
+    const size_t base = 3 * (size_t)tile * kXfTile;
+    const uint32_t v = tile * kXfTile + tid;
+    uint2 b = make_uint2(0u, 0u);
+    float4 w4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (v < nVerts) b = bone[v], w4 = weight[v];
+#pragma unroll
+    for (uint32_t r = 0; r < 3; ++r) {
+      const size_t k = base + r * kXfTile + tid;
+      if (k < nFloats) sP[r * kXfTile + tid] = restPos[k], sN[r * kXfTile + tid] = restNrm[k];
+    }
+    __syncthreads();
+    const float w[4] = {w4.x, w4.y, w4.z, w4.w};
+    const uint32_t idx[4] = {b.x & 0xffffu, b.x >> 16, b.y & 0xffffu, b.y >> 16};
+    if (w[0] != 0.f || w[1] != 0.f || w[2] != 0.f || w[3] != 0.f) {  // (lanes past the end hold zero weights)
+      const float x = sP[3 * tid], y = sP[3 * tid + 1], z = sP[3 * tid + 2];
+      const float a = sN[3 * tid], bb = sN[3 * tid + 1], c = sN[3 * tid + 2];
+      float X[3] = {0.f, 0.f, 0.f}, N[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (w[k] != 0.f) {
+          float p[3], q[3];
+          xf_apply(table[idx[k]], x, y, z, a, bb, c, p, q);
+#pragma unroll
+          for (int i = 0; i < 3; ++i) X[i] = __fadd_rn(X[i], __fmul_rn(w[k], p[i])), N[i] = __fadd_rn(N[i], __fmul_rn(w[k], q[i]));
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < 3; ++i) sP[3 * tid + i] = X[i], sN[3 * tid + i] = N[i];
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t r = 0; r < 3; ++r) {
+      const size_t k = base + r * kXfTile + tid;
+      if (k < nFloats) {
+        const float p = sP[r * kXfTile + tid], q = sN[r * kXfTile + tid];
+        outPos[k] = p, outNrm[k] = q;
+        mPos = max(mPos, __float_as_uint(p) & 0x7fffffffu), mNrm = max(mNrm, __float_as_uint(q) & 0x7fffffffu);
+      }
+    }
+    __syncthreads();
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    mPos = max(mPos, (uint32_t)__shfl_xor((int)mPos, off));
+    mNrm = max(mNrm, (uint32_t)__shfl_xor((int)mNrm, off));
+  }
+  if ((tid & 63u) == 0u) {
+    if (mPos) atomicMax(out + 1, mPos);
+    if (mNrm) atomicMax(out + 2, mNrm);
+  }
+}
+
 // the leaf-order records again: each record keeps its triangle (the id it holds), its vertices are read anew
 __global__ void k_refit_tris(const float* __restrict__ vpos, const uint4* __restrict__ triShade, uint32_t n, float4* __restrict__ recs) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1908,6 +1978,20 @@ hipError_t launch_transform(const float* dRestPos, const float* dRestNrm, const 
   hipLaunchKernelGGL(k_transform, dim3(std::min(4096u, tiles)), dim3(kXfTile), 0, stream, dRestPos, dRestNrm, dTable, dMeshVtxBegin, nMeshes,
                      nVerts, dOutPos, dOutNrm, dOut3);
   // word 0 over the finished positions: k_magnitudes' triangle loop alone (no vertices, no normals: words 1 and 2 stay)
+  const uint32_t blocks = std::max(1u, std::min(4096u, (nTris + 255u) / 256u));
+  hipLaunchKernelGGL(k_magnitudes, dim3(blocks), dim3(256), 0, stream, (const float*)dOutPos, (const float*)nullptr, dTriShade, nTris, 0u, dOut3);
+  return hipGetLastError();
+}
+
+hipError_t launch_skin(const float* dRestPos, const float* dRestNrm, const uint16_t* dBone, const float* dWeight,
+                       const rt_mesh_transform* dTable, uint32_t nVerts, float* dOutPos, float* dOutNrm, const uint4* dTriShade,
+                       uint32_t nTris, uint32_t* dOut3, hipStream_t stream) {
+  hipError_t e = hipMemsetAsync(dOut3, 0, 3 * sizeof(uint32_t), stream);
+  if (e != hipSuccess || nVerts == 0) return e;
+  const uint32_t tiles = (nVerts + kXfTile - 1) / kXfTile;
+  hipLaunchKernelGGL(k_skin, dim3(std::min(4096u, tiles)), dim3(kXfTile), 0, stream, dRestPos, dRestNrm, reinterpret_cast<const uint2*>(dBone),
+                     reinterpret_cast<const float4*>(dWeight), dTable, nVerts, dOutPos, dOutNrm, dOut3);
+  // word 0 over the finished positions, as launch_transform
   const uint32_t blocks = std::max(1u, std::min(4096u, (nTris + 255u) / 256u));
   hipLaunchKernelGGL(k_magnitudes, dim3(blocks), dim3(256), 0, stream, (const float*)dOutPos, (const float*)nullptr, dTriShade, nTris, 0u, dOut3);
   return hipGetLastError();

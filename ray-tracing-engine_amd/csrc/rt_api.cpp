@@ -313,6 +313,12 @@ struct rt_ctx {
   DevBuf<float> restPos, restNrm;
   bool restValid = false;
   DevBuf<rt_mesh_transform> xfTable;
+  // rt_set_skin / rt_update_skin: the resident skin — [nVertices][4] bone indices and weights, as the caller laid them out —
+  // and the table the bone records of a call go to (skinBones of them; 0 = no skin)
+  DevBuf<uint16_t> skinBone;
+  DevBuf<float> skinWeight;
+  DevBuf<rt_mesh_transform> skinTable;
+  uint32_t skinBones = 0;
   // scratch of rt_denoise_device and rt_svgf_device (rtk::filter_scratch; grows on demand: ensure_filter_scratch)
   DevBuf<float4> dnScratch;
   size_t dnCap = 0;
@@ -2292,6 +2298,40 @@ int update_ctx(rt_ctx* c, const Update& u, hipStream_t stream, std::chrono::stea
   return RT_OK;
 }
 
+// rt_update_transforms and rt_update_skin, before their kernel: the rest pose — a copy of the live arrays, taken on `stream`
+// when none is valid —, the scratch of rt_update's host form that the result goes to, and the magnitude block.  Nothing
+// here is visible until update_ctx's own validation has passed.
+int prepare_rest_pose(rt_ctx* c, hipStream_t stream) {
+  const size_t nv = 3 * (size_t)c->nVertices;
+  if (!c->restPos) HIP_TRY(dev_alloc(&c->restPos, nv));
+  if (!c->restNrm) HIP_TRY(dev_alloc(&c->restNrm, nv));
+  if (!c->updPos) HIP_TRY(dev_alloc(&c->updPos, nv));
+  if (!c->updNrm) HIP_TRY(dev_alloc(&c->updNrm, nv));
+  if (!c->dMag) HIP_TRY(dev_alloc(&c->dMag, 3));
+  if (!c->restValid) {
+    HIP_TRY(hipMemcpyAsync(c->restPos.get(), c->vpos.get(), nv * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(c->restNrm.get(), c->vnrm.get(), nv * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    c->restValid = true;
+  }
+  return RT_OK;
+}
+// ... and after it: the posed arrays wait in the scratch and their summary is on its way into c->dMag
+int update_from_rest(rt_ctx* c, const rt_camera* camera, const rt_light* lights, uint32_t nLights, void* dPrevPos, hipStream_t stream,
+                     std::chrono::steady_clock::time_point t0, rt_update_report* rep) {
+  Update x;
+  x.dPos = c->updPos.get(), x.dNrm = c->updNrm.get();
+  x.camera = camera, x.lights = lights, x.nLights = nLights;
+  x.fromRest = x.magQueued = true, x.dPrevPos = dPrevPos;
+  return update_ctx(c, x, stream, t0, rep);
+}
+// the entries of a record that its call reads, all finite
+bool finite_record(const rt_mesh_transform& t) {
+  bool finite = true;
+  for (int i = 0; i < 12; ++i) finite = finite && std::isfinite(t.m[i / 4][i % 4]);
+  for (int i = 0; i < 9; ++i) finite = finite && std::isfinite(t.n[i / 3][i % 3]);
+  return finite;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2344,10 +2384,7 @@ int rt_update_transforms(rt_ctx* c, const rt_transform_update* u, void* stream_,
     const rt_mesh_transform& t = u->transforms[j];
     if (t.flags & ~(uint32_t)RT_XF_STATIC) return fail(RT_ERR_INVALID, "update: mesh %u: unknown transform flags 0x%x", j, t.flags);
     if (t.flags & RT_XF_STATIC) continue;
-    bool finite = true;
-    for (int i = 0; i < 12; ++i) finite = finite && std::isfinite(t.m[i / 4][i % 4]);
-    for (int i = 0; i < 9; ++i) finite = finite && std::isfinite(t.n[i / 3][i % 3]);
-    if (!finite) return fail(RT_ERR_INVALID, "update: mesh %u: non-finite entry in its transform", j);
+    if (!finite_record(t)) return fail(RT_ERR_INVALID, "update: mesh %u: non-finite entry in its transform", j);
   }
   if (!u->lights && u->n_lights) return fail(RT_ERR_INVALID, "update: lights is null but n_lights is %u", u->n_lights);
   if (!c) return fail(RT_ERR_INVALID, "ctx/update is null");
@@ -2356,28 +2393,78 @@ int rt_update_transforms(rt_ctx* c, const rt_transform_update* u, void* stream_,
   if (rc != RT_OK) return rc;
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  const size_t nv = 3 * (size_t)c->nVertices;
-  // nothing below is visible until update_ctx's own validation has passed: the rest pose is a copy of the live arrays,
-  // the result goes to the scratch of rt_update's host form
-  if (!c->restPos) HIP_TRY(dev_alloc(&c->restPos, nv));
-  if (!c->restNrm) HIP_TRY(dev_alloc(&c->restNrm, nv));
-  if (!c->updPos) HIP_TRY(dev_alloc(&c->updPos, nv));
-  if (!c->updNrm) HIP_TRY(dev_alloc(&c->updNrm, nv));
+  if ((rc = prepare_rest_pose(c, stream)) != RT_OK) return rc;
   if (!c->xfTable) HIP_TRY(dev_alloc(&c->xfTable, c->nMeshes));
-  if (!c->dMag) HIP_TRY(dev_alloc(&c->dMag, 3));
-  if (!c->restValid) {
-    HIP_TRY(hipMemcpyAsync(c->restPos.get(), c->vpos.get(), nv * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(c->restNrm.get(), c->vnrm.get(), nv * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    c->restValid = true;
-  }
   HIP_TRY(hipMemcpyAsync(c->xfTable.get(), u->transforms, c->nMeshes * sizeof(rt_mesh_transform), hipMemcpyHostToDevice, stream));
   HIP_TRY(rtk::launch_transform(c->restPos.get(), c->restNrm.get(), c->xfTable.get(), c->meshVtxBegin.get(), c->nMeshes, c->nVertices,
                                 c->updPos.get(), c->updNrm.get(), c->triShade.get(), c->S.n_tris, c->dMag.get(), stream));
-  Update x;
-  x.dPos = c->updPos.get(), x.dNrm = c->updNrm.get();
-  x.camera = u->camera, x.lights = u->lights, x.nLights = u->n_lights;
-  x.fromRest = x.magQueued = true, x.dPrevPos = u->d_prev_pos;
-  return update_ctx(c, x, stream, t0, rep);
+  return update_from_rest(c, u->camera, u->lights, u->n_lights, u->d_prev_pos, stream, t0, rep);
+}
+
+int rt_set_skin(rt_ctx* c, const rt_skin* s) {
+  if (!s) {
+    if (!c) return fail(RT_ERR_INVALID, "ctx/skin is null");
+    HIP_TRY(hipSetDevice(c->device));
+    c->skinBone.reset(), c->skinWeight.reset(), c->skinTable.reset();
+    c->skinBones = 0;
+    return RT_OK;
+  }
+  // what the skin says of itself comes before anything of the context
+  if (!s->bone || !s->weight) return fail(RT_ERR_INVALID, "skin: bone/weight is null");
+  for (uint32_t r : s->reserved)
+    if (r) return fail(RT_ERR_INVALID, "skin: reserved words must be zero");
+  if (s->n_bones < 1 || s->n_bones > 65536) return fail(RT_ERR_INVALID, "skin: n_bones is %u, outside 1..65536", s->n_bones);
+  for (uint32_t v = 0; v < s->n_vertices; ++v) {
+    const size_t at = RT_SKIN_INFLUENCES * (size_t)v;
+    for (uint32_t k = 0; k < RT_SKIN_INFLUENCES; ++k)
+      if (!std::isfinite(s->weight[at + k])) return fail(RT_ERR_INVALID, "skin: vertex %u: non-finite weight", v);
+    for (uint32_t k = 0; k < RT_SKIN_INFLUENCES; ++k)
+      if (s->bone[at + k] >= s->n_bones)
+        return fail(RT_ERR_INVALID, "skin: vertex %u slot %u: bone index %u of %u bones", v, k, (uint32_t)s->bone[at + k], s->n_bones);
+  }
+  if (!c) return fail(RT_ERR_INVALID, "ctx/skin is null");
+  if (s->n_vertices != c->nVertices) return fail(RT_ERR_INVALID, "skin: %u vertices for a context of %u", s->n_vertices, c->nVertices);
+  int rc = update_checks(c, nullptr, 0);
+  if (rc != RT_OK) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  // the new skin replaces the old one only when all of it is resident
+  DevBuf<uint16_t> bone;
+  DevBuf<float> weight;
+  DevBuf<rt_mesh_transform> table;
+  const size_t n = RT_SKIN_INFLUENCES * (size_t)c->nVertices;
+  if ((rc = upload(&bone, s->bone, n)) != RT_OK || (rc = upload(&weight, s->weight, n)) != RT_OK) return rc;
+  HIP_TRY(dev_alloc(&table, s->n_bones));
+  c->skinBone = std::move(bone), c->skinWeight = std::move(weight), c->skinTable = std::move(table);
+  c->skinBones = s->n_bones;
+  return RT_OK;
+}
+
+int rt_update_skin(rt_ctx* c, const rt_skin_update* u, void* stream_, rt_update_report* rep) {
+  const auto t0 = std::chrono::steady_clock::now();
+  if (rep) memset(rep, 0, sizeof *rep);
+  // what the update says of itself comes before anything of the context
+  if (!u) return fail(RT_ERR_INVALID, "ctx/update is null");
+  if (!u->bones) return fail(RT_ERR_INVALID, "update: bones is null");
+  for (uint32_t r : u->reserved)
+    if (r) return fail(RT_ERR_INVALID, "update: reserved words must be zero");
+  for (uint32_t j = 0; j < u->n_bones; ++j) {
+    const rt_mesh_transform& t = u->bones[j];
+    if (t.flags) return fail(RT_ERR_INVALID, "update: bone %u: flags must be zero (0x%x)", j, t.flags);
+    if (!finite_record(t)) return fail(RT_ERR_INVALID, "update: bone %u: non-finite entry in its transform", j);
+  }
+  if (!u->lights && u->n_lights) return fail(RT_ERR_INVALID, "update: lights is null but n_lights is %u", u->n_lights);
+  if (!c) return fail(RT_ERR_INVALID, "ctx/update is null");
+  if (!c->skinBones) return fail(RT_ERR_STATE, "update: the context has no resident skin (rt_set_skin)");
+  if (u->n_bones != c->skinBones) return fail(RT_ERR_INVALID, "update: %u bones for a skin of %u bones", u->n_bones, c->skinBones);
+  int rc = update_checks(c, u->lights, u->n_lights);
+  if (rc != RT_OK) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if ((rc = prepare_rest_pose(c, stream)) != RT_OK) return rc;
+  HIP_TRY(hipMemcpyAsync(c->skinTable.get(), u->bones, c->skinBones * sizeof(rt_mesh_transform), hipMemcpyHostToDevice, stream));
+  HIP_TRY(rtk::launch_skin(c->restPos.get(), c->restNrm.get(), c->skinBone.get(), c->skinWeight.get(), c->skinTable.get(), c->nVertices,
+                           c->updPos.get(), c->updNrm.get(), c->triShade.get(), c->S.n_tris, c->dMag.get(), stream));
+  return update_from_rest(c, u->camera, u->lights, u->n_lights, u->d_prev_pos, stream, t0, rep);
 }
 
 int rt_group_update(rt_group* g, const rt_scene_update* u, rt_update_report* rep) {

@@ -324,6 +324,12 @@ hipError_t launch_magnitudes(const float* dPos, const float* dNrm, const uint4* 
 hipError_t launch_transform(const float* dRestPos, const float* dRestNrm, const rt_mesh_transform* dTable, const uint32_t* dMeshVtxBegin,
                             uint32_t nMeshes, uint32_t nVerts, float* dOutPos, float* dOutNrm, const uint4* dTriShade, uint32_t nTris,
                             uint32_t* dOut3, hipStream_t stream);
+// rt_update_skin: dOutPos / dOutNrm = the rest arrays blended under the bone records of dTable by the resident skin
+// (dBone [nVerts][4] indices into dTable, dWeight [nVerts][4], both 16-byte aligned; rt_amd.h's arithmetic, vertices of
+// four zero weights copied), and dOut3 as launch_transform's.  The out arrays must not alias the rest arrays.
+hipError_t launch_skin(const float* dRestPos, const float* dRestNrm, const uint16_t* dBone, const float* dWeight,
+                       const rt_mesh_transform* dTable, uint32_t nVerts, float* dOutPos, float* dOutNrm, const uint4* dTriShade,
+                       uint32_t nTris, uint32_t* dOut3, hipStream_t stream);
 hipError_t gpu_bvh_depths(const float4* nodesF, uint32_t n, uint8_t* dDepth, uint32_t* maxDepthOut, hipStream_t stream);
 hipError_t gpu_bvh_refit(const float* dVpos, const uint4* dTriShade, uint32_t nTris, bool records, float4* tris, float4* trisRef,
                          float4* nodesF, uint4* nodes16, uint32_t nNodes, const uint8_t* dDepth, uint32_t maxDepth, float pad,

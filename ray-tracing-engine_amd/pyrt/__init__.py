@@ -151,6 +151,21 @@ def make_transforms(n_meshes):
     return t
 
 
+SKIN_INFLUENCES = 4
+
+
+class Skin(C.Structure):
+    """rt_skin: [n_vertices][4] bone indices (uint16) and weights (float32) in host memory."""
+    _fields_ = [("n_vertices", C.c_uint32), ("n_bones", C.c_uint32), ("bone", C.POINTER(C.c_uint16)),
+                ("weight", C.POINTER(C.c_float)), ("reserved", C.c_uint32 * 6)]
+
+
+class SkinUpdate(C.Structure):
+    _fields_ = [("bones", C.POINTER(MeshTransform)), ("n_bones", C.c_uint32), ("n_lights", C.c_uint32),
+                ("camera", C.POINTER(Camera)), ("lights", C.POINTER(Light)), ("d_prev_pos", C.c_void_p),
+                ("reserved", C.c_uint32 * 6)]
+
+
 class Aov(C.Structure):
     """rt_aov: channel pointers (host or device), None = channel not wanted."""
     _fields_ = [("albedo", C.c_void_p), ("normal", C.c_void_p), ("position", C.c_void_p), ("depth", C.c_void_p),
@@ -399,7 +414,7 @@ AMD_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_create", "rt_destroy", "rt
                "rt_bvh_export", "rt_bvh_build_host", "rt_bvh_check_host", "rt_bvh_top_check_host", "rt_bvh_tune", "rt_profile_reset", "rt_profile_collect", "rt_test_unit",
                "rt_trace_stream_device", "rt_build_photon_map", "rt_get_photons", "rt_test_kd_order", "rt_owned_granules", "rt_pack_owned_device", "rt_unpack_owned_device", "rt_group_create", "rt_group_destroy",
                "rt_group_size", "rt_group_uses_rccl", "rt_group_ctx", "rt_group_set_photons", "rt_group_render",
-               "rt_update", "rt_update_vertices_device", "rt_update_transforms", "rt_group_update", "rt_render_aov", "rt_render_aov_device",
+               "rt_update", "rt_update_vertices_device", "rt_update_transforms", "rt_set_skin", "rt_update_skin", "rt_group_update", "rt_render_aov", "rt_render_aov_device",
                "rt_denoise", "rt_denoise_device", "rt_render_adaptive", "rt_render_adaptive_device", "rt_render_views",
                "rt_render_views_device", "rt_render_motion", "rt_render_motion_device", "rt_temporal_accumulate",
                "rt_temporal_accumulate_device", "rt_svgf", "rt_svgf_device", "rt_bvh_quality_get", "rt_rebuild",
@@ -536,6 +551,8 @@ def amd():
         L.rt_update.argtypes = [C.c_void_p, C.POINTER(SceneUpdate), C.POINTER(UpdateReport)]
         L.rt_update_vertices_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(UpdateReport)]
         L.rt_update_transforms.argtypes = [C.c_void_p, C.POINTER(TransformUpdate), C.c_void_p, C.POINTER(UpdateReport)]
+        L.rt_set_skin.argtypes = [C.c_void_p, C.POINTER(Skin)]
+        L.rt_update_skin.argtypes = [C.c_void_p, C.POINTER(SkinUpdate), C.c_void_p, C.POINTER(UpdateReport)]
         L.rt_group_update.argtypes = [C.c_void_p, C.POINTER(SceneUpdate), C.POINTER(UpdateReport)]
         L.rt_bvh_quality_get.argtypes = [C.c_void_p, C.POINTER(BvhQuality)]
         L.rt_rebuild.argtypes = [C.c_void_p, C.POINTER(RebuildParams), C.POINTER(RebuildReport)]
@@ -829,6 +846,36 @@ class Context:
         x.d_prev_pos = int(d_prev_pos) if d_prev_pos else None
         rep = UpdateReport()
         _check(amd().rt_update_transforms(self._h, C.byref(x), C.c_void_p(stream or None), C.byref(rep)))
+        return rep.as_dict()
+
+    def set_skin(self, bone, weight, n_bones):
+        """rt_set_skin: bone [n_vertices][4] indices below n_bones and weight [n_vertices][4] become the resident skin
+        (a zero weight = the slot is unused)."""
+        b = np.ascontiguousarray(bone, np.uint16)
+        w = np.ascontiguousarray(weight, np.float32)
+        if b.ndim != 2 or b.shape[1] != SKIN_INFLUENCES or w.shape != b.shape:
+            raise ValueError("bone and weight must both be [n_vertices][%d]" % SKIN_INFLUENCES)
+        s = Skin()
+        s.n_vertices, s.n_bones = len(b), int(n_bones)
+        s.bone, s.weight = C.cast(b.ctypes.data, C.POINTER(C.c_uint16)), C.cast(w.ctypes.data, C.POINTER(C.c_float))
+        _check(amd().rt_set_skin(self._h, C.byref(s)))
+
+    def clear_skin(self):
+        """rt_set_skin(ctx, NULL): the resident skin is released."""
+        _check(amd().rt_set_skin(self._h, None))
+
+    def update_skin(self, bones, camera=None, lights=None, d_prev_pos=None, stream=0):
+        """rt_update_skin: the rest pose blended under one record per bone of the resident skin (make_transforms' layout
+        with flags 0), computed on the device; camera / lights / d_prev_pos / stream as update_transforms'.  Returns the
+        report as a dict."""
+        t = np.ascontiguousarray(bones, TRANSFORM_DTYPE).reshape(-1)
+        u, _keep = _scene_update(None, None, camera, lights, None)
+        x = SkinUpdate()
+        x.bones = C.cast(t.ctypes.data, C.POINTER(MeshTransform))
+        x.n_bones, x.n_lights, x.camera, x.lights = len(t), u.n_lights, u.camera, u.lights
+        x.d_prev_pos = int(d_prev_pos) if d_prev_pos else None
+        rep = UpdateReport()
+        _check(amd().rt_update_skin(self._h, C.byref(x), C.c_void_p(stream or None), C.byref(rep)))
         return rep.as_dict()
 
     def bvh_quality(self):
