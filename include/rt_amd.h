@@ -44,6 +44,8 @@
  *                                  lights for the rays of one frame (+ _device form)
  *   rt_render_pick              <- (no counterpart) sampled direct lighting for scenes of many lights: m <= 3 lights per
  *                                  sample, picked by importance and weighted by 1 / (m p) (+ _device form)
+ *   rt_set_vertex_colors / rt_render_colors / rt_render_aov_colors <- (no counterpart) per-vertex albedo: the frame and
+ *                                  its first-hit AOVs with the colour interpolated at every shaded vertex (+ _device forms)
  *   rt_render_aov_views / rt_render_motion_views / rt_denoise_batch <- (no counterpart) the AOVs, motion vectors and
  *                                  denoised frames of those views, one launch each (+ _device forms)
  *   rt_trace                    <- RayTracer::rayTrace (RayTracer.h:27-53) test hook
@@ -64,10 +66,10 @@
  *   written in stream order, and the call returns without waiting for the stream:
  *     rt_render_device, rt_render_views_device, rt_render_rays_device, rt_render_shutter_device,
  *     rt_render_views_shutter_device (tests/test_gpu_views_shutter.py), rt_render_lights_device
- *     (tests/test_gpu_lights.py), rt_render_pick_device (tests/test_gpu_pick.py) and
- *     rt_render_lens_device with stats == NULL;
+ *     (tests/test_gpu_lights.py), rt_render_pick_device (tests/test_gpu_pick.py), rt_render_colors_device
+ *     (tests/test_gpu_vcol.py) and rt_render_lens_device with stats == NULL;
  *     rt_resolve_device;
- *     rt_render_aov_device, rt_render_ao_device, rt_render_motion_device; rt_temporal_accumulate_device,
+ *     rt_render_aov_device, rt_render_aov_colors_device, rt_render_ao_device, rt_render_motion_device; rt_temporal_accumulate_device,
  *     rt_svgf_device, rt_denoise_device, rt_denoise_batch_device; rt_render_aov_views_device,
  *     rt_render_motion_views_device; rt_pack_owned_device, rt_unpack_owned_device; rt_trace_stream_device.
  *     Host arguments (params, cameras, seeds, previous cameras, a pick's importance array) are copied before the call
@@ -79,7 +81,7 @@
  *     does the fifth rt_render_pick_device call for the table of the first.
  *   SYNCHRONISE `stream`, and only it, before they return, because the host reads a result back:
  *     rt_render_device, rt_render_views_device, rt_render_rays_device, rt_render_shutter_device,
- *     rt_render_views_shutter_device, rt_render_lights_device, rt_render_pick_device,
+ *     rt_render_views_shutter_device, rt_render_lights_device, rt_render_pick_device, rt_render_colors_device,
  *     rt_render_lens_device with stats != NULL;
  *     rt_render_adaptive_device and rt_render_adaptive_shutter_device (every pass); rt_update_vertices_device,
  *     rt_update_transforms and rt_update_skin (twice);
@@ -869,6 +871,54 @@ int rt_render_pick(rt_ctx* ctx, const rt_params* p, const rt_light_pick* pick, c
  * asynchronous; stats != NULL: synchronises `stream`, and only it). */
 int rt_render_pick_device(rt_ctx* ctx, const rt_params* p, const rt_light_pick* pick, void* d_accum, void* stream,
                           rt_stats* stats);
+
+/* ---- per-vertex albedo -------------------------------------------------------------------------------
+ * rt_material is indexed by mesh: every surface rt_render draws has one albedo per mesh.  rt_set_vertex_colors makes one
+ * colour per vertex resident — rgb [n_vertices][3] floats, indexed by the global vertex id as the normals are — and
+ * rt_render_colors renders rt_render's frame with ONE substitution at every shaded vertex: the material is the hit mesh's
+ * with albedo replaced, per component, by
+ *     c = (c0 + u * (c1 - c0)) + v * (c2 - c0)
+ * where c0, c1, c2 are the colours of the triangle's three vertices in the order of its index triple and u, v are the hit's
+ * barycentrics (the bits the normal is interpolated with).  Every difference, product and sum is rounded on its own to
+ * float32, nothing fused.  This form, not w c0 + u c1 + v c2, is the definition: three equal colours give c0 exactly.
+ * From c the vertex forms kdDiffuse = kd * (c / float(M_PI)), the two float32 operations rt_render applies to albedo; every
+ * other field is the mesh's material.  The RNG streams, the jitter, every ray, the hit selection, both ray counts, the
+ * per-sample clamp and the accumulation are rt_render's: colours never move a ray.
+ * Guarantees, bit for bit on accumulator, image, samples and both ray counts, for colours that are not -0:
+ *   - C1: if every vertex of every mesh carries its mesh's albedo, the frame is rt_render's.
+ *   - C2: if the three vertices of every triangle carry one colour, the frame is rt_render's on the scene in which every
+ *     triangle is a mesh of its own (in the same order), with that colour as albedo.
+ *   - C3: sample ranges chain.
+ *   - C4: reserved[0] (lanes per pixel), reserved[1] bit 0 (no pool), collect_stats, RT_ACCEL_BRUTE and the node format
+ *     change the schedule, never the bits.
+ * rt_set_vertex_colors copies rgb to the context's device (replacing the colours before); rgb == NULL releases them
+ * (n_vertices is then not read).  It changes nothing any other entry point reads; the colours stay across every update,
+ * refit and rt_rebuild (the vertex count of a context never changes) and go with rt_destroy.  It is a host form: it
+ * returns when the copy is done; the array it replaces is freed once the launches that read it have run.
+ *   RT_ERR_INVALID  a null rgb with a null ctx; a value that is not finite (rt_last_error names the first bad index); a
+ *   null ctx; n_vertices different from the context's.  No range is imposed, as none is on rt_material.albedo.
+ *   RT_ERR_STATE  a context that refuses launches (nothing is uploaded to it).
+ * rt_render_colors / rt_render_colors_device take rt_render's / rt_render_device's arguments.  Validation comes first and
+ * a rejected call writes nothing; what the arguments alone decide is answered before the device is asked for.
+ * RT_ERR_INVALID: a null ctx or p; host form: neither out_rgb nor accum_out, or out_rgb without background_rgb; device
+ * form: a null d_accum; every check rt_render applies to p.  RT_ERR_UNSUPPORTED: world > 1, use_photons, the wavefront
+ * integrator (reserved[2] bit 0), the legacy RNG.  Then the device (RT_ERR_NO_DEVICE); then the context: RT_ERR_STATE for
+ * one that refuses launches or has no resident colours.  The frame runs on the one-wave-per-workgroup kernel family of
+ * rt_render_lens (no persistent instances); RT_NODES_Q8 contexts walk their resident 32-byte records, as there.
+ * rt_render_aov_colors / rt_render_aov_colors_device are rt_render_aov / rt_render_aov_device with the albedo channel
+ * summing c at the first hit instead of the mesh's albedo (the guide rt_denoise and rt_svgf demodulate by); every other
+ * channel is rt_render_aov's bit for bit.  rt_render_aov's checks, then RT_ERR_STATE without resident colours.
+ * Out of scope: colours combined with the lens, the shutter, light groups, light picks, views, adaptive passes or
+ * rt_render_rays; rt_group; image textures (they need texture coordinates, which nothing here loads).                   */
+int rt_set_vertex_colors(rt_ctx* ctx, const float* rgb /* [n_vertices][3] HOST memory, NULL: release */, uint32_t n_vertices);
+/* out_rgb [h][w][3] or NULL, accum_out [h][w][4] or NULL, background_rgb [h][w][3]: as rt_render's */
+int rt_render_colors(rt_ctx* ctx, const rt_params* p, const float* background_rgb, float* out_rgb, float* accum_out,
+                     rt_stats* stats);
+/* Accumulate into caller-zeroed DEVICE d_accum [h][w][4] on `stream` (a hipStream_t, may be NULL), as rt_render_device
+ * does: sample ranges chain (stats == NULL: asynchronous; stats != NULL: synchronises `stream`, and only it). */
+int rt_render_colors_device(rt_ctx* ctx, const rt_params* p, void* d_accum, void* stream, rt_stats* stats);
+int rt_render_aov_colors(rt_ctx* ctx, const rt_params* p, const rt_aov* host_out);
+int rt_render_aov_colors_device(rt_ctx* ctx, const rt_params* p, const rt_aov* device_out, void* stream);
 
 /* ---- motion vectors and temporal accumulation (DESIGN.md "Motion vectors and temporal accumulation") ----------------
  * Two stateless calls for animated frames.  The library keeps nothing between frames: the caller hands in last frame's

@@ -32,7 +32,9 @@ RT_DEV ViewOfWave view_of_wave(const ViewRec* views, uint32_t tilesPerView) {
 // fields and is the kernel it was before they existed).  VIEWS = true: n_views x A.tilesPerView workgroups, view-major; the tile,
 // the camera and the seed are the wave's view's, the pixel index that feeds the RNG stream is local to the view, and every
 // channel is written into the view's slice (view_slice, in 64 bits).
-template <bool BRUTE, bool VIEWS>
+// VCOL (rt_render_aov_colors): the albedo channel sums the colour interpolated from A.vcol at the hit (vertex_color)
+// instead of the mesh's albedo; the other instances do not read A.vcol and are the kernels they were before it existed.
+template <bool BRUTE, bool VIEWS, bool VCOL = false>
 __global__ __launch_bounds__(64) void k_aov(DevScene S, AovArgs A) {
   __shared__ uint32_t lds[(rtbvh::kMaxDepth + 1) * 64];
   ViewOfWave vw;
@@ -57,9 +59,17 @@ __global__ __launch_bounds__(64) void k_aov(DevScene S, AovArgs A) {
     if (in && hit) {
       f3 nrm, pt;
       uint32_t mesh;
-      vertex_setup_ray(S, h.id, o, d, nrm, pt, mesh);
-      const rt_material& m = S.mats[mesh];
-      alb = alb + mk(m.albedo[0], m.albedo[1], m.albedo[2]);
+      if constexpr (VCOL) {
+        uint4 tv;
+        float u, v;
+        vertex_setup_ray(S, h.id, o, d, nrm, pt, tv, u, v);
+        mesh = tv.w;
+        alb = alb + vertex_color(A.vcol, tv, u, v);
+      } else {
+        vertex_setup_ray(S, h.id, o, d, nrm, pt, mesh);
+        const rt_material& m = S.mats[mesh];
+        alb = alb + mk(m.albedo[0], m.albedo[1], m.albedo[2]);
+      }
       nsum = nsum + nrm;
       psum = psum + pt;
       dsum += h.t;
@@ -83,6 +93,17 @@ hipError_t launch_aov(bool brute_force, const DevScene& S, const AovArgs& A, hip
   if (tiles == 0 || A.s1 <= A.s0) return hipSuccess;
   if (brute_force) hipLaunchKernelGGL((k_aov<true, false>), dim3(tiles), dim3(64), 0, stream, S, A);
   else hipLaunchKernelGGL((k_aov<false, false>), dim3(tiles), dim3(64), 0, stream, S, A);
+  return hipGetLastError();
+}
+
+hipError_t launch_aov_colors(bool brute_force, const DevScene& S, const AovArgs& A, const float* vcol, hipStream_t stream) {
+  const uint32_t tiles = ((A.width + 7u) / 8u) * ((A.height + 7u) / 8u);
+  if (!vcol) return hipErrorInvalidValue;
+  if (tiles == 0 || A.s1 <= A.s0) return hipSuccess;
+  AovArgs C = A;
+  C.vcol = vcol;
+  if (brute_force) hipLaunchKernelGGL((k_aov<true, false, true>), dim3(tiles), dim3(64), 0, stream, S, C);
+  else hipLaunchKernelGGL((k_aov<false, false, true>), dim3(tiles), dim3(64), 0, stream, S, C);
   return hipGetLastError();
 }
 

@@ -319,6 +319,9 @@ struct rt_ctx {
   DevBuf<float> skinWeight;
   DevBuf<rt_mesh_transform> skinTable;
   uint32_t skinBones = 0;
+  // rt_set_vertex_colors: the resident [nVertices][3] colours that rt_render_colors and rt_render_aov_colors interpolate
+  // (null: none); nothing else reads them, and no update touches them
+  DevBuf<float> vcol;
   // scratch of rt_denoise_device and rt_svgf_device (rtk::filter_scratch; grows on demand: ensure_filter_scratch)
   DevBuf<float4> dnScratch;
   size_t dnCap = 0;
@@ -2666,27 +2669,28 @@ rtk::AovArgs aov_args(const rt_params& q, const rt_aov& out) {
   return A;
 }
 
-}  // namespace
-
-extern "C" {
-
-int rt_render_aov_device(rt_ctx* c, const rt_params* p, const rt_aov* out, void* stream) {
+// rt_render_aov_device, or (colors) rt_render_aov_colors_device: the albedo channel from the resident vertex colours
+int aov_device(rt_ctx* c, const rt_params* p, const rt_aov* out, void* stream, bool colors) {
   rt_params q;
   int rc = aov_checks(c, p, &q);
   if (rc != RT_OK) return rc;
   if (!out) return fail(RT_ERR_INVALID, "aov is null");
+  if (colors && !c->vcol) return fail(RT_ERR_STATE, "the context has no resident vertex colours (rt_set_vertex_colors)");
   HIP_TRY(hipSetDevice(c->device));
   const rtk::AovArgs A = aov_args(q, *out);
-  const hipError_t he = rtk::launch_aov(q.accel == RT_ACCEL_BRUTE, c->S, A, static_cast<hipStream_t>(stream));
+  const hipError_t he = colors ? rtk::launch_aov_colors(q.accel == RT_ACCEL_BRUTE, c->S, A, c->vcol.get(), static_cast<hipStream_t>(stream))
+                               : rtk::launch_aov(q.accel == RT_ACCEL_BRUTE, c->S, A, static_cast<hipStream_t>(stream));
   if (he != hipSuccess) return fail(RT_ERR_HIP, "AOV launch failed: %s", hipGetErrorString(he));
   return RT_OK;
 }
 
-int rt_render_aov(rt_ctx* c, const rt_params* p, const rt_aov* out) {
+// the host form of either
+int aov_host(rt_ctx* c, const rt_params* p, const rt_aov* out, bool colors) {
   rt_params q;
   int rc = aov_checks(c, p, &q);
   if (rc != RT_OK) return rc;
   if (!out) return fail(RT_ERR_INVALID, "aov is null");
+  if (colors && !c->vcol) return fail(RT_ERR_STATE, "the context has no resident vertex colours (rt_set_vertex_colors)");
   HIP_TRY(hipSetDevice(c->device));
   const size_t npx = (size_t)q.width * q.height;
   Staging st;
@@ -2694,9 +2698,18 @@ int rt_render_aov(rt_ctx* c, const rt_params* p, const rt_aov* out) {
   d.albedo = st.out(out->albedo, 3 * npx), d.normal = st.out(out->normal, 3 * npx), d.position = st.out(out->position, 3 * npx);
   d.depth = st.out(out->depth, npx), d.hits = st.out(out->hits, npx), d.mesh = st.out(out->mesh, npx), d.tri = st.out(out->tri, npx);
   if (st.rc != RT_OK) return st.rc;
-  if ((rc = rt_render_aov_device(c, &q, &d, nullptr)) != RT_OK) return rc;
+  if ((rc = aov_device(c, &q, &d, nullptr, colors)) != RT_OK) return rc;
   return st.download();
 }
+
+}  // namespace
+
+extern "C" {
+
+int rt_render_aov_device(rt_ctx* c, const rt_params* p, const rt_aov* out, void* stream) { return aov_device(c, p, out, stream, false); }
+int rt_render_aov(rt_ctx* c, const rt_params* p, const rt_aov* out) { return aov_host(c, p, out, false); }
+int rt_render_aov_colors_device(rt_ctx* c, const rt_params* p, const rt_aov* out, void* stream) { return aov_device(c, p, out, stream, true); }
+int rt_render_aov_colors(rt_ctx* c, const rt_params* p, const rt_aov* out) { return aov_host(c, p, out, true); }
 
 int rt_denoise_device(rt_ctx* c, const rt_denoise_params* d, const void* d_rgb, const rt_aov* aov, void* d_out, void* stream) {
   int rc = denoise_checks(c, d, d_rgb, aov, d_out);
@@ -3888,6 +3901,70 @@ int rt_render_pick(rt_ctx* c, const rt_params* p, const rt_light_pick* k, const 
   if (rc != RT_OK) return rc;
   rtk::PickRec R;
   if ((rc = stage_pick(c, k, T, nullptr, &R)) != RT_OK) return rc;
+  return frame_host(c, p, R, 1, bg, out_rgb, accum_out, stats);
+}
+
+}  // extern "C"
+
+// ---- per-vertex albedo ---------------------------------------------------------------------------------
+namespace {
+
+// Everything both forms of rt_render_colors check, in the header's order (lens_checks' shape: the arguments alone first,
+// then the device, the context last), and the record the kernels take.
+int colors_checks(const rt_ctx* c, const rt_params* p, const char* outputs, rtk::VColRec* R) {
+  if (!c || !p) return fail(RT_ERR_INVALID, "ctx/params is null");
+  if (outputs) return fail(RT_ERR_INVALID, "%s", outputs);
+  int rc = check_params_shape(p);
+  if (rc != RT_OK) return rc;
+  if (p->world > 1) return fail(RT_ERR_UNSUPPORTED, "tile-sharded coloured frames (world %u) are not supported", p->world);
+  if (p->use_photons) return fail(RT_ERR_UNSUPPORTED, "coloured frames do not shade from the photon map");
+  if (p->reserved[2] & 1u) return fail(RT_ERR_UNSUPPORTED, "coloured frames do not run the wavefront integrator");
+  if ((rc = check_device_present()) != RT_OK) return rc;
+  if ((rc = check_not_broken(c)) != RT_OK) return rc;
+  if (!c->vcol) return fail(RT_ERR_STATE, "the context has no resident vertex colours (rt_set_vertex_colors)");
+  R->vcol = c->vcol.get();
+  return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_set_vertex_colors(rt_ctx* c, const float* rgb, uint32_t n_vertices) {
+  if (!rgb) {
+    if (!c) return fail(RT_ERR_INVALID, "ctx/rgb is null");
+    HIP_TRY(hipSetDevice(c->device));
+    c->vcol.reset();
+    return RT_OK;
+  }
+  // what the array says of itself comes before anything of the context
+  for (size_t j = 0; j < 3 * (size_t)n_vertices; ++j)
+    if (!std::isfinite(rgb[j]))
+      return fail(RT_ERR_INVALID, "vertex colours: rgb[%zu] (vertex %zu, component %zu) is not finite", j, j / 3, j % 3);
+  if (!c) return fail(RT_ERR_INVALID, "ctx/rgb is null");
+  if (n_vertices != c->nVertices) return fail(RT_ERR_INVALID, "vertex colours: %u vertices for a context of %u", n_vertices, c->nVertices);
+  int rc = check_not_broken(c);  // (as rt_set_skin: nothing is uploaded to a context that refuses launches)
+  if (rc != RT_OK) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  // the new colours replace the old ones only when all of them are resident; the old array is then freed under launches
+  // that may still read it, which hipFree waits for
+  DevBuf<float> fresh;
+  if ((rc = upload(&fresh, rgb, 3 * (size_t)n_vertices)) != RT_OK) return rc;
+  c->vcol = std::move(fresh);
+  return RT_OK;
+}
+
+int rt_render_colors_device(rt_ctx* c, const rt_params* p, void* d_accum, void* stream, rt_stats* stats) {
+  rtk::VColRec R;
+  const int rc = colors_checks(c, p, d_accum ? nullptr : "d_accum is null", &R);
+  if (rc != RT_OK) return rc;
+  return frame_device(c, p, R, d_accum, stream, stats);
+}
+
+int rt_render_colors(rt_ctx* c, const rt_params* p, const float* bg, float* out_rgb, float* accum_out, rt_stats* stats) {
+  rtk::VColRec R;
+  const int rc = colors_checks(c, p, outputs_refused(bg, out_rgb, accum_out), &R);
+  if (rc != RT_OK) return rc;
   return frame_host(c, p, R, 1, bg, out_rgb, accum_out, stats);
 }
 

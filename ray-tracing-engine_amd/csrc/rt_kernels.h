@@ -138,8 +138,13 @@ struct AovArgs {
   // multi-view launches only (launch_aov_views sets them; the single-view instances do not read them)
   const ViewRec* views = nullptr;
   uint32_t tilesPerView = 0;
+  // coloured launches only (launch_aov_colors sets it; the other instances do not read it)
+  const float* vcol = nullptr;
 };
 hipError_t launch_aov(bool brute_force, const DevScene& S, const AovArgs& A, hipStream_t stream);
+// the same with the albedo channel summing the colour interpolated from vcol [n_vertices][3] at the first hit
+// (rt_render_aov_colors) instead of the mesh's albedo; instances of their own
+hipError_t launch_aov_colors(bool brute_force, const DevScene& S, const AovArgs& A, const float* vcol, hipStream_t stream);
 // ambient occlusion and bent normals at the first hit (ao_kernels.h, rt_render_ao): per pixel, over the samples [s0, s1),
 // the occlusion rays that escaped, the hit samples, and the float32 sum of the escaped directions; null channels are not written
 struct AoArgs {
@@ -200,30 +205,38 @@ struct PickRec {
   const float* thresholds;  // [n] t_k = (float)C_k, 1.0f from the last light with q_k > 0 onwards: pick(u) = the smallest k with u < t_k
   const PickLight* lights;  // [n]
 };
+// the frame with per-vertex albedo (rt_render_colors): every shaded vertex takes its material's albedo from the colours of
+// the hit triangle's three vertices (rt_amd.h's interpolation); the array is device memory the launch reads in stream
+// order, gathered per lane by vertex id as the normals are.
+struct VColRec {
+  const float* vcol;  // [n_vertices][3]
+};
 // Which variant a frame is, with its record (which the caller keeps alive over the launch call).  VIEWS_SHUTTER, many
 // views each under its own open shutter (rt_render_views_shutter), has none: tile t renders with views[tileView[t]]'s
 // camera, seed and slice under viewShutters[tileView[t]], from RenderArgs' three tables.
 struct FrameVariant {
-  enum Kind { NONE, LENS, SHUTTER, LIGHTS, VIEWS_SHUTTER, PICK };
+  enum Kind { NONE, LENS, SHUTTER, LIGHTS, VIEWS_SHUTTER, PICK, VCOL };
   Kind kind = NONE;
-  const void* rec = nullptr;  // the LensRec, ShutterRec, LightGroupsRec or PickRec of kind, else null
+  const void* rec = nullptr;  // the LensRec, ShutterRec, LightGroupsRec, PickRec or VColRec of kind, else null
   FrameVariant() = default;
   explicit FrameVariant(Kind k) : kind(k) {}
   FrameVariant(const LensRec& r) : kind(LENS), rec(&r) {}
   FrameVariant(const ShutterRec& r) : kind(SHUTTER), rec(&r) {}
   FrameVariant(const LightGroupsRec& r) : kind(LIGHTS), rec(&r) {}
   FrameVariant(const PickRec& r) : kind(PICK), rec(&r) {}
+  FrameVariant(const VColRec& r) : kind(VCOL), rec(&r) {}
   explicit operator bool() const { return kind != NONE; }
   // the variant in an error message: "<name> render launch failed"
   const char* name() const {
-    static const char* const names[] = {"", "lens", "shutter", "light-group", "multi-view shutter", "light-pick"};
+    static const char* const names[] = {"", "lens", "shutter", "light-group", "multi-view shutter", "light-pick", "vertex-colour"};
     return names[kind];
   }
 };
 // launch_render's one-wave-per-workgroup family (brute, sequential, pooled; counted or timed) for a variant (F.kind not
 // NONE); A as launch_render takes it: tileView null, but for VIEWS_SHUTTER a multi-view frame's with the three tables
 // set.  LIGHTS: accum is [G.n][height][width], slice g at accum + g * width * height.  PICK: pooled whenever A.flags bit 0
-// is set, whatever the scene's light count (a vertex sends m <= POOL_L shadow rays).  hipErrorInvalidValue where A, the
+// is set, whatever the scene's light count (a vertex sends m <= POOL_L shadow rays).  VCOL: a launch allocates
+// VP_VCOL_WORDS more words of LDS per wave (the vertex's parked kdDiffuse).  hipErrorInvalidValue where A, the
 // record or the scene's light count do not fit the variant.
 hipError_t launch_render_variant(const FrameVariant& F, bool brute_force, bool stats, const DevScene& S, const RenderArgs& A,
                                  float4* accum, unsigned long long* counters, hipStream_t stream);

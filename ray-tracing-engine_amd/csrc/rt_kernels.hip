@@ -233,6 +233,10 @@ constexpr int LT_LIGHTS = 4096;
 // indices from a stream of its own before the primary cast; the vertex pool and shade_direct_seq then run over those m
 // slots of the record's scaled lights instead of the scene's list (their PICK switch).
 constexpr int LT_PICK = 8192;
+// A frame with per-vertex albedo (rt_render_colors): render_tile takes a VColRec and forms every vertex's kdDiffuse from
+// the colours of the hit triangle's three vertices; the vertex pool and shade_direct_seq shade with it in place of the
+// mesh's (their VC switch).
+constexpr int LT_VCOL = 16384;
 constexpr uint32_t kPrioMaxNodes = 65536;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(3))) u32x4* lds_u4_ptr;
@@ -803,17 +807,51 @@ RT_DEV void vertex_setup(const DevScene& S, const HitRec& h, f3& hitNormal, f3& 
 // walker's record holds — p0 and the float edge differences bvh_build.cpp stores —
 // so they are the bits the walker had; the vertex loads are the ones the
 // interpolation needs anyway.
+// (tv, u, v: the triangle's record and the barycentrics, for the callers that interpolate more than the normal)
 template <bool FAST = false>
-RT_DEV void vertex_setup_ray(const DevScene& S, uint32_t id, f3 o, f3 d, f3& hitNormal, f3& point, uint32_t& mesh) {
-  const uint4 tv = S.triShade[id];
+RT_DEV void vertex_setup_ray(const DevScene& S, uint32_t id, f3 o, f3 d, f3& hitNormal, f3& point, uint4& tv, float& u, float& v) {
+  tv = S.triShade[id];
   const f3 p0 = ld(S.vpos + 3 * (size_t)tv.x), p1 = ld(S.vpos + 3 * (size_t)tv.y), p2 = ld(S.vpos + 3 * (size_t)tv.z);
-  float u, v, t;
+  float t;
   tri_test(o, d, p0, p1 - p0, p2 - p0, u, v, t, true);  // (once per vertex: the division; the same bits as the walker's)
   const float w = 1.f - u - v;
   hitNormal = unit3<FAST>(interp3(S.vnrm, tv, w, u, v));
   point = w * p0 + u * p1 + v * p2;
+}
+template <bool FAST = false>
+RT_DEV void vertex_setup_ray(const DevScene& S, uint32_t id, f3 o, f3 d, f3& hitNormal, f3& point, uint32_t& mesh) {
+  uint4 tv;
+  float u, v;
+  vertex_setup_ray<FAST>(S, id, o, d, hitNormal, point, tv, u, v);
   mesh = tv.w;
 }
+
+// Per-vertex albedo (rt_render_colors, rt_amd.h): the colour of the hit from the three vertices' colours,
+// c = (c0 + u (c1 - c0)) + v (c2 - c0) per component, every operation rounded on its own — three equal colours give c0
+// exactly — gathered per lane by vertex id as the normals are ...
+RT_DEV f3 vertex_color(const float* vcol, uint4 tv, float u, float v) {
+  const f3 c0 = ld(vcol + 3 * (size_t)tv.x), c1 = ld(vcol + 3 * (size_t)tv.y), c2 = ld(vcol + 3 * (size_t)tv.z);
+  return (c0 + u * (c1 - c0)) + v * (c2 - c0);
+}
+// ... and the kdDiffuse the vertex shades with: make_dev_mat's two operations on c in place of the mesh's albedo
+RT_DEV f3 vertex_kd(const DevScene& S, const float* vcol, uint4 tv, float u, float v) {
+  const f3 diffuse = vertex_color(vcol, tv, u, v) / 3.14159274f;  // c / float(M_PI)
+  return S.mats[tv.w].kd * diffuse;
+}
+// What a vertex of a coloured frame shades with in place of its mesh's kdDiffuse, and the three rows of LDS (the wave's:
+// [3][64] floats behind its stack rows and pool, allocated for these instances alone) where it is parked while the wave
+// traverses: held in registers, it would cost the timed instances, which sit at their budget, three more of them.
+// NoVCol: every other frame — an empty argument, so that the instances without colours keep the signatures (and the
+// code) they had.
+struct NoVCol {};
+struct VColKd {
+  f3 kd;
+  float* park;
+};
+RT_DEV void park_kd(const VColKd& vc, uint32_t lane) { vc.park[lane] = vc.kd.x, vc.park[64 + lane] = vc.kd.y, vc.park[128 + lane] = vc.kd.z; }
+RT_DEV f3 parked_kd(const VColKd& vc, uint32_t lane) { return mk(vc.park[lane], vc.park[64 + lane], vc.park[128 + lane]); }
+template <class VC>
+constexpr bool is_vcol = std::is_same_v<VC, VColKd>;
 
 // Renderer.cpp:63-104: photon-map radiance estimate at the vertex (HP: the heap's layout, WideHeap for k > 16)
 template <bool STATS, class HP = Heap>
@@ -903,10 +941,13 @@ RT_DEV uint32_t loop_lights(const DevScene&, const PickArgs& a) { return a.R->m;
 // with more than POOL_L lights).  Called by lanes that own a vertex only.
 // GROUPS (rt_render_lights): the terms go into *gc by group instead of into the returned colour, which stays 0.
 // PK = PickArgs (rt_render_pick): the light list is the sample's picked lights, in slot order, instead of the scene's.
-template <bool BRUTE, bool STATS, bool GROUPS = false, class PK = NoPick>
+// VC = VColKd (rt_render_colors): the vertex's own kdDiffuse in place of the mesh's, parked in LDS over every walk.
+template <bool BRUTE, bool STATS, bool GROUPS = false, class PK = NoPick, class VC = NoVCol>
 RT_DEV f3 shade_direct_seq(const DevScene& S, Rng& g, f3 rayDir, const HitRec& h, uint32_t* stack, f3 hitNormal,
-                           f3 point, LaneStats& st, const LightGroupsRec* G = nullptr, GroupCols* gc = nullptr, PK pk = PK()) {
-  const BsdfBase base = bsdf_base(S.matsDev[h.mesh], hitNormal, -rayDir);  // the light-independent half, once
+                           f3 point, LaneStats& st, const LightGroupsRec* G = nullptr, GroupCols* gc = nullptr, PK pk = PK(),
+                           VC vc = VC()) {
+  BsdfBase base = bsdf_base(S.matsDev[h.mesh], hitNormal, -rayDir);  // the light-independent half, once
+  if constexpr (is_vcol<VC>) park_kd(vc, threadIdx.x & 63u);
   f3 color = mk(0.f, 0.f, 0.f);
   if constexpr (GROUPS) group_cols_zero(*gc);
   for (uint32_t li = 0; li < loop_lights(S, pk); li++) {
@@ -915,6 +956,10 @@ RT_DEV f3 shade_direct_seq(const DevScene& S, Rng& g, f3 rayDir, const HitRec& h
     HitRec tmp;
     st.shadow++;
     if (cast<BRUTE, true, STATS>(S, true, point, toLight, stack, tmp, st)) continue;
+    if constexpr (is_vcol<VC>) {
+      asm volatile("" ::: "memory");  // (read back behind the walk, not held over it)
+      base.kdDiffuse = parked_kd(vc, threadIdx.x & 63u);
+    }
     const f3 bsdf = bsdf_apply(base, toLight);
     f3 radiance;
     if constexpr (is_pick<PK>) {
@@ -945,6 +990,8 @@ constexpr int VP_PT = 0, VP_DIR = 192, VP_BDIR = VP_DIR + 192 * POOL_L, VP_KEY =
               VP_RES = VP_LIST + 32;
 constexpr int VP_WORDS = VP_RES + 2 * POOL_L + 2;
 constexpr int VP_COMPACT_SAVES = 64 * POOL_L;  // words a compact pool is shorter by
+// (rt_render_colors) three rows more per wave: the vertex's kdDiffuse while the wave traverses (VColKd::park)
+constexpr int VP_VCOL_WORDS = 192;
 // offsets of everything behind the per-light block, by layout
 template <int CP> struct VpLayout {  // CP = 0: full, 1: light parameters, 2: ... and no bounce directions, 3: keys, list and result bits only
   static constexpr int PER_LIGHT = CP ? 128 : 192;
@@ -969,16 +1016,20 @@ static_assert(VP_WORDS == (int)rtbvh::kWavePoolWords && BLOCK == (int)rtbvh::kSt
 // PK = PickArgs (rt_render_pick): the pool's lights are the lane's picked ones, in slot order: the fill loop samples
 // them and the colour loop evaluates them, each lane fetching its own from the record's table.  The workers read the full
 // layout's toLight directions only, so the rounds, the hand-out, the stealing and the result bits are the same code.
-template <bool STATS, int LT, bool BOUNCE, bool GROUPS = false, class PK = NoPick>
+// VC = VColKd (rt_render_colors): the vertex's own kdDiffuse in place of the mesh's.  It is parked in three rows of LDS
+// behind the pool's words (the launcher allocates them for these instances alone) as the point is in the pool, and read
+// back behind the rounds as the point is: nothing more of the vertex is live while the wave traverses.
+template <bool STATS, int LT, bool BOUNCE, bool GROUPS = false, class PK = NoPick, class VC = NoVCol>
 RT_DEV f3 vertex_pool(const DevScene& S, bool alive, bool bounceRay, Rng& g, f3 rayDir, uint32_t mesh, f3 hitNormal,
                       f3& point, f3& bdir, uint32_t* stack, uint32_t* pool, HitRec& next, bool& nextFound, LaneStats& st,
-                      const LightGroupsRec* G = nullptr, GroupCols* gc = nullptr, PK pk = PK()) {
+                      const LightGroupsRec* G = nullptr, GroupCols* gc = nullptr, PK pk = PK(), VC vc = VC()) {
   const bool bounce = BOUNCE && bounceRay;
   if constexpr (GROUPS) group_cols_zero(*gc);
   constexpr bool FR = (LT & LT_FASTDET) != 0;  // 1 / length by rtd::recip_fast (see rtd::unit3)
   const uint32_t lane = threadIdx.x & 63u, nl = loop_lights(S, pk);
   constexpr bool CP3 = (LT & LT_COMPACT3) != 0, CP2 = CP3 || (LT & LT_COMPACT2) != 0, CP = CP2 || (LT & LT_COMPACT) != 0;
   static_assert(!is_pick<PK> || !CP, "the picked frames' instances use the full pool layout: workers read directions, never a light");
+  static_assert(!is_vcol<VC> || !CP, "the coloured frames' instances use the full pool layout, with the parked rows behind it");
   using VP = VpLayout<CP3 ? 3 : CP2 ? 2 : CP ? 1 : 0>;
   float* fp = reinterpret_cast<float*>(pool);
   // 32 words: rank -> pixel lane (64 bytes) while rays are handed out; then rank -> victim
@@ -997,6 +1048,7 @@ RT_DEV f3 vertex_pool(const DevScene& S, bool alive, bool bounceRay, Rng& g, f3 
   PHC(PH_N_POOLS);
   if (alive) {
     if (!CP3) fp[VP_PT + lane] = point.x, fp[VP_PT + 64 + lane] = point.y, fp[VP_PT + 128 + lane] = point.z;
+    if constexpr (is_vcol<VC>) park_kd(vc, lane);
     // draw order of the reference: the light samples in light order (Renderer.cpp:52),
     // then the hemisphere sample (Renderer.cpp:164)
     if (CP3) gsave = g.s;  // (the light samples are re-drawn from here wherever they are needed)
@@ -1195,7 +1247,8 @@ RT_DEV f3 vertex_pool(const DevScene& S, bool alive, bool bounceRay, Rng& g, f3 
   point = pt;
   if (bounce && !CP2) bdir = mk(fp[VP::BDIR + lane], fp[VP::BDIR + 64 + lane], fp[VP::BDIR + 128 + lane]);
   if (alive) {
-    const BsdfBase base = bsdf_base<FR>(S.matsDev[mesh], hitNormal, -rayDir);  // the light-independent half, once
+    BsdfBase base = bsdf_base<FR>(S.matsDev[mesh], hitNormal, -rayDir);  // the light-independent half, once
+    if constexpr (is_vcol<VC>) base.kdDiffuse = parked_kd(vc, lane);
     Rng relight{gsave};
     for (uint32_t l = 0; l < nl; l++) {
       float rh3 = 0.f, rv3 = 0.f;
@@ -1401,13 +1454,15 @@ RT_DEV void group_samples_add(const RenderArgs& A, const LightGroupsRec& G, floa
 
 // The record a frame variant's instances take as a kernel argument of their own, by its LT_* bits: the lens, the shutter
 // of a single-view frame (a multi-view one reads its records from RenderArgs' tables), the light groups, the light
-// picks — or none.
+// picks, the vertex colours — or none.  park: (LT_VCOL) the wave's three parked rows of LDS (VColKd), from the kernel
+// that lays its LDS out.
 struct NoRec {};
 template <int LTV>
 using frame_rec_t = std::conditional_t<(LTV & LT_LENS) != 0, LensRec,
                     std::conditional_t<(LTV & LT_LIGHTS) != 0, LightGroupsRec,
                     std::conditional_t<(LTV & LT_PICK) != 0, PickRec,
-                    std::conditional_t<(LTV & LT_SHUTTER) != 0 && (LTV & LT_VIEWS) == 0, ShutterRec, NoRec>>>>;
+                    std::conditional_t<(LTV & LT_VCOL) != 0, VColRec,
+                    std::conditional_t<(LTV & LT_SHUTTER) != 0 && (LTV & LT_VIEWS) == 0, ShutterRec, NoRec>>>>>;
 // (what the instances without a record leave out; the others do not compile without theirs)
 template <int LTV>
 constexpr const frame_rec_t<LTV>* no_record() {
@@ -1417,13 +1472,16 @@ constexpr const frame_rec_t<LTV>* no_record() {
 
 template <bool BRUTE, bool PHOTON, bool POOLED, bool STATS, int LTV, class HP = Heap>
 RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restrict__ accum, const Lds& L, uint32_t* pool,
-                        float* ex, uint32_t wave, LaneStats& st, const frame_rec_t<LTV>* rec = no_record<LTV>()) {
-  constexpr int LT = LTV & ~(LT_VIEWS | LT_LENS | LT_SHUTTER | LT_LIGHTS | LT_PICK);
+                        float* ex, uint32_t wave, LaneStats& st, const frame_rec_t<LTV>* rec = no_record<LTV>(),
+                        float* park = nullptr) {
+  constexpr int LT = LTV & ~(LT_VIEWS | LT_LENS | LT_SHUTTER | LT_LIGHTS | LT_PICK | LT_VCOL);
   constexpr bool VIEWS = (LTV & LT_VIEWS) != 0;
   constexpr bool LENS = (LTV & LT_LENS) != 0;
   constexpr bool SHUTTER = (LTV & LT_SHUTTER) != 0;
   constexpr bool LIGHTS = (LTV & LT_LIGHTS) != 0;
   constexpr bool PICK = (LTV & LT_PICK) != 0;
+  constexpr bool VCOL = (LTV & LT_VCOL) != 0;
+  static_assert(!VCOL || (!VIEWS && !LENS && !SHUTTER && !LIGHTS && !PICK && !PHOTON), "vertex colours go with the plain frame only");
   static_assert(!LIGHTS || (!VIEWS && !LENS && !SHUTTER && !PHOTON), "light groups go with the plain frame only");
   static_assert(!PICK || (!VIEWS && !LENS && !SHUTTER && !LIGHTS && !PHOTON), "light picks go with the plain frame only");
   static_assert(!LENS || !VIEWS, "no multi-view lens frames");
@@ -1501,9 +1559,18 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
         const bool bounce = A.mode == RT_MODE_PATH && depth + 1 < nvert;  // wave-uniform
         f3 nrm = mk(0.f, 0.f, 0.f), pt = nrm, bdir = nrm;
         uint32_t mesh = 0;
+        VColKd vk{nrm, park};  // (LT_VCOL) the vertex's kdDiffuse
         // (the vertex set-up is three dependent loads deep: it goes out ahead of other waves'
         // arithmetic, like the pool loop that follows; +0.4 % on C2)
         if (!(LT & LT_NOPRIO)) __builtin_amdgcn_s_setprio(1);
+        if constexpr (VCOL) {
+          if (alive) {
+            uint4 tv;
+            float u, v;
+            vertex_setup_ray<FR>(S, h.id, o, d, nrm, pt, tv, u, v);
+            mesh = tv.w, vk.kd = vertex_kd(S, rec->vcol, tv, u, v);
+          }
+        } else
         if (alive) vertex_setup_ray<FR>(S, h.id, o, d, nrm, pt, mesh);
         // (Renderer.cpp:164: the hemisphere sample is drawn after every shaded vertex;
         // after the LAST one the reference draws it too but never traces it, and the
@@ -1524,6 +1591,9 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
         } else if constexpr (PICK) {
           static_assert(!SHADOW_BODY, "the light-pick instances keep their trees in HBM / L2");
           c = vertex_pool<STATS, LT, true, false, PickArgs>(S, alive, bounce, g, d, mesh, nrm, pt, bdir, L.stack, pool, nh, nfound, st, nullptr, nullptr, PickArgs{rec, pk});
+        } else if constexpr (VCOL) {
+          static_assert(!SHADOW_BODY, "the coloured instances keep their trees in HBM / L2");
+          c = vertex_pool<STATS, LT, true, false, NoPick, VColKd>(S, alive, bounce, g, d, mesh, nrm, pt, bdir, L.stack, pool, nh, nfound, st, nullptr, nullptr, NoPick(), vk);
         } else
         c = SHADOW_BODY && !bounce
                          ? vertex_pool<STATS, LT, false>(S, alive, false, g, d, mesh, nrm, pt, bdir, L.stack, pool, nh, nfound, st)
@@ -1559,6 +1629,10 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
         if (alive) c = shade_direct_seq<BRUTE, STATS, true>(S, g, d, h, L.stack, nrm, pt, st, rec, &gv);
       } else if constexpr (PICK) {
         if (alive) c = shade_direct_seq<BRUTE, STATS, false, PickArgs>(S, g, d, h, L.stack, nrm, pt, st, nullptr, nullptr, PickArgs{rec, pk});
+      } else if constexpr (VCOL) {
+        if (alive)
+          c = shade_direct_seq<BRUTE, STATS, false, NoPick, VColKd>(S, g, d, h, L.stack, nrm, pt, st, nullptr, nullptr, NoPick(),
+                                                                    VColKd{vertex_kd(S, rec->vcol, S.triShade[h.id], h.u, h.v), park});
       } else {
         if (alive) c = shade_direct_seq<BRUTE, STATS>(S, g, d, h, L.stack, nrm, pt, st);
       }
@@ -1819,7 +1893,7 @@ __global__ __launch_bounds__(1024, 8) void k_trace_stream(DevScene S, const floa
 #include "rays_kernels.h"
 
 // ---------------------------------------------------------------- the frame's generator variants (rt_render_lens,
-// rt_render_shutter, rt_render_views_shutter, rt_render_lights, rt_render_pick)
+// rt_render_shutter, rt_render_views_shutter, rt_render_lights, rt_render_pick, rt_render_colors)
 #include "frame_variants.h"
 
 // ---------------------------------------------------------------- frame assembly (multi-GPU)

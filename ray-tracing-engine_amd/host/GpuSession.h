@@ -89,6 +89,7 @@ struct GpuSettings {
   float shutterMove[3] = {0.f, 0.f, 0.f};  // ... while the camera translates by this vector; -aperture / -focus put the lens on it
   bool lightsEach = false;            // also one frame per light (rt_render_lights: Renderer::lightGroups(); single device, plain frames only) ...
   std::vector<unsigned> lightMasks;   // ... or one per mask of lights (bit l: light l is lit); at most RT_LIGHT_GROUPS_MAX groups
+  bool vcolors = false;               // shade with the meshes' per-vertex colours where any mesh has them (rt_render_colors; single device, plain frames only)
   unsigned lightPick = 0;             // > 0: the frame with this many sampled lights per path vertex (rt_render_pick; single device, plain frames only)
   std::vector<int> devices;  // more than one entry: Renderer::render tile-shards the frame over them (rt_group)
   static GpuSettings& get() {

@@ -142,6 +142,15 @@ int main(int argc, char** argv) {
     }
     GpuSettings::get().lightPick = static_cast<unsigned>(args.lightPick());
   }
+  if (args.vcolors() != 0) {
+    // -vcolors 1: the frame with the per-vertex colours of the scene's COFF meshes, and nothing else
+    if (GpuSettings::get().devices.size() > 1 || args.numPhotons() > 0 || args.adaptive() >= 0. || !args.shutter().empty() ||
+        args.aperture() > 0. || !args.lights().empty() || args.lightPick() != 0) {
+      std::cerr << "error: -vcolors runs on one GPU, without -p, -adaptive, -shutter, -aperture, -lights and -lightpick" << std::endl;
+      return 1;
+    }
+    GpuSettings::get().vcolors = true;
+  }
   if (args.adaptive() >= 0.) {
     if (GpuSettings::get().devices.size() > 1) {
       std::cerr << "error: -adaptive runs on one GPU only (not with -gpus > 1)" << std::endl;

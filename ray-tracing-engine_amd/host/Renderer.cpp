@@ -10,6 +10,13 @@
 #include <string>
 #include <vector>
 
+// does any mesh carry per-vertex colours (a COFF file)?
+inline bool sceneHasVertexColors(const Scene& scene) {
+  for (const Mesh& m : scene.meshes())
+    if (!m.vertexColors().empty() && m.vertexColors().size() == m.vertexPositions().size()) return true;
+  return false;
+}
+
 inline void Renderer::render(Image& image) {
   const uint32_t w = static_cast<uint32_t>(image.width()), h = static_cast<uint32_t>(image.height());
   // one device, or (GpuSettings::devices, `-gpus N`) the frame tile-sharded over N of them
@@ -80,6 +87,7 @@ inline void Renderer::render(Image& image) {
   }
 
   Image result(w, h);
+  bool colouredFrame = false;  // the frame went through rt_render_colors: its AOVs' albedo is the interpolated colour
   if (p.spp > 0 && multi) {
     // N devices: the whole frame in one sharded launch per device (rt_group_render);
     // update.ppm is written once, after the last pass
@@ -166,6 +174,31 @@ inline void Renderer::render(Image& image) {
     std::cout << "Raytracing with " << pick.slots << " of " << m_scene.lightsources().size() << " lights sampled per path vertex... ["
               << std::string(50, '#') << "] 100%" << std::endl;
     image = result;
+  } else if (p.spp > 0 && GpuSettings::get().vcolors && sceneHasVertexColors(m_scene)) {
+    // -vcolors 1 (extension): the frame with per-vertex albedo (rt_render_colors), in one launch: the colours of the
+    // meshes that have them (COFF files), their material's albedo on the vertices of the others, which those meshes then
+    // shade with as they always did.  update.ppm is written once.  Without -vcolors, or where no mesh has colours, this
+    // branch is not taken.
+    if (multi || p.use_photons) throw std::runtime_error("-vcolors runs on one GPU, without -p");
+    std::vector<float> rgb;
+    size_t colored = 0;
+    for (const Mesh& m : m_scene.meshes()) {
+      const bool has = m.vertexColors().size() == m.vertexPositions().size() && !m.vertexColors().empty();
+      colored += has ? 1 : 0;
+      for (size_t i = 0; i < m.vertexPositions().size(); ++i) {
+        const Vec3f c = has ? m.vertexColors()[i] : m.material().albedo();
+        rgb.insert(rgb.end(), {c[0], c[1], c[2]});
+      }
+    }
+    GpuSession::check(rt_set_vertex_colors(ctx0, rgb.data(), static_cast<uint32_t>(rgb.size() / 3)), "rt_set_vertex_colors");
+    rt_stats st = {};
+    GpuSession::check(rt_render_colors(ctx0, &p, image.data(), result.data(), nullptr, &st), "rt_render_colors");
+    colouredFrame = true;
+    m_stats = st;
+    result.savePPM("update.ppm");
+    std::cout << "Raytracing with the vertex colours of " << colored << " of " << m_scene.meshes().size() << " meshes... ["
+              << std::string(50, '#') << "] 100%" << std::endl;
+    image = result;
   } else if (p.spp > 0) {
     // The reference re-saves update.ppm after EVERY pass (Renderer.cpp:261-269).  Here a
     // "pass" is a sample range of one launch; GpuSettings::progress = P > 0 renders P
@@ -189,8 +222,9 @@ inline void Renderer::render(Image& image) {
     image = result;
   }
 
-  // -aov / -denoise (extensions): the first-hit AOVs of this frame's primary rays (rt_render_aov) and the a-trous filter
-  // of the frame guided by them (rt_denoise).  The frame itself stays as it is.
+  // -aov / -denoise (extensions): the first-hit AOVs of this frame's primary rays (rt_render_aov; of a coloured frame
+  // rt_render_aov_colors, whose albedo channel is the colour the frame shaded with) and the a-trous filter of the frame
+  // guided by them (rt_denoise).  The frame itself stays as it is.
   const bool wantAov = GpuSettings::get().aov, wantDenoise = GpuSettings::get().denoise;
   if ((wantAov || wantDenoise) && multi) throw std::runtime_error("-aov / -denoise run on one GPU only (not with -gpus > 1)");
   if ((wantAov || wantDenoise) && p.spp > 0) {
@@ -200,7 +234,8 @@ inline void Renderer::render(Image& image) {
     std::vector<uint32_t> hits(npx);
     rt_aov aov = {};
     aov.albedo = alb.data(), aov.normal = nrm.data(), aov.position = pos.data(), aov.hits = hits.data();
-    GpuSession::check(rt_render_aov(ctx0, &p, &aov), "rt_render_aov");
+    if (colouredFrame) GpuSession::check(rt_render_aov_colors(ctx0, &p, &aov), "rt_render_aov_colors");
+    else GpuSession::check(rt_render_aov(ctx0, &p, &aov), "rt_render_aov");
     if (wantAov) {  // the means (sum / hits; 0 where no sample hit)
       m_albedo = Image(w, h), m_normal = Image(w, h);
       for (size_t i = 0; i < npx; ++i)

@@ -423,7 +423,8 @@ AMD_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_create", "rt_destroy", "rt
                "rt_render_rays_device", "rt_render_lens", "rt_render_lens_device", "rt_render_shutter",
                "rt_render_shutter_device", "rt_render_views_shutter", "rt_render_views_shutter_device",
                "rt_render_adaptive_shutter", "rt_render_adaptive_shutter_device", "rt_render_lights",
-               "rt_render_lights_device", "rt_render_pick", "rt_render_pick_device"]
+               "rt_render_lights_device", "rt_render_pick", "rt_render_pick_device", "rt_set_vertex_colors",
+               "rt_render_colors", "rt_render_colors_device", "rt_render_aov_colors", "rt_render_aov_colors_device"]
 HOST_SYMBOLS = ["rt_host_scene_build", "rt_host_scene_desc", "rt_host_scene_free", "rt_host_last_error",
                 "rt_host_fill_background", "rt_host_save_ppm", "rt_host_kd_order", "rt_host_light_basis"]
 
@@ -558,6 +559,11 @@ def amd():
         L.rt_rebuild.argtypes = [C.c_void_p, C.POINTER(RebuildParams), C.POINTER(RebuildReport)]
         L.rt_render_aov.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Aov)]
         L.rt_render_aov_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Aov), C.c_void_p]
+        L.rt_render_aov_colors.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Aov)]
+        L.rt_render_aov_colors_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Aov), C.c_void_p]
+        L.rt_set_vertex_colors.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        L.rt_render_colors.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        L.rt_render_colors_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         L.rt_render_ao.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(AoParams), C.POINTER(Ao)]
         L.rt_render_ao_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(AoParams), C.POINTER(Ao), C.c_void_p]
         L.rt_render_rays.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(RayBatch), C.c_void_p, C.c_void_p, C.c_void_p,
@@ -1005,10 +1011,11 @@ class Context:
         _check(amd().rt_trace(self._h, _ptr(rays), len(rays), accel, kind, _ptr(hits)))
         return hits
 
-    def render_aov(self, params, raw=False, channels=AOV_CHANNELS):
+    def render_aov(self, params, raw=False, channels=AOV_CHANNELS, colors=False):
         """rt_render_aov: first-hit AOVs of the frame `params` describes, as a dict of numpy arrays ([h][w][3] albedo,
         normal, position; [h][w] depth, hits, mesh, tri).  The means (sum / hits, 0 where hits == 0); raw=True: the
-        sums rt_render_aov returns.  `channels`: the ones wanted (the others are not computed)."""
+        sums rt_render_aov returns.  `channels`: the ones wanted (the others are not computed).  colors:
+        rt_render_aov_colors, whose albedo channel is the interpolated vertex colour."""
         w, h = params.width, params.height
         if not raw and "hits" not in channels:
             channels = tuple(channels) + ("hits",)  # (the means divide by it)
@@ -1018,15 +1025,53 @@ class Context:
             arr = np.zeros((h, w, 3) if k in AOV_FLOAT3 else (h, w), np.float32 if k in AOV_FLOAT3 or k == "depth" else np.uint32)
             sums[k] = arr
             setattr(a, k, arr.ctypes.data)
-        _check(amd().rt_render_aov(self._h, C.byref(params), C.byref(a)))
+        _check((amd().rt_render_aov_colors if colors else amd().rt_render_aov)(self._h, C.byref(params), C.byref(a)))
         return sums if raw else aov_means(sums)
 
-    def render_aov_device(self, params, ptrs, stream=0):
-        """rt_render_aov_device: the sums into device buffers; ptrs = {channel: device pointer} (missing = not wanted)."""
+    def render_aov_device(self, params, ptrs, stream=0, colors=False):
+        """rt_render_aov_device: the sums into device buffers; ptrs = {channel: device pointer} (missing = not wanted).
+        colors: rt_render_aov_colors_device."""
         a = Aov()
         for k, v in ptrs.items():
             setattr(a, k, v or None)
-        _check(amd().rt_render_aov_device(self._h, C.byref(params), C.byref(a), C.c_void_p(stream or None)))
+        f = amd().rt_render_aov_colors_device if colors else amd().rt_render_aov_device
+        _check(f(self._h, C.byref(params), C.byref(a), C.c_void_p(stream or None)))
+
+    def render_aov_colors(self, params, raw=False, channels=AOV_CHANNELS):
+        """rt_render_aov_colors: render_aov with the albedo channel from the resident vertex colours."""
+        return self.render_aov(params, raw, channels, colors=True)
+
+    def render_aov_colors_device(self, params, ptrs, stream=0):
+        """rt_render_aov_colors_device: render_aov_device with the albedo channel from the resident vertex colours."""
+        self.render_aov_device(params, ptrs, stream, colors=True)
+
+    def set_vertex_colors(self, rgb):
+        """rt_set_vertex_colors: rgb [n_vertices][3] floats become the resident per-vertex albedo (copied); None releases
+        it."""
+        if rgb is None:
+            _check(amd().rt_set_vertex_colors(self._h, None, 0))
+            return
+        rgb = np.ascontiguousarray(rgb, np.float32).reshape(-1, 3)
+        _check(amd().rt_set_vertex_colors(self._h, _ptr(rgb), len(rgb)))
+
+    def render_colors(self, params, bg=None, want_accum=True):
+        """rt_render_colors: the frame with the resident per-vertex albedo; returns (out [h][w][3] or None without bg,
+        accum [h][w][4] or None, stats)."""
+        w, h = params.width, params.height
+        out = np.empty((h, w, 3), np.float32) if bg is not None else None
+        acc = np.empty((h, w, 4), np.float32) if want_accum else None
+        st = Stats()
+        bgc = None if bg is None else np.ascontiguousarray(bg, np.float32)
+        _check(amd().rt_render_colors(self._h, C.byref(params), _ptr(bgc), _ptr(out), _ptr(acc), C.byref(st)))
+        return out, acc, st
+
+    def render_colors_device(self, params, d_accum, stream=0, stats=False):
+        """rt_render_colors_device: accumulate into the caller-zeroed device d_accum [h][w][4] on `stream`; sample ranges
+        chain."""
+        st = Stats() if stats else None
+        _check(amd().rt_render_colors_device(self._h, C.byref(params), C.c_void_p(d_accum), C.c_void_p(stream or None),
+                                             C.byref(st) if stats else None))
+        return st
 
     @staticmethod
     def _ao_params(n_rays, bias, max_distance):
