@@ -14,6 +14,7 @@ import numpy as np
 
 import ao_ref
 import aov_ref
+import depth_scenes
 import orc
 import pyrt
 import rays_ref
@@ -193,10 +194,11 @@ def expected_pinhole(scene, params, accel=orc.ACCEL_OBVH):
 
 # ---- scenes, cameras and the cases test_gpu_lens.py compares bit for bit ---------------------------------------------------
 def scene(name, opened, w, h):
-    """The preset at the frame's aspect, or (opened) without its enclosing room: primary rays then miss."""
+    """The preset at the frame's aspect, or (opened) without its enclosing room: primary rays then miss.  name: a
+    preset's, or "depth:X" for depth_scenes' shallow scene X."""
     key = ("scene", name, opened, w, h)
     if key not in _cache:
-        s = pyrt.Scene(name, w, h)
+        s = depth_scenes.preset(name, w, h)
         s = ao_ref.without_mesh0(s) if opened else s
         pos = np.asarray(s.arrays()["camera"], F32).reshape(4, 3)[0]
         assert (pos != 0).all(), "a camera position component is +-0: the oracle's F + u 0 would lose a -0"

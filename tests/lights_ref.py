@@ -8,6 +8,7 @@ oracle alone, together with the condition that keeps a kernel which ignores or s
 import numpy as np
 
 import ao_ref
+import depth_scenes
 import lens_ref
 import orc
 import pyrt
@@ -23,13 +24,14 @@ RAY, PATH = pyrt.MODE_RAY, pyrt.MODE_PATH
 
 def scene(key, w, h):
     """key: (preset, opened) — the preset, or without its enclosing room, three lights — or ("sweep", preset, idx): the
-    preset's geometry with the materials and the 1, 2 or 4 lights of shading_sweep's scene idx."""
+    preset's geometry with the materials and the 1, 2 or 4 lights of shading_sweep's scene idx.  preset: a preset's name,
+    or "depth:X" for depth_scenes' shallow scene X."""
     ck = ("scene", key, w, h)
     if ck not in _cache:
         if key[0] == "sweep":
             _cache[ck] = shading_sweep.build_scene(key[1], w, h, key[2])
         else:
-            s = pyrt.Scene(key[0], w, h)
+            s = depth_scenes.preset(key[0], w, h)
             _cache[ck] = ao_ref.without_mesh0(s) if key[1] else s
     return _cache[ck]
 

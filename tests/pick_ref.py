@@ -12,6 +12,7 @@ import ctypes as C
 import numpy as np
 
 import ao_ref
+import depth_scenes
 import lens_ref
 import orc
 import pyrt
@@ -114,10 +115,10 @@ def with_lights(s, lights):
 
 def scene(key, w, h):
     """key: (preset, opened, n lights[, dim]) — the preset, or without its enclosing room, with its lights replaced by n
-    of many_lights'."""
+    of many_lights'.  preset: a preset's name, or "depth:X" for depth_scenes' shallow scene X."""
     ck = ("scene", key, w, h)
     if ck not in _cache:
-        s = pyrt.Scene(key[0], w, h)
+        s = depth_scenes.preset(key[0], w, h)
         if key[1]:
             s = ao_ref.without_mesh0(s)
         _cache[ck] = with_lights(s, many_lights(s.arrays()["lights"], key[2], *key[3:]))

@@ -12,6 +12,7 @@ import numpy as np
 
 import ao_ref
 import aov_ref
+import depth_scenes
 import orc
 import pyrt
 
@@ -22,10 +23,11 @@ _cache = {}
 
 
 def scene(name, opened):
-    """The preset scene, or (opened) the preset without its enclosing room: rays then miss."""
+    """The preset scene, or (opened) the preset without its enclosing room: rays then miss.  name: a preset's, or
+    "depth:X" for depth_scenes' shallow scene X."""
     key = ("scene", name, opened)
     if key not in _cache:
-        s = pyrt.Scene(name, FRAME_W, FRAME_H)
+        s = depth_scenes.preset(name, FRAME_W, FRAME_H)
         _cache[key] = ao_ref.without_mesh0(s) if opened else s
     return _cache[key]
 

@@ -98,10 +98,11 @@ def clamp01(x):
     return np.fmax(np.fmin(x, F32(1)), F32(0)).astype(F32)
 
 
-def frame(scene, params, colors, bg=None, brute=False):
+def frame(scene, params, colors, bg=None, brute=False, touched=True):
     """The coloured frame `params` describes: dict(accum [h][w][4], out [h][w][3] or None, closest, shadow, albedo
     [h][w][3] — the first-hit sums of c, rt_render_aov_colors' albedo channel — and touched [h][w][n_tris] bool: the
-    triangles the pixel's paths shaded a vertex on)."""
+    triangles the pixel's paths shaded a vertex on (None with touched=False: at a million triangles it is 48 MB for an
+    8x6 frame)."""
     a = scene.arrays()
     w, h = params.width, params.height
     ns = params.spp_count if params.spp_count else params.spp
@@ -166,11 +167,14 @@ def frame(scene, params, colors, bg=None, brute=False):
         acc[:, 3] = np.where(found[:, i], acc[:, 3] + F32(1), acc[:, 3])
         alb = np.where(found[:, i, None], (alb + first[:, i]).astype(F32), alb)
     acc = acc.reshape(h, w, 4)
-    touched = np.zeros((w * h, len(a["tri"])), bool)
-    touched[vs // ns, gid] = True
+    seen = None
+    if touched:
+        seen = np.zeros((w * h, len(a["tri"])), bool)
+        seen[vs // ns, gid] = True
+        seen = seen.reshape(h, w, -1)
     out = None if bg is None else lens_ref.resolve(acc, np.asarray(bg, F32), params.spp)
     return dict(accum=acc, out=out, closest=int(closest.sum()), shadow=int(shadow.sum()), albedo=alb.reshape(h, w, 3),
-                touched=touched.reshape(h, w, -1))
+                touched=seen)
 
 
 # ---- the frames test_gpu_vcol.py compares bit for bit, shared with test_vcol_ref_cpu.py -----------------------------------
