@@ -46,6 +46,8 @@
  *                                  sample, picked by importance and weighted by 1 / (m p) (+ _device form)
  *   rt_set_vertex_colors / rt_render_colors / rt_render_aov_colors <- (no counterpart) per-vertex albedo: the frame and
  *                                  its first-hit AOVs with the colour interpolated at every shaded vertex (+ _device forms)
+ *   rt_set_textures / rt_render_textured / rt_render_aov_textured <- (no counterpart) image-textured albedo: the frame and
+ *                                  its first-hit AOVs with the hit mesh's texture sampled at every shaded vertex (+ _device forms)
  *   rt_render_aov_views / rt_render_motion_views / rt_denoise_batch <- (no counterpart) the AOVs, motion vectors and
  *                                  denoised frames of those views, one launch each (+ _device forms)
  *   rt_trace                    <- RayTracer::rayTrace (RayTracer.h:27-53) test hook
@@ -67,9 +69,10 @@
  *     rt_render_device, rt_render_views_device, rt_render_rays_device, rt_render_shutter_device,
  *     rt_render_views_shutter_device (tests/test_gpu_views_shutter.py), rt_render_lights_device
  *     (tests/test_gpu_lights.py), rt_render_pick_device (tests/test_gpu_pick.py), rt_render_colors_device
- *     (tests/test_gpu_vcol.py) and rt_render_lens_device with stats == NULL;
+ *     (tests/test_gpu_vcol.py), rt_render_textured_device (tests/test_gpu_tex.py) and
+ *     rt_render_lens_device with stats == NULL;
  *     rt_resolve_device;
- *     rt_render_aov_device, rt_render_aov_colors_device, rt_render_ao_device, rt_render_motion_device; rt_temporal_accumulate_device,
+ *     rt_render_aov_device, rt_render_aov_colors_device, rt_render_aov_textured_device, rt_render_ao_device, rt_render_motion_device; rt_temporal_accumulate_device,
  *     rt_svgf_device, rt_denoise_device, rt_denoise_batch_device; rt_render_aov_views_device,
  *     rt_render_motion_views_device; rt_pack_owned_device, rt_unpack_owned_device; rt_trace_stream_device.
  *     Host arguments (params, cameras, seeds, previous cameras, a pick's importance array) are copied before the call
@@ -82,7 +85,7 @@
  *   SYNCHRONISE `stream`, and only it, before they return, because the host reads a result back:
  *     rt_render_device, rt_render_views_device, rt_render_rays_device, rt_render_shutter_device,
  *     rt_render_views_shutter_device, rt_render_lights_device, rt_render_pick_device, rt_render_colors_device,
- *     rt_render_lens_device with stats != NULL;
+ *     rt_render_textured_device, rt_render_lens_device with stats != NULL;
  *     rt_render_adaptive_device and rt_render_adaptive_shutter_device (every pass); rt_update_vertices_device,
  *     rt_update_transforms and rt_update_skin (twice);
  *     the four multi-view forms when a view lies far enough out to need a wider box padding (a refit).
@@ -919,6 +922,88 @@ int rt_render_colors(rt_ctx* ctx, const rt_params* p, const float* background_rg
 int rt_render_colors_device(rt_ctx* ctx, const rt_params* p, void* d_accum, void* stream, rt_stats* stats);
 int rt_render_aov_colors(rt_ctx* ctx, const rt_params* p, const rt_aov* host_out);
 int rt_render_aov_colors_device(rt_ctx* ctx, const rt_params* p, const rt_aov* device_out, void* stream);
+
+/* ---- image-textured albedo ------------------------------------------------------------------------------
+ * rt_set_textures makes a set of images resident — the textures, one texture index (or RT_TEX_NONE) per mesh and one
+ * texture coordinate pair per vertex, indexed by the global vertex id as the normals are — and rt_render_textured renders
+ * rt_render's frame with ONE substitution at every shaded vertex: on a mesh with a texture the material is the hit mesh's
+ * with albedo replaced, per component, by the sample c of that texture at the hit; from c the vertex forms
+ * kdDiffuse = kd * (c / float(M_PI)), as rt_render_colors does.  A mesh mapped to RT_TEX_NONE shades with its own material.
+ * The RNG streams, the jitter, every ray, the hit selection, both ray counts, the per-sample clamp and the accumulation are
+ * rt_render's: textures never move a ray.  Resident vertex colours are not read.
+ * The sample is defined operation by operation (the device has no image instructions): all of it is float32, every
+ * operation rounded on its own, nothing fused.
+ *   coordinates, per axis, from the uvs of the triangle's three vertices in the order of its index triple and the hit's
+ *   barycentrics:  s = (s0 + u * (s1 - s0)) + v * (s2 - s0)      (three equal uvs give s0 exactly); t likewise
+ *   RT_TEX_NEAREST:   i = wrap(int(floorf(s * float(W))), W), j = wrap(int(floorf(t * float(H))), H);  c = texel[j][i]
+ *   RT_TEX_BILINEAR:  x = s * float(W) - 0.5f; xf = floorf(x); fx = x - xf; i0 = wrap(int(xf), W); i1 = wrap(int(xf) + 1, W);
+ *                     y, yf, fy, j0, j1 from t and H in the same way; per component
+ *                     a = texel[j0][i0] + fx * (texel[j0][i1] - texel[j0][i0])
+ *                     b = texel[j1][i0] + fx * (texel[j1][i1] - texel[j1][i0])
+ *                     c = a + fy * (b - a)                        (four equal texels give that texel exactly)
+ *   wrap(i, N):       RT_TEX_REPEAT: the non-negative remainder ((i % N) + N) % N in int32; RT_TEX_CLAMP: min(max(i, 0), N - 1)
+ * Row j of a texture covers t in [j / H, (j + 1) / H): row 0 is t = 0.  |uv| <= 1024 and W, H <= 16384 keep int(...) far
+ * inside int32 (|s| <= 5 * 1024, so |s * W| < 2^27).
+ * Guarantees, bit for bit on accumulator, image, samples and both ray counts, for texels that are not -0:
+ *   - T1: a set in which every mesh is RT_TEX_NONE gives rt_render's frame; so does a set in which every textured mesh's
+ *     texels all equal its material's albedo, whatever the uvs, filters and wraps.
+ *   - T2: on a scene in which triangle k of n owns its three vertices, all three with uv ((3k + 1.5) / (3n), 0.5), and a
+ *     3n x 1 texture whose texels 3k .. 3k + 2 hold colour k, the frame under either filter is rt_render_colors' with colour k
+ *     on the vertices of triangle k — and so (C2) rt_render's on the scene of one mesh per triangle: every texel a sample can
+ *     touch holds the same colour, so the rounding of x cannot show.
+ *   - T3: sample ranges chain (spp_begin / spp_count), and host and device forms agree.
+ *   - T4: reserved[0] (lanes per pixel), reserved[1] bit 0 (no pool), collect_stats, RT_ACCEL_BRUTE and the node format
+ *     change the schedule, never the bits.
+ * rt_set_textures copies the whole set to the context's device, into fresh allocations, and then replaces the set before;
+ * NULL releases it.  It changes nothing any other entry point reads; the set stays across every update, refit, rt_rebuild,
+ * transform and skin (uvs go by global vertex id, and the vertex and mesh counts of a context never change) and goes with
+ * rt_destroy.  It is a host form: it returns when the copies are done; the arrays it replaces are freed once the launches
+ * that read them have run.
+ *   RT_ERR_INVALID, with rt_last_error naming the first offending value, in this order: a null textures, mesh_texture or
+ *   vertex_uv; n_textures == 0; a non-zero reserved word of the set; per texture, in index order: a width or height outside
+ *   1..16384, an unknown wrap_s, wrap_t or filter, a non-zero reserved word, a null texels, a running total of texels above
+ *   2^28; then a texel that is not finite; a mesh_texture entry that is neither an index nor RT_TEX_NONE; a uv that is not
+ *   finite or beyond 1024 in magnitude; then a null ctx with a non-null set; n_meshes or n_vertices different from the
+ *   context's.  A null set with a null ctx.
+ *   RT_ERR_STATE  a context that refuses launches (nothing is uploaded to it).
+ * rt_render_textured / rt_render_textured_device take rt_render's / rt_render_device's arguments and rt_render_colors'
+ * checks in its order: RT_ERR_INVALID for what the arguments alone decide; RT_ERR_UNSUPPORTED: world > 1, use_photons, the
+ * wavefront integrator (reserved[2] bit 0), the legacy RNG; then the device (RT_ERR_NO_DEVICE); then the context:
+ * RT_ERR_STATE for one that refuses launches or has no resident set.  The frame runs on the one-wave-per-workgroup kernel
+ * family of rt_render_lens (no persistent instances); RT_NODES_Q8 contexts walk their resident 32-byte records, as there.
+ * rt_render_aov_textured / rt_render_aov_textured_device are rt_render_aov / rt_render_aov_device with the albedo channel
+ * summing c at the first hit (the mesh's albedo on an RT_TEX_NONE mesh); every other channel is rt_render_aov's bit for
+ * bit.  rt_render_aov's checks, then RT_ERR_STATE without a resident set.
+ * Out of scope: mip maps and any filter that needs ray footprints; 8-bit or sRGB texel storage; textures on alpha, f0 or
+ * normals; textures combined with vertex colours, the lens, the shutter, light groups, light picks, views, adaptive passes
+ * or rt_render_rays; rt_group; a device-memory form of the set.                                                          */
+#define RT_TEX_NONE 0xffffffffu
+enum { RT_TEX_REPEAT = 0, RT_TEX_CLAMP = 1 };
+enum { RT_TEX_NEAREST = 0, RT_TEX_BILINEAR = 1 };
+typedef struct rt_texture {
+  uint32_t width, height;      /* 1..16384 each                                            */
+  uint32_t wrap_s, wrap_t;     /* RT_TEX_REPEAT | RT_TEX_CLAMP                             */
+  uint32_t filter;             /* RT_TEX_NEAREST | RT_TEX_BILINEAR                         */
+  uint32_t reserved[3];        /* 0                                                        */
+  const float* texels;         /* [height][width][3] HOST memory, linear rgb, any finite value;
+                                  row j covers t in [j/height, (j+1)/height)               */
+} rt_texture;
+typedef struct rt_texture_set {
+  uint32_t n_textures, n_meshes, n_vertices;   /* the last two must be the context's       */
+  const rt_texture* textures;                  /* [n_textures]                             */
+  const uint32_t* mesh_texture;                /* [n_meshes]: a texture index or RT_TEX_NONE */
+  const float* vertex_uv;                      /* [n_vertices][2], global vertex ids, finite, |.| <= 1024 */
+  uint32_t reserved[4];
+} rt_texture_set;
+int rt_set_textures(rt_ctx* ctx, const rt_texture_set* set /* NULL: release */);
+/* out_rgb [h][w][3] or NULL, accum_out [h][w][4] or NULL, background_rgb [h][w][3]: as rt_render's */
+int rt_render_textured(rt_ctx* ctx, const rt_params* p, const float* background_rgb, float* out_rgb, float* accum_out,
+                       rt_stats* stats);
+/* Accumulate into caller-zeroed DEVICE d_accum [h][w][4] on `stream` (a hipStream_t, may be NULL), as rt_render_device
+ * does: sample ranges chain (stats == NULL: asynchronous; stats != NULL: synchronises `stream`, and only it). */
+int rt_render_textured_device(rt_ctx* ctx, const rt_params* p, void* d_accum, void* stream, rt_stats* stats);
+int rt_render_aov_textured(rt_ctx* ctx, const rt_params* p, const rt_aov* host_out);
+int rt_render_aov_textured_device(rt_ctx* ctx, const rt_params* p, const rt_aov* device_out, void* stream);
 
 /* ---- motion vectors and temporal accumulation (DESIGN.md "Motion vectors and temporal accumulation") ----------------
  * Two stateless calls for animated frames.  The library keeps nothing between frames: the caller hands in last frame's

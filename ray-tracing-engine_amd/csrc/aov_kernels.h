@@ -34,7 +34,9 @@ RT_DEV ViewOfWave view_of_wave(const ViewRec* views, uint32_t tilesPerView) {
 // channel is written into the view's slice (view_slice, in 64 bits).
 // VCOL (rt_render_aov_colors): the albedo channel sums the colour interpolated from A.vcol at the hit (vertex_color)
 // instead of the mesh's albedo; the other instances do not read A.vcol and are the kernels they were before it existed.
-template <bool BRUTE, bool VIEWS, bool VCOL = false>
+// TEX (rt_render_aov_textured): the albedo channel sums the sample of the hit mesh's texture (tex_color), or the mesh's
+// albedo where it has none, from A's four tex* tables; the other instances do not read them.
+template <bool BRUTE, bool VIEWS, bool VCOL = false, bool TEX = false>
 __global__ __launch_bounds__(64) void k_aov(DevScene S, AovArgs A) {
   __shared__ uint32_t lds[(rtbvh::kMaxDepth + 1) * 64];
   ViewOfWave vw;
@@ -65,6 +67,15 @@ __global__ __launch_bounds__(64) void k_aov(DevScene S, AovArgs A) {
         vertex_setup_ray(S, h.id, o, d, nrm, pt, tv, u, v);
         mesh = tv.w;
         alb = alb + vertex_color(A.vcol, tv, u, v);
+      } else if constexpr (TEX) {
+        uint4 tv;
+        float u, v;
+        vertex_setup_ray(S, h.id, o, d, nrm, pt, tv, u, v);
+        mesh = tv.w;
+        bool textured;
+        const f3 c = tex_color(TexRec{A.texUv, A.texMesh, A.texDesc, A.texels}, tv, u, v, textured);
+        const rt_material& m = S.mats[mesh];
+        alb = alb + (textured ? c : mk(m.albedo[0], m.albedo[1], m.albedo[2]));
       } else {
         vertex_setup_ray(S, h.id, o, d, nrm, pt, mesh);
         const rt_material& m = S.mats[mesh];
@@ -104,6 +115,17 @@ hipError_t launch_aov_colors(bool brute_force, const DevScene& S, const AovArgs&
   C.vcol = vcol;
   if (brute_force) hipLaunchKernelGGL((k_aov<true, false, true>), dim3(tiles), dim3(64), 0, stream, S, C);
   else hipLaunchKernelGGL((k_aov<false, false, true>), dim3(tiles), dim3(64), 0, stream, S, C);
+  return hipGetLastError();
+}
+
+hipError_t launch_aov_textured(bool brute_force, const DevScene& S, const AovArgs& A, const TexRec& T, hipStream_t stream) {
+  const uint32_t tiles = ((A.width + 7u) / 8u) * ((A.height + 7u) / 8u);
+  if (!T.uv || !T.meshTex || !T.desc || !T.texels) return hipErrorInvalidValue;
+  if (tiles == 0 || A.s1 <= A.s0) return hipSuccess;
+  AovArgs C = A;
+  C.texUv = T.uv, C.texMesh = T.meshTex, C.texDesc = T.desc, C.texels = T.texels;
+  if (brute_force) hipLaunchKernelGGL((k_aov<true, false, false, true>), dim3(tiles), dim3(64), 0, stream, S, C);
+  else hipLaunchKernelGGL((k_aov<false, false, false, true>), dim3(tiles), dim3(64), 0, stream, S, C);
   return hipGetLastError();
 }
 

@@ -1,6 +1,6 @@
 // frame_variants.h — the frame integrator with another generator, another split of its samples or another light list:
 // rt_render_lens, rt_render_shutter, rt_render_views_shutter, rt_render_lights (DESIGN.md §6m–§6p), rt_render_pick (§6r)
-// and, with another albedo at every vertex, rt_render_colors (§6t).
+// and, with another albedo at every vertex, rt_render_colors (§6t) and rt_render_textured (§6u).
 //
 // Every variant is render_tile itself under one more LT_* bit, on the one-wave-per-workgroup family that k_render serves:
 // brute, sequential and pooled, each counted (STATS, one wave per SIMD) and timed (four waves per SIMD, k_render's target);
@@ -26,6 +26,9 @@
 //                                        triangle's vertices (vertex_kd) and shades with it (vertex_pool's and
 //                                        shade_direct_seq's VC switch); a launch allocates VP_VCOL_WORDS more words of
 //                                        LDS per wave, where it is parked over every walk
+//   textures      LT_TEX                 TexRec: every shaded vertex of a mesh with a texture forms its kdDiffuse from
+//                                        the texture's sample at the hit's uv (tex_kd) and shades with it through the
+//                                        same VC switch and the same parked rows as a coloured frame's
 // A new variant supplies a row of the same kind (a struct below, a FrameVariant kind, a case in launch_render_variant):
 // its LT_* bits, its record, the stack rows its sample hand-over needs, and its argument check.
 // (included by rt_kernels.hip inside namespace rtk: shares its device functions)
@@ -46,10 +49,10 @@ __global__ __launch_bounds__(BLOCK, MINW) void k_render_rec(DevScene S, RenderAr
   const Lds L = carve_lds<false>(lds, A.stackLevels, 0);
   uint32_t* pool = lds + A.stackLevels * BLOCK;
   float* ex = reinterpret_cast<float*>(POOLED ? pool : lds);
-  // (LT_VCOL) then three rows where a vertex's kdDiffuse is parked: behind everything launch_variant2 allocates before
+  // (LT_VCOL, LT_TEX) then three rows where a vertex's kdDiffuse is parked: behind everything launch_variant2 allocates before
   // them — max(stackLevels, kParkMinRows) stack rows and, with one, the pool
   float* park = nullptr;
-  if constexpr ((LTV & LT_VCOL) != 0)
+  if constexpr ((LTV & (LT_VCOL | LT_TEX)) != 0)
     park = reinterpret_cast<float*>(lds + (A.stackLevels < kParkMinRows ? kParkMinRows : A.stackLevels) * BLOCK + (POOLED ? VP_WORDS : 0));
   LaneStats st;
   const uint32_t t0 = blockIdx.x * A.tilesPerBlock, t1 = min(A.n_tiles, t0 + A.tilesPerBlock);
@@ -95,6 +98,14 @@ struct VariantVCol {
   static constexpr uint32_t ROWS = 4, ROWS_POOLED = 4;
   static bool refused(const DevScene&, const RenderArgs& A, const Rec& R) { return A.tileView || !R.vcol; }
 };
+struct VariantTex {
+  static constexpr int LTV = LT_TEX;
+  using Rec = TexRec;
+  static constexpr uint32_t ROWS = 4, ROWS_POOLED = 4;
+  static bool refused(const DevScene&, const RenderArgs& A, const Rec& R) {
+    return A.tileView || !R.uv || !R.meshTex || !R.desc || !R.texels;
+  }
+};
 struct VariantViewsShutter {
   static constexpr int LTV = LT_VIEWS | LT_SHUTTER;
   using Rec = NoRec;
@@ -117,8 +128,8 @@ static hipError_t launch_variant2(bool stats, const DevScene& S, const RenderArg
                                   unsigned long long* counters, hipStream_t stream) {
   if (A.n_tiles == 0) return hipSuccess;
   constexpr uint32_t minRows = POOLED ? V::ROWS_POOLED : V::ROWS;
-  // (a coloured frame's wave parks the vertex's kdDiffuse behind its stack rows and pool: k_render_rec's `park`)
-  constexpr uint32_t parkWords = (V::LTV & LT_VCOL) != 0 ? VP_VCOL_WORDS : 0;
+  // (a coloured or textured frame's wave parks the vertex's kdDiffuse behind its stack rows and pool: k_render_rec's `park`)
+  constexpr uint32_t parkWords = (V::LTV & (LT_VCOL | LT_TEX)) != 0 ? VP_VCOL_WORDS : 0;
   static_assert(parkWords == 0 || minRows == kParkMinRows, "k_render_rec places the parked rows behind kParkMinRows stack rows at least");
   const size_t ldsBytes = 4u * ((A.stackLevels < minRows ? minRows : A.stackLevels) * BLOCK + (POOLED ? VP_WORDS : 0) + parkWords);
   RenderArgs A1 = A;
@@ -157,6 +168,8 @@ hipError_t launch_render_variant(const FrameVariant& F, bool brute_force, bool s
       return launch_variant<VariantPick>(brute_force, stats, S, A, *static_cast<const PickRec*>(F.rec), accum, counters, stream);
     case FrameVariant::VCOL:
       return launch_variant<VariantVCol>(brute_force, stats, S, A, *static_cast<const VColRec*>(F.rec), accum, counters, stream);
+    case FrameVariant::TEX:
+      return launch_variant<VariantTex>(brute_force, stats, S, A, *static_cast<const TexRec*>(F.rec), accum, counters, stream);
     case FrameVariant::VIEWS_SHUTTER:
       return launch_variant<VariantViewsShutter>(brute_force, stats, S, A, NoRec(), accum, counters, stream);
     case FrameVariant::NONE: break;

@@ -322,6 +322,16 @@ struct rt_ctx {
   // rt_set_vertex_colors: the resident [nVertices][3] colours that rt_render_colors and rt_render_aov_colors interpolate
   // (null: none); nothing else reads them, and no update touches them
   DevBuf<float> vcol;
+  // rt_set_textures: the resident texture set that rt_render_textured and rt_render_aov_textured sample (texels null:
+  // none) — the uvs by global vertex id, every mesh's texture index, one descriptor per texture and the texel pool;
+  // nothing else reads them, and no update touches them
+  struct TexSet {
+    DevBuf<float> uv, texels;
+    DevBuf<uint32_t> meshTex;
+    DevBuf<rtk::TexDesc> desc;
+    explicit operator bool() const { return (bool)texels; }
+    rtk::TexRec rec() const { return rtk::TexRec{uv.get(), meshTex.get(), desc.get(), texels.get()}; }
+  } tex;
   // scratch of rt_denoise_device and rt_svgf_device (rtk::filter_scratch; grows on demand: ensure_filter_scratch)
   DevBuf<float4> dnScratch;
   size_t dnCap = 0;
@@ -2669,28 +2679,42 @@ rtk::AovArgs aov_args(const rt_params& q, const rt_aov& out) {
   return A;
 }
 
-// rt_render_aov_device, or (colors) rt_render_aov_colors_device: the albedo channel from the resident vertex colours
-int aov_device(rt_ctx* c, const rt_params* p, const rt_aov* out, void* stream, bool colors) {
+// what the albedo channel of an AOV pass sums: the mesh's albedo, the resident vertex colours' interpolation
+// (rt_render_aov_colors) or the resident textures' sample (rt_render_aov_textured)
+enum AovAlbedo { ALBEDO_MESH, ALBEDO_COLORS, ALBEDO_TEXTURES };
+
+// RT_ERR_STATE where the context lacks what the albedo channel reads
+int aov_albedo_resident(const rt_ctx* c, AovAlbedo alb) {
+  if (alb == ALBEDO_COLORS && !c->vcol) return fail(RT_ERR_STATE, "the context has no resident vertex colours (rt_set_vertex_colors)");
+  if (alb == ALBEDO_TEXTURES && !c->tex) return fail(RT_ERR_STATE, "the context has no resident textures (rt_set_textures)");
+  return RT_OK;
+}
+
+// rt_render_aov_device, rt_render_aov_colors_device or rt_render_aov_textured_device
+int aov_device(rt_ctx* c, const rt_params* p, const rt_aov* out, void* stream, AovAlbedo alb) {
   rt_params q;
   int rc = aov_checks(c, p, &q);
   if (rc != RT_OK) return rc;
   if (!out) return fail(RT_ERR_INVALID, "aov is null");
-  if (colors && !c->vcol) return fail(RT_ERR_STATE, "the context has no resident vertex colours (rt_set_vertex_colors)");
+  if ((rc = aov_albedo_resident(c, alb)) != RT_OK) return rc;
   HIP_TRY(hipSetDevice(c->device));
   const rtk::AovArgs A = aov_args(q, *out);
-  const hipError_t he = colors ? rtk::launch_aov_colors(q.accel == RT_ACCEL_BRUTE, c->S, A, c->vcol.get(), static_cast<hipStream_t>(stream))
-                               : rtk::launch_aov(q.accel == RT_ACCEL_BRUTE, c->S, A, static_cast<hipStream_t>(stream));
+  const bool brute = q.accel == RT_ACCEL_BRUTE;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const hipError_t he = alb == ALBEDO_COLORS     ? rtk::launch_aov_colors(brute, c->S, A, c->vcol.get(), s)
+                        : alb == ALBEDO_TEXTURES ? rtk::launch_aov_textured(brute, c->S, A, c->tex.rec(), s)
+                                                 : rtk::launch_aov(brute, c->S, A, s);
   if (he != hipSuccess) return fail(RT_ERR_HIP, "AOV launch failed: %s", hipGetErrorString(he));
   return RT_OK;
 }
 
-// the host form of either
-int aov_host(rt_ctx* c, const rt_params* p, const rt_aov* out, bool colors) {
+// the host form of each
+int aov_host(rt_ctx* c, const rt_params* p, const rt_aov* out, AovAlbedo alb) {
   rt_params q;
   int rc = aov_checks(c, p, &q);
   if (rc != RT_OK) return rc;
   if (!out) return fail(RT_ERR_INVALID, "aov is null");
-  if (colors && !c->vcol) return fail(RT_ERR_STATE, "the context has no resident vertex colours (rt_set_vertex_colors)");
+  if ((rc = aov_albedo_resident(c, alb)) != RT_OK) return rc;
   HIP_TRY(hipSetDevice(c->device));
   const size_t npx = (size_t)q.width * q.height;
   Staging st;
@@ -2698,7 +2722,7 @@ int aov_host(rt_ctx* c, const rt_params* p, const rt_aov* out, bool colors) {
   d.albedo = st.out(out->albedo, 3 * npx), d.normal = st.out(out->normal, 3 * npx), d.position = st.out(out->position, 3 * npx);
   d.depth = st.out(out->depth, npx), d.hits = st.out(out->hits, npx), d.mesh = st.out(out->mesh, npx), d.tri = st.out(out->tri, npx);
   if (st.rc != RT_OK) return st.rc;
-  if ((rc = aov_device(c, &q, &d, nullptr, colors)) != RT_OK) return rc;
+  if ((rc = aov_device(c, &q, &d, nullptr, alb)) != RT_OK) return rc;
   return st.download();
 }
 
@@ -2706,10 +2730,12 @@ int aov_host(rt_ctx* c, const rt_params* p, const rt_aov* out, bool colors) {
 
 extern "C" {
 
-int rt_render_aov_device(rt_ctx* c, const rt_params* p, const rt_aov* out, void* stream) { return aov_device(c, p, out, stream, false); }
-int rt_render_aov(rt_ctx* c, const rt_params* p, const rt_aov* out) { return aov_host(c, p, out, false); }
-int rt_render_aov_colors_device(rt_ctx* c, const rt_params* p, const rt_aov* out, void* stream) { return aov_device(c, p, out, stream, true); }
-int rt_render_aov_colors(rt_ctx* c, const rt_params* p, const rt_aov* out) { return aov_host(c, p, out, true); }
+int rt_render_aov_device(rt_ctx* c, const rt_params* p, const rt_aov* out, void* stream) { return aov_device(c, p, out, stream, ALBEDO_MESH); }
+int rt_render_aov(rt_ctx* c, const rt_params* p, const rt_aov* out) { return aov_host(c, p, out, ALBEDO_MESH); }
+int rt_render_aov_colors_device(rt_ctx* c, const rt_params* p, const rt_aov* out, void* stream) { return aov_device(c, p, out, stream, ALBEDO_COLORS); }
+int rt_render_aov_colors(rt_ctx* c, const rt_params* p, const rt_aov* out) { return aov_host(c, p, out, ALBEDO_COLORS); }
+int rt_render_aov_textured_device(rt_ctx* c, const rt_params* p, const rt_aov* out, void* stream) { return aov_device(c, p, out, stream, ALBEDO_TEXTURES); }
+int rt_render_aov_textured(rt_ctx* c, const rt_params* p, const rt_aov* out) { return aov_host(c, p, out, ALBEDO_TEXTURES); }
 
 int rt_denoise_device(rt_ctx* c, const rt_denoise_params* d, const void* d_rgb, const rt_aov* aov, void* d_out, void* stream) {
   int rc = denoise_checks(c, d, d_rgb, aov, d_out);
@@ -3964,6 +3990,126 @@ int rt_render_colors_device(rt_ctx* c, const rt_params* p, void* d_accum, void* 
 int rt_render_colors(rt_ctx* c, const rt_params* p, const float* bg, float* out_rgb, float* accum_out, rt_stats* stats) {
   rtk::VColRec R;
   const int rc = colors_checks(c, p, outputs_refused(bg, out_rgb, accum_out), &R);
+  if (rc != RT_OK) return rc;
+  return frame_host(c, p, R, 1, bg, out_rgb, accum_out, stats);
+}
+
+}  // extern "C"
+
+// ---- image-textured albedo ------------------------------------------------------------------------------
+namespace {
+
+// Everything both forms of rt_render_textured check, in colors_checks' order, and the record the kernels take.
+int textured_checks(const rt_ctx* c, const rt_params* p, const char* outputs, rtk::TexRec* R) {
+  if (!c || !p) return fail(RT_ERR_INVALID, "ctx/params is null");
+  if (outputs) return fail(RT_ERR_INVALID, "%s", outputs);
+  int rc = check_params_shape(p);
+  if (rc != RT_OK) return rc;
+  if (p->world > 1) return fail(RT_ERR_UNSUPPORTED, "tile-sharded textured frames (world %u) are not supported", p->world);
+  if (p->use_photons) return fail(RT_ERR_UNSUPPORTED, "textured frames do not shade from the photon map");
+  if (p->reserved[2] & 1u) return fail(RT_ERR_UNSUPPORTED, "textured frames do not run the wavefront integrator");
+  if ((rc = check_device_present()) != RT_OK) return rc;
+  if ((rc = check_not_broken(c)) != RT_OK) return rc;
+  if (!c->tex) return fail(RT_ERR_STATE, "the context has no resident textures (rt_set_textures)");
+  *R = c->tex.rec();
+  return RT_OK;
+}
+
+constexpr uint32_t kTexMaxSide = 16384u;       // with |uv| <= kTexMaxUv: int(floorf(s * W)) stays far inside int32 (rt_kernels.hip tex_sample)
+constexpr float kTexMaxUv = 1024.f;
+constexpr uint64_t kTexMaxTexels = 1ull << 28;  // 3 floats each: the pool's float index stays below 2^32
+
+// What a texture set says of itself, before anything of a context: the headers of all textures, then the total, then
+// the texels (so no texel of a refused header is read), the meshes' indices and the uvs.
+int texture_set_checks(const rt_texture_set* t) {
+  if (!t->textures || !t->mesh_texture || !t->vertex_uv) return fail(RT_ERR_INVALID, "textures: textures/mesh_texture/vertex_uv is null");
+  if (t->n_textures == 0) return fail(RT_ERR_INVALID, "textures: n_textures is 0");
+  for (int k = 0; k < 4; ++k)
+    if (t->reserved[k]) return fail(RT_ERR_INVALID, "textures: reserved[%d] of the set is %u, not 0", k, t->reserved[k]);
+  uint64_t total = 0;
+  for (uint32_t i = 0; i < t->n_textures; ++i) {
+    const rt_texture& x = t->textures[i];
+    if (x.width < 1u || x.width > kTexMaxSide) return fail(RT_ERR_INVALID, "textures: texture %u: width %u is outside 1..%u", i, x.width, kTexMaxSide);
+    if (x.height < 1u || x.height > kTexMaxSide) return fail(RT_ERR_INVALID, "textures: texture %u: height %u is outside 1..%u", i, x.height, kTexMaxSide);
+    if (x.wrap_s > (uint32_t)RT_TEX_CLAMP) return fail(RT_ERR_INVALID, "textures: texture %u: wrap_s %u is unknown", i, x.wrap_s);
+    if (x.wrap_t > (uint32_t)RT_TEX_CLAMP) return fail(RT_ERR_INVALID, "textures: texture %u: wrap_t %u is unknown", i, x.wrap_t);
+    if (x.filter > (uint32_t)RT_TEX_BILINEAR) return fail(RT_ERR_INVALID, "textures: texture %u: filter %u is unknown", i, x.filter);
+    for (int k = 0; k < 3; ++k)
+      if (x.reserved[k]) return fail(RT_ERR_INVALID, "textures: texture %u: reserved[%d] is %u, not 0", i, k, x.reserved[k]);
+    if (!x.texels) return fail(RT_ERR_INVALID, "textures: texture %u: texels is null", i);
+    total += (uint64_t)x.width * x.height;
+    if (total > kTexMaxTexels) return fail(RT_ERR_INVALID, "textures: %llu texels up to texture %u, more than %llu", (unsigned long long)total, i, (unsigned long long)kTexMaxTexels);
+  }
+  for (uint32_t i = 0; i < t->n_textures; ++i) {
+    const rt_texture& x = t->textures[i];
+    const size_t n = 3 * (size_t)x.width * x.height;
+    for (size_t j = 0; j < n; ++j)
+      if (!std::isfinite(x.texels[j]))
+        return fail(RT_ERR_INVALID, "textures: texture %u: texels[%zu] (row %zu, column %zu, component %zu) is not finite", i, j,
+                    j / 3 / x.width, j / 3 % x.width, j % 3);
+  }
+  for (uint32_t m = 0; m < t->n_meshes; ++m)
+    if (t->mesh_texture[m] != RT_TEX_NONE && t->mesh_texture[m] >= t->n_textures)
+      return fail(RT_ERR_INVALID, "textures: mesh_texture[%u] is %u: neither one of %u textures nor RT_TEX_NONE", m, t->mesh_texture[m], t->n_textures);
+  for (size_t j = 0; j < 2 * (size_t)t->n_vertices; ++j)
+    if (!std::isfinite(t->vertex_uv[j]) || std::fabs(t->vertex_uv[j]) > kTexMaxUv)
+      return fail(RT_ERR_INVALID, "textures: vertex_uv[%zu] (vertex %zu, component %zu) is %g: not finite or beyond %g", j, j / 2, j % 2,
+                  (double)t->vertex_uv[j], (double)kTexMaxUv);
+  return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_set_textures(rt_ctx* c, const rt_texture_set* t) {
+  if (!t) {
+    if (!c) return fail(RT_ERR_INVALID, "ctx/textures is null");
+    HIP_TRY(hipSetDevice(c->device));
+    c->tex = rt_ctx::TexSet();
+    return RT_OK;
+  }
+  int rc = texture_set_checks(t);
+  if (rc != RT_OK) return rc;
+  if (!c) return fail(RT_ERR_INVALID, "ctx/textures is null");
+  if (t->n_meshes != c->nMeshes) return fail(RT_ERR_INVALID, "textures: %u meshes for a context of %u", t->n_meshes, c->nMeshes);
+  if (t->n_vertices != c->nVertices) return fail(RT_ERR_INVALID, "textures: %u vertices for a context of %u", t->n_vertices, c->nVertices);
+  if ((rc = check_not_broken(c)) != RT_OK) return rc;  // (as rt_set_vertex_colors: nothing is uploaded to a context that refuses launches)
+  HIP_TRY(hipSetDevice(c->device));
+  // the pool: every texture's texels one behind the other, and where each starts
+  std::vector<rtk::TexDesc> desc(t->n_textures);
+  size_t total = 0;
+  for (uint32_t i = 0; i < t->n_textures; ++i) {
+    const rt_texture& x = t->textures[i];
+    desc[i] = rtk::TexDesc{(uint32_t)total, x.width, x.height,
+                           (x.wrap_s == RT_TEX_CLAMP ? rtk::TEX_CLAMP_S : 0u) | (x.wrap_t == RT_TEX_CLAMP ? rtk::TEX_CLAMP_T : 0u) |
+                               (x.filter == RT_TEX_BILINEAR ? rtk::TEX_BILINEAR : 0u)};
+    total += (size_t)x.width * x.height;
+  }
+  // the new set replaces the old one only when all of it is resident; the old arrays are then freed under launches that
+  // may still read them, which hipFree waits for
+  rt_ctx::TexSet fresh;
+  HIP_TRY(dev_alloc(&fresh.texels, 3 * total));
+  for (uint32_t i = 0; i < t->n_textures; ++i)
+    HIP_TRY(hipMemcpy(fresh.texels.get() + 3 * (size_t)desc[i].offset, t->textures[i].texels,
+                      3 * sizeof(float) * (size_t)desc[i].width * desc[i].height, hipMemcpyHostToDevice));
+  if ((rc = upload(&fresh.uv, t->vertex_uv, 2 * (size_t)t->n_vertices)) != RT_OK ||
+      (rc = upload(&fresh.meshTex, t->mesh_texture, t->n_meshes)) != RT_OK || (rc = upload(&fresh.desc, desc.data(), desc.size())) != RT_OK)
+    return rc;
+  c->tex = std::move(fresh);
+  return RT_OK;
+}
+
+int rt_render_textured_device(rt_ctx* c, const rt_params* p, void* d_accum, void* stream, rt_stats* stats) {
+  rtk::TexRec R;
+  const int rc = textured_checks(c, p, d_accum ? nullptr : "d_accum is null", &R);
+  if (rc != RT_OK) return rc;
+  return frame_device(c, p, R, d_accum, stream, stats);
+}
+
+int rt_render_textured(rt_ctx* c, const rt_params* p, const float* bg, float* out_rgb, float* accum_out, rt_stats* stats) {
+  rtk::TexRec R;
+  const int rc = textured_checks(c, p, outputs_refused(bg, out_rgb, accum_out), &R);
   if (rc != RT_OK) return rc;
   return frame_host(c, p, R, 1, bg, out_rgb, accum_out, stats);
 }

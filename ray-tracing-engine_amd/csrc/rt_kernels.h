@@ -131,6 +131,8 @@ hipError_t launch_wavefront(const DevScene& S, const WfArgs& W, uint32_t mode, u
                             hipStream_t stream);
 // first-hit AOVs of a frame's primary rays (aov_kernels.h, rt_render_aov): sums over the samples [s0, s1) of every pixel;
 // null channels are not written
+struct TexDesc;  // (with TexRec, among the frame's variants below)
+struct TexRec;
 struct AovArgs {
   float *albedo, *normal, *position, *depth;  // [h][w][3], [h][w][3], [h][w][3], [h][w]
   uint32_t *hits, *mesh, *tri;                // [h][w] each
@@ -140,11 +142,19 @@ struct AovArgs {
   uint32_t tilesPerView = 0;
   // coloured launches only (launch_aov_colors sets it; the other instances do not read it)
   const float* vcol = nullptr;
+  // textured launches only (launch_aov_textured sets them; the other instances do not read them): TexRec's four tables
+  const float* texUv = nullptr;
+  const uint32_t* texMesh = nullptr;
+  const TexDesc* texDesc = nullptr;
+  const float* texels = nullptr;
 };
 hipError_t launch_aov(bool brute_force, const DevScene& S, const AovArgs& A, hipStream_t stream);
 // the same with the albedo channel summing the colour interpolated from vcol [n_vertices][3] at the first hit
 // (rt_render_aov_colors) instead of the mesh's albedo; instances of their own
 hipError_t launch_aov_colors(bool brute_force, const DevScene& S, const AovArgs& A, const float* vcol, hipStream_t stream);
+// the same with the albedo channel summing the texture sample at the first hit (rt_render_aov_textured; the mesh's albedo
+// on a mesh without a texture); instances of their own
+hipError_t launch_aov_textured(bool brute_force, const DevScene& S, const AovArgs& A, const TexRec& T, hipStream_t stream);
 // ambient occlusion and bent normals at the first hit (ao_kernels.h, rt_render_ao): per pixel, over the samples [s0, s1),
 // the occlusion rays that escaped, the hit samples, and the float32 sum of the escaped directions; null channels are not written
 struct AoArgs {
@@ -211,13 +221,28 @@ struct PickRec {
 struct VColRec {
   const float* vcol;  // [n_vertices][3]
 };
+// the frame with image-textured albedo (rt_render_textured): every shaded vertex of a mesh with a texture takes its
+// material's albedo from the texture's sample at the hit's interpolated uv (rt_amd.h's sampler); a mesh whose meshTex
+// entry is kTexNone shades with its own material.  All four tables are device memory the launch reads in stream order.
+// TexDesc is one 16-byte load: where the texture's texels start in the pool (in texels), its size and its wrap/filter bits.
+struct alignas(16) TexDesc {
+  uint32_t offset, width, height, bits;  // bits: TEX_CLAMP_S | TEX_CLAMP_T | TEX_BILINEAR
+};
+constexpr uint32_t TEX_CLAMP_S = 1u, TEX_CLAMP_T = 2u, TEX_BILINEAR = 4u;
+constexpr uint32_t kTexNone = 0xffffffffu;  // RT_TEX_NONE
+struct TexRec {
+  const float* uv;           // [n_vertices][2]
+  const uint32_t* meshTex;   // [n_meshes]: an index into desc, or kTexNone
+  const TexDesc* desc;       // [n_textures]
+  const float* texels;       // the pool: every texture's [height][width][3], one behind the other
+};
 // Which variant a frame is, with its record (which the caller keeps alive over the launch call).  VIEWS_SHUTTER, many
 // views each under its own open shutter (rt_render_views_shutter), has none: tile t renders with views[tileView[t]]'s
 // camera, seed and slice under viewShutters[tileView[t]], from RenderArgs' three tables.
 struct FrameVariant {
-  enum Kind { NONE, LENS, SHUTTER, LIGHTS, VIEWS_SHUTTER, PICK, VCOL };
+  enum Kind { NONE, LENS, SHUTTER, LIGHTS, VIEWS_SHUTTER, PICK, VCOL, TEX };
   Kind kind = NONE;
-  const void* rec = nullptr;  // the LensRec, ShutterRec, LightGroupsRec, PickRec or VColRec of kind, else null
+  const void* rec = nullptr;  // the LensRec, ShutterRec, LightGroupsRec, PickRec, VColRec or TexRec of kind, else null
   FrameVariant() = default;
   explicit FrameVariant(Kind k) : kind(k) {}
   FrameVariant(const LensRec& r) : kind(LENS), rec(&r) {}
@@ -225,10 +250,11 @@ struct FrameVariant {
   FrameVariant(const LightGroupsRec& r) : kind(LIGHTS), rec(&r) {}
   FrameVariant(const PickRec& r) : kind(PICK), rec(&r) {}
   FrameVariant(const VColRec& r) : kind(VCOL), rec(&r) {}
+  FrameVariant(const TexRec& r) : kind(TEX), rec(&r) {}
   explicit operator bool() const { return kind != NONE; }
   // the variant in an error message: "<name> render launch failed"
   const char* name() const {
-    static const char* const names[] = {"", "lens", "shutter", "light-group", "multi-view shutter", "light-pick", "vertex-colour"};
+    static const char* const names[] = {"", "lens", "shutter", "light-group", "multi-view shutter", "light-pick", "vertex-colour", "textured"};
     return names[kind];
   }
 };
@@ -236,7 +262,7 @@ struct FrameVariant {
 // NONE); A as launch_render takes it: tileView null, but for VIEWS_SHUTTER a multi-view frame's with the three tables
 // set.  LIGHTS: accum is [G.n][height][width], slice g at accum + g * width * height.  PICK: pooled whenever A.flags bit 0
 // is set, whatever the scene's light count (a vertex sends m <= POOL_L shadow rays).  VCOL: a launch allocates
-// VP_VCOL_WORDS more words of LDS per wave (the vertex's parked kdDiffuse).  hipErrorInvalidValue where A, the
+// VP_VCOL_WORDS more words of LDS per wave (the vertex's parked kdDiffuse), and so does TEX.  hipErrorInvalidValue where A, the
 // record or the scene's light count do not fit the variant.
 hipError_t launch_render_variant(const FrameVariant& F, bool brute_force, bool stats, const DevScene& S, const RenderArgs& A,
                                  float4* accum, unsigned long long* counters, hipStream_t stream);

@@ -237,6 +237,10 @@ constexpr int LT_PICK = 8192;
 // the colours of the hit triangle's three vertices; the vertex pool and shade_direct_seq shade with it in place of the
 // mesh's (their VC switch).
 constexpr int LT_VCOL = 16384;
+// A frame with image-textured albedo (rt_render_textured): render_tile takes a TexRec and forms every vertex's kdDiffuse
+// from the texture sample at the hit's uv (tex_kd); it reaches the vertex pool and shade_direct_seq as the coloured
+// frame's does (their VC switch, a second producer of VColKd::kd).
+constexpr int LT_TEX = 32768;
 constexpr uint32_t kPrioMaxNodes = 65536;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(3))) u32x4* lds_u4_ptr;
@@ -853,6 +857,62 @@ RT_DEV f3 parked_kd(const VColKd& vc, uint32_t lane) { return mk(vc.park[lane], 
 template <class VC>
 constexpr bool is_vcol = std::is_same_v<VC, VColKd>;
 
+// Image-textured albedo (rt_render_textured, rt_amd.h's sampler).  gfx950 has no image instructions: a sample is plain
+// loads and float32 arithmetic, every operation rounded on its own.
+// tex_wrap: the texel index of the integer coordinate i on an axis of n texels — REPEAT: the non-negative remainder,
+// ((i % n) + n) % n; CLAMP: min(max(i, 0), n - 1).
+RT_DEV int tex_wrap(int i, int n, bool clamp) {
+  if (clamp) return min(max(i, 0), n - 1);
+  const int r = i % n;
+  return r < 0 ? r + n : r;
+}
+// the sample of texture D at (s, t).  int(floorf(.)) stays far inside int32: |uv| <= 1024 at the vertices and u, v in
+// [0, 1] give |s| <= 1024 + 2 * 2048 = 5120, and 5120 * 16384 + 1 < 2^27.  The bilinear filter samples row by row (a, then
+// b): six texel floats are live at most.
+RT_DEV f3 tex_sample(const float* __restrict__ texels, TexDesc D, float s, float t) {
+  const int W = (int)D.width, H = (int)D.height;
+  const bool cs = (D.bits & TEX_CLAMP_S) != 0, ct = (D.bits & TEX_CLAMP_T) != 0;
+  const float* base = texels + 3 * (size_t)D.offset;
+  if (!(D.bits & TEX_BILINEAR)) {
+    const int i = tex_wrap((int)floorf(s * (float)W), W, cs), j = tex_wrap((int)floorf(t * (float)H), H, ct);
+    return ld(base + 3 * ((size_t)j * (size_t)W + (size_t)i));
+  }
+  const float x = s * (float)W - 0.5f, y = t * (float)H - 0.5f;
+  const float xf = floorf(x), yf = floorf(y);
+  const float fx = x - xf, fy = y - yf;
+  const int i0 = tex_wrap((int)xf, W, cs), i1 = tex_wrap((int)xf + 1, W, cs);
+  const int j0 = tex_wrap((int)yf, H, ct), j1 = tex_wrap((int)yf + 1, H, ct);
+  const float* r0 = base + 3 * (size_t)j0 * (size_t)W;
+  const float* r1 = base + 3 * (size_t)j1 * (size_t)W;
+  const f3 t00 = ld(r0 + 3 * i0), t01 = ld(r0 + 3 * i1);
+  const f3 a = t00 + fx * (t01 - t00);
+  const f3 t10 = ld(r1 + 3 * i0), t11 = ld(r1 + 3 * i1);
+  const f3 b = t10 + fx * (t11 - t10);
+  return a + fy * (b - a);
+}
+// the hit's texture coordinate on one axis, vertex_color's form: three equal values give s0 exactly
+RT_DEV float tex_coord(float s0, float s1, float s2, float u, float v) { return (s0 + u * (s1 - s0)) + v * (s2 - s0); }
+// The albedo a vertex of a textured frame shades with: the sample of its mesh's texture at the hit's uv, or (no texture)
+// the mesh's own.  found: the mesh has a texture.  The three uv gathers and the mesh's texture index are independent of
+// each other and go out together.
+RT_DEV f3 tex_color(const TexRec& T, uint4 tv, float u, float v, bool& found) {
+  const float2* uv = reinterpret_cast<const float2*>(T.uv);
+  const uint32_t ti = T.meshTex[tv.w];
+  const float2 a = uv[tv.x], b = uv[tv.y], c = uv[tv.z];
+  found = ti != kTexNone;
+  if (!found) return mk(0.f, 0.f, 0.f);
+  const TexDesc D = T.desc[ti];
+  return tex_sample(T.texels, D, tex_coord(a.x, b.x, c.x, u, v), tex_coord(a.y, b.y, c.y, u, v));
+}
+// ... and the kdDiffuse: vertex_kd's two operations on the sample; a mesh without a texture keeps its DevMat's
+RT_DEV f3 tex_kd(const DevScene& S, const TexRec& T, uint4 tv, float u, float v) {
+  bool found;
+  const f3 c = tex_color(T, tv, u, v, found);
+  if (!found) return ld(S.matsDev[tv.w].kdDiffuse);
+  const f3 diffuse = c / 3.14159274f;  // c / float(M_PI)
+  return S.mats[tv.w].kd * diffuse;
+}
+
 // Renderer.cpp:63-104: photon-map radiance estimate at the vertex (HP: the heap's layout, WideHeap for k > 16)
 template <bool STATS, class HP = Heap>
 RT_DEV f3 shade_photon(const DevScene& S, const RenderArgs& A, f3 rayDir, const HitRec& h, const Lds& L, f3 hitNormal,
@@ -1454,15 +1514,16 @@ RT_DEV void group_samples_add(const RenderArgs& A, const LightGroupsRec& G, floa
 
 // The record a frame variant's instances take as a kernel argument of their own, by its LT_* bits: the lens, the shutter
 // of a single-view frame (a multi-view one reads its records from RenderArgs' tables), the light groups, the light
-// picks, the vertex colours — or none.  park: (LT_VCOL) the wave's three parked rows of LDS (VColKd), from the kernel
-// that lays its LDS out.
+// picks, the vertex colours, the textures — or none.  park: (LT_VCOL, LT_TEX) the wave's three parked rows of LDS
+// (VColKd), from the kernel that lays its LDS out.
 struct NoRec {};
 template <int LTV>
 using frame_rec_t = std::conditional_t<(LTV & LT_LENS) != 0, LensRec,
                     std::conditional_t<(LTV & LT_LIGHTS) != 0, LightGroupsRec,
                     std::conditional_t<(LTV & LT_PICK) != 0, PickRec,
                     std::conditional_t<(LTV & LT_VCOL) != 0, VColRec,
-                    std::conditional_t<(LTV & LT_SHUTTER) != 0 && (LTV & LT_VIEWS) == 0, ShutterRec, NoRec>>>>>;
+                    std::conditional_t<(LTV & LT_TEX) != 0, TexRec,
+                    std::conditional_t<(LTV & LT_SHUTTER) != 0 && (LTV & LT_VIEWS) == 0, ShutterRec, NoRec>>>>>>;
 // (what the instances without a record leave out; the others do not compile without theirs)
 template <int LTV>
 constexpr const frame_rec_t<LTV>* no_record() {
@@ -1474,14 +1535,16 @@ template <bool BRUTE, bool PHOTON, bool POOLED, bool STATS, int LTV, class HP = 
 RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restrict__ accum, const Lds& L, uint32_t* pool,
                         float* ex, uint32_t wave, LaneStats& st, const frame_rec_t<LTV>* rec = no_record<LTV>(),
                         float* park = nullptr) {
-  constexpr int LT = LTV & ~(LT_VIEWS | LT_LENS | LT_SHUTTER | LT_LIGHTS | LT_PICK | LT_VCOL);
+  constexpr int LT = LTV & ~(LT_VIEWS | LT_LENS | LT_SHUTTER | LT_LIGHTS | LT_PICK | LT_VCOL | LT_TEX);
   constexpr bool VIEWS = (LTV & LT_VIEWS) != 0;
   constexpr bool LENS = (LTV & LT_LENS) != 0;
   constexpr bool SHUTTER = (LTV & LT_SHUTTER) != 0;
   constexpr bool LIGHTS = (LTV & LT_LIGHTS) != 0;
   constexpr bool PICK = (LTV & LT_PICK) != 0;
   constexpr bool VCOL = (LTV & LT_VCOL) != 0;
+  constexpr bool TEX = (LTV & LT_TEX) != 0;
   static_assert(!VCOL || (!VIEWS && !LENS && !SHUTTER && !LIGHTS && !PICK && !PHOTON), "vertex colours go with the plain frame only");
+  static_assert(!TEX || (!VIEWS && !LENS && !SHUTTER && !LIGHTS && !PICK && !VCOL && !PHOTON), "textures go with the plain frame only");
   static_assert(!LIGHTS || (!VIEWS && !LENS && !SHUTTER && !PHOTON), "light groups go with the plain frame only");
   static_assert(!PICK || (!VIEWS && !LENS && !SHUTTER && !LIGHTS && !PHOTON), "light picks go with the plain frame only");
   static_assert(!LENS || !VIEWS, "no multi-view lens frames");
@@ -1559,7 +1622,7 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
         const bool bounce = A.mode == RT_MODE_PATH && depth + 1 < nvert;  // wave-uniform
         f3 nrm = mk(0.f, 0.f, 0.f), pt = nrm, bdir = nrm;
         uint32_t mesh = 0;
-        VColKd vk{nrm, park};  // (LT_VCOL) the vertex's kdDiffuse
+        VColKd vk{nrm, park};  // (LT_VCOL, LT_TEX) the vertex's kdDiffuse
         // (the vertex set-up is three dependent loads deep: it goes out ahead of other waves'
         // arithmetic, like the pool loop that follows; +0.4 % on C2)
         if (!(LT & LT_NOPRIO)) __builtin_amdgcn_s_setprio(1);
@@ -1569,6 +1632,13 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
             float u, v;
             vertex_setup_ray<FR>(S, h.id, o, d, nrm, pt, tv, u, v);
             mesh = tv.w, vk.kd = vertex_kd(S, rec->vcol, tv, u, v);
+          }
+        } else if constexpr (TEX) {
+          if (alive) {
+            uint4 tv;
+            float u, v;
+            vertex_setup_ray<FR>(S, h.id, o, d, nrm, pt, tv, u, v);
+            mesh = tv.w, vk.kd = tex_kd(S, *rec, tv, u, v);
           }
         } else
         if (alive) vertex_setup_ray<FR>(S, h.id, o, d, nrm, pt, mesh);
@@ -1591,8 +1661,8 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
         } else if constexpr (PICK) {
           static_assert(!SHADOW_BODY, "the light-pick instances keep their trees in HBM / L2");
           c = vertex_pool<STATS, LT, true, false, PickArgs>(S, alive, bounce, g, d, mesh, nrm, pt, bdir, L.stack, pool, nh, nfound, st, nullptr, nullptr, PickArgs{rec, pk});
-        } else if constexpr (VCOL) {
-          static_assert(!SHADOW_BODY, "the coloured instances keep their trees in HBM / L2");
+        } else if constexpr (VCOL || TEX) {
+          static_assert(!SHADOW_BODY, "the coloured and textured instances keep their trees in HBM / L2");
           c = vertex_pool<STATS, LT, true, false, NoPick, VColKd>(S, alive, bounce, g, d, mesh, nrm, pt, bdir, L.stack, pool, nh, nfound, st, nullptr, nullptr, NoPick(), vk);
         } else
         c = SHADOW_BODY && !bounce
@@ -1633,6 +1703,10 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
         if (alive)
           c = shade_direct_seq<BRUTE, STATS, false, NoPick, VColKd>(S, g, d, h, L.stack, nrm, pt, st, nullptr, nullptr, NoPick(),
                                                                     VColKd{vertex_kd(S, rec->vcol, S.triShade[h.id], h.u, h.v), park});
+      } else if constexpr (TEX) {
+        if (alive)
+          c = shade_direct_seq<BRUTE, STATS, false, NoPick, VColKd>(S, g, d, h, L.stack, nrm, pt, st, nullptr, nullptr, NoPick(),
+                                                                    VColKd{tex_kd(S, *rec, S.triShade[h.id], h.u, h.v), park});
       } else {
         if (alive) c = shade_direct_seq<BRUTE, STATS>(S, g, d, h, L.stack, nrm, pt, st);
       }
@@ -1893,7 +1967,7 @@ __global__ __launch_bounds__(1024, 8) void k_trace_stream(DevScene S, const floa
 #include "rays_kernels.h"
 
 // ---------------------------------------------------------------- the frame's generator variants (rt_render_lens,
-// rt_render_shutter, rt_render_views_shutter, rt_render_lights, rt_render_pick, rt_render_colors)
+// rt_render_shutter, rt_render_views_shutter, rt_render_lights, rt_render_pick, rt_render_colors, rt_render_textured)
 #include "frame_variants.h"
 
 // ---------------------------------------------------------------- frame assembly (multi-GPU)

@@ -90,6 +90,7 @@ struct GpuSettings {
   bool lightsEach = false;            // also one frame per light (rt_render_lights: Renderer::lightGroups(); single device, plain frames only) ...
   std::vector<unsigned> lightMasks;   // ... or one per mask of lights (bit l: light l is lit); at most RT_LIGHT_GROUPS_MAX groups
   bool vcolors = false;               // shade with the meshes' per-vertex colours where any mesh has them (rt_render_colors; single device, plain frames only)
+  bool textures = false;              // shade the meshes that have texture coordinates and a <stem>.ppm beside their .off with that image (rt_render_textured; single device, plain frames only)
   unsigned lightPick = 0;             // > 0: the frame with this many sampled lights per path vertex (rt_render_pick; single device, plain frames only)
   std::vector<int> devices;  // more than one entry: Renderer::render tile-shards the frame over them (rt_group)
   static GpuSettings& get() {

@@ -151,6 +151,15 @@ int main(int argc, char** argv) {
     }
     GpuSettings::get().vcolors = true;
   }
+  if (args.textures() != 0) {
+    // -textures 1: the frame with the images beside the scene's STOFF meshes as albedo, and nothing else
+    if (GpuSettings::get().devices.size() > 1 || args.numPhotons() > 0 || args.adaptive() >= 0. || !args.shutter().empty() ||
+        args.aperture() > 0. || !args.lights().empty() || args.lightPick() != 0 || args.vcolors() != 0) {
+      std::cerr << "error: -textures runs on one GPU, without -p, -adaptive, -shutter, -aperture, -lights, -lightpick and -vcolors" << std::endl;
+      return 1;
+    }
+    GpuSettings::get().textures = true;
+  }
   if (args.adaptive() >= 0.) {
     if (GpuSettings::get().devices.size() > 1) {
       std::cerr << "error: -adaptive runs on one GPU only (not with -gpus > 1)" << std::endl;

@@ -4,16 +4,36 @@
 #include "Renderer.h"
 
 #include <algorithm>
+#include <fstream>
 #include <iostream>
 #include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
+#include "Texture.h"
+
 // does any mesh carry per-vertex colours (a COFF file)?
 inline bool sceneHasVertexColors(const Scene& scene) {
   for (const Mesh& m : scene.meshes())
     if (!m.vertexColors().empty() && m.vertexColors().size() == m.vertexPositions().size()) return true;
+  return false;
+}
+
+// The image -textures gives a mesh: <stem>.ppm beside the .off it was loaded from, if the mesh has texture coordinates
+// and that file can be opened ("" otherwise).
+inline std::string meshTextureFile(const Mesh& m) {
+  if (m.vertexUVs().empty() || m.vertexUVs().size() != 2 * m.vertexPositions().size()) return "";
+  const std::string& off = m.sourceFile();
+  const size_t dot = off.rfind('.'), slash = off.find_last_of("/\\");
+  if (dot == std::string::npos || (slash != std::string::npos && dot < slash)) return "";
+  const std::string ppm = off.substr(0, dot) + ".ppm";
+  return std::ifstream(ppm.c_str()) ? ppm : "";
+}
+
+inline bool sceneHasTextures(const Scene& scene) {
+  for (const Mesh& m : scene.meshes())
+    if (!meshTextureFile(m).empty()) return true;
   return false;
 }
 
@@ -88,6 +108,7 @@ inline void Renderer::render(Image& image) {
 
   Image result(w, h);
   bool colouredFrame = false;  // the frame went through rt_render_colors: its AOVs' albedo is the interpolated colour
+  bool texturedFrame = false;  // the frame went through rt_render_textured: its AOVs' albedo is the texture sample
   if (p.spp > 0 && multi) {
     // N devices: the whole frame in one sharded launch per device (rt_group_render);
     // update.ppm is written once, after the last pass
@@ -199,6 +220,42 @@ inline void Renderer::render(Image& image) {
     std::cout << "Raytracing with the vertex colours of " << colored << " of " << m_scene.meshes().size() << " meshes... ["
               << std::string(50, '#') << "] 100%" << std::endl;
     image = result;
+  } else if (p.spp > 0 && GpuSettings::get().textures && sceneHasTextures(m_scene)) {
+    // -textures 1 (extension): the frame with image-textured albedo (rt_render_textured), in one launch: every mesh with
+    // texture coordinates (an STOFF file) and a <stem>.ppm beside its .off samples that image, bilinear and repeating on
+    // both axes; the other meshes stay untextured and shade as they always did.  update.ppm is written once.  Without
+    // -textures, or where no mesh has a texture, this branch is not taken.
+    if (multi || p.use_photons) throw std::runtime_error("-textures runs on one GPU, without -p");
+    std::vector<TextureImage> images;
+    std::vector<rt_texture> textures;
+    std::vector<uint32_t> meshTexture;
+    std::vector<float> uv;
+    for (const Mesh& m : m_scene.meshes()) {
+      const std::string file = meshTextureFile(m);
+      meshTexture.push_back(file.empty() ? RT_TEX_NONE : static_cast<uint32_t>(images.size()));
+      if (!file.empty()) images.push_back(TextureImage::loadPPM(file));
+      // (the coordinates of a mesh without a texture are never read)
+      if (m.vertexUVs().size() == 2 * m.vertexPositions().size()) uv.insert(uv.end(), m.vertexUVs().begin(), m.vertexUVs().end());
+      else uv.insert(uv.end(), 2 * m.vertexPositions().size(), 0.f);
+    }
+    for (const TextureImage& t : images) {
+      rt_texture x = {};
+      x.width = t.width, x.height = t.height, x.wrap_s = x.wrap_t = RT_TEX_REPEAT, x.filter = RT_TEX_BILINEAR, x.texels = t.texels.data();
+      textures.push_back(x);
+    }
+    rt_texture_set set = {};
+    set.n_textures = static_cast<uint32_t>(textures.size()), set.n_meshes = static_cast<uint32_t>(meshTexture.size());
+    set.n_vertices = static_cast<uint32_t>(uv.size() / 2);
+    set.textures = textures.data(), set.mesh_texture = meshTexture.data(), set.vertex_uv = uv.data();
+    GpuSession::check(rt_set_textures(ctx0, &set), "rt_set_textures");
+    rt_stats st = {};
+    GpuSession::check(rt_render_textured(ctx0, &p, image.data(), result.data(), nullptr, &st), "rt_render_textured");
+    texturedFrame = true;
+    m_stats = st;
+    result.savePPM("update.ppm");
+    std::cout << "Raytracing with the textures of " << images.size() << " of " << m_scene.meshes().size() << " meshes... ["
+              << std::string(50, '#') << "] 100%" << std::endl;
+    image = result;
   } else if (p.spp > 0) {
     // The reference re-saves update.ppm after EVERY pass (Renderer.cpp:261-269).  Here a
     // "pass" is a sample range of one launch; GpuSettings::progress = P > 0 renders P
@@ -223,7 +280,7 @@ inline void Renderer::render(Image& image) {
   }
 
   // -aov / -denoise (extensions): the first-hit AOVs of this frame's primary rays (rt_render_aov; of a coloured frame
-  // rt_render_aov_colors, whose albedo channel is the colour the frame shaded with) and the a-trous filter of the frame
+  // rt_render_aov_colors, of a textured one rt_render_aov_textured: the albedo channel is the colour the frame shaded with) and the a-trous filter of the frame
   // guided by them (rt_denoise).  The frame itself stays as it is.
   const bool wantAov = GpuSettings::get().aov, wantDenoise = GpuSettings::get().denoise;
   if ((wantAov || wantDenoise) && multi) throw std::runtime_error("-aov / -denoise run on one GPU only (not with -gpus > 1)");
@@ -235,6 +292,7 @@ inline void Renderer::render(Image& image) {
     rt_aov aov = {};
     aov.albedo = alb.data(), aov.normal = nrm.data(), aov.position = pos.data(), aov.hits = hits.data();
     if (colouredFrame) GpuSession::check(rt_render_aov_colors(ctx0, &p, &aov), "rt_render_aov_colors");
+    else if (texturedFrame) GpuSession::check(rt_render_aov_textured(ctx0, &p, &aov), "rt_render_aov_textured");
     else GpuSession::check(rt_render_aov(ctx0, &p, &aov), "rt_render_aov");
     if (wantAov) {  // the means (sum / hits; 0 where no sample hit)
       m_albedo = Image(w, h), m_normal = Image(w, h);

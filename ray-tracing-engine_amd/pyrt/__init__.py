@@ -172,6 +172,52 @@ class Aov(C.Structure):
                 ("hits", C.c_void_p), ("mesh", C.c_void_p), ("tri", C.c_void_p), ("reserved", C.c_uint32 * 4)]
 
 
+TEX_NONE = 0xffffffff
+TEX_REPEAT, TEX_CLAMP = 0, 1
+TEX_NEAREST, TEX_BILINEAR = 0, 1
+TEX_MAX_SIDE, TEX_MAX_UV, TEX_MAX_TEXELS = 16384, 1024.0, 1 << 28
+
+
+class Texture(C.Structure):
+    """rt_texture."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("wrap_s", C.c_uint32), ("wrap_t", C.c_uint32),
+                ("filter", C.c_uint32), ("reserved", C.c_uint32 * 3), ("texels", C.c_void_p)]
+
+
+class TextureSet(C.Structure):
+    """rt_texture_set."""
+    _fields_ = [("n_textures", C.c_uint32), ("n_meshes", C.c_uint32), ("n_vertices", C.c_uint32),
+                ("textures", C.POINTER(Texture)), ("mesh_texture", C.c_void_p), ("vertex_uv", C.c_void_p),
+                ("reserved", C.c_uint32 * 4)]
+
+
+def texture_set(textures, mesh_texture, vertex_uv):
+    """The rt_texture_set of Context.set_textures' arguments, and the arrays it points into (keep them alive while the
+    structure is in use)."""
+    recs = (Texture * max(len(textures), 1))()
+    keep = [recs]
+    for k, t in enumerate(textures):
+        if isinstance(t, dict):
+            t = (t["texels"], t.get("wrap_s", TEX_REPEAT), t.get("wrap_t", TEX_REPEAT), t.get("filter", TEX_BILINEAR))
+        elif not isinstance(t, tuple):
+            t = (t, TEX_REPEAT, TEX_REPEAT, TEX_BILINEAR)
+        texels = np.ascontiguousarray(t[0], np.float32)
+        if texels.ndim != 3 or texels.shape[2] != 3:
+            raise ValueError("texture %d: texels must be [h][w][3], not %r" % (k, texels.shape))
+        keep.append(texels)
+        recs[k].height, recs[k].width = texels.shape[0], texels.shape[1]
+        recs[k].wrap_s, recs[k].wrap_t, recs[k].filter = t[1], t[2], t[3]
+        recs[k].texels = texels.ctypes.data
+    mt = np.ascontiguousarray(mesh_texture, np.uint32).reshape(-1)
+    uv = np.ascontiguousarray(vertex_uv, np.float32).reshape(-1, 2)
+    keep += [mt, uv]
+    ts = TextureSet()
+    ts.n_textures, ts.n_meshes, ts.n_vertices = len(textures), len(mt), len(uv)
+    ts.textures = C.cast(recs, C.POINTER(Texture))
+    ts.mesh_texture, ts.vertex_uv = mt.ctypes.data, uv.ctypes.data
+    return ts, keep
+
+
 AO_MAX_RAYS = 256
 
 
@@ -424,7 +470,9 @@ AMD_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_create", "rt_destroy", "rt
                "rt_render_shutter_device", "rt_render_views_shutter", "rt_render_views_shutter_device",
                "rt_render_adaptive_shutter", "rt_render_adaptive_shutter_device", "rt_render_lights",
                "rt_render_lights_device", "rt_render_pick", "rt_render_pick_device", "rt_set_vertex_colors",
-               "rt_render_colors", "rt_render_colors_device", "rt_render_aov_colors", "rt_render_aov_colors_device"]
+               "rt_render_colors", "rt_render_colors_device", "rt_render_aov_colors", "rt_render_aov_colors_device",
+               "rt_set_textures", "rt_render_textured", "rt_render_textured_device", "rt_render_aov_textured",
+               "rt_render_aov_textured_device"]
 HOST_SYMBOLS = ["rt_host_scene_build", "rt_host_scene_desc", "rt_host_scene_free", "rt_host_last_error",
                 "rt_host_fill_background", "rt_host_save_ppm", "rt_host_kd_order", "rt_host_light_basis"]
 
@@ -564,6 +612,11 @@ def amd():
         L.rt_set_vertex_colors.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         L.rt_render_colors.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         L.rt_render_colors_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        L.rt_render_aov_textured.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Aov)]
+        L.rt_render_aov_textured_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Aov), C.c_void_p]
+        L.rt_set_textures.argtypes = [C.c_void_p, C.POINTER(TextureSet)]
+        L.rt_render_textured.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        L.rt_render_textured_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         L.rt_render_ao.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(AoParams), C.POINTER(Ao)]
         L.rt_render_ao_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(AoParams), C.POINTER(Ao), C.c_void_p]
         L.rt_render_rays.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(RayBatch), C.c_void_p, C.c_void_p, C.c_void_p,
@@ -1011,11 +1064,12 @@ class Context:
         _check(amd().rt_trace(self._h, _ptr(rays), len(rays), accel, kind, _ptr(hits)))
         return hits
 
-    def render_aov(self, params, raw=False, channels=AOV_CHANNELS, colors=False):
+    def render_aov(self, params, raw=False, channels=AOV_CHANNELS, colors=False, textured=False):
         """rt_render_aov: first-hit AOVs of the frame `params` describes, as a dict of numpy arrays ([h][w][3] albedo,
         normal, position; [h][w] depth, hits, mesh, tri).  The means (sum / hits, 0 where hits == 0); raw=True: the
         sums rt_render_aov returns.  `channels`: the ones wanted (the others are not computed).  colors:
-        rt_render_aov_colors, whose albedo channel is the interpolated vertex colour."""
+        rt_render_aov_colors, whose albedo channel is the interpolated vertex colour; textured: rt_render_aov_textured,
+        whose albedo channel is the texture sample."""
         w, h = params.width, params.height
         if not raw and "hits" not in channels:
             channels = tuple(channels) + ("hits",)  # (the means divide by it)
@@ -1025,16 +1079,18 @@ class Context:
             arr = np.zeros((h, w, 3) if k in AOV_FLOAT3 else (h, w), np.float32 if k in AOV_FLOAT3 or k == "depth" else np.uint32)
             sums[k] = arr
             setattr(a, k, arr.ctypes.data)
-        _check((amd().rt_render_aov_colors if colors else amd().rt_render_aov)(self._h, C.byref(params), C.byref(a)))
+        f = amd().rt_render_aov_textured if textured else amd().rt_render_aov_colors if colors else amd().rt_render_aov
+        _check(f(self._h, C.byref(params), C.byref(a)))
         return sums if raw else aov_means(sums)
 
-    def render_aov_device(self, params, ptrs, stream=0, colors=False):
+    def render_aov_device(self, params, ptrs, stream=0, colors=False, textured=False):
         """rt_render_aov_device: the sums into device buffers; ptrs = {channel: device pointer} (missing = not wanted).
-        colors: rt_render_aov_colors_device."""
+        colors: rt_render_aov_colors_device; textured: rt_render_aov_textured_device."""
         a = Aov()
         for k, v in ptrs.items():
             setattr(a, k, v or None)
-        f = amd().rt_render_aov_colors_device if colors else amd().rt_render_aov_device
+        f = (amd().rt_render_aov_textured_device if textured else amd().rt_render_aov_colors_device if colors
+             else amd().rt_render_aov_device)
         _check(f(self._h, C.byref(params), C.byref(a), C.c_void_p(stream or None)))
 
     def render_aov_colors(self, params, raw=False, channels=AOV_CHANNELS):
@@ -1071,6 +1127,44 @@ class Context:
         st = Stats() if stats else None
         _check(amd().rt_render_colors_device(self._h, C.byref(params), C.c_void_p(d_accum), C.c_void_p(stream or None),
                                              C.byref(st) if stats else None))
+        return st
+
+    def render_aov_textured(self, params, raw=False, channels=AOV_CHANNELS):
+        """rt_render_aov_textured: render_aov with the albedo channel from the resident textures."""
+        return self.render_aov(params, raw, channels, textured=True)
+
+    def render_aov_textured_device(self, params, ptrs, stream=0):
+        """rt_render_aov_textured_device: render_aov_device with the albedo channel from the resident textures."""
+        self.render_aov_device(params, ptrs, stream, textured=True)
+
+    def set_textures(self, textures, mesh_texture=None, vertex_uv=None):
+        """rt_set_textures: the set becomes resident (copied); set_textures(None) releases it.  textures: a list whose
+        entries are an [h][w][3] float array (repeat, bilinear) or a dict(texels=..., wrap_s=, wrap_t=, filter=) or a tuple
+        (texels, wrap_s, wrap_t, filter); mesh_texture [n_meshes]: a texture index or TEX_NONE; vertex_uv
+        [n_vertices][2] by global vertex id."""
+        if textures is None:
+            _check(amd().rt_set_textures(self._h, None))
+            return
+        ts, keep = texture_set(textures, mesh_texture, vertex_uv)
+        _check(amd().rt_set_textures(self._h, C.byref(ts)))
+
+    def render_textured(self, params, bg=None, want_accum=True):
+        """rt_render_textured: the frame with the resident textures as albedo; returns (out [h][w][3] or None without
+        bg, accum [h][w][4] or None, stats)."""
+        w, h = params.width, params.height
+        out = np.empty((h, w, 3), np.float32) if bg is not None else None
+        acc = np.empty((h, w, 4), np.float32) if want_accum else None
+        st = Stats()
+        bgc = None if bg is None else np.ascontiguousarray(bg, np.float32)
+        _check(amd().rt_render_textured(self._h, C.byref(params), _ptr(bgc), _ptr(out), _ptr(acc), C.byref(st)))
+        return out, acc, st
+
+    def render_textured_device(self, params, d_accum, stream=0, stats=False):
+        """rt_render_textured_device: accumulate into the caller-zeroed device d_accum [h][w][4] on `stream`; sample
+        ranges chain."""
+        st = Stats() if stats else None
+        _check(amd().rt_render_textured_device(self._h, C.byref(params), C.c_void_p(d_accum), C.c_void_p(stream or None),
+                                               C.byref(st) if stats else None))
         return st
 
     @staticmethod
