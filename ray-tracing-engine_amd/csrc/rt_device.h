@@ -282,7 +282,12 @@ RT_DEV f3 bsdf_eval(const rt_material& m, f3 normal, f3 wi_in, f3 wo_in) {
 // Ray.cpp:9-24 on a flattened record (p0, e1 = p1-p0, e2 = p2-p0 precomputed with
 // the same float subtraction the reference performs per test).
 // (the part of the test behind the reciprocal of the determinant)
-RT_DEV bool tri_finish(f3 o, f3 d, f3 p0, f3 e1, f3 e2, f3 pvec, float det, float inv, float& u, float& v, float& t) {
+// `masks` (a compile-time constant at every call site): the four comparisons are all evaluated and combined bitwise — the
+// same booleans, each comparison's NaN behaviour included.  With && the compiler guards the later comparisons with nested
+// exec-mask regions (one holds a v_add and a v_cmp); the pair test of the pooled kernel's two-record-leaf instances
+// (rt_kernels.hip Trav::test_pair, KEYED) is 0.9 % of a C2 frame faster without them (profiles/leaf_accept/).  The other
+// callers keep the && form they were measured with.
+RT_DEV bool tri_finish(f3 o, f3 d, f3 p0, f3 e1, f3 e2, f3 pvec, float det, float inv, float& u, float& v, float& t, bool masks = false) {
   f3 tvec = o - p0;
   u = dot3(tvec, pvec) * inv;
   f3 qvec = cross3(tvec, e1);
@@ -290,11 +295,12 @@ RT_DEV bool tri_finish(f3 o, f3 d, f3 p0, f3 e1, f3 e2, f3 pvec, float det, floa
   t = dot3(e2, qvec) * inv;
   const bool detOk = !(fabsf(det) < 0.000001f);
   const bool uOk = !(u < 0.f || u > 1.f);
+  if (masks) return (bool)((int)detOk & (int)uOk & (int)(v >= 0.f) & (int)(u + v <= 1.f));
   return detOk && uOk && v >= 0.f && u + v <= 1.f;
 }
 // `divide` (a compile-time constant at every call site) = this kernel instance's rays are not known to keep |det| below
 // 2^100 (rt_kernels.hip LT_FASTDET): 1 / det by the division.
-RT_DEV bool tri_test(f3 o, f3 d, f3 p0, f3 e1, f3 e2, float& u, float& v, float& t, bool divide) {
+RT_DEV bool tri_test(f3 o, f3 d, f3 p0, f3 e1, f3 e2, float& u, float& v, float& t, bool divide, bool masks = false) {
   // Branch-free form: the reference returns early when |det| < EPSILON or u is out of
   // range; here everything is evaluated (a zero det just yields inf/NaN values that
   // the combined predicate discards) so that a wave never splits inside the test.
@@ -305,7 +311,7 @@ RT_DEV bool tri_test(f3 o, f3 d, f3 p0, f3 e1, f3 e2, float& u, float& v, float&
   // create_ctx: longest edge^2 x longest ray direction < 2^100; a determinant below recip_fast's range is below
   // EPSILON too and rejected whatever inv holds), the division otherwise.  Same bits either way.
   const float inv = divide ? 1.0f / det : recip_fast(det);
-  return tri_finish(o, d, p0, e1, e2, pvec, det, inv, u, v, t);
+  return tri_finish(o, d, p0, e1, e2, pvec, det, inv, u, v, t, masks);
 }
 // Same test with the reference's early exits (leaves u, v, t untouched exactly where
 // Ray.cpp:9-24 does) — the unit-test hook compares those side effects too.

@@ -254,6 +254,7 @@ struct Trav {
   static constexpr bool DIVIDE = (LTX & LT_FASTDET) == 0;
   static constexpr bool Q8 = (LTX & LT_Q8) != 0;
   static constexpr bool LEAF2 = (LTX & LT_LEAF2) != 0;
+  static constexpr bool KEYED = LEAF2;  // test_pair accepts by one compare of hit_key (see there)
   static_assert(!Q8 || LT == LT_NONE, "Q8 records are fetched from HBM / L2");
   // any-hit rays enter child 0 (the smaller box) first: the big-scene instances and the whole-tree-in-LDS ones (measured:
   // C5 -2.5 %, C5x8 -1.9 %, C2 -0.7 %, C1 -3 %; the partial-top instance of C4 loses 0.7 % to the extra scalar op and keeps
@@ -471,25 +472,47 @@ struct Trav {
   // acceptance is a select (RayTracer.h:40's rule applied to A, then to B), so the leaf
   // phase stays one basic block instead of a dozen exec-mask regions.  `two` = the leaf
   // holds a second record (else B is a re-read of A and is ignored).
+  // That sentence is the intent; what the compiler makes of `ta < best || (ta == best && ida < bestId)` is an exec-mask
+  // region per short-circuit operand, each around one or two vector instructions (about 100 lines of assembly for A and B).
+  // KEYED instances therefore state the SAME rule as one unsigned compare of hit_key — the order publish and refresh_best
+  // keep — with the booleans combined bitwise, and take tri_test's predicate as masks too (C2 -1.1 %: DESIGN.md §4.3,
+  // profiles/leaf_accept/).  Why the keys order as the rule does: ha / hb contain t > 0, so an accepted t is a positive
+  // float and no NaN; best is FLT_MAX, an accepted t or a published key's t (and, were a general instance keyed,
+  // ao_occluded's finite maxDistance > 0) — never negative, never -0, never NaN.  Positive floats order as their bit
+  // patterns do and equal ones have equal bits, so kA < k0 is the rule for every candidate that ha lets through; the key
+  // of a rejected one may hold anything (NaN, negative t), and its mask discards it (tests/test_leaf_accept_rule.py).
+  // KEYED is the LT_LEAF2 instances, which it was measured in; the others keep the text and the registers they had (keyed,
+  // k_ao<false, true> would lose a wave per SIMD and some counted instances spill more).
   template <bool STATS>
   RT_DEV bool test_pair(const float4& p0, const float4& p1, const float4& p2, const float4& q0, const float4& q1,
                         const float4& q2, bool two, LaneStats& st) {
     if (STATS) st.tris += two ? 2u : 1u;
     float ua, va, ta, ub, vb, tb;
-    const bool ha = tri_test(o, d, mk(p0.x, p0.y, p0.z), mk(p0.w, p1.x, p1.y), mk(p1.z, p1.w, p2.x), ua, va, ta, DIVIDE) && ta > 0.f;
-    const bool hb = tri_test(o, d, mk(q0.x, q0.y, q0.z), mk(q0.w, q1.x, q1.y), mk(q1.z, q1.w, q2.x), ub, vb, tb, DIVIDE) && tb > 0.f && two;
+    const bool ha = tri_test(o, d, mk(p0.x, p0.y, p0.z), mk(p0.w, p1.x, p1.y), mk(p1.z, p1.w, p2.x), ua, va, ta, DIVIDE, KEYED) && ta > 0.f;
+    const bool hb = tri_test(o, d, mk(q0.x, q0.y, q0.z), mk(q0.w, q1.x, q1.y), mk(q1.z, q1.w, q2.x), ub, vb, tb, DIVIDE, KEYED) && tb > 0.f && two;
     const bool isAny = MODE == TRAV_ANY || (MODE == TRAV_MIXED && anyHit);
     const uint32_t ida = __float_as_uint(p2.y), idb = __float_as_uint(q2.y);
-    const bool ba = !isAny && ha && (ta < best || (ta == best && ida < bestId));
-    const float b1 = ba ? ta : best;
-    const uint32_t i1 = ba ? ida : bestId;
-    const bool bb = !isAny && hb && (tb < b1 || (tb == b1 && idb < i1));
-    best = bb ? tb : b1, bestId = bb ? idb : i1;
+    bool ba, bb;
+    if constexpr (KEYED) {
+      const unsigned long long k0 = hit_key(best, bestId), kA = hit_key(ta, ida), kB = hit_key(tb, idb);
+      ba = (bool)((int)!isAny & (int)ha & (int)(kA < k0));
+      const unsigned long long k1 = ba ? kA : k0;
+      bb = (bool)((int)!isAny & (int)hb & (int)(kB < k1));
+      const unsigned long long k2 = bb ? kB : k1;
+      best = __uint_as_float((uint32_t)(k2 >> 32)), bestId = (uint32_t)k2;
+    } else {
+      ba = !isAny && ha && (ta < best || (ta == best && ida < bestId));
+      const float b1 = ba ? ta : best;
+      const uint32_t i1 = ba ? ida : bestId;
+      bb = !isAny && hb && (tb < b1 || (tb == b1 && idb < i1));
+      best = bb ? tb : b1, bestId = bb ? idb : i1;
+    }
     if (MODE == TRAV_CLOSEST) {  // (pool mode recomputes u, v from the id: vertex_setup_ray)
       hit.u = bb ? ub : ba ? ua : hit.u, hit.v = bb ? vb : ba ? va : hit.v;
       hit.mesh = bb ? __float_as_uint(q2.z) : ba ? __float_as_uint(p2.z) : hit.mesh;
     }
     hit.t = best, hit.id = bestId;
+    // (these three as mask arithmetic too were measured and lose: profiles/leaf_accept/)
     found = found || (isAny ? (ha || hb) : (ba || bb));
     if (MODE == TRAV_MIXED && shared && (ba || bb)) publish();
     return isAny && (ha || hb);
@@ -517,10 +540,12 @@ struct Trav {
     return false;
   }
 
+  // the order of hits as one unsigned number: t bits << 32 | triangle id
+  static RT_DEV unsigned long long hit_key(float t, uint32_t id) { return ((unsigned long long)__float_as_uint(t) << 32) | id; }
+
   // pool mode: make this lane's closest hit visible to the other lanes / the pixel lane
   RT_DEV void publish() {
-    const unsigned long long key = ((unsigned long long)__float_as_uint(hit.t) << 32) | hit.id;
-    atomicMin(sharedKey + (int32_t)pj, key);
+    atomicMin(sharedKey + (int32_t)pj, hit_key(hit.t, hit.id));
   }
 
   // pool mode: adopt a closer hit another lane has published for the same ray
