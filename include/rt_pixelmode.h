@@ -104,13 +104,17 @@ RT_HD double rt_asin(double x) {
   double ax = x < 0.0 ? -x : x;
   if (!(ax <= 1.0)) return rt_u2d(0x7ff8000000000000ull); /* NaN, also for NaN input */
   if (ax == 1.0) return x * pio2_hi + x * pio2_lo;
-  if (ax < 0.5) {
-    if (ax < 7.450580596923828125e-09) return x; /* 2^-27 */
-    return x + x * rt_asin_poly(x * x);
-  }
+  /* one polynomial and one quotient for both arms: the argument is selected first (the same
+   * operations on the same operands per value as a call in each arm, so the same bits; a device
+   * wave would otherwise issue both arms' polynomials and quotients for every lane) */
+  const int small = ax < 0.5;
   double w = 1.0 - ax;
-  double t = w * 0.5;
+  double t = small ? x * x : w * 0.5;
   double r = rt_asin_poly(t);
+  if (small) {
+    if (ax < 7.450580596923828125e-09) return x; /* 2^-27 */
+    return x + x * r;
+  }
   double s = rt_sqrt_d(t);
   double res;
   if (ax >= 0.975) {

@@ -27,6 +27,7 @@
 #include "filters.h"
 #include "rt_amd.h"
 #include "rt_kernels.h"
+#include "wave_tiles.h"
 
 namespace {
 
@@ -231,19 +232,10 @@ int use_on(const StreamList& L, hipStream_t stream) {
   return RT_OK;
 }
 
-struct TileKey {
-  uint32_t w = 0, h = 0, rank = 0, world = 0, tile = 0, sshift = 0;
-  bool operator==(const TileKey& o) const {
-    return w == o.w && h == o.h && rank == o.rank && world == o.world && tile == o.tile && sshift == o.sshift;
-  }
-};
-
-// A wave integrates (64 >> sshift) pixels x (1 << sshift) samples at a time.  Pixel
-// footprint of one wave for sshift = 0..6: 8x8, 8x4, 4x4, 4x2, 2x2, 2x1, 1x1.
-void wave_tile_shape(uint32_t sshift, uint32_t& tw, uint32_t& th) {
-  static const uint32_t W[7] = {8, 8, 4, 4, 2, 2, 1}, H[7] = {8, 4, 4, 2, 2, 1, 1};
-  tw = W[sshift], th = H[sshift];
-}
+using rtl::owned_granules;
+using rtl::TileKey;
+using rtl::wave_tile_shape;
+using rtl::wave_tiles;
 
 constexpr int kEventPairs = 256;
 
@@ -270,6 +262,7 @@ struct rt_ctx {
   DevBuf<uint4> phTopo;  // explicit kd topology over phPos (rtk::launch_kd_topology)
   StreamList tiles;  // the frame's wave tiles, for tileKey
   TileKey tileKey;
+  uint32_t tilesFineFrom = 0;  // index of the list's first fine item (== tiles.n: none)
   DevBuf<unsigned long long> dCounters;
   DevBuf<uint32_t> dTileCounter;  // work queue head of the persistent render kernel
   // owned-granule lists of the ranks of a tile-sharded frame (multi-GPU assembly), by key
@@ -463,18 +456,6 @@ uint32_t choose_sshift(const rt_ctx* c, const rt_params* p, uint32_t spp_count, 
   return choose_sshift_px(c, p, (uint64_t)p->width * p->height / world, spp_count, pick);
 }
 
-// f(x8, y8) for each 8x8-pixel granule rank `rank` of `world` owns, row-major — the order ensure_tiles
-// renders them in and the order of the packed exchange buffer.
-template <class F>
-void owned_granules(uint32_t w, uint32_t h, uint32_t rank, uint32_t world, uint32_t tile, F f) {
-  if (tile == 0) tile = 8;
-  if (world == 0) world = 1;
-  const uint32_t gx = (w + 7) / 8, gy = (h + 7) / 8;
-  for (uint32_t y8 = 0; y8 < gy; ++y8)
-    for (uint32_t x8 = 0; x8 < gx; ++x8)
-      if (world <= 1 || (x8 * 8 / tile + y8 * 8 / tile) % world == rank) f(x8, y8);
-}
-
 TileKey tile_key(const rt_params* p, uint32_t sshift) {
   TileKey k;
   k.w = p->width, k.h = p->height, k.rank = p->rank, k.world = p->world ? p->world : 1;
@@ -482,25 +463,30 @@ TileKey tile_key(const rt_params* p, uint32_t sshift) {
   k.sshift = sshift;
   return k;
 }
-// the wave tiles inside each owned granule, row-major, so that consecutive waves touch neighbouring pixels
-std::vector<uint32_t> wave_tiles(const TileKey& k) {
-  std::vector<uint32_t> tiles;
-  uint32_t tw, th;
-  wave_tile_shape(k.sshift, tw, th);
-  owned_granules(k.w, k.h, k.rank, k.world, k.tile, [&](uint32_t x8, uint32_t y8) {
-    for (uint32_t y = y8 * 8; y < y8 * 8 + 8 && y < k.h; y += th)
-      for (uint32_t x = x8 * 8; x < x8 * 8 + 8 && x < k.w; x += tw) tiles.push_back(x | (y << 16));
-  });
-  return tiles;
+
+// fine, sshiftFine: the list's fine tail (TileKey); 0: none
+int ensure_tiles(rt_ctx* c, const rt_params* p, uint32_t sshift, hipStream_t stream, uint32_t fine = 0, uint32_t sshiftFine = 0) {
+  TileKey k = tile_key(p, sshift);
+  if (fine && sshiftFine > sshift) k.fine = fine, k.sshiftFine = sshiftFine;
+  if (c->tiles.d && k == c->tileKey) return use_on(c->tiles, stream);
+  uint32_t from = 0;
+  const int rc = stream_upload(&c->tiles, wave_tiles(k, &from), stream);
+  if (rc != RT_OK) return rc;
+  c->tileKey = k, c->tilesFineFrom = from;
+  return RT_OK;
 }
 
-int ensure_tiles(rt_ctx* c, const rt_params* p, uint32_t sshift, hipStream_t stream) {
-  const TileKey k = tile_key(p, sshift);
-  if (c->tiles.d && k == c->tileKey) return use_on(c->tiles, stream);
-  const int rc = stream_upload(&c->tiles, wave_tiles(k), stream);
-  if (rc != RT_OK) return rc;
-  c->tileKey = k;
-  return RT_OK;
+// How many coarse tiles of a plain frame's list are split for the end of the launch: one per wave the device holds at
+// once (rtk::persist_fine_waves: 0 where the frame does not run in k_render_persist; measured on C2 at 0 / 1 / 2 / 4 per
+// wave: 42.83 / 42.63 / 42.67 / 42.72 ms, profiles/fine_tail/).  RT_FINE_TAIL, read per launch: 0 none, n that many,
+// "all" the whole list.
+uint32_t fine_tail_tiles(uint32_t waves) {
+  if (!waves) return 0;
+  const char* const e = getenv("RT_FINE_TAIL");
+  if (!e || !*e) return waves;
+  if (!strcmp(e, "all")) return ~0u;
+  const long n = atol(e);
+  return n <= 0 ? 0u : (uint32_t)std::min<long>(n, 0x7fffffff);
 }
 
 int ensure_granules(rt_ctx* c, const rt_params* p, uint32_t rank, hipStream_t stream, const rt_ctx::GranList** out) {
@@ -703,12 +689,10 @@ int launch_frame(rt_ctx* c, const rt_params* p, float4* dAccum, hipStream_t stre
                  const TileList* own = nullptr, const FrameGen& gen = FrameGen()) {
   const SampleRange sr = sample_range(*p);
   const uint32_t sshift = own ? own->sshift : choose_sshift(c, p, sr.count, gen.kind == FrameGen::PICK);
-  int rc = own ? RT_OK : ensure_tiles(c, p, sshift, stream);
-  if (rc != RT_OK) return rc;
+  int rc = RT_OK;
   rtk::RenderArgs A;
   A.sshift = sshift;
   wave_tile_shape(sshift, A.tileW, A.tileH);
-  A.tiles = own ? own->tiles : c->tiles.d.get(), A.n_tiles = own ? own->n : c->tiles.n;
   A.tileView = own ? own->tileView : nullptr, A.views = own ? own->views : nullptr;
   A.viewShutters = own ? own->viewShutters : nullptr;
   A.width = p->width, A.height = p->height, A.spp = p->spp;
@@ -734,6 +718,15 @@ int launch_frame(rt_ctx* c, const rt_params* p, float4* dAccum, hipStream_t stre
   // rt_params.reserved[2] bit 0: the queue-based (wavefront) integrator — BVH direct lighting with
   // at most 3 lights, like the pooled kernel; same frame bit for bit
   const bool wavefront = (p->reserved[2] & 1u) && !p->use_photons && p->accel != RT_ACCEL_BRUTE && c->S.n_lights <= 3u;
+  // The wave tiles: the caller's, or the context's list — with a fine tail where the plain frame runs in k_render_persist:
+  // the same pixels at up to four times the samples per wave (<= 64, and no more than the launch has: choose_sshift_px's rule)
+  uint32_t fine = 0, sshiftFine = std::min(6u, sshift + 2u);
+  while (sshiftFine > sshift && (1u << sshiftFine) > sr.count) --sshiftFine;
+  if (!own && !gen && !wavefront)
+    fine = fine_tail_tiles(rtk::persist_fine_waves(p->accel == RT_ACCEL_BRUTE, p->use_photons != 0, c->S, A));
+  if (!own && (rc = ensure_tiles(c, p, sshift, stream, fine, sshiftFine)) != RT_OK) return rc;
+  A.tiles = own ? own->tiles : c->tiles.d.get(), A.n_tiles = own ? own->n : c->tiles.n;
+  A.fineFrom = own ? A.n_tiles : c->tilesFineFrom, A.sshiftFine = own ? sshift : c->tileKey.sshiftFine;
   rtk::WfArgs W{};
   if (wavefront && (rc = wavefront_args(c, p, A, sr.count, stream, &W)) != RT_OK) return rc;
   return timed_launch(c, stream, evIndex, [&] {

@@ -104,8 +104,15 @@ struct RenderArgs {
   const ViewRec* views;
   // multi-view shutter frames (rt_render_views_shutter): the views' shutter records, indexed as views; else null
   const ViewShutterRec* viewShutters;
+  // the fine tail of a plain single-view frame's list (k_render_persist): items [fineFrom, n_tiles) are the last coarse
+  // tiles' pixels again at sshiftFine >= sshift — more samples of fewer pixels side by side, so shorter items — for the
+  // end of the launch, where every wave is inside its last item.  fineFrom == n_tiles: none (every other launch).
+  uint32_t fineFrom = ~0u, sshiftFine = 0;
 };
 
+// Waves the device holds at once if launch_render runs this frame in k_render_persist, the kernel that takes a fine tail;
+// 0 if it runs in another kernel (k_render, k_render_persist5, k_render_wide), whose lists have none.
+uint32_t persist_fine_waves(bool brute_force, bool photon, const DevScene& S, const RenderArgs& A);
 hipError_t launch_render(bool brute_force, bool photon, bool stats, const DevScene& S, const RenderArgs& A,
                          float4* accum, unsigned long long* counters, hipStream_t stream);
 hipError_t launch_resolve(uint32_t n_pixels, uint32_t spp, const float4* accum, const float* bg, float* out,

@@ -1556,7 +1556,9 @@ constexpr const frame_rec_t<LTV>* no_record() {
   return nullptr;
 }
 
-template <bool BRUTE, bool PHOTON, bool POOLED, bool STATS, int LTV, class HP = Heap>
+// FINE (k_render_persist's plain single-view instances): the list may end in a fine tail (RenderArgs::fineFrom), whose items
+// take their samples per wave and their footprint from A.sshiftFine: wave-uniform values, read once per item here.
+template <bool BRUTE, bool PHOTON, bool POOLED, bool STATS, int LTV, class HP = Heap, bool FINE = false>
 RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restrict__ accum, const Lds& L, uint32_t* pool,
                         float* ex, uint32_t wave, LaneStats& st, const frame_rec_t<LTV>* rec = no_record<LTV>(),
                         float* park = nullptr) {
@@ -1603,10 +1605,18 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
       vsh.open = Q->open, vsh.close = Q->close, vsh.aperture = Q->aperture, vsh.fs0 = Q->fs0, vsh.dfs = Q->dfs;
     }
   }
-  const uint32_t S_ = 1u << A.sshift, P_ = 64u >> A.sshift;
-  const uint32_t pl = lane & (P_ - 1u), sj = lane >> (6u - A.sshift);
-  const uint32_t wsh = (uint32_t)__builtin_ctz(A.tileW);
-  const uint32_t px = (tile & 0xffffu) + (pl & (A.tileW - 1u)), py = (tile >> 16) + (pl >> wsh);
+  uint32_t sshift = A.sshift, tileW = A.tileW;
+  if constexpr (FINE) {
+    static_assert(POOLED && LTV == LT, "the fine tail goes with the plain pooled frame only");
+    if (wave >= A.fineFrom) {
+      // (the footprints of rt_api.cpp wave_tile_shape: 8, 8, 4, 4, 2, 2, 1 pixels wide)
+      sshift = A.sshiftFine, tileW = 8u >> (A.sshiftFine >> 1);
+    }
+  }
+  const uint32_t S_ = 1u << sshift, P_ = 64u >> sshift;
+  const uint32_t pl = lane & (P_ - 1u), sj = lane >> (6u - sshift);
+  const uint32_t wsh = (uint32_t)__builtin_ctz(tileW);
+  const uint32_t px = (tile & 0xffffu) + (pl & (tileW - 1u)), py = (tile >> 16) + (pl >> wsh);
   const bool inImage = px < A.width && py < A.height;
   const bool owner = inImage && sj == 0;  // adds this pixel's samples, in order
   const uint32_t pix = inImage ? py * A.width + px : 0u;
@@ -1759,7 +1769,7 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
     }
     const f3 total = c0 + (c1 + (c2 + mk(0.f, 0.f, 0.f)));
     const float r0 = clamp01(total.x), r1 = clamp01(total.y), r2 = clamp01(total.z);
-    if (A.sshift == 0) {
+    if (sshift == 0) {
       if (active) {
         sum.x += r0, sum.y += r1, sum.z += r2;
         if (primary) sum.w += 1.f;
@@ -1832,7 +1842,7 @@ __global__ __launch_bounds__(BLOCK, MINW) void k_render_wide(DevScene S, RenderA
 // left — so a CU never idles behind a slow neighbour wave, and the node fetches of the
 // upper tree levels (all of them for the 1.2k-triangle scene) never touch the vector L1.
 // Waves never synchronise with each other after the tree copy.
-template <bool STATS, int LT>
+template <bool STATS, int LT, bool FINE = false>
 RT_DEV void persist_body(const DevScene& S, const RenderArgs& A, float4* __restrict__ accum, unsigned long long* __restrict__ counters) {
   const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
   {
@@ -1857,7 +1867,7 @@ RT_DEV void persist_body(const DevScene& S, const RenderArgs& A, float4* __restr
     if (lane == 0) t = atomicAdd(A.tileCounter, 1u);
     t = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
     if (t >= A.n_tiles) break;
-    render_tile<false, false, true, STATS, LT>(S, A, accum, L, pool, ex, t, st);
+    render_tile<false, false, true, STATS, LT, Heap, FINE>(S, A, accum, L, pool, ex, t, st);
   }
 #ifdef RT_PHASE_TIMING
   __syncthreads();
@@ -1869,7 +1879,7 @@ RT_DEV void persist_body(const DevScene& S, const RenderArgs& A, float4* __restr
 template <bool STATS, int LT>
 __global__ __launch_bounds__(1024) void k_render_persist(DevScene S, RenderArgs A, float4* __restrict__ accum,
                                                          unsigned long long* __restrict__ counters) {
-  persist_body<STATS, LT>(S, A, accum, counters);
+  persist_body<STATS, LT, (LT & LT_VIEWS) == 0>(S, A, accum, counters);
 }
 // The same for the trees that leave the LDS to the stacks (LT_COMPACT3: the 424-word pool): workgroups of FOUR waves, one per
 // SIMD, five of them per CU — 20 waves at 96 VGPRs (the compiler spills 28 registers, outside the descent: 1.4 % at equal
@@ -2408,13 +2418,26 @@ static hipError_t launch_render_wide(bool stats, const DevScene& S, const Render
   return hipGetLastError();
 }
 
+static bool persist_wanted(const RenderArgs& A) {
+  static const bool noPersist = getenv("RT_NO_PERSIST") != nullptr;
+  return !noPersist && A.tileCounter && A.numCUs;
+}
+static bool pool_wanted(const DevScene& S, const RenderArgs& A) { return (A.flags & 1u) && S.n_lights <= (uint32_t)POOL_L; }
+
+uint32_t persist_fine_waves(bool brute_force, bool photon, const DevScene& S, const RenderArgs& A) {
+  if (brute_force || photon || !pool_wanted(S, A) || !persist_wanted(A) || A.tileView) return 0;
+  const PersistPlan P = plan_persist(S, A);
+  return P.compact == 3 ? 0u : P.waves * A.numCUs;  // (the four-wave flavour keeps the coarse list)
+}
+
 template <bool BRUTE, bool PHOTON, bool POOLED>
 static hipError_t launch_render2(bool stats, const DevScene& S, const RenderArgs& A, float4* accum,
                                  unsigned long long* counters, hipStream_t stream) {
   const uint32_t blocks = A.n_tiles;
   if (blocks == 0) return hipSuccess;
-  static const bool noPersist = getenv("RT_NO_PERSIST") != nullptr;
-  if (POOLED && !noPersist && A.tileCounter && A.numCUs) {
+  // (a list with a fine tail is k_render_persist's alone: persist_fine_waves says 0 for every other launch)
+  if (A.fineFrom < A.n_tiles && !(POOLED && persist_fine_waves(false, false, S, A))) return hipErrorInvalidValue;
+  if (POOLED && persist_wanted(A)) {
     const PersistPlan P = plan_persist(S, A);
     if (P.waves) {
       DevScene S2 = S;
@@ -2518,7 +2541,7 @@ hipError_t launch_render(bool brute_force, bool photon, bool stats, const DevSce
                                  : launch_render2<true, false, false>(stats, S, A, accum, counters, stream);
   if (photon) return launch_render2<false, true, false>(stats, S, A, accum, counters, stream);
   // direct lighting through the BVH: the vertex pool handles up to POOL_L lights
-  if ((A.flags & 1u) && S.n_lights <= (uint32_t)POOL_L) return launch_render2<false, false, true>(stats, S, A, accum, counters, stream);
+  if (pool_wanted(S, A)) return launch_render2<false, false, true>(stats, S, A, accum, counters, stream);
   return launch_render2<false, false, false>(stats, S, A, accum, counters, stream);
 }
 
