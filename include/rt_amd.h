@@ -1343,6 +1343,54 @@ int rt_denoise_batch(rt_ctx* ctx, const rt_denoise_params* d, uint32_t n_frames,
 int rt_denoise_batch_device(rt_ctx* ctx, const rt_denoise_params* d, uint32_t n_frames, const void* d_rgb, const rt_aov* d_aov,
                             void* d_out, void* stream);
 
+/* ---- vertex colours and textures under the lens, the shutter and many views ---------------------------
+ * rt_render_views_shutter_albedo is rt_render_views_shutter with the albedo of every shaded vertex taken from the
+ * context's resident vertex colours or texture set.  Since rt_render_views_shutter is the general camera form (one view
+ * is a single frame; camera_close == cameras[j], open == close == 0 and aperture > 0 is a pure lens; a record that
+ * changes nothing is rt_render_views), this one call gives a coloured or textured scene depth of field, motion blur,
+ * many cameras per launch and every mixture of them. */
+#define RT_ALBEDO_MATERIAL 0u   /* the meshes' own albedo: the call is the parent form                 */
+#define RT_ALBEDO_COLORS   1u   /* the resident vertex colours (rt_set_vertex_colors), rt_render_colors' rule */
+#define RT_ALBEDO_TEXTURES 2u   /* the resident texture set (rt_set_textures), rt_render_textured's sampler   */
+/* Every sample of view j is generated exactly as rt_render_views_shutter generates it: steps 1 to 6 of the
+ * rt_render_shutter contract with seeds[j] (p->seed when seeds is NULL), a pixel index local to the view, and the per-view
+ * host-derived constants.  Every ray, the hit selection, both ray counts, the clamp and the accumulation are that form's.
+ * The only change is at each shaded vertex: with RT_ALBEDO_COLORS, `albedo` is rt_render_colors' interpolated colour;
+ * with RT_ALBEDO_TEXTURES it is rt_render_textured's sample, or the mesh's own albedo on an RT_TEX_NONE mesh; in both
+ * cases kdDiffuse = kd * (albedo / float(M_PI)) in the two float32 operations those forms use.
+ * Guarantees (all bit for bit: accumulator words and both ray counts):
+ *   - X1, slices: slice j is what the same call leaves for n_views == 1, cameras[j], seeds[j], shutters[j].
+ *   - X2, no optics: with n_views == 1, cameras[0] equal to the context's camera with no -0 component (the condition V2
+ *     and V4 rest on) and a record that changes nothing, the call is rt_render_colors_device / rt_render_textured_device.
+ *   - X3, no surface: RT_ALBEDO_MATERIAL is rt_render_views_shutter itself (the same kernels); vertex colours equal to
+ *     each mesh's albedo on all of its vertices give that frame too (rt_render_colors' C1), and so do texels all equal to
+ *     each mesh's albedo (rt_render_textured's T1).
+ *   - X4, faces: on a vertex-split scene with one strip texel per triangle (T2), or per-face colours, the frame is
+ *     rt_render_views_shutter of the one-mesh-per-triangle scene under the same views and shutters.
+ *   - X5, schedule: sample ranges chain; reserved[0] and reserved[1] bit 0 never change the bits; RT_ACCEL_BRUTE gives the
+ *     frame of the tree; an RT_NODES_Q8 context gives the frame of a default context.
+ * Validation comes first and a rejected call writes nothing.  The order is rt_render_views_shutter's with two additions:
+ * albedo > 2 is RT_ERR_INVALID among the checks the arguments alone decide (after the outputs, before p), ahead of the
+ * device; and after the device and rt_render_views_shutter's checks of the context, RT_ERR_STATE when albedo names data the
+ * context does not hold (no resident vertex colours, no resident texture set), with rt_render_colors' / rt_render_textured's
+ * messages.  world > 1, use_photons, the wavefront bit and the legacy RNG are refused as by rt_render_views_shutter.
+ * Buffers, stats and the device form's synchronisation are rt_render_views_shutter's; the resident colours or textures
+ * are read in stream order, as by rt_render_colors_device / rt_render_textured_device.  Not combined (each its own form):
+ * adaptive passes, light groups, light picks, ray batches, rt_group, textures and colours at once, motion vectors. */
+int rt_render_views_shutter_albedo(rt_ctx* ctx, const rt_params* p, const rt_views* v, const rt_shutter* shutters,
+                                   uint32_t albedo, const float* background_rgb, float* out_rgb, float* accum_out,
+                                   rt_stats* stats);
+int rt_render_views_shutter_albedo_device(rt_ctx* ctx, const rt_params* p, const rt_views* v, const rt_shutter* shutters,
+                                          uint32_t albedo, void* d_accum, void* stream, rt_stats* stats);
+/* rt_render_aov_views whose albedo channel sums what rt_render_aov_colors / rt_render_aov_textured sum: slice j of every
+ * non-NULL channel is, bit for bit, the single-view coloured or textured AOV call for the same p on this context after a
+ * camera-only rt_update to cameras[j], with seeds[j].  All other channels are rt_render_aov_views'; RT_ALBEDO_MATERIAL is
+ * rt_render_aov_views itself.  Validation is rt_render_aov_views' with albedo > 2 (RT_ERR_INVALID) after the null and
+ * reserved-word checks, and RT_ERR_STATE for data the context does not hold after the device and the context's checks. */
+int rt_render_aov_views_albedo(rt_ctx* ctx, const rt_params* p, const rt_views* v, uint32_t albedo, const rt_aov* host_out);
+int rt_render_aov_views_albedo_device(rt_ctx* ctx, const rt_params* p, const rt_views* v, uint32_t albedo,
+                                      const rt_aov* device_out, void* stream);
+
 /* ---- multi-GPU (Renderer.cpp:219-265 sharded by pixel tiles) -------------
  * A tile-sharded frame: rank r of `world` integrates the pixels whose `tile`-pixel granule
  * (tx + ty) mod world == r (rt_params.rank/world/tile) into its own zeroed full-frame

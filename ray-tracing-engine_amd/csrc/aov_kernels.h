@@ -36,6 +36,7 @@ RT_DEV ViewOfWave view_of_wave(const ViewRec* views, uint32_t tilesPerView) {
 // instead of the mesh's albedo; the other instances do not read A.vcol and are the kernels they were before it existed.
 // TEX (rt_render_aov_textured): the albedo channel sums the sample of the hit mesh's texture (tex_color), or the mesh's
 // albedo where it has none, from A's four tex* tables; the other instances do not read them.
+// VIEWS with VCOL or TEX (rt_render_aov_views_albedo): both at once, each as above.
 template <bool BRUTE, bool VIEWS, bool VCOL = false, bool TEX = false>
 __global__ __launch_bounds__(64) void k_aov(DevScene S, AovArgs A) {
   __shared__ uint32_t lds[(rtbvh::kMaxDepth + 1) * 64];
@@ -136,5 +137,26 @@ hipError_t launch_aov_views(bool brute_force, const DevScene& S, const AovArgs& 
   if ((uint64_t)V.tilesPerView * nViews > 0x7fffffffull) return hipErrorInvalidValue;  // (a tile holds a pixel: n w h < 2^31 keeps it below)
   if (brute_force) hipLaunchKernelGGL((k_aov<true, true>), dim3(V.tilesPerView * nViews), dim3(64), 0, stream, S, V);
   else hipLaunchKernelGGL((k_aov<false, true>), dim3(V.tilesPerView * nViews), dim3(64), 0, stream, S, V);
+  return hipGetLastError();
+}
+
+hipError_t launch_aov_views_albedo(bool brute_force, const DevScene& S, const AovArgs& A, const ViewRec* views, uint32_t nViews,
+                                   const float* vcol, const TexRec* T, hipStream_t stream) {
+  if ((vcol != nullptr) == (T != nullptr)) return hipErrorInvalidValue;
+  if (T && (!T->uv || !T->meshTex || !T->desc || !T->texels)) return hipErrorInvalidValue;
+  AovArgs V = A;
+  V.views = views, V.tilesPerView = ((A.width + 7u) / 8u) * ((A.height + 7u) / 8u);
+  if (V.tilesPerView == 0 || nViews == 0 || A.s1 <= A.s0) return hipSuccess;
+  if ((uint64_t)V.tilesPerView * nViews > 0x7fffffffull) return hipErrorInvalidValue;  // (as launch_aov_views)
+  const dim3 grid(V.tilesPerView * nViews);
+  if (vcol) {
+    V.vcol = vcol;
+    if (brute_force) hipLaunchKernelGGL((k_aov<true, true, true, false>), grid, dim3(64), 0, stream, S, V);
+    else hipLaunchKernelGGL((k_aov<false, true, true, false>), grid, dim3(64), 0, stream, S, V);
+  } else {
+    V.texUv = T->uv, V.texMesh = T->meshTex, V.texDesc = T->desc, V.texels = T->texels;
+    if (brute_force) hipLaunchKernelGGL((k_aov<true, true, false, true>), grid, dim3(64), 0, stream, S, V);
+    else hipLaunchKernelGGL((k_aov<false, true, false, true>), grid, dim3(64), 0, stream, S, V);
+  }
   return hipGetLastError();
 }

@@ -1,6 +1,7 @@
 // frame_variants.h — the frame integrator with another generator, another split of its samples or another light list:
 // rt_render_lens, rt_render_shutter, rt_render_views_shutter, rt_render_lights (DESIGN.md §6m–§6p), rt_render_pick (§6r)
-// and, with another albedo at every vertex, rt_render_colors (§6t) and rt_render_textured (§6u).
+// and, with another albedo at every vertex, rt_render_colors (§6t), rt_render_textured (§6u) and both under the multi-view
+// shutter's generator, rt_render_views_shutter_albedo (§6v).
 //
 // Every variant is render_tile itself under one more LT_* bit, on the one-wave-per-workgroup family that k_render serves:
 // brute, sequential and pooled, each counted (STATS, one wave per SIMD) and timed (four waves per SIMD, k_render's target);
@@ -29,6 +30,11 @@
 //   textures      LT_TEX                 TexRec: every shaded vertex of a mesh with a texture forms its kdDiffuse from
 //                                        the texture's sample at the hit's uv (tex_kd) and shades with it through the
 //                                        same VC switch and the same parked rows as a coloured frame's
+//   views+shutter+colours   LT_VIEWS | LT_SHUTTER | LT_VCOL   VColRec: the camera side of the views+shutter row (the
+//   views+shutter+textures  LT_VIEWS | LT_SHUTTER | LT_TEX    TexRec   three tables of RenderArgs) and the surface side of
+//                                        the colour / texture row (the record, the parked rows) in one instance; the
+//                                        two meet nowhere in render_tile: the sample's primary ray is complete before
+//                                        the first vertex reads the record
 // A new variant supplies a row of the same kind (a struct below, a FrameVariant kind, a case in launch_render_variant):
 // its LT_* bits, its record, the stack rows its sample hand-over needs, and its argument check.
 // (included by rt_kernels.hip inside namespace rtk: shares its device functions)
@@ -114,6 +120,23 @@ struct VariantViewsShutter {
   static bool refused(const DevScene&, const RenderArgs& A, const Rec&) { return !A.tileView || !A.views || !A.viewShutters; }
 };
 
+// The surface rows under the multi-view shutter's generator (rt_render_views_shutter_albedo): VariantViewsShutter's
+// tables and VariantVCol's / VariantTex's record, rows and parked words.
+struct VariantViewsShutterVCol {
+  static constexpr int LTV = LT_VIEWS | LT_SHUTTER | LT_VCOL;
+  using Rec = VColRec;
+  static constexpr uint32_t ROWS = 4, ROWS_POOLED = 4;
+  static bool refused(const DevScene&, const RenderArgs& A, const Rec& R) { return !A.tileView || !A.views || !A.viewShutters || !R.vcol; }
+};
+struct VariantViewsShutterTex {
+  static constexpr int LTV = LT_VIEWS | LT_SHUTTER | LT_TEX;
+  using Rec = TexRec;
+  static constexpr uint32_t ROWS = 4, ROWS_POOLED = 4;
+  static bool refused(const DevScene&, const RenderArgs& A, const Rec& R) {
+    return !A.tileView || !A.views || !A.viewShutters || !R.uv || !R.meshTex || !R.desc || !R.texels;
+  }
+};
+
 template <class V, bool BRUTE, bool POOLED, bool STATS, int MINW>
 static void launch_variant_instance(size_t ldsBytes, hipStream_t stream, const DevScene& S, const RenderArgs& A,
                                     const typename V::Rec& R, float4* accum, unsigned long long* counters) {
@@ -172,6 +195,10 @@ hipError_t launch_render_variant(const FrameVariant& F, bool brute_force, bool s
       return launch_variant<VariantTex>(brute_force, stats, S, A, *static_cast<const TexRec*>(F.rec), accum, counters, stream);
     case FrameVariant::VIEWS_SHUTTER:
       return launch_variant<VariantViewsShutter>(brute_force, stats, S, A, NoRec(), accum, counters, stream);
+    case FrameVariant::VIEWS_SHUTTER_VCOL:
+      return launch_variant<VariantViewsShutterVCol>(brute_force, stats, S, A, *static_cast<const VColRec*>(F.rec), accum, counters, stream);
+    case FrameVariant::VIEWS_SHUTTER_TEX:
+      return launch_variant<VariantViewsShutterTex>(brute_force, stats, S, A, *static_cast<const TexRec*>(F.rec), accum, counters, stream);
     case FrameVariant::NONE: break;
   }
   return hipErrorInvalidValue;  // (the plain frame is launch_render's)

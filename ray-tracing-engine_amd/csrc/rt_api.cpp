@@ -730,7 +730,8 @@ int launch_frame(rt_ctx* c, const rt_params* p, float4* dAccum, hipStream_t stre
   rtk::WfArgs W{};
   if (wavefront && (rc = wavefront_args(c, p, A, sr.count, stream, &W)) != RT_OK) return rc;
   return timed_launch(c, stream, evIndex, [&] {
-    if (const FrameGen V = A.viewShutters ? FrameGen(FrameGen::VIEWS_SHUTTER) : gen) {
+    // (a multi-view shutter frame keeps the surface record of a coloured or textured gen: rt_render_views_shutter_albedo)
+    if (const FrameGen V = A.viewShutters ? FrameGen::under_views_shutter(gen) : gen) {
       hipError_t he = rtk::launch_render_variant(V, p->accel == RT_ACCEL_BRUTE, p->collect_stats != 0, c->S, A, dAccum,
                                                  c->dCounters.get(), stream);
       if (he != hipSuccess) return fail(RT_ERR_HIP, "%s render launch failed: %s", V.name(), hipGetErrorString(he));
@@ -2675,6 +2676,10 @@ rtk::AovArgs aov_args(const rt_params& q, const rt_aov& out) {
 // what the albedo channel of an AOV pass sums: the mesh's albedo, the resident vertex colours' interpolation
 // (rt_render_aov_colors) or the resident textures' sample (rt_render_aov_textured)
 enum AovAlbedo { ALBEDO_MESH, ALBEDO_COLORS, ALBEDO_TEXTURES };
+static_assert(ALBEDO_MESH == RT_ALBEDO_MATERIAL && ALBEDO_COLORS == RT_ALBEDO_COLORS && ALBEDO_TEXTURES == RT_ALBEDO_TEXTURES,
+              "the public constants of the *_albedo forms are this enumeration");
+// (of a checked `albedo` argument)
+inline AovAlbedo albedo_kind(uint32_t albedo) { return static_cast<AovAlbedo>(albedo); }
 
 // RT_ERR_STATE where the context lacks what the albedo channel reads
 int aov_albedo_resident(const rt_ctx* c, AovAlbedo alb) {
@@ -3355,9 +3360,10 @@ int upload_views(rt_ctx* c, const rt_params* p, const rt_views* v, const rt_came
 
 // The multi-view frame of checked p and v into d_accum on `stream`, behind rt_render_views_device and both forms of
 // rt_render_views_shutter: pad and refit as views_checks (or views_shutter_checks) left them; shutters: the views'
-// shutter records, the third table of a multi-view shutter frame, or null.
+// shutter records, the third table of a multi-view shutter frame, or null.  gen: with shutters, the colours or textures
+// the frame shades with (rt_render_views_shutter_albedo), else none.
 int views_frame_device(rt_ctx* c, const rt_params* p, const rt_views* v, const rtk::ViewShutterRec* shutters, const rtbvh::Padding& pad,
-                       bool refit, void* d_accum, void* stream, rt_stats* stats) {
+                       bool refit, void* d_accum, void* stream, rt_stats* stats, const FrameGen& gen = FrameGen()) {
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   int rc;
@@ -3371,21 +3377,21 @@ int views_frame_device(rt_ctx* c, const rt_params* p, const rt_views* v, const r
   TileList own = {c->vwTiles.d.get(), c->vwNTiles, sshift};
   own.tileView = c->vwTileView.d.get(), own.views = c->vwRecs.get(), own.viewShutters = shutters ? c->vwShutters.get() : nullptr;
   int e = 0;
-  if ((rc = launch_frame(c, p, static_cast<float4*>(d_accum), s, &e, &own)) != RT_OK) return rc;
+  if ((rc = launch_frame(c, p, static_cast<float4*>(d_accum), s, &e, &own, gen)) != RT_OK) return rc;
   return stats ? frame_stats(c, s, e, (uint64_t)n * p->width * p->height * sppCount, stats) : (int)RT_OK;
 }
 
 // The host form of such a frame, after its checks: frame_host's steps over one accumulator slice per view, each view
 // resolved over its slice with the shared background.
 int views_frame_host(rt_ctx* c, const rt_params* p, const rt_views* v, const rtk::ViewShutterRec* shutters, const rtbvh::Padding& pad,
-                     bool refit, const float* bg, float* out_rgb, float* accum_out, rt_stats* stats) {
+                     bool refit, const float* bg, float* out_rgb, float* accum_out, rt_stats* stats, const FrameGen& gen = FrameGen()) {
   HIP_TRY(hipSetDevice(c->device));
   const size_t npx = (size_t)p->width * p->height, all = npx * v->n_views;
   Staging st;
   float4* dAccum = st.zeroed<float4>(accum_out, all);
   if (st.rc != RT_OK) return st.rc;
   rt_stats local;
-  int rc = views_frame_device(c, p, v, shutters, pad, refit, dAccum, nullptr, stats ? stats : &local);
+  int rc = views_frame_device(c, p, v, shutters, pad, refit, dAccum, nullptr, stats ? stats : &local, gen);
   if (rc != RT_OK) return rc;
   if ((rc = stage_resolve(&st, bg, out_rgb, dAccum, v->n_views, npx, p->spp)) != RT_OK) return rc;
   return st.download();
@@ -4117,11 +4123,14 @@ namespace {
 // record; then the device; then the context: rt_render_views' camera rule with every camera_close counted in the padding,
 // and rt_render_shutter's camera checks per view with cameras[j] in the place of the context's camera, under the origin
 // bound the frame runs with (*pad's).  recs: the records the kernels take.
+// albedo (rt_render_views_shutter_albedo; RT_ALBEDO_MATERIAL for the plain form): a value that is none of the three is
+// refused among the arguments, and data the context does not hold last of all.
 int views_shutter_checks(rt_ctx* c, const rt_params* p, const rt_views* v, const rt_shutter* sh, const char* outputs,
-                         rtbvh::Padding* pad, bool* refit, std::vector<rtk::ViewShutterRec>* recs) {
+                         rtbvh::Padding* pad, bool* refit, std::vector<rtk::ViewShutterRec>* recs, uint32_t albedo = RT_ALBEDO_MATERIAL) {
   if (!c || !p || !v || !v->cameras) return fail(RT_ERR_INVALID, "ctx/params/views/cameras is null");
   if (!sh) return fail(RT_ERR_INVALID, "shutters is null");
   if (outputs) return fail(RT_ERR_INVALID, "%s", outputs);
+  if (albedo > RT_ALBEDO_TEXTURES) return fail(RT_ERR_INVALID, "albedo %u is none of RT_ALBEDO_MATERIAL, RT_ALBEDO_COLORS, RT_ALBEDO_TEXTURES", albedo);
   int rc = check_params_shape(p);
   if (rc != RT_OK) return rc;
   if ((rc = views_shape_checks(p, v)) != RT_OK) return rc;
@@ -4151,8 +4160,22 @@ int views_shutter_checks(rt_ctx* c, const rt_params* p, const rt_views* v, const
     memcpy(Q.d, R.d, sizeof Q.d);
     Q.open = R.open, Q.close = R.close, Q.aperture = R.aperture, Q.fs0 = R.fs0, Q.dfs = R.dfs;
   }
-  return RT_OK;
+  return aov_albedo_resident(c, albedo_kind(albedo));
 }
+
+// The surface record of a coloured or textured multi-view shutter frame, as rt_render_colors / rt_render_textured build
+// it from the resident data (which views_shutter_checks found present); the holder keeps it alive over the launch call.
+struct AlbedoGen {
+  rtk::VColRec vcol;
+  rtk::TexRec tex;
+  FrameGen gen;
+  AlbedoGen(const rt_ctx* c, uint32_t albedo) : vcol{c->vcol.get()}, tex(c->tex.rec()) {
+    if (albedo == RT_ALBEDO_COLORS) gen = FrameGen(vcol);
+    else if (albedo == RT_ALBEDO_TEXTURES) gen = FrameGen(tex);
+  }
+  AlbedoGen(const AlbedoGen&) = delete;
+  AlbedoGen& operator=(const AlbedoGen&) = delete;
+};
 
 }  // namespace
 
@@ -4176,6 +4199,28 @@ int rt_render_views_shutter(rt_ctx* c, const rt_params* p, const rt_views* v, co
   const int rc = views_shutter_checks(c, p, v, shutters, outputs_refused(bg, out_rgb, accum_out), &pad, &refit, &recs);
   if (rc != RT_OK) return rc;
   return views_frame_host(c, p, v, recs.data(), pad, refit, bg, out_rgb, accum_out, stats);
+}
+
+int rt_render_views_shutter_albedo_device(rt_ctx* c, const rt_params* p, const rt_views* v, const rt_shutter* shutters, uint32_t albedo,
+                                          void* d_accum, void* stream, rt_stats* stats) {
+  rtbvh::Padding pad;
+  bool refit = false;
+  std::vector<rtk::ViewShutterRec> recs;
+  const int rc = views_shutter_checks(c, p, v, shutters, d_accum ? nullptr : "d_accum is null", &pad, &refit, &recs, albedo);
+  if (rc != RT_OK) return rc;
+  const AlbedoGen G(c, albedo);
+  return views_frame_device(c, p, v, recs.data(), pad, refit, d_accum, stream, stats, G.gen);
+}
+
+int rt_render_views_shutter_albedo(rt_ctx* c, const rt_params* p, const rt_views* v, const rt_shutter* shutters, uint32_t albedo,
+                                   const float* bg, float* out_rgb, float* accum_out, rt_stats* stats) {
+  rtbvh::Padding pad;
+  bool refit = false;
+  std::vector<rtk::ViewShutterRec> recs;
+  const int rc = views_shutter_checks(c, p, v, shutters, outputs_refused(bg, out_rgb, accum_out), &pad, &refit, &recs, albedo);
+  if (rc != RT_OK) return rc;
+  const AlbedoGen G(c, albedo);
+  return views_frame_host(c, p, v, recs.data(), pad, refit, bg, out_rgb, accum_out, stats, G.gen);
 }
 
 }  // extern "C"
@@ -4204,10 +4249,15 @@ int views_pass_checks(rt_ctx* c, const rt_params* p, const rt_views* v, const rt
   return views_checks(c, q, v, pad, refit);
 }
 
-int aov_views_checks(rt_ctx* c, const rt_params* p, const rt_views* v, const rt_aov* out, rt_params* q, rtbvh::Padding* pad, bool* refit) {
+// alb: what the albedo channel sums (rt_render_aov_views_albedo; ALBEDO_MESH for rt_render_aov_views) — an unknown value
+// is refused among the arguments, data the context does not hold last of all
+int aov_views_checks(rt_ctx* c, const rt_params* p, const rt_views* v, const rt_aov* out, rt_params* q, rtbvh::Padding* pad, bool* refit,
+                     uint32_t alb = RT_ALBEDO_MATERIAL) {
   if (!c || !p || !v || !v->cameras || !out) return fail(RT_ERR_INVALID, "ctx/params/views/cameras/aov is null");
   if (any_set(out->reserved, 4)) return fail(RT_ERR_INVALID, "reserved words must be zero");
-  return views_pass_checks(c, p, v, nullptr, q, pad, refit);
+  if (alb > RT_ALBEDO_TEXTURES) return fail(RT_ERR_INVALID, "albedo %u is none of RT_ALBEDO_MATERIAL, RT_ALBEDO_COLORS, RT_ALBEDO_TEXTURES", alb);
+  const int rc = views_pass_checks(c, p, v, nullptr, q, pad, refit);
+  return rc != RT_OK ? rc : aov_albedo_resident(c, albedo_kind(alb));
 }
 
 int motion_views_checks(rt_ctx* c, const rt_params* p, const rt_views* v, const rt_motion_prev_views* prev, const rt_motion* out,
@@ -4225,6 +4275,46 @@ int stage_views(rt_ctx* c, const rt_params* q, const rt_views* v, const rt_motio
   int rc;
   if (refit && (rc = refit_to_padding(c, pad, s)) != RT_OK) return rc;
   return upload_views(c, q, v, prev ? (prev->cameras ? prev->cameras : v->cameras) : nullptr, s);
+}
+
+// rt_render_aov_views_device and rt_render_aov_views_albedo_device: the multi-view forms of aov_device, the albedo
+// channel by `alb`
+int aov_views_device(rt_ctx* c, const rt_params* p, const rt_views* v, const rt_aov* out, void* stream, uint32_t alb) {
+  rt_params q;
+  rtbvh::Padding pad;
+  bool refit = false;
+  int rc = aov_views_checks(c, p, v, out, &q, &pad, &refit, alb);
+  if (rc != RT_OK) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if ((rc = stage_views(c, &q, v, nullptr, pad, refit, s)) != RT_OK) return rc;
+  const bool brute = q.accel == RT_ACCEL_BRUTE;
+  const rtk::AovArgs A = aov_args(q, *out);
+  const rtk::TexRec T = c->tex.rec();
+  const hipError_t he = alb == RT_ALBEDO_MATERIAL ? rtk::launch_aov_views(brute, c->S, A, c->vwRecs.get(), v->n_views, s)
+                                                  : rtk::launch_aov_views_albedo(brute, c->S, A, c->vwRecs.get(), v->n_views,
+                                                                                 alb == RT_ALBEDO_COLORS ? c->vcol.get() : nullptr,
+                                                                                 alb == RT_ALBEDO_TEXTURES ? &T : nullptr, s);
+  if (he != hipSuccess) return fail(RT_ERR_HIP, "AOV launch failed: %s", hipGetErrorString(he));
+  return RT_OK;
+}
+
+// ... and of aov_host
+int aov_views_host(rt_ctx* c, const rt_params* p, const rt_views* v, const rt_aov* out, uint32_t alb) {
+  rt_params q;
+  rtbvh::Padding pad;
+  bool refit = false;
+  int rc = aov_views_checks(c, p, v, out, &q, &pad, &refit, alb);
+  if (rc != RT_OK) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t all = rtk::view_slice(v->n_views, q.width, q.height, 1);
+  Staging st;
+  rt_aov d = {};
+  d.albedo = st.out(out->albedo, 3 * all), d.normal = st.out(out->normal, 3 * all), d.position = st.out(out->position, 3 * all);
+  d.depth = st.out(out->depth, all), d.hits = st.out(out->hits, all), d.mesh = st.out(out->mesh, all), d.tri = st.out(out->tri, all);
+  if (st.rc != RT_OK) return st.rc;
+  if ((rc = aov_views_device(c, &q, v, &d, nullptr, alb)) != RT_OK) return rc;
+  return st.download();
 }
 
 // Everything rt_denoise_batch checks, the context last (it exists only where a device does).
@@ -4245,34 +4335,16 @@ int denoise_batch_checks(const rt_ctx* c, const rt_denoise_params* d, uint32_t n
 extern "C" {
 
 int rt_render_aov_views_device(rt_ctx* c, const rt_params* p, const rt_views* v, const rt_aov* out, void* stream) {
-  rt_params q;
-  rtbvh::Padding pad;
-  bool refit = false;
-  int rc = aov_views_checks(c, p, v, out, &q, &pad, &refit);
-  if (rc != RT_OK) return rc;
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if ((rc = stage_views(c, &q, v, nullptr, pad, refit, s)) != RT_OK) return rc;
-  const hipError_t he = rtk::launch_aov_views(q.accel == RT_ACCEL_BRUTE, c->S, aov_args(q, *out), c->vwRecs.get(), v->n_views, s);
-  if (he != hipSuccess) return fail(RT_ERR_HIP, "AOV launch failed: %s", hipGetErrorString(he));
-  return RT_OK;
+  return aov_views_device(c, p, v, out, stream, RT_ALBEDO_MATERIAL);
 }
-
 int rt_render_aov_views(rt_ctx* c, const rt_params* p, const rt_views* v, const rt_aov* out) {
-  rt_params q;
-  rtbvh::Padding pad;
-  bool refit = false;
-  int rc = aov_views_checks(c, p, v, out, &q, &pad, &refit);
-  if (rc != RT_OK) return rc;
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t all = rtk::view_slice(v->n_views, q.width, q.height, 1);
-  Staging st;
-  rt_aov d = {};
-  d.albedo = st.out(out->albedo, 3 * all), d.normal = st.out(out->normal, 3 * all), d.position = st.out(out->position, 3 * all);
-  d.depth = st.out(out->depth, all), d.hits = st.out(out->hits, all), d.mesh = st.out(out->mesh, all), d.tri = st.out(out->tri, all);
-  if (st.rc != RT_OK) return st.rc;
-  if ((rc = rt_render_aov_views_device(c, &q, v, &d, nullptr)) != RT_OK) return rc;
-  return st.download();
+  return aov_views_host(c, p, v, out, RT_ALBEDO_MATERIAL);
+}
+int rt_render_aov_views_albedo_device(rt_ctx* c, const rt_params* p, const rt_views* v, uint32_t albedo, const rt_aov* out, void* stream) {
+  return aov_views_device(c, p, v, out, stream, albedo);
+}
+int rt_render_aov_views_albedo(rt_ctx* c, const rt_params* p, const rt_views* v, uint32_t albedo, const rt_aov* out) {
+  return aov_views_host(c, p, v, out, albedo);
 }
 
 int rt_render_motion_views_device(rt_ctx* c, const rt_params* p, const rt_views* v, const rt_motion_prev_views* prev,

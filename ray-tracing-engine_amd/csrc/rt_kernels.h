@@ -162,6 +162,10 @@ hipError_t launch_aov_colors(bool brute_force, const DevScene& S, const AovArgs&
 // the same with the albedo channel summing the texture sample at the first hit (rt_render_aov_textured; the mesh's albedo
 // on a mesh without a texture); instances of their own
 hipError_t launch_aov_textured(bool brute_force, const DevScene& S, const AovArgs& A, const TexRec& T, hipStream_t stream);
+// launch_aov_views (below) with the albedo channel of launch_aov_colors (vcol, T null) or launch_aov_textured (T, vcol
+// null): rt_render_aov_views_albedo; instances of their own
+hipError_t launch_aov_views_albedo(bool brute_force, const DevScene& S, const AovArgs& A, const ViewRec* views, uint32_t nViews,
+                                   const float* vcol, const TexRec* T, hipStream_t stream);
 // ambient occlusion and bent normals at the first hit (ao_kernels.h, rt_render_ao): per pixel, over the samples [s0, s1),
 // the occlusion rays that escaped, the hit samples, and the float32 sum of the escaped directions; null channels are not written
 struct AoArgs {
@@ -245,9 +249,10 @@ struct TexRec {
 };
 // Which variant a frame is, with its record (which the caller keeps alive over the launch call).  VIEWS_SHUTTER, many
 // views each under its own open shutter (rt_render_views_shutter), has none: tile t renders with views[tileView[t]]'s
-// camera, seed and slice under viewShutters[tileView[t]], from RenderArgs' three tables.
+// camera, seed and slice under viewShutters[tileView[t]], from RenderArgs' three tables.  VIEWS_SHUTTER_VCOL and
+// VIEWS_SHUTTER_TEX are that frame with the VColRec / TexRec of a coloured / textured one.
 struct FrameVariant {
-  enum Kind { NONE, LENS, SHUTTER, LIGHTS, VIEWS_SHUTTER, PICK, VCOL, TEX };
+  enum Kind { NONE, LENS, SHUTTER, LIGHTS, VIEWS_SHUTTER, PICK, VCOL, TEX, VIEWS_SHUTTER_VCOL, VIEWS_SHUTTER_TEX };
   Kind kind = NONE;
   const void* rec = nullptr;  // the LensRec, ShutterRec, LightGroupsRec, PickRec, VColRec or TexRec of kind, else null
   FrameVariant() = default;
@@ -258,16 +263,24 @@ struct FrameVariant {
   FrameVariant(const PickRec& r) : kind(PICK), rec(&r) {}
   FrameVariant(const VColRec& r) : kind(VCOL), rec(&r) {}
   FrameVariant(const TexRec& r) : kind(TEX), rec(&r) {}
+  // the coloured or textured frame F under the multi-view shutter's generator (rt_render_views_shutter_albedo): F's
+  // record with RenderArgs' three tables; any other F is the multi-view shutter frame itself
+  static FrameVariant under_views_shutter(const FrameVariant& F) {
+    FrameVariant V(F.kind == VCOL ? VIEWS_SHUTTER_VCOL : F.kind == TEX ? VIEWS_SHUTTER_TEX : VIEWS_SHUTTER);
+    if (V.kind != VIEWS_SHUTTER) V.rec = F.rec;
+    return V;
+  }
   explicit operator bool() const { return kind != NONE; }
   // the variant in an error message: "<name> render launch failed"
   const char* name() const {
-    static const char* const names[] = {"", "lens", "shutter", "light-group", "multi-view shutter", "light-pick", "vertex-colour", "textured"};
+    static const char* const names[] = {"", "lens", "shutter", "light-group", "multi-view shutter", "light-pick", "vertex-colour", "textured",
+                                        "multi-view shutter vertex-colour", "multi-view shutter textured"};
     return names[kind];
   }
 };
 // launch_render's one-wave-per-workgroup family (brute, sequential, pooled; counted or timed) for a variant (F.kind not
 // NONE); A as launch_render takes it: tileView null, but for VIEWS_SHUTTER a multi-view frame's with the three tables
-// set.  LIGHTS: accum is [G.n][height][width], slice g at accum + g * width * height.  PICK: pooled whenever A.flags bit 0
+// set, and so for VIEWS_SHUTTER_VCOL and VIEWS_SHUTTER_TEX.  LIGHTS: accum is [G.n][height][width], slice g at accum + g * width * height.  PICK: pooled whenever A.flags bit 0
 // is set, whatever the scene's light count (a vertex sends m <= POOL_L shadow rays).  VCOL: a launch allocates
 // VP_VCOL_WORDS more words of LDS per wave (the vertex's parked kdDiffuse), and so does TEX.  hipErrorInvalidValue where A, the
 // record or the scene's light count do not fit the variant.

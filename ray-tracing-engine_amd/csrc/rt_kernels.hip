@@ -1539,7 +1539,7 @@ RT_DEV void group_samples_add(const RenderArgs& A, const LightGroupsRec& G, floa
 
 // The record a frame variant's instances take as a kernel argument of their own, by its LT_* bits: the lens, the shutter
 // of a single-view frame (a multi-view one reads its records from RenderArgs' tables), the light groups, the light
-// picks, the vertex colours, the textures — or none.  park: (LT_VCOL, LT_TEX) the wave's three parked rows of LDS
+// picks, the vertex colours, the textures (with or without LT_VIEWS | LT_SHUTTER beside them) — or none.  park: (LT_VCOL, LT_TEX) the wave's three parked rows of LDS
 // (VColKd), from the kernel that lays its LDS out.
 struct NoRec {};
 template <int LTV>
@@ -1570,8 +1570,10 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
   constexpr bool PICK = (LTV & LT_PICK) != 0;
   constexpr bool VCOL = (LTV & LT_VCOL) != 0;
   constexpr bool TEX = (LTV & LT_TEX) != 0;
-  static_assert(!VCOL || (!VIEWS && !LENS && !SHUTTER && !LIGHTS && !PICK && !PHOTON), "vertex colours go with the plain frame only");
-  static_assert(!TEX || (!VIEWS && !LENS && !SHUTTER && !LIGHTS && !PICK && !VCOL && !PHOTON), "textures go with the plain frame only");
+  // (the surface side and the camera side are orthogonal: a record of colours or textures goes with the plain generator
+  // or with the multi-view shutter's, the general camera form, whose tables come from RenderArgs)
+  static_assert(!VCOL || (VIEWS == SHUTTER && !LENS && !LIGHTS && !PICK && !PHOTON), "vertex colours go with the plain frame or the multi-view shutter frame");
+  static_assert(!TEX || (VIEWS == SHUTTER && !LENS && !LIGHTS && !PICK && !VCOL && !PHOTON), "textures go with the plain frame or the multi-view shutter frame");
   static_assert(!LIGHTS || (!VIEWS && !LENS && !SHUTTER && !PHOTON), "light groups go with the plain frame only");
   static_assert(!PICK || (!VIEWS && !LENS && !SHUTTER && !LIGHTS && !PHOTON), "light picks go with the plain frame only");
   static_assert(!LENS || !VIEWS, "no multi-view lens frames");

@@ -176,6 +176,9 @@ TEX_NONE = 0xffffffff
 TEX_REPEAT, TEX_CLAMP = 0, 1
 TEX_NEAREST, TEX_BILINEAR = 0, 1
 TEX_MAX_SIDE, TEX_MAX_UV, TEX_MAX_TEXELS = 16384, 1024.0, 1 << 28
+# the `albedo` argument of the *_albedo forms (rt_amd.h RT_ALBEDO_*): the meshes' own, the resident vertex colours, the
+# resident texture set
+ALBEDO_MATERIAL, ALBEDO_COLORS, ALBEDO_TEXTURES = 0, 1, 2
 
 
 class Texture(C.Structure):
@@ -472,7 +475,8 @@ AMD_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_create", "rt_destroy", "rt
                "rt_render_lights_device", "rt_render_pick", "rt_render_pick_device", "rt_set_vertex_colors",
                "rt_render_colors", "rt_render_colors_device", "rt_render_aov_colors", "rt_render_aov_colors_device",
                "rt_set_textures", "rt_render_textured", "rt_render_textured_device", "rt_render_aov_textured",
-               "rt_render_aov_textured_device"]
+               "rt_render_aov_textured_device", "rt_render_views_shutter_albedo", "rt_render_views_shutter_albedo_device",
+               "rt_render_aov_views_albedo", "rt_render_aov_views_albedo_device"]
 HOST_SYMBOLS = ["rt_host_scene_build", "rt_host_scene_desc", "rt_host_scene_free", "rt_host_last_error",
                 "rt_host_fill_background", "rt_host_save_ppm", "rt_host_kd_order", "rt_host_light_basis"]
 
@@ -653,6 +657,13 @@ def amd():
                                               C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         L.rt_render_views_shutter_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Views), C.POINTER(Shutter),
                                                      C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        L.rt_render_views_shutter_albedo.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Views), C.POINTER(Shutter),
+                                                     C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        L.rt_render_views_shutter_albedo_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Views), C.POINTER(Shutter),
+                                                            C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        L.rt_render_aov_views_albedo.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Views), C.c_uint32, C.POINTER(Aov)]
+        L.rt_render_aov_views_albedo_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Views), C.c_uint32,
+                                                        C.POINTER(Aov), C.c_void_p]
         L.rt_render_adaptive_shutter.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(AdaptiveParams), C.POINTER(Shutter),
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AdaptiveReport),
                                                  C.POINTER(Stats)]
@@ -1325,6 +1336,31 @@ class Context:
                                                     C.c_void_p(stream or None), C.byref(st) if stats else None))
         return st
 
+    def render_views_shutter_albedo(self, params, cameras, shutters, albedo=ALBEDO_TEXTURES, bg=None, seeds=None, want_accum=True):
+        """rt_render_views_shutter_albedo: render_views_shutter with every shaded vertex's albedo from the resident vertex
+        colours (ALBEDO_COLORS) or texture set (ALBEDO_TEXTURES); ALBEDO_MATERIAL is render_views_shutter itself.
+        Returns (out [n][h][w][3] or None without bg, accum [n][h][w][4] or None, stats)."""
+        v, _keep = make_views(cameras, seeds)
+        sh = make_shutters(shutters, v.n_views)
+        w, h, n = params.width, params.height, v.n_views
+        out = np.empty((n, h, w, 3), np.float32) if bg is not None else None
+        acc = np.empty((n, h, w, 4), np.float32) if want_accum else None
+        st = Stats()
+        bgc = None if bg is None else np.ascontiguousarray(bg, np.float32)
+        _check(amd().rt_render_views_shutter_albedo(self._h, C.byref(params), C.byref(v), sh, albedo, _ptr(bgc), _ptr(out),
+                                                    _ptr(acc), C.byref(st)))
+        return out, acc, st
+
+    def render_views_shutter_albedo_device(self, params, cameras, shutters, d_accum_ptr, albedo=ALBEDO_TEXTURES, stream=0,
+                                           seeds=None, stats=False):
+        """rt_render_views_shutter_albedo_device: accumulate into the caller-zeroed device d_accum [n][h][w][4] on `stream`."""
+        v, _keep = make_views(cameras, seeds)
+        sh = make_shutters(shutters, v.n_views)
+        st = Stats() if stats else None
+        _check(amd().rt_render_views_shutter_albedo_device(self._h, C.byref(params), C.byref(v), sh, albedo, C.c_void_p(d_accum_ptr),
+                                                           C.c_void_p(stream or None), C.byref(st) if stats else None))
+        return st
+
     def render_adaptive_shutter(self, params, shutter, bg, threshold, max_passes, min_passes=0, floor=0.):
         """rt_render_adaptive_shutter: render_adaptive whose passes are render_shutter frames under `shutter`.  Returns
         (out [h][w][3], accum [h][w][4], spp [h][w] uint32, AdaptiveReport, Stats)."""
@@ -1540,6 +1576,27 @@ class Context:
         for k, p in ptrs.items():
             setattr(a, k, p or None)
         _check(amd().rt_render_aov_views_device(self._h, C.byref(params), C.byref(v), C.byref(a), C.c_void_p(stream or None)))
+
+    def render_aov_views_albedo(self, params, cameras, albedo=ALBEDO_TEXTURES, seeds=None, channels=AOV_CHANNELS):
+        """rt_render_aov_views_albedo: render_aov_views whose albedo channel sums the resident vertex colours'
+        interpolation (ALBEDO_COLORS) or the resident textures' sample (ALBEDO_TEXTURES)."""
+        v, _keep = make_views(cameras, seeds)
+        w, h, n = params.width, params.height, v.n_views
+        sums, a = {}, Aov()
+        for k in channels:
+            sums[k] = np.zeros((n, h, w, 3) if k in AOV_FLOAT3 else (n, h, w), np.float32 if k in AOV_FLOAT3 or k == "depth" else np.uint32)
+            setattr(a, k, sums[k].ctypes.data)
+        _check(amd().rt_render_aov_views_albedo(self._h, C.byref(params), C.byref(v), albedo, C.byref(a)))
+        return sums
+
+    def render_aov_views_albedo_device(self, params, cameras, ptrs, albedo=ALBEDO_TEXTURES, stream=0, seeds=None):
+        """rt_render_aov_views_albedo_device: the sums into device buffers [n][h][w][..]; ptrs = {channel: device pointer}."""
+        v, _keep = make_views(cameras, seeds)
+        a = Aov()
+        for k, p in ptrs.items():
+            setattr(a, k, p or None)
+        _check(amd().rt_render_aov_views_albedo_device(self._h, C.byref(params), C.byref(v), albedo, C.byref(a),
+                                                       C.c_void_p(stream or None)))
 
     @staticmethod
     def _motion_prev_views(prev_pos, prev_cameras, n):
