@@ -48,6 +48,8 @@
  *                                  its first-hit AOVs with the colour interpolated at every shaded vertex (+ _device forms)
  *   rt_set_textures / rt_render_textured / rt_render_aov_textured <- (no counterpart) image-textured albedo: the frame and
  *                                  its first-hit AOVs with the hit mesh's texture sampled at every shaded vertex (+ _device forms)
+ *   rt_set_material_maps / rt_render_material <- (no counterpart) textured kd, alpha and f0: the textured frame with the
+ *                                  whole material of every shaded vertex sampled from the resident textures (+ _device form)
  *   rt_render_aov_views / rt_render_motion_views / rt_denoise_batch <- (no counterpart) the AOVs, motion vectors and
  *                                  denoised frames of those views, one launch each (+ _device forms)
  *   rt_trace                    <- RayTracer::rayTrace (RayTracer.h:27-53) test hook
@@ -69,8 +71,8 @@
  *     rt_render_device, rt_render_views_device, rt_render_rays_device, rt_render_shutter_device,
  *     rt_render_views_shutter_device (tests/test_gpu_views_shutter.py), rt_render_lights_device
  *     (tests/test_gpu_lights.py), rt_render_pick_device (tests/test_gpu_pick.py), rt_render_colors_device
- *     (tests/test_gpu_vcol.py), rt_render_textured_device (tests/test_gpu_tex.py) and
- *     rt_render_lens_device with stats == NULL;
+ *     (tests/test_gpu_vcol.py), rt_render_textured_device (tests/test_gpu_tex.py), rt_render_material_device
+ *     (tests/test_gpu_mat.py) and rt_render_lens_device with stats == NULL;
  *     rt_resolve_device;
  *     rt_render_aov_device, rt_render_aov_colors_device, rt_render_aov_textured_device, rt_render_ao_device, rt_render_motion_device; rt_temporal_accumulate_device,
  *     rt_svgf_device, rt_denoise_device, rt_denoise_batch_device; rt_render_aov_views_device,
@@ -85,7 +87,7 @@
  *   SYNCHRONISE `stream`, and only it, before they return, because the host reads a result back:
  *     rt_render_device, rt_render_views_device, rt_render_rays_device, rt_render_shutter_device,
  *     rt_render_views_shutter_device, rt_render_lights_device, rt_render_pick_device, rt_render_colors_device,
- *     rt_render_textured_device, rt_render_lens_device with stats != NULL;
+ *     rt_render_textured_device, rt_render_material_device, rt_render_lens_device with stats != NULL;
  *     rt_render_adaptive_device and rt_render_adaptive_shutter_device (every pass); rt_update_vertices_device,
  *     rt_update_transforms and rt_update_skin (twice);
  *     the four multi-view forms when a view lies far enough out to need a wider box padding (a refit).
@@ -974,8 +976,8 @@ int rt_render_aov_colors_device(rt_ctx* ctx, const rt_params* p, const rt_aov* d
  * rt_render_aov_textured / rt_render_aov_textured_device are rt_render_aov / rt_render_aov_device with the albedo channel
  * summing c at the first hit (the mesh's albedo on an RT_TEX_NONE mesh); every other channel is rt_render_aov's bit for
  * bit.  rt_render_aov's checks, then RT_ERR_STATE without a resident set.
- * Out of scope: mip maps and any filter that needs ray footprints; 8-bit or sRGB texel storage; textures on alpha, f0 or
- * normals; textures combined with vertex colours, the lens, the shutter, light groups, light picks, views, adaptive passes
+ * Out of scope: mip maps and any filter that needs ray footprints; 8-bit or sRGB texel storage; textures on
+ * normals (on kd, alpha and f0: rt_render_material below); textures combined with vertex colours, the lens, the shutter, light groups, light picks, views, adaptive passes
  * or rt_render_rays; rt_group; a device-memory form of the set.                                                          */
 #define RT_TEX_NONE 0xffffffffu
 enum { RT_TEX_REPEAT = 0, RT_TEX_CLAMP = 1 };
@@ -1390,6 +1392,65 @@ int rt_render_views_shutter_albedo_device(rt_ctx* ctx, const rt_params* p, const
 int rt_render_aov_views_albedo(rt_ctx* ctx, const rt_params* p, const rt_views* v, uint32_t albedo, const rt_aov* host_out);
 int rt_render_aov_views_albedo_device(rt_ctx* ctx, const rt_params* p, const rt_views* v, uint32_t albedo,
                                       const rt_aov* device_out, void* stream);
+
+/* ---- textured material maps: kd, alpha and f0 from the resident textures -------------------------------
+ * rt_set_material_maps names, per mesh, two more textures of the RESIDENT texture set (rt_set_textures), and
+ * rt_render_material renders rt_render_textured's frame with two more substitutions at every shaded vertex.  The vertex
+ * shades with the material {kd, alpha, albedo, f0} in which
+ *   albedo      is rt_render_textured's: the sample of texture mesh_texture[mesh], or the mesh's own;
+ *   f0          is the rgb sample of texture mesh_f0[mesh];
+ *   (kd, alpha) are the r and g of the sample of texture mesh_kd_alpha[mesh] (b is not read: any finite value);
+ *   on RT_TEX_NONE, f0 and (kd, alpha) are the mesh's own.
+ * All three samples are taken at the same hit coordinate (the one uv per vertex, interpolated as rt_render_textured
+ * does), each by rt_render_textured's sampler under its own texture's filter and wraps.  From those eight floats the BSDF
+ * is evaluateColorResponse of that material, in exactly the operations rt_create performs on an rt_material: albedo /
+ * float(M_PI) then * kd; 1 - kd; alpha * alpha; 1 - f0; k = float(double(alpha) * sqrt(2 / pi)); 1 - k — all float32 but
+ * k's product, nothing fused.  No range is imposed on the sampled fields beyond the set's finiteness, as none is on
+ * rt_material: an alpha of 0 shades as an rt_material with alpha = 0 does.  The RNG streams, the jitter, every ray, the
+ * hit selection, both ray counts, the per-sample clamp and the accumulation are rt_render_textured's: the frame's bounce
+ * is drawn from the shading normal alone, so no material field moves a ray.
+ * Guarantees, bit for bit on accumulator, image, samples and both ray counts:
+ *   - M1: maps that are RT_TEX_NONE on every mesh (or both NULL) give rt_render_textured's frame; so do maps whose texels
+ *     equal the mesh's own f0 / (kd, alpha, anything), whatever the uvs, filters and wraps; with T1 that frame is rt_render's.
+ *   - M2: on T2's vertex-split scene (triangle k of n with uv ((3k + 1.5) / (3n), 0.5) on its three vertices) and 3n x 1
+ *     textures whose texels 3k .. 3k + 2 hold triangle k's albedo, f0 and (kd, alpha, any), the frame under either filter is
+ *     rt_render's on the scene of one mesh per triangle whose material k has those four fields.
+ *   - M3: sample ranges chain (spp_begin / spp_count), and host and device forms agree.
+ *   - M4: reserved[0] (lanes per pixel), reserved[1] bit 0 (no pool), collect_stats, RT_ACCEL_BRUTE and the node format
+ *     change the schedule, never the bits.
+ * rt_set_material_maps is a host form: it copies the two tables to the context's device, into fresh allocations, and then
+ * replaces the ones before, which are freed once the launches that read them have run; NULL releases.  It changes nothing
+ * any other entry point reads; the maps stay across every update, refit, rt_rebuild, transform and skin.  The indices
+ * refer to the texture set resident AT THE CALL: a later rt_set_textures (replace or release) makes the maps stale until
+ * rt_set_material_maps is called again.  Refusals, in this order, with rt_last_error naming the first offender:
+ *   RT_ERR_INVALID  a null maps with a null ctx; a non-zero reserved word; a null ctx; n_meshes different from the context's
+ *   RT_ERR_STATE    a context that refuses launches
+ *   RT_ERR_STATE    no resident texture set
+ *   RT_ERR_INVALID  an entry that is neither an index below the resident set's n_textures nor RT_TEX_NONE (mesh_f0 is
+ *                   scanned first; the message names the table and the mesh)
+ * rt_render_material / rt_render_material_device take rt_render_textured's / rt_render_textured_device's arguments and
+ * its checks in its order and with its codes (RT_ERR_UNSUPPORTED: world > 1, use_photons, the wavefront integrator, the
+ * legacy RNG); then, last of all, RT_ERR_STATE without a resident texture set, without resident maps, or with stale maps
+ * ("the material maps were set for another texture set").  A rejected call writes nothing.  The kernels are
+ * rt_render_textured's family (one wave per workgroup, no persistent instances); buffers, stats and the device form's
+ * stream order are rt_render_textured_device's.
+ * Out of scope: maps under the lens, the shutter or views (rt_render_views_shutter_albedo refuses albedo > 2), under light
+ * groups, picks, adaptive passes or ray batches; f0 / roughness AOV channels (rt_aov has no room); a second uv set;
+ * normal maps (they move the bounce ray); rt_group.                                                                    */
+typedef struct rt_material_maps {
+  uint32_t n_meshes;              /* must be the context's */
+  const uint32_t* mesh_f0;        /* [n_meshes] HOST: index into the RESIDENT texture set or RT_TEX_NONE; rgb -> f0.
+                                     NULL = RT_TEX_NONE on every mesh */
+  const uint32_t* mesh_kd_alpha;  /* [n_meshes] HOST: likewise; r -> kd, g -> alpha, b ignored (any finite value).
+                                     NULL = RT_TEX_NONE on every mesh */
+  uint32_t reserved[5];           /* zero */
+} rt_material_maps;
+int rt_set_material_maps(rt_ctx* ctx, const rt_material_maps* maps /* NULL: release */);
+/* out_rgb [h][w][3] or NULL, accum_out [h][w][4] or NULL, background_rgb [h][w][3]: as rt_render's */
+int rt_render_material(rt_ctx* ctx, const rt_params* p, const float* background_rgb, float* out_rgb, float* accum_out,
+                       rt_stats* stats);
+/* Accumulate into caller-zeroed DEVICE d_accum [h][w][4] on `stream`, as rt_render_textured_device does. */
+int rt_render_material_device(rt_ctx* ctx, const rt_params* p, void* d_accum, void* stream, rt_stats* stats);
 
 /* ---- multi-GPU (Renderer.cpp:219-265 sharded by pixel tiles) -------------
  * A tile-sharded frame: rank r of `world` integrates the pixels whose `tile`-pixel granule

@@ -1,7 +1,8 @@
 // frame_variants.h — the frame integrator with another generator, another split of its samples or another light list:
 // rt_render_lens, rt_render_shutter, rt_render_views_shutter, rt_render_lights (DESIGN.md §6m–§6p), rt_render_pick (§6r)
-// and, with another albedo at every vertex, rt_render_colors (§6t), rt_render_textured (§6u) and both under the multi-view
-// shutter's generator, rt_render_views_shutter_albedo (§6v).
+// and, with another albedo at every vertex, rt_render_colors (§6t), rt_render_textured (§6u), both under the multi-view
+// shutter's generator, rt_render_views_shutter_albedo (§6v), and, with a whole material at every vertex, rt_render_material
+// (§6w).
 //
 // Every variant is render_tile itself under one more LT_* bit, on the one-wave-per-workgroup family that k_render serves:
 // brute, sequential and pooled, each counted (STATS, one wave per SIMD) and timed (four waves per SIMD, k_render's target);
@@ -35,6 +36,10 @@
 //                                        the colour / texture row (the record, the parked rows) in one instance; the
 //                                        two meet nowhere in render_tile: the sample's primary ray is complete before
 //                                        the first vertex reads the record
+//   material maps LT_MAT                 MatRec: every shaded vertex forms its whole material from up to three samples
+//                                        at the hit's uv (tex_mat: albedo, f0, (kd, alpha)) and shades with
+//                                        bsdf_base(const rt_material&) of it (the VC switch's second payload, VMat); a
+//                                        launch allocates VP_MAT_WORDS words of LDS per wave, the eight parked rows
 // A new variant supplies a row of the same kind (a struct below, a FrameVariant kind, a case in launch_render_variant):
 // its LT_* bits, its record, the stack rows its sample hand-over needs, and its argument check.
 // (included by rt_kernels.hip inside namespace rtk: shares its device functions)
@@ -59,6 +64,9 @@ __global__ __launch_bounds__(BLOCK, MINW) void k_render_rec(DevScene S, RenderAr
   // them — max(stackLevels, kParkMinRows) stack rows and, with one, the pool
   float* park = nullptr;
   if constexpr ((LTV & (LT_VCOL | LT_TEX)) != 0)
+    park = reinterpret_cast<float*>(lds + (A.stackLevels < kParkMinRows ? kParkMinRows : A.stackLevels) * BLOCK + (POOLED ? VP_WORDS : 0));
+  // (LT_MAT) eight rows in the same place: the vertex's material
+  if constexpr ((LTV & LT_MAT) != 0)
     park = reinterpret_cast<float*>(lds + (A.stackLevels < kParkMinRows ? kParkMinRows : A.stackLevels) * BLOCK + (POOLED ? VP_WORDS : 0));
   LaneStats st;
   const uint32_t t0 = blockIdx.x * A.tilesPerBlock, t1 = min(A.n_tiles, t0 + A.tilesPerBlock);
@@ -112,6 +120,14 @@ struct VariantTex {
     return A.tileView || !R.uv || !R.meshTex || !R.desc || !R.texels;
   }
 };
+struct VariantMat {
+  static constexpr int LTV = LT_MAT;
+  using Rec = MatRec;
+  static constexpr uint32_t ROWS = 4, ROWS_POOLED = 4;
+  static bool refused(const DevScene&, const RenderArgs& A, const Rec& R) {
+    return A.tileView || !R.uv || !R.meshTex || !R.desc || !R.texels || !R.meshF0 || !R.meshKdAlpha;
+  }
+};
 struct VariantViewsShutter {
   static constexpr int LTV = LT_VIEWS | LT_SHUTTER;
   using Rec = NoRec;
@@ -152,7 +168,8 @@ static hipError_t launch_variant2(bool stats, const DevScene& S, const RenderArg
   if (A.n_tiles == 0) return hipSuccess;
   constexpr uint32_t minRows = POOLED ? V::ROWS_POOLED : V::ROWS;
   // (a coloured or textured frame's wave parks the vertex's kdDiffuse behind its stack rows and pool: k_render_rec's `park`)
-  constexpr uint32_t parkWords = (V::LTV & (LT_VCOL | LT_TEX)) != 0 ? VP_VCOL_WORDS : 0;
+  // (a material-map frame's parks the vertex's whole material there)
+  constexpr uint32_t parkWords = (V::LTV & LT_MAT) != 0 ? VP_MAT_WORDS : (V::LTV & (LT_VCOL | LT_TEX)) != 0 ? VP_VCOL_WORDS : 0;
   static_assert(parkWords == 0 || minRows == kParkMinRows, "k_render_rec places the parked rows behind kParkMinRows stack rows at least");
   const size_t ldsBytes = 4u * ((A.stackLevels < minRows ? minRows : A.stackLevels) * BLOCK + (POOLED ? VP_WORDS : 0) + parkWords);
   RenderArgs A1 = A;
@@ -193,6 +210,8 @@ hipError_t launch_render_variant(const FrameVariant& F, bool brute_force, bool s
       return launch_variant<VariantVCol>(brute_force, stats, S, A, *static_cast<const VColRec*>(F.rec), accum, counters, stream);
     case FrameVariant::TEX:
       return launch_variant<VariantTex>(brute_force, stats, S, A, *static_cast<const TexRec*>(F.rec), accum, counters, stream);
+    case FrameVariant::MAT:
+      return launch_variant<VariantMat>(brute_force, stats, S, A, *static_cast<const MatRec*>(F.rec), accum, counters, stream);
     case FrameVariant::VIEWS_SHUTTER:
       return launch_variant<VariantViewsShutter>(brute_force, stats, S, A, NoRec(), accum, counters, stream);
     case FrameVariant::VIEWS_SHUTTER_VCOL:

@@ -25,6 +25,7 @@
 
 #include "bvh_build.h"
 #include "filters.h"
+#include "material_maps.h"
 #include "rt_amd.h"
 #include "rt_kernels.h"
 #include "wave_tiles.h"
@@ -324,7 +325,18 @@ struct rt_ctx {
     DevBuf<rtk::TexDesc> desc;
     explicit operator bool() const { return (bool)texels; }
     rtk::TexRec rec() const { return rtk::TexRec{uv.get(), meshTex.get(), desc.get(), texels.get()}; }
+    // how many sets (and releases) this context has seen: every rt_set_textures that replaces or releases moves it on,
+    // so that what was checked against one set (rt_set_material_maps' indices) can tell that it has gone
+    uint64_t generation = 0;
+    uint32_t nTextures = 0;
   } tex;
+  // rt_set_material_maps: every mesh's f0 and (kd, alpha) texture index into the set of generation texGeneration (f0
+  // null: none); rt_render_material alone reads them, and no update touches them
+  struct MatMaps {
+    DevBuf<uint32_t> f0, kdAlpha;
+    uint64_t texGeneration = 0;
+    explicit operator bool() const { return (bool)f0; }
+  } matMaps;
   // scratch of rt_denoise_device and rt_svgf_device (rtk::filter_scratch; grows on demand: ensure_filter_scratch)
   DevBuf<float4> dnScratch;
   size_t dnCap = 0;
@@ -4065,7 +4077,9 @@ int rt_set_textures(rt_ctx* c, const rt_texture_set* t) {
   if (!t) {
     if (!c) return fail(RT_ERR_INVALID, "ctx/textures is null");
     HIP_TRY(hipSetDevice(c->device));
-    c->tex = rt_ctx::TexSet();
+    rt_ctx::TexSet none;
+    none.generation = c->tex.generation + 1;  // (resident material maps are stale from here on)
+    c->tex = std::move(none);
     return RT_OK;
   }
   int rc = texture_set_checks(t);
@@ -4095,6 +4109,7 @@ int rt_set_textures(rt_ctx* c, const rt_texture_set* t) {
   if ((rc = upload(&fresh.uv, t->vertex_uv, 2 * (size_t)t->n_vertices)) != RT_OK ||
       (rc = upload(&fresh.meshTex, t->mesh_texture, t->n_meshes)) != RT_OK || (rc = upload(&fresh.desc, desc.data(), desc.size())) != RT_OK)
     return rc;
+  fresh.generation = c->tex.generation + 1, fresh.nTextures = t->n_textures;  // (resident material maps are stale from here on)
   c->tex = std::move(fresh);
   return RT_OK;
 }
@@ -4109,6 +4124,79 @@ int rt_render_textured_device(rt_ctx* c, const rt_params* p, void* d_accum, void
 int rt_render_textured(rt_ctx* c, const rt_params* p, const float* bg, float* out_rgb, float* accum_out, rt_stats* stats) {
   rtk::TexRec R;
   const int rc = textured_checks(c, p, outputs_refused(bg, out_rgb, accum_out), &R);
+  if (rc != RT_OK) return rc;
+  return frame_host(c, p, R, 1, bg, out_rgb, accum_out, stats);
+}
+
+}  // extern "C"
+
+// ---- textured material maps -----------------------------------------------------------------------------
+namespace {
+
+// Everything both forms of rt_render_material check: textured_checks' in its order, then what this frame needs resident,
+// and the record the kernels take.
+int material_checks(const rt_ctx* c, const rt_params* p, const char* outputs, rtk::MatRec* R) {
+  if (!c || !p) return fail(RT_ERR_INVALID, "ctx/params is null");
+  if (outputs) return fail(RT_ERR_INVALID, "%s", outputs);
+  int rc = check_params_shape(p);
+  if (rc != RT_OK) return rc;
+  if (p->world > 1) return fail(RT_ERR_UNSUPPORTED, "tile-sharded material-map frames (world %u) are not supported", p->world);
+  if (p->use_photons) return fail(RT_ERR_UNSUPPORTED, "material-map frames do not shade from the photon map");
+  if (p->reserved[2] & 1u) return fail(RT_ERR_UNSUPPORTED, "material-map frames do not run the wavefront integrator");
+  if ((rc = check_device_present()) != RT_OK) return rc;
+  if ((rc = check_not_broken(c)) != RT_OK) return rc;
+  if (!c->tex) return fail(RT_ERR_STATE, "the context has no resident textures (rt_set_textures)");
+  if (!c->matMaps) return fail(RT_ERR_STATE, "the context has no resident material maps (rt_set_material_maps)");
+  if (c->matMaps.texGeneration != c->tex.generation)
+    return fail(RT_ERR_STATE, "the material maps were set for another texture set (rt_set_material_maps after rt_set_textures)");
+  const rtk::TexRec T = c->tex.rec();
+  *R = rtk::MatRec{T.uv, T.meshTex, T.desc, T.texels, c->matMaps.f0.get(), c->matMaps.kdAlpha.get()};
+  return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_set_material_maps(rt_ctx* c, const rt_material_maps* m) {
+  if (!m) {
+    if (!c) return fail(RT_ERR_INVALID, "ctx/maps is null");
+    HIP_TRY(hipSetDevice(c->device));
+    c->matMaps = rt_ctx::MatMaps();
+    return RT_OK;
+  }
+  const int word = rtmat::first_reserved(*m);
+  if (word >= 0) return fail(RT_ERR_INVALID, "material maps: reserved[%d] is %u, not 0", word, m->reserved[word]);
+  if (!c) return fail(RT_ERR_INVALID, "ctx/maps is null");
+  if (m->n_meshes != c->nMeshes) return fail(RT_ERR_INVALID, "material maps: %u meshes for a context of %u", m->n_meshes, c->nMeshes);
+  int rc = check_not_broken(c);  // (as rt_set_textures: nothing is uploaded to a context that refuses launches)
+  if (rc != RT_OK) return rc;
+  if (!c->tex) return fail(RT_ERR_STATE, "the context has no resident textures (rt_set_textures)");
+  rtmat::Tables tables;
+  std::string why;
+  if (!rtmat::build_tables(*m, c->tex.nTextures, &tables, &why)) return fail(RT_ERR_INVALID, "%s", why.c_str());
+  HIP_TRY(hipSetDevice(c->device));
+  // the new tables replace the old ones only when both are resident; the old ones are then freed under launches that may
+  // still read them, which hipFree waits for
+  rt_ctx::MatMaps fresh;
+  if ((rc = upload(&fresh.f0, tables.f0.data(), tables.f0.size())) != RT_OK ||
+      (rc = upload(&fresh.kdAlpha, tables.kdAlpha.data(), tables.kdAlpha.size())) != RT_OK)
+    return rc;
+  fresh.texGeneration = c->tex.generation;
+  c->matMaps = std::move(fresh);
+  return RT_OK;
+}
+
+int rt_render_material_device(rt_ctx* c, const rt_params* p, void* d_accum, void* stream, rt_stats* stats) {
+  rtk::MatRec R;
+  const int rc = material_checks(c, p, d_accum ? nullptr : "d_accum is null", &R);
+  if (rc != RT_OK) return rc;
+  return frame_device(c, p, R, d_accum, stream, stats);
+}
+
+int rt_render_material(rt_ctx* c, const rt_params* p, const float* bg, float* out_rgb, float* accum_out, rt_stats* stats) {
+  rtk::MatRec R;
+  const int rc = material_checks(c, p, outputs_refused(bg, out_rgb, accum_out), &R);
   if (rc != RT_OK) return rc;
   return frame_host(c, p, R, 1, bg, out_rgb, accum_out, stats);
 }

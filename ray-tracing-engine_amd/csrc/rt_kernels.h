@@ -247,14 +247,26 @@ struct TexRec {
   const TexDesc* desc;       // [n_textures]
   const float* texels;       // the pool: every texture's [height][width][3], one behind the other
 };
+// the frame with textured material maps (rt_render_material): TexRec's frame in which, beside the albedo, f0 and
+// (kd, alpha) of every shaded vertex come from textures of the same set, sampled at the same hit coordinate: meshF0's
+// texture gives f0 from its rgb, meshKdAlpha's gives kd from r and alpha from g (b is not read); kTexNone keeps the mesh's
+// own.  The first four pointers are TexRec's; the two tables are device memory the launch reads in stream order.
+struct MatRec {
+  const float* uv;              // [n_vertices][2]
+  const uint32_t* meshTex;      // [n_meshes]: the albedo's texture, or kTexNone
+  const TexDesc* desc;          // [n_textures]
+  const float* texels;          // the pool
+  const uint32_t* meshF0;       // [n_meshes]: f0's texture, or kTexNone
+  const uint32_t* meshKdAlpha;  // [n_meshes]: (kd, alpha)'s texture, or kTexNone
+};
 // Which variant a frame is, with its record (which the caller keeps alive over the launch call).  VIEWS_SHUTTER, many
 // views each under its own open shutter (rt_render_views_shutter), has none: tile t renders with views[tileView[t]]'s
 // camera, seed and slice under viewShutters[tileView[t]], from RenderArgs' three tables.  VIEWS_SHUTTER_VCOL and
 // VIEWS_SHUTTER_TEX are that frame with the VColRec / TexRec of a coloured / textured one.
 struct FrameVariant {
-  enum Kind { NONE, LENS, SHUTTER, LIGHTS, VIEWS_SHUTTER, PICK, VCOL, TEX, VIEWS_SHUTTER_VCOL, VIEWS_SHUTTER_TEX };
+  enum Kind { NONE, LENS, SHUTTER, LIGHTS, VIEWS_SHUTTER, PICK, VCOL, TEX, VIEWS_SHUTTER_VCOL, VIEWS_SHUTTER_TEX, MAT };
   Kind kind = NONE;
-  const void* rec = nullptr;  // the LensRec, ShutterRec, LightGroupsRec, PickRec, VColRec or TexRec of kind, else null
+  const void* rec = nullptr;  // the LensRec, ShutterRec, LightGroupsRec, PickRec, VColRec, TexRec or MatRec of kind, else null
   FrameVariant() = default;
   explicit FrameVariant(Kind k) : kind(k) {}
   FrameVariant(const LensRec& r) : kind(LENS), rec(&r) {}
@@ -263,6 +275,7 @@ struct FrameVariant {
   FrameVariant(const PickRec& r) : kind(PICK), rec(&r) {}
   FrameVariant(const VColRec& r) : kind(VCOL), rec(&r) {}
   FrameVariant(const TexRec& r) : kind(TEX), rec(&r) {}
+  FrameVariant(const MatRec& r) : kind(MAT), rec(&r) {}
   // the coloured or textured frame F under the multi-view shutter's generator (rt_render_views_shutter_albedo): F's
   // record with RenderArgs' three tables; any other F is the multi-view shutter frame itself
   static FrameVariant under_views_shutter(const FrameVariant& F) {
@@ -274,7 +287,7 @@ struct FrameVariant {
   // the variant in an error message: "<name> render launch failed"
   const char* name() const {
     static const char* const names[] = {"", "lens", "shutter", "light-group", "multi-view shutter", "light-pick", "vertex-colour", "textured",
-                                        "multi-view shutter vertex-colour", "multi-view shutter textured"};
+                                        "multi-view shutter vertex-colour", "multi-view shutter textured", "material-map"};
     return names[kind];
   }
 };
@@ -282,7 +295,8 @@ struct FrameVariant {
 // NONE); A as launch_render takes it: tileView null, but for VIEWS_SHUTTER a multi-view frame's with the three tables
 // set, and so for VIEWS_SHUTTER_VCOL and VIEWS_SHUTTER_TEX.  LIGHTS: accum is [G.n][height][width], slice g at accum + g * width * height.  PICK: pooled whenever A.flags bit 0
 // is set, whatever the scene's light count (a vertex sends m <= POOL_L shadow rays).  VCOL: a launch allocates
-// VP_VCOL_WORDS more words of LDS per wave (the vertex's parked kdDiffuse), and so does TEX.  hipErrorInvalidValue where A, the
+// VP_VCOL_WORDS more words of LDS per wave (the vertex's parked kdDiffuse), and so does TEX; MAT allocates VP_MAT_WORDS (the vertex's parked
+// material).  hipErrorInvalidValue where A, the
 // record or the scene's light count do not fit the variant.
 hipError_t launch_render_variant(const FrameVariant& F, bool brute_force, bool stats, const DevScene& S, const RenderArgs& A,
                                  float4* accum, unsigned long long* counters, hipStream_t stream);

@@ -241,6 +241,10 @@ constexpr int LT_VCOL = 16384;
 // from the texture sample at the hit's uv (tex_kd); it reaches the vertex pool and shade_direct_seq as the coloured
 // frame's does (their VC switch, a second producer of VColKd::kd).
 constexpr int LT_TEX = 32768;
+// A frame with textured material maps (rt_render_material): render_tile takes a MatRec and forms every vertex's whole
+// material from the samples at the hit's uv (tex_mat); it reaches the vertex pool and shade_direct_seq through their VC
+// switch as the payload VMat, which shades with bsdf_base(const rt_material&) in place of the mesh's DevMat.
+constexpr int LT_MAT = 65536;
 constexpr uint32_t kPrioMaxNodes = 65536;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(3))) u32x4* lds_u4_ptr;
@@ -938,6 +942,52 @@ RT_DEV f3 tex_kd(const DevScene& S, const TexRec& T, uint4 tv, float u, float v)
   return S.mats[tv.w].kd * diffuse;
 }
 
+// The material a vertex of a material-map frame shades with (rt_render_material): the hit mesh's, with albedo, f0 and
+// (kd, alpha) replaced by the samples of the mesh's three textures at the hit's one uv, each under its own texture's
+// filter and wraps; kTexNone keeps the mesh's field.  The three per-mesh indices and the three uv gathers are independent
+// of each other and go out together, the descriptors follow their indices, and the maps are sampled one after the other:
+// one map's six texel floats are live at most.  (The descriptor of a map that is kTexNone is texture 0's, which a
+// resident set always has, and is not used.)
+RT_DEV rt_material tex_mat(const DevScene& S, const MatRec& M, uint4 tv, float u, float v) {
+  const float2* uv = reinterpret_cast<const float2*>(M.uv);
+  const uint32_t ta = M.meshTex[tv.w], tf = M.meshF0[tv.w], tk = M.meshKdAlpha[tv.w];
+  const float2 a = uv[tv.x], b = uv[tv.y], c = uv[tv.z];
+  rt_material m = S.mats[tv.w];
+  const TexDesc Da = M.desc[ta != kTexNone ? ta : 0u], Df = M.desc[tf != kTexNone ? tf : 0u], Dk = M.desc[tk != kTexNone ? tk : 0u];
+  const float s = tex_coord(a.x, b.x, c.x, u, v), t = tex_coord(a.y, b.y, c.y, u, v);
+  if (ta != kTexNone) {
+    const f3 x = tex_sample(M.texels, Da, s, t);
+    m.albedo[0] = x.x, m.albedo[1] = x.y, m.albedo[2] = x.z;
+  }
+  if (tf != kTexNone) {
+    const f3 x = tex_sample(M.texels, Df, s, t);
+    m.f0[0] = x.x, m.f0[1] = x.y, m.f0[2] = x.z;
+  }
+  if (tk != kTexNone) {
+    const f3 x = tex_sample(M.texels, Dk, s, t);
+    m.kd = x.x, m.alpha = x.y;
+  }
+  return m;
+}
+// The VC switch's second payload: the vertex's whole material, and the eight rows of LDS ([8][64] floats in VColKd's
+// place behind the wave's stack rows and pool) where it is parked while the wave traverses, in rt_material's field order.
+struct VMat {
+  rt_material m;
+  float* park;
+};
+RT_DEV void park_mat(const VMat& vc, uint32_t lane) {
+  vc.park[lane] = vc.m.kd, vc.park[64 + lane] = vc.m.alpha;
+  for (int c = 0; c < 3; ++c) vc.park[(2 + c) * 64 + lane] = vc.m.albedo[c], vc.park[(5 + c) * 64 + lane] = vc.m.f0[c];
+}
+RT_DEV rt_material parked_mat(const VMat& vc, uint32_t lane) {
+  rt_material m;
+  m.kd = vc.park[lane], m.alpha = vc.park[64 + lane];
+  for (int c = 0; c < 3; ++c) m.albedo[c] = vc.park[(2 + c) * 64 + lane], m.f0[c] = vc.park[(5 + c) * 64 + lane];
+  return m;
+}
+template <class VC>
+constexpr bool is_vmat = std::is_same_v<VC, VMat>;
+
 // Renderer.cpp:63-104: photon-map radiance estimate at the vertex (HP: the heap's layout, WideHeap for k > 16)
 template <bool STATS, class HP = Heap>
 RT_DEV f3 shade_photon(const DevScene& S, const RenderArgs& A, f3 rayDir, const HitRec& h, const Lds& L, f3 hitNormal,
@@ -1027,12 +1077,15 @@ RT_DEV uint32_t loop_lights(const DevScene&, const PickArgs& a) { return a.R->m;
 // GROUPS (rt_render_lights): the terms go into *gc by group instead of into the returned colour, which stays 0.
 // PK = PickArgs (rt_render_pick): the light list is the sample's picked lights, in slot order, instead of the scene's.
 // VC = VColKd (rt_render_colors): the vertex's own kdDiffuse in place of the mesh's, parked in LDS over every walk.
+// VC = VMat (rt_render_material): the vertex's own material in place of the mesh's, parked in LDS likewise; the
+// light-independent half is formed from it behind every walk (the same operands every time, so the same bits).
 template <bool BRUTE, bool STATS, bool GROUPS = false, class PK = NoPick, class VC = NoVCol>
 RT_DEV f3 shade_direct_seq(const DevScene& S, Rng& g, f3 rayDir, const HitRec& h, uint32_t* stack, f3 hitNormal,
                            f3 point, LaneStats& st, const LightGroupsRec* G = nullptr, GroupCols* gc = nullptr, PK pk = PK(),
                            VC vc = VC()) {
   BsdfBase base = bsdf_base(S.matsDev[h.mesh], hitNormal, -rayDir);  // the light-independent half, once
   if constexpr (is_vcol<VC>) park_kd(vc, threadIdx.x & 63u);
+  if constexpr (is_vmat<VC>) park_mat(vc, threadIdx.x & 63u);  // (base is formed behind every walk: the mesh's is not used)
   f3 color = mk(0.f, 0.f, 0.f);
   if constexpr (GROUPS) group_cols_zero(*gc);
   for (uint32_t li = 0; li < loop_lights(S, pk); li++) {
@@ -1044,6 +1097,10 @@ RT_DEV f3 shade_direct_seq(const DevScene& S, Rng& g, f3 rayDir, const HitRec& h
     if constexpr (is_vcol<VC>) {
       asm volatile("" ::: "memory");  // (read back behind the walk, not held over it)
       base.kdDiffuse = parked_kd(vc, threadIdx.x & 63u);
+    }
+    if constexpr (is_vmat<VC>) {
+      asm volatile("" ::: "memory");  // (read back behind the walk, not held over it)
+      base = bsdf_base(parked_mat(vc, threadIdx.x & 63u), hitNormal, -rayDir);
     }
     const f3 bsdf = bsdf_apply(base, toLight);
     f3 radiance;
@@ -1077,6 +1134,8 @@ constexpr int VP_WORDS = VP_RES + 2 * POOL_L + 2;
 constexpr int VP_COMPACT_SAVES = 64 * POOL_L;  // words a compact pool is shorter by
 // (rt_render_colors) three rows more per wave: the vertex's kdDiffuse while the wave traverses (VColKd::park)
 constexpr int VP_VCOL_WORDS = 192;
+// (rt_render_material) eight rows per wave in their place: the vertex's material (VMat::park)
+constexpr int VP_MAT_WORDS = 8 * 64;
 // offsets of everything behind the per-light block, by layout
 template <int CP> struct VpLayout {  // CP = 0: full, 1: light parameters, 2: ... and no bounce directions, 3: keys, list and result bits only
   static constexpr int PER_LIGHT = CP ? 128 : 192;
@@ -1104,6 +1163,8 @@ static_assert(VP_WORDS == (int)rtbvh::kWavePoolWords && BLOCK == (int)rtbvh::kSt
 // VC = VColKd (rt_render_colors): the vertex's own kdDiffuse in place of the mesh's.  It is parked in three rows of LDS
 // behind the pool's words (the launcher allocates them for these instances alone) as the point is in the pool, and read
 // back behind the rounds as the point is: nothing more of the vertex is live while the wave traverses.
+// VC = VMat (rt_render_material): the vertex's own material, parked in eight rows in the same place and read back
+// behind the rounds into bsdf_base(const rt_material&).
 template <bool STATS, int LT, bool BOUNCE, bool GROUPS = false, class PK = NoPick, class VC = NoVCol>
 RT_DEV f3 vertex_pool(const DevScene& S, bool alive, bool bounceRay, Rng& g, f3 rayDir, uint32_t mesh, f3 hitNormal,
                       f3& point, f3& bdir, uint32_t* stack, uint32_t* pool, HitRec& next, bool& nextFound, LaneStats& st,
@@ -1115,6 +1176,7 @@ RT_DEV f3 vertex_pool(const DevScene& S, bool alive, bool bounceRay, Rng& g, f3 
   constexpr bool CP3 = (LT & LT_COMPACT3) != 0, CP2 = CP3 || (LT & LT_COMPACT2) != 0, CP = CP2 || (LT & LT_COMPACT) != 0;
   static_assert(!is_pick<PK> || !CP, "the picked frames' instances use the full pool layout: workers read directions, never a light");
   static_assert(!is_vcol<VC> || !CP, "the coloured frames' instances use the full pool layout, with the parked rows behind it");
+  static_assert(!is_vmat<VC> || !CP, "the material-map frames' instances use the full pool layout, with the parked rows behind it");
   using VP = VpLayout<CP3 ? 3 : CP2 ? 2 : CP ? 1 : 0>;
   float* fp = reinterpret_cast<float*>(pool);
   // 32 words: rank -> pixel lane (64 bytes) while rays are handed out; then rank -> victim
@@ -1134,6 +1196,7 @@ RT_DEV f3 vertex_pool(const DevScene& S, bool alive, bool bounceRay, Rng& g, f3 
   if (alive) {
     if (!CP3) fp[VP_PT + lane] = point.x, fp[VP_PT + 64 + lane] = point.y, fp[VP_PT + 128 + lane] = point.z;
     if constexpr (is_vcol<VC>) park_kd(vc, lane);
+    if constexpr (is_vmat<VC>) park_mat(vc, lane);
     // draw order of the reference: the light samples in light order (Renderer.cpp:52),
     // then the hemisphere sample (Renderer.cpp:164)
     if (CP3) gsave = g.s;  // (the light samples are re-drawn from here wherever they are needed)
@@ -1334,6 +1397,7 @@ RT_DEV f3 vertex_pool(const DevScene& S, bool alive, bool bounceRay, Rng& g, f3 
   if (alive) {
     BsdfBase base = bsdf_base<FR>(S.matsDev[mesh], hitNormal, -rayDir);  // the light-independent half, once
     if constexpr (is_vcol<VC>) base.kdDiffuse = parked_kd(vc, lane);
+    if constexpr (is_vmat<VC>) base = bsdf_base<FR>(parked_mat(vc, lane), hitNormal, -rayDir);  // (in place of the mesh's)
     Rng relight{gsave};
     for (uint32_t l = 0; l < nl; l++) {
       float rh3 = 0.f, rv3 = 0.f;
@@ -1540,7 +1604,7 @@ RT_DEV void group_samples_add(const RenderArgs& A, const LightGroupsRec& G, floa
 // The record a frame variant's instances take as a kernel argument of their own, by its LT_* bits: the lens, the shutter
 // of a single-view frame (a multi-view one reads its records from RenderArgs' tables), the light groups, the light
 // picks, the vertex colours, the textures (with or without LT_VIEWS | LT_SHUTTER beside them) — or none.  park: (LT_VCOL, LT_TEX) the wave's three parked rows of LDS
-// (VColKd), from the kernel that lays its LDS out.
+// (VColKd), or (LT_MAT) its eight (VMat), from the kernel that lays its LDS out.
 struct NoRec {};
 template <int LTV>
 using frame_rec_t = std::conditional_t<(LTV & LT_LENS) != 0, LensRec,
@@ -1548,7 +1612,8 @@ using frame_rec_t = std::conditional_t<(LTV & LT_LENS) != 0, LensRec,
                     std::conditional_t<(LTV & LT_PICK) != 0, PickRec,
                     std::conditional_t<(LTV & LT_VCOL) != 0, VColRec,
                     std::conditional_t<(LTV & LT_TEX) != 0, TexRec,
-                    std::conditional_t<(LTV & LT_SHUTTER) != 0 && (LTV & LT_VIEWS) == 0, ShutterRec, NoRec>>>>>>;
+                    std::conditional_t<(LTV & LT_MAT) != 0, MatRec,
+                    std::conditional_t<(LTV & LT_SHUTTER) != 0 && (LTV & LT_VIEWS) == 0, ShutterRec, NoRec>>>>>>>;
 // (what the instances without a record leave out; the others do not compile without theirs)
 template <int LTV>
 constexpr const frame_rec_t<LTV>* no_record() {
@@ -1562,7 +1627,7 @@ template <bool BRUTE, bool PHOTON, bool POOLED, bool STATS, int LTV, class HP = 
 RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restrict__ accum, const Lds& L, uint32_t* pool,
                         float* ex, uint32_t wave, LaneStats& st, const frame_rec_t<LTV>* rec = no_record<LTV>(),
                         float* park = nullptr) {
-  constexpr int LT = LTV & ~(LT_VIEWS | LT_LENS | LT_SHUTTER | LT_LIGHTS | LT_PICK | LT_VCOL | LT_TEX);
+  constexpr int LT = LTV & ~(LT_VIEWS | LT_LENS | LT_SHUTTER | LT_LIGHTS | LT_PICK | LT_VCOL | LT_TEX | LT_MAT);
   constexpr bool VIEWS = (LTV & LT_VIEWS) != 0;
   constexpr bool LENS = (LTV & LT_LENS) != 0;
   constexpr bool SHUTTER = (LTV & LT_SHUTTER) != 0;
@@ -1570,10 +1635,12 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
   constexpr bool PICK = (LTV & LT_PICK) != 0;
   constexpr bool VCOL = (LTV & LT_VCOL) != 0;
   constexpr bool TEX = (LTV & LT_TEX) != 0;
+  constexpr bool MAT = (LTV & LT_MAT) != 0;
   // (the surface side and the camera side are orthogonal: a record of colours or textures goes with the plain generator
   // or with the multi-view shutter's, the general camera form, whose tables come from RenderArgs)
   static_assert(!VCOL || (VIEWS == SHUTTER && !LENS && !LIGHTS && !PICK && !PHOTON), "vertex colours go with the plain frame or the multi-view shutter frame");
   static_assert(!TEX || (VIEWS == SHUTTER && !LENS && !LIGHTS && !PICK && !VCOL && !PHOTON), "textures go with the plain frame or the multi-view shutter frame");
+  static_assert(!MAT || (!VIEWS && !LENS && !SHUTTER && !LIGHTS && !PICK && !VCOL && !TEX && !PHOTON), "material maps go with the plain frame only");
   static_assert(!LIGHTS || (!VIEWS && !LENS && !SHUTTER && !PHOTON), "light groups go with the plain frame only");
   static_assert(!PICK || (!VIEWS && !LENS && !SHUTTER && !LIGHTS && !PHOTON), "light picks go with the plain frame only");
   static_assert(!LENS || !VIEWS, "no multi-view lens frames");
@@ -1660,6 +1727,8 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
         f3 nrm = mk(0.f, 0.f, 0.f), pt = nrm, bdir = nrm;
         uint32_t mesh = 0;
         VColKd vk{nrm, park};  // (LT_VCOL, LT_TEX) the vertex's kdDiffuse
+        std::conditional_t<MAT, VMat, NoVCol> vm;  // (LT_MAT) the vertex's material
+        if constexpr (MAT) vm = VMat{rt_material{}, park};
         // (the vertex set-up is three dependent loads deep: it goes out ahead of other waves'
         // arithmetic, like the pool loop that follows; +0.4 % on C2)
         if (!(LT & LT_NOPRIO)) __builtin_amdgcn_s_setprio(1);
@@ -1676,6 +1745,13 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
             float u, v;
             vertex_setup_ray<FR>(S, h.id, o, d, nrm, pt, tv, u, v);
             mesh = tv.w, vk.kd = tex_kd(S, *rec, tv, u, v);
+          }
+        } else if constexpr (MAT) {
+          if (alive) {
+            uint4 tv;
+            float u, v;
+            vertex_setup_ray<FR>(S, h.id, o, d, nrm, pt, tv, u, v);
+            mesh = tv.w, vm.m = tex_mat(S, *rec, tv, u, v);
           }
         } else
         if (alive) vertex_setup_ray<FR>(S, h.id, o, d, nrm, pt, mesh);
@@ -1701,6 +1777,9 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
         } else if constexpr (VCOL || TEX) {
           static_assert(!SHADOW_BODY, "the coloured and textured instances keep their trees in HBM / L2");
           c = vertex_pool<STATS, LT, true, false, NoPick, VColKd>(S, alive, bounce, g, d, mesh, nrm, pt, bdir, L.stack, pool, nh, nfound, st, nullptr, nullptr, NoPick(), vk);
+        } else if constexpr (MAT) {
+          static_assert(!SHADOW_BODY, "the material-map instances keep their trees in HBM / L2");
+          c = vertex_pool<STATS, LT, true, false, NoPick, VMat>(S, alive, bounce, g, d, mesh, nrm, pt, bdir, L.stack, pool, nh, nfound, st, nullptr, nullptr, NoPick(), vm);
         } else
         c = SHADOW_BODY && !bounce
                          ? vertex_pool<STATS, LT, false>(S, alive, false, g, d, mesh, nrm, pt, bdir, L.stack, pool, nh, nfound, st)
@@ -1744,6 +1823,10 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
         if (alive)
           c = shade_direct_seq<BRUTE, STATS, false, NoPick, VColKd>(S, g, d, h, L.stack, nrm, pt, st, nullptr, nullptr, NoPick(),
                                                                     VColKd{tex_kd(S, *rec, S.triShade[h.id], h.u, h.v), park});
+      } else if constexpr (MAT) {
+        if (alive)
+          c = shade_direct_seq<BRUTE, STATS, false, NoPick, VMat>(S, g, d, h, L.stack, nrm, pt, st, nullptr, nullptr, NoPick(),
+                                                                  VMat{tex_mat(S, *rec, S.triShade[h.id], h.u, h.v), park});
       } else {
         if (alive) c = shade_direct_seq<BRUTE, STATS>(S, g, d, h, L.stack, nrm, pt, st);
       }
@@ -2004,7 +2087,7 @@ __global__ __launch_bounds__(1024, 8) void k_trace_stream(DevScene S, const floa
 #include "rays_kernels.h"
 
 // ---------------------------------------------------------------- the frame's generator variants (rt_render_lens,
-// rt_render_shutter, rt_render_views_shutter, rt_render_lights, rt_render_pick, rt_render_colors, rt_render_textured)
+// rt_render_shutter, rt_render_views_shutter, rt_render_lights, rt_render_pick, rt_render_colors, rt_render_textured, rt_render_material)
 #include "frame_variants.h"
 
 // ---------------------------------------------------------------- frame assembly (multi-GPU)

@@ -151,6 +151,20 @@ int main(int argc, char** argv) {
     }
     GpuSettings::get().vcolors = true;
   }
+  if (args.matmaps() != 0) {
+    // -matmaps 1: the textured frame with f0 and (kd, alpha) from the images beside the scene's STOFF meshes too; it
+    // needs -textures 1 and composes with what that composes with
+    if (args.textures() == 0) {
+      std::cerr << "error: -matmaps needs -textures 1" << std::endl;
+      return 1;
+    }
+    if (GpuSettings::get().devices.size() > 1 || args.numPhotons() > 0 || args.adaptive() >= 0. || !args.shutter().empty() ||
+        args.aperture() > 0. || !args.lights().empty() || args.lightPick() != 0 || args.vcolors() != 0) {
+      std::cerr << "error: -matmaps runs on one GPU, without -p, -adaptive, -shutter, -aperture, -lights, -lightpick and -vcolors" << std::endl;
+      return 1;
+    }
+    GpuSettings::get().matmaps = true;
+  }
   if (args.textures() != 0) {
     // -textures 1: the frame with the images beside the scene's STOFF meshes as albedo, and nothing else
     if (GpuSettings::get().devices.size() > 1 || args.numPhotons() > 0 || args.adaptive() >= 0. || !args.shutter().empty() ||

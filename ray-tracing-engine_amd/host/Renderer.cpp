@@ -22,12 +22,13 @@ inline bool sceneHasVertexColors(const Scene& scene) {
 
 // The image -textures gives a mesh: <stem>.ppm beside the .off it was loaded from, if the mesh has texture coordinates
 // and that file can be opened ("" otherwise).
-inline std::string meshTextureFile(const Mesh& m) {
+// suffix: "" for the albedo image; "_f0" and "_kda" name the images -matmaps binds (<stem>_f0.ppm, <stem>_kda.ppm).
+inline std::string meshTextureFile(const Mesh& m, const std::string& suffix = "") {
   if (m.vertexUVs().empty() || m.vertexUVs().size() != 2 * m.vertexPositions().size()) return "";
   const std::string& off = m.sourceFile();
   const size_t dot = off.rfind('.'), slash = off.find_last_of("/\\");
   if (dot == std::string::npos || (slash != std::string::npos && dot < slash)) return "";
-  const std::string ppm = off.substr(0, dot) + ".ppm";
+  const std::string ppm = off.substr(0, dot) + suffix + ".ppm";
   return std::ifstream(ppm.c_str()) ? ppm : "";
 }
 
@@ -228,12 +229,21 @@ inline void Renderer::render(Image& image) {
     if (multi || p.use_photons) throw std::runtime_error("-textures runs on one GPU, without -p");
     std::vector<TextureImage> images;
     std::vector<rt_texture> textures;
-    std::vector<uint32_t> meshTexture;
+    std::vector<uint32_t> meshTexture, meshF0, meshKdAlpha;
     std::vector<float> uv;
+    // -matmaps 1 (extension): <stem>_f0.ppm and <stem>_kda.ppm beside the .off join the set, bilinear and repeating as
+    // the albedo image, and the frame goes through rt_render_material; a mesh without one keeps that field of its material
+    const bool matmaps = GpuSettings::get().matmaps;
+    uint32_t nMaps = 0;
     for (const Mesh& m : m_scene.meshes()) {
       const std::string file = meshTextureFile(m);
       meshTexture.push_back(file.empty() ? RT_TEX_NONE : static_cast<uint32_t>(images.size()));
       if (!file.empty()) images.push_back(TextureImage::loadPPM(file));
+      const std::string f0 = matmaps ? meshTextureFile(m, "_f0") : "", kda = matmaps ? meshTextureFile(m, "_kda") : "";
+      meshF0.push_back(f0.empty() ? RT_TEX_NONE : static_cast<uint32_t>(images.size()));
+      if (!f0.empty()) images.push_back(TextureImage::loadPPM(f0)), ++nMaps;
+      meshKdAlpha.push_back(kda.empty() ? RT_TEX_NONE : static_cast<uint32_t>(images.size()));
+      if (!kda.empty()) images.push_back(TextureImage::loadPPM(kda)), ++nMaps;
       // (the coordinates of a mesh without a texture are never read)
       if (m.vertexUVs().size() == 2 * m.vertexPositions().size()) uv.insert(uv.end(), m.vertexUVs().begin(), m.vertexUVs().end());
       else uv.insert(uv.end(), 2 * m.vertexPositions().size(), 0.f);
@@ -249,11 +259,18 @@ inline void Renderer::render(Image& image) {
     set.textures = textures.data(), set.mesh_texture = meshTexture.data(), set.vertex_uv = uv.data();
     GpuSession::check(rt_set_textures(ctx0, &set), "rt_set_textures");
     rt_stats st = {};
+    if (matmaps) {
+      rt_material_maps maps = {};
+      maps.n_meshes = set.n_meshes, maps.mesh_f0 = meshF0.data(), maps.mesh_kd_alpha = meshKdAlpha.data();
+      GpuSession::check(rt_set_material_maps(ctx0, &maps), "rt_set_material_maps");
+      GpuSession::check(rt_render_material(ctx0, &p, image.data(), result.data(), nullptr, &st), "rt_render_material");
+    } else
     GpuSession::check(rt_render_textured(ctx0, &p, image.data(), result.data(), nullptr, &st), "rt_render_textured");
     texturedFrame = true;
     m_stats = st;
     result.savePPM("update.ppm");
-    std::cout << "Raytracing with the textures of " << images.size() << " of " << m_scene.meshes().size() << " meshes... ["
+    if (matmaps) std::cout << "Material maps: " << nMaps << " images" << std::endl;
+    std::cout << "Raytracing with the textures of " << images.size() - nMaps << " of " << m_scene.meshes().size() << " meshes... ["
               << std::string(50, '#') << "] 100%" << std::endl;
     image = result;
   } else if (p.spp > 0) {

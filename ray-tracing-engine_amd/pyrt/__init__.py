@@ -194,6 +194,26 @@ class TextureSet(C.Structure):
                 ("reserved", C.c_uint32 * 4)]
 
 
+class MaterialMaps(C.Structure):
+    """rt_material_maps."""
+    _fields_ = [("n_meshes", C.c_uint32), ("mesh_f0", C.c_void_p), ("mesh_kd_alpha", C.c_void_p),
+                ("reserved", C.c_uint32 * 5)]
+
+
+def material_maps(n_meshes, mesh_f0=None, mesh_kd_alpha=None):
+    """The rt_material_maps of Context.set_material_maps' arguments, and the arrays it points into (keep them alive while
+    the structure is in use).  A table that is None is NULL: RT_TEX_NONE on every mesh."""
+    m = MaterialMaps()
+    keep = []
+    m.n_meshes = n_meshes
+    for field, table in (("mesh_f0", mesh_f0), ("mesh_kd_alpha", mesh_kd_alpha)):
+        if table is not None:
+            a = np.ascontiguousarray(table, np.uint32).reshape(-1)
+            keep.append(a)
+            setattr(m, field, a.ctypes.data)
+    return m, keep
+
+
 def texture_set(textures, mesh_texture, vertex_uv):
     """The rt_texture_set of Context.set_textures' arguments, and the arrays it points into (keep them alive while the
     structure is in use)."""
@@ -476,7 +496,8 @@ AMD_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_create", "rt_destroy", "rt
                "rt_render_colors", "rt_render_colors_device", "rt_render_aov_colors", "rt_render_aov_colors_device",
                "rt_set_textures", "rt_render_textured", "rt_render_textured_device", "rt_render_aov_textured",
                "rt_render_aov_textured_device", "rt_render_views_shutter_albedo", "rt_render_views_shutter_albedo_device",
-               "rt_render_aov_views_albedo", "rt_render_aov_views_albedo_device"]
+               "rt_render_aov_views_albedo", "rt_render_aov_views_albedo_device", "rt_set_material_maps",
+               "rt_render_material", "rt_render_material_device"]
 HOST_SYMBOLS = ["rt_host_scene_build", "rt_host_scene_desc", "rt_host_scene_free", "rt_host_last_error",
                 "rt_host_fill_background", "rt_host_save_ppm", "rt_host_kd_order", "rt_host_light_basis"]
 
@@ -661,6 +682,9 @@ def amd():
                                                      C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         L.rt_render_views_shutter_albedo_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Views), C.POINTER(Shutter),
                                                             C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        L.rt_set_material_maps.argtypes = [C.c_void_p, C.POINTER(MaterialMaps)]
+        L.rt_render_material.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        L.rt_render_material_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         L.rt_render_aov_views_albedo.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Views), C.c_uint32, C.POINTER(Aov)]
         L.rt_render_aov_views_albedo_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Views), C.c_uint32,
                                                         C.POINTER(Aov), C.c_void_p]
@@ -1169,6 +1193,38 @@ class Context:
         bgc = None if bg is None else np.ascontiguousarray(bg, np.float32)
         _check(amd().rt_render_textured(self._h, C.byref(params), _ptr(bgc), _ptr(out), _ptr(acc), C.byref(st)))
         return out, acc, st
+
+    def set_material_maps(self, mesh_f0=None, mesh_kd_alpha=None, release=False, n_meshes=None):
+        """rt_set_material_maps: per mesh, the texture of the RESIDENT set (an index, or TEX_NONE) that gives f0 (rgb) and
+        the one that gives kd (r) and alpha (g); either may be None (TEX_NONE on every mesh).  release=True releases the
+        maps.  n_meshes: the count the call states (the length of a given table, else the context's)."""
+        if release:
+            _check(amd().rt_set_material_maps(self._h, None))
+            return
+        if n_meshes is None:
+            given = mesh_f0 if mesh_f0 is not None else mesh_kd_alpha
+            n_meshes = len(given) if given is not None else self.scene.desc.n_meshes
+        m, keep = material_maps(n_meshes, mesh_f0, mesh_kd_alpha)
+        _check(amd().rt_set_material_maps(self._h, C.byref(m)))
+
+    def render_material(self, params, bg=None, want_accum=True):
+        """rt_render_material: the textured frame with f0 and (kd, alpha) from the resident material maps; returns (out
+        [h][w][3] or None without bg, accum [h][w][4] or None, stats)."""
+        w, h = params.width, params.height
+        out = np.empty((h, w, 3), np.float32) if bg is not None else None
+        acc = np.empty((h, w, 4), np.float32) if want_accum else None
+        st = Stats()
+        bgc = None if bg is None else np.ascontiguousarray(bg, np.float32)
+        _check(amd().rt_render_material(self._h, C.byref(params), _ptr(bgc), _ptr(out), _ptr(acc), C.byref(st)))
+        return out, acc, st
+
+    def render_material_device(self, params, d_accum, stream=0, stats=False):
+        """rt_render_material_device: accumulate into the caller-zeroed device d_accum [h][w][4] on `stream`; sample
+        ranges chain."""
+        st = Stats() if stats else None
+        _check(amd().rt_render_material_device(self._h, C.byref(params), C.c_void_p(d_accum), C.c_void_p(stream or None),
+                                               C.byref(st) if stats else None))
+        return st
 
     def render_textured_device(self, params, d_accum, stream=0, stats=False):
         """rt_render_textured_device: accumulate into the caller-zeroed device d_accum [h][w][4] on `stream`; sample
