@@ -37,6 +37,7 @@ RT_DEV ViewOfWave view_of_wave(const ViewRec* views, uint32_t tilesPerView) {
 // TEX (rt_render_aov_textured): the albedo channel sums the sample of the hit mesh's texture (tex_color), or the mesh's
 // albedo where it has none, from A's four tex* tables; the other instances do not read them.
 // VIEWS with VCOL or TEX (rt_render_aov_views_albedo): both at once, each as above.
+// launch_aov (below) picks the instance: views null is the single-view form, the surface part of `surface` the channel.
 template <bool BRUTE, bool VIEWS, bool VCOL = false, bool TEX = false>
 __global__ __launch_bounds__(64) void k_aov(DevScene S, AovArgs A) {
   __shared__ uint32_t lds[(rtbvh::kMaxDepth + 1) * 64];
@@ -100,63 +101,37 @@ __global__ __launch_bounds__(64) void k_aov(DevScene S, AovArgs A) {
   if (A.tri) A.tri[p1] = tri0;
 }
 
-hipError_t launch_aov(bool brute_force, const DevScene& S, const AovArgs& A, hipStream_t stream) {
-  const uint32_t tiles = ((A.width + 7u) / 8u) * ((A.height + 7u) / 8u);
-  if (tiles == 0 || A.s1 <= A.s0) return hipSuccess;
-  if (brute_force) hipLaunchKernelGGL((k_aov<true, false>), dim3(tiles), dim3(64), 0, stream, S, A);
-  else hipLaunchKernelGGL((k_aov<false, false>), dim3(tiles), dim3(64), 0, stream, S, A);
-  return hipGetLastError();
-}
-
-hipError_t launch_aov_colors(bool brute_force, const DevScene& S, const AovArgs& A, const float* vcol, hipStream_t stream) {
-  const uint32_t tiles = ((A.width + 7u) / 8u) * ((A.height + 7u) / 8u);
-  if (!vcol) return hipErrorInvalidValue;
-  if (tiles == 0 || A.s1 <= A.s0) return hipSuccess;
-  AovArgs C = A;
-  C.vcol = vcol;
-  if (brute_force) hipLaunchKernelGGL((k_aov<true, false, true>), dim3(tiles), dim3(64), 0, stream, S, C);
-  else hipLaunchKernelGGL((k_aov<false, false, true>), dim3(tiles), dim3(64), 0, stream, S, C);
-  return hipGetLastError();
-}
-
-hipError_t launch_aov_textured(bool brute_force, const DevScene& S, const AovArgs& A, const TexRec& T, hipStream_t stream) {
-  const uint32_t tiles = ((A.width + 7u) / 8u) * ((A.height + 7u) / 8u);
-  if (!T.uv || !T.meshTex || !T.desc || !T.texels) return hipErrorInvalidValue;
-  if (tiles == 0 || A.s1 <= A.s0) return hipSuccess;
-  AovArgs C = A;
-  C.texUv = T.uv, C.texMesh = T.meshTex, C.texDesc = T.desc, C.texels = T.texels;
-  if (brute_force) hipLaunchKernelGGL((k_aov<true, false, false, true>), dim3(tiles), dim3(64), 0, stream, S, C);
-  else hipLaunchKernelGGL((k_aov<false, false, false, true>), dim3(tiles), dim3(64), 0, stream, S, C);
-  return hipGetLastError();
-}
-
-hipError_t launch_aov_views(bool brute_force, const DevScene& S, const AovArgs& A, const ViewRec* views, uint32_t nViews, hipStream_t stream) {
-  AovArgs V = A;
-  V.views = views, V.tilesPerView = ((A.width + 7u) / 8u) * ((A.height + 7u) / 8u);
-  if (V.tilesPerView == 0 || nViews == 0 || A.s1 <= A.s0) return hipSuccess;
-  if ((uint64_t)V.tilesPerView * nViews > 0x7fffffffull) return hipErrorInvalidValue;  // (a tile holds a pixel: n w h < 2^31 keeps it below)
-  if (brute_force) hipLaunchKernelGGL((k_aov<true, true>), dim3(V.tilesPerView * nViews), dim3(64), 0, stream, S, V);
-  else hipLaunchKernelGGL((k_aov<false, true>), dim3(V.tilesPerView * nViews), dim3(64), 0, stream, S, V);
-  return hipGetLastError();
-}
-
-hipError_t launch_aov_views_albedo(bool brute_force, const DevScene& S, const AovArgs& A, const ViewRec* views, uint32_t nViews,
-                                   const float* vcol, const TexRec* T, hipStream_t stream) {
-  if ((vcol != nullptr) == (T != nullptr)) return hipErrorInvalidValue;
-  if (T && (!T->uv || !T->meshTex || !T->desc || !T->texels)) return hipErrorInvalidValue;
-  AovArgs V = A;
-  V.views = views, V.tilesPerView = ((A.width + 7u) / 8u) * ((A.height + 7u) / 8u);
-  if (V.tilesPerView == 0 || nViews == 0 || A.s1 <= A.s0) return hipSuccess;
-  if ((uint64_t)V.tilesPerView * nViews > 0x7fffffffull) return hipErrorInvalidValue;  // (as launch_aov_views)
-  const dim3 grid(V.tilesPerView * nViews);
-  if (vcol) {
-    V.vcol = vcol;
-    if (brute_force) hipLaunchKernelGGL((k_aov<true, true, true, false>), grid, dim3(64), 0, stream, S, V);
-    else hipLaunchKernelGGL((k_aov<false, true, true, false>), grid, dim3(64), 0, stream, S, V);
+template <bool VCOL, bool TEX>
+static void launch_aov_instance(bool brute_force, dim3 grid, hipStream_t stream, const DevScene& S, const AovArgs& A) {
+  if (A.views) {
+    if (brute_force) hipLaunchKernelGGL((k_aov<true, true, VCOL, TEX>), grid, dim3(64), 0, stream, S, A);
+    else hipLaunchKernelGGL((k_aov<false, true, VCOL, TEX>), grid, dim3(64), 0, stream, S, A);
   } else {
-    V.texUv = T->uv, V.texMesh = T->meshTex, V.texDesc = T->desc, V.texels = T->texels;
-    if (brute_force) hipLaunchKernelGGL((k_aov<true, true, false, true>), grid, dim3(64), 0, stream, S, V);
-    else hipLaunchKernelGGL((k_aov<false, true, false, true>), grid, dim3(64), 0, stream, S, V);
+    if (brute_force) hipLaunchKernelGGL((k_aov<true, false, VCOL, TEX>), grid, dim3(64), 0, stream, S, A);
+    else hipLaunchKernelGGL((k_aov<false, false, VCOL, TEX>), grid, dim3(64), 0, stream, S, A);
   }
+}
+
+hipError_t launch_aov(bool brute_force, const DevScene& S, const AovArgs& A, const ViewRec* views, uint32_t nViews,
+                      const FrameVariant& surface, hipStream_t stream) {
+  AovArgs C = A;
+  // the albedo channel's tables: a record with a null one is refused whatever the launch's size
+  if (surface.surface == FrameVariant::VCOL) {
+    const VColRec* R = static_cast<const VColRec*>(surface.rec);
+    if (!R || SurfVCol::refused(*R)) return hipErrorInvalidValue;
+    C.vcol = R->vcol;
+  } else if (surface.surface == FrameVariant::TEX) {
+    const TexRec* T = static_cast<const TexRec*>(surface.rec);
+    if (!T || SurfTex::refused(*T)) return hipErrorInvalidValue;
+    C.texUv = T->uv, C.texMesh = T->meshTex, C.texDesc = T->desc, C.texels = T->texels;
+  } else if (surface.surface != FrameVariant::NONE) return hipErrorInvalidValue;  // (no albedo channel of material maps)
+  const uint32_t tiles = ((A.width + 7u) / 8u) * ((A.height + 7u) / 8u);
+  if (views) C.views = views, C.tilesPerView = tiles;
+  if (tiles == 0 || (views && nViews == 0) || A.s1 <= A.s0) return hipSuccess;
+  if (views && (uint64_t)tiles * nViews > 0x7fffffffull) return hipErrorInvalidValue;  // (a tile holds a pixel: n w h < 2^31 keeps it below)
+  const dim3 grid(views ? tiles * nViews : tiles);
+  if (surface.surface == FrameVariant::VCOL) launch_aov_instance<true, false>(brute_force, grid, stream, S, C);
+  else if (surface.surface == FrameVariant::TEX) launch_aov_instance<false, true>(brute_force, grid, stream, S, C);
+  else launch_aov_instance<false, false>(brute_force, grid, stream, S, C);
   return hipGetLastError();
 }

@@ -24,29 +24,29 @@
 //   light picks   LT_PICK                PickRec: every sample draws m <= POOL_L indices into the record's table of scaled
 //                                        lights and all of its vertices shade with those (vertex_pool's and
 //                                        shade_direct_seq's PICK switch): pooled whatever the scene's light count
-//   vertex colours LT_VCOL               VColRec: every shaded vertex forms its kdDiffuse from the colours of the hit
+// Those are the GENERATOR parts: what forms a sample's primary ray, splits its samples or lists its lights.  The SURFACE
+// parts are rt_kernels.hip's surface policies, what a path vertex shades with:
+//   vertex colours SurfVCol (LT_VCOL)    VColRec: every shaded vertex forms its kdDiffuse from the colours of the hit
 //                                        triangle's vertices (vertex_kd) and shades with it (vertex_pool's and
-//                                        shade_direct_seq's VC switch); a launch allocates VP_VCOL_WORDS more words of
-//                                        LDS per wave, where it is parked over every walk
-//   textures      LT_TEX                 TexRec: every shaded vertex of a mesh with a texture forms its kdDiffuse from
-//                                        the texture's sample at the hit's uv (tex_kd) and shades with it through the
-//                                        same VC switch and the same parked rows as a coloured frame's
-//   views+shutter+colours   LT_VIEWS | LT_SHUTTER | LT_VCOL   VColRec: the camera side of the views+shutter row (the
-//   views+shutter+textures  LT_VIEWS | LT_SHUTTER | LT_TEX    TexRec   three tables of RenderArgs) and the surface side of
-//                                        the colour / texture row (the record, the parked rows) in one instance; the
-//                                        two meet nowhere in render_tile: the sample's primary ray is complete before
-//                                        the first vertex reads the record
-//   material maps LT_MAT                 MatRec: every shaded vertex forms its whole material from up to three samples
-//                                        at the hit's uv (tex_mat: albedo, f0, (kd, alpha)) and shades with
-//                                        bsdf_base(const rt_material&) of it (the VC switch's second payload, VMat); a
-//                                        launch allocates VP_MAT_WORDS words of LDS per wave, the eight parked rows
-// A new variant supplies a row of the same kind (a struct below, a FrameVariant kind, a case in launch_render_variant):
-// its LT_* bits, its record, the stack rows its sample hand-over needs, and its argument check.
+//                                        shade_direct_seq's VC switch), parked in three rows of LDS over every walk
+//   textures      SurfTex (LT_TEX)       TexRec: every shaded vertex of a mesh with a texture forms its kdDiffuse from
+//                                        the texture's sample at the hit's uv (tex_kd), in the same three rows
+//   material maps SurfMat (LT_MAT)       MatRec: every shaded vertex forms its whole material from up to three samples
+//                                        at the hit's uv (tex_mat: albedo, f0, (kd, alpha)), parked in eight rows, and
+//                                        shades with bsdf_base(const rt_material&) of it
+// A variant is one generator part with one surface part (Variant<G, SF>): its LT_* bits are the OR of theirs, its record
+// the one part's that has one, its LDS the generator's stack rows and the surface's parked rows.  The two meet nowhere in
+// render_tile: the sample's primary ray is complete before the first vertex reads the surface's record.  variant_exists
+// says which pairs are compiled: every generator alone, every surface under the plain generator, and the colours and the
+// textures under views+shutter (rt_render_views_shutter_albedo); the launcher refuses every other pair.
+// A new generator supplies a Gen* row below (its LT_* bits, its record, the stack rows its sample hand-over needs, its
+// argument check), a FrameVariant::Gen and a case in launch_render_variant.  A new surface supplies a policy in
+// rt_kernels.hip, a FrameVariant::Surface and a case in launch_surface; a new pair, a term in variant_exists.
 // (included by rt_kernels.hip inside namespace rtk: shares its device functions)
 
 static_assert(LG_EX_ROWS * BLOCK <= VP_WORDS, "the pooled instances hand the groups' samples over in the pool's words");
 
-// the fewest stack rows of a launch whose waves park a value behind them (VariantVCol's ROWS and ROWS_POOLED)
+// the fewest stack rows of a launch whose waves park a value behind them (the ROWS and ROWS_POOLED of their generators)
 constexpr uint32_t kParkMinRows = 4;
 
 // k_render (no photons) with the variant's record R beside its arguments
@@ -60,13 +60,10 @@ __global__ __launch_bounds__(BLOCK, MINW) void k_render_rec(DevScene S, RenderAr
   const Lds L = carve_lds<false>(lds, A.stackLevels, 0);
   uint32_t* pool = lds + A.stackLevels * BLOCK;
   float* ex = reinterpret_cast<float*>(POOLED ? pool : lds);
-  // (LT_VCOL, LT_TEX) then three rows where a vertex's kdDiffuse is parked: behind everything launch_variant2 allocates before
-  // them — max(stackLevels, kParkMinRows) stack rows and, with one, the pool
+  // then (a surface with rows) the rows where a vertex's value is parked: behind everything launch_variant2 allocates
+  // before them — max(stackLevels, kParkMinRows) stack rows and, with one, the pool
   float* park = nullptr;
-  if constexpr ((LTV & (LT_VCOL | LT_TEX)) != 0)
-    park = reinterpret_cast<float*>(lds + (A.stackLevels < kParkMinRows ? kParkMinRows : A.stackLevels) * BLOCK + (POOLED ? VP_WORDS : 0));
-  // (LT_MAT) eight rows in the same place: the vertex's material
-  if constexpr ((LTV & LT_MAT) != 0)
+  if constexpr (surface_t<LTV>::Parked::ROWS != 0)
     park = reinterpret_cast<float*>(lds + (A.stackLevels < kParkMinRows ? kParkMinRows : A.stackLevels) * BLOCK + (POOLED ? VP_WORDS : 0));
   LaneStats st;
   const uint32_t t0 = blockIdx.x * A.tilesPerBlock, t1 = min(A.n_tiles, t0 + A.tilesPerBlock);
@@ -75,81 +72,68 @@ __global__ __launch_bounds__(BLOCK, MINW) void k_render_rec(DevScene S, RenderAr
   else flush_stats_striped(st, counters);  // (launch_variant2 folds the stripes)
 }
 
-// The variants' rows.  ROWS, ROWS_POOLED: the fewest stack rows a launch without / with a vertex pool allocates (the
+// The generators' rows.  ROWS, ROWS_POOLED: the fewest stack rows a launch without / with a vertex pool allocates (the
 // hand-over area lies in the stack rows without a pool, in the pool's words with one: launch_render2's four in both
 // cases, LG_EX_ROWS and none for the light groups).  refused: the arguments the launcher answers hipErrorInvalidValue to.
-struct VariantLens {
-  static constexpr int LTV = LT_LENS;
+struct GenPlain {
+  static constexpr int LT = 0;
+  using Rec = NoRec;
+  static constexpr uint32_t ROWS = 4, ROWS_POOLED = 4;
+  static bool refused(const DevScene&, const RenderArgs& A, const Rec&) { return A.tileView != nullptr; }
+};
+struct GenLens {
+  static constexpr int LT = LT_LENS;
   using Rec = LensRec;
   static constexpr uint32_t ROWS = 4, ROWS_POOLED = 4;
   static bool refused(const DevScene&, const RenderArgs& A, const Rec&) { return A.tileView != nullptr; }  // (no multi-view lens frames)
 };
-struct VariantShutter {
-  static constexpr int LTV = LT_SHUTTER;
+struct GenShutter {
+  static constexpr int LT = LT_SHUTTER;
   using Rec = ShutterRec;
   static constexpr uint32_t ROWS = 4, ROWS_POOLED = 4;
-  static bool refused(const DevScene&, const RenderArgs& A, const Rec&) { return A.tileView != nullptr; }  // (those are VariantViewsShutter's)
+  static bool refused(const DevScene&, const RenderArgs& A, const Rec&) { return A.tileView != nullptr; }  // (those are GenViewsShutter's)
 };
-struct VariantLights {
-  static constexpr int LTV = LT_LIGHTS;
+struct GenLights {
+  static constexpr int LT = LT_LIGHTS;
   using Rec = LightGroupsRec;
   static constexpr uint32_t ROWS = LG_EX_ROWS, ROWS_POOLED = 0;
   static bool refused(const DevScene& S, const RenderArgs& A, const Rec& G) {
     return A.tileView || G.n < 1u || G.n > (uint32_t)RT_LIGHT_GROUPS_MAX || S.n_lights > 32u;
   }
 };
-struct VariantPick {
-  static constexpr int LTV = LT_PICK;
+struct GenPick {
+  static constexpr int LT = LT_PICK;
   using Rec = PickRec;
   static constexpr uint32_t ROWS = 4, ROWS_POOLED = 4;
   static bool refused(const DevScene&, const RenderArgs& A, const Rec& R) {
     return A.tileView || R.m < 1u || R.m > (uint32_t)RT_PICK_SLOTS_MAX || R.n == 0u || !R.thresholds || !R.lights;
   }
 };
-struct VariantVCol {
-  static constexpr int LTV = LT_VCOL;
-  using Rec = VColRec;
-  static constexpr uint32_t ROWS = 4, ROWS_POOLED = 4;
-  static bool refused(const DevScene&, const RenderArgs& A, const Rec& R) { return A.tileView || !R.vcol; }
-};
-struct VariantTex {
-  static constexpr int LTV = LT_TEX;
-  using Rec = TexRec;
-  static constexpr uint32_t ROWS = 4, ROWS_POOLED = 4;
-  static bool refused(const DevScene&, const RenderArgs& A, const Rec& R) {
-    return A.tileView || !R.uv || !R.meshTex || !R.desc || !R.texels;
-  }
-};
-struct VariantMat {
-  static constexpr int LTV = LT_MAT;
-  using Rec = MatRec;
-  static constexpr uint32_t ROWS = 4, ROWS_POOLED = 4;
-  static bool refused(const DevScene&, const RenderArgs& A, const Rec& R) {
-    return A.tileView || !R.uv || !R.meshTex || !R.desc || !R.texels || !R.meshF0 || !R.meshKdAlpha;
-  }
-};
-struct VariantViewsShutter {
-  static constexpr int LTV = LT_VIEWS | LT_SHUTTER;
+struct GenViewsShutter {
+  static constexpr int LT = LT_VIEWS | LT_SHUTTER;
   using Rec = NoRec;
   static constexpr uint32_t ROWS = 4, ROWS_POOLED = 4;
   // (the three tables of a multi-view shutter frame)
   static bool refused(const DevScene&, const RenderArgs& A, const Rec&) { return !A.tileView || !A.views || !A.viewShutters; }
 };
 
-// The surface rows under the multi-view shutter's generator (rt_render_views_shutter_albedo): VariantViewsShutter's
-// tables and VariantVCol's / VariantTex's record, rows and parked words.
-struct VariantViewsShutterVCol {
-  static constexpr int LTV = LT_VIEWS | LT_SHUTTER | LT_VCOL;
-  using Rec = VColRec;
-  static constexpr uint32_t ROWS = 4, ROWS_POOLED = 4;
-  static bool refused(const DevScene&, const RenderArgs& A, const Rec& R) { return !A.tileView || !A.views || !A.viewShutters || !R.vcol; }
-};
-struct VariantViewsShutterTex {
-  static constexpr int LTV = LT_VIEWS | LT_SHUTTER | LT_TEX;
-  using Rec = TexRec;
-  static constexpr uint32_t ROWS = 4, ROWS_POOLED = 4;
-  static bool refused(const DevScene&, const RenderArgs& A, const Rec& R) {
-    return !A.tileView || !A.views || !A.viewShutters || !R.uv || !R.meshTex || !R.desc || !R.texels;
+// the pairs that are compiled, by the parts' LT_* bits ((0, 0), the plain frame itself, is launch_render's)
+constexpr bool variant_exists(int gen, int surface) {
+  return surface == 0 || gen == 0 || (gen == (LT_VIEWS | LT_SHUTTER) && (surface == LT_VCOL || surface == LT_TEX));
+}
+
+// generator G with surface SF
+template <class G, class SF>
+struct Variant {
+  static constexpr bool SURFACE = SF::LT != 0;
+  static_assert(!SURFACE || std::is_same_v<typename G::Rec, NoRec>, "k_render_rec takes one record: the generator's or the surface's");
+  static constexpr int LTV = G::LT | SF::LT;
+  using Rec = std::conditional_t<SURFACE, typename SF::Rec, typename G::Rec>;
+  static constexpr uint32_t ROWS = G::ROWS, ROWS_POOLED = G::ROWS_POOLED;
+  static constexpr uint32_t PARK_WORDS = SF::Parked::ROWS * 64;  // (the vertex's value behind the stack rows and pool: k_render_rec's `park`)
+  static bool refused(const DevScene& S, const RenderArgs& A, const Rec& R) {
+    if constexpr (SURFACE) return G::refused(S, A, NoRec()) || SF::refused(R);
+    else return G::refused(S, A, R);
   }
 };
 
@@ -167,9 +151,7 @@ static hipError_t launch_variant2(bool stats, const DevScene& S, const RenderArg
                                   unsigned long long* counters, hipStream_t stream) {
   if (A.n_tiles == 0) return hipSuccess;
   constexpr uint32_t minRows = POOLED ? V::ROWS_POOLED : V::ROWS;
-  // (a coloured or textured frame's wave parks the vertex's kdDiffuse behind its stack rows and pool: k_render_rec's `park`)
-  // (a material-map frame's parks the vertex's whole material there)
-  constexpr uint32_t parkWords = (V::LTV & LT_MAT) != 0 ? VP_MAT_WORDS : (V::LTV & (LT_VCOL | LT_TEX)) != 0 ? VP_VCOL_WORDS : 0;
+  constexpr uint32_t parkWords = V::PARK_WORDS;
   static_assert(parkWords == 0 || minRows == kParkMinRows, "k_render_rec places the parked rows behind kParkMinRows stack rows at least");
   const size_t ldsBytes = 4u * ((A.stackLevels < minRows ? minRows : A.stackLevels) * BLOCK + (POOLED ? VP_WORDS : 0) + parkWords);
   RenderArgs A1 = A;
@@ -195,30 +177,38 @@ static hipError_t launch_variant(bool brute_force, bool stats, const DevScene& S
   return launch_variant2<V, false, false>(stats, S, A, R, accum, counters, stream);
 }
 
+// F's launch under generator G: by F's surface, the pairs that exist
+template <class G, class SF>
+static hipError_t launch_pair(const FrameVariant& F, bool brute_force, bool stats, const DevScene& S, const RenderArgs& A, float4* accum,
+                              unsigned long long* counters, hipStream_t stream) {
+  if constexpr (!variant_exists(G::LT, SF::LT) || (G::LT | SF::LT) == 0) return hipErrorInvalidValue;  // (nothing of the pair is instantiated)
+  else {
+    using V = Variant<G, SF>;
+    if constexpr (std::is_same_v<typename V::Rec, NoRec>) return launch_variant<V>(brute_force, stats, S, A, NoRec(), accum, counters, stream);
+    else return launch_variant<V>(brute_force, stats, S, A, *static_cast<const typename V::Rec*>(F.rec), accum, counters, stream);
+  }
+}
+template <class G>
+static hipError_t launch_surface(const FrameVariant& F, bool brute_force, bool stats, const DevScene& S, const RenderArgs& A, float4* accum,
+                                 unsigned long long* counters, hipStream_t stream) {
+  switch (F.surface) {
+    case FrameVariant::NONE: return launch_pair<G, SurfNone>(F, brute_force, stats, S, A, accum, counters, stream);
+    case FrameVariant::VCOL: return launch_pair<G, SurfVCol>(F, brute_force, stats, S, A, accum, counters, stream);
+    case FrameVariant::TEX: return launch_pair<G, SurfTex>(F, brute_force, stats, S, A, accum, counters, stream);
+    case FrameVariant::MAT: return launch_pair<G, SurfMat>(F, brute_force, stats, S, A, accum, counters, stream);
+  }
+  return hipErrorInvalidValue;
+}
+
 hipError_t launch_render_variant(const FrameVariant& F, bool brute_force, bool stats, const DevScene& S, const RenderArgs& A,
                                  float4* accum, unsigned long long* counters, hipStream_t stream) {
-  switch (F.kind) {
-    case FrameVariant::LENS:
-      return launch_variant<VariantLens>(brute_force, stats, S, A, *static_cast<const LensRec*>(F.rec), accum, counters, stream);
-    case FrameVariant::SHUTTER:
-      return launch_variant<VariantShutter>(brute_force, stats, S, A, *static_cast<const ShutterRec*>(F.rec), accum, counters, stream);
-    case FrameVariant::LIGHTS:
-      return launch_variant<VariantLights>(brute_force, stats, S, A, *static_cast<const LightGroupsRec*>(F.rec), accum, counters, stream);
-    case FrameVariant::PICK:
-      return launch_variant<VariantPick>(brute_force, stats, S, A, *static_cast<const PickRec*>(F.rec), accum, counters, stream);
-    case FrameVariant::VCOL:
-      return launch_variant<VariantVCol>(brute_force, stats, S, A, *static_cast<const VColRec*>(F.rec), accum, counters, stream);
-    case FrameVariant::TEX:
-      return launch_variant<VariantTex>(brute_force, stats, S, A, *static_cast<const TexRec*>(F.rec), accum, counters, stream);
-    case FrameVariant::MAT:
-      return launch_variant<VariantMat>(brute_force, stats, S, A, *static_cast<const MatRec*>(F.rec), accum, counters, stream);
-    case FrameVariant::VIEWS_SHUTTER:
-      return launch_variant<VariantViewsShutter>(brute_force, stats, S, A, NoRec(), accum, counters, stream);
-    case FrameVariant::VIEWS_SHUTTER_VCOL:
-      return launch_variant<VariantViewsShutterVCol>(brute_force, stats, S, A, *static_cast<const VColRec*>(F.rec), accum, counters, stream);
-    case FrameVariant::VIEWS_SHUTTER_TEX:
-      return launch_variant<VariantViewsShutterTex>(brute_force, stats, S, A, *static_cast<const TexRec*>(F.rec), accum, counters, stream);
-    case FrameVariant::NONE: break;
+  switch (F.gen) {
+    case FrameVariant::PLAIN: return launch_surface<GenPlain>(F, brute_force, stats, S, A, accum, counters, stream);
+    case FrameVariant::LENS: return launch_surface<GenLens>(F, brute_force, stats, S, A, accum, counters, stream);
+    case FrameVariant::SHUTTER: return launch_surface<GenShutter>(F, brute_force, stats, S, A, accum, counters, stream);
+    case FrameVariant::LIGHTS: return launch_surface<GenLights>(F, brute_force, stats, S, A, accum, counters, stream);
+    case FrameVariant::PICK: return launch_surface<GenPick>(F, brute_force, stats, S, A, accum, counters, stream);
+    case FrameVariant::VIEWS_SHUTTER: return launch_surface<GenViewsShutter>(F, brute_force, stats, S, A, accum, counters, stream);
   }
-  return hipErrorInvalidValue;  // (the plain frame is launch_render's)
+  return hipErrorInvalidValue;
 }

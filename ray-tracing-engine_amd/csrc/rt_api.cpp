@@ -691,16 +691,26 @@ struct TileList {
 
 // What forms or splits a frame's samples in place of the plain frame, if anything: the thin lens of rt_render_lens, the
 // open shutter of rt_render_shutter, the light groups of rt_render_lights (dAccum then holds one slice per group) or the
-// light picks of rt_render_pick, with the record its kernels take; their callers have refused photons and the wavefront bit.  A multi-view shutter frame
-// carries its records in its TileList instead: launch_frame tells it from them.
+// light picks of rt_render_pick — and what its vertices shade with in place of their meshes' materials: the vertex colours
+// of rt_render_colors, the textures of rt_render_textured or the material maps of rt_render_material — with the record
+// its kernels take; their callers have refused photons and the wavefront bit (frame_params_checks).  A multi-view
+// shutter frame carries its records in its TileList instead: launch_frame tells it from them.
 using FrameGen = rtk::FrameVariant;
+
+// What every such frame refuses of a p of the right shape; noun names the frames in the messages.
+int frame_params_checks(const rt_params* p, const char* noun) {
+  if (p->world > 1) return fail(RT_ERR_UNSUPPORTED, "tile-sharded %s frames (world %u) are not supported", noun, p->world);
+  if (p->use_photons) return fail(RT_ERR_UNSUPPORTED, "%s frames do not shade from the photon map", noun);
+  if (p->reserved[2] & 1u) return fail(RT_ERR_UNSUPPORTED, "%s frames do not run the wavefront integrator", noun);
+  return RT_OK;
+}
 
 // Launch the integrate kernel for p on `stream`, bracketed by an event pair.  own: render those wave tiles only.
 // gen: the frame's variant, if any.
 int launch_frame(rt_ctx* c, const rt_params* p, float4* dAccum, hipStream_t stream, int* evIndex,
                  const TileList* own = nullptr, const FrameGen& gen = FrameGen()) {
   const SampleRange sr = sample_range(*p);
-  const uint32_t sshift = own ? own->sshift : choose_sshift(c, p, sr.count, gen.kind == FrameGen::PICK);
+  const uint32_t sshift = own ? own->sshift : choose_sshift(c, p, sr.count, gen.gen == FrameGen::PICK);
   int rc = RT_OK;
   rtk::RenderArgs A;
   A.sshift = sshift;
@@ -746,7 +756,7 @@ int launch_frame(rt_ctx* c, const rt_params* p, float4* dAccum, hipStream_t stre
     if (const FrameGen V = A.viewShutters ? FrameGen::under_views_shutter(gen) : gen) {
       hipError_t he = rtk::launch_render_variant(V, p->accel == RT_ACCEL_BRUTE, p->collect_stats != 0, c->S, A, dAccum,
                                                  c->dCounters.get(), stream);
-      if (he != hipSuccess) return fail(RT_ERR_HIP, "%s render launch failed: %s", V.name(), hipGetErrorString(he));
+      if (he != hipSuccess) return fail(RT_ERR_HIP, "%s render launch failed: %s", V.name().c_str(), hipGetErrorString(he));
     } else if (!wavefront) {
       hipError_t he = rtk::launch_render(p->accel == RT_ACCEL_BRUTE, p->use_photons != 0, p->collect_stats != 0, c->S, A,
                                          dAccum, c->dCounters.get(), stream);
@@ -2685,46 +2695,67 @@ rtk::AovArgs aov_args(const rt_params& q, const rt_aov& out) {
   return A;
 }
 
-// what the albedo channel of an AOV pass sums: the mesh's albedo, the resident vertex colours' interpolation
-// (rt_render_aov_colors) or the resident textures' sample (rt_render_aov_textured)
-enum AovAlbedo { ALBEDO_MESH, ALBEDO_COLORS, ALBEDO_TEXTURES };
-static_assert(ALBEDO_MESH == RT_ALBEDO_MATERIAL && ALBEDO_COLORS == RT_ALBEDO_COLORS && ALBEDO_TEXTURES == RT_ALBEDO_TEXTURES,
-              "the public constants of the *_albedo forms are this enumeration");
-// (of a checked `albedo` argument)
-inline AovAlbedo albedo_kind(uint32_t albedo) { return static_cast<AovAlbedo>(albedo); }
-
-// RT_ERR_STATE where the context lacks what the albedo channel reads
-int aov_albedo_resident(const rt_ctx* c, AovAlbedo alb) {
-  if (alb == ALBEDO_COLORS && !c->vcol) return fail(RT_ERR_STATE, "the context has no resident vertex colours (rt_set_vertex_colors)");
-  if (alb == ALBEDO_TEXTURES && !c->tex) return fail(RT_ERR_STATE, "the context has no resident textures (rt_set_textures)");
+// What the vertices of a frame shade with, or the albedo channel of an AOV pass sums, in place of the meshes' own: the
+// record its kernels take, built from the context's resident data, and the FrameGen that names it (gen points into this
+// object, which its owner keeps alive over the launch call).
+struct SurfaceGen {
+  rtk::VColRec vcol{};
+  rtk::TexRec tex{};
+  rtk::MatRec mat{};
+  FrameGen gen;
+  SurfaceGen() = default;
+  SurfaceGen(const SurfaceGen&) = delete;
+  SurfaceGen& operator=(const SurfaceGen&) = delete;
+};
+// (of a checked `albedo` argument of the *_albedo forms)
+inline FrameGen::Surface albedo_surface(uint32_t albedo) {
+  return albedo == RT_ALBEDO_COLORS ? FrameGen::VCOL : albedo == RT_ALBEDO_TEXTURES ? FrameGen::TEX : FrameGen::NONE;
+}
+// G for surface `kind`, or RT_ERR_STATE where the context lacks what it reads: the colours; the textures, then the maps,
+// then maps that were set for these textures
+int resident_surface(const rt_ctx* c, FrameGen::Surface kind, SurfaceGen* G) {
+  if (kind == FrameGen::VCOL && !c->vcol) return fail(RT_ERR_STATE, "the context has no resident vertex colours (rt_set_vertex_colors)");
+  if ((kind == FrameGen::TEX || kind == FrameGen::MAT) && !c->tex) return fail(RT_ERR_STATE, "the context has no resident textures (rt_set_textures)");
+  if (kind == FrameGen::MAT && !c->matMaps) return fail(RT_ERR_STATE, "the context has no resident material maps (rt_set_material_maps)");
+  if (kind == FrameGen::MAT && c->matMaps.texGeneration != c->tex.generation)
+    return fail(RT_ERR_STATE, "the material maps were set for another texture set (rt_set_material_maps after rt_set_textures)");
+  const rtk::TexRec T = c->tex.rec();
+  switch (kind) {
+    case FrameGen::NONE: G->gen = FrameGen(); break;
+    case FrameGen::VCOL: G->vcol = rtk::VColRec{c->vcol.get()}, G->gen = FrameGen(G->vcol); break;
+    case FrameGen::TEX: G->tex = T, G->gen = FrameGen(G->tex); break;
+    case FrameGen::MAT:
+      G->mat = rtk::MatRec{T.uv, T.meshTex, T.desc, T.texels, c->matMaps.f0.get(), c->matMaps.kdAlpha.get()}, G->gen = FrameGen(G->mat);
+      break;
+  }
   return RT_OK;
 }
 
 // rt_render_aov_device, rt_render_aov_colors_device or rt_render_aov_textured_device
-int aov_device(rt_ctx* c, const rt_params* p, const rt_aov* out, void* stream, AovAlbedo alb) {
+int aov_device(rt_ctx* c, const rt_params* p, const rt_aov* out, void* stream, FrameGen::Surface alb) {
   rt_params q;
   int rc = aov_checks(c, p, &q);
   if (rc != RT_OK) return rc;
   if (!out) return fail(RT_ERR_INVALID, "aov is null");
-  if ((rc = aov_albedo_resident(c, alb)) != RT_OK) return rc;
+  SurfaceGen G;
+  if ((rc = resident_surface(c, alb, &G)) != RT_OK) return rc;
   HIP_TRY(hipSetDevice(c->device));
   const rtk::AovArgs A = aov_args(q, *out);
   const bool brute = q.accel == RT_ACCEL_BRUTE;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const hipError_t he = alb == ALBEDO_COLORS     ? rtk::launch_aov_colors(brute, c->S, A, c->vcol.get(), s)
-                        : alb == ALBEDO_TEXTURES ? rtk::launch_aov_textured(brute, c->S, A, c->tex.rec(), s)
-                                                 : rtk::launch_aov(brute, c->S, A, s);
+  const hipError_t he = rtk::launch_aov(brute, c->S, A, nullptr, 0, G.gen, s);
   if (he != hipSuccess) return fail(RT_ERR_HIP, "AOV launch failed: %s", hipGetErrorString(he));
   return RT_OK;
 }
 
 // the host form of each
-int aov_host(rt_ctx* c, const rt_params* p, const rt_aov* out, AovAlbedo alb) {
+int aov_host(rt_ctx* c, const rt_params* p, const rt_aov* out, FrameGen::Surface alb) {
   rt_params q;
   int rc = aov_checks(c, p, &q);
   if (rc != RT_OK) return rc;
   if (!out) return fail(RT_ERR_INVALID, "aov is null");
-  if ((rc = aov_albedo_resident(c, alb)) != RT_OK) return rc;
+  SurfaceGen G;
+  if ((rc = resident_surface(c, alb, &G)) != RT_OK) return rc;
   HIP_TRY(hipSetDevice(c->device));
   const size_t npx = (size_t)q.width * q.height;
   Staging st;
@@ -2740,12 +2771,12 @@ int aov_host(rt_ctx* c, const rt_params* p, const rt_aov* out, AovAlbedo alb) {
 
 extern "C" {
 
-int rt_render_aov_device(rt_ctx* c, const rt_params* p, const rt_aov* out, void* stream) { return aov_device(c, p, out, stream, ALBEDO_MESH); }
-int rt_render_aov(rt_ctx* c, const rt_params* p, const rt_aov* out) { return aov_host(c, p, out, ALBEDO_MESH); }
-int rt_render_aov_colors_device(rt_ctx* c, const rt_params* p, const rt_aov* out, void* stream) { return aov_device(c, p, out, stream, ALBEDO_COLORS); }
-int rt_render_aov_colors(rt_ctx* c, const rt_params* p, const rt_aov* out) { return aov_host(c, p, out, ALBEDO_COLORS); }
-int rt_render_aov_textured_device(rt_ctx* c, const rt_params* p, const rt_aov* out, void* stream) { return aov_device(c, p, out, stream, ALBEDO_TEXTURES); }
-int rt_render_aov_textured(rt_ctx* c, const rt_params* p, const rt_aov* out) { return aov_host(c, p, out, ALBEDO_TEXTURES); }
+int rt_render_aov_device(rt_ctx* c, const rt_params* p, const rt_aov* out, void* stream) { return aov_device(c, p, out, stream, FrameGen::NONE); }
+int rt_render_aov(rt_ctx* c, const rt_params* p, const rt_aov* out) { return aov_host(c, p, out, FrameGen::NONE); }
+int rt_render_aov_colors_device(rt_ctx* c, const rt_params* p, const rt_aov* out, void* stream) { return aov_device(c, p, out, stream, FrameGen::VCOL); }
+int rt_render_aov_colors(rt_ctx* c, const rt_params* p, const rt_aov* out) { return aov_host(c, p, out, FrameGen::VCOL); }
+int rt_render_aov_textured_device(rt_ctx* c, const rt_params* p, const rt_aov* out, void* stream) { return aov_device(c, p, out, stream, FrameGen::TEX); }
+int rt_render_aov_textured(rt_ctx* c, const rt_params* p, const rt_aov* out) { return aov_host(c, p, out, FrameGen::TEX); }
 
 int rt_denoise_device(rt_ctx* c, const rt_denoise_params* d, const void* d_rgb, const rt_aov* aov, void* d_out, void* stream) {
   int rc = denoise_checks(c, d, d_rgb, aov, d_out);
@@ -3646,9 +3677,7 @@ int lens_checks(const rt_ctx* c, const rt_params* p, const rt_lens* l, const cha
     return fail(RT_ERR_INVALID, "focus_distance must be finite and > 0");
   int rc = check_params_shape(p);
   if (rc != RT_OK) return rc;
-  if (p->world > 1) return fail(RT_ERR_UNSUPPORTED, "tile-sharded lens frames (world %u) are not supported", p->world);
-  if (p->use_photons) return fail(RT_ERR_UNSUPPORTED, "lens frames do not shade from the photon map");
-  if (p->reserved[2] & 1u) return fail(RT_ERR_UNSUPPORTED, "lens frames do not run the wavefront integrator");
+  if ((rc = frame_params_checks(p, "lens")) != RT_OK) return rc;
   if ((rc = check_device_present()) != RT_OK) return rc;
   if ((rc = check_not_broken(c)) != RT_OK) return rc;
   const rt_camera& cam = c->S.cam;
@@ -3686,11 +3715,7 @@ int shutter_record_checks(const rt_shutter* s, const char* who) {
 // ... then what p alone decides ...
 int shutter_params_checks(const rt_params* p) {
   const int rc = check_params_shape(p);
-  if (rc != RT_OK) return rc;
-  if (p->world > 1) return fail(RT_ERR_UNSUPPORTED, "tile-sharded shutter frames (world %u) are not supported", p->world);
-  if (p->use_photons) return fail(RT_ERR_UNSUPPORTED, "shutter frames do not shade from the photon map");
-  if (p->reserved[2] & 1u) return fail(RT_ERR_UNSUPPORTED, "shutter frames do not run the wavefront integrator");
-  return RT_OK;
+  return rc != RT_OK ? rc : frame_params_checks(p, "shutter");
 }
 // ... and last what reads the camera A the shutter opens on (the context's, or a view's) and the origin bound the frame
 // runs under, and the record the kernels take.
@@ -3782,9 +3807,7 @@ int lights_checks(const rt_ctx* c, const rt_params* p, const rt_light_groups* g,
   if (outputs) return fail(RT_ERR_INVALID, "%s", outputs);
   int rc = check_params_shape(p);
   if (rc != RT_OK) return rc;
-  if (p->world > 1) return fail(RT_ERR_UNSUPPORTED, "tile-sharded light-group frames (world %u) are not supported", p->world);
-  if (p->use_photons) return fail(RT_ERR_UNSUPPORTED, "light-group frames do not shade from the photon map");
-  if (p->reserved[2] & 1u) return fail(RT_ERR_UNSUPPORTED, "light-group frames do not run the wavefront integrator");
+  if ((rc = frame_params_checks(p, "light-group")) != RT_OK) return rc;
   if ((rc = check_device_present()) != RT_OK) return rc;
   if ((rc = check_not_broken(c)) != RT_OK) return rc;
   const uint32_t nl = c->S.n_lights;
@@ -3847,9 +3870,7 @@ int pick_checks(const rt_ctx* c, const rt_params* p, const rt_light_pick* k, con
   if (outputs) return fail(RT_ERR_INVALID, "%s", outputs);
   int rc = check_params_shape(p);
   if (rc != RT_OK) return rc;
-  if (p->world > 1) return fail(RT_ERR_UNSUPPORTED, "tile-sharded light-pick frames (world %u) are not supported", p->world);
-  if (p->use_photons) return fail(RT_ERR_UNSUPPORTED, "light-pick frames do not shade from the photon map");
-  if (p->reserved[2] & 1u) return fail(RT_ERR_UNSUPPORTED, "light-pick frames do not run the wavefront integrator");
+  if ((rc = frame_params_checks(p, "light-pick")) != RT_OK) return rc;
   if ((rc = check_device_present()) != RT_OK) return rc;
   if ((rc = check_not_broken(c)) != RT_OK) return rc;
   const uint32_t n = (uint32_t)c->hostLights.size(), m = k->slots;
@@ -3946,21 +3967,32 @@ int rt_render_pick(rt_ctx* c, const rt_params* p, const rt_light_pick* k, const 
 // ---- per-vertex albedo ---------------------------------------------------------------------------------
 namespace {
 
-// Everything both forms of rt_render_colors check, in the header's order (lens_checks' shape: the arguments alone first,
-// then the device, the context last), and the record the kernels take.
-int colors_checks(const rt_ctx* c, const rt_params* p, const char* outputs, rtk::VColRec* R) {
+// Everything both forms of rt_render_colors, rt_render_textured and rt_render_material check, in the header's order
+// (lens_checks' shape: the arguments alone first, then the device, the context last), and the surface the kernels take.
+int surface_checks(const rt_ctx* c, const rt_params* p, const char* outputs, FrameGen::Surface kind, SurfaceGen* G) {
+  static const char* const nouns[] = {"", "coloured", "textured", "material-map"};
   if (!c || !p) return fail(RT_ERR_INVALID, "ctx/params is null");
   if (outputs) return fail(RT_ERR_INVALID, "%s", outputs);
   int rc = check_params_shape(p);
   if (rc != RT_OK) return rc;
-  if (p->world > 1) return fail(RT_ERR_UNSUPPORTED, "tile-sharded coloured frames (world %u) are not supported", p->world);
-  if (p->use_photons) return fail(RT_ERR_UNSUPPORTED, "coloured frames do not shade from the photon map");
-  if (p->reserved[2] & 1u) return fail(RT_ERR_UNSUPPORTED, "coloured frames do not run the wavefront integrator");
+  if ((rc = frame_params_checks(p, nouns[kind])) != RT_OK) return rc;
   if ((rc = check_device_present()) != RT_OK) return rc;
   if ((rc = check_not_broken(c)) != RT_OK) return rc;
-  if (!c->vcol) return fail(RT_ERR_STATE, "the context has no resident vertex colours (rt_set_vertex_colors)");
-  R->vcol = c->vcol.get();
-  return RT_OK;
+  return resident_surface(c, kind, G);
+}
+
+// the device and the host form of each
+int surface_frame_device(rt_ctx* c, const rt_params* p, FrameGen::Surface kind, void* d_accum, void* stream, rt_stats* stats) {
+  SurfaceGen G;
+  const int rc = surface_checks(c, p, d_accum ? nullptr : "d_accum is null", kind, &G);
+  if (rc != RT_OK) return rc;
+  return frame_device(c, p, G.gen, d_accum, stream, stats);
+}
+int surface_frame_host(rt_ctx* c, const rt_params* p, FrameGen::Surface kind, const float* bg, float* out_rgb, float* accum_out, rt_stats* stats) {
+  SurfaceGen G;
+  const int rc = surface_checks(c, p, outputs_refused(bg, out_rgb, accum_out), kind, &G);
+  if (rc != RT_OK) return rc;
+  return frame_host(c, p, G.gen, 1, bg, out_rgb, accum_out, stats);
 }
 
 }  // namespace
@@ -3992,39 +4024,16 @@ int rt_set_vertex_colors(rt_ctx* c, const float* rgb, uint32_t n_vertices) {
 }
 
 int rt_render_colors_device(rt_ctx* c, const rt_params* p, void* d_accum, void* stream, rt_stats* stats) {
-  rtk::VColRec R;
-  const int rc = colors_checks(c, p, d_accum ? nullptr : "d_accum is null", &R);
-  if (rc != RT_OK) return rc;
-  return frame_device(c, p, R, d_accum, stream, stats);
+  return surface_frame_device(c, p, FrameGen::VCOL, d_accum, stream, stats);
 }
-
 int rt_render_colors(rt_ctx* c, const rt_params* p, const float* bg, float* out_rgb, float* accum_out, rt_stats* stats) {
-  rtk::VColRec R;
-  const int rc = colors_checks(c, p, outputs_refused(bg, out_rgb, accum_out), &R);
-  if (rc != RT_OK) return rc;
-  return frame_host(c, p, R, 1, bg, out_rgb, accum_out, stats);
+  return surface_frame_host(c, p, FrameGen::VCOL, bg, out_rgb, accum_out, stats);
 }
 
 }  // extern "C"
 
 // ---- image-textured albedo ------------------------------------------------------------------------------
 namespace {
-
-// Everything both forms of rt_render_textured check, in colors_checks' order, and the record the kernels take.
-int textured_checks(const rt_ctx* c, const rt_params* p, const char* outputs, rtk::TexRec* R) {
-  if (!c || !p) return fail(RT_ERR_INVALID, "ctx/params is null");
-  if (outputs) return fail(RT_ERR_INVALID, "%s", outputs);
-  int rc = check_params_shape(p);
-  if (rc != RT_OK) return rc;
-  if (p->world > 1) return fail(RT_ERR_UNSUPPORTED, "tile-sharded textured frames (world %u) are not supported", p->world);
-  if (p->use_photons) return fail(RT_ERR_UNSUPPORTED, "textured frames do not shade from the photon map");
-  if (p->reserved[2] & 1u) return fail(RT_ERR_UNSUPPORTED, "textured frames do not run the wavefront integrator");
-  if ((rc = check_device_present()) != RT_OK) return rc;
-  if ((rc = check_not_broken(c)) != RT_OK) return rc;
-  if (!c->tex) return fail(RT_ERR_STATE, "the context has no resident textures (rt_set_textures)");
-  *R = c->tex.rec();
-  return RT_OK;
-}
 
 constexpr uint32_t kTexMaxSide = 16384u;       // with |uv| <= kTexMaxUv: int(floorf(s * W)) stays far inside int32 (rt_kernels.hip tex_sample)
 constexpr float kTexMaxUv = 1024.f;
@@ -4115,47 +4124,15 @@ int rt_set_textures(rt_ctx* c, const rt_texture_set* t) {
 }
 
 int rt_render_textured_device(rt_ctx* c, const rt_params* p, void* d_accum, void* stream, rt_stats* stats) {
-  rtk::TexRec R;
-  const int rc = textured_checks(c, p, d_accum ? nullptr : "d_accum is null", &R);
-  if (rc != RT_OK) return rc;
-  return frame_device(c, p, R, d_accum, stream, stats);
+  return surface_frame_device(c, p, FrameGen::TEX, d_accum, stream, stats);
 }
-
 int rt_render_textured(rt_ctx* c, const rt_params* p, const float* bg, float* out_rgb, float* accum_out, rt_stats* stats) {
-  rtk::TexRec R;
-  const int rc = textured_checks(c, p, outputs_refused(bg, out_rgb, accum_out), &R);
-  if (rc != RT_OK) return rc;
-  return frame_host(c, p, R, 1, bg, out_rgb, accum_out, stats);
+  return surface_frame_host(c, p, FrameGen::TEX, bg, out_rgb, accum_out, stats);
 }
 
 }  // extern "C"
 
 // ---- textured material maps -----------------------------------------------------------------------------
-namespace {
-
-// Everything both forms of rt_render_material check: textured_checks' in its order, then what this frame needs resident,
-// and the record the kernels take.
-int material_checks(const rt_ctx* c, const rt_params* p, const char* outputs, rtk::MatRec* R) {
-  if (!c || !p) return fail(RT_ERR_INVALID, "ctx/params is null");
-  if (outputs) return fail(RT_ERR_INVALID, "%s", outputs);
-  int rc = check_params_shape(p);
-  if (rc != RT_OK) return rc;
-  if (p->world > 1) return fail(RT_ERR_UNSUPPORTED, "tile-sharded material-map frames (world %u) are not supported", p->world);
-  if (p->use_photons) return fail(RT_ERR_UNSUPPORTED, "material-map frames do not shade from the photon map");
-  if (p->reserved[2] & 1u) return fail(RT_ERR_UNSUPPORTED, "material-map frames do not run the wavefront integrator");
-  if ((rc = check_device_present()) != RT_OK) return rc;
-  if ((rc = check_not_broken(c)) != RT_OK) return rc;
-  if (!c->tex) return fail(RT_ERR_STATE, "the context has no resident textures (rt_set_textures)");
-  if (!c->matMaps) return fail(RT_ERR_STATE, "the context has no resident material maps (rt_set_material_maps)");
-  if (c->matMaps.texGeneration != c->tex.generation)
-    return fail(RT_ERR_STATE, "the material maps were set for another texture set (rt_set_material_maps after rt_set_textures)");
-  const rtk::TexRec T = c->tex.rec();
-  *R = rtk::MatRec{T.uv, T.meshTex, T.desc, T.texels, c->matMaps.f0.get(), c->matMaps.kdAlpha.get()};
-  return RT_OK;
-}
-
-}  // namespace
-
 extern "C" {
 
 int rt_set_material_maps(rt_ctx* c, const rt_material_maps* m) {
@@ -4188,17 +4165,10 @@ int rt_set_material_maps(rt_ctx* c, const rt_material_maps* m) {
 }
 
 int rt_render_material_device(rt_ctx* c, const rt_params* p, void* d_accum, void* stream, rt_stats* stats) {
-  rtk::MatRec R;
-  const int rc = material_checks(c, p, d_accum ? nullptr : "d_accum is null", &R);
-  if (rc != RT_OK) return rc;
-  return frame_device(c, p, R, d_accum, stream, stats);
+  return surface_frame_device(c, p, FrameGen::MAT, d_accum, stream, stats);
 }
-
 int rt_render_material(rt_ctx* c, const rt_params* p, const float* bg, float* out_rgb, float* accum_out, rt_stats* stats) {
-  rtk::MatRec R;
-  const int rc = material_checks(c, p, outputs_refused(bg, out_rgb, accum_out), &R);
-  if (rc != RT_OK) return rc;
-  return frame_host(c, p, R, 1, bg, out_rgb, accum_out, stats);
+  return surface_frame_host(c, p, FrameGen::MAT, bg, out_rgb, accum_out, stats);
 }
 
 }  // extern "C"
@@ -4211,10 +4181,11 @@ namespace {
 // record; then the device; then the context: rt_render_views' camera rule with every camera_close counted in the padding,
 // and rt_render_shutter's camera checks per view with cameras[j] in the place of the context's camera, under the origin
 // bound the frame runs with (*pad's).  recs: the records the kernels take.
-// albedo (rt_render_views_shutter_albedo; RT_ALBEDO_MATERIAL for the plain form): a value that is none of the three is
-// refused among the arguments, and data the context does not hold last of all.
+// albedo (rt_render_views_shutter_albedo; RT_ALBEDO_MATERIAL is the plain form): a value that is none of the three is
+// refused among the arguments, and data the context does not hold last of all.  G: the surface the frame shades with.
 int views_shutter_checks(rt_ctx* c, const rt_params* p, const rt_views* v, const rt_shutter* sh, const char* outputs,
-                         rtbvh::Padding* pad, bool* refit, std::vector<rtk::ViewShutterRec>* recs, uint32_t albedo = RT_ALBEDO_MATERIAL) {
+                         rtbvh::Padding* pad, bool* refit, std::vector<rtk::ViewShutterRec>* recs, uint32_t albedo,
+                         SurfaceGen* G) {
   if (!c || !p || !v || !v->cameras) return fail(RT_ERR_INVALID, "ctx/params/views/cameras is null");
   if (!sh) return fail(RT_ERR_INVALID, "shutters is null");
   if (outputs) return fail(RT_ERR_INVALID, "%s", outputs);
@@ -4248,22 +4219,8 @@ int views_shutter_checks(rt_ctx* c, const rt_params* p, const rt_views* v, const
     memcpy(Q.d, R.d, sizeof Q.d);
     Q.open = R.open, Q.close = R.close, Q.aperture = R.aperture, Q.fs0 = R.fs0, Q.dfs = R.dfs;
   }
-  return aov_albedo_resident(c, albedo_kind(albedo));
+  return resident_surface(c, albedo_surface(albedo), G);
 }
-
-// The surface record of a coloured or textured multi-view shutter frame, as rt_render_colors / rt_render_textured build
-// it from the resident data (which views_shutter_checks found present); the holder keeps it alive over the launch call.
-struct AlbedoGen {
-  rtk::VColRec vcol;
-  rtk::TexRec tex;
-  FrameGen gen;
-  AlbedoGen(const rt_ctx* c, uint32_t albedo) : vcol{c->vcol.get()}, tex(c->tex.rec()) {
-    if (albedo == RT_ALBEDO_COLORS) gen = FrameGen(vcol);
-    else if (albedo == RT_ALBEDO_TEXTURES) gen = FrameGen(tex);
-  }
-  AlbedoGen(const AlbedoGen&) = delete;
-  AlbedoGen& operator=(const AlbedoGen&) = delete;
-};
 
 }  // namespace
 
@@ -4271,22 +4228,11 @@ extern "C" {
 
 int rt_render_views_shutter_device(rt_ctx* c, const rt_params* p, const rt_views* v, const rt_shutter* shutters, void* d_accum,
                                    void* stream, rt_stats* stats) {
-  rtbvh::Padding pad;
-  bool refit = false;
-  std::vector<rtk::ViewShutterRec> recs;
-  const int rc = views_shutter_checks(c, p, v, shutters, d_accum ? nullptr : "d_accum is null", &pad, &refit, &recs);
-  if (rc != RT_OK) return rc;
-  return views_frame_device(c, p, v, recs.data(), pad, refit, d_accum, stream, stats);
+  return rt_render_views_shutter_albedo_device(c, p, v, shutters, RT_ALBEDO_MATERIAL, d_accum, stream, stats);
 }
-
 int rt_render_views_shutter(rt_ctx* c, const rt_params* p, const rt_views* v, const rt_shutter* shutters, const float* bg,
                             float* out_rgb, float* accum_out, rt_stats* stats) {
-  rtbvh::Padding pad;
-  bool refit = false;
-  std::vector<rtk::ViewShutterRec> recs;
-  const int rc = views_shutter_checks(c, p, v, shutters, outputs_refused(bg, out_rgb, accum_out), &pad, &refit, &recs);
-  if (rc != RT_OK) return rc;
-  return views_frame_host(c, p, v, recs.data(), pad, refit, bg, out_rgb, accum_out, stats);
+  return rt_render_views_shutter_albedo(c, p, v, shutters, RT_ALBEDO_MATERIAL, bg, out_rgb, accum_out, stats);
 }
 
 int rt_render_views_shutter_albedo_device(rt_ctx* c, const rt_params* p, const rt_views* v, const rt_shutter* shutters, uint32_t albedo,
@@ -4294,9 +4240,9 @@ int rt_render_views_shutter_albedo_device(rt_ctx* c, const rt_params* p, const r
   rtbvh::Padding pad;
   bool refit = false;
   std::vector<rtk::ViewShutterRec> recs;
-  const int rc = views_shutter_checks(c, p, v, shutters, d_accum ? nullptr : "d_accum is null", &pad, &refit, &recs, albedo);
+  SurfaceGen G;
+  const int rc = views_shutter_checks(c, p, v, shutters, d_accum ? nullptr : "d_accum is null", &pad, &refit, &recs, albedo, &G);
   if (rc != RT_OK) return rc;
-  const AlbedoGen G(c, albedo);
   return views_frame_device(c, p, v, recs.data(), pad, refit, d_accum, stream, stats, G.gen);
 }
 
@@ -4305,9 +4251,9 @@ int rt_render_views_shutter_albedo(rt_ctx* c, const rt_params* p, const rt_views
   rtbvh::Padding pad;
   bool refit = false;
   std::vector<rtk::ViewShutterRec> recs;
-  const int rc = views_shutter_checks(c, p, v, shutters, outputs_refused(bg, out_rgb, accum_out), &pad, &refit, &recs, albedo);
+  SurfaceGen G;
+  const int rc = views_shutter_checks(c, p, v, shutters, outputs_refused(bg, out_rgb, accum_out), &pad, &refit, &recs, albedo, &G);
   if (rc != RT_OK) return rc;
-  const AlbedoGen G(c, albedo);
   return views_frame_host(c, p, v, recs.data(), pad, refit, bg, out_rgb, accum_out, stats, G.gen);
 }
 
@@ -4337,15 +4283,15 @@ int views_pass_checks(rt_ctx* c, const rt_params* p, const rt_views* v, const rt
   return views_checks(c, q, v, pad, refit);
 }
 
-// alb: what the albedo channel sums (rt_render_aov_views_albedo; ALBEDO_MESH for rt_render_aov_views) — an unknown value
-// is refused among the arguments, data the context does not hold last of all
+// alb: what the albedo channel sums (rt_render_aov_views_albedo; RT_ALBEDO_MATERIAL for rt_render_aov_views) — an unknown
+// value is refused among the arguments, data the context does not hold last of all.  G: the surface the channel reads.
 int aov_views_checks(rt_ctx* c, const rt_params* p, const rt_views* v, const rt_aov* out, rt_params* q, rtbvh::Padding* pad, bool* refit,
-                     uint32_t alb = RT_ALBEDO_MATERIAL) {
+                     uint32_t alb, SurfaceGen* G) {
   if (!c || !p || !v || !v->cameras || !out) return fail(RT_ERR_INVALID, "ctx/params/views/cameras/aov is null");
   if (any_set(out->reserved, 4)) return fail(RT_ERR_INVALID, "reserved words must be zero");
   if (alb > RT_ALBEDO_TEXTURES) return fail(RT_ERR_INVALID, "albedo %u is none of RT_ALBEDO_MATERIAL, RT_ALBEDO_COLORS, RT_ALBEDO_TEXTURES", alb);
   const int rc = views_pass_checks(c, p, v, nullptr, q, pad, refit);
-  return rc != RT_OK ? rc : aov_albedo_resident(c, albedo_kind(alb));
+  return rc != RT_OK ? rc : resident_surface(c, albedo_surface(alb), G);
 }
 
 int motion_views_checks(rt_ctx* c, const rt_params* p, const rt_views* v, const rt_motion_prev_views* prev, const rt_motion* out,
@@ -4371,18 +4317,15 @@ int aov_views_device(rt_ctx* c, const rt_params* p, const rt_views* v, const rt_
   rt_params q;
   rtbvh::Padding pad;
   bool refit = false;
-  int rc = aov_views_checks(c, p, v, out, &q, &pad, &refit, alb);
+  SurfaceGen G;
+  int rc = aov_views_checks(c, p, v, out, &q, &pad, &refit, alb, &G);
   if (rc != RT_OK) return rc;
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   if ((rc = stage_views(c, &q, v, nullptr, pad, refit, s)) != RT_OK) return rc;
   const bool brute = q.accel == RT_ACCEL_BRUTE;
   const rtk::AovArgs A = aov_args(q, *out);
-  const rtk::TexRec T = c->tex.rec();
-  const hipError_t he = alb == RT_ALBEDO_MATERIAL ? rtk::launch_aov_views(brute, c->S, A, c->vwRecs.get(), v->n_views, s)
-                                                  : rtk::launch_aov_views_albedo(brute, c->S, A, c->vwRecs.get(), v->n_views,
-                                                                                 alb == RT_ALBEDO_COLORS ? c->vcol.get() : nullptr,
-                                                                                 alb == RT_ALBEDO_TEXTURES ? &T : nullptr, s);
+  const hipError_t he = rtk::launch_aov(brute, c->S, A, c->vwRecs.get(), v->n_views, G.gen, s);
   if (he != hipSuccess) return fail(RT_ERR_HIP, "AOV launch failed: %s", hipGetErrorString(he));
   return RT_OK;
 }
@@ -4392,7 +4335,8 @@ int aov_views_host(rt_ctx* c, const rt_params* p, const rt_views* v, const rt_ao
   rt_params q;
   rtbvh::Padding pad;
   bool refit = false;
-  int rc = aov_views_checks(c, p, v, out, &q, &pad, &refit, alb);
+  SurfaceGen G;
+  int rc = aov_views_checks(c, p, v, out, &q, &pad, &refit, alb, &G);
   if (rc != RT_OK) return rc;
   HIP_TRY(hipSetDevice(c->device));
   const size_t all = rtk::view_slice(v->n_views, q.width, q.height, 1);

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <string>
+
 #include "bvh_build.h"
 #include "rt_amd.h"
 #include "rt_device.h"
@@ -139,33 +141,22 @@ hipError_t launch_wavefront(const DevScene& S, const WfArgs& W, uint32_t mode, u
 // first-hit AOVs of a frame's primary rays (aov_kernels.h, rt_render_aov): sums over the samples [s0, s1) of every pixel;
 // null channels are not written
 struct TexDesc;  // (with TexRec, among the frame's variants below)
-struct TexRec;
 struct AovArgs {
   float *albedo, *normal, *position, *depth;  // [h][w][3], [h][w][3], [h][w][3], [h][w]
   uint32_t *hits, *mesh, *tri;                // [h][w] each
   uint32_t width, height, spp, seed, s0, s1;
-  // multi-view launches only (launch_aov_views sets them; the single-view instances do not read them)
+  // multi-view launches only (launch_aov sets them; the single-view instances do not read them)
   const ViewRec* views = nullptr;
   uint32_t tilesPerView = 0;
-  // coloured launches only (launch_aov_colors sets it; the other instances do not read it)
+  // coloured launches only (launch_aov sets it; the other instances do not read it)
   const float* vcol = nullptr;
-  // textured launches only (launch_aov_textured sets them; the other instances do not read them): TexRec's four tables
+  // textured launches only (launch_aov sets them; the other instances do not read them): TexRec's four tables
   const float* texUv = nullptr;
   const uint32_t* texMesh = nullptr;
   const TexDesc* texDesc = nullptr;
   const float* texels = nullptr;
 };
-hipError_t launch_aov(bool brute_force, const DevScene& S, const AovArgs& A, hipStream_t stream);
-// the same with the albedo channel summing the colour interpolated from vcol [n_vertices][3] at the first hit
-// (rt_render_aov_colors) instead of the mesh's albedo; instances of their own
-hipError_t launch_aov_colors(bool brute_force, const DevScene& S, const AovArgs& A, const float* vcol, hipStream_t stream);
-// the same with the albedo channel summing the texture sample at the first hit (rt_render_aov_textured; the mesh's albedo
-// on a mesh without a texture); instances of their own
-hipError_t launch_aov_textured(bool brute_force, const DevScene& S, const AovArgs& A, const TexRec& T, hipStream_t stream);
-// launch_aov_views (below) with the albedo channel of launch_aov_colors (vcol, T null) or launch_aov_textured (T, vcol
-// null): rt_render_aov_views_albedo; instances of their own
-hipError_t launch_aov_views_albedo(bool brute_force, const DevScene& S, const AovArgs& A, const ViewRec* views, uint32_t nViews,
-                                   const float* vcol, const TexRec* T, hipStream_t stream);
+// (launch_aov: below FrameVariant, whose surface part says what the albedo channel sums)
 // ambient occlusion and bent normals at the first hit (ao_kernels.h, rt_render_ao): per pixel, over the samples [s0, s1),
 // the occlusion rays that escaped, the hit samples, and the float32 sum of the escaped directions; null channels are not written
 struct AoArgs {
@@ -259,55 +250,64 @@ struct MatRec {
   const uint32_t* meshF0;       // [n_meshes]: f0's texture, or kTexNone
   const uint32_t* meshKdAlpha;  // [n_meshes]: (kd, alpha)'s texture, or kTexNone
 };
-// Which variant a frame is, with its record (which the caller keeps alive over the launch call).  VIEWS_SHUTTER, many
-// views each under its own open shutter (rt_render_views_shutter), has none: tile t renders with views[tileView[t]]'s
-// camera, seed and slice under viewShutters[tileView[t]], from RenderArgs' three tables.  VIEWS_SHUTTER_VCOL and
-// VIEWS_SHUTTER_TEX are that frame with the VColRec / TexRec of a coloured / textured one.
+// Which variant a frame is: a generator part (what forms its primary rays, splits its samples or lists its lights) and
+// a surface part (what its vertices shade with), with the one record of the pair (which the caller keeps alive over the
+// launch call): the generator's LensRec, ShutterRec, LightGroupsRec or PickRec, or the surface's VColRec, TexRec or
+// MatRec.  VIEWS_SHUTTER, many views each under its own open shutter (rt_render_views_shutter), has no record of its own
+// — tile t renders with views[tileView[t]]'s camera, seed and slice under viewShutters[tileView[t]], from RenderArgs'
+// three tables — so it carries a surface's.
 struct FrameVariant {
-  enum Kind { NONE, LENS, SHUTTER, LIGHTS, VIEWS_SHUTTER, PICK, VCOL, TEX, VIEWS_SHUTTER_VCOL, VIEWS_SHUTTER_TEX, MAT };
-  Kind kind = NONE;
-  const void* rec = nullptr;  // the LensRec, ShutterRec, LightGroupsRec, PickRec, VColRec, TexRec or MatRec of kind, else null
+  enum Gen { PLAIN, LENS, SHUTTER, LIGHTS, PICK, VIEWS_SHUTTER };
+  enum Surface { NONE, VCOL, TEX, MAT };
+  Gen gen = PLAIN;
+  Surface surface = NONE;
+  const void* rec = nullptr;
   FrameVariant() = default;
-  explicit FrameVariant(Kind k) : kind(k) {}
-  FrameVariant(const LensRec& r) : kind(LENS), rec(&r) {}
-  FrameVariant(const ShutterRec& r) : kind(SHUTTER), rec(&r) {}
-  FrameVariant(const LightGroupsRec& r) : kind(LIGHTS), rec(&r) {}
-  FrameVariant(const PickRec& r) : kind(PICK), rec(&r) {}
-  FrameVariant(const VColRec& r) : kind(VCOL), rec(&r) {}
-  FrameVariant(const TexRec& r) : kind(TEX), rec(&r) {}
-  FrameVariant(const MatRec& r) : kind(MAT), rec(&r) {}
-  // the coloured or textured frame F under the multi-view shutter's generator (rt_render_views_shutter_albedo): F's
-  // record with RenderArgs' three tables; any other F is the multi-view shutter frame itself
-  static FrameVariant under_views_shutter(const FrameVariant& F) {
-    FrameVariant V(F.kind == VCOL ? VIEWS_SHUTTER_VCOL : F.kind == TEX ? VIEWS_SHUTTER_TEX : VIEWS_SHUTTER);
-    if (V.kind != VIEWS_SHUTTER) V.rec = F.rec;
-    return V;
+  FrameVariant(const LensRec& r) : gen(LENS), rec(&r) {}
+  FrameVariant(const ShutterRec& r) : gen(SHUTTER), rec(&r) {}
+  FrameVariant(const LightGroupsRec& r) : gen(LIGHTS), rec(&r) {}
+  FrameVariant(const PickRec& r) : gen(PICK), rec(&r) {}
+  FrameVariant(const VColRec& r) : surface(VCOL), rec(&r) {}
+  FrameVariant(const TexRec& r) : surface(TEX), rec(&r) {}
+  FrameVariant(const MatRec& r) : surface(MAT), rec(&r) {}
+  // F's surface under the multi-view shutter's generator (rt_render_views_shutter_albedo; a plain F: the multi-view
+  // shutter frame itself), with RenderArgs' three tables
+  static FrameVariant under_views_shutter(FrameVariant F) {
+    F.gen = VIEWS_SHUTTER;
+    return F;
   }
-  explicit operator bool() const { return kind != NONE; }
+  explicit operator bool() const { return gen != PLAIN || surface != NONE; }
   // the variant in an error message: "<name> render launch failed"
-  const char* name() const {
-    static const char* const names[] = {"", "lens", "shutter", "light-group", "multi-view shutter", "light-pick", "vertex-colour", "textured",
-                                        "multi-view shutter vertex-colour", "multi-view shutter textured", "material-map"};
-    return names[kind];
+  std::string name() const {
+    static const char* const gens[] = {"", "lens", "shutter", "light-group", "light-pick", "multi-view shutter"};
+    static const char* const surfaces[] = {"", "vertex-colour", "textured", "material-map"};
+    return std::string(gens[gen]) + (gen != PLAIN && surface != NONE ? " " : "") + surfaces[surface];
   }
 };
-// launch_render's one-wave-per-workgroup family (brute, sequential, pooled; counted or timed) for a variant (F.kind not
-// NONE); A as launch_render takes it: tileView null, but for VIEWS_SHUTTER a multi-view frame's with the three tables
-// set, and so for VIEWS_SHUTTER_VCOL and VIEWS_SHUTTER_TEX.  LIGHTS: accum is [G.n][height][width], slice g at accum + g * width * height.  PICK: pooled whenever A.flags bit 0
-// is set, whatever the scene's light count (a vertex sends m <= POOL_L shadow rays).  VCOL: a launch allocates
-// VP_VCOL_WORDS more words of LDS per wave (the vertex's parked kdDiffuse), and so does TEX; MAT allocates VP_MAT_WORDS (the vertex's parked
-// material).  hipErrorInvalidValue where A, the
+// launch_render's one-wave-per-workgroup family (brute, sequential, pooled; counted or timed) for a variant F (not the
+// plain frame, which is launch_render's).  The pairs that exist: every generator without a surface, every surface under
+// the plain generator, and VCOL and TEX under VIEWS_SHUTTER; hipErrorInvalidValue for every other pair, and where A, the
 // record or the scene's light count do not fit the variant.
+// The generator decides what A is: launch_render's with tileView null, but for VIEWS_SHUTTER a multi-view frame's with
+// the three tables set.  LIGHTS: accum is [G.n][height][width], slice g at accum + g * width * height.  PICK: pooled
+// whenever A.flags bit 0 is set, whatever the scene's light count (a vertex sends m <= POOL_L shadow rays).
+// The surface decides the LDS a launch allocates per wave beyond the generator's: the rows its policy parks a vertex's
+// value in (VCOL and TEX three, the kdDiffuse; MAT eight, the material).
 hipError_t launch_render_variant(const FrameVariant& F, bool brute_force, bool stats, const DevScene& S, const RenderArgs& A,
                                  float4* accum, unsigned long long* counters, hipStream_t stream);
+// The AOV pass.  views null: the frame of S.cam and A.seed; else the same pass over nViews views in one launch
+// (rt_render_aov_views): view j renders with views[j]'s camera and seed (A.seed is not read) into slice j of every channel.
+// surface (its surface part alone is read): what the albedo channel sums at the first hit — NONE the mesh's albedo, VCOL
+// the colour interpolated from the VColRec's array (rt_render_aov_colors), TEX the TexRec's texture sample, or the mesh's
+// albedo on a mesh without a texture (rt_render_aov_textured); instances of their own each.  hipErrorInvalidValue for a
+// record with a null table, for MAT, and for views of 2^31 tiles or more together; an empty launch is a success.
+hipError_t launch_aov(bool brute_force, const DevScene& S, const AovArgs& A, const ViewRec* views, uint32_t nViews,
+                      const FrameVariant& surface, hipStream_t stream);
 // First element of view j's slice of a per-view output with c floats or words per pixel (rt_render_aov_views,
 // rt_render_motion_views, rt_denoise_batch): formed in 64 bits — n w h may reach 2^31 - 1 and 3 x that is not 32-bit.
 __host__ __device__ inline size_t view_slice(uint32_t j, uint32_t width, uint32_t height, uint32_t c) {
   return (size_t)j * width * height * c;
 }
-// the same pass over nViews views in one launch (rt_render_aov_views): view j renders with views[j]'s camera and seed (A.seed
-// is not read) into slice j of every channel
-hipError_t launch_aov_views(bool brute_force, const DevScene& S, const AovArgs& A, const ViewRec* views, uint32_t nViews, hipStream_t stream);
 // the motion pass (motion_kernels.h, rt_render_motion): per pixel, for the primary ray of sample s0, the hit point over the
 // context's positions and over prevVpos (never null: the context's own when the geometry did not move), and the screen
 // motion between prevCam and S.cam; null channels are not written

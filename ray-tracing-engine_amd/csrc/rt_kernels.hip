@@ -235,16 +235,17 @@ constexpr int LT_LIGHTS = 4096;
 constexpr int LT_PICK = 8192;
 // A frame with per-vertex albedo (rt_render_colors): render_tile takes a VColRec and forms every vertex's kdDiffuse from
 // the colours of the hit triangle's three vertices; the vertex pool and shade_direct_seq shade with it in place of the
-// mesh's (their VC switch).
+// mesh's (their VC switch: ParkKd, the value the surface policy SurfVCol parks).
 constexpr int LT_VCOL = 16384;
 // A frame with image-textured albedo (rt_render_textured): render_tile takes a TexRec and forms every vertex's kdDiffuse
 // from the texture sample at the hit's uv (tex_kd); it reaches the vertex pool and shade_direct_seq as the coloured
-// frame's does (their VC switch, a second producer of VColKd::kd).
+// frame's does (SurfTex: the same three parked rows).
 constexpr int LT_TEX = 32768;
 // A frame with textured material maps (rt_render_material): render_tile takes a MatRec and forms every vertex's whole
 // material from the samples at the hit's uv (tex_mat); it reaches the vertex pool and shade_direct_seq through their VC
-// switch as the payload VMat, which shades with bsdf_base(const rt_material&) in place of the mesh's DevMat.
+// switch as SurfMat's ParkMat, which shades with bsdf_base(const rt_material&) in place of the mesh's DevMat.
 constexpr int LT_MAT = 65536;
+constexpr int LT_SURFACES = LT_VCOL | LT_TEX | LT_MAT;  // (the bits surface_t reads)
 constexpr uint32_t kPrioMaxNodes = 65536;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(3))) u32x4* lds_u4_ptr;
@@ -871,21 +872,6 @@ RT_DEV f3 vertex_kd(const DevScene& S, const float* vcol, uint4 tv, float u, flo
   const f3 diffuse = vertex_color(vcol, tv, u, v) / 3.14159274f;  // c / float(M_PI)
   return S.mats[tv.w].kd * diffuse;
 }
-// What a vertex of a coloured frame shades with in place of its mesh's kdDiffuse, and the three rows of LDS (the wave's:
-// [3][64] floats behind its stack rows and pool, allocated for these instances alone) where it is parked while the wave
-// traverses: held in registers, it would cost the timed instances, which sit at their budget, three more of them.
-// NoVCol: every other frame — an empty argument, so that the instances without colours keep the signatures (and the
-// code) they had.
-struct NoVCol {};
-struct VColKd {
-  f3 kd;
-  float* park;
-};
-RT_DEV void park_kd(const VColKd& vc, uint32_t lane) { vc.park[lane] = vc.kd.x, vc.park[64 + lane] = vc.kd.y, vc.park[128 + lane] = vc.kd.z; }
-RT_DEV f3 parked_kd(const VColKd& vc, uint32_t lane) { return mk(vc.park[lane], vc.park[64 + lane], vc.park[128 + lane]); }
-template <class VC>
-constexpr bool is_vcol = std::is_same_v<VC, VColKd>;
-
 // Image-textured albedo (rt_render_textured, rt_amd.h's sampler).  gfx950 has no image instructions: a sample is plain
 // loads and float32 arithmetic, every operation rounded on its own.
 // tex_wrap: the texel index of the integer coordinate i on an axis of n texels — REPEAT: the non-negative remainder,
@@ -969,24 +955,76 @@ RT_DEV rt_material tex_mat(const DevScene& S, const MatRec& M, uint4 tv, float u
   }
   return m;
 }
-// The VC switch's second payload: the vertex's whole material, and the eight rows of LDS ([8][64] floats in VColKd's
-// place behind the wave's stack rows and pool) where it is parked while the wave traverses, in rt_material's field order.
-struct VMat {
-  rt_material m;
-  float* park;
+// What a vertex shades with in place of its mesh's DevMat, while the wave traverses: the value (v) and the rows of LDS
+// where it is parked over every walk (ROWS of [64] floats, the wave's, behind its stack rows and pool, allocated for these
+// instances alone: held in registers, it would cost the timed instances, which sit at their budget, as many more of
+// them).  WHOLE says how the read-back value enters the light-independent half of the BSDF: a kdDiffuse overwrites the
+// mesh's; a whole material forms the half anew by bsdf_base(const rt_material&) (the same operands every time, so the
+// same bits).  ParkNone: a frame without a surface — an empty argument, so that its instances keep the signatures (and
+// the code) they had.
+struct ParkNone {
+  static constexpr int ROWS = 0;
 };
-RT_DEV void park_mat(const VMat& vc, uint32_t lane) {
-  vc.park[lane] = vc.m.kd, vc.park[64 + lane] = vc.m.alpha;
-  for (int c = 0; c < 3; ++c) vc.park[(2 + c) * 64 + lane] = vc.m.albedo[c], vc.park[(5 + c) * 64 + lane] = vc.m.f0[c];
-}
-RT_DEV rt_material parked_mat(const VMat& vc, uint32_t lane) {
-  rt_material m;
-  m.kd = vc.park[lane], m.alpha = vc.park[64 + lane];
-  for (int c = 0; c < 3; ++c) m.albedo[c] = vc.park[(2 + c) * 64 + lane], m.f0[c] = vc.park[(5 + c) * 64 + lane];
-  return m;
-}
-template <class VC>
-constexpr bool is_vmat = std::is_same_v<VC, VMat>;
+struct ParkKd {  // a kdDiffuse, in three rows
+  static constexpr int ROWS = 3;
+  static constexpr bool WHOLE = false;
+  f3 v;
+  float* park;
+  RT_DEV void store(uint32_t lane) const { park[lane] = v.x, park[64 + lane] = v.y, park[128 + lane] = v.z; }
+  RT_DEV f3 load(uint32_t lane) const { return mk(park[lane], park[64 + lane], park[128 + lane]); }
+};
+struct ParkMat {  // a material, in eight rows in rt_material's field order
+  static constexpr int ROWS = 8;
+  static constexpr bool WHOLE = true;
+  rt_material v;
+  float* park;
+  RT_DEV void store(uint32_t lane) const {
+    park[lane] = v.kd, park[64 + lane] = v.alpha;
+    for (int c = 0; c < 3; ++c) park[(2 + c) * 64 + lane] = v.albedo[c], park[(5 + c) * 64 + lane] = v.f0[c];
+  }
+  RT_DEV rt_material load(uint32_t lane) const {
+    rt_material m;
+    m.kd = park[lane], m.alpha = park[64 + lane];
+    for (int c = 0; c < 3; ++c) m.albedo[c] = park[(2 + c) * 64 + lane], m.f0[c] = park[(5 + c) * 64 + lane];
+    return m;
+  }
+};
+// The surface policies, one per surface a frame can carry (surface_t picks it by the frame's LT_* bits): the record its
+// frames take (Rec), what a vertex parks (Parked), how that value is formed from the hit's (tv, u, v) (form), and the
+// records the launcher answers hipErrorInvalidValue to (refused).  A new surface is one more policy here, its bit in
+// surface_t and its row in frame_variants.h.
+struct NoRec {};
+struct SurfNone {
+  using Rec = NoRec;
+  using Parked = ParkNone;
+  static constexpr int LT = 0;
+  static bool refused(const Rec&) { return false; }
+};
+struct SurfVCol {  // rt_render_colors
+  using Rec = VColRec;
+  using Parked = ParkKd;
+  static constexpr int LT = LT_VCOL;
+  static RT_DEV f3 form(const DevScene& S, const Rec& R, uint4 tv, float u, float v) { return vertex_kd(S, R.vcol, tv, u, v); }
+  static bool refused(const Rec& R) { return !R.vcol; }
+};
+struct SurfTex {  // rt_render_textured
+  using Rec = TexRec;
+  using Parked = ParkKd;
+  static constexpr int LT = LT_TEX;
+  static RT_DEV f3 form(const DevScene& S, const Rec& R, uint4 tv, float u, float v) { return tex_kd(S, R, tv, u, v); }
+  static bool refused(const Rec& R) { return !R.uv || !R.meshTex || !R.desc || !R.texels; }
+};
+struct SurfMat {  // rt_render_material
+  using Rec = MatRec;
+  using Parked = ParkMat;
+  static constexpr int LT = LT_MAT;
+  static RT_DEV rt_material form(const DevScene& S, const Rec& R, uint4 tv, float u, float v) { return tex_mat(S, R, tv, u, v); }
+  static bool refused(const Rec& R) { return !R.uv || !R.meshTex || !R.desc || !R.texels || !R.meshF0 || !R.meshKdAlpha; }
+};
+template <int LTV>
+using surface_t = std::conditional_t<(LTV & LT_VCOL) != 0, SurfVCol,
+                  std::conditional_t<(LTV & LT_TEX) != 0, SurfTex,
+                  std::conditional_t<(LTV & LT_MAT) != 0, SurfMat, SurfNone>>>;
 
 // Renderer.cpp:63-104: photon-map radiance estimate at the vertex (HP: the heap's layout, WideHeap for k > 16)
 template <bool STATS, class HP = Heap>
@@ -1076,16 +1114,14 @@ RT_DEV uint32_t loop_lights(const DevScene&, const PickArgs& a) { return a.R->m;
 // with more than POOL_L lights).  Called by lanes that own a vertex only.
 // GROUPS (rt_render_lights): the terms go into *gc by group instead of into the returned colour, which stays 0.
 // PK = PickArgs (rt_render_pick): the light list is the sample's picked lights, in slot order, instead of the scene's.
-// VC = VColKd (rt_render_colors): the vertex's own kdDiffuse in place of the mesh's, parked in LDS over every walk.
-// VC = VMat (rt_render_material): the vertex's own material in place of the mesh's, parked in LDS likewise; the
-// light-independent half is formed from it behind every walk (the same operands every time, so the same bits).
-template <bool BRUTE, bool STATS, bool GROUPS = false, class PK = NoPick, class VC = NoVCol>
+// VC with rows (ParkKd, ParkMat: the coloured, textured and material-map frames): the vertex's own value in place of
+// the mesh's, parked in LDS over every walk and entered into the light-independent half behind each.
+template <bool BRUTE, bool STATS, bool GROUPS = false, class PK = NoPick, class VC = ParkNone>
 RT_DEV f3 shade_direct_seq(const DevScene& S, Rng& g, f3 rayDir, const HitRec& h, uint32_t* stack, f3 hitNormal,
                            f3 point, LaneStats& st, const LightGroupsRec* G = nullptr, GroupCols* gc = nullptr, PK pk = PK(),
                            VC vc = VC()) {
   BsdfBase base = bsdf_base(S.matsDev[h.mesh], hitNormal, -rayDir);  // the light-independent half, once
-  if constexpr (is_vcol<VC>) park_kd(vc, threadIdx.x & 63u);
-  if constexpr (is_vmat<VC>) park_mat(vc, threadIdx.x & 63u);  // (base is formed behind every walk: the mesh's is not used)
+  if constexpr (VC::ROWS != 0) vc.store(threadIdx.x & 63u);
   f3 color = mk(0.f, 0.f, 0.f);
   if constexpr (GROUPS) group_cols_zero(*gc);
   for (uint32_t li = 0; li < loop_lights(S, pk); li++) {
@@ -1094,13 +1130,10 @@ RT_DEV f3 shade_direct_seq(const DevScene& S, Rng& g, f3 rayDir, const HitRec& h
     HitRec tmp;
     st.shadow++;
     if (cast<BRUTE, true, STATS>(S, true, point, toLight, stack, tmp, st)) continue;
-    if constexpr (is_vcol<VC>) {
+    if constexpr (VC::ROWS != 0) {
       asm volatile("" ::: "memory");  // (read back behind the walk, not held over it)
-      base.kdDiffuse = parked_kd(vc, threadIdx.x & 63u);
-    }
-    if constexpr (is_vmat<VC>) {
-      asm volatile("" ::: "memory");  // (read back behind the walk, not held over it)
-      base = bsdf_base(parked_mat(vc, threadIdx.x & 63u), hitNormal, -rayDir);
+      if constexpr (VC::WHOLE) base = bsdf_base(vc.load(threadIdx.x & 63u), hitNormal, -rayDir);
+      else base.kdDiffuse = vc.load(threadIdx.x & 63u);
     }
     const f3 bsdf = bsdf_apply(base, toLight);
     f3 radiance;
@@ -1132,10 +1165,6 @@ constexpr int VP_PT = 0, VP_DIR = 192, VP_BDIR = VP_DIR + 192 * POOL_L, VP_KEY =
               VP_RES = VP_LIST + 32;
 constexpr int VP_WORDS = VP_RES + 2 * POOL_L + 2;
 constexpr int VP_COMPACT_SAVES = 64 * POOL_L;  // words a compact pool is shorter by
-// (rt_render_colors) three rows more per wave: the vertex's kdDiffuse while the wave traverses (VColKd::park)
-constexpr int VP_VCOL_WORDS = 192;
-// (rt_render_material) eight rows per wave in their place: the vertex's material (VMat::park)
-constexpr int VP_MAT_WORDS = 8 * 64;
 // offsets of everything behind the per-light block, by layout
 template <int CP> struct VpLayout {  // CP = 0: full, 1: light parameters, 2: ... and no bounce directions, 3: keys, list and result bits only
   static constexpr int PER_LIGHT = CP ? 128 : 192;
@@ -1160,12 +1189,10 @@ static_assert(VP_WORDS == (int)rtbvh::kWavePoolWords && BLOCK == (int)rtbvh::kSt
 // PK = PickArgs (rt_render_pick): the pool's lights are the lane's picked ones, in slot order: the fill loop samples
 // them and the colour loop evaluates them, each lane fetching its own from the record's table.  The workers read the full
 // layout's toLight directions only, so the rounds, the hand-out, the stealing and the result bits are the same code.
-// VC = VColKd (rt_render_colors): the vertex's own kdDiffuse in place of the mesh's.  It is parked in three rows of LDS
+// VC with rows (ParkKd, ParkMat): the vertex's own value in place of the mesh's.  It is parked in VC::ROWS rows of LDS
 // behind the pool's words (the launcher allocates them for these instances alone) as the point is in the pool, and read
 // back behind the rounds as the point is: nothing more of the vertex is live while the wave traverses.
-// VC = VMat (rt_render_material): the vertex's own material, parked in eight rows in the same place and read back
-// behind the rounds into bsdf_base(const rt_material&).
-template <bool STATS, int LT, bool BOUNCE, bool GROUPS = false, class PK = NoPick, class VC = NoVCol>
+template <bool STATS, int LT, bool BOUNCE, bool GROUPS = false, class PK = NoPick, class VC = ParkNone>
 RT_DEV f3 vertex_pool(const DevScene& S, bool alive, bool bounceRay, Rng& g, f3 rayDir, uint32_t mesh, f3 hitNormal,
                       f3& point, f3& bdir, uint32_t* stack, uint32_t* pool, HitRec& next, bool& nextFound, LaneStats& st,
                       const LightGroupsRec* G = nullptr, GroupCols* gc = nullptr, PK pk = PK(), VC vc = VC()) {
@@ -1175,8 +1202,7 @@ RT_DEV f3 vertex_pool(const DevScene& S, bool alive, bool bounceRay, Rng& g, f3 
   const uint32_t lane = threadIdx.x & 63u, nl = loop_lights(S, pk);
   constexpr bool CP3 = (LT & LT_COMPACT3) != 0, CP2 = CP3 || (LT & LT_COMPACT2) != 0, CP = CP2 || (LT & LT_COMPACT) != 0;
   static_assert(!is_pick<PK> || !CP, "the picked frames' instances use the full pool layout: workers read directions, never a light");
-  static_assert(!is_vcol<VC> || !CP, "the coloured frames' instances use the full pool layout, with the parked rows behind it");
-  static_assert(!is_vmat<VC> || !CP, "the material-map frames' instances use the full pool layout, with the parked rows behind it");
+  static_assert(VC::ROWS == 0 || !CP, "a surface that parks its value uses the full pool layout, with the parked rows behind it");
   using VP = VpLayout<CP3 ? 3 : CP2 ? 2 : CP ? 1 : 0>;
   float* fp = reinterpret_cast<float*>(pool);
   // 32 words: rank -> pixel lane (64 bytes) while rays are handed out; then rank -> victim
@@ -1195,8 +1221,7 @@ RT_DEV f3 vertex_pool(const DevScene& S, bool alive, bool bounceRay, Rng& g, f3 
   PHC(PH_N_POOLS);
   if (alive) {
     if (!CP3) fp[VP_PT + lane] = point.x, fp[VP_PT + 64 + lane] = point.y, fp[VP_PT + 128 + lane] = point.z;
-    if constexpr (is_vcol<VC>) park_kd(vc, lane);
-    if constexpr (is_vmat<VC>) park_mat(vc, lane);
+    if constexpr (VC::ROWS != 0) vc.store(lane);
     // draw order of the reference: the light samples in light order (Renderer.cpp:52),
     // then the hemisphere sample (Renderer.cpp:164)
     if (CP3) gsave = g.s;  // (the light samples are re-drawn from here wherever they are needed)
@@ -1396,8 +1421,10 @@ RT_DEV f3 vertex_pool(const DevScene& S, bool alive, bool bounceRay, Rng& g, f3 
   if (bounce && !CP2) bdir = mk(fp[VP::BDIR + lane], fp[VP::BDIR + 64 + lane], fp[VP::BDIR + 128 + lane]);
   if (alive) {
     BsdfBase base = bsdf_base<FR>(S.matsDev[mesh], hitNormal, -rayDir);  // the light-independent half, once
-    if constexpr (is_vcol<VC>) base.kdDiffuse = parked_kd(vc, lane);
-    if constexpr (is_vmat<VC>) base = bsdf_base<FR>(parked_mat(vc, lane), hitNormal, -rayDir);  // (in place of the mesh's)
+    if constexpr (VC::ROWS != 0) {  // (in place of the mesh's)
+      if constexpr (VC::WHOLE) base = bsdf_base<FR>(vc.load(lane), hitNormal, -rayDir);
+      else base.kdDiffuse = vc.load(lane);
+    }
     Rng relight{gsave};
     for (uint32_t l = 0; l < nl; l++) {
       float rh3 = 0.f, rv3 = 0.f;
@@ -1603,17 +1630,14 @@ RT_DEV void group_samples_add(const RenderArgs& A, const LightGroupsRec& G, floa
 
 // The record a frame variant's instances take as a kernel argument of their own, by its LT_* bits: the lens, the shutter
 // of a single-view frame (a multi-view one reads its records from RenderArgs' tables), the light groups, the light
-// picks, the vertex colours, the textures (with or without LT_VIEWS | LT_SHUTTER beside them) — or none.  park: (LT_VCOL, LT_TEX) the wave's three parked rows of LDS
-// (VColKd), or (LT_MAT) its eight (VMat), from the kernel that lays its LDS out.
-struct NoRec {};
+// picks — or, whatever the generator, the surface's (surface_t<LTV>::Rec) — or none.  park: the wave's parked rows of
+// LDS (surface_t<LTV>::Parked::ROWS of them), from the kernel that lays its LDS out.
 template <int LTV>
 using frame_rec_t = std::conditional_t<(LTV & LT_LENS) != 0, LensRec,
                     std::conditional_t<(LTV & LT_LIGHTS) != 0, LightGroupsRec,
                     std::conditional_t<(LTV & LT_PICK) != 0, PickRec,
-                    std::conditional_t<(LTV & LT_VCOL) != 0, VColRec,
-                    std::conditional_t<(LTV & LT_TEX) != 0, TexRec,
-                    std::conditional_t<(LTV & LT_MAT) != 0, MatRec,
-                    std::conditional_t<(LTV & LT_SHUTTER) != 0 && (LTV & LT_VIEWS) == 0, ShutterRec, NoRec>>>>>>>;
+                    std::conditional_t<surface_t<LTV>::LT != 0, typename surface_t<LTV>::Rec,
+                    std::conditional_t<(LTV & LT_SHUTTER) != 0 && (LTV & LT_VIEWS) == 0, ShutterRec, NoRec>>>>>;
 // (what the instances without a record leave out; the others do not compile without theirs)
 template <int LTV>
 constexpr const frame_rec_t<LTV>* no_record() {
@@ -1627,7 +1651,7 @@ template <bool BRUTE, bool PHOTON, bool POOLED, bool STATS, int LTV, class HP = 
 RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restrict__ accum, const Lds& L, uint32_t* pool,
                         float* ex, uint32_t wave, LaneStats& st, const frame_rec_t<LTV>* rec = no_record<LTV>(),
                         float* park = nullptr) {
-  constexpr int LT = LTV & ~(LT_VIEWS | LT_LENS | LT_SHUTTER | LT_LIGHTS | LT_PICK | LT_VCOL | LT_TEX | LT_MAT);
+  constexpr int LT = LTV & ~(LT_VIEWS | LT_LENS | LT_SHUTTER | LT_LIGHTS | LT_PICK | LT_SURFACES);
   constexpr bool VIEWS = (LTV & LT_VIEWS) != 0;
   constexpr bool LENS = (LTV & LT_LENS) != 0;
   constexpr bool SHUTTER = (LTV & LT_SHUTTER) != 0;
@@ -1636,8 +1660,11 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
   constexpr bool VCOL = (LTV & LT_VCOL) != 0;
   constexpr bool TEX = (LTV & LT_TEX) != 0;
   constexpr bool MAT = (LTV & LT_MAT) != 0;
-  // (the surface side and the camera side are orthogonal: a record of colours or textures goes with the plain generator
-  // or with the multi-view shutter's, the general camera form, whose tables come from RenderArgs)
+  // (the surface side and the camera side are orthogonal — below, the surface is SF alone and meets the generator
+  // nowhere: a record of colours or textures goes with the plain generator or with the multi-view shutter's, the general
+  // camera form, whose tables come from RenderArgs)
+  using SF = surface_t<LTV>;
+  using PV = typename SF::Parked;
   static_assert(!VCOL || (VIEWS == SHUTTER && !LENS && !LIGHTS && !PICK && !PHOTON), "vertex colours go with the plain frame or the multi-view shutter frame");
   static_assert(!TEX || (VIEWS == SHUTTER && !LENS && !LIGHTS && !PICK && !VCOL && !PHOTON), "textures go with the plain frame or the multi-view shutter frame");
   static_assert(!MAT || (!VIEWS && !LENS && !SHUTTER && !LIGHTS && !PICK && !VCOL && !TEX && !PHOTON), "material maps go with the plain frame only");
@@ -1726,32 +1753,17 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
         const bool bounce = A.mode == RT_MODE_PATH && depth + 1 < nvert;  // wave-uniform
         f3 nrm = mk(0.f, 0.f, 0.f), pt = nrm, bdir = nrm;
         uint32_t mesh = 0;
-        VColKd vk{nrm, park};  // (LT_VCOL, LT_TEX) the vertex's kdDiffuse
-        std::conditional_t<MAT, VMat, NoVCol> vm;  // (LT_MAT) the vertex's material
-        if constexpr (MAT) vm = VMat{rt_material{}, park};
+        PV sf;  // the vertex's surface value (zero without a vertex) with the wave's rows; ParkNone: empty
+        if constexpr (PV::ROWS != 0) sf = PV{{}, park};
         // (the vertex set-up is three dependent loads deep: it goes out ahead of other waves'
         // arithmetic, like the pool loop that follows; +0.4 % on C2)
         if (!(LT & LT_NOPRIO)) __builtin_amdgcn_s_setprio(1);
-        if constexpr (VCOL) {
+        if constexpr (PV::ROWS != 0) {
           if (alive) {
             uint4 tv;
             float u, v;
             vertex_setup_ray<FR>(S, h.id, o, d, nrm, pt, tv, u, v);
-            mesh = tv.w, vk.kd = vertex_kd(S, rec->vcol, tv, u, v);
-          }
-        } else if constexpr (TEX) {
-          if (alive) {
-            uint4 tv;
-            float u, v;
-            vertex_setup_ray<FR>(S, h.id, o, d, nrm, pt, tv, u, v);
-            mesh = tv.w, vk.kd = tex_kd(S, *rec, tv, u, v);
-          }
-        } else if constexpr (MAT) {
-          if (alive) {
-            uint4 tv;
-            float u, v;
-            vertex_setup_ray<FR>(S, h.id, o, d, nrm, pt, tv, u, v);
-            mesh = tv.w, vm.m = tex_mat(S, *rec, tv, u, v);
+            mesh = tv.w, sf.v = SF::form(S, *rec, tv, u, v);
           }
         } else
         if (alive) vertex_setup_ray<FR>(S, h.id, o, d, nrm, pt, mesh);
@@ -1774,12 +1786,9 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
         } else if constexpr (PICK) {
           static_assert(!SHADOW_BODY, "the light-pick instances keep their trees in HBM / L2");
           c = vertex_pool<STATS, LT, true, false, PickArgs>(S, alive, bounce, g, d, mesh, nrm, pt, bdir, L.stack, pool, nh, nfound, st, nullptr, nullptr, PickArgs{rec, pk});
-        } else if constexpr (VCOL || TEX) {
-          static_assert(!SHADOW_BODY, "the coloured and textured instances keep their trees in HBM / L2");
-          c = vertex_pool<STATS, LT, true, false, NoPick, VColKd>(S, alive, bounce, g, d, mesh, nrm, pt, bdir, L.stack, pool, nh, nfound, st, nullptr, nullptr, NoPick(), vk);
-        } else if constexpr (MAT) {
-          static_assert(!SHADOW_BODY, "the material-map instances keep their trees in HBM / L2");
-          c = vertex_pool<STATS, LT, true, false, NoPick, VMat>(S, alive, bounce, g, d, mesh, nrm, pt, bdir, L.stack, pool, nh, nfound, st, nullptr, nullptr, NoPick(), vm);
+        } else if constexpr (PV::ROWS != 0) {
+          static_assert(!SHADOW_BODY, "the instances with a surface keep their trees in HBM / L2");
+          c = vertex_pool<STATS, LT, true, false, NoPick, PV>(S, alive, bounce, g, d, mesh, nrm, pt, bdir, L.stack, pool, nh, nfound, st, nullptr, nullptr, NoPick(), sf);
         } else
         c = SHADOW_BODY && !bounce
                          ? vertex_pool<STATS, LT, false>(S, alive, false, g, d, mesh, nrm, pt, bdir, L.stack, pool, nh, nfound, st)
@@ -1815,18 +1824,10 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
         if (alive) c = shade_direct_seq<BRUTE, STATS, true>(S, g, d, h, L.stack, nrm, pt, st, rec, &gv);
       } else if constexpr (PICK) {
         if (alive) c = shade_direct_seq<BRUTE, STATS, false, PickArgs>(S, g, d, h, L.stack, nrm, pt, st, nullptr, nullptr, PickArgs{rec, pk});
-      } else if constexpr (VCOL) {
+      } else if constexpr (PV::ROWS != 0) {
         if (alive)
-          c = shade_direct_seq<BRUTE, STATS, false, NoPick, VColKd>(S, g, d, h, L.stack, nrm, pt, st, nullptr, nullptr, NoPick(),
-                                                                    VColKd{vertex_kd(S, rec->vcol, S.triShade[h.id], h.u, h.v), park});
-      } else if constexpr (TEX) {
-        if (alive)
-          c = shade_direct_seq<BRUTE, STATS, false, NoPick, VColKd>(S, g, d, h, L.stack, nrm, pt, st, nullptr, nullptr, NoPick(),
-                                                                    VColKd{tex_kd(S, *rec, S.triShade[h.id], h.u, h.v), park});
-      } else if constexpr (MAT) {
-        if (alive)
-          c = shade_direct_seq<BRUTE, STATS, false, NoPick, VMat>(S, g, d, h, L.stack, nrm, pt, st, nullptr, nullptr, NoPick(),
-                                                                  VMat{tex_mat(S, *rec, S.triShade[h.id], h.u, h.v), park});
+          c = shade_direct_seq<BRUTE, STATS, false, NoPick, PV>(S, g, d, h, L.stack, nrm, pt, st, nullptr, nullptr, NoPick(),
+                                                                PV{SF::form(S, *rec, S.triShade[h.id], h.u, h.v), park});
       } else {
         if (alive) c = shade_direct_seq<BRUTE, STATS>(S, g, d, h, L.stack, nrm, pt, st);
       }
