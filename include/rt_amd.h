@@ -50,6 +50,8 @@
  *                                  its first-hit AOVs with the hit mesh's texture sampled at every shaded vertex (+ _device forms)
  *   rt_set_material_maps / rt_render_material <- (no counterpart) textured kd, alpha and f0: the textured frame with the
  *                                  whole material of every shaded vertex sampled from the resident textures (+ _device form)
+ *   rt_set_normal_maps / rt_render_normal_mapped <- (no counterpart) tangent-space normal maps: that frame with the shading
+ *                                  normal of every shaded vertex turned by a texture of the resident set (+ _device form)
  *   rt_render_aov_views / rt_render_motion_views / rt_denoise_batch <- (no counterpart) the AOVs, motion vectors and
  *                                  denoised frames of those views, one launch each (+ _device forms)
  *   rt_trace                    <- RayTracer::rayTrace (RayTracer.h:27-53) test hook
@@ -72,7 +74,8 @@
  *     rt_render_views_shutter_device (tests/test_gpu_views_shutter.py), rt_render_lights_device
  *     (tests/test_gpu_lights.py), rt_render_pick_device (tests/test_gpu_pick.py), rt_render_colors_device
  *     (tests/test_gpu_vcol.py), rt_render_textured_device (tests/test_gpu_tex.py), rt_render_material_device
- *     (tests/test_gpu_mat.py) and rt_render_lens_device with stats == NULL;
+ *     (tests/test_gpu_mat.py), rt_render_normal_mapped_device (tests/test_gpu_nmap.py) and
+ *     rt_render_lens_device with stats == NULL;
  *     rt_resolve_device;
  *     rt_render_aov_device, rt_render_aov_colors_device, rt_render_aov_textured_device, rt_render_ao_device, rt_render_motion_device; rt_temporal_accumulate_device,
  *     rt_svgf_device, rt_denoise_device, rt_denoise_batch_device; rt_render_aov_views_device,
@@ -87,7 +90,8 @@
  *   SYNCHRONISE `stream`, and only it, before they return, because the host reads a result back:
  *     rt_render_device, rt_render_views_device, rt_render_rays_device, rt_render_shutter_device,
  *     rt_render_views_shutter_device, rt_render_lights_device, rt_render_pick_device, rt_render_colors_device,
- *     rt_render_textured_device, rt_render_material_device, rt_render_lens_device with stats != NULL;
+ *     rt_render_textured_device, rt_render_material_device, rt_render_normal_mapped_device,
+ *     rt_render_lens_device with stats != NULL;
  *     rt_render_adaptive_device and rt_render_adaptive_shutter_device (every pass); rt_update_vertices_device,
  *     rt_update_transforms and rt_update_skin (twice);
  *     the four multi-view forms when a view lies far enough out to need a wider box padding (a refit).
@@ -977,7 +981,7 @@ int rt_render_aov_colors_device(rt_ctx* ctx, const rt_params* p, const rt_aov* d
  * summing c at the first hit (the mesh's albedo on an RT_TEX_NONE mesh); every other channel is rt_render_aov's bit for
  * bit.  rt_render_aov's checks, then RT_ERR_STATE without a resident set.
  * Out of scope: mip maps and any filter that needs ray footprints; 8-bit or sRGB texel storage; textures on
- * normals (on kd, alpha and f0: rt_render_material below); textures combined with vertex colours, the lens, the shutter, light groups, light picks, views, adaptive passes
+ * kd, alpha and f0 and on normals here (rt_render_material and rt_render_normal_mapped below); textures combined with vertex colours, the lens, the shutter, light groups, light picks, views, adaptive passes
  * or rt_render_rays; rt_group; a device-memory form of the set.                                                          */
 #define RT_TEX_NONE 0xffffffffu
 enum { RT_TEX_REPEAT = 0, RT_TEX_CLAMP = 1 };
@@ -1436,7 +1440,7 @@ int rt_render_aov_views_albedo_device(rt_ctx* ctx, const rt_params* p, const rt_
  * stream order are rt_render_textured_device's.
  * Out of scope: maps under the lens, the shutter or views (rt_render_views_shutter_albedo refuses albedo > 2), under light
  * groups, picks, adaptive passes or ray batches; f0 / roughness AOV channels (rt_aov has no room); a second uv set;
- * normal maps (they move the bounce ray); rt_group.                                                                    */
+ * rt_group.  (Normal maps, which move the bounce ray, are rt_render_normal_mapped's below.)                            */
 typedef struct rt_material_maps {
   uint32_t n_meshes;              /* must be the context's */
   const uint32_t* mesh_f0;        /* [n_meshes] HOST: index into the RESIDENT texture set or RT_TEX_NONE; rgb -> f0.
@@ -1451,6 +1455,72 @@ int rt_render_material(rt_ctx* ctx, const rt_params* p, const float* background_
                        rt_stats* stats);
 /* Accumulate into caller-zeroed DEVICE d_accum [h][w][4] on `stream`, as rt_render_textured_device does. */
 int rt_render_material_device(rt_ctx* ctx, const rt_params* p, void* d_accum, void* stream, rt_stats* stats);
+
+/* ---- tangent-space normal maps: the shading normal from the resident textures --------------------------
+ * rt_set_normal_maps names, per mesh, one more texture of the RESIDENT texture set (rt_set_textures), and
+ * rt_render_normal_mapped renders rt_render_material's frame with one more substitution at every shaded vertex: the
+ * interpolated unit shading normal N (Renderer.cpp:42) is replaced by N' BEFORE anything reads it.  From then on the
+ * light terms, the BSDF and the hemisphere sample of the bounce all use N', so — unlike every other surface form — the
+ * paths differ from rt_render's from depth 1 on, and so do both ray counts.  The reference integrator never looks at a
+ * geometric normal, and neither does this frame: no side test, no clamping of N' to the hemisphere of the incoming ray.
+ * Material maps are optional: without resident material maps the frame behaves as under maps that are RT_TEX_NONE on
+ * every mesh; rt_set_material_maps and rt_set_normal_maps may be called in either order.
+ * N' is formed in float32, every operation rounded on its own, nothing fused, in exactly these operations (dot3, cross3
+ * and unit3 are Vec3.h's: products summed left to right; a * (1 / sqrt(dot3(a, a))) per component):
+ *   p0, p1, p2   the hit triangle's CURRENT vertex positions;  e1 = p1 - p0, e2 = p2 - p0
+ *   (s_k, t_k)   its three vertices' uvs;  a1 = s1 - s0, a2 = s2 - s0, b1 = t1 - t0, b2 = t2 - t0
+ *   r  = a1 * b2 - a2 * b1
+ *   Tr = b2 * e1 - b1 * e2,  Br = a1 * e2 - a2 * e1   (per component; both negated when r < 0)
+ *   Tp = Tr - dot3(N, Tr) * N;  T = unit3(Tp)
+ *   B  = cross3(N, T), negated when dot3(B, Br) < 0
+ *   m  = the sample of texture mesh_normal[mesh] at the hit coordinate the albedo uses (rt_render_textured's (s, t)), by
+ *        rt_render_textured's sampler under that texture's own filter and wraps
+ *   x = 2 * m.r - 1,  y = 2 * m.g - 1,  z = 2 * m.b - 1
+ *   V  = (x * T + y * B) + z * N;  N' = unit3(V)
+ * The vertex keeps N, with no arithmetic on it, when the mesh's entry is RT_TEX_NONE; when x == 0 && y == 0; when
+ * !(r != 0) (zero or NaN: the uvs span no area); when !(dot3(Tp, Tp) > 0); or when dot3(V, V) is not finite and positive.
+ * Nothing of the tangent frame is stored: it is formed at every vertex from the positions and uvs resident then.
+ * Guarantees, bit for bit on accumulator, image, samples and both ray counts:
+ *   - N1: a table that is RT_TEX_NONE on every mesh (or NULL) gives rt_render_material's frame; so does any map whose
+ *     texels are (0.5, 0.5, b) with any b, whatever the uvs, filters and wraps (equal texels sample to that texel exactly,
+ *     as M1 argues, and 2 * 0.5 - 1 is 0).  With M1 and T1 that frame is rt_render's.
+ *   - N2: the frame follows the geometry: after rt_update, rt_update_transforms or rt_update_skin it is the frame of a
+ *     fresh context created on the moved scene with the same sets.
+ *   - N3: sample ranges chain (spp_begin / spp_count), and host and device forms agree.
+ *   - N4: reserved[0] (lanes per pixel), reserved[1] bit 0 (no pool), collect_stats, RT_ACCEL_BRUTE and the node format
+ *     change the schedule, never the bits.
+ * rt_set_normal_maps is a host form in rt_set_material_maps' pattern: it copies the table to the context's device, into a
+ * fresh allocation, and then replaces the one before, which is freed once the launches that read it have run; NULL
+ * releases.  It changes nothing any other entry point reads; the table stays across every update, refit, rt_rebuild,
+ * transform and skin.  The indices refer to the texture set resident AT THE CALL: a later rt_set_textures (replace or
+ * release) makes the table stale until rt_set_normal_maps is called again.  Refusals, in this order, with rt_last_error
+ * naming the first offender:
+ *   RT_ERR_INVALID  a null maps with a null ctx; a non-zero reserved word; a null ctx; n_meshes different from the context's
+ *   RT_ERR_STATE    a context that refuses launches
+ *   RT_ERR_STATE    no resident texture set
+ *   RT_ERR_INVALID  an entry that is neither an index below the resident set's n_textures nor RT_TEX_NONE (the message
+ *                   names the mesh)
+ * rt_render_normal_mapped / rt_render_normal_mapped_device take rt_render_material's / rt_render_material_device's
+ * arguments and rt_render_textured's checks in its order and with its codes; then, last of all, RT_ERR_STATE without a
+ * resident texture set, without resident normal maps, with stale normal maps ("the normal maps were set for another
+ * texture set"), or with resident material maps that are stale.  A rejected call writes nothing.  The kernels are
+ * rt_render_material's family (one wave per workgroup, no persistent instances); buffers, stats and the device form's
+ * stream order are rt_render_material_device's.
+ * Out of scope: normal maps under the lens, the shutter, views, light groups, picks, adaptive passes, ray batches or
+ * rt_group; the perturbed normal in the AOV normal channel and the denoisers' guides; object-space maps; a strength
+ * factor; height or bump maps; per-vertex tangents supplied by the caller; 8-bit texel storage; a second uv set.       */
+typedef struct rt_normal_maps {
+  uint32_t n_meshes;            /* must be the context's */
+  const uint32_t* mesh_normal;  /* [n_meshes] HOST: index into the RESIDENT texture set or RT_TEX_NONE; rgb -> (x, y, z) of
+                                   the tangent-space normal by 2 c - 1.  NULL = RT_TEX_NONE on every mesh */
+  uint32_t reserved[6];         /* zero */
+} rt_normal_maps;
+int rt_set_normal_maps(rt_ctx* ctx, const rt_normal_maps* maps /* NULL: release */);
+/* out_rgb [h][w][3] or NULL, accum_out [h][w][4] or NULL, background_rgb [h][w][3]: as rt_render's */
+int rt_render_normal_mapped(rt_ctx* ctx, const rt_params* p, const float* background_rgb, float* out_rgb, float* accum_out,
+                            rt_stats* stats);
+/* Accumulate into caller-zeroed DEVICE d_accum [h][w][4] on `stream`, as rt_render_material_device does. */
+int rt_render_normal_mapped_device(rt_ctx* ctx, const rt_params* p, void* d_accum, void* stream, rt_stats* stats);
 
 /* ---- multi-GPU (Renderer.cpp:219-265 sharded by pixel tiles) -------------
  * A tile-sharded frame: rank r of `world` integrates the pixels whose `tile`-pixel granule

@@ -2,7 +2,7 @@
 // rt_render_lens, rt_render_shutter, rt_render_views_shutter, rt_render_lights (DESIGN.md §6m–§6p), rt_render_pick (§6r)
 // and, with another albedo at every vertex, rt_render_colors (§6t), rt_render_textured (§6u), both under the multi-view
 // shutter's generator, rt_render_views_shutter_albedo (§6v), and, with a whole material at every vertex, rt_render_material
-// (§6w).
+// (§6w), and with a tangent-space normal map turning every vertex's shading normal, rt_render_normal_mapped (§6y).
 //
 // Every variant is render_tile itself under one more LT_* bit, on the one-wave-per-workgroup family that k_render serves:
 // brute, sequential and pooled, each counted (STATS, one wave per SIMD) and timed (four waves per SIMD, k_render's target);
@@ -34,6 +34,11 @@
 //   material maps SurfMat (LT_MAT)       MatRec: every shaded vertex forms its whole material from up to three samples
 //                                        at the hit's uv (tex_mat: albedo, f0, (kd, alpha)), parked in eight rows, and
 //                                        shades with bsdf_base(const rt_material&) of it
+//   normal maps   SurfNrm (LT_NMAP)      NrmRec: the material-map frame's vertex (tex_mat, the same eight rows; without
+//                                        resident material maps the two tables are kTexNone everywhere) whose shading
+//                                        normal is replaced at the set-up, before anything reads it, by the one the
+//                                        mesh's normal map turns in the triangle's tangent frame (nmap_bend): the
+//                                        light terms, the BSDF and the bounce use that, so the paths are its own
 // A variant is one generator part with one surface part (Variant<G, SF>): its LT_* bits are the OR of theirs, its record
 // the one part's that has one, its LDS the generator's stack rows and the surface's parked rows.  The two meet nowhere in
 // render_tile: the sample's primary ray is complete before the first vertex reads the surface's record.  variant_exists
@@ -119,6 +124,7 @@ struct GenViewsShutter {
 
 // the pairs that are compiled, by the parts' LT_* bits ((0, 0), the plain frame itself, is launch_render's)
 constexpr bool variant_exists(int gen, int surface) {
+  // (every surface, SurfNrm among them, under the plain generator; the two albedo surfaces under views+shutter too)
   return surface == 0 || gen == 0 || (gen == (LT_VIEWS | LT_SHUTTER) && (surface == LT_VCOL || surface == LT_TEX));
 }
 
@@ -196,6 +202,7 @@ static hipError_t launch_surface(const FrameVariant& F, bool brute_force, bool s
     case FrameVariant::VCOL: return launch_pair<G, SurfVCol>(F, brute_force, stats, S, A, accum, counters, stream);
     case FrameVariant::TEX: return launch_pair<G, SurfTex>(F, brute_force, stats, S, A, accum, counters, stream);
     case FrameVariant::MAT: return launch_pair<G, SurfMat>(F, brute_force, stats, S, A, accum, counters, stream);
+    case FrameVariant::NMAP: return launch_pair<G, SurfNrm>(F, brute_force, stats, S, A, accum, counters, stream);
   }
   return hipErrorInvalidValue;
 }

@@ -26,6 +26,7 @@
 #include "bvh_build.h"
 #include "filters.h"
 #include "material_maps.h"
+#include "normal_maps.h"
 #include "rt_amd.h"
 #include "rt_kernels.h"
 #include "wave_tiles.h"
@@ -337,6 +338,15 @@ struct rt_ctx {
     uint64_t texGeneration = 0;
     explicit operator bool() const { return (bool)f0; }
   } matMaps;
+  // rt_set_normal_maps: every mesh's normal map, a texture index into the set of generation texGeneration (normal null:
+  // none); rt_render_normal_mapped alone reads it, and no update touches it.  noMaps: [nMeshes] RT_TEX_NONE, which that
+  // frame reads in place of the two material tables while no material maps are resident (made with the first table)
+  struct NrmMaps {
+    DevBuf<uint32_t> normal;
+    uint64_t texGeneration = 0;
+    explicit operator bool() const { return (bool)normal; }
+  } nrmMaps;
+  DevBuf<uint32_t> noMaps;
   // scratch of rt_denoise_device and rt_svgf_device (rtk::filter_scratch; grows on demand: ensure_filter_scratch)
   DevBuf<float4> dnScratch;
   size_t dnCap = 0;
@@ -692,7 +702,8 @@ struct TileList {
 // What forms or splits a frame's samples in place of the plain frame, if anything: the thin lens of rt_render_lens, the
 // open shutter of rt_render_shutter, the light groups of rt_render_lights (dAccum then holds one slice per group) or the
 // light picks of rt_render_pick — and what its vertices shade with in place of their meshes' materials: the vertex colours
-// of rt_render_colors, the textures of rt_render_textured or the material maps of rt_render_material — with the record
+// of rt_render_colors, the textures of rt_render_textured, the material maps of rt_render_material or the normal maps of
+// rt_render_normal_mapped — with the record
 // its kernels take; their callers have refused photons and the wavefront bit (frame_params_checks).  A multi-view
 // shutter frame carries its records in its TileList instead: launch_frame tells it from them.
 using FrameGen = rtk::FrameVariant;
@@ -2702,6 +2713,7 @@ struct SurfaceGen {
   rtk::VColRec vcol{};
   rtk::TexRec tex{};
   rtk::MatRec mat{};
+  rtk::NrmRec nrm{};
   FrameGen gen;
   SurfaceGen() = default;
   SurfaceGen(const SurfaceGen&) = delete;
@@ -2712,12 +2724,18 @@ inline FrameGen::Surface albedo_surface(uint32_t albedo) {
   return albedo == RT_ALBEDO_COLORS ? FrameGen::VCOL : albedo == RT_ALBEDO_TEXTURES ? FrameGen::TEX : FrameGen::NONE;
 }
 // G for surface `kind`, or RT_ERR_STATE where the context lacks what it reads: the colours; the textures, then the maps,
-// then maps that were set for these textures
+// then maps that were set for these textures (NMAP: the normal maps, then material maps if any are resident — without
+// them the frame reads noMaps, RT_TEX_NONE on every mesh, for both material tables)
 int resident_surface(const rt_ctx* c, FrameGen::Surface kind, SurfaceGen* G) {
   if (kind == FrameGen::VCOL && !c->vcol) return fail(RT_ERR_STATE, "the context has no resident vertex colours (rt_set_vertex_colors)");
-  if ((kind == FrameGen::TEX || kind == FrameGen::MAT) && !c->tex) return fail(RT_ERR_STATE, "the context has no resident textures (rt_set_textures)");
+  if ((kind == FrameGen::TEX || kind == FrameGen::MAT || kind == FrameGen::NMAP) && !c->tex) return fail(RT_ERR_STATE, "the context has no resident textures (rt_set_textures)");
   if (kind == FrameGen::MAT && !c->matMaps) return fail(RT_ERR_STATE, "the context has no resident material maps (rt_set_material_maps)");
   if (kind == FrameGen::MAT && c->matMaps.texGeneration != c->tex.generation)
+    return fail(RT_ERR_STATE, "the material maps were set for another texture set (rt_set_material_maps after rt_set_textures)");
+  if (kind == FrameGen::NMAP && !c->nrmMaps) return fail(RT_ERR_STATE, "the context has no resident normal maps (rt_set_normal_maps)");
+  if (kind == FrameGen::NMAP && c->nrmMaps.texGeneration != c->tex.generation)
+    return fail(RT_ERR_STATE, "the normal maps were set for another texture set (rt_set_normal_maps after rt_set_textures)");
+  if (kind == FrameGen::NMAP && c->matMaps && c->matMaps.texGeneration != c->tex.generation)
     return fail(RT_ERR_STATE, "the material maps were set for another texture set (rt_set_material_maps after rt_set_textures)");
   const rtk::TexRec T = c->tex.rec();
   switch (kind) {
@@ -2727,6 +2745,12 @@ int resident_surface(const rt_ctx* c, FrameGen::Surface kind, SurfaceGen* G) {
     case FrameGen::MAT:
       G->mat = rtk::MatRec{T.uv, T.meshTex, T.desc, T.texels, c->matMaps.f0.get(), c->matMaps.kdAlpha.get()}, G->gen = FrameGen(G->mat);
       break;
+    case FrameGen::NMAP: {
+      const uint32_t* f0 = c->matMaps ? c->matMaps.f0.get() : c->noMaps.get();
+      const uint32_t* kdAlpha = c->matMaps ? c->matMaps.kdAlpha.get() : c->noMaps.get();
+      G->nrm = rtk::NrmRec{rtk::MatRec{T.uv, T.meshTex, T.desc, T.texels, f0, kdAlpha}, c->nrmMaps.normal.get()}, G->gen = FrameGen(G->nrm);
+      break;
+    }
   }
   return RT_OK;
 }
@@ -3967,10 +3991,10 @@ int rt_render_pick(rt_ctx* c, const rt_params* p, const rt_light_pick* k, const 
 // ---- per-vertex albedo ---------------------------------------------------------------------------------
 namespace {
 
-// Everything both forms of rt_render_colors, rt_render_textured and rt_render_material check, in the header's order
+// Everything both forms of rt_render_colors, rt_render_textured, rt_render_material and rt_render_normal_mapped check, in the header's order
 // (lens_checks' shape: the arguments alone first, then the device, the context last), and the surface the kernels take.
 int surface_checks(const rt_ctx* c, const rt_params* p, const char* outputs, FrameGen::Surface kind, SurfaceGen* G) {
-  static const char* const nouns[] = {"", "coloured", "textured", "material-map"};
+  static const char* const nouns[] = {"", "coloured", "textured", "material-map", "normal-mapped"};
   if (!c || !p) return fail(RT_ERR_INVALID, "ctx/params is null");
   if (outputs) return fail(RT_ERR_INVALID, "%s", outputs);
   int rc = check_params_shape(p);
@@ -4169,6 +4193,50 @@ int rt_render_material_device(rt_ctx* c, const rt_params* p, void* d_accum, void
 }
 int rt_render_material(rt_ctx* c, const rt_params* p, const float* bg, float* out_rgb, float* accum_out, rt_stats* stats) {
   return surface_frame_host(c, p, FrameGen::MAT, bg, out_rgb, accum_out, stats);
+}
+
+}  // extern "C"
+
+// ---- tangent-space normal maps ---------------------------------------------------------------------------
+extern "C" {
+
+int rt_set_normal_maps(rt_ctx* c, const rt_normal_maps* m) {
+  if (!m) {
+    if (!c) return fail(RT_ERR_INVALID, "ctx/maps is null");
+    HIP_TRY(hipSetDevice(c->device));
+    c->nrmMaps = rt_ctx::NrmMaps();
+    return RT_OK;
+  }
+  const int word = rtnrm::first_reserved(*m);
+  if (word >= 0) return fail(RT_ERR_INVALID, "normal maps: reserved[%d] is %u, not 0", word, m->reserved[word]);
+  if (!c) return fail(RT_ERR_INVALID, "ctx/maps is null");
+  if (m->n_meshes != c->nMeshes) return fail(RT_ERR_INVALID, "normal maps: %u meshes for a context of %u", m->n_meshes, c->nMeshes);
+  int rc = check_not_broken(c);  // (as rt_set_material_maps: nothing is uploaded to a context that refuses launches)
+  if (rc != RT_OK) return rc;
+  if (!c->tex) return fail(RT_ERR_STATE, "the context has no resident textures (rt_set_textures)");
+  std::vector<uint32_t> table;
+  std::string why;
+  if (!rtnrm::build_table(*m, c->tex.nTextures, &table, &why)) return fail(RT_ERR_INVALID, "%s", why.c_str());
+  HIP_TRY(hipSetDevice(c->device));
+  // the table of RT_TEX_NONE a frame without material maps reads: made once, never written again
+  if (!c->noMaps) {
+    const std::vector<uint32_t> none(c->nMeshes, RT_TEX_NONE);
+    if ((rc = upload(&c->noMaps, none.data(), none.size())) != RT_OK) return rc;
+  }
+  // the new table replaces the old one only when it is resident; the old one is then freed under launches that may still
+  // read it, which hipFree waits for
+  rt_ctx::NrmMaps fresh;
+  if ((rc = upload(&fresh.normal, table.data(), table.size())) != RT_OK) return rc;
+  fresh.texGeneration = c->tex.generation;
+  c->nrmMaps = std::move(fresh);
+  return RT_OK;
+}
+
+int rt_render_normal_mapped_device(rt_ctx* c, const rt_params* p, void* d_accum, void* stream, rt_stats* stats) {
+  return surface_frame_device(c, p, FrameGen::NMAP, d_accum, stream, stats);
+}
+int rt_render_normal_mapped(rt_ctx* c, const rt_params* p, const float* bg, float* out_rgb, float* accum_out, rt_stats* stats) {
+  return surface_frame_host(c, p, FrameGen::NMAP, bg, out_rgb, accum_out, stats);
 }
 
 }  // extern "C"

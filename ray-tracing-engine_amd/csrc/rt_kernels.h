@@ -250,15 +250,23 @@ struct MatRec {
   const uint32_t* meshF0;       // [n_meshes]: f0's texture, or kTexNone
   const uint32_t* meshKdAlpha;  // [n_meshes]: (kd, alpha)'s texture, or kTexNone
 };
+// the frame with tangent-space normal maps (rt_render_normal_mapped): MatRec's frame (mat: its six fields; a context
+// without resident material maps passes tables of kTexNone for the last two) in which the shading normal of every shaded
+// vertex of a mesh with a normal map is turned by the map's sample at the same hit coordinate, in the tangent frame formed
+// from the triangle's current positions and uvs (rt_amd.h's operations); kTexNone keeps the interpolated normal.
+struct NrmRec {
+  MatRec mat;
+  const uint32_t* meshNormal;  // [n_meshes]: the normal map's texture, or kTexNone
+};
 // Which variant a frame is: a generator part (what forms its primary rays, splits its samples or lists its lights) and
 // a surface part (what its vertices shade with), with the one record of the pair (which the caller keeps alive over the
-// launch call): the generator's LensRec, ShutterRec, LightGroupsRec or PickRec, or the surface's VColRec, TexRec or
-// MatRec.  VIEWS_SHUTTER, many views each under its own open shutter (rt_render_views_shutter), has no record of its own
+// launch call): the generator's LensRec, ShutterRec, LightGroupsRec or PickRec, or the surface's VColRec, TexRec,
+// MatRec or NrmRec.  VIEWS_SHUTTER, many views each under its own open shutter (rt_render_views_shutter), has no record of its own
 // — tile t renders with views[tileView[t]]'s camera, seed and slice under viewShutters[tileView[t]], from RenderArgs'
 // three tables — so it carries a surface's.
 struct FrameVariant {
   enum Gen { PLAIN, LENS, SHUTTER, LIGHTS, PICK, VIEWS_SHUTTER };
-  enum Surface { NONE, VCOL, TEX, MAT };
+  enum Surface { NONE, VCOL, TEX, MAT, NMAP };
   Gen gen = PLAIN;
   Surface surface = NONE;
   const void* rec = nullptr;
@@ -270,6 +278,7 @@ struct FrameVariant {
   FrameVariant(const VColRec& r) : surface(VCOL), rec(&r) {}
   FrameVariant(const TexRec& r) : surface(TEX), rec(&r) {}
   FrameVariant(const MatRec& r) : surface(MAT), rec(&r) {}
+  FrameVariant(const NrmRec& r) : surface(NMAP), rec(&r) {}
   // F's surface under the multi-view shutter's generator (rt_render_views_shutter_albedo; a plain F: the multi-view
   // shutter frame itself), with RenderArgs' three tables
   static FrameVariant under_views_shutter(FrameVariant F) {
@@ -280,7 +289,7 @@ struct FrameVariant {
   // the variant in an error message: "<name> render launch failed"
   std::string name() const {
     static const char* const gens[] = {"", "lens", "shutter", "light-group", "light-pick", "multi-view shutter"};
-    static const char* const surfaces[] = {"", "vertex-colour", "textured", "material-map"};
+    static const char* const surfaces[] = {"", "vertex-colour", "textured", "material-map", "normal-mapped"};
     return std::string(gens[gen]) + (gen != PLAIN && surface != NONE ? " " : "") + surfaces[surface];
   }
 };
@@ -292,7 +301,7 @@ struct FrameVariant {
 // the three tables set.  LIGHTS: accum is [G.n][height][width], slice g at accum + g * width * height.  PICK: pooled
 // whenever A.flags bit 0 is set, whatever the scene's light count (a vertex sends m <= POOL_L shadow rays).
 // The surface decides the LDS a launch allocates per wave beyond the generator's: the rows its policy parks a vertex's
-// value in (VCOL and TEX three, the kdDiffuse; MAT eight, the material).
+// value in (VCOL and TEX three, the kdDiffuse; MAT and NMAP eight, the material).
 hipError_t launch_render_variant(const FrameVariant& F, bool brute_force, bool stats, const DevScene& S, const RenderArgs& A,
                                  float4* accum, unsigned long long* counters, hipStream_t stream);
 // The AOV pass.  views null: the frame of S.cam and A.seed; else the same pass over nViews views in one launch

@@ -245,7 +245,11 @@ constexpr int LT_TEX = 32768;
 // material from the samples at the hit's uv (tex_mat); it reaches the vertex pool and shade_direct_seq through their VC
 // switch as SurfMat's ParkMat, which shades with bsdf_base(const rt_material&) in place of the mesh's DevMat.
 constexpr int LT_MAT = 65536;
-constexpr int LT_SURFACES = LT_VCOL | LT_TEX | LT_MAT;  // (the bits surface_t reads)
+// A frame with tangent-space normal maps (rt_render_normal_mapped): render_tile takes a NrmRec, forms every vertex's
+// material as the material-map frame does (SurfNrm parks SurfMat's ParkMat) and, before anything reads the shading
+// normal, replaces it by the perturbed one (nmap_bend): the light terms, the BSDF and the bounce then use that.
+constexpr int LT_NMAP = 131072;
+constexpr int LT_SURFACES = LT_VCOL | LT_TEX | LT_MAT | LT_NMAP;  // (the bits surface_t reads)
 constexpr uint32_t kPrioMaxNodes = 65536;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(3))) u32x4* lds_u4_ptr;
@@ -852,6 +856,20 @@ RT_DEV void vertex_setup_ray(const DevScene& S, uint32_t id, f3 o, f3 d, f3& hit
   hitNormal = unit3<FAST>(interp3(S.vnrm, tv, w, u, v));
   point = w * p0 + u * p1 + v * p2;
 }
+// (... and e1 = p1 - p0, e2 = p2 - p0, the edges the test ran on, for the caller that forms a tangent frame: the
+// positions are loaded once)
+template <bool FAST = false>
+RT_DEV void vertex_setup_ray(const DevScene& S, uint32_t id, f3 o, f3 d, f3& hitNormal, f3& point, uint4& tv, float& u, float& v,
+                             f3& e1, f3& e2) {
+  tv = S.triShade[id];
+  const f3 p0 = ld(S.vpos + 3 * (size_t)tv.x), p1 = ld(S.vpos + 3 * (size_t)tv.y), p2 = ld(S.vpos + 3 * (size_t)tv.z);
+  e1 = p1 - p0, e2 = p2 - p0;
+  float t;
+  tri_test(o, d, p0, e1, e2, u, v, t, true);
+  const float w = 1.f - u - v;
+  hitNormal = unit3<FAST>(interp3(S.vnrm, tv, w, u, v));
+  point = w * p0 + u * p1 + v * p2;
+}
 template <bool FAST = false>
 RT_DEV void vertex_setup_ray(const DevScene& S, uint32_t id, f3 o, f3 d, f3& hitNormal, f3& point, uint32_t& mesh) {
   uint4 tv;
@@ -955,6 +973,37 @@ RT_DEV rt_material tex_mat(const DevScene& S, const MatRec& M, uint4 tv, float u
   }
   return m;
 }
+// The shading normal a vertex of a normal-mapped frame shades and bounces with (rt_render_normal_mapped): N, the
+// interpolated unit normal, turned by the sample of the mesh's normal map in the tangent frame of the hit triangle.  The
+// frame is formed here, from the triangle's CURRENT edges e1, e2 (p1 - p0, p2 - p0) and its three uvs: nothing of it is
+// cached, so it follows every update.  The operations are rt_amd.h's list, one by one, every one rounded on its own.  N
+// comes back untouched — no arithmetic on it — where the mesh has no map, where the sample's x and y are both 0 (a flat
+// texel), and where the frame or the result degenerates.  The uv gathers and the map's index are tex_mat's loads again
+// (the same addresses, no store between: the compiler keeps one copy), and the map is sampled behind tex_mat's three.
+RT_DEV f3 nmap_bend(const NrmRec& R, uint4 tv, float u, float v, f3 e1, f3 e2, f3 N) {
+  const float2* uv = reinterpret_cast<const float2*>(R.mat.uv);
+  const uint32_t tn = R.meshNormal[tv.w];
+  const float2 a = uv[tv.x], b = uv[tv.y], c = uv[tv.z];
+  if (tn == kTexNone) return N;
+  const TexDesc D = R.mat.desc[tn];
+  const float a1 = b.x - a.x, a2 = c.x - a.x, b1 = b.y - a.y, b2 = c.y - a.y;
+  const float r = a1 * b2 - a2 * b1;
+  if (!(r != 0.f)) return N;  // (zero or NaN: the uvs span no area)
+  f3 Tr = b2 * e1 - b1 * e2, Br = a1 * e2 - a2 * e1;
+  if (r < 0.f) Tr = -Tr, Br = -Br;
+  const f3 Tp = Tr - dot3(N, Tr) * N;
+  if (!(dot3(Tp, Tp) > 0.f)) return N;
+  const f3 T = unit3(Tp);
+  f3 B = cross3(N, T);
+  if (dot3(B, Br) < 0.f) B = -B;
+  const f3 m = tex_sample(R.mat.texels, D, tex_coord(a.x, b.x, c.x, u, v), tex_coord(a.y, b.y, c.y, u, v));
+  const float x = 2.f * m.x - 1.f, y = 2.f * m.y - 1.f, z = 2.f * m.z - 1.f;
+  if (x == 0.f && y == 0.f) return N;
+  const f3 V = (x * T + y * B) + z * N;
+  const float vv = dot3(V, V);
+  if (!(vv > 0.f) || !(vv < __builtin_inff())) return N;  // (not finite and positive)
+  return unit3(V);
+}
 // What a vertex shades with in place of its mesh's DevMat, while the wave traverses: the value (v) and the rows of LDS
 // where it is parked over every walk (ROWS of [64] floats, the wave's, behind its stack rows and pool, allocated for these
 // instances alone: held in registers, it would cost the timed instances, which sit at their budget, as many more of
@@ -990,20 +1039,23 @@ struct ParkMat {  // a material, in eight rows in rt_material's field order
   }
 };
 // The surface policies, one per surface a frame can carry (surface_t picks it by the frame's LT_* bits): the record its
-// frames take (Rec), what a vertex parks (Parked), how that value is formed from the hit's (tv, u, v) (form), and the
-// records the launcher answers hipErrorInvalidValue to (refused).  A new surface is one more policy here, its bit in
-// surface_t and its row in frame_variants.h.
+// frames take (Rec), what a vertex parks (Parked), how that value is formed from the hit's (tv, u, v) (form), whether
+// the surface replaces the vertex's shading normal before anything reads it (BENDS, then by bend), and the records the
+// launcher answers hipErrorInvalidValue to (refused).  A new surface is one more policy here, its bit in surface_t and
+// its row in frame_variants.h.
 struct NoRec {};
 struct SurfNone {
   using Rec = NoRec;
   using Parked = ParkNone;
   static constexpr int LT = 0;
+  static constexpr bool BENDS = false;
   static bool refused(const Rec&) { return false; }
 };
 struct SurfVCol {  // rt_render_colors
   using Rec = VColRec;
   using Parked = ParkKd;
   static constexpr int LT = LT_VCOL;
+  static constexpr bool BENDS = false;
   static RT_DEV f3 form(const DevScene& S, const Rec& R, uint4 tv, float u, float v) { return vertex_kd(S, R.vcol, tv, u, v); }
   static bool refused(const Rec& R) { return !R.vcol; }
 };
@@ -1011,6 +1063,7 @@ struct SurfTex {  // rt_render_textured
   using Rec = TexRec;
   using Parked = ParkKd;
   static constexpr int LT = LT_TEX;
+  static constexpr bool BENDS = false;
   static RT_DEV f3 form(const DevScene& S, const Rec& R, uint4 tv, float u, float v) { return tex_kd(S, R, tv, u, v); }
   static bool refused(const Rec& R) { return !R.uv || !R.meshTex || !R.desc || !R.texels; }
 };
@@ -1018,13 +1071,24 @@ struct SurfMat {  // rt_render_material
   using Rec = MatRec;
   using Parked = ParkMat;
   static constexpr int LT = LT_MAT;
+  static constexpr bool BENDS = false;
   static RT_DEV rt_material form(const DevScene& S, const Rec& R, uint4 tv, float u, float v) { return tex_mat(S, R, tv, u, v); }
   static bool refused(const Rec& R) { return !R.uv || !R.meshTex || !R.desc || !R.texels || !R.meshF0 || !R.meshKdAlpha; }
+};
+struct SurfNrm {  // rt_render_normal_mapped: the material-map frame's value and rows, and a bent normal
+  using Rec = NrmRec;
+  using Parked = ParkMat;
+  static constexpr int LT = LT_NMAP;
+  static constexpr bool BENDS = true;
+  static RT_DEV rt_material form(const DevScene& S, const Rec& R, uint4 tv, float u, float v) { return tex_mat(S, R.mat, tv, u, v); }
+  static RT_DEV f3 bend(const Rec& R, uint4 tv, float u, float v, f3 e1, f3 e2, f3 N) { return nmap_bend(R, tv, u, v, e1, e2, N); }
+  static bool refused(const Rec& R) { return SurfMat::refused(R.mat) || !R.meshNormal; }
 };
 template <int LTV>
 using surface_t = std::conditional_t<(LTV & LT_VCOL) != 0, SurfVCol,
                   std::conditional_t<(LTV & LT_TEX) != 0, SurfTex,
-                  std::conditional_t<(LTV & LT_MAT) != 0, SurfMat, SurfNone>>>;
+                  std::conditional_t<(LTV & LT_MAT) != 0, SurfMat,
+                  std::conditional_t<(LTV & LT_NMAP) != 0, SurfNrm, SurfNone>>>>;
 
 // Renderer.cpp:63-104: photon-map radiance estimate at the vertex (HP: the heap's layout, WideHeap for k > 16)
 template <bool STATS, class HP = Heap>
@@ -1660,6 +1724,7 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
   constexpr bool VCOL = (LTV & LT_VCOL) != 0;
   constexpr bool TEX = (LTV & LT_TEX) != 0;
   constexpr bool MAT = (LTV & LT_MAT) != 0;
+  constexpr bool NMAP = (LTV & LT_NMAP) != 0;
   // (the surface side and the camera side are orthogonal — below, the surface is SF alone and meets the generator
   // nowhere: a record of colours or textures goes with the plain generator or with the multi-view shutter's, the general
   // camera form, whose tables come from RenderArgs)
@@ -1668,6 +1733,7 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
   static_assert(!VCOL || (VIEWS == SHUTTER && !LENS && !LIGHTS && !PICK && !PHOTON), "vertex colours go with the plain frame or the multi-view shutter frame");
   static_assert(!TEX || (VIEWS == SHUTTER && !LENS && !LIGHTS && !PICK && !VCOL && !PHOTON), "textures go with the plain frame or the multi-view shutter frame");
   static_assert(!MAT || (!VIEWS && !LENS && !SHUTTER && !LIGHTS && !PICK && !VCOL && !TEX && !PHOTON), "material maps go with the plain frame only");
+  static_assert(!NMAP || (!VIEWS && !LENS && !SHUTTER && !LIGHTS && !PICK && !VCOL && !TEX && !MAT && !PHOTON), "normal maps go with the plain frame only");
   static_assert(!LIGHTS || (!VIEWS && !LENS && !SHUTTER && !PHOTON), "light groups go with the plain frame only");
   static_assert(!PICK || (!VIEWS && !LENS && !SHUTTER && !LIGHTS && !PHOTON), "light picks go with the plain frame only");
   static_assert(!LENS || !VIEWS, "no multi-view lens frames");
@@ -1762,8 +1828,13 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
           if (alive) {
             uint4 tv;
             float u, v;
-            vertex_setup_ray<FR>(S, h.id, o, d, nrm, pt, tv, u, v);
+            [[maybe_unused]] f3 e1, e2;  // (a surface that bends the normal: the triangle's edges, from the same loads)
+            if constexpr (SF::BENDS) vertex_setup_ray<FR>(S, h.id, o, d, nrm, pt, tv, u, v, e1, e2);
+            else vertex_setup_ray<FR>(S, h.id, o, d, nrm, pt, tv, u, v);
             mesh = tv.w, sf.v = SF::form(S, *rec, tv, u, v);
+            // (the bent normal replaces the interpolated one here, before the pool's light terms, its BSDF half and its
+            // hemisphere sample see nrm; only nrm survives the set-up)
+            if constexpr (SF::BENDS) nrm = SF::bend(*rec, tv, u, v, e1, e2, nrm);
           }
         } else
         if (alive) vertex_setup_ray<FR>(S, h.id, o, d, nrm, pt, mesh);
@@ -1818,6 +1889,14 @@ RT_DEV void render_tile(const DevScene& S, const RenderArgs& A, float4* __restri
       if (wave_ballot(alive) == 0) break;
       f3 nrm = mk(0.f, 0.f, 0.f), pt = nrm, c = nrm;
       if (alive) vertex_setup<FR>(S, h, nrm, pt);
+      if constexpr (SF::BENDS) {
+        // (before shade_direct_seq and the hemisphere sample below read nrm; the positions are vertex_setup's loads)
+        if (alive) {
+          const uint4 tv = S.triShade[h.id];
+          const f3 p0 = ld(S.vpos + 3 * (size_t)tv.x), p1 = ld(S.vpos + 3 * (size_t)tv.y), p2 = ld(S.vpos + 3 * (size_t)tv.z);
+          nrm = SF::bend(*rec, tv, h.u, h.v, p1 - p0, p2 - p0, nrm);
+        }
+      }
       if (PHOTON) {
         if (alive) c = shade_photon<STATS, HP>(S, A, d, h, L, nrm, pt, st);
       } else if constexpr (LIGHTS) {

@@ -6,7 +6,7 @@
 // than 0/1 silently becomes 0), plus build-defined extensions the reference has
 // no equivalent for: -scene, -meshdir, -seed, -gpu, -gpus, -devices, -accel,
 // -progress, -tune, -denoise, -aov, -adaptive, -pass, -ao, -aodist, -aperture, -focus, -shutter, -lights, -lightpick, -vcolors, -textures,
-// -matmaps.
+// -matmaps, -normalmaps.
 #pragma once
 
 #include <cstdlib>
@@ -20,7 +20,7 @@ class CommandLine {
  public:
   CommandLine()
       : m_width(380), m_height(270), m_numRays(16), m_mode(0), m_numPhotons(0), m_k(5), m_seed(1), m_gpu(0),
-        m_accel(0), m_progress(0), m_gpus(1), m_denoise(0), m_aov(0), m_pass(16), m_ao(0), m_vcolors(0), m_textures(0), m_matmaps(0), m_lightPick(0), m_tune(0.), m_adaptive(-1.), m_aoDist(0.), m_aperture(0.), m_focus(0.), m_outputFilename("output.ppm"), m_scene("cubes"), m_meshDir("../meshes") {}
+        m_accel(0), m_progress(0), m_gpus(1), m_denoise(0), m_aov(0), m_pass(16), m_ao(0), m_vcolors(0), m_textures(0), m_matmaps(0), m_normalmaps(0), m_lightPick(0), m_tune(0.), m_adaptive(-1.), m_aoDist(0.), m_aperture(0.), m_focus(0.), m_outputFilename("output.ppm"), m_scene("cubes"), m_meshDir("../meshes") {}
   virtual ~CommandLine() {}
 
   size_t width() const { return m_width; }
@@ -50,6 +50,7 @@ class CommandLine {
   size_t vcolors() const { return m_vcolors; }
   size_t textures() const { return m_textures; }
   size_t matmaps() const { return m_matmaps; }
+  size_t normalmaps() const { return m_normalmaps; }
   size_t gpus() const { return m_gpus; }
   const std::string& devices() const { return m_devices; }
   const std::string& scene() const { return m_scene; }
@@ -81,6 +82,7 @@ class CommandLine {
                  "[-vcolors <1: shade with the per-vertex colours of COFF meshes (meshes without colours keep their material's albedo)>]"
                  "[-textures <1: shade every mesh that has texture coordinates (STOFF) and a <mesh stem>.ppm beside its .off with that image as albedo, bilinear and repeating>]"
                  "[-matmaps <1: with -textures 1, also take f0 from <mesh stem>_f0.ppm (rgb) and kd and alpha from <mesh stem>_kda.ppm (r, g) where they lie beside the .off>]"
+                 "[-normalmaps <1: with -textures 1, also turn the shading normal by the tangent-space normal map <mesh stem>_n.ppm (rgb = (n + 1) / 2) where it lies beside the .off>]"
               << std::endl;
   }
 
@@ -125,6 +127,7 @@ class CommandLine {
       else if (flag == "-vcolors") m_vcolors = std::atoi(value);
       else if (flag == "-textures") m_textures = std::atoi(value);
       else if (flag == "-matmaps") m_matmaps = std::atoi(value);
+      else if (flag == "-normalmaps") m_normalmaps = std::atoi(value);
       else throw std::runtime_error("Unknown argument <" + flag + ">");
     }
     if (m_mode != 0 && m_mode != 1) m_mode = 0;
@@ -139,7 +142,7 @@ class CommandLine {
   }
 
  private:
-  size_t m_width, m_height, m_numRays, m_mode, m_numPhotons, m_k, m_seed, m_gpu, m_accel, m_progress, m_gpus, m_denoise, m_aov, m_pass, m_ao, m_vcolors, m_textures, m_matmaps;
+  size_t m_width, m_height, m_numRays, m_mode, m_numPhotons, m_k, m_seed, m_gpu, m_accel, m_progress, m_gpus, m_denoise, m_aov, m_pass, m_ao, m_vcolors, m_textures, m_matmaps, m_normalmaps;
   int m_lightPick;
   double m_tune, m_adaptive, m_aoDist, m_aperture, m_focus;
   std::string m_outputFilename, m_scene, m_meshDir, m_devices, m_shutter, m_lights;

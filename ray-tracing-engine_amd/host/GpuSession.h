@@ -92,6 +92,7 @@ struct GpuSettings {
   bool vcolors = false;               // shade with the meshes' per-vertex colours where any mesh has them (rt_render_colors; single device, plain frames only)
   bool textures = false;              // shade the meshes that have texture coordinates and a <stem>.ppm beside their .off with that image (rt_render_textured; single device, plain frames only)
   bool matmaps = false;               // with textures: also f0 from <stem>_f0.ppm and (kd, alpha) from <stem>_kda.ppm where they lie beside the .off (rt_render_material)
+  bool normalmaps = false;            // with textures: also the shading normal turned by <stem>_n.ppm where it lies beside the .off (rt_render_normal_mapped; with or without matmaps)
   unsigned lightPick = 0;             // > 0: the frame with this many sampled lights per path vertex (rt_render_pick; single device, plain frames only)
   std::vector<int> devices;  // more than one entry: Renderer::render tile-shards the frame over them (rt_group)
   static GpuSettings& get() {

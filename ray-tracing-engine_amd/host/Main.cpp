@@ -165,6 +165,20 @@ int main(int argc, char** argv) {
     }
     GpuSettings::get().matmaps = true;
   }
+  if (args.normalmaps() != 0) {
+    // -normalmaps 1: the textured frame, with or without -matmaps 1, with the shading normals turned by the normal maps
+    // beside the scene's STOFF meshes; it needs -textures 1 and composes with what that composes with
+    if (args.textures() == 0) {
+      std::cerr << "error: -normalmaps needs -textures 1" << std::endl;
+      return 1;
+    }
+    if (GpuSettings::get().devices.size() > 1 || args.numPhotons() > 0 || args.adaptive() >= 0. || !args.shutter().empty() ||
+        args.aperture() > 0. || !args.lights().empty() || args.lightPick() != 0 || args.vcolors() != 0) {
+      std::cerr << "error: -normalmaps runs on one GPU, without -p, -adaptive, -shutter, -aperture, -lights, -lightpick and -vcolors" << std::endl;
+      return 1;
+    }
+    GpuSettings::get().normalmaps = true;
+  }
   if (args.textures() != 0) {
     // -textures 1: the frame with the images beside the scene's STOFF meshes as albedo, and nothing else
     if (GpuSettings::get().devices.size() > 1 || args.numPhotons() > 0 || args.adaptive() >= 0. || !args.shutter().empty() ||

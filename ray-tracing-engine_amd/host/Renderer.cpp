@@ -22,7 +22,8 @@ inline bool sceneHasVertexColors(const Scene& scene) {
 
 // The image -textures gives a mesh: <stem>.ppm beside the .off it was loaded from, if the mesh has texture coordinates
 // and that file can be opened ("" otherwise).
-// suffix: "" for the albedo image; "_f0" and "_kda" name the images -matmaps binds (<stem>_f0.ppm, <stem>_kda.ppm).
+// suffix: "" for the albedo image; "_f0" and "_kda" name the images -matmaps binds (<stem>_f0.ppm, <stem>_kda.ppm), "_n"
+// the one -normalmaps binds (<stem>_n.ppm).
 inline std::string meshTextureFile(const Mesh& m, const std::string& suffix = "") {
   if (m.vertexUVs().empty() || m.vertexUVs().size() != 2 * m.vertexPositions().size()) return "";
   const std::string& off = m.sourceFile();
@@ -229,12 +230,16 @@ inline void Renderer::render(Image& image) {
     if (multi || p.use_photons) throw std::runtime_error("-textures runs on one GPU, without -p");
     std::vector<TextureImage> images;
     std::vector<rt_texture> textures;
-    std::vector<uint32_t> meshTexture, meshF0, meshKdAlpha;
+    std::vector<uint32_t> meshTexture, meshF0, meshKdAlpha, meshNormal;
     std::vector<float> uv;
     // -matmaps 1 (extension): <stem>_f0.ppm and <stem>_kda.ppm beside the .off join the set, bilinear and repeating as
     // the albedo image, and the frame goes through rt_render_material; a mesh without one keeps that field of its material
     const bool matmaps = GpuSettings::get().matmaps;
     uint32_t nMaps = 0;
+    // -normalmaps 1 (extension): <stem>_n.ppm beside the .off joins the set likewise, and the frame goes through
+    // rt_render_normal_mapped, with the material maps where -matmaps 1 is given too; a mesh without one keeps its normals
+    const bool normalmaps = GpuSettings::get().normalmaps;
+    uint32_t nNormals = 0;
     for (const Mesh& m : m_scene.meshes()) {
       const std::string file = meshTextureFile(m);
       meshTexture.push_back(file.empty() ? RT_TEX_NONE : static_cast<uint32_t>(images.size()));
@@ -244,6 +249,9 @@ inline void Renderer::render(Image& image) {
       if (!f0.empty()) images.push_back(TextureImage::loadPPM(f0)), ++nMaps;
       meshKdAlpha.push_back(kda.empty() ? RT_TEX_NONE : static_cast<uint32_t>(images.size()));
       if (!kda.empty()) images.push_back(TextureImage::loadPPM(kda)), ++nMaps;
+      const std::string nrm = normalmaps ? meshTextureFile(m, "_n") : "";
+      meshNormal.push_back(nrm.empty() ? RT_TEX_NONE : static_cast<uint32_t>(images.size()));
+      if (!nrm.empty()) images.push_back(TextureImage::loadPPM(nrm)), ++nNormals;
       // (the coordinates of a mesh without a texture are never read)
       if (m.vertexUVs().size() == 2 * m.vertexPositions().size()) uv.insert(uv.end(), m.vertexUVs().begin(), m.vertexUVs().end());
       else uv.insert(uv.end(), 2 * m.vertexPositions().size(), 0.f);
@@ -263,6 +271,13 @@ inline void Renderer::render(Image& image) {
       rt_material_maps maps = {};
       maps.n_meshes = set.n_meshes, maps.mesh_f0 = meshF0.data(), maps.mesh_kd_alpha = meshKdAlpha.data();
       GpuSession::check(rt_set_material_maps(ctx0, &maps), "rt_set_material_maps");
+    }
+    if (normalmaps) {
+      rt_normal_maps maps = {};
+      maps.n_meshes = set.n_meshes, maps.mesh_normal = meshNormal.data();
+      GpuSession::check(rt_set_normal_maps(ctx0, &maps), "rt_set_normal_maps");
+      GpuSession::check(rt_render_normal_mapped(ctx0, &p, image.data(), result.data(), nullptr, &st), "rt_render_normal_mapped");
+    } else if (matmaps) {
       GpuSession::check(rt_render_material(ctx0, &p, image.data(), result.data(), nullptr, &st), "rt_render_material");
     } else
     GpuSession::check(rt_render_textured(ctx0, &p, image.data(), result.data(), nullptr, &st), "rt_render_textured");
@@ -270,7 +285,8 @@ inline void Renderer::render(Image& image) {
     m_stats = st;
     result.savePPM("update.ppm");
     if (matmaps) std::cout << "Material maps: " << nMaps << " images" << std::endl;
-    std::cout << "Raytracing with the textures of " << images.size() - nMaps << " of " << m_scene.meshes().size() << " meshes... ["
+    if (normalmaps) std::cout << "Normal maps: " << nNormals << " images" << std::endl;
+    std::cout << "Raytracing with the textures of " << images.size() - nMaps - nNormals << " of " << m_scene.meshes().size() << " meshes... ["
               << std::string(50, '#') << "] 100%" << std::endl;
     image = result;
   } else if (p.spp > 0) {

@@ -214,6 +214,24 @@ def material_maps(n_meshes, mesh_f0=None, mesh_kd_alpha=None):
     return m, keep
 
 
+class NormalMaps(C.Structure):
+    """rt_normal_maps."""
+    _fields_ = [("n_meshes", C.c_uint32), ("mesh_normal", C.c_void_p), ("reserved", C.c_uint32 * 6)]
+
+
+def normal_maps(n_meshes, mesh_normal=None):
+    """The rt_normal_maps of Context.set_normal_maps' arguments, and the array it points into (keep it alive while the
+    structure is in use).  A table that is None is NULL: RT_TEX_NONE on every mesh."""
+    m = NormalMaps()
+    keep = []
+    m.n_meshes = n_meshes
+    if mesh_normal is not None:
+        a = np.ascontiguousarray(mesh_normal, np.uint32).reshape(-1)
+        keep.append(a)
+        m.mesh_normal = a.ctypes.data
+    return m, keep
+
+
 def texture_set(textures, mesh_texture, vertex_uv):
     """The rt_texture_set of Context.set_textures' arguments, and the arrays it points into (keep them alive while the
     structure is in use)."""
@@ -497,7 +515,8 @@ AMD_SYMBOLS = ["rt_abi_version", "rt_last_error", "rt_create", "rt_destroy", "rt
                "rt_set_textures", "rt_render_textured", "rt_render_textured_device", "rt_render_aov_textured",
                "rt_render_aov_textured_device", "rt_render_views_shutter_albedo", "rt_render_views_shutter_albedo_device",
                "rt_render_aov_views_albedo", "rt_render_aov_views_albedo_device", "rt_set_material_maps",
-               "rt_render_material", "rt_render_material_device"]
+               "rt_render_material", "rt_render_material_device", "rt_set_normal_maps", "rt_render_normal_mapped",
+               "rt_render_normal_mapped_device"]
 HOST_SYMBOLS = ["rt_host_scene_build", "rt_host_scene_desc", "rt_host_scene_free", "rt_host_last_error",
                 "rt_host_fill_background", "rt_host_save_ppm", "rt_host_kd_order", "rt_host_light_basis"]
 
@@ -685,6 +704,9 @@ def amd():
         L.rt_set_material_maps.argtypes = [C.c_void_p, C.POINTER(MaterialMaps)]
         L.rt_render_material.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         L.rt_render_material_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        L.rt_set_normal_maps.argtypes = [C.c_void_p, C.POINTER(NormalMaps)]
+        L.rt_render_normal_mapped.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        L.rt_render_normal_mapped_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         L.rt_render_aov_views_albedo.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Views), C.c_uint32, C.POINTER(Aov)]
         L.rt_render_aov_views_albedo_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Views), C.c_uint32,
                                                         C.POINTER(Aov), C.c_void_p]
@@ -1224,6 +1246,38 @@ class Context:
         st = Stats() if stats else None
         _check(amd().rt_render_material_device(self._h, C.byref(params), C.c_void_p(d_accum), C.c_void_p(stream or None),
                                                C.byref(st) if stats else None))
+        return st
+
+    def set_normal_maps(self, mesh_normal=None, release=False, n_meshes=None):
+        """rt_set_normal_maps: per mesh, the texture of the RESIDENT set (an index, or TEX_NONE) whose rgb gives the
+        tangent-space normal (2 c - 1) that turns the shading normal; None: TEX_NONE on every mesh.  release=True releases
+        the maps.  n_meshes: the count the call states (the length of a given table, else the context's)."""
+        if release:
+            _check(amd().rt_set_normal_maps(self._h, None))
+            return
+        if n_meshes is None:
+            n_meshes = len(mesh_normal) if mesh_normal is not None else self.scene.desc.n_meshes
+        m, keep = normal_maps(n_meshes, mesh_normal)
+        _check(amd().rt_set_normal_maps(self._h, C.byref(m)))
+
+    def render_normal_mapped(self, params, bg=None, want_accum=True):
+        """rt_render_normal_mapped: the material-map frame (with or without resident material maps) with every shaded
+        vertex's normal turned by the resident normal maps; returns (out [h][w][3] or None without bg, accum [h][w][4] or
+        None, stats)."""
+        w, h = params.width, params.height
+        out = np.empty((h, w, 3), np.float32) if bg is not None else None
+        acc = np.empty((h, w, 4), np.float32) if want_accum else None
+        st = Stats()
+        bgc = None if bg is None else np.ascontiguousarray(bg, np.float32)
+        _check(amd().rt_render_normal_mapped(self._h, C.byref(params), _ptr(bgc), _ptr(out), _ptr(acc), C.byref(st)))
+        return out, acc, st
+
+    def render_normal_mapped_device(self, params, d_accum, stream=0, stats=False):
+        """rt_render_normal_mapped_device: accumulate into the caller-zeroed device d_accum [h][w][4] on `stream`; sample
+        ranges chain."""
+        st = Stats() if stats else None
+        _check(amd().rt_render_normal_mapped_device(self._h, C.byref(params), C.c_void_p(d_accum), C.c_void_p(stream or None),
+                                                    C.byref(st) if stats else None))
         return st
 
     def render_textured_device(self, params, d_accum, stream=0, stats=False):
