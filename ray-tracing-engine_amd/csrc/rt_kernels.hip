@@ -250,6 +250,9 @@ constexpr int LT_MAT = 65536;
 // normal, replaces it by the perturbed one (nmap_bend): the light terms, the BSDF and the bounce then use that.
 constexpr int LT_NMAP = 131072;
 constexpr int LT_SURFACES = LT_VCOL | LT_TEX | LT_MAT | LT_NMAP;  // (the bits surface_t reads)
+// The descent loop of Trav::round as the compiler writes it, in an instance that would otherwise take the hand-written
+// loop (Trav::DESCENT): the launcher's RT_DESCENT=0 twin of the timed LT_ALL | LT_FASTDET | LT_LEAF2 instance.
+constexpr int LT_CLOOP = 262144;
 constexpr uint32_t kPrioMaxNodes = 65536;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(3))) u32x4* lds_u4_ptr;
@@ -264,6 +267,16 @@ struct Trav {
   static constexpr bool Q8 = (LTX & LT_Q8) != 0;
   static constexpr bool LEAF2 = (LTX & LT_LEAF2) != 0;
   static constexpr bool KEYED = LEAF2;  // test_pair accepts by one compare of hit_key (see there)
+  // round()'s descent loop as one assembly block that only ever NARROWS exec (descent_asm): the timed whole-tree-in-LDS
+  // two-record-leaf instance, in the three walkers it was written for and read back in (closest-hit, mixed, any-hit of a
+  // shadow-only pool); LT_CLOOP keeps the compiler's loop.  So does the diagnostic build (RT_PHASE_TIMING): the block takes
+  // a node's offset for its LDS address, which holds only without static LDS in front of g_lds (the step in round()),
+  // and it does not count PH_N_STEPS.
+#ifdef RT_PHASE_TIMING
+  static constexpr bool DESCENT = false;
+#else
+  static constexpr bool DESCENT = LT == LT_ALL && LEAF2 && !DIVIDE && !Q8 && (LTX & LT_CLOOP) == 0 && (MODE != TRAV_ANY || POOL);
+#endif
   static_assert(!Q8 || LT == LT_NONE, "Q8 records are fetched from HBM / L2");
   // any-hit rays enter child 0 (the smaller box) first: the big-scene instances and the whole-tree-in-LDS ones (measured:
   // C5 -2.5 %, C5x8 -1.9 %, C2 -0.7 %, C1 -3 %; the partial-top instance of C4 loses 0.7 % to the extra scalar op and keeps
@@ -334,6 +347,130 @@ struct Trav {
   }
   RT_DEV bool live() const { return cur != TERM; }
 
+  // The descent loop of round() for the DESCENT instances, exit rule and step as in the loop there (its comments apply):
+  // the same vector and LDS instructions per step, taken from the compiler's own body, under five control instructions
+  // instead of eight.  The lanes of successive steps are nested — a lane that stops descending never resumes inside the
+  // loop — so exec is only narrowed (s_mov exec, vcc: a compare under exec writes 0 for the lanes that are off, which is
+  // what they are) and restored once, after the loop; the compiler re-enters and leaves the step's region every step
+  // (s_or exec / s_and_saveexec / a never-taken execz branch / a branch back to the latch).
+  // Every adjacent pair of the control sequence occurs in the compiler's output for these kernels (a compare into vcc and
+  // s_bcnt1 of vcc; a scalar write of exec and a DS or vector instruction), no vector instruction reads a mask that a vector
+  // instruction wrote (they pass through a scalar operation, as in the compiler's step), and the scalar unit writes
+  // registers only.  The waits count LDS operations, which return in order: the block opens with lgkmcnt(0) because
+  // scalar loads share the counter and do not.  It leaves with the last step's stack write in flight, as the compiler's
+  // loop does.  The two 16-byte halves of the node need register tuples whose elements the text can name: v[16:19] and
+  // v[2:5], with the scalar temporaries beside them (the registers the compiler's mixed walker uses for them).
+#define RT_DESCENT_HEAD                                                         \
+  "s_waitcnt lgkmcnt(0)\n\t"                                                    \
+  "v_cmp_lt_i32_e32 vcc, -1, %[cur]\n\t"                                        \
+  "s_and_saveexec_b64 %[save], vcc\n\t"                                         \
+  "s_cbranch_execz 2f\n"                                                        \
+  "1:\n\t"                                                                      \
+  "ds_read_b128 v[16:19], %[cur]\n\t"                                           \
+  "ds_read_b128 v[2:5], %[cur] offset:16\n\t"                                   \
+  "ds_read_b32 v6, %[top]\n\t"                                                  \
+  "s_waitcnt lgkmcnt(2)\n\t"                                                    \
+  "v_alignbit_b32 v7, v16, v16, %[rx]\n\t"                                      \
+  "v_alignbit_b32 v16, v17, v17, %[ry]\n\t"                                     \
+  "v_alignbit_b32 v17, v18, v18, %[rz]\n\t"                                     \
+  "v_fma_mix_f32 v21, v17, %[iz], -%[oz] op_sel_hi:[1,0,0]\n\t"                 \
+  "v_alignbit_b32 v18, v19, v19, %[rx]\n\t"                                     \
+  "s_waitcnt lgkmcnt(1)\n\t"                                                    \
+  "v_alignbit_b32 v3, v3, v3, %[rz]\n\t"                                        \
+  "v_fma_mix_f32 v19, v7, %[ix], -%[ox] op_sel_hi:[1,0,0]\n\t"                  \
+  "v_fma_mix_f32 v7, v7, %[ix], -%[ox] op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"    \
+  "v_fma_mix_f32 v20, v16, %[iy], -%[oy] op_sel_hi:[1,0,0]\n\t"                 \
+  "v_fma_mix_f32 v16, v16, %[iy], -%[oy] op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"  \
+  "v_max_f32_e32 v21, 0, v21\n\t"                                               \
+  "v_alignbit_b32 v2, v2, v2, %[ry]\n\t"                                        \
+  "v_fma_mix_f32 v17, v17, %[iz], -%[oz] op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"  \
+  "v_max3_f32 v19, v19, v20, v21\n\t"                                           \
+  "v_min_f32_e32 v7, v7, v16\n\t"                                               \
+  "v_fma_mix_f32 v20, v3, %[iz], -%[oz] op_sel_hi:[1,0,0]\n\t"                  \
+  "v_min3_f32 v7, v7, v17, %[best]\n\t"                                         \
+  "v_fma_mix_f32 v16, v18, %[ix], -%[ox] op_sel_hi:[1,0,0]\n\t"                 \
+  "v_fma_mix_f32 v17, v18, %[ix], -%[ox] op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"  \
+  "v_fma_mix_f32 v18, v2, %[iy], -%[oy] op_sel_hi:[1,0,0]\n\t"                  \
+  "v_max_f32_e32 v20, 0, v20\n\t"                                               \
+  "v_fma_mix_f32 v2, v2, %[iy], -%[oy] op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"    \
+  "v_max3_f32 v16, v16, v18, v20\n\t"                                           \
+  "v_fma_mix_f32 v3, v3, %[iz], -%[oz] op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"    \
+  "v_min_f32_e32 v2, v17, v2\n\t"
+  // (v19 / v7: child 0's entry and exit distance, v16 / v2: child 1's.  vcc = m0, %[m1] = m1, %[ty] = takeY)
+#define RT_DESCENT_TAIL                                                         \
+  "v_cndmask_b32_e64 v20, v5, v4, %[ty]\n\t"                                    \
+  "ds_write_b32 %[top], v20 offset:%[row]\n\t"                                  \
+  "v_cndmask_b32_e64 v20, v4, v5, %[ty]\n\t"                                    \
+  "s_or_b64 %[ty], %[m1], vcc\n\t"                                              \
+  "s_waitcnt lgkmcnt(1)\n\t"                                                    \
+  "v_cndmask_b32_e64 %[cur], v6, v20, %[ty]\n\t"                                \
+  "v_cndmask_b32_e64 v20, %[pop], 0, %[ty]\n\t"                                 \
+  "s_and_b64 %[m1], %[m1], vcc\n\t"                                             \
+  "v_cndmask_b32_e64 v20, v20, %[blk], %[m1]\n\t"                               \
+  "v_lshl_add_u32 %[top], v20, 2, %[top]\n\t"                                   \
+  "v_cmp_lt_i32_e32 vcc, -1, %[cur]\n\t"                                        \
+  "s_bcnt1_i32_b64 %[n], vcc\n\t"                                               \
+  "s_cmp_le_u32 %[exitBelow], %[n]\n\t"                                         \
+  "s_mov_b64 exec, vcc\n\t"                                                     \
+  "s_cbranch_scc1 1b\n"                                                         \
+  "2:\n\t"                                                                      \
+  "s_or_b64 exec, exec, %[save]"
+#define RT_DESCENT_OUT [cur] "+v"(cur), [top] "+v"(t), [save] "=&s"(save), [ty] "=&s"(ty), [m1] "=&s"(m1), [n] "=&s"(n)
+#define RT_DESCENT_IN                                                                                                  \
+  [ix] "v"(inv.x), [iy] "v"(inv.y), [iz] "v"(inv.z), [ox] "v"(oi.x), [oy] "v"(oi.y), [oz] "v"(oi.z), [rx] "v"(rotX),   \
+      [ry] "v"(rotY), [rz] "v"(rotZ), [best] "v"(best), [pop] "v"(-BLOCK), [exitBelow] "s"(exitBelow), [blk] "i"(BLOCK), \
+      [row] "i"(4 * BLOCK)
+#define RT_DESCENT_CLOBBER "v2", "v3", "v4", "v5", "v6", "v7", "v16", "v17", "v18", "v19", "v20", "v21", "vcc", "scc", "memory"
+  RT_DEV void descent_asm(int exitBelow, uint64_t anyFirst) {
+    typedef __attribute__((address_space(3))) uint32_t* lds_u32_ptr;
+    lds_u32_ptr t = (lds_u32_ptr)top;
+    uint64_t save, ty, m1;
+    uint32_t n;
+    if constexpr (MODE == TRAV_MIXED) {
+      // takeY = m1 & ~(m0 & (t0 <= t1 | anyFirst))
+      asm volatile(RT_DESCENT_HEAD
+                   "v_cmp_le_f32_e64 %[ty], v19, v16\n\t"
+                   "v_min3_f32 v2, v2, v3, %[best]\n\t"
+                   "v_cmp_le_f32_e32 vcc, v19, v7\n\t"
+                   "s_or_b64 %[ty], %[ty], %[anyFirst]\n\t"
+                   "v_cmp_le_f32_e64 %[m1], v16, v2\n\t"
+                   "s_and_b64 %[ty], %[ty], vcc\n\t"
+                   "s_andn2_b64 %[ty], %[m1], %[ty]\n\t" RT_DESCENT_TAIL
+                   : RT_DESCENT_OUT
+                   : RT_DESCENT_IN, [anyFirst] "s"(anyFirst)
+                   : RT_DESCENT_CLOBBER);
+    } else if constexpr (MODE == TRAV_ANY) {
+      // (ANYORD: every ray enters child 0 whenever it is hit) takeY = m1 & ~m0
+      static_assert(ANYORD, "the any-hit block is the ANYORD step");
+      asm volatile(RT_DESCENT_HEAD
+                   "v_min3_f32 v2, v2, v3, %[best]\n\t"
+                   "v_cmp_le_f32_e32 vcc, v19, v7\n\t"
+                   "v_cmp_le_f32_e64 %[m1], v16, v2\n\t"
+                   "s_andn2_b64 %[ty], %[m1], vcc\n\t" RT_DESCENT_TAIL
+                   : RT_DESCENT_OUT
+                   : RT_DESCENT_IN
+                   : RT_DESCENT_CLOBBER);
+    } else {
+      // takeY = m1 & ~(m0 & t0 <= t1)
+      asm volatile(RT_DESCENT_HEAD
+                   "v_cmp_le_f32_e64 %[ty], v19, v16\n\t"
+                   "v_min3_f32 v2, v2, v3, %[best]\n\t"
+                   "v_cmp_le_f32_e32 vcc, v19, v7\n\t"
+                   "v_cmp_le_f32_e64 %[m1], v16, v2\n\t"
+                   "s_and_b64 %[ty], %[ty], vcc\n\t"
+                   "s_andn2_b64 %[ty], %[m1], %[ty]\n\t" RT_DESCENT_TAIL
+                   : RT_DESCENT_OUT
+                   : RT_DESCENT_IN
+                   : RT_DESCENT_CLOBBER);
+    }
+    top = (uint32_t*)t;
+  }
+#undef RT_DESCENT_HEAD
+#undef RT_DESCENT_TAIL
+#undef RT_DESCENT_OUT
+#undef RT_DESCENT_IN
+#undef RT_DESCENT_CLOBBER
+
   template <bool STATS>
   RT_DEV void round(const DevScene& S, LaneStats& st) {
     const int live0 = __popcll(wave_ballot(cur != TERM));
@@ -356,7 +493,8 @@ struct Trav {
     // (Denser-subtree-first, larger-box-first and the RTSAH rule lose: profiles/r03_anyhit_order_ab.txt.)
     const uint64_t anyFirst = !ANYORD ? 0ull : MODE == TRAV_ANY ? ~0ull : MODE == TRAV_MIXED ? __builtin_amdgcn_ballot_w64(anyHit) : 0ull;
     if (PRIO) __builtin_amdgcn_s_setprio(2);
-    if (inner) for (;;) {
+    if constexpr (DESCENT && !STATS) descent_asm(exitBelow, anyFirst);
+    else if (inner) for (;;) {
      if (__builtin_amdgcn_inverse_ballot_w64(inner)) {
       {
       float t0, t1;
@@ -2638,10 +2776,15 @@ static hipError_t launch_render2(bool stats, const DevScene& S, const RenderArgs
       // general instances; it is read at every launch, so one process can compare the two.
       const char* const leaf2Env = getenv("RT_LEAF2");
       const bool leaf2 = (A.flags & 2u) && !(leaf2Env && atoi(leaf2Env) == 0) && !stats && !S.slowRecip && !A.tileView;
-#define RT_LAUNCH_LEAF2(LTV)                                             \
-  do {                                                                   \
-    if (leaf2) RT_LAUNCH_PERSIST1(false, (LTV) | LT_FASTDET | LT_LEAF2); \
-    else RT_LAUNCH_EITHER(LTV);                                          \
+      // ... and of the LT_ALL one a twin with the compiler's descent loop (LT_CLOOP; Trav::DESCENT): RT_DESCENT=0, read at
+      // every launch like RT_LEAF2.
+      const char* const descentEnv = getenv("RT_DESCENT");
+      const bool cloop = descentEnv && atoi(descentEnv) == 0;
+#define RT_LAUNCH_LEAF2(LTV)                                                                               \
+  do {                                                                                                     \
+    if (leaf2 && cloop && ((LTV) & 3) == LT_ALL) RT_LAUNCH_PERSIST1(false, LT_ALL | LT_FASTDET | LT_LEAF2 | LT_CLOOP); \
+    else if (leaf2) RT_LAUNCH_PERSIST1(false, (LTV) | LT_FASTDET | LT_LEAF2);                              \
+    else RT_LAUNCH_EITHER(LTV);                                                                            \
   } while (0)
       const int lt = P.topK == 0 ? LT_NONE : P.topK >= S.n_nodes ? LT_ALL : LT_TOP;
       if (P.compact == 3) {
