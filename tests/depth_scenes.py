@@ -3,7 +3,9 @@
 The frame kernels carve their per-wave LDS from RenderArgs::stackLevels = BVH max_depth + 1 rows, and every launcher
 clamps that number in its own way.  The presets the suite runs give 7 (cubes), 14 (lowres), 17 (hires) and 25 (stress)
 rows; the scenes here give 2, 3, 4 and 5 and still have occluded shadow rays and bounce rays that hit, which the flat
-one-to-three-triangle scenes of tiescenes.py do not.
+one-to-three-triangle scenes of tiescenes.py do not.  (The suite's other purpose-built scenes: tiescenes.py — exact ties
+between hits; soups.py — triangle soups for the tree builders; probe_card.py — 24 textured quads, each at one limit of the
+sampler, the material maps or the normal maps.)
 
 Shallow family: sub-scenes of the cubes preset — a subset of its five meshes, in mesh order, with their materials, all
 three lights and the camera (ao_ref.without_mesh0, generalised), each with the bvh_leaf_max to create the context with.

@@ -43,7 +43,8 @@ def vertex_sample(mset, which, mesh, tv, u, v, own):
 
 
 def frame(scene, params, mset, bg=None, brute=False):
-    """The material-map frame `params` describes: dict(accum [h][w][4], out [h][w][3] or None, closest, shadow).  mset: a
+    """The material-map frame `params` describes: dict(accum [h][w][4], out [h][w][3] or None, closest, shadow, nonfinite —
+    how many rgb words of the samples' sums were not finite before the clamp).  mset: a
     texture set of tex_ref's form with mesh_f0 and mesh_kd_alpha beside mesh_texture (either None)."""
     a = scene.arrays()
     w, h = params.width, params.height
@@ -99,6 +100,7 @@ def frame(scene, params, mset, bg=None, brute=False):
     for dd in (2, 1, 0):
         m = vd == dd
         total[vs[m]] = (color[m] + total[vs[m]]).astype(F32)
+    nonfinite = int((~np.isfinite(total)).sum())
     total = clamp01(total).reshape(w * h, ns, 3)
     found = np.zeros(nsmp, bool)
     found[vs[vd == 0]] = True
@@ -109,7 +111,7 @@ def frame(scene, params, mset, bg=None, brute=False):
         acc[:, 3] = np.where(found[:, i], acc[:, 3] + F32(1), acc[:, 3])
     acc = acc.reshape(h, w, 4)
     out = None if bg is None else lens_ref.resolve(acc, np.asarray(bg, F32), params.spp)
-    return dict(accum=acc, out=out, closest=int(closest.sum()), shadow=int(shadow.sum()))
+    return dict(accum=acc, out=out, closest=int(closest.sum()), shadow=int(shadow.sum()), nonfinite=nonfinite)
 
 
 # ---- map sets --------------------------------------------------------------------------------------------------------------

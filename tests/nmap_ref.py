@@ -39,7 +39,7 @@ def _cross(a, b):
 def bend(N, e1, e2, uv0, uv1, uv2, m, parts=False):
     """N' [n][3] of the unit normals N [n][3] for triangles of edges e1, e2 [n][3], vertex uvs uv0..2 [n][2] and the
     normal map's samples m [n][3] (a row of NaN in m stands for RT_TEX_NONE: it keeps N).  parts: also a dict of T, B and
-    the five keep conditions."""
+    the five keep conditions (none, flat, r0, tp0, v0, and kept: any of them), with r, Tr (after the flip), Tp, xyz and vv."""
     N, e1, e2, m = (np.asarray(x, F32) for x in (N, e1, e2, m))
     uv0, uv1, uv2 = (np.asarray(x, F32) for x in (uv0, uv1, uv2))
     with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
@@ -62,9 +62,33 @@ def bend(N, e1, e2, uv0, uv1, uv2, m, parts=False):
         kept = keep["none"] | keep["flat"] | keep["r0"] | keep["tp0"] | keep["v0"]
         out = np.where(kept[:, None], N, aov_ref._unit(V)).astype(F32)
     if parts:
-        keep.update(T=T, B=B, kept=kept)
+        keep.update(T=T, B=B, kept=kept, r=r, Tr=Tr, Tp=Tp, xyz=np.stack([x, y, z], axis=-1).astype(F32), vv=vv)
         return out, keep
     return out
+
+
+# What frame() counts over its shaded vertices, all depths together (bend_events).  The keep conditions are counted on the
+# vertices of meshes that have a normal map, each on its own: a vertex at which two of them hold counts under both, and
+# under kept_two.
+EVENTS = ("kept_flat", "kept_r0", "kept_tp0", "kept_v0", "kept_v0_inf", "kept_two", "r_neg", "r_subnormal", "tp_subnormal",
+          "z_neg_moved")
+TINY = np.finfo(F32).tiny
+
+
+def bend_events(parts, N, N2):
+    """name -> bool [n]: the events of EVENTS among the vertices bend(..., parts=True) was given (N, N2: the normals
+    before and after).  kept_v0_inf: V's squared length overflowed; r_subnormal, tp_subnormal: r, dot3(Tp, Tp) are
+    subnormal and not zero; z_neg_moved: the map's z is negative and N' is not N."""
+    has = ~parts["none"]
+    with np.errstate(invalid="ignore", over="ignore"):
+        tt = _dot(parts["Tp"], parts["Tp"])
+        r, vv = parts["r"], parts["vv"]
+        conds = [parts[k] & has for k in ("flat", "r0", "tp0", "v0")]
+        moved = (np.ascontiguousarray(N2).view(np.uint32) != np.ascontiguousarray(N).view(np.uint32)).any(axis=1)
+        return dict(kept_flat=conds[0], kept_r0=conds[1], kept_tp0=conds[2], kept_v0=conds[3],
+                    kept_v0_inf=conds[3] & np.isinf(vv), kept_two=np.sum(conds, axis=0) >= 2, r_neg=has & (r < 0),
+                    r_subnormal=has & (r != 0) & (np.abs(r) < TINY), tp_subnormal=has & (tt > 0) & (tt < TINY),
+                    z_neg_moved=has & (parts["xyz"][:, 2] < 0) & moved)
 
 
 # ---- the two restated pieces of the integrator -----------------------------------------------------------------------------
@@ -90,7 +114,8 @@ def light_sample(state, light):
 
 def frame(scene, params, mset, bg=None, brute=False):
     """The normal-mapped frame `params` describes: dict(accum [h][w][4], out [h][w][3] or None, closest, shadow, bent — the
-    shaded vertices whose normal the maps moved — and kept_r0 — those a degenerate uv triangle kept).  mset: a map set of
+    shaded vertices whose normal the maps moved —, kept_r0 — those a degenerate uv triangle kept — and events: EVENTS'
+    counts).  mset: a map set of
     mat_ref's form with mesh_normal beside its tables (None: RT_TEX_NONE on every mesh)."""
     a = scene.arrays()
     w, h = params.width, params.height
@@ -115,6 +140,7 @@ def frame(scene, params, mset, bg=None, brute=False):
     found = np.zeros(nsmp, bool)
     cols = np.zeros((3, nsmp, 3), F32)
     closest = shadow = bent = kept_r0 = 0
+    events = dict.fromkeys(EVENTS, 0)
     for depth in range(nvert):
         idx = np.nonzero(alive)[0]
         if not len(idx):
@@ -145,6 +171,8 @@ def frame(scene, params, mset, bg=None, brute=False):
         nrm2, parts = bend(nrm, (p1 - p0).astype(F32), (p2 - p0).astype(F32), uvs[tv[:, 0]], uvs[tv[:, 1]], uvs[tv[:, 2]], m, parts=True)
         bent += int((~parts["kept"]).sum())
         kept_r0 += int((parts["r0"] & ~parts["none"]).sum())
+        for name, mask in bend_events(parts, nrm, nrm2).items():
+            events[name] += int(mask.sum())
         nrm = nrm2
         kda_own = np.concatenate([mats[mesh, 0:2], np.zeros((nv, 1), F32)], axis=1)
         rows = np.zeros((nv, 17), F32)
@@ -182,7 +210,7 @@ def frame(scene, params, mset, bg=None, brute=False):
         acc[:, 3] = np.where(found[:, i], acc[:, 3] + F32(1), acc[:, 3])
     acc = acc.reshape(h, w, 4)
     out = None if bg is None else lens_ref.resolve(acc, np.asarray(bg, F32), params.spp)
-    return dict(accum=acc, out=out, closest=closest, shadow=shadow, bent=bent, kept_r0=kept_r0)
+    return dict(accum=acc, out=out, closest=closest, shadow=shadow, bent=bent, kept_r0=kept_r0, events=events)
 
 
 # ---- normal-map sets -------------------------------------------------------------------------------------------------------

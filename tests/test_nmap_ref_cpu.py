@@ -62,6 +62,7 @@ def test_every_reference_frame_is_finite(case):
 def test_the_sets_cover_what_they_claim():
     nx = len(tex_ref.MIXED_TEXTURES)
     used, degenerate, kept = set(), 0, 0
+    events = dict.fromkeys(nmap_ref.EVENTS, 0)
     for case in nmap_ref.CASES:
         t, base = nmap_ref.case_maps(case), mat_ref.case_maps(case)
         n0 = len(base["textures"])
@@ -78,9 +79,15 @@ def test_the_sets_cover_what_they_claim():
         degenerate += nmap_ref.degenerate_triangles(nmap_ref.case_scene(case), t)
         if case[6] != T_FACES:
             kept += nmap_ref.case_reference(case)["kept_r0"]
+            for name, n in nmap_ref.case_reference(case)["events"].items():
+                events[name] += n
     assert used == set(range(nx + 1))  # every shape, both filters, both wraps, and the flat map
     assert degenerate > 0
     assert kept > 0, "no case beside the strips shades a vertex of a triangle with degenerate uvs"
+    # ... and each keep condition on its own (nmap_ref.EVENTS).  These cases reach the degenerate uv triangle, the flat
+    # texel and mirrored uvs; a vanishing Tp, an overflowing V, z < 0 and subnormal terms are tests/probe_card.py's
+    print(events)
+    assert events["kept_r0"] == kept and events["kept_flat"] > 0 and events["r_neg"] > 0
 
 
 # ---- the perturbation alone ------------------------------------------------------------------------------------------------

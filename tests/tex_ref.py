@@ -37,25 +37,38 @@ def coord(s0, s1, s2, u, v):
     return ((s0 + (u * (s1 - s0)).astype(F32)).astype(F32) + (v * (s2 - s0)).astype(F32)).astype(F32)
 
 
-def sample(tex, s, t):
-    """The sample [n][3] of tex = (texels [h][w][3], wrap_s, wrap_t, filter) at the float32 coordinates s, t [n]."""
+def sample(tex, s, t, parts=False):
+    """The sample [n][3] of tex = (texels [h][w][3], wrap_s, wrap_t, filter) at the float32 coordinates s, t [n].  parts:
+    also a dict of what the sample went through, [n] each — sw, th: the float32 products s * W and t * H; xi, yj: the
+    integer coordinates before the wrap (NEAREST: the texel's; BILINEAR: int(xf), int(yf)); i0, i1, j0, j1: the wrapped
+    indices (NEAREST: i1 == i0, j1 == j0); fx, fy (NEAREST: 0) — and bilinear, a bool."""
     texels, wrap_s, wrap_t, filt = tex
     texels = np.asarray(texels, F32)
     h, w = texels.shape[:2]
     s, t = np.asarray(s, F32), np.asarray(t, F32)
+    sw, th = (s * F32(w)).astype(F32), (t * F32(h)).astype(F32)
     if filt == NEAREST:
-        i = wrap(np.floor((s * F32(w)).astype(F32)), w, wrap_s)
-        j = wrap(np.floor((t * F32(h)).astype(F32)), h, wrap_t)
+        xi, yj = np.floor(sw).astype(np.int64), np.floor(th).astype(np.int64)
+        i = wrap(xi, w, wrap_s)
+        j = wrap(yj, h, wrap_t)
+        if parts:
+            zero = np.zeros(s.shape, F32)
+            return texels[j, i], dict(sw=sw, th=th, xi=xi, yj=yj, i0=i, i1=i, j0=j, j1=j, fx=zero, fy=zero, bilinear=False)
         return texels[j, i]
-    x = ((s * F32(w)).astype(F32) - F32(0.5)).astype(F32)
-    y = ((t * F32(h)).astype(F32) - F32(0.5)).astype(F32)
+    x = (sw - F32(0.5)).astype(F32)
+    y = (th - F32(0.5)).astype(F32)
     xf, yf = np.floor(x).astype(F32), np.floor(y).astype(F32)
     fx, fy = (x - xf).astype(F32)[..., None], (y - yf).astype(F32)[..., None]
     i0, i1 = wrap(xf, w, wrap_s), wrap(xf.astype(np.int64) + 1, w, wrap_s)
     j0, j1 = wrap(yf, h, wrap_t), wrap(yf.astype(np.int64) + 1, h, wrap_t)
-    a = (texels[j0, i0] + (fx * (texels[j0, i1] - texels[j0, i0]).astype(F32)).astype(F32)).astype(F32)
-    b = (texels[j1, i0] + (fx * (texels[j1, i1] - texels[j1, i0]).astype(F32)).astype(F32)).astype(F32)
-    return (a + (fy * (b - a).astype(F32)).astype(F32)).astype(F32)
+    with np.errstate(over="ignore", invalid="ignore"):  # (texels near the float32 range: the sums may overflow, as they do on the device)
+        a = (texels[j0, i0] + (fx * (texels[j0, i1] - texels[j0, i0]).astype(F32)).astype(F32)).astype(F32)
+        b = (texels[j1, i0] + (fx * (texels[j1, i1] - texels[j1, i0]).astype(F32)).astype(F32)).astype(F32)
+        c = (a + (fy * (b - a).astype(F32)).astype(F32)).astype(F32)
+    if parts:
+        return c, dict(sw=sw, th=th, xi=xf.astype(np.int64), yj=yf.astype(np.int64), i0=i0, i1=i1, j0=j0, j1=j1, fx=fx[..., 0],
+                       fy=fy[..., 0], bilinear=True)
+    return c
 
 
 def vertex_albedo(a, tset, mesh, tv, u, v):
@@ -141,7 +154,8 @@ def frame(scene, params, tset, bg=None, brute=False, touched=True):
     for i in range(ns):  # float32 adds in sample order
         acc[:, :3] = (acc[:, :3] + total[:, i]).astype(F32)
         acc[:, 3] = np.where(found[:, i], acc[:, 3] + F32(1), acc[:, 3])
-        alb = np.where(found[:, i, None], (alb + first[:, i]).astype(F32), alb)
+        with np.errstate(over="ignore"):  # (texels near the float32 range sum to inf, here as on the device)
+            alb = np.where(found[:, i, None], (alb + first[:, i]).astype(F32), alb)
     acc = acc.reshape(h, w, 4)
     seen = None
     if touched:
@@ -225,6 +239,8 @@ def texture_set(s, kind, shift=0):
 # (scene key as lights_ref.scene's, w, h, sample range, mode, max_depth, texturing): vcol_ref.CASES' frames, ranges, modes
 # and scenes — cubes and lowres closed and open (three lights, the pooled body), sweep scenes of one, two and four lights
 # (scene 3: the sequential body) — under the four texturings.  T_FACES cases run on the vertex-split scene of their key.
+# (These scenes keep uvs within -2.5 .. 3.5 and textures within 64 x 32; the sampler at the header's bounds is run on the
+# probe card of tests/probe_card.py, by tests/test_gpu_surface_limits.py.)
 CASES = [
     (("cubes", False), 16, 16, SPP4, PATH, 3, T_MIXED),
     (("cubes", False), 13, 9, SPP7, RAY, 1, T_FACES),
